@@ -12,7 +12,20 @@ patch / crop / stitch on the device are inside it.  Each rank (= one GPU) interp
 frame pairs: no collective on the data path, weights are broadcast once over RCCL before timing
 ("scaling": "weak").
 
-Extra objects in the JSON line:
+A plain run does what the headline figure needs and nothing else: set-up (weights, plan, the first call that autotunes the
+shape), `--warmup` untimed steps, `--steps` timed steps, the outputs of the last timed step when `--dump-outputs DIR` is given,
+and the JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step).
+`--full` adds every other measurement and check: the parity of the timed callable against the committed golden vectors
+before and after the loop, the bit-identity of the last timed step with the first call, `output_crc32`, the per-depth
+times of a recursion, the profiled forward behind `roofline` / `roofline_warp` / `kernel_ms_per_step` (and
+`--profile-out`), the host-buffer path, the opt-in precision modes and the CPU baseline.
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy (float32): the mid
+frames (`interpolated`) or the frame sequence of a recursion (`frames`).  Inputs and weights are seeded, so two builds
+run with the same arguments can be compared output for output.  More than 64 MB of outputs in all are written as a
+fixed, seeded sample of their flattened elements (DUMP_SEED; the same positions in every run of the same shapes).
+
+Extra objects in the JSON line of a `--full` run:
   roofline     fp32-MFMA roofline of the dominant kernel class (the MFMA convolutions): FLOPs the matrix
                pipe EXECUTES in one forward (the Winograd F(4,3) / F(2,3) kernels and the sub-pixel fold
                execute 1/2, 2/3, 9/16 of the direct convolution's multiplies) / summed duration of its
@@ -86,6 +99,32 @@ PARITY_CASES = {
 }
 PARITY_TOL = 1e-3   # north_star: |delta| < 1e-3 per pixel, fp32
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000 - 64 * 1024   # --dump-outputs: at most 64 MB in all, .npy headers included
+DUMP_SEED = 0
+
+
+def dump_outputs(dump_dir, arrays):
+    """Writes every tensor of `arrays` (name -> tensor) as dump_dir/<name>.npy in float32.  When they hold more than
+    DUMP_LIMIT_BYTES in all, each is replaced by a sample of its flattened elements at sorted positions drawn with DUMP_SEED,
+    in proportion to its size.  Returns {name: {'shape': full shape, 'sampled_elements': sample size or None}}."""
+    os.makedirs(dump_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values())
+    budget = DUMP_LIMIT_BYTES // 4
+    report = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        k = None
+        if total > budget:
+            k = flat.numel() * budget // total
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), k))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arr = flat.float().cpu().numpy()
+        else:
+            arr = t.detach().float().cpu().numpy()
+        np.save(os.path.join(dump_dir, f'{name}.npy'), np.ascontiguousarray(arr, dtype=np.float32))
+        report[name] = {'shape': list(t.shape), 'sampled_elements': k}
+    return report
+
 
 def _tests_on_path():
     if os.path.join(ROOT, 'tests') not in sys.path:
@@ -135,7 +174,7 @@ def cli_files_workload(eng, args):
     temporary directory -> `--times_to_interpolate 3 --align 64 --block_height 2 --block_width 2` -> nine PNGs, files to files,
     decode / H2D / recursion / quantise / D2H / encode all inside the timed region.  Timed twice: the device pipeline the CLI uses
     (eval.util.interpolate_pairs_to_files) and the round-3 path (float32 frames back in one blocking copy, host to_uint8, PNGs one
-    after the other on one thread); the files of the two runs are compared byte for byte."""
+    after the other on one thread, `--full` only); the files of the two runs are compared byte for byte."""
     import filecmp
     import shutil
     import tempfile
@@ -158,30 +197,41 @@ def cli_files_workload(eng, args):
             n_new, _ = util.interpolate_pairs_to_files(inputs, 0, 1, 1, T, it, new_dir)
             if rep >= args.warmup:
                 ms_new.append((time.perf_counter() - t0) * 1e3)
-        for rep in range(1 + min(args.steps, 3)):
-            t0 = time.perf_counter()
-            frames = list(util.interpolate_recursively_from_files(inputs, T, it))
-            cli.output_frames(frames, old_dir)
-            if rep >= 1:
-                ms_old.append((time.perf_counter() - t0) * 1e3)
-        same = all(filecmp.cmp(os.path.join(new_dir, f), os.path.join(old_dir, f), shallow=False) for f in sorted(os.listdir(old_dir)))
+        dumped = None
+        if args.dump_outputs:      # the files of the last timed step, as the frames a caller reads back from them
+            files = sorted(os.listdir(new_dir))
+            dumped = dump_outputs(args.dump_outputs, {'frames': torch.from_numpy(np.stack([util.read_image(os.path.join(new_dir, f)) for f in files]))})
+        if args.full:
+            for rep in range(1 + min(args.steps, 3)):
+                t0 = time.perf_counter()
+                frames = list(util.interpolate_recursively_from_files(inputs, T, it))
+                cli.output_frames(frames, old_dir)
+                if rep >= 1:
+                    ms_old.append((time.perf_counter() - t0) * 1e3)
+            same = all(filecmp.cmp(os.path.join(new_dir, f), os.path.join(old_dir, f), shallow=False) for f in sorted(os.listdir(old_dir)))
         n_files = len(os.listdir(new_dir))
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     gen = 2 ** T - 1
     ms = float(np.median(ms_new))
-    return {
+    result = {
         'metric': 'interpolated frames/sec @1080p, files to files (interpolator_cli, times_to_interpolate 3)', 'value': round(gen / (ms * 1e-3), 4),
         'unit': 'frames/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3), 'higher_is_better': True,
         'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
         'config': {'workload': 'cli_1080p_T3: two 1920x1080 PNGs -> align 64, block_shape [2, 2], times_to_interpolate 3 -> 9 PNGs (7 generated); '
                                'PNG decode, H2D, 7 tiled forwards, device to_uint8, D2H, PNG encode all timed',
                    'files_written': n_files, 'frames_generated': gen, 'host_threads': os.cpu_count()},
-        'round3_path': {'ms_per_step': round(float(np.median(ms_old)), 3), 'frames_per_s': round(gen / (float(np.median(ms_old)) * 1e-3), 4),
-                        'what': 'float32 frames back in one blocking copy, host to_uint8, serial PIL PNG encode'},
-        'speedup_vs_round3_path': round(float(np.median(ms_old)) / ms, 3),
-        'files_byte_identical_to_round3_path': bool(same),
     }
+    if dumped is not None:
+        result['dump_outputs'] = dumped
+    if args.full:
+        result.update({
+            'round3_path': {'ms_per_step': round(float(np.median(ms_old)), 3), 'frames_per_s': round(gen / (float(np.median(ms_old)) * 1e-3), 4),
+                            'what': 'float32 frames back in one blocking copy, host to_uint8, serial PIL PNG encode'},
+            'speedup_vs_round3_path': round(float(np.median(ms_old)) / ms, 3),
+            'files_byte_identical_to_round3_path': bool(same),
+        })
+    return result
 
 
 def cpu_baseline(weights):
@@ -375,12 +425,19 @@ def main():
     ap.add_argument('--opt', action='append', default=[], metavar='KEY=VALUE', help='extra engine option (film_set_option), repeatable - A/B experiments')
     ap.add_argument('--wino2d', type=int, default=None, choices=[0, 1, 2], help='engine option "wino2d" (nested Winograd kernel); default: the engine default')
     ap.add_argument('--no-split', action='store_true', help='skip the extra bf16x6 / bf16x3 precision-mode measurements')
-    ap.add_argument('--profile-out', default='', help='write the per-op profile JSON here')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the timed steps: parity and bit-identity checks, output_crc32, per-depth times, the profiled forward '
+                         '(roofline, kernel_ms_per_step), the host-buffer path, the opt-in precision modes, the CPU baseline')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step returned as DIR/<name>.npy (float32; a seeded sample beyond 64 MB in all)')
+    ap.add_argument('--profile-out', default='', help='write the per-op profile JSON of the profiled forward here (needs --full)')
     ap.add_argument('--plan-only', action='store_true',
                     help='CPU rehearsal of the N-rank path: gloo + plan-only engine handles, no compute (tests)')
     ap.add_argument('--tiny-net', action='store_true', help='with --plan-only: the small test architecture')
     ap.add_argument('--pairs', type=int, default=8, help='with --plan-only: frame pairs sharded over the ranks')
     args = ap.parse_args()
+    if args.profile_out and not args.full:
+        ap.error('--profile-out writes the profiled forward of a --full run: add --full')
     if args.steps is None:
         args.steps = 2 if args.workload == '4k_4x4_T6' else 10
     if args.warmup is None:
@@ -488,13 +545,13 @@ def main():
         # tunes - rank 0 warms up on its own share of the tiles instead (TileShardedRecursion.local: no collective)
         autotune_once(eng, dist, rank, (lambda: drv.local(x0[0], x1[0], T)) if strong else step, torch.cuda.synchronize)
     parity, parity_ref = None, None
-    if args.workload in PARITY_CASES and T == 1 and not strong and args.flow_scale == 1.0:
+    if args.full and args.workload in PARITY_CASES and T == 1 and not strong and args.flow_scale == 1.0:
         parity_ref, parity = parity_check(args.workload, it, dev)
         if not parity[next(iter(parity))] < PARITY_TOL:
             sys.stderr.write(f'bench.py: rank {rank}: PARITY FAILED before the timed loop: {json.dumps(parity)}\n')
             raise SystemExit(3)
-    first = step()
-    first = None if first is None else first.clone()
+    first = step()     # set-up: the first call on these shapes builds the plan and autotunes it, never timed
+    first = None if (first is None or not args.full) else first.clone()
     for _ in range(args.warmup):
         out = step()
     torch.cuda.synchronize()
@@ -522,7 +579,12 @@ def main():
         ones = torch.ones(1, dtype=torch.float64, device=dev)
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         reported = int(ones.item())
-    assert (out is not None or (strong and rank != 0)) and (out is None or bool(torch.isfinite(out).all()))
+    assert out is not None or (strong and rank != 0)
+    dumped = None
+    if args.dump_outputs and rank == 0 and out is not None:
+        dumped = dump_outputs(args.dump_outputs, {'frames' if T > 1 else 'interpolated': out})
+    if args.full:
+        assert out is None or bool(torch.isfinite(out).all())
     # the timed output itself: the last timed step must reproduce the first call on the same inputs bit for bit (no atomics,
     # fixed summation orders: a side lane or a replayed graph that read stale data would show here), and the golden pair pushed through the
     # timed callable AFTER the loop must reproduce its pre-loop result bit for bit
@@ -541,176 +603,177 @@ def main():
 
     result = None
     if rank == 0:
-        ms_per_depth = None
-        if T > 1 and world == 1:
-            # one more recursion with a host synchronisation after every depth (depth d = 2^(d-1) pairs x the tiles)
-            frames = torch.stack([x0[0], x1[0]]).contiguous()
-            ms_per_depth = []
-            for _ in range(T):
-                torch.cuda.synchronize()
-                td = time.perf_counter()
-                mids = dev_it.batch(frames[:-1].contiguous(), frames[1:].contiguous())
-                torch.cuda.synchronize()
-                ms_per_depth.append(round((time.perf_counter() - td) * 1e3, 2))
-                nxt = torch.empty((2 * frames.shape[0] - 1,) + tuple(frames.shape[1:]), dtype=frames.dtype, device=dev)
-                nxt[0::2] = frames
-                nxt[1::2] = mids
-                frames = nxt
-            del frames, mids, nxt
-        # ---- roofline of the dominant kernel class: hipEvents around every launch, on the launch stream
-        # steady state: a normal forward is queued right in front of the profiled one, with no host
-        # synchronisation in between, so the first kernels are not timed on a GPU that is ramping up from idle
-        it(x0, x1)
-        eng.set_option('profile', 1)
-        it(x0, x1)
-        torch.cuda.synchronize()
-        prof = eng.profile()      # the LAST model invocation of that call (one chunk of tiles when the frame was chunked)
-        eng.set_option('profile', 0)
-        if args.profile_out:
-            with open(args.profile_out, 'w') as f:
-                json.dump(prof, f)
-        cls = prof['classes']
-        conv = cls['conv_mfma']
-        npix = prof['B'] * prof['H'] * prof['W']      # padded input pixels of the profiled invocation
-        alg_flops = CONV_FLOP_PER_PIXEL * npix
-        # conv_mfma launches carry all conv FLOPs except the Cin=3 first layer and the tiny 1x1 heads
-        conv_tflops = conv['flops'] / (conv['ms'] * 1e-3) / 1e12
-        total_ms = sum(c['ms'] for c in cls.values())
-        # FLOPs the matrix pipe really executes: the Winograd F(2,3) kernel (tile id & 256) does 2/3 of the direct
-        # convolution's multiplies, the sub-pixel-folded upsample + 2x2 conv (tag ':phases') 9/16
-        exec_flops = 0.0
-        per_kernel = {k: {'launches': 0, 'ms': 0.0, 'executed_flops': 0.0} for k in ('conv_wino2d_kernel', 'conv_wino43_kernel', 'conv_fold4_kernel')}
-        for o in prof['ops']:
-            if o['kind'] != 'conv_mfma':
-                continue
-            f = o['flops']
-            if o['tile'] & 8192:
-                f *= 1.0 / 3.0                                   # nested Winograd F(4,3)x x F(2,3)y: 3 multiplies per output of 9
-            elif o['tile'] & 256:
-                f *= 0.5 if o['tile'] & 2048 else 2.0 / 3.0    # Winograd F(4,3) / F(2,3) along x
-            elif o['tile'] & 16384:
-                f *= 4.0 / 16.0                                  # conv_fold4_kernel: upsample + 2x2 in its difference form, 4 multiplies of 16
-            elif o['tag'].endswith(':phases'):
-                f *= 9.0 / 16.0
-            exec_flops += f
-            kname = 'conv_wino2d_kernel' if (o['tile'] & 8192) else 'conv_fold4_kernel' if (o['tile'] & 16384) else 'conv_wino43_kernel' if ((o['tile'] & 256) and (o['tile'] & 2048)) else None
-            if kname:
-                per_kernel[kname]['launches'] += 1
-                per_kernel[kname]['ms'] += o['ms']
-                per_kernel[kname]['executed_flops'] += f
-        exec_tflops = exec_flops / (conv['ms'] * 1e-3) / 1e12
-        traffic, traffic_src, warp_traffic, traffic_why = None, None, None, None
-        try:  # fabric-side bytes per launch REPLAYED from the committed PMC passes (profiles/; PMC needs its own rocprofv3
-            # processes) - only from a file made with THIS build of the kernels (film_version() carries a hash of csrc/ + the header)
-            import glob
-            pmc_files = sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_pmc_conv.json')))
-            if pmc_files and args.workload == '1080p_2x2':
-                pmc = json.load(open(pmc_files[-1]))
-                traffic_src = os.path.relpath(pmc_files[-1], ROOT)
-                if pmc.get('build') != eng.version():
-                    traffic_why = (f'{traffic_src} was collected with build "{pmc.get("build")}", this run is "{eng.version()}": not replayed '
-                                   f'(tools/gpu_pmc.sh + tools/pmc_summary.py refresh it)')
-                else:
-                    traffic = round(pmc['hbm_bytes_per_launch'])
-                    wcls = next((v for k, v in pmc.get('classes', {}).items() if k.startswith('warp')), None)
-                    if wcls and wcls.get('hbm_bytes_per_launch'):
-                        warp_traffic = round(wcls['hbm_bytes_per_launch'])
-        except Exception as e:   # noqa: BLE001
-            traffic, traffic_why = None, repr(e)
-        # the roofline the conv class is priced against: the fp32 MFMA peak in the default mode; in the opt-in
-        # split modes the dense bf16 MFMA peak divided by the bf16 products one fp32 product costs
-        peak = {0: PEAK_FP32_MFMA_TFLOPS, 1: PEAK_BF16_MFMA_TFLOPS / 6, 2: PEAK_BF16_MFMA_TFLOPS / 3}[args.precision]
-        roofline = {
-            'bound': 'mfma',
-            'kernel': ('conv class = conv_wino2d_kernel (every 3x3 layer of the levels >= 1536 pixels: 91 % of the FLOPs) / conv_buf_kernel / conv_c3_kernel (fp32 v_mfma_f32_32x32x2_f32); '
-                       '`achieved` / `frac` count the FLOPs the matrix pipe executes (nested Winograd F(4,3)x x F(2,3)y layers x1/3, F(4,3) x1/2, F(2,3) x2/3, folded 2x2 layers x9/16 '
-                       'of the direct convolution)')
-                      if not args.precision else
-                      ('conv class in the opt-in split mode = conv_winox3_kernel / conv_halo_split_kernel '
-                       '(v_mfma_f32_32x32x16_bf16, fp32 accumulate) + the fp32 kernels on the small / 2x2 layers; '
-                       'peak = dense bf16 MFMA peak / bf16 products per fp32 product'),
-            'achieved': round(exec_tflops, 3), 'peak': round(peak, 1), 'unit': 'TFLOP/s',
-            'frac': round(exec_tflops / peak, 4),
-            'frac_note': 'utilisation of the peak by the multiplies the matrix pipe EXECUTES; the kernels that execute fewer of them per output '
-                         '(conv_wino2d_kernel: 1/3 of the direct count) lower it while the step gets faster - see direct_equivalent and kernels[]',
-            'traffic': traffic if not args.precision else None,
-            'traffic_note': (f'REPLAYED, not measured in this run: bytes per launch, (2*FETCH_SIZE + WRITE_SIZE) of the rocprofv3 PMC passes '
-                             f'committed in {traffic_src}, collected with the same build of the kernels ("{eng.version()}"; PMC needs its own '
-                             f'rocprofv3 processes)') if traffic else traffic_why,
-            # the two Winograd kernels on their own (executed FLOPs: nested F(4,3)x x F(2,3)y = 1/3, 1-D F(4,3) = 1/2 of the direct
-            # count); `dominant_kernel` = the one with the larger share of the step
-            'kernels': None if args.precision else [
-                {'name': k, 'launches': v['launches'], 'ms': round(v['ms'], 3),
-                 'executed_tflops': round(v['executed_flops'] / max(v['ms'], 1e-9) / 1e9, 3),
-                 'frac': round(v['executed_flops'] / max(v['ms'], 1e-9) / 1e9 / PEAK_FP32_MFMA_TFLOPS, 4),
-                 'direct_equivalent_tflops': round(v['executed_flops'] * (3.0 if k == 'conv_wino2d_kernel' else 4.0 if k == 'conv_fold4_kernel' else 2.0) / max(v['ms'], 1e-9) / 1e9, 3),
-                 'avg_launch_ms': round(v['ms'] / max(1, v['launches']), 5)}
-                for k, v in sorted(per_kernel.items(), key=lambda kv: -kv[1]['ms']) if v['launches']],
-            'launches_per_step': conv['launches'],
-            'avg_launch_ms': round(conv['ms'] / conv['launches'], 5),
-            'class_ms_per_step': round(conv['ms'], 3),
-            'executed_flops_per_step': exec_flops,
-            'algorithmic_flops_per_step': conv['flops'],
-            'all_conv_flops_per_step': alg_flops,
-            'share_of_kernel_time': round(conv['ms'] / total_ms, 4),
-            'direct_equivalent': {'achieved': round(conv_tflops, 3), 'ratio_to_peak': round(conv_tflops / peak, 4),
-                                  'note': 'same launches priced with the direct convolution\'s FLOPs (SURVEY 8d formula); exceeds the fp32 MFMA '
-                                          'peak because Winograd / the sub-pixel fold execute fewer multiplies - an algorithmic saving, not a utilisation'},
-        }
-        roofline['dominant_kernel'] = roofline['kernels'][0] if roofline.get('kernels') else None
-        if roofline['dominant_kernel'] is not None and not args.precision:
-            # the dominant kernel by K depth: its prologue / epilogue are a fixed cost per workgroup (s_memtime: 10-19k + 7-9k cycles
-            # against 1.5k per K chunk of eight channels), so the short-K layers pull the kernel's average down
-            ktot = {o['tag']: o['Ctot'] for o in eng.plan(prof['B'], prof['H'], prof['W'])['ops'] if o['kind'] == 'conv_mfma'}
-            classes = []
-            for lo, hi in ((0, 64), (65, 128), (129, 256), (257, 528), (529, 100000)):
-                sel = [o for o in prof['ops'] if o['kind'] == 'conv_mfma' and (o['tile'] & 8192) and lo <= ktot.get(o['tag'], -1) <= hi]
-                if sel:
-                    ms_c = sum(o['ms'] for o in sel)
-                    classes.append({'K': f'{lo}..{hi}' if hi < 100000 else f'{lo}..', 'launches': len(sel), 'ms': round(ms_c, 3),
-                                    'frac': round(sum(o['flops'] for o in sel) / 3.0 / max(ms_c, 1e-9) / 1e9 / PEAK_FP32_MFMA_TFLOPS, 4)})
-            roofline['dominant_kernel']['by_input_channels'] = classes
-        extra = {}
-        if 'warp' in cls:
-            wgbs = cls['warp']['bytes'] / (cls['warp']['ms'] * 1e-3) / 1e9
-            extra['roofline_warp'] = {
-                'bound': 'hbm', 'kernel': 'warp_vec_kernel (bilinear gather)', 'achieved': round(wgbs, 1),
-                'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': round(wgbs / PEAK_HBM_GBS, 4),
-                'traffic': warp_traffic if not args.precision else None,
-                'traffic_note': (f'REPLAYED like roofline.traffic ({traffic_src}): (2*FETCH_SIZE + WRITE_SIZE) of the warp launches / their number; '
-                                 f'algorithmic bytes per launch = {cls["warp"]["bytes"] / max(cls["warp"]["launches"], 1):.0f}') if warp_traffic else None,
-                'launches_per_step': cls['warp']['launches'], 'class_ms_per_step': round(cls['warp']['ms'], 3),
-                'algorithmic_bytes_per_step': cls['warp']['bytes'],
+        ms_per_depth, roofline, extra, prof = None, None, {}, None
+        if args.full:
+            if T > 1 and world == 1:
+                # one more recursion with a host synchronisation after every depth (depth d = 2^(d-1) pairs x the tiles)
+                frames = torch.stack([x0[0], x1[0]]).contiguous()
+                ms_per_depth = []
+                for _ in range(T):
+                    torch.cuda.synchronize()
+                    td = time.perf_counter()
+                    mids = dev_it.batch(frames[:-1].contiguous(), frames[1:].contiguous())
+                    torch.cuda.synchronize()
+                    ms_per_depth.append(round((time.perf_counter() - td) * 1e3, 2))
+                    nxt = torch.empty((2 * frames.shape[0] - 1,) + tuple(frames.shape[1:]), dtype=frames.dtype, device=dev)
+                    nxt[0::2] = frames
+                    nxt[1::2] = mids
+                    frames = nxt
+                del frames, mids, nxt
+            # ---- roofline of the dominant kernel class: hipEvents around every launch, on the launch stream
+            # steady state: a normal forward is queued right in front of the profiled one, with no host
+            # synchronisation in between, so the first kernels are not timed on a GPU that is ramping up from idle
+            it(x0, x1)
+            eng.set_option('profile', 1)
+            it(x0, x1)
+            torch.cuda.synchronize()
+            prof = eng.profile()      # the LAST model invocation of that call (one chunk of tiles when the frame was chunked)
+            eng.set_option('profile', 0)
+            if args.profile_out:
+                with open(args.profile_out, 'w') as f:
+                    json.dump(prof, f)
+            cls = prof['classes']
+            conv = cls['conv_mfma']
+            npix = prof['B'] * prof['H'] * prof['W']      # padded input pixels of the profiled invocation
+            alg_flops = CONV_FLOP_PER_PIXEL * npix
+            # conv_mfma launches carry all conv FLOPs except the Cin=3 first layer and the tiny 1x1 heads
+            conv_tflops = conv['flops'] / (conv['ms'] * 1e-3) / 1e12
+            total_ms = sum(c['ms'] for c in cls.values())
+            # FLOPs the matrix pipe really executes: the Winograd F(2,3) kernel (tile id & 256) does 2/3 of the direct
+            # convolution's multiplies, the sub-pixel-folded upsample + 2x2 conv (tag ':phases') 9/16
+            exec_flops = 0.0
+            per_kernel = {k: {'launches': 0, 'ms': 0.0, 'executed_flops': 0.0} for k in ('conv_wino2d_kernel', 'conv_wino43_kernel', 'conv_fold4_kernel')}
+            for o in prof['ops']:
+                if o['kind'] != 'conv_mfma':
+                    continue
+                f = o['flops']
+                if o['tile'] & 8192:
+                    f *= 1.0 / 3.0                                   # nested Winograd F(4,3)x x F(2,3)y: 3 multiplies per output of 9
+                elif o['tile'] & 256:
+                    f *= 0.5 if o['tile'] & 2048 else 2.0 / 3.0    # Winograd F(4,3) / F(2,3) along x
+                elif o['tile'] & 16384:
+                    f *= 4.0 / 16.0                                  # conv_fold4_kernel: upsample + 2x2 in its difference form, 4 multiplies of 16
+                elif o['tag'].endswith(':phases'):
+                    f *= 9.0 / 16.0
+                exec_flops += f
+                kname = 'conv_wino2d_kernel' if (o['tile'] & 8192) else 'conv_fold4_kernel' if (o['tile'] & 16384) else 'conv_wino43_kernel' if ((o['tile'] & 256) and (o['tile'] & 2048)) else None
+                if kname:
+                    per_kernel[kname]['launches'] += 1
+                    per_kernel[kname]['ms'] += o['ms']
+                    per_kernel[kname]['executed_flops'] += f
+            exec_tflops = exec_flops / (conv['ms'] * 1e-3) / 1e12
+            traffic, traffic_src, warp_traffic, traffic_why = None, None, None, None
+            try:  # fabric-side bytes per launch REPLAYED from the committed PMC passes (profiles/; PMC needs its own rocprofv3
+                # processes) - only from a file made with THIS build of the kernels (film_version() carries a hash of csrc/ + the header)
+                import glob
+                pmc_files = sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_pmc_conv.json')))
+                if pmc_files and args.workload == '1080p_2x2':
+                    pmc = json.load(open(pmc_files[-1]))
+                    traffic_src = os.path.relpath(pmc_files[-1], ROOT)
+                    if pmc.get('build') != eng.version():
+                        traffic_why = (f'{traffic_src} was collected with build "{pmc.get("build")}", this run is "{eng.version()}": not replayed '
+                                       f'(tools/gpu_pmc.sh + tools/pmc_summary.py refresh it)')
+                    else:
+                        traffic = round(pmc['hbm_bytes_per_launch'])
+                        wcls = next((v for k, v in pmc.get('classes', {}).items() if k.startswith('warp')), None)
+                        if wcls and wcls.get('hbm_bytes_per_launch'):
+                            warp_traffic = round(wcls['hbm_bytes_per_launch'])
+            except Exception as e:   # noqa: BLE001
+                traffic, traffic_why = None, repr(e)
+            # the roofline the conv class is priced against: the fp32 MFMA peak in the default mode; in the opt-in
+            # split modes the dense bf16 MFMA peak divided by the bf16 products one fp32 product costs
+            peak = {0: PEAK_FP32_MFMA_TFLOPS, 1: PEAK_BF16_MFMA_TFLOPS / 6, 2: PEAK_BF16_MFMA_TFLOPS / 3}[args.precision]
+            roofline = {
+                'bound': 'mfma',
+                'kernel': ('conv class = conv_wino2d_kernel (every 3x3 layer of the levels >= 1536 pixels: 91 % of the FLOPs) / conv_buf_kernel / conv_c3_kernel (fp32 v_mfma_f32_32x32x2_f32); '
+                           '`achieved` / `frac` count the FLOPs the matrix pipe executes (nested Winograd F(4,3)x x F(2,3)y layers x1/3, F(4,3) x1/2, F(2,3) x2/3, folded 2x2 layers x9/16 '
+                           'of the direct convolution)')
+                          if not args.precision else
+                          ('conv class in the opt-in split mode = conv_winox3_kernel / conv_halo_split_kernel '
+                           '(v_mfma_f32_32x32x16_bf16, fp32 accumulate) + the fp32 kernels on the small / 2x2 layers; '
+                           'peak = dense bf16 MFMA peak / bf16 products per fp32 product'),
+                'achieved': round(exec_tflops, 3), 'peak': round(peak, 1), 'unit': 'TFLOP/s',
+                'frac': round(exec_tflops / peak, 4),
+                'frac_note': 'utilisation of the peak by the multiplies the matrix pipe EXECUTES; the kernels that execute fewer of them per output '
+                             '(conv_wino2d_kernel: 1/3 of the direct count) lower it while the step gets faster - see direct_equivalent and kernels[]',
+                'traffic': traffic if not args.precision else None,
+                'traffic_note': (f'REPLAYED, not measured in this run: bytes per launch, (2*FETCH_SIZE + WRITE_SIZE) of the rocprofv3 PMC passes '
+                                 f'committed in {traffic_src}, collected with the same build of the kernels ("{eng.version()}"; PMC needs its own '
+                                 f'rocprofv3 processes)') if traffic else traffic_why,
+                # the two Winograd kernels on their own (executed FLOPs: nested F(4,3)x x F(2,3)y = 1/3, 1-D F(4,3) = 1/2 of the direct
+                # count); `dominant_kernel` = the one with the larger share of the step
+                'kernels': None if args.precision else [
+                    {'name': k, 'launches': v['launches'], 'ms': round(v['ms'], 3),
+                     'executed_tflops': round(v['executed_flops'] / max(v['ms'], 1e-9) / 1e9, 3),
+                     'frac': round(v['executed_flops'] / max(v['ms'], 1e-9) / 1e9 / PEAK_FP32_MFMA_TFLOPS, 4),
+                     'direct_equivalent_tflops': round(v['executed_flops'] * (3.0 if k == 'conv_wino2d_kernel' else 4.0 if k == 'conv_fold4_kernel' else 2.0) / max(v['ms'], 1e-9) / 1e9, 3),
+                     'avg_launch_ms': round(v['ms'] / max(1, v['launches']), 5)}
+                    for k, v in sorted(per_kernel.items(), key=lambda kv: -kv[1]['ms']) if v['launches']],
+                'launches_per_step': conv['launches'],
+                'avg_launch_ms': round(conv['ms'] / conv['launches'], 5),
+                'class_ms_per_step': round(conv['ms'], 3),
+                'executed_flops_per_step': exec_flops,
+                'algorithmic_flops_per_step': conv['flops'],
+                'all_conv_flops_per_step': alg_flops,
+                'share_of_kernel_time': round(conv['ms'] / total_ms, 4),
+                'direct_equivalent': {'achieved': round(conv_tflops, 3), 'ratio_to_peak': round(conv_tflops / peak, 4),
+                                      'note': 'same launches priced with the direct convolution\'s FLOPs (SURVEY 8d formula); exceeds the fp32 MFMA '
+                                              'peak because Winograd / the sub-pixel fold execute fewer multiplies - an algorithmic saving, not a utilisation'},
             }
-        extra['kernel_ms_per_step'] = {k: round(v['ms'], 3) for k, v in cls.items()}
-        if world == 1 and T == 1 and not strong:
-            # the same step through the drop-in boundary with HOST buffers (numpy in, numpy out: film_interpolate with
-            # FILM_MEM_HOST copies the two frames up and the result down inside the call) - never `value`
-            x0h, x1h = x0.cpu().numpy(), x1.cpu().numpy()
-            host_call = lambda: eng.interpolate_frames(x0h, x1h, align=align, block_shape=block) if pairs == 1 else eng.interpolate_frames(x0h, x1h, align=align)   # noqa: E731
-            host_call()
-            t_h = []
-            for _ in range(5):
-                th0 = time.perf_counter()
+            roofline['dominant_kernel'] = roofline['kernels'][0] if roofline.get('kernels') else None
+            if roofline['dominant_kernel'] is not None and not args.precision:
+                # the dominant kernel by K depth: its prologue / epilogue are a fixed cost per workgroup (s_memtime: 10-19k + 7-9k cycles
+                # against 1.5k per K chunk of eight channels), so the short-K layers pull the kernel's average down
+                ktot = {o['tag']: o['Ctot'] for o in eng.plan(prof['B'], prof['H'], prof['W'])['ops'] if o['kind'] == 'conv_mfma'}
+                classes = []
+                for lo, hi in ((0, 64), (65, 128), (129, 256), (257, 528), (529, 100000)):
+                    sel = [o for o in prof['ops'] if o['kind'] == 'conv_mfma' and (o['tile'] & 8192) and lo <= ktot.get(o['tag'], -1) <= hi]
+                    if sel:
+                        ms_c = sum(o['ms'] for o in sel)
+                        classes.append({'K': f'{lo}..{hi}' if hi < 100000 else f'{lo}..', 'launches': len(sel), 'ms': round(ms_c, 3),
+                                        'frac': round(sum(o['flops'] for o in sel) / 3.0 / max(ms_c, 1e-9) / 1e9 / PEAK_FP32_MFMA_TFLOPS, 4)})
+                roofline['dominant_kernel']['by_input_channels'] = classes
+            extra = {}
+            if 'warp' in cls:
+                wgbs = cls['warp']['bytes'] / (cls['warp']['ms'] * 1e-3) / 1e9
+                extra['roofline_warp'] = {
+                    'bound': 'hbm', 'kernel': 'warp_vec_kernel (bilinear gather)', 'achieved': round(wgbs, 1),
+                    'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': round(wgbs / PEAK_HBM_GBS, 4),
+                    'traffic': warp_traffic if not args.precision else None,
+                    'traffic_note': (f'REPLAYED like roofline.traffic ({traffic_src}): (2*FETCH_SIZE + WRITE_SIZE) of the warp launches / their number; '
+                                     f'algorithmic bytes per launch = {cls["warp"]["bytes"] / max(cls["warp"]["launches"], 1):.0f}') if warp_traffic else None,
+                    'launches_per_step': cls['warp']['launches'], 'class_ms_per_step': round(cls['warp']['ms'], 3),
+                    'algorithmic_bytes_per_step': cls['warp']['bytes'],
+                }
+            extra['kernel_ms_per_step'] = {k: round(v['ms'], 3) for k, v in cls.items()}
+            if world == 1 and T == 1 and not strong:
+                # the same step through the drop-in boundary with HOST buffers (numpy in, numpy out: film_interpolate with
+                # FILM_MEM_HOST copies the two frames up and the result down inside the call) - never `value`
+                x0h, x1h = x0.cpu().numpy(), x1.cpu().numpy()
+                host_call = lambda: eng.interpolate_frames(x0h, x1h, align=align, block_shape=block) if pairs == 1 else eng.interpolate_frames(x0h, x1h, align=align)   # noqa: E731
                 host_call()
-                t_h.append((time.perf_counter() - th0) * 1e3)
-            pin_in, pin_out = torch.empty(x0.shape, dtype=torch.float32, pin_memory=True), torch.empty(x0.shape, dtype=torch.float32, pin_memory=True)
-            torch.cuda.synchronize()
-            pin_in.copy_(x0.cpu())
-            scratch0, scratch1 = torch.empty_like(x0), torch.empty_like(x1)     # never into x0 / x1: later measurements read them
-            torch.cuda.synchronize()
-            th0 = time.perf_counter(); scratch0.copy_(pin_in); scratch1.copy_(pin_in); torch.cuda.synchronize(); h2d = (time.perf_counter() - th0) * 1e3   # noqa: E702
-            del scratch0, scratch1
-            th0 = time.perf_counter(); pin_out.copy_(out if out is not None else x0); torch.cuda.synchronize(); d2h = (time.perf_counter() - th0) * 1e3   # noqa: E702
-            hm = float(np.median(t_h))
-            extra['host_buffers'] = {'ms_per_step': round(hm, 3), 'frames_per_s': round(frames_per_step / (hm * 1e-3), 4),
-                                     'h2d_ms': round(h2d, 3), 'd2h_ms': round(d2h, 3), 'bytes_in': int(2 * x0h.nbytes), 'bytes_out': int(x0h.nbytes),
-                                     'over_device_resident_ms': round(hm - dt / args.steps * 1e3, 3),
-                                     'note': 'numpy -> numpy through film_interpolate(FILM_MEM_HOST), pageable host memory, the reference interface '
-                                             '(eval/interpolator.py:152-209); the call pipelines its copies: second frame uploaded behind the first '
-                                             'frame\'s first layers, first half of the result downloaded behind the second half\'s last layer (option '
-                                             'host_overlap); h2d / d2h: the same bytes from / to pinned memory on their own; the headline `value` '
-                                             'keeps the frames resident in HBM'}
+                t_h = []
+                for _ in range(5):
+                    th0 = time.perf_counter()
+                    host_call()
+                    t_h.append((time.perf_counter() - th0) * 1e3)
+                pin_in, pin_out = torch.empty(x0.shape, dtype=torch.float32, pin_memory=True), torch.empty(x0.shape, dtype=torch.float32, pin_memory=True)
+                torch.cuda.synchronize()
+                pin_in.copy_(x0.cpu())
+                scratch0, scratch1 = torch.empty_like(x0), torch.empty_like(x1)     # never into x0 / x1: later measurements read them
+                torch.cuda.synchronize()
+                th0 = time.perf_counter(); scratch0.copy_(pin_in); scratch1.copy_(pin_in); torch.cuda.synchronize(); h2d = (time.perf_counter() - th0) * 1e3   # noqa: E702
+                del scratch0, scratch1
+                th0 = time.perf_counter(); pin_out.copy_(out if out is not None else x0); torch.cuda.synchronize(); d2h = (time.perf_counter() - th0) * 1e3   # noqa: E702
+                hm = float(np.median(t_h))
+                extra['host_buffers'] = {'ms_per_step': round(hm, 3), 'frames_per_s': round(frames_per_step / (hm * 1e-3), 4),
+                                         'h2d_ms': round(h2d, 3), 'd2h_ms': round(d2h, 3), 'bytes_in': int(2 * x0h.nbytes), 'bytes_out': int(x0h.nbytes),
+                                         'over_device_resident_ms': round(hm - dt / args.steps * 1e3, 3),
+                                         'note': 'numpy -> numpy through film_interpolate(FILM_MEM_HOST), pageable host memory, the reference interface '
+                                                 '(eval/interpolator.py:152-209); the call pipelines its copies: second frame uploaded behind the first '
+                                                 'frame\'s first layers, first half of the result downloaded behind the second half\'s last layer (option '
+                                                 'host_overlap); h2d / d2h: the same bytes from / to pinned memory on their own; the headline `value` '
+                                                 'keeps the frames resident in HBM'}
         value = (1 if strong else reported) * args.steps * frames_per_step / dt
         result = {
             'metric': METRIC.get(args.workload, 'interpolated frames/sec @1080p'), 'value': round(value, 4), 'unit': 'frames/s',
@@ -727,17 +790,22 @@ def main():
                        'parallelism': (f'{world} GPU(s): the {ntiles} tiles of ONE pair sharded over the ranks for the whole recursion tree, '
                                        f'one gather of the generated tiles to rank 0 per step (timed); weights RCCL-broadcast once') if strong
                                       else f'{world} independent GPU(s), weights RCCL-broadcast once',
-                       'roofline_profiled_on': f'one model invocation of {prof["B"]} tile(s) / pair(s) of {prof["W"]}x{prof["H"]}',
                        'exec': 'one stream' if args.no_graph else 'hipGraph replay' if args.graph else 'direct launches, two lanes', 'lanes': args.lanes},
-            'parity': parity,
-            'timed_output_bit_identical_to_first_call': timed_same,
-            # crc32 of rank 0's last timed output (weak: its own pairs, seeds independent of the world size; strong: the gathered frames of
-            # the one pair): equal across --gpus N for the same workload - tests/test_gpu_multi.py compares 2 ranks with 1
-            'output_crc32': None if out is None else int(__import__('zlib').crc32(out.detach().cpu().numpy().tobytes())),
             'build': eng.version(),
-            'roofline': roofline,
         }
-        result.update(extra)
+        if dumped is not None:
+            result['dump_outputs'] = dumped
+        if args.full:
+            result['config']['roofline_profiled_on'] = f'one model invocation of {prof["B"]} tile(s) / pair(s) of {prof["W"]}x{prof["H"]}'
+            result.update({
+                'parity': parity,
+                'timed_output_bit_identical_to_first_call': timed_same,
+                # crc32 of rank 0's last timed output (weak: its own pairs, seeds independent of the world size; strong: the gathered frames of
+                # the one pair): equal across --gpus N for the same workload - tests/test_gpu_multi.py compares 2 ranks with 1
+                'output_crc32': None if out is None else int(__import__('zlib').crc32(out.detach().cpu().numpy().tobytes())),
+                'roofline': roofline,
+            })
+            result.update(extra)
         if ms_per_depth is not None:
             result['ms_per_depth'] = ms_per_depth
         if dist is not None:   # first contact with N > 1 ranks: what the job looked like from the inside
@@ -746,7 +814,7 @@ def main():
                                'weight_broadcast_ms': None if bcast_ms is None else round(bcast_ms, 2),
                                'gather_ms_per_step': (round(drv.gather_ms / max(1, drv.runs), 3) if strong and hasattr(drv, 'gather_ms') else None),
                                'tune': 'rank 0 measured, every rank imported its choices (film_export_tune / film_import_tune)'}
-        if world == 1 and not args.no_split and T == 1 and '+extra' in eng.version():   # the opt-in modes exist in FILM_EXTRA_FAMILIES=1 builds only
+        if args.full and world == 1 and not args.no_split and T == 1 and '+extra' in eng.version():   # the opt-in modes exist in FILM_EXTRA_FAMILIES=1 builds only
             # Extra, NOT the headline value: the opt-in precision mode "bf16x6" (exact 3-way bf16 split of every fp32
             # operand, six partial products, fp32 accumulate) on the same workload, with its distance from the
             # default fp32-MFMA result.
@@ -772,12 +840,12 @@ def main():
                 except Exception as e:   # noqa: BLE001
                     result['precision_mode_' + name] = {'error': repr(e)}
             eng.set_option('precision', 0)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 result['cpu_baseline'] = cpu_baseline(weights)
             except Exception as e:   # noqa: BLE001
                 result['cpu_baseline'] = {'error': repr(e)}
-        else:
+        elif args.full:
             result['cpu_baseline'] = None
     if dist is not None:
         dist.barrier()

@@ -3,6 +3,7 @@ headline number runs on): HIP engine through the C-ABI vs (a) the CPU oracle on 
 committed vectors produced by the reference's own graph code (tests/golden/ref_*.npz, tools/make_ref_golden.py;
 tf_*.npz when a TensorFlow-made set exists).  Inputs are structured frames with >= 8 px motion (tests/inputs.py)
 and the reference's photos.  max|delta| per stage is printed."""
+import importlib.util
 import os
 
 import numpy as np
@@ -94,6 +95,36 @@ def test_1080p_2x2_device_resident_bench_path(published):
     assert d_gold < IMAGE_TOL and torch.equal(first, again) and not torch.equal(first, other)
     host = _interp(eng, w, align=64, block_shape=[2, 2])(x0, x1, HALF)
     assert np.array_equal(again.cpu().numpy(), host)
+
+
+def test_plain_bench_run_dumps_the_last_timed_output(published, tmp_path):
+    """`bench.py --gpus 1 --steps 2 --warmup 1 --workload 256 --dump-outputs DIR` in a process of its own: a plain run (no
+    --full) prints the headline fields and none of the --full ones, and DIR/interpolated.npy - the output of its last timed
+    step - is the oracle's mid frame for bench.py's own seeded pair and weights."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from oracle import film_oracle as fo
+    opt, w, _ = published
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                          '--workload', '256', '--dump-outputs', str(tmp_path / 'out')], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    print({k: line[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'dtype', 'higher_is_better', 'steps', 'warmup')})
+    assert line['steps'] == 2 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0 and line['dtype'] == 'f32'
+    assert not {'roofline', 'parity', 'cpu_baseline', 'output_crc32', 'host_buffers'} & set(line)
+    assert line['dump_outputs'] == {'interpolated': {'shape': [1, 256, 256, 3], 'sampled_elements': None}}
+    assert os.listdir(tmp_path / 'out') == ['interpolated.npy']
+    got = np.load(tmp_path / 'out' / 'interpolated.npy')
+    spec = importlib.util.spec_from_file_location('bench', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x0, x1 = bench.synth_pair(256, 256, 2)
+    want = fo.OracleInterpolator(w, align=64)(x0, x1, HALF)
+    d = float(np.abs(got - want).max())
+    print(f'bench 256, last timed step vs oracle: max|d| {d:.3e}')
+    assert got.dtype == np.float32 and got.shape == want.shape and d < IMAGE_TOL
 
 
 @needs_extra_families

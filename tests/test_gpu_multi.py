@@ -32,7 +32,7 @@ def _bench(*args, timeout=900):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--no-split', *args],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--no-split', *args],
                          capture_output=True, text=True, env=env, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
     return json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])

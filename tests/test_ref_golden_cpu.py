@@ -205,29 +205,49 @@ def test_tensorflow_pinning_status():
                     'Recipe: python tools/make_ref_golden.py --backend tf')
 
 
+def _reference_layer_graph(tf):
+    """The layer objects the reference's own create_model built for the small architecture on oracle/tf_shim, rebuilt from
+    tests/golden/ref_tiny_layer_graph.json (tools/make_ref_golden.py --only tiny_layer_graph) out of the shim's layer classes: the
+    same classes (Conv2D / Layer), names, attribute order, list positions and shared objects.  Returns (top-level layers, the
+    (canonical name, name chain, object path) the shim's weight provider logged while that graph executed)."""
+    import json
+    with open(os.path.join(G.GOLDEN, 'ref_tiny_layer_graph.json')) as f:
+        g = json.load(f)
+    objs = []
+    for n in g['nodes']:
+        o = object.__new__(tf.keras.layers.Conv2D if n['class'] == 'Conv2D' else tf.keras.layers.Layer)
+        o.name = n['name']
+        objs.append(o)
+
+    def value(r):
+        if r is None:
+            return None
+        return objs[r['node']] if 'node' in r else [value(x) for x in r['list']]
+    for o, n in zip(objs, g['nodes']):
+        for attr, r in n['attrs']:
+            setattr(o, attr, value(r))
+    return [objs[i] for i in g['top']], [tuple(e) for e in g['conv_log']]
+
+
 def test_tf_backend_naming_walk_runs_over_the_reference_layers():
     """`tools/make_ref_golden.py --backend tf` (the recipe for the first TensorFlow-capable machine) assigns the weights to the
     Keras model by WALKING its layer objects (walk_conv_layers).  No TensorFlow here - but the walk itself can run: over the layer
-    objects the REFERENCE'S OWN create_model builds on oracle/tf_shim.  It must find the 41 Conv2D layers (tiny net: fewer) exactly
-    once, give each the canonical name and object-graph path the shim's weight provider logged while the graph executed (two
-    independent derivations: attribute walk vs call-time name chains), and hand every layer the tensors of that name.
-    Needs /root/reference (present in the build container only)."""
+    objects the REFERENCE'S OWN create_model builds on oracle/tf_shim (stored as tests/golden/ref_tiny_layer_graph.json).  It must
+    find the 41 Conv2D layers (tiny net: fewer) exactly once, give each the canonical name and object-graph path the shim's weight
+    provider logged while the graph executed (two independent derivations: attribute walk vs call-time name chains), and hand every
+    layer the tensors of that name."""
     import importlib.util
     from conftest import ROOT
-    if not os.path.isdir('/root/reference/models/film_net'):
-        pytest.skip('the reference checkout is not on this machine')
+    from oracle.tf_shim import tensorflow as tf
     spec = importlib.util.spec_from_file_location('make_ref_golden', os.path.join(ROOT, 'tools', 'make_ref_golden.py'))
     mg = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mg)
     from film_hip import options as O, weights as W
-    ref = mg.Reference('/root/reference', 'shim')
     w = W.make_synthetic_weights(O.TINY, seed=0)
-    model = ref.model_fn(w, O.TINY)
-    x0, x1 = TI.frame_pair(1, 32, 32, seed=5)
-    model({'x0': x0, 'x1': x1, 'time': np.full((1, 1), 0.5, np.float32)})
-    by_call = {n: (c, p) for n, c, p in model.conv_log}          # names logged while the reference graph executed
+    top_layers, conv_log = _reference_layer_graph(tf)
+    by_call = {n: (c, p) for n, c, p in conv_log}                 # names logged while the reference graph executed
     handed = {}
-    log = mg.walk_conv_layers(ref.tf, model.keras_model.layers, w, lambda layer, k, b: handed.__setitem__(id(layer), (k, b)))
+    log = mg.walk_conv_layers(tf, top_layers, w, lambda layer, k, b: handed.__setitem__(id(layer), (k, b)))
     assert len(log) == len(w) // 2 == len(by_call) == len(handed)
     assert {n for n, _, _ in log} == set(by_call) == {n for n, _, _ in W.weight_specs(O.TINY)}
     for name, chain, path in log:

@@ -24,6 +24,7 @@ Large outputs are stored as a stride-4 pixel sample plus float64 row / column su
 """
 import argparse
 import importlib
+import json
 import os
 import shutil
 import sys
@@ -359,8 +360,48 @@ def case_recursive6(ref, prefix):
     return out
 
 
+def layer_graph(tf, top_layers):
+    """The object graph below create_model's top-level layers as data, for walk_conv_layers to run over without the reference:
+    every Layer reachable through instance attributes and (nested) lists / tuples gets one node {class, name, attrs}, where
+    attrs lists, in attribute order, the attributes that hold layers as [attr, ref]; a ref is {'node': index} (a shared layer is
+    one node) or {'list': [ref or None, ...]} (None keeps the position of an element that is not a layer)."""
+    nodes, index = [], {}
+
+    def ref(v):
+        if isinstance(v, tf.keras.layers.Layer):
+            if id(v) not in index:
+                index[id(v)] = len(nodes)
+                node = {'class': 'Conv2D' if isinstance(v, tf.keras.layers.Conv2D) else 'Layer', 'name': v.name, 'attrs': []}
+                nodes.append(node)
+                for attr, val in list(vars(v).items()):
+                    r = ref(val)
+                    if r is not None:
+                        node['attrs'].append([attr, r])
+            return {'node': index[id(v)]}
+        if isinstance(v, (list, tuple)):
+            items = [ref(x) for x in v]
+            return {'list': items} if any(r is not None for r in items) else None
+        return None
+    top = [ref(layer)['node'] for layer in top_layers]
+    return {'top': top, 'nodes': nodes}
+
+
+def case_tiny_layer_graph(ref, prefix):
+    """The layer objects the reference's create_model builds for the small architecture on oracle/tf_shim (layer_graph) and the
+    (canonical name, name chain, object path) of every Conv2D as the shim's weight provider logged them while the graph executed:
+    what tests/test_ref_golden_cpu.py runs the `--backend tf` naming walk over.  Shim backend only."""
+    w = W.make_synthetic_weights(O.TINY, seed=0)
+    x0, x1 = TI.frame_pair(1, 32, 32, seed=5)
+    model = ref.model_fn(w, O.TINY)
+    model({'x0': x0, 'x1': x1, 'time': np.full((1, 1), 0.5, np.float32)})
+    out = layer_graph(ref.tf, model.keras_model.layers)
+    out['conv_log'] = [list(e) for e in model.conv_log]
+    return out
+
+
 CASES = {'recursive6': case_recursive6, 'tiny': case_tiny, '256': case_256, 'photos': case_photos, 'vimeo': case_vimeo,
          'recursive': case_recursive, '1080p': case_1080p}
+JSON_CASES = {'tiny_layer_graph': case_tiny_layer_graph}     # written as tests/golden/<prefix>_<name>.json
 
 
 def main():
@@ -380,6 +421,14 @@ def main():
         path = os.path.join(GOLDEN, f'{prefix}_{name}.npz')
         np.savez_compressed(path, **out)
         print(f'{name}: {time.time() - t0:.1f} s -> {path} ({os.path.getsize(path) / 1e6:.2f} MB)')
+    for name, fn in JSON_CASES.items():
+        if (args.only and name not in args.only) or args.backend != 'shim':
+            continue
+        path = os.path.join(GOLDEN, f'{prefix}_{name}.json')
+        with open(path, 'w') as f:
+            json.dump(fn(ref, prefix), f, indent=1)
+            f.write('\n')
+        print(f'{name} -> {path} ({os.path.getsize(path) / 1e3:.1f} kB)')
 
 
 if __name__ == '__main__':
