@@ -340,7 +340,9 @@ void free_plan(Plan* p) {
   if (p->arena) (void)hipFree(p->arena);
 }
 
-int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out) {
+// Plans are cached per (B, H, W, tiles): tiles = 0 for pair plans, > 0 for sequence plans (Plan::tiles) - the two kinds never
+// stand in for each other.  Both count toward the three device plans kept alive.
+int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles = 0) {
   const int div = 1 << (h->cfg.pyramid_levels - 1);
   if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
   if (H % div || W % div)
@@ -352,17 +354,17 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out) {
     return fail(h, FILM_ERR_INVALID, "input %d x %d too small: warped pyramid level %d would be smaller than 2x2", H, W, wl);
   if ((int64_t)2 * B * H * W >= (int64_t)1 << 31) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
   for (auto& p : h->plans)
-    if (p->B == B && p->H == H && p->W == W && (!need_device || p->arena)) { *out = p.get(); p->last_use = ++h->tick; return FILM_OK; }
+    if (p->B == B && p->H == H && p->W == W && p->tiles == tiles && (!need_device || p->arena)) { *out = p.get(); p->last_use = ++h->tick; return FILM_OK; }
   if (need_device)   // a description-only plan of this shape (film_plan_json, unit_buffer_bytes) is superseded, not kept beside the new one
     for (size_t i = 0; i < h->plans.size(); ++i)
-      if (h->plans[i]->B == B && h->plans[i]->H == H && h->plans[i]->W == W) {
+      if (h->plans[i]->B == B && h->plans[i]->H == H && h->plans[i]->W == W && h->plans[i]->tiles == tiles) {
         if (h->last_plan == h->plans[i].get()) h->last_plan = nullptr;
         free_plan(h->plans[i].get());
         h->plans.erase(h->plans.begin() + i);
         break;
       }
   std::unique_ptr<Plan> P(new Plan);
-  int rc = plan_build(h, P.get(), B, H, W);
+  int rc = plan_build(h, P.get(), B, H, W, tiles);
   if (rc) return rc;
   if (need_device) {
     // keep at most 3 device plans alive (workspaces are GBs at 1080p tiles)
@@ -704,6 +706,16 @@ int film_plan_json(film_t* h, int B, int H, int W, char* buf, int64_t cap, int64
   return copy_out_string(h, plan_json(h, *P), buf, cap, needed);
 }
 
+int film_sequence_plan_json(film_t* h, int n_pairs, int tiles_per_frame, int H, int W, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (n_pairs < 1 || tiles_per_frame < 1) return fail(h, FILM_ERR_INVALID, "n_pairs and tiles_per_frame must be positive");
+  if ((int64_t)n_pairs * tiles_per_frame >= (int64_t)1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
+  Plan* P = nullptr;
+  int rc = get_plan(h, n_pairs * tiles_per_frame, H, W, false, &P, tiles_per_frame);
+  if (rc) return rc;
+  return copy_out_string(h, plan_json(h, *P), buf, cap, needed);
+}
+
 int film_profile_json(film_t* h, char* buf, int64_t cap, int64_t* needed) {
   if (!h) return FILM_ERR_INVALID;
   if (h->profile_json.empty()) return fail(h, FILM_ERR_STATE, "no profiled forward yet (film_set_option(\"profile\", 1))");
@@ -893,6 +905,120 @@ int film_interpolate(film_t* h, const float* x0, const float* x1, int B, int H, 
   }
   if (mem_kind == FILM_MEM_HOST) {
     HIPCHK(h, hipMemcpyAsync(out, dout, frame_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+  }
+  return FILM_OK;
+}
+
+// ---- frame sequences ------------------------------------------------------------------------------------------------------------
+namespace {
+// Chunk of a sequence of n frame pairs of T tiles each, at most cap pair-tiles per plan: k consecutive pairs x nt tiles, i.e. (k + 1) * nt
+// extracted image-tiles for k * nt pair-tiles.  Most pairs per extracted image = the largest k; ties go to the larger tile range (whole
+// frames first).  Then balanced like balanced_chunk, so that the chunks of a sequence share one cached plan where they can.
+// cap comes from the PAIR plan of one pair-tile: every buffer of a sequence plan of k * nt pair-tiles is at most the pair plan's of
+// k * nt (images (k + 1) * nt <= 2 k nt, the flow estimator and the decoder the same), so its 4 GiB and arena limits hold here too.
+void sequence_chunk(int n, int T, int cap, int* k, int* nt) {
+  int bk = 0, bt = 1;
+  for (int t = std::min(T, cap); t >= 1; --t) {
+    const int kk = std::min(n, cap / t);
+    if (kk > bk) { bk = kk; bt = t; }
+  }
+  *k = balanced_chunk(n, std::max(bk, 1));
+  *nt = balanced_chunk(T, bt);
+}
+}  // namespace
+
+int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int W, int align, int block_h, int block_w, float* out,
+                              int mem_kind, void* stream) {
+  // (the arguments are checked before the device: a plan-only handle reports them like a device handle does)
+  if (!h || !frames || !out) return fail(h, FILM_ERR_INVALID, "NULL argument");
+  if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
+  if (F < 2) return fail(h, FILM_ERR_INVALID, "a sequence needs at least 2 frames, got %d", F);
+  if (H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
+  const int bh = block_h > 0 ? block_h : 1, bw = block_w > 0 ? block_w : 1;
+  // the reference's asserts (eval/interpolator.py:84-89), same messages
+  if (H % bh) return fail(h, FILM_ERR_INVALID, "block_height=%d should evenly divide height=%d.", bh, H);
+  if (W % bw) return fail(h, FILM_ERR_INVALID, "block_width=%d should evenly divide width=%d.", bw, W);
+  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: film_interpolate_sequence needs a HIP device (no CPU fallback)");
+  if (!h->finalized) return fail(h, FILM_ERR_STATE, "film_finalize has not been called");
+  TileMapParams tp{};
+  tp.B = 1; tp.H = H; tp.W = W; tp.bh = bh; tp.bw = bw; tp.ph = H / bh; tp.pw = W / bw;
+  const int hp = (align > 0 && tp.ph % align) ? align - tp.ph % align : 0;   // _pad_to_align, eval/interpolator.py:45-52
+  const int wp = (align > 0 && tp.pw % align) ? align - tp.pw % align : 0;
+  tp.TH = tp.ph + hp; tp.TW = tp.pw + wp; tp.oy = hp / 2; tp.ox = wp / 2;
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = 0;
+  int tmax = 1;
+  const int64_t unit = unit_buffer_bytes(h, tp.TH, tp.TW, &rc, &tmax);
+  if (rc) return rc;
+  if (unit > kMaxBufferBytes)
+    return fail(h, FILM_ERR_INVALID, "a %d x %d tile needs a %.1f GB activation buffer in front of a kernel that addresses 4 GiB per "
+                "buffer - use a finer block_shape", tp.TH, tp.TW, unit * 1e-9);
+  if (h->opt_max_batch) tmax = std::min(tmax, h->opt_max_batch);
+  const int n = F - 1, T = bh * bw;
+  int k = 1, nt = 1;
+  sequence_chunk(n, T, tmax, &k, &nt);
+  hipStream_t s = pick_stream(h, mem_kind, stream);
+  const size_t frame = (size_t)H * W * 3;
+  const float* dfr = frames;
+  float* dout = out;
+  if (mem_kind == FILM_MEM_HOST) {  // stage in HBM: [F frames | F - 1 results], plain upload, work, download
+    const size_t need = (2 * (size_t)F - 1) * frame * sizeof(float);
+    if (h->stage_bytes < need) {
+      if (h->stage) { HIPCHK(h, hipStreamSynchronize(s)); HIPCHK(h, hipFree(h->stage)); h->stage = nullptr; h->stage_bytes = 0; }
+      hipError_t e = hipMalloc(&h->stage, need);
+      if (e != hipSuccess) return fail(h, FILM_ERR_NOMEM, "frame staging hipMalloc of %.1f MB failed", need * 1e-6);
+      h->stage_bytes = need;
+    }
+    float* st = (float*)h->stage;
+    HIPCHK(h, hipMemcpyAsync(st, frames, (size_t)F * frame * sizeof(float), hipMemcpyHostToDevice, s));
+    dfr = st; dout = st + (size_t)F * frame;
+  }
+  const int64_t tile_floats = (int64_t)tp.TH * tp.TW * 3;
+  for (int j0 = 0; j0 < n;) {
+    const int kk = std::min(k, n - j0);
+    int t0 = 0;
+    while (t0 < T) {
+      const int nn = std::min(nt, T - t0);
+      Plan* P = nullptr;
+      rc = get_plan(h, kk * nn, tp.TH, tp.TW, true, &P, nn);
+      if (rc == FILM_ERR_NOMEM && kk * nn > 1) break;
+      if (rc) return rc;
+      const Buffer& img0 = P->bufs[P->find("img0")];
+      const Buffer& ob = P->bufs[P->find("out")];
+      TileMapParams q = tp;
+      if (nn == T) {   // whole frames: frames j0 .. j0 + kk are consecutive tiles of one frame batch
+        q.tile0 = 0; q.ntiles = (kk + 1) * T; q.src = dfr + (size_t)j0 * frame; q.dst = P->arena + img0.off;
+        HIPCHK(h, film_launch_frame_to_tiles(q, s));
+      } else {         // tiles [t0, t0 + nn) of each frame, frame-major
+        for (int f = 0; f <= kk; ++f) {
+          q.tile0 = t0; q.ntiles = nn; q.src = dfr + (size_t)(j0 + f) * frame; q.dst = P->arena + img0.off + (int64_t)f * nn * tile_floats;
+          HIPCHK(h, film_launch_frame_to_tiles(q, s));
+        }
+      }
+      rc = run_plan(h, P, s);
+      if (rc) return rc;
+      if (nn == T) {
+        q.tile0 = 0; q.ntiles = kk * T; q.src = P->arena + ob.off; q.dst = dout + (size_t)j0 * frame;
+        HIPCHK(h, film_launch_tiles_to_frame(q, s));
+      } else {
+        for (int j = 0; j < kk; ++j) {
+          q.tile0 = t0; q.ntiles = nn; q.src = P->arena + ob.off + (int64_t)j * nn * tile_floats; q.dst = dout + (size_t)(j0 + j) * frame;
+          HIPCHK(h, film_launch_tiles_to_frame(q, s));
+        }
+      }
+      t0 += nn;
+    }
+    if (t0 < T) {   // workspace did not fit: smaller chunks, this block of pairs again from its first tile (a tile range already done is
+                    // recomputed into the same outputs, with the same bits)
+      if (kk > 1) k = (kk + 1) / 2;
+      else nt = (nt + 1) / 2;
+      continue;
+    }
+    j0 += kk;
+  }
+  if (mem_kind == FILM_MEM_HOST) {
+    HIPCHK(h, hipMemcpyAsync(out, dout, (size_t)n * frame * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
   }
   return FILM_OK;

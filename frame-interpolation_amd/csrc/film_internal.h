@@ -145,7 +145,10 @@ struct HostTensor {
 };
 
 struct Plan {
-  int B = 0, H = 0, W = 0;
+  int B = 0, H = 0, W = 0;   // B = pair-tiles (frame pairs x tiles per pair)
+  // 0: a pair plan (img0 = [x0 tiles | x1 tiles], 2B images); > 0: a sequence plan over B / tiles consecutive frame pairs of `tiles`
+  // tiles each (img0 = B + tiles images, frame-major: image f * tiles + t; pair-tile p reads images p and p + tiles)
+  int tiles = 0;
   std::vector<Buffer> bufs;
   std::vector<OpDesc> ops;
   int64_t arena_floats = 0;
@@ -252,7 +255,7 @@ int validate_config(film_t* h, const film_config& c);
 void build_layers(film_t* h);
 
 // ---- film_planner.cpp
-int plan_build(film_t* h, Plan* P, int B, int H, int W);   // fills P->bufs / ops / arena_floats for (B, H, W)
+int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles = 0);   // fills P->bufs / ops / arena_floats for (B, H, W) (tiles > 0: sequence plan)
 int64_t limited_buffer_bytes(const Plan* P);                // largest buffer a kernel with whole-buffer 32-bit offsets reads
 std::string plan_json(film_t* h, const Plan& P);
 

@@ -6,6 +6,9 @@
 //   flow synthesis     util.py:106-117              -> reuses the estimator's v (identical arithmetic)
 //   warps + concat     interpolator.py:163-183      -> warp ops writing into the aligned pyramid
 //   fusion             fusion.py:103-140            -> NN-upsample folded into the 2x2 conv's gather
+// A sequence plan (tiles > 0) runs F - 1 consecutive pairs of F frames: the image pyramids and the extractor run once per
+// frame (B + tiles images), every op that reaches the other image of a pair is emitted per direction with that image one
+// pointer offset of `tiles` images away, and the flow estimator (2B) and the decoder (B) are the pair plan's.
 // decides the kernel family of every convolution from its shape and the options (never from timing or the batch size),
 // derives the cross-lane dependencies of the two-stream replay, and renders a plan as JSON (film_plan_json).
 #include "film_internal.h"
@@ -313,27 +316,30 @@ struct Planner {
     P->ops.push_back(op);
   }
 
-  int build(int B, int H, int W) {
+  int build(int B, int H, int W, int T) {
     const film_config& c = h->cfg;
     const int L = c.pyramid_levels, FL = c.fusion_pyramid_levels;
     const int N2 = 2 * B;
+    const bool seq = T > 0;
+    const int NI = seq ? B + T : N2;   // images of the per-image stages (image pyramids, feature extractor)
+    const int o1 = seq ? T : B;        // image 1 of pair-tile b is image b + o1
     auto fc = feature_channels(c);
     auto ff = fusion_filters(c);
     auto HL = [&](int l) { return H >> l; };
     auto WL = [&](int l) { return W >> l; };
-    P->B = B; P->H = H; P->W = W;
+    P->B = B; P->H = H; P->W = W; P->tiles = T;
 
     // ---- buffers ---------------------------------------------------------------------------
     std::vector<int> img(L), feat(L), res(L), v(L), vup(L), warped(L), aligned(FL), fu_u(FL), fu_a(FL), fu_b(FL);
-    for (int l = 0; l < L; ++l) img[l] = add_buffer("img" + std::to_string(l), N2, HL(l), WL(l), 3);
-    for (int l = 0; l < L; ++l) feat[l] = add_buffer("feat" + std::to_string(l), N2, HL(l), WL(l), fc[l]);
+    for (int l = 0; l < L; ++l) img[l] = add_buffer("img" + std::to_string(l), NI, HL(l), WL(l), 3);
+    for (int l = 0; l < L; ++l) feat[l] = add_buffer("feat" + std::to_string(l), NI, HL(l), WL(l), fc[l]);
     // feature-extractor scratch: stage-j conv_2j output and pooled input, sized for the largest use
     int64_t fx_sz = 0, fxp_sz = 0, fp_sz = 0;
     for (int i = 0; i < L; ++i)
       for (int j = 0; j < std::min(L - i, c.sub_levels); ++j) {
-        fx_sz = std::max<int64_t>(fx_sz, (int64_t)N2 * HL(i + j) * WL(i + j) * (c.filters << j));
+        fx_sz = std::max<int64_t>(fx_sz, (int64_t)NI * HL(i + j) * WL(i + j) * (c.filters << j));
         if (j + 1 < std::min(L - i, c.sub_levels))
-          fxp_sz = std::max<int64_t>(fxp_sz, (int64_t)N2 * HL(i + j + 1) * WL(i + j + 1) * (c.filters << j));
+          fxp_sz = std::max<int64_t>(fxp_sz, (int64_t)NI * HL(i + j + 1) * WL(i + j + 1) * (c.filters << j));
       }
     // one scratch pair per pyramid level's subtree: the subtrees are independent chains (two of them run beside the
     // rest on the side stream of the replay graph) and 288 GB of HBM makes sharing pointless
@@ -341,9 +347,9 @@ struct Planner {
     for (int i = 0; i < L; ++i) {
       int64_t a_sz = 0, p_sz = 0;
       for (int j = 0; j < std::min(L - i, c.sub_levels); ++j) {
-        a_sz = std::max<int64_t>(a_sz, (int64_t)N2 * HL(i + j) * WL(i + j) * (c.filters << j));
+        a_sz = std::max<int64_t>(a_sz, (int64_t)NI * HL(i + j) * WL(i + j) * (c.filters << j));
         if (j + 1 < std::min(L - i, c.sub_levels))
-          p_sz = std::max<int64_t>(p_sz, (int64_t)N2 * HL(i + j + 1) * WL(i + j + 1) * (c.filters << j));
+          p_sz = std::max<int64_t>(p_sz, (int64_t)NI * HL(i + j + 1) * WL(i + j + 1) * (c.filters << j));
       }
       fx_a_v[i] = add_scratch("scratch_fx_a" + std::to_string(i), a_sz);
       fx_p_v[i] = add_scratch("scratch_fx_p" + std::to_string(i), p_sz);
@@ -380,9 +386,9 @@ struct Planner {
     const int out = add_buffer("out", B, H, W, 3);
     P->arena_floats = cursor;
 
-    // ---- image pyramids (util.py:23-45), both images as one batch of 2B ----------------------
+    // ---- image pyramids (util.py:23-45), both images as one batch of 2B (sequence: every frame once) ----------------------
     for (int l = 0; l + 1 < L; ++l) {
-      pool("image_pyramid_l" + std::to_string(l + 1), view(img[l], 0, 0, 3), view(img[l + 1], 0, 0, 3), N2, HL(l), WL(l));
+      pool("image_pyramid_l" + std::to_string(l + 1), view(img[l], 0, 0, 3), view(img[l + 1], 0, 0, 3), NI, HL(l), WL(l));
       // on the side stream: the level-0 subtree (main stream) reads img[0] only and starts at once; six 6-us launches less in front of it
       // (256x256: 2.31 -> 2.28 ms per step, 1080p: -0.1 ms; profiles/r06_pool_lane_ab.log)
       P->ops.back().lane = 1;
@@ -406,17 +412,17 @@ struct Planner {
           op.nseg = 1; op.seg[0].v = view(img[i], 0, 0, 3);
           op.ksize = 3; op.leaky = 1; op.Cout = k; op.Ctot = 3;
           op.w_off = Lp.w_off; op.b_off = Lp.b_off;
-          op.out = tmp; op.NB = N2; op.H = HL(lv); op.W = WL(lv);
+          op.out = tmp; op.NB = NI; op.H = HL(lv); op.W = WL(lv);
           op.tile = TILE_C3_DIRECT | CONV_TILE_XCD | CONV_TILE_C3;
-          op.flops = 2.0 * N2 * HL(lv) * WL(lv) * k * 27; op.bytes = 4.0 * N2 * HL(lv) * WL(lv) * (3 + k);
+          op.flops = 2.0 * NI * HL(lv) * WL(lv) * k * 27; op.bytes = 4.0 * NI * HL(lv) * WL(lv) * (3 + k);
           P->ops.push_back(op);
         } else {
           SegDesc s; s.v = scratch(fx_p, k >> 1);
-          conv(tg, w0, {s}, tmp, N2, HL(lv), WL(lv), true);
+          conv(tg, w0, {s}, tmp, NI, HL(lv), WL(lv), true);
         }
         SegDesc s1; s1.v = tmp;
         View dst = view(feat[lv], 0, slot_offset(c, j), k);
-        conv(tg, w1, {s1}, dst, N2, HL(lv), WL(lv), true);
+        conv(tg, w1, {s1}, dst, NI, HL(lv), WL(lv), true);
         if (j < n - 1) {
           OpDesc& cv = P->ops.back();
           if ((h->opt_fuse & 8) && cv.kind == OP_CONV && (cv.wino == 3 || cv.wino == 4) && cv.ksplit <= 1 && !(HL(lv) & 1) && !(WL(lv) & 1)) {
@@ -424,7 +430,7 @@ struct Planner {
             cv.tag += "+pool";
             cv.out2 = scratch(fx_p, k);
           } else
-            pool(tg + ":pool", dst, scratch(fx_p, k), N2, HL(lv), WL(lv));
+            pool(tg + ":pool", dst, scratch(fx_p, k), NI, HL(lv), WL(lv));
         }
       }
       // every subtree but the level-0 one (75 % of the extractor's FLOPs) goes to the side stream: they and the coarse
@@ -448,7 +454,7 @@ struct Planner {
       SegDesc sa; sa.v = view(feat[l], 0, 0, fc[l]);
       SegDesc sb;
       if (l == L - 1) {
-        sb.v = view(feat[l], 0, 0, fc[l]); sb.boff = B; sb.bmod = N2;  // the other image's features
+        sb.v = view(feat[l], 0, 0, fc[l]); sb.boff = B; sb.bmod = N2;  // the other image's features (sequence: per direction, below)
       } else {
         // tf.image.resize(2 * v) inside the warps that consume it (fuse bit 1) pays on the small, launch-bound levels; on the
         // large ones every (pixel, channel group) thread of the warp would recompute the flow behind four gathers, a second
@@ -466,21 +472,42 @@ struct Planner {
         // Both directions in ONE launch (batch n = d * B + b, like every other op of the estimator): direction d warps the OTHER
         // image's features, i.e. the source batch is rotated by B (pyramid_flow_estimator.py:150-158 runs the two directions as
         // two calls; the arithmetic per pixel is the same).
-        warp(tg + ":warp_d01", view(feat[l], 0, 0, fc[l]), view(vup[l], 0, 0, 2), view(warped[l], 0, 0, fc[l]), N2, Hl, Wl, 1.f);
-        P->ops.back().src_brot = B;
-        if (fuse_up) {
-          // tf.image.resize(2 * v) (pyramid_flow_estimator.py:155) inside the warp: the flow of this level is computed
-          // from the coarser level's v by every thread of a pixel and stored once (to vup, which v = res + up reads)
-          OpDesc& w = P->ops.back();
-          w.tag += "+resize2x";
-          w.in2 = View();
-          w.in3 = view(v[l + 1], 0, 0, 2);
-          w.out2 = view(vup[l], 0, 0, 2);
+        // Sequence plan: one launch per direction, the other image's features one offset of T images away (no batch rotation).
+        for (int d = 0; d < (seq ? 2 : 1); ++d) {
+          if (seq)
+            warp(tg + ":warp_d" + std::to_string(d), view(feat[l], d ? 0 : T, 0, fc[l]), view(vup[l], d * B, 0, 2),
+                 view(warped[l], d * B, 0, fc[l]), B, Hl, Wl, 1.f);
+          else {
+            warp(tg + ":warp_d01", view(feat[l], 0, 0, fc[l]), view(vup[l], 0, 0, 2), view(warped[l], 0, 0, fc[l]), N2, Hl, Wl, 1.f);
+            P->ops.back().src_brot = B;
+          }
+          if (fuse_up) {
+            // tf.image.resize(2 * v) (pyramid_flow_estimator.py:155) inside the warp: the flow of this level is computed
+            // from the coarser level's v by every thread of a pixel and stored once (to vup, which v = res + up reads)
+            OpDesc& w = P->ops.back();
+            w.tag += "+resize2x";
+            w.in2 = View();
+            w.in3 = view(v[l + 1], d * B, 0, 2);
+            w.out2 = view(vup[l], d * B, 0, 2);
+          }
         }
         sb.v = view(warped[l], 0, 0, fc[l]);
       }
       View cur = scratch(fp[0], nf);
-      conv(tg, prefix + "/conv_0", {sa, sb}, cur, N2, Hl, Wl, true);
+      if (!seq) {
+        conv(tg, prefix + "/conv_0", {sa, sb}, cur, N2, Hl, Wl, true);
+      } else {
+        // [features of image a | (warped) features of image b] per direction d: a = image p + d T, b = image p + (1 - d) T
+        // (coarsest level) or warped[d B + p]; the two halves of the output are the 2B batch of the pair plan
+        for (int d = 0; d < 2; ++d) {
+          SegDesc a, b;
+          a.v = view(feat[l], d * T, 0, fc[l]);
+          b.v = l == L - 1 ? view(feat[l], (1 - d) * T, 0, fc[l]) : view(warped[l], d * B, 0, fc[l]);
+          View o = cur;
+          o.off += (int64_t)d * B * Hl * Wl * nf;
+          conv(tg + ":d" + std::to_string(d), prefix + "/conv_0", {a, b}, o, B, Hl, Wl, true);
+        }
+      }
       int which = 0;
       for (int j = 1; j < nconv; ++j) {
         View nxt = scratch(fp[which ^ 1], nf);
@@ -535,7 +562,9 @@ struct Planner {
       const std::string tg = "align_l" + std::to_string(l);
       // Planar level: the planes of image 0 and image 1 follow each other, i.e. they are ONE [2B][H][W][C] array - both feature warps
       // in one launch (batch n = s * B + b; image s is sampled with the flow of the opposite direction: the flow batch is rotated by B).
-      const bool pair = P->bufs[aligned[l]].planar > 0;
+      // (sequence plans: image 1 is not at +B, so both the pair launch and the fused misc16 warp are out - the per-image branch)
+      const bool pair = P->bufs[aligned[l]].planar > 0 && !seq;
+      const bool misc16 = (h->opt_fuse & 4) && !seq;
       if (pair) {
         warp(tg + ":warp_feat01", view(feat[l], 0, 0, fc[l]), view(v[l], 0, 0, 2), aligned_part(aligned[l], 0, fc[l]), N2, HL(l), WL(l), 0.5f);
         P->ops.back().flow_brot = B;
@@ -543,13 +572,13 @@ struct Planner {
       for (int s = 0; s < 2; ++s) {
         View fl = view(v[l], (1 - s) * B, 0, 2);
         if (!pair)
-          warp(tg + ":warp_feat" + std::to_string(s), view(feat[l], s * B, 0, fc[l]), fl,
+          warp(tg + ":warp_feat" + std::to_string(s), view(feat[l], s * o1, 0, fc[l]), fl,
                aligned_part(aligned[l], s, fc[l]), B, HL(l), WL(l), 0.5f);
-        if (!(h->opt_fuse & 4))
-          warp(tg + ":warp_img" + std::to_string(s), view(img[l], s * B, 0, 3), fl,
+        if (!misc16)
+          warp(tg + ":warp_img" + std::to_string(s), view(img[l], s * o1, 0, 3), fl,
                sub(aligned_part(aligned[l], 2, fc[l]), 3 * s, 3), B, HL(l), WL(l), 0.5f, false);
       }
-      if (h->opt_fuse & 4) {
+      if (misc16) {
         // the sixteen miscellaneous channels [warp(img0) 3 | warp(img1) 3 | 0.5 bflow 2 | 0.5 fflow 2 | 0 x 6] ride in the second
         // feature warp of the level as one more channel slice (one full 64-byte line per pixel and store)
         OpDesc& w = P->ops.back();
@@ -692,9 +721,9 @@ struct Planner {
 
 }  // namespace
 
-int plan_build(film_t* h, Plan* P, int B, int H, int W) {
+int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles) {
   Planner pl{h, P};
-  return pl.build(B, H, W);
+  return pl.build(B, H, W, tiles);
 }
 
 // The conv kernels other than conv_wino43_kernel address their inputs with 32-bit byte offsets from the start of the
@@ -702,6 +731,8 @@ int plan_build(film_t* h, Plan* P, int B, int H, int W) {
 // to the workgroup's own halo rows and every other kernel with 64-bit pointers, so the large levels of a large frame
 // (F(4,3) layers only: an untiled 4K frame has 4.4-5 GB level-0 buffers) are not limited.  Largest limited buffer of a
 // B = 1 plan, in bytes (buffers scale linearly with the batch; the kernel family of a layer does not depend on it).
+// The whole buffer bounds what a kernel addresses through a view that starts inside it (a sequence plan's view of the
+// images from `tiles` on: its resource begins at the view and reaches no further than the buffer's end).
 int64_t limited_buffer_bytes(const Plan* P) {
   int64_t mx = 1;
   for (const OpDesc& op : P->ops) {
@@ -721,7 +752,9 @@ void json_view(std::ostringstream& o, const char* key, const View& v, const Plan
 
 std::string plan_json(film_t* h, const Plan& P) {
   std::ostringstream o;
-  o << "{\"B\":" << P.B << ",\"H\":" << P.H << ",\"W\":" << P.W << ",\"arena_floats\":" << P.arena_floats
+  o << "{\"B\":" << P.B << ",\"H\":" << P.H << ",\"W\":" << P.W;
+  if (P.tiles > 0) o << ",\"kind\":\"sequence\",\"n_pairs\":" << P.B / P.tiles << ",\"tiles\":" << P.tiles;
+  o << ",\"arena_floats\":" << P.arena_floats
     << ",\"offset32_buffer_bytes\":" << limited_buffer_bytes(&P)
     << ",\"packed_floats\":" << h->packed_floats << ",\"buffers\":[";
   for (size_t i = 0; i < P.bufs.size(); ++i) {

@@ -157,6 +157,15 @@ class Interpolator:
       assert self._align > 0, 'align must be a positive number.'
     return self._engine.interpolate_frames(x0, x1, align=self._align)
 
+  def interpolate_sequence(self, frames: np.ndarray) -> np.ndarray:
+    """(extension) The mid-frame of every consecutive pair of a frame sequence: float32 [F,H,W,3] -> [F-1,H,W,3], output j
+    bit-identical to self(frames[j:j+1], frames[j+1:j+2], dt) (align and block_shape as set), with one feature extraction
+    per frame (film_interpolate_sequence).  Not clipped."""
+    if self._align is not None:
+      assert self._align > 0, 'align must be a positive number.'
+    bs = self._block_shape if self._block_shape is not None and np.prod(self._block_shape) > 1 else None
+    return self._engine.interpolate_sequence(frames, align=self._align, block_shape=bs)
+
   def __call__(self, x0: np.ndarray, x1: np.ndarray,
                dt: np.ndarray) -> np.ndarray:
     """Same contract as interpolate(); with block_shape set, the (single) image is split into

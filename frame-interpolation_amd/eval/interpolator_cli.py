@@ -52,6 +52,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--block_width', type=int, default=1, help='Number of patches along width.')
     ap.add_argument('--precision', type=int, default=0, choices=[0, 1, 2],
                     help='(extension) engine precision mode: 0 fp32 MFMA, 1 bf16x6, 2 bf16x3.')
+    ap.add_argument('--sequence_window', type=int, default=0,
+                    help='(extension) 0: one input pair at a time (default).  K >= 2: windows of K consecutive input frames, one feature '
+                         'extraction per frame and recursion depth (film_interpolate_sequence); same files.')
     ap.add_argument('--output_video', action='store_true', default=False,
                     help='If true, creates a video of the frames in the interpolated_frames/ subdirectory')
     return ap
@@ -105,14 +108,21 @@ def write_video_uint8(path: str, frames: List[np.ndarray], fps: int) -> None:
         p.wait()
 
 
+def pairs_to_files(inputs: List[str], first: int, end: int, n_pairs: int, it, args, frames_dir: str, keep: bool = False):
+    """The device pipeline for input pairs [first, end): one pair at a time, or in windows of --sequence_window input frames."""
+    window = getattr(args, 'sequence_window', 0)
+    if window:
+        return util.interpolate_windows_to_files(inputs, first, end, n_pairs, args.times_to_interpolate, it, frames_dir, window, keep=keep)
+    return util.interpolate_pairs_to_files(inputs, first, end, n_pairs, args.times_to_interpolate, it, frames_dir, keep=keep)
+
+
 def process_directory(directory: str, it, args) -> int:
     inputs = list_input_frames(directory)
     if len(inputs) < 2:
         return 0
     frames_dir = f'{directory}/interpolated_frames'
     output_frames([], frames_dir)      # (creates the directory / removes stale frame_*.png, as the reference does before writing)
-    fast = util.interpolate_pairs_to_files(inputs, 0, len(inputs) - 1, len(inputs) - 1, args.times_to_interpolate, it, frames_dir,
-                                           keep=bool(args.output_video))
+    fast = pairs_to_files(inputs, 0, len(inputs) - 1, len(inputs) - 1, it, args, frames_dir, keep=bool(args.output_video))
     if fast is not None:               # the device pipeline (HIP-backed Interpolator): same files, encoded while the GPU works
         n, kept = fast
         if args.output_video:
@@ -191,7 +201,7 @@ def process_pair_range(directory: str, first: int, end: int, n_pairs: int, it, a
     else:
         os.makedirs(frames_dir, exist_ok=True)
     step = 2 ** args.times_to_interpolate
-    fast = util.interpolate_pairs_to_files(inputs, first, end, n_pairs, args.times_to_interpolate, it, frames_dir)
+    fast = pairs_to_files(inputs, first, end, n_pairs, it, args, frames_dir)
     if fast is not None:
         return fast[0]
     n = 0
@@ -206,6 +216,8 @@ def process_pair_range(directory: str, first: int, end: int, n_pairs: int, it, a
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
+    if args.sequence_window != 0 and args.sequence_window < 2:
+        raise SystemExit(f'--sequence_window: 0 (off) or at least 2 frames, got {args.sequence_window}')
     if args.output_video:
         util.get_ffmpeg_path()
     world = int(os.environ.get('WORLD_SIZE', '1'))

@@ -132,6 +132,76 @@ def interpolate_pairs_to_files(inputs: List[str], first: int, end: int, n_pairs:
     return written, ([kept[i] for i in sorted(kept)] if kept is not None else None)
 
 
+def interpolate_windows_to_files(inputs: List[str], first: int, end: int, n_pairs: int, times_to_interpolate: int,
+                                 interpolator: 'interpolator_lib.Interpolator', frames_dir: str, window: int, keep: bool = False,
+                                 workers: Optional[int] = None):
+    """interpolate_pairs_to_files in sequence mode (eval/interpolator_cli.py --sequence_window): input pairs [first, end) in windows of
+    `window` consecutive input frames (window - 1 pairs; a window's last frame is the next window's first), the recursion of a
+    window breadth first on the device with one feature extraction per frame and depth (film_hip.recursive.Uint8SequenceStream).
+    Same file names and bytes as interpolate_pairs_to_files; same return value; None for an Interpolator that is not HIP-backed."""
+    engine = getattr(interpolator, 'engine', None)
+    if engine is None or engine.device < 0 or os.environ.get('FILM_HOST_RECURSION') == '1':
+        return None
+    if window < 2:
+        raise ValueError(f'a sequence window holds at least 2 frames, got {window}')
+    import concurrent.futures
+    import torch
+    from film_hip.recursive import Uint8SequenceStream
+    from film_hip.torch_io import DeviceInterpolator
+    T = times_to_interpolate
+    step = 2 ** T
+    dev = torch.device('cuda', engine.device)
+    dev_it = DeviceInterpolator(engine, align=interpolator.align, block_shape=interpolator.block_shape)
+    nw = workers or max(2, min(32, (os.cpu_count() or 4)))
+    kept = {} if keep else None
+    written = 0
+    with torch.cuda.device(dev), concurrent.futures.ThreadPoolExecutor(max_workers=nw) as enc:
+        stream = Uint8SequenceStream(dev_it, engine)
+        pending = []
+
+        def emit(index: int, pixels: np.ndarray) -> None:
+            if kept is not None:
+                kept[index] = pixels
+            pending.append(enc.submit(write_image_uint8, f'{frames_dir}/frame_{index:03d}.png', pixels))
+
+        reads = {}
+        try:
+            a = first
+            while a < end:
+                b = min(a + window - 1, end)
+                for i in range(a, b + 1):
+                    if i not in reads:
+                        reads[i] = enc.submit(read_image, inputs[i])
+                imgs = [reads.pop(i).result() for i in range(a, b)] + [reads[b].result()]   # (frame b stays: the next window's first)
+                for i in range(b + 1, min(b + window, end + 1)):   # decode the next window while this one computes
+                    reads[i] = enc.submit(read_image, inputs[i])
+                for i in range(a, b):
+                    emit(i * step, to_uint8(imgs[i - a]))
+                written += b - a
+                if T > 0:
+                    x = torch.from_numpy(np.ascontiguousarray(np.stack(imgs), dtype=np.float32)).to(dev, non_blocking=False)
+                    futs = stream.run(x, T, lambda k, px, base=a * step: emit(base + k, px))
+                    for fu in futs:
+                        fu.result()
+                    written += (b - a) * (step - 1)
+                if b == n_pairs:
+                    emit(b * step, to_uint8(imgs[-1]))
+                    written += 1
+                a = b
+            for fu in pending:
+                fu.result()
+        except BaseException:
+            for fu in pending:
+                fu.cancel()
+            for fu in reads.values():
+                fu.cancel()
+            raise
+        finally:
+            stream.close()
+            engine.save_tune_cache()
+    return written, ([kept[i] for i in sorted(kept)] if kept is not None else None)
+
+
 def _recursive_generator(
         frame1: np.ndarray, frame2: np.ndarray, num_recursions: int,
         interpolator: 'interpolator_lib.Interpolator',

@@ -48,7 +48,8 @@ EXPORTED_SYMBOLS = (
     'film_finalize', 'film_packed_size', 'film_export_packed', 'film_import_packed', 'film_export_layouts', 'film_forward',
     'film_interpolate',
     'film_set_option', 'film_profile_json', 'film_plan_json', 'film_get_tap', 'film_crc32c', 'film_version',
-    'film_export_tune', 'film_import_tune', 'film_to_uint8', 'film_load_bundle', 'film_bcast_weights')
+    'film_export_tune', 'film_import_tune', 'film_to_uint8', 'film_load_bundle', 'film_bcast_weights',
+    'film_interpolate_sequence', 'film_sequence_plan_json')
 
 _lib = None
 
@@ -90,9 +91,13 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_forward.argtypes = [vp, fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, ctypes.c_int, vp]
     lib.film_interpolate.argtypes = [vp, fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, fp, ctypes.c_int, vp]
+    lib.film_interpolate_sequence.argtypes = [vp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, fp, ctypes.c_int, vp]
     lib.film_set_option.argtypes = [vp, cp, ctypes.c_int64]
     lib.film_profile_json.argtypes = [vp, ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_plan_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
+    lib.film_sequence_plan_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
+                                            ctypes.c_int64, i64p]
     lib.film_get_tap.argtypes = [vp, cp, fp, ctypes.c_int64, i64p]
     lib.film_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_int64]
     lib.film_crc32c.restype = ctypes.c_uint32
@@ -343,6 +348,34 @@ class FilmEngine:
                                                int(align or 0), bh, bw, ctypes.c_void_p(out_ptr), FILM_MEM_DEVICE,
                                                ctypes.c_void_p(stream) if stream else None))
 
+    def interpolate_sequence(self, frames: np.ndarray, align: Optional[int] = None, block_shape=None,
+                             out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Mid-frames of every consecutive pair of a frame sequence (film_interpolate_sequence): frames float32 [F,H,W,3], F >= 2
+        -> [F-1,H,W,3], out[j] bit-identical to interpolate_frames(frames[:-1], frames[1:], align, block_shape)[j], with one feature
+        extraction per frame instead of two per pair.  `out` as for interpolate_frames (shape [F-1,H,W,3])."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        if frames.ndim != 4 or frames.shape[3] != 3:
+            raise ValueError(f'expected a [F,H,W,3] array, got {frames.shape}')
+        f, h, w, _ = frames.shape
+        bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
+        shape = (max(f - 1, 0), h, w, 3)
+        if out is None:
+            out = np.empty(shape, np.float32)
+        elif out.dtype != np.float32 or out.shape != shape or not out.flags['C_CONTIGUOUS'] or not out.flags['WRITEABLE']:
+            raise ValueError(f'out must be a writable C-contiguous float32 array of shape {shape}')
+        self._check(self._lib.film_interpolate_sequence(self._h, frames.ctypes.data, f, h, w, int(align or 0), bh, bw,
+                                                        out.ctypes.data, FILM_MEM_HOST, None))
+        self.save_tune_cache()
+        return out
+
+    def interpolate_sequence_device(self, frames_ptr: int, f: int, h: int, w: int, out_ptr: int, align: Optional[int] = None,
+                                    block_shape=None, stream: Optional[int] = None) -> None:
+        """Device-resident film_interpolate_sequence: frames [f,h,w,3] -> out [f-1,h,w,3] (raw device pointers), asynchronous on `stream`."""
+        bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
+        self._check(self._lib.film_interpolate_sequence(self._h, ctypes.c_void_p(frames_ptr), f, h, w, int(align or 0), bh, bw,
+                                                        ctypes.c_void_p(out_ptr), FILM_MEM_DEVICE,
+                                                        ctypes.c_void_p(stream) if stream else None))
+
     def to_uint8_device(self, src_ptr: int, dst_ptr: int, n: int, stream: Optional[int] = None) -> None:
         """film_to_uint8: write_image's quantisation (eval/util.py:51-52) of n device floats into n device bytes, asynchronous."""
         rc = self._lib.film_to_uint8(ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), int(n), ctypes.c_void_p(stream) if stream else None)
@@ -362,6 +395,10 @@ class FilmEngine:
 
     def plan(self, b: int, h: int, w: int) -> dict:
         return self._json_call(self._lib.film_plan_json, b, h, w)
+
+    def sequence_plan(self, n_pairs: int, tiles: int, h: int, w: int) -> dict:
+        """film_sequence_plan_json: the plan film_interpolate_sequence runs for n_pairs consecutive pairs of `tiles` h x w tiles."""
+        return self._json_call(self._lib.film_sequence_plan_json, n_pairs, tiles, h, w)
 
     def profile(self) -> dict:
         return self._json_call(self._lib.film_profile_json)

@@ -42,6 +42,24 @@ def interpolate_recursively(frames: List[torch.Tensor], times_to_interpolate: in
     yield frames[-1]
 
 
+def interpolate_sequence_recursively(frames: List[torch.Tensor], times_to_interpolate: int,
+                                     interpolator: DeviceInterpolator) -> List[torch.Tensor]:
+    """The same (n-1)*2^T + 1 frames as interpolate_recursively, breadth first over the WHOLE sequence: depth d is one
+    DeviceInterpolator.sequence call on the (n-1)*2^(d-1) + 1 frames of depth d - 1 (one feature extraction per frame, and the
+    pairs of different input pairs in one batch), its mid-frames interleaved with them.  Bit-identical to interpolate_recursively."""
+    seq = torch.stack(list(frames)).contiguous()
+    for _ in range(times_to_interpolate):
+        seq = _interleave(seq, interpolator.sequence(seq))
+    return list(seq)
+
+
+def _interleave(frames: torch.Tensor, mids: torch.Tensor) -> torch.Tensor:
+    out = torch.empty((2 * frames.shape[0] - 1,) + tuple(frames.shape[1:]), dtype=frames.dtype, device=frames.device)
+    out[0::2] = frames
+    out[1::2] = mids
+    return out
+
+
 class Uint8FrameStream:
     """The recursion of ONE input pair as a stream of quantised frames (round 4; replaces "all 2^T + 1 float32 frames in one
     blocking .cpu()" for callers that write files - eval/interpolator_cli.py).
@@ -95,6 +113,58 @@ class Uint8FrameStream:
             out[0::2] = frames
             out[1::2] = mids
             frames = out
+        return futures
+
+    def close(self) -> None:
+        self._pool.shutdown(wait=True)
+
+
+class Uint8SequenceStream:
+    """Uint8FrameStream for a WINDOW of consecutive input frames: the recursion of all its pairs breadth first, each depth one
+    DeviceInterpolator.sequence call over the window's frames of the previous depth; behind every depth its new frames are quantised
+    on the device (film_to_uint8), copied to pinned host memory on a copy stream and handed to `sink(index, uint8 [H,W,3])` from a
+    worker thread while the next depth computes.  index = position in the window's (m-1)*2^T + 1 long temporal sequence (the m
+    input frames, at multiples of 2^T, are not emitted)."""
+
+    def __init__(self, interpolator: DeviceInterpolator, engine, workers: int = 2):
+        import concurrent.futures
+        self._it = interpolator
+        self._engine = engine
+        self._copy_stream = torch.cuda.Stream(device=torch.device('cuda', engine.device))
+        self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=workers)
+        self._pinned = {}          # (depth, shape) -> pinned uint8 buffer (reused across windows)
+
+    def run(self, frames: torch.Tensor, times_to_interpolate: int, sink) -> List:
+        """frames: [m,H,W,3] float32 on the device, m >= 2.  Returns the futures of the hand-offs."""
+        T = times_to_interpolate
+        seq = frames.contiguous()
+        compute = torch.cuda.current_stream(seq.device)
+        futures = []
+        for d in range(1, T + 1):
+            mids = self._it.sequence(seq)
+            u8 = torch.empty(mids.shape, dtype=torch.uint8, device=mids.device)
+            self._engine.to_uint8_device(mids.data_ptr(), u8.data_ptr(), mids.numel(), stream=compute.cuda_stream)
+            ready = torch.cuda.Event()
+            ready.record(compute)
+            host = self._pinned.get((d, tuple(mids.shape)))
+            if host is None:
+                host = torch.empty(mids.shape, dtype=torch.uint8, pin_memory=True)
+                self._pinned[(d, tuple(mids.shape))] = host
+            done = torch.cuda.Event()
+            with torch.cuda.stream(self._copy_stream):
+                self._copy_stream.wait_event(ready)
+                host.copy_(u8, non_blocking=True)
+                u8.record_stream(self._copy_stream)
+                done.record(self._copy_stream)
+            step = 2 ** (T - d)
+
+            def hand_off(done=done, host=host, step=step, count=mids.shape[0]):
+                done.synchronize()
+                arr = host.numpy()
+                for j in range(count):
+                    sink((2 * j + 1) * step, arr[j].copy())   # (the pinned buffer is reused by the next window)
+            futures.append(self._pool.submit(hand_off))
+            seq = _interleave(seq, mids)
         return futures
 
     def close(self) -> None:

@@ -82,6 +82,19 @@ class DeviceInterpolator:
         bs = self._block_shape
         return self._run(x0, x1, bs if bs is not None and bs[0] * bs[1] > 1 else None)
 
+    def sequence(self, frames: torch.Tensor) -> torch.Tensor:
+        """Extension: the mid-frames of every consecutive pair of frames [F,H,W,3] -> [F-1,H,W,3] (film_interpolate_sequence: one feature
+        extraction per frame).  Bit-identical to batch(frames[:-1], frames[1:]), tiled by block_shape the same way."""
+        assert frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 4 and frames.shape[-1] == 3
+        frames = frames.contiguous()
+        f, h, w, _ = frames.shape
+        out = torch.empty((f - 1, h, w, 3), dtype=frames.dtype, device=frames.device)
+        bs = self._block_shape
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+        self._engine.interpolate_sequence_device(frames.data_ptr(), f, h, w, out.data_ptr(), align=self._align,
+                                                 block_shape=bs if bs is not None and bs[0] * bs[1] > 1 else None, stream=stream)
+        return out
+
     def __call__(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         if self._block_shape is not None and self._block_shape[0] * self._block_shape[1] > 1:
             if x0.shape[0] != 1:    # the reference's tiled path takes one pair (eval/interpolator.py:96-98); see .batch

@@ -139,6 +139,17 @@ int film_forward(film_t* h, const float* x0, const float* x1, int B, int H, int 
 int film_interpolate(film_t* h, const float* x0, const float* x1, int B, int H, int W, int align, int block_h,
                      int block_w, float* out, int mem_kind, void* stream);
 
+/* film_interpolate over a frame SEQUENCE: frames [F,H,W,3] -> out [F-1,H,W,3], out[j] = the mid-frame of frames[j] and frames[j+1],
+ * bit-identical to film_interpolate(frames[:-1], frames[1:], F - 1, ...).  The image pyramid and the feature extractor run once per
+ * frame (F extractions instead of 2 (F - 1)): a sequence plan holds k consecutive pairs x nt tiles per invocation ((k + 1) * nt
+ * image-tiles; the boundary frame is extracted again by the next chunk), pairs of different input pairs batch together.  Chunks are
+ * bounded by the limits of film_interpolate and "max_batch" (counted in pair-tiles), prefer the most pairs per extracted image, then
+ * whole frames, and are halved when a workspace allocation fails (results unchanged).  F < 2: FILM_ERR_INVALID.  align / block_h /
+ * block_w / mem_kind / stream as for film_interpolate (same padding, tiling, asserts); FILM_MEM_HOST is upload, work, download
+ * ("host_overlap" does not apply). */
+int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int W, int align, int block_h, int block_w,
+                              float* out, int mem_kind, void* stream);
+
 /* Execution options.  Keys:
  *   "autotune" 0/1 time every distinct conv shape of a new plan with each fitting tile shape and keep
  *                  the fastest (default 1; cannot change results - same k-ordered fma chain per output)
@@ -240,6 +251,12 @@ int film_profile_json(film_t* h, char* buf, int64_t capacity, int64_t* needed);
  * weight packing without a GPU.  "offset32_buffer_bytes" = the largest buffer a kernel with whole-buffer 32-bit
  * offsets reads (must stay below 4 GiB; conv_wino43_kernel and the pointer-addressed kernels are not limited). */
 int film_plan_json(film_t* h, int B, int H, int W, char* buf, int64_t capacity, int64_t* needed);
+
+/* The same for the sequence plan of n_pairs consecutive frame pairs of tiles_per_frame (padded) H x W tiles each, as
+ * film_interpolate_sequence runs it: "kind":"sequence", "n_pairs", "tiles"; B = n_pairs * tiles_per_frame pair-tiles; img0 holds
+ * (n_pairs + 1) * tiles_per_frame images, frame-major (pair-tile p reads images p and p + tiles_per_frame).  Works on plan-only handles. */
+int film_sequence_plan_json(film_t* h, int n_pairs, int tiles_per_frame, int H, int W, char* buf, int64_t capacity,
+                            int64_t* needed);
 
 /* Copies a named workspace buffer of the last forward (see "buffers" in film_plan_json) to a
  * host array; dims receives {N,H,W,C}.  Debug / parity taps, mirrors the aux outputs of
