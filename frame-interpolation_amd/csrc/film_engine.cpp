@@ -514,6 +514,7 @@ void film_destroy(film_t* h) {
   for (auto& p : h->plans) free_plan(p.get());
   if (h->packed_dev) (void)hipFree(h->packed_dev);
   if (h->stage) (void)hipFree(h->stage);
+  if (h->metrics_buf) (void)hipFree(h->metrics_buf);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   for (hipEvent_t& e : h->pipe_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (h->stream2) (void)hipStreamDestroy(h->stream2);

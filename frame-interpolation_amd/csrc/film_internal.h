@@ -171,6 +171,8 @@ struct Plan {
 struct film_handle {
   void* stage = nullptr;       // device staging of whole frames for film_interpolate(FILM_MEM_HOST)
   size_t stage_bytes = 0;
+  void* metrics_buf = nullptr;  // film_image_metrics: partials + results (+ the images with FILM_MEM_HOST), grown on demand
+  size_t metrics_bytes = 0;
   int device = -1;
   bool plan_only = true;
   film_config cfg{};

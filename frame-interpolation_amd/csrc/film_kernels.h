@@ -297,3 +297,21 @@ hipError_t film_launch_tiles_to_frame(const TileMapParams& p, hipStream_t s);   
 hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipStream_t s);
 // fills n floats with a deterministic pseudo-random pattern in [-1, 1) (autotune inputs only)
 hipError_t film_launch_fill_random(float* dst, int64_t n, uint32_t seed, hipStream_t s);
+
+// metrics_kernels.hip: the per-image metrics of film_image_metrics (eval/metrics.py) on float32 NHWC [B][H][W][C] images, C = 1 or 3
+#define FILM_SSIM_TAPS 11
+struct MetricsParams {
+  const float* pred;    // [B][H][W][C]; clipped to [0,1] on read with FILM_METRIC_CLIP
+  const float* ref;     // [B][H][W][C]
+  int B, H, W, C;
+  int flags;            // FILM_METRIC_* (include/film_hip.h)
+  double g[FILM_SSIM_TAPS];   // normalised Gaussian window (metrics._gauss_window), computed on the host
+  double c1, c2;        // (k1 max_val)^2, (k2 max_val)^2
+  // layout (film_metrics_layout): per image, sum_blocks x 3 partial sums, then C x ssim_tiles_y x ssim_tiles_x ssim partials
+  int sum_blocks, ssim_tiles_x, ssim_tiles_y;
+  int64_t part_per_image;
+  double* part;         // B * part_per_image doubles of scratch
+  double* out;          // [B][4]: sum |d|, sum d*d (float32 d), sum of squared float64 differences, ssim
+};
+void film_metrics_layout(MetricsParams& p);   // fills sum_blocks, ssim_tiles_x / _y and part_per_image from H, W, C
+hipError_t film_launch_image_metrics(const MetricsParams& p, hipStream_t s);

@@ -25,6 +25,9 @@ FILM_MEM_HOST = 0
 FILM_MEM_DEVICE = 1
 FILM_ERR_INVALID = -1
 FILM_ERR_NO_DEVICE = -3
+# film_image_metrics flags (include/film_hip.h); METRIC_FLAGS maps the metric names of eval/metrics.py to them
+FILM_METRIC_L1, FILM_METRIC_L2, FILM_METRIC_PSNR, FILM_METRIC_SSIM, FILM_METRIC_CLIP = 1, 2, 4, 8, 16
+METRIC_FLAGS = {'l1': FILM_METRIC_L1, 'l2': FILM_METRIC_L2, 'psnr': FILM_METRIC_PSNR, 'ssim': FILM_METRIC_SSIM}
 _MAXS = 8
 
 
@@ -49,7 +52,7 @@ EXPORTED_SYMBOLS = (
     'film_interpolate',
     'film_set_option', 'film_profile_json', 'film_plan_json', 'film_get_tap', 'film_crc32c', 'film_version',
     'film_export_tune', 'film_import_tune', 'film_to_uint8', 'film_load_bundle', 'film_bcast_weights',
-    'film_interpolate_sequence', 'film_sequence_plan_json')
+    'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics')
 
 _lib = None
 
@@ -108,6 +111,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_to_uint8.argtypes = [vp, vp, ctypes.c_int64, vp]
     lib.film_load_bundle.argtypes = [vp, cp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_bcast_weights.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp]
+    lib.film_image_metrics.argtypes = [vp, fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_double, fp, ctypes.c_int, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ('film_destroy',):
@@ -375,6 +380,45 @@ class FilmEngine:
         self._check(self._lib.film_interpolate_sequence(self._h, ctypes.c_void_p(frames_ptr), f, h, w, int(align or 0), bh, bw,
                                                         ctypes.c_void_p(out_ptr), FILM_MEM_DEVICE,
                                                         ctypes.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def _metric_flags(names, clip: bool) -> int:
+        unknown = [n for n in names if n not in METRIC_FLAGS]
+        if unknown:
+            raise ValueError(f'film_image_metrics computes {sorted(METRIC_FLAGS)}, not {unknown}')
+        flags = FILM_METRIC_CLIP if clip else 0
+        for n in names:
+            flags |= METRIC_FLAGS[n]
+        return flags
+
+    def image_metrics(self, pred: np.ndarray, ref: np.ndarray, names=('l1', 'l2', 'ssim', 'psnr'), clip: bool = False,
+                      max_val: float = 1.0) -> np.ndarray:
+        """film_image_metrics on host arrays: pred, ref float32 [B,H,W,C] (or [H,W,C]), C = 1 or 3 -> float64 [B,4] per image:
+        sum |d| and sum d*d of the float32 difference d, psnr in dB, ssim; NaN where the metric is not in `names`.  clip: pred is
+        clipped to [0,1] first.  eval.device_metrics.compose turns these into the values of eval/metrics.py."""
+        pred = np.ascontiguousarray(pred, dtype=np.float32)
+        ref = np.ascontiguousarray(ref, dtype=np.float32)
+        if pred.ndim == 3:
+            pred, ref = pred[None], ref[None]
+        if pred.ndim != 4 or pred.shape != ref.shape:
+            raise ValueError(f'expected two [B,H,W,C] arrays of equal shape, got {pred.shape} and {ref.shape}')
+        b, h, w, c = pred.shape
+        out = np.empty((b, 4), np.float64)
+        self._check(self._lib.film_image_metrics(self._h, pred.ctypes.data, ref.ctypes.data, b, h, w, c,
+                                                 self._metric_flags(names, clip), float(max_val), out.ctypes.data,
+                                                 FILM_MEM_HOST, None))
+        return out
+
+    def image_metrics_device(self, pred_ptr: int, ref_ptr: int, b: int, h: int, w: int, c: int,
+                             names=('l1', 'l2', 'ssim', 'psnr'), clip: bool = False, max_val: float = 1.0,
+                             stream: Optional[int] = None) -> np.ndarray:
+        """image_metrics on device pointers ([b,h,w,c] float32 each) on `stream` (ordered after the work queued there before);
+        returns the same float64 [b,4] host array once the stream has reached the end of the call."""
+        out = np.empty((int(b), 4), np.float64)
+        self._check(self._lib.film_image_metrics(self._h, ctypes.c_void_p(pred_ptr), ctypes.c_void_p(ref_ptr), int(b), int(h),
+                                                 int(w), int(c), self._metric_flags(names, clip), float(max_val),
+                                                 out.ctypes.data, FILM_MEM_DEVICE, ctypes.c_void_p(stream) if stream else None))
+        return out
 
     def to_uint8_device(self, src_ptr: int, dst_ptr: int, n: int, stream: Optional[int] = None) -> None:
         """film_to_uint8: write_image's quantisation (eval/util.py:51-52) of n device floats into n device bytes, asynchronous."""

@@ -263,6 +263,24 @@ int film_sequence_plan_json(film_t* h, int n_pairs, int tiles_per_frame, int H, 
  * models/film_net/interpolator.py:191-199. */
 int film_get_tap(film_t* h, const char* name, float* dst, int64_t capacity_floats, int64_t dims[4]);
 
+/* The per-image evaluation metrics of the benchmark loop on the device: the reference's losses/losses.py:72-113 (l1, l2, psnr, ssim
+ * of eval/eval_cli.py:160-170), restated in frame-interpolation_amd/eval/metrics.py, whose arithmetic the kernels follow (float32
+ * differences for l1 / l2, float64 differences for psnr, float64 SSIM: 11-tap Gaussian window, sigma 1.5, 'VALID', k1 0.01, k2 0.03).
+ * pred, ref: float32 [B,H,W,C], C = 1 or 3.  `flags`: the FILM_METRIC_* bits of the metrics to compute, + FILM_METRIC_CLIP to clip pred to
+ * [0,1] first (np.clip of the eval loop).  out: HOST array [B][4] of double = {sum |d| (f32 d), sum d*d (f32 d), psnr dB, ssim};
+ * entries not asked for = NaN; psnr = +inf for identical images.  mem_kind / stream as for film_forward (with FILM_MEM_DEVICE pred
+ * and ref are device pointers, out stays a host array).  Synchronises the stream it ran on before returning.  Deterministic: image k
+ * gives the same bits on every run, alone or in a batch, from host or device memory.  Works on any handle with a device: no weights
+ * and no film_finalize needed; the handle owns the scratch.  FILM_ERR_INVALID: B <= 0, H or W <= 0, C not 1 / 3, a NULL pointer,
+ * max_val <= 0, unknown flag bits, H or W < 11 with FILM_METRIC_SSIM (metrics.ssim's refusal). */
+#define FILM_METRIC_L1 1
+#define FILM_METRIC_L2 2
+#define FILM_METRIC_PSNR 4
+#define FILM_METRIC_SSIM 8
+#define FILM_METRIC_CLIP 16 /* clip pred to [0,1] first */
+int film_image_metrics(film_t* h, const float* pred, const float* ref, int B, int H, int W, int C, int flags, double max_val,
+                       double* out, int mem_kind, void* stream);
+
 /* write_image's quantisation on the device (replaces the host loop of the reference's eval/util.py:44-59 write_image,
  * lines 51-52): dst[i] = uint8(clip(src[i] * 255, 0, 255) + 0.5), the same float32 operations in the same order = the same bytes.
  * src (float32) and dst (uint8) are DEVICE pointers to n values; asynchronous on `stream` (NULL: the default stream) of the
