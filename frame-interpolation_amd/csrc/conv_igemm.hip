@@ -203,61 +203,52 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const float* __
   *reinterpret_cast<float4*>(out + (size_t)m * ostride + g * 4) = a;
 }
 
-static hipError_t film_launch_conv_main(const ConvParams& p, int tile, hipStream_t s) {
-  const int shape = (tile & (CONV_TILE_XCD - 1)) + (((tile & CONV_TILE_EXT) && (tile & CONV_TILE_F43)) ? 16 : 0);
-  if ((p.pool_out != nullptr || p.pw_out != nullptr) && !(tile & CONV_TILE_W2D) && !((tile & CONV_TILE_WINO) && (tile & CONV_TILE_F43) && !(tile & CONV_TILE_X3))) return hipErrorInvalidValue;
-  if (tile & CONV_TILE_FOLD4) return (tile & CONV_TILE_XCD) ? launch_fold4<CONV_B_XCD_M>(p, shape, s) : launch_fold4<0>(p, shape, s);   // (the launcher checks the op)
-  if (tile & CONV_TILE_W2D) {
-    if (p.ksize != 3) return hipErrorInvalidValue;   // (fused pool / 1x1: checked by the launcher)
-    return (tile & CONV_TILE_XCD) ? launch_wino2d<CONV_B_XCD_M>(p, shape, s) : launch_wino2d<0>(p, shape, s);
-  }
-#ifndef FILM_EXTRA_FAMILIES
-  // families that are not in this build (the planner never selects them without FILM_EXTRA_FAMILIES)
-  if ((tile & (CONV_TILE_FOLDX3 | CONV_TILE_SPLIT | CONV_TILE_HALO | CONV_TILE_X3)) || ((tile & CONV_TILE_WINO) && !(tile & CONV_TILE_F43)))
-    return hipErrorNotSupported;
-  if (tile & CONV_TILE_WINO) {
-    if (p.ksize != 3) return hipErrorInvalidValue;
-    if (p.pool_out != nullptr && shape < W43_Q16_4x64_T21) return hipErrorInvalidValue;   // fused pool: 64-pixel tiles only
-    if (p.pw_out != nullptr && ((shape != W43_Q16_4x64_N1 && shape != W43_Q16_4x64_N1_P2 && shape != W43_Q8_8x64_N1_P2) || p.Cout != 64 || p.ksplit > 1 ||
-                                p.pool_out != nullptr || p.pw_cout < 1 || p.pw_cout > 4))
-      return hipErrorInvalidValue;   // fused 1x1: a workgroup must hold all 64 channels of its pixels in one wave set
-    return (tile & CONV_TILE_XCD) ? launch_wino43<CONV_B_XCD_M>(p, shape, s) : launch_wino43<0>(p, shape, s);
-  }
-#else
-  if (tile & CONV_TILE_FOLDX3) {
-    if (p.ksize != 2 || p.fold != 2) return hipErrorInvalidValue;
-    return (tile & CONV_TILE_XCD) ? launch_foldx3<CONV_B_XCD_M>(p, shape, s) : launch_foldx3<0>(p, shape, s);
-  }
-  if (tile & CONV_TILE_WINO) {
-    if (p.ksize != 3) return hipErrorInvalidValue;
-    if (tile & CONV_TILE_X3) return (tile & CONV_TILE_XCD) ? launch_winox3<CONV_B_XCD_M>(p, shape, s) : launch_winox3<0>(p, shape, s);
-    if ((tile & CONV_TILE_F43) && p.pool_out != nullptr && shape < W43_Q16_4x64_T21) return hipErrorInvalidValue;   // fused pool: 64-pixel tiles only
-    if (p.pw_out != nullptr && (!(tile & CONV_TILE_F43) || (shape != W43_Q16_4x64_N1 && shape != W43_Q16_4x64_N1_P2 && shape != W43_Q8_8x64_N1_P2) || p.Cout != 64 || p.ksplit > 1 ||
-                                p.pool_out != nullptr || p.pw_cout < 1 || p.pw_cout > 4))
-      return hipErrorInvalidValue;   // fused 1x1: a workgroup must hold all 64 channels of its pixels in one wave set
-    if (tile & CONV_TILE_F43) return (tile & CONV_TILE_XCD) ? launch_wino43<CONV_B_XCD_M>(p, shape, s) : launch_wino43<0>(p, shape, s);
-    return (tile & CONV_TILE_XCD) ? launch_wino<CONV_B_XCD_M>(p, shape, s) : launch_wino<0>(p, shape, s);
-  }
-  if (tile & CONV_TILE_SPLIT) {
-    if (p.ksize != 3) return hipErrorInvalidValue;
-    if (tile & CONV_TILE_X3) return (tile & CONV_TILE_XCD) ? launch_split<CONV_B_XCD_M, 3>(p, shape, s) : launch_split<0, 3>(p, shape, s);
-    return (tile & CONV_TILE_XCD) ? launch_split<CONV_B_XCD_M, 6>(p, shape, s) : launch_split<0, 6>(p, shape, s);
-  }
-  if (tile & CONV_TILE_HALO) {
-    if (p.ksize != 3) return hipErrorInvalidValue;
-    return (tile & CONV_TILE_XCD) ? launch_halo<CONV_B_XCD_M>(p, shape, s) : launch_halo<0>(p, shape, s);
-  }
+static hipError_t film_launch_conv_main(const ConvParams& p, int fam, int tile, hipStream_t s) {
+  const int shape = conv_tile_shape(tile);
+  const bool xcd = tile & CONV_TILE_XCD;
+  if ((p.pool_out != nullptr || p.pw_out != nullptr) && kConvFamily[fam].fused_shape < 0) return hipErrorInvalidValue;
+  switch (fam) {
+    case FAM_BUF: return xcd ? launch_shape<CONV_B_XCD_M>(p, shape, s) : launch_shape<0>(p, shape, s);
+    case FAM_C3: return launch_c3(p, shape, s);
+    case FAM_FOLD4: return xcd ? launch_fold4<CONV_B_XCD_M>(p, shape, s) : launch_fold4<0>(p, shape, s);   // (the launcher checks the op)
+    case FAM_W2D:
+      if (p.ksize != 3) return hipErrorInvalidValue;   // (fused pool / 1x1: checked by the launcher)
+      return xcd ? launch_wino2d<CONV_B_XCD_M>(p, shape, s) : launch_wino2d<0>(p, shape, s);
+    case FAM_W43:
+      if (p.ksize != 3) return hipErrorInvalidValue;
+      if (p.pool_out != nullptr && shape < W43_Q16_4x64_T21) return hipErrorInvalidValue;   // fused pool: 64-pixel tiles only
+      if (p.pw_out != nullptr && ((shape != W43_Q16_4x64_N1 && shape != W43_Q16_4x64_N1_P2 && shape != W43_Q8_8x64_N1_P2) || p.Cout != 64 || p.ksplit > 1 ||
+                                  p.pool_out != nullptr || p.pw_cout < 1 || p.pw_cout > 4))
+        return hipErrorInvalidValue;   // fused 1x1: a workgroup must hold all 64 channels of its pixels in one wave set
+      return xcd ? launch_wino43<CONV_B_XCD_M>(p, shape, s) : launch_wino43<0>(p, shape, s);
+#ifdef FILM_EXTRA_FAMILIES
+    case FAM_HALO:
+      if (p.ksize != 3) return hipErrorInvalidValue;
+      return xcd ? launch_halo<CONV_B_XCD_M>(p, shape, s) : launch_halo<0>(p, shape, s);
+    case FAM_SPLIT6:
+      if (p.ksize != 3) return hipErrorInvalidValue;
+      return xcd ? launch_split<CONV_B_XCD_M, 6>(p, shape, s) : launch_split<0, 6>(p, shape, s);
+    case FAM_SPLIT3:
+      if (p.ksize != 3) return hipErrorInvalidValue;
+      return xcd ? launch_split<CONV_B_XCD_M, 3>(p, shape, s) : launch_split<0, 3>(p, shape, s);
+    case FAM_WINO:
+      if (p.ksize != 3) return hipErrorInvalidValue;
+      return xcd ? launch_wino<CONV_B_XCD_M>(p, shape, s) : launch_wino<0>(p, shape, s);
+    case FAM_WINOX3:
+      if (p.ksize != 3) return hipErrorInvalidValue;
+      return xcd ? launch_winox3<CONV_B_XCD_M>(p, shape, s) : launch_winox3<0>(p, shape, s);
+    case FAM_FOLDX3:
+      if (p.ksize != 2 || p.fold != 2) return hipErrorInvalidValue;
+      return xcd ? launch_foldx3<CONV_B_XCD_M>(p, shape, s) : launch_foldx3<0>(p, shape, s);
 #endif   // FILM_EXTRA_FAMILIES
-  if (tile & CONV_TILE_C3) return launch_c3(p, shape, s);
-  return (tile & CONV_TILE_XCD) ? launch_shape<CONV_B_XCD_M>(p, shape, s) : launch_shape<0>(p, shape, s);
+    default: return hipErrorNotSupported;   // a family this build of the library does not hold (the planner never selects one)
+  }
 }
 
 hipError_t film_launch_conv(const ConvParams& p, int tile, hipStream_t s) {
-  // split-K is implemented by conv_buf_kernel, conv_wino43_kernel, conv_wino2d_kernel and conv_fold4_kernel
-  const bool can_split = !(tile & (CONV_TILE_FOLDX3 | CONV_TILE_SPLIT | CONV_TILE_HALO | CONV_TILE_C3 | CONV_TILE_X3)) &&
-                         (!(tile & CONV_TILE_WINO) || (tile & CONV_TILE_F43));
-  if (p.ksplit > 1 && !can_split) return hipErrorInvalidValue;
-  const hipError_t e = film_launch_conv_main(p, tile, s);
+  const int fam = conv_family_of(tile);
+  if (fam < 0 || (p.ksplit > 1 && !kConvFamily[fam].splitk)) return hipErrorInvalidValue;
+  const hipError_t e = film_launch_conv_main(p, fam, tile, s);
   if (e != hipSuccess || p.ksplit <= 1) return e;
   const long long Mout = (long long)p.M * (p.fold == 3 ? 4 : 1);   // conv_fold4_kernel: M counts the low-resolution pixels, four outputs each
   if (!p.part || (p.Cout & 3) || Mout * (p.Cout >> 2) >= (1ll << 32)) return hipErrorInvalidValue;

@@ -45,9 +45,7 @@ hipError_t launch_op(const OpDesc& op, float* arena, const float* wts, hipStream
         p.seg[i].boff = op.seg[i].boff; p.seg[i].bmod = op.seg[i].bmod; p.seg[i].up = op.seg[i].up;
       }
       p.ksize = op.ksize;
-      p.w = wts + ((op.tile & CONV_TILE_W2D) ? op.w2d_off : (op.tile & CONV_TILE_FOLDX3) ? op.wfx_off
-                   : (op.tile & CONV_TILE_WINO) ? ((op.tile & CONV_TILE_X3) ? op.wx_off : (op.tile & CONV_TILE_F43) ? op.w43_off : op.ww_off) : (op.tile & CONV_TILE_SPLIT) ? op.ws_off
-                   : (op.tile & CONV_TILE_HALO) ? op.wh_off : op.w_off);
+      p.w = wts + op.*kConvFamily[op.family].weights;
       p.bias = wts + op.b_off;
       p.out = mptr(arena, op.out); p.ostride = op.out.stride;
       p.NB = op.NB; p.H = op.H; p.W = op.W; p.Cout = op.Cout; p.Ctot = op.Ctot; p.leaky = op.leaky;
@@ -120,110 +118,101 @@ hipError_t launch_op(const OpDesc& op, float* arena, const float* wts, hipStream
   return hipErrorInvalidValue;
 }
 
-std::vector<int> halo_candidates(int Cout) {
+}  // namespace
+
+// ---- autotune candidates of each kernel family (kConvFamily, film_kernels.h) ------------------------------------------------
+namespace film_internal {
+namespace {
+// every shape with and without the XCD-contiguous block mapping
+std::vector<int> both_maps(ConvFamily f, const std::vector<int>& shapes) {
+  std::vector<int> out;
+  for (int sh : shapes) { out.push_back(conv_tile(f, sh, false)); out.push_back(conv_tile(f, sh, true)); }
+  return out;
+}
+}  // namespace
+
+std::vector<int> tile_candidates(const OpDesc& op) {
+  if (op.Cout % 128 == 0) return both_maps(FAM_BUF, {TILE_128x128, TILE_256x128, TILE_256x64, TILE_128x64, TILE_64x64});
+  if (op.Cout % 64 == 0) return both_maps(FAM_BUF, {TILE_256x64, TILE_128x64, TILE_64x64, TILE_256x32, TILE_128x32});
+  return both_maps(FAM_BUF, {TILE_256x32, TILE_128x32});
+}
+
+// the 3-channel first layer has one kernel (conv_c3_kernel)
+std::vector<int> c3_candidates(const OpDesc&) { return {conv_tile(FAM_C3, TILE_C3_DIRECT, false)}; }
+
+// conv_halo_kernel, and the same shapes on conv_halo_split_kernel (bf16x6 / bf16x3)
+std::vector<int> halo_candidates(const OpDesc& op) {
+  if (op.Cout % 128 == 0) return both_maps(op.family, {HALO_4x64, HALO_4x128, HALO_8x64, HALO_8x128});
+  if (op.Cout % 64 == 0) return both_maps(op.family, {HALO_4x64, HALO_8x64, HALO_4x32, HALO_8x32});
+  return both_maps(op.family, {HALO_8x32, HALO_4x32});
+}
+
+std::vector<int> wino_candidates(const OpDesc& op) {
+  if (op.Cout % 128 == 0) return both_maps(FAM_WINO, {WINO_4x64_W8, WINO_8x64_W16, WINO_2x64, WINO_4x128_W16, WINO_4x128});
+  if (op.Cout % 64 == 0) return both_maps(FAM_WINO, {WINO_4x64_W8, WINO_8x64_W16, WINO_2x64, WINO_4x32});
+  return both_maps(FAM_WINO, {WINO_4x32, WINO_8x32_W8});
+}
+
+std::vector<int> wino43_candidates(const OpDesc& op) {
+  const bool pool = op.out2.buf >= 0, pw = op.pw_out.buf >= 0;
   std::vector<int> shapes;
-  if (Cout % 128 == 0) shapes = {HALO_4x64, HALO_4x128, HALO_8x64, HALO_8x128};
-  else if (Cout % 64 == 0) shapes = {HALO_4x64, HALO_8x64, HALO_4x32, HALO_8x32};
-  else shapes = {HALO_8x32, HALO_4x32};
-  std::vector<int> out;
-  for (int sh : shapes) { out.push_back(sh | CONV_TILE_HALO); out.push_back(sh | CONV_TILE_HALO | CONV_TILE_XCD); }
-  return out;
-}
-
-std::vector<int> wino_candidates(int Cout) {
-  std::vector<int> shapes = Cout % 128 == 0 ? std::vector<int>{WINO_4x64_W8, WINO_8x64_W16, WINO_2x64, WINO_4x128_W16, WINO_4x128}
-                            : Cout % 64 == 0 ? std::vector<int>{WINO_4x64_W8, WINO_8x64_W16, WINO_2x64, WINO_4x32}
-                                             : std::vector<int>{WINO_4x32, WINO_8x32_W8};
-  std::vector<int> out;
-  for (int sh : shapes) { out.push_back(sh | CONV_TILE_WINO); out.push_back(sh | CONV_TILE_WINO | CONV_TILE_XCD); }
-  return out;
-}
-
-// tile id of a Wino43Tile shape: ids >= 16 go into the low four bits with CONV_TILE_EXT set (bit 4 is CONV_TILE_XCD)
-inline int w43_tile(int sh) { return (sh & 15) | (sh >= 16 ? CONV_TILE_EXT : 0) | CONV_TILE_WINO | CONV_TILE_F43; }
-
-std::vector<int> wino43_candidates(int Cout, bool pool = false, bool pw = false) {
-  if (pw) {   // the fused 1x1 needs every channel of a pixel in one workgroup: the NH = 1 tiles at Cout = 64
-    std::vector<int> out;
-    for (int sh : {W43_Q16_4x64_N1, W43_Q16_4x64_N1_P2, W43_Q8_8x64_N1_P2}) {
-      if (!film_w43_shape_built(sh)) continue;
-      out.push_back(w43_tile(sh)); out.push_back(w43_tile(sh) | CONV_TILE_XCD);
-    }
-    return out;
-  }
+  if (pw)   // the fused 1x1 needs every channel of a pixel in one workgroup: the NH = 1 tiles at Cout = 64
+    shapes = {W43_Q16_4x64_N1, W43_Q16_4x64_N1_P2, W43_Q8_8x64_N1_P2};
   // the 64-pixel ("Q16", two workgroups per CU) tiles won every layer of the 1080p plan against the 128-pixel ones
   // (profiles/r02_conv_bench_w43.log); one 128-pixel tile stays in the list for shapes nobody measured.  The 32-pixel x
   // 8-row ("Q8") tiles win on the 480-wide level (15 patches per row exactly: -3..5 %) and, with 32 channels and the weight
   // ring (three workgroups per CU), on the 128 -> 32 layer of flow level 0 (-7 %): profiles/r03_conv_bench_w43.log
-  std::vector<int> shapes = Cout % 64 == 0 ? std::vector<int>{W43_4x64_T21, W43_Q16_4x64_T21, W43_Q16_4x64_T12, W43_Q16_4x32_T11, W43_Q16_4x64_N1,
-                                                              W43_Q16_4x64_T21_P2, W43_Q16_4x64_T12_P2, W43_Q16_4x32_T11_P2, W43_Q16_4x64_N1_P2, W43_Q16_4x32_T11_BG,
-                                                              W43_Q8_8x64_T21_P2, W43_Q8_8x64_T12_P2, W43_Q8_8x64_N1_P2, W43_Q8_8x32_T11_BG, W43_Q8_8x32_T11_P2}
-                                            : std::vector<int>{W43_4x32_T11, W43_Q16_4x32_T11, W43_Q16_4x32_T11_P2, W43_Q16_4x32_T11_BG, W43_Q8_8x32_T11_BG, W43_Q8_8x32_T11_P2};
-  std::vector<int> out;
+  else if (op.Cout % 64 == 0)
+    shapes = {W43_4x64_T21, W43_Q16_4x64_T21, W43_Q16_4x64_T12, W43_Q16_4x32_T11, W43_Q16_4x64_N1,
+              W43_Q16_4x64_T21_P2, W43_Q16_4x64_T12_P2, W43_Q16_4x32_T11_P2, W43_Q16_4x64_N1_P2, W43_Q16_4x32_T11_BG,
+              W43_Q8_8x64_T21_P2, W43_Q8_8x64_T12_P2, W43_Q8_8x64_N1_P2, W43_Q8_8x32_T11_BG, W43_Q8_8x32_T11_P2};
+  else
+    shapes = {W43_4x32_T11, W43_Q16_4x32_T11, W43_Q16_4x32_T11_P2, W43_Q16_4x32_T11_BG, W43_Q8_8x32_T11_BG, W43_Q8_8x32_T11_P2};
+  std::vector<int> keep;
   for (int sh : shapes) {
     if (!film_w43_shape_built(sh)) continue;   // (the default library holds seven of the seventeen tiles)
     if (pool && (sh == W43_4x64_T21 || sh == W43_4x64_T12 || sh == W43_4x32_T11)) continue;   // the fused pool needs a <= 64-pixel tile
-    out.push_back(w43_tile(sh)); out.push_back(w43_tile(sh) | CONV_TILE_XCD);
+    keep.push_back(sh);
   }
-  return out;
+  return both_maps(FAM_W43, keep);
 }
 
 // (H, W: the level.  The square arrangement is a candidate where its tiles pad the level no more than the 8 x 32 ones.)
-std::vector<int> wino2d_candidates(int Cout, bool pw, int H, int W) {
+std::vector<int> wino2d_candidates(const OpDesc& op) {
+  const int H = op.H, W = op.W;
+  const bool pw = op.pw_out.buf >= 0;
   const int64_t pad_r = (int64_t)((W + 31) / 32) * ((H + 7) / 8), pad_s = (int64_t)((W + 15) / 16) * ((H + 15) / 16);
   const bool sq = pad_s <= pad_r;
   std::vector<int> shapes;
-  if (pw || Cout % 64 == 0) { shapes.push_back(W2D_8x64); if (sq) shapes.push_back(W2D_16x64); }
+  if (pw || op.Cout % 64 == 0) { shapes.push_back(W2D_8x64); if (sq) shapes.push_back(W2D_16x64); }
   if (!pw) {   // (the fused 1x1 needs every channel of a pixel in one workgroup)
     shapes.push_back(W2D_8x32); shapes.push_back(W2D_8x32_S2);
     if (sq) { shapes.push_back(W2D_16x32); shapes.push_back(W2D_16x32_S2); }
   }
-  std::vector<int> out;
-  for (int sh : shapes) { out.push_back(sh | CONV_TILE_W2D); out.push_back(sh | CONV_TILE_W2D | CONV_TILE_XCD); }
-  return out;
+  return both_maps(FAM_W2D, shapes);
 }
 
-std::vector<int> fold4_candidates(int Cout) {
-  std::vector<int> out;
-  for (int sh : (Cout % 64 == 0 ? std::vector<int>{F4_4x64, F4_4x32} : std::vector<int>{F4_4x32})) { out.push_back(sh | CONV_TILE_FOLD4); out.push_back(sh | CONV_TILE_FOLD4 | CONV_TILE_XCD); }
-  return out;
+std::vector<int> fold4_candidates(const OpDesc& op) {
+  return both_maps(FAM_FOLD4, op.Cout % 64 == 0 ? std::vector<int>{F4_4x64, F4_4x32} : std::vector<int>{F4_4x32});
 }
 
-std::vector<int> foldx3_candidates(int Cout) {
-  std::vector<int> shapes = Cout % 128 == 0 ? std::vector<int>{FX3_4x64, FX3_8x64, FX3_4x128} : std::vector<int>{FX3_4x64, FX3_8x64};
-  std::vector<int> out;
-  for (int sh : shapes) { out.push_back(sh | CONV_TILE_FOLDX3); out.push_back(sh | CONV_TILE_FOLDX3 | CONV_TILE_XCD); }
-  return out;
+std::vector<int> foldx3_candidates(const OpDesc& op) {
+  return both_maps(FAM_FOLDX3, op.Cout % 128 == 0 ? std::vector<int>{FX3_4x64, FX3_8x64, FX3_4x128} : std::vector<int>{FX3_4x64, FX3_8x64});
 }
 
-std::vector<int> winox3_candidates(int Cout) {
-  std::vector<int> shapes = Cout % 128 == 0 ? std::vector<int>{WX3_4x128_T22, WX3_4x64_T12, WX3_4x64_T21}
-                            : Cout % 64 == 0 ? std::vector<int>{WX3_4x64_T12, WX3_4x64_T21, WX3_4x32_T11}
-                                             : std::vector<int>{WX3_4x32_T11};
-  std::vector<int> out;
-  for (int sh : shapes) { out.push_back(sh | CONV_TILE_WINO | CONV_TILE_X3); out.push_back(sh | CONV_TILE_WINO | CONV_TILE_X3 | CONV_TILE_XCD); }
-  return out;
+std::vector<int> winox3_candidates(const OpDesc& op) {
+  if (op.Cout % 128 == 0) return both_maps(FAM_WINOX3, {WX3_4x128_T22, WX3_4x64_T12, WX3_4x64_T21});
+  if (op.Cout % 64 == 0) return both_maps(FAM_WINOX3, {WX3_4x64_T12, WX3_4x64_T21, WX3_4x32_T11});
+  return both_maps(FAM_WINOX3, {WX3_4x32_T11});
 }
+}  // namespace film_internal
 
-std::vector<int> split_candidates(int Cout, bool x3) {
-  std::vector<int> out;
-  for (int t : halo_candidates(Cout)) out.push_back((t & ~CONV_TILE_HALO) | CONV_TILE_SPLIT | (x3 ? CONV_TILE_X3 : 0));
-  return out;
-}
-
-std::vector<int> tile_candidates(int Cout) {
-  std::vector<int> shapes;
-  if (Cout % 128 == 0) shapes = {TILE_128x128, TILE_256x128, TILE_256x64, TILE_128x64, TILE_64x64};
-  else if (Cout % 64 == 0) shapes = {TILE_256x64, TILE_128x64, TILE_64x64, TILE_256x32, TILE_128x32};
-  else shapes = {TILE_256x32, TILE_128x32};
-  std::vector<int> out;
-  for (int sh : shapes) { out.push_back(sh); out.push_back(sh | CONV_TILE_XCD); }
-  return out;
-}
+namespace {
 
 std::string conv_signature(const OpDesc& op) {
   std::ostringstream o;
-  o << op.NB << 'x' << op.H << 'x' << op.W << ':' << op.Cout << ':' << op.ksize << ':' << op.out.stride << ':' << op.c3 << ':' << op.halo << ':' << op.split << ':' << op.wino << ':' << op.fold << ':' << op.ksplit << ':' << (op.out2.buf >= 0) << ':' << op.pw_cout;
+  const FamilyCodes fc = family_codes(op.family);
+  o << op.NB << 'x' << op.H << 'x' << op.W << ':' << op.Cout << ':' << op.ksize << ':' << op.out.stride << ':' << fc.c3 << ':' << fc.halo << ':' << fc.split << ':' << fc.wino << ':' << op.fold << ':' << op.ksplit << ':' << (op.out2.buf >= 0) << ':' << op.pw_cout;
   for (int i = 0; i < op.nseg; ++i)
     o << '|' << op.seg[i].v.C << ',' << op.seg[i].v.stride << ',' << op.seg[i].up << ',' << op.seg[i].bmod;
   return o.str();
@@ -234,14 +223,7 @@ hipError_t launch_op(const OpDesc& op, float* arena, const float* wts, hipStream
 // Measure, don't guess: every distinct conv shape of a plan is timed once with each tile shape that fits
 // its Cout (random activations, the real weights) and keeps the fastest.  The choice cannot change the
 // results: every output element is the same k-ordered fma chain whatever the tile.
-std::vector<int> conv_candidates(const OpDesc& op) {
-  std::vector<int> cands = op.fold == 3 ? fold4_candidates(op.Cout) : (op.fold == 2 && op.split == 2) ? foldx3_candidates(op.Cout) : op.wino == 4 ? wino2d_candidates(op.Cout, op.pw_out.buf >= 0, op.H, op.W) : op.wino == 3 ? wino43_candidates(op.Cout, op.out2.buf >= 0, op.pw_out.buf >= 0) : op.wino == 2 ? winox3_candidates(op.Cout) : op.wino ? wino_candidates(op.Cout) : op.split ? split_candidates(op.Cout, op.split == 2) : op.halo ? halo_candidates(op.Cout) : tile_candidates(op.Cout);
-  if (op.c3) {   // the 3-channel first layer has one kernel (conv_c3_kernel)
-    cands.clear();
-    cands.push_back(TILE_C3_DIRECT | CONV_TILE_C3);
-  }
-  return cands;
-}
+std::vector<int> conv_candidates(const OpDesc& op) { return kConvFamily[op.family].candidates(op); }
 
 int autotune_plan(film_t* h, Plan* P) {
   bool need = false;
@@ -312,7 +294,7 @@ int autotune_plan(film_t* h, Plan* P) {
         if (timed[c].first < best_ms) { best_ms = timed[c].first; best = timed[c].second; }
       // conv_wino2d_kernel: a 64-channel tile within 2 % of the fastest wins - it reads its input patch half as often (45.2 -> 40.2
       // GB of fabric reads per 1080p forward with the tile forced, same step time: profiles/r04_w2d_tile64_ab.log)
-      if (op.wino == 4 && !film_w2d_64(best & 15)) {
+      if (op.family == FAM_W2D && !film_w2d_64(best & 15)) {
         float ms64 = 1e30f;
         int t64 = -1;
         for (size_t c = 0; c < std::max<size_t>(nfin, 1) && c < timed.size(); ++c)
@@ -404,27 +386,17 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
       if (trc) { free_plan(P.get()); return trc; }
     }
   }
-  if (h->opt_w43_shape >= 0)   // test knob: one tile shape for every F(4,3) op it fits (same bits as any other, by construction)
+  // test knobs: one tile shape for every F(4,3) / nested-Winograd / conv_fold4_kernel op it fits (same bits as any other, by construction)
+  const std::pair<ConvFamily, int> forced[] = {{FAM_W43, h->opt_w43_shape}, {FAM_W2D, h->opt_w2d_shape}, {FAM_FOLD4, h->opt_fold4_shape}};
+  for (const auto& [fam, shape] : forced) {
+    if (shape < 0) continue;
     for (OpDesc& op : P->ops) {
-      if (op.kind != OP_CONV || op.wino != 3) continue;
+      if (op.kind != OP_CONV || op.family != fam) continue;
       const std::vector<int> cands = conv_candidates(op);
-      const int want = w43_tile(h->opt_w43_shape) | CONV_TILE_XCD;
+      const int want = conv_tile(fam, shape, true);
       if (std::find(cands.begin(), cands.end(), want) != cands.end()) op.tile = want;
     }
-  if (h->opt_w2d_shape >= 0)   // the same for the nested-Winograd tiles
-    for (OpDesc& op : P->ops) {
-      if (op.kind != OP_CONV || op.wino != 4) continue;
-      const std::vector<int> cands = conv_candidates(op);
-      const int want = h->opt_w2d_shape | CONV_TILE_W2D | CONV_TILE_XCD;
-      if (std::find(cands.begin(), cands.end(), want) != cands.end()) op.tile = want;
-    }
-  if (h->opt_fold4_shape >= 0)   // ... and for conv_fold4_kernel's
-    for (OpDesc& op : P->ops) {
-      if (op.kind != OP_CONV || op.fold != 3) continue;
-      const std::vector<int> cands = conv_candidates(op);
-      const int want = h->opt_fold4_shape | CONV_TILE_FOLD4 | CONV_TILE_XCD;
-      if (std::find(cands.begin(), cands.end(), want) != cands.end()) op.tile = want;
-    }
+  }
   P->last_use = ++h->tick;
   *out = P.get();
   h->plans.push_back(std::move(P));
@@ -579,9 +551,8 @@ int film_set_option(film_t* h, const char* key, int64_t value) {
   }
   else if (!strcmp(key, "winograd")) {
     if (value < 0 || value > 3) return fail(h, FILM_ERR_INVALID, "winograd: 0, 1, 2 or 3");
-#ifndef FILM_EXTRA_FAMILIES
-    if (value == 2) return fail(h, FILM_ERR_INVALID, "winograd = 2 (F(2,3) kernel on every level) needs a library built with FILM_EXTRA_FAMILIES=1");
-#endif
+    if (value == 2 && !conv_family_built(FAM_WINO))
+      return fail(h, FILM_ERR_INVALID, "winograd = 2 (F(2,3) kernel on every level) needs a library built with FILM_EXTRA_FAMILIES=1");
     if ((int)value != h->opt_wino) {  // plans carry the kernel choice: drop them
       if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
       for (auto& p : h->plans) free_plan(p.get());
@@ -591,9 +562,7 @@ int film_set_option(film_t* h, const char* key, int64_t value) {
     }
   }
   else if (!strcmp(key, "halo_all")) {
-#ifndef FILM_EXTRA_FAMILIES
-    if (value) return fail(h, FILM_ERR_INVALID, "halo_all needs a library built with FILM_EXTRA_FAMILIES=1");
-#endif
+    if (value && !conv_family_built(FAM_HALO)) return fail(h, FILM_ERR_INVALID, "halo_all needs a library built with FILM_EXTRA_FAMILIES=1");
     if ((value != 0) != (h->opt_halo_all != 0)) {  // plans carry the kernel choice: drop them
       if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
       for (auto& p : h->plans) free_plan(p.get());
@@ -684,9 +653,8 @@ int film_set_option(film_t* h, const char* key, int64_t value) {
   }
   else if (!strcmp(key, "precision")) {
     if (value != 0 && value != 1 && value != 2) return fail(h, FILM_ERR_INVALID, "precision: 0 (f32), 1 (bf16x6) or 2 (bf16x3)");
-#ifndef FILM_EXTRA_FAMILIES
-    if (value) return fail(h, FILM_ERR_INVALID, "precision %d (bf16 split modes) needs a library built with FILM_EXTRA_FAMILIES=1; this build runs fp32 MFMA only", (int)value);
-#endif
+    if (value && !conv_family_built(FAM_SPLIT6))
+      return fail(h, FILM_ERR_INVALID, "precision %d (bf16 split modes) needs a library built with FILM_EXTRA_FAMILIES=1; this build runs fp32 MFMA only", (int)value);
     if ((int)value != h->opt_precision) {  // plans carry the kernel choice: drop them
       if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); (void)hipDeviceSynchronize(); }
       for (auto& p : h->plans) free_plan(p.get());

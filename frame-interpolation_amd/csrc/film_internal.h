@@ -59,36 +59,25 @@ struct SegDesc {
   int boff = 0, bmod = 0, up = 0;
 };
 
-struct OpDesc {
+// conv ops: the weight copies of the layer (ConvWeights; w_off is what conv_buf_kernel reads, = wf4_off when fold == 3), `family` the kernel
+struct OpDesc : ConvWeights {
   int kind = 0;
   std::string tag;
   // conv
   SegDesc seg[FILM_MAX_SEG];
   int nseg = 0;
   int ksize = 1, leaky = 0, Cout = 0, Ctot = 0, tile = 0;
-  int c3 = 0;                         // first-layer mode of the conv kernel (3-channel image input)
-  int64_t w_off = 0, b_off = 0;
+  ConvFamily family = FAM_BUF;        // conv: the kernel family (Planner::conv); tile carries its flag bits
+  int64_t b_off = 0;
   int64_t w2_off = 0, b2_off = 0;     // flow_head: second 1x1 conv
-  int64_t wh_off = -1;                // conv: the layer's conv_halo_kernel weight copy (-1: none)
-  int64_t ws_off = -1;                // conv: the layer's bf16x6 weight copy
   int ksplit = 1;                     // conv (conv_buf_kernel): split-K factor, partial sums at part_off (film_kernels.h)
   int64_t part_off = 0;
   int fold = 0, py = 0, px = 0;       // conv: sub-pixel phase of a folded upsample + 2x2 conv (H, W = low-res grid)
   int ftaps = 0; int tdy[4] = {0, 0, 0, 0}, tdx[4] = {0, 0, 0, 0};
   int64_t fold_woff[4] = {0, 0, 0, 0};  // fold == 2: weight offset of phase q relative to w_off
-  int64_t ww_off = -1;                // conv: the layer's Winograd F(2,3) weight copy
-  int64_t wx_off = -1;                // conv: ... and its 2-plane bf16 split (precision mode bf16x3, conv_winox3_kernel)
-  int64_t w43_off = -1;               // conv: the layer's Winograd F(4,3) weight copy (conv_wino43_kernel)
-  int64_t w2d_off = -1;               // conv: the layer's nested F(4,3) x F(2,3) weight copy (conv_wino2d_kernel; deep-K layers only)
-  int64_t wfx_off = -1;               // conv: phase-summed weights of a folded 2x2 layer as bf16 hi / mid (conv_foldx3_kernel)
-  int64_t wf4_off = -1;               // conv: the difference-form planes S, Sx, Sy, W11 of a folded 2x2 layer (conv_fold4_kernel; = w_off when fold == 3)
-  int wino = 0;                       // conv: 1 = runs on conv_wino_kernel, 2 = on conv_winox3_kernel (precision bf16x3), 3 = conv_wino43_kernel,
-                                      //       4 = conv_wino2d_kernel (nested F(4,3) x F(2,3))
-  int split = 0;                      // conv: runs on conv_halo_split_kernel (precision mode bf16x6)
   int lane = 0;                       // graph replay: 0 = main stream, 1 = side stream (small / HBM-bound work)
   std::vector<int> xdeps;             // ops on the OTHER lane this op must wait for (from the buffer overlap analysis)
   bool signal = false;                // some op on the other lane waits for this one
-  int halo = 0;                       // conv: runs on conv_halo_kernel (decided by shape, see Planner::conv)
   // generic views
   View in, in2, out;
   // warp: the fused sixteen miscellaneous channels of an aligned level (t = 0.5 stage): img_in = both images [2 NB][H][W][3],
@@ -105,7 +94,7 @@ struct OpDesc {
   double bytes = 0;  // algorithmic bytes (read once + write once)
 };
 
-struct LayerPack {
+struct LayerPack : ConvWeights {   // (+ the offsets of its weight layouts)
   std::string name;
   int kh, kw, cin, cout;     // reference shape
   std::vector<int> perm;     // internal input channel -> reference input channel, -1 = zero row
@@ -113,22 +102,9 @@ struct LayerPack {
   // layers run by the MFMA conv kernel (Cout % 32 == 0) are packed K-contiguous per output channel:
   // [Cout][kh*kw*ctot] with k = tap*ctot + channel; the 1x1 heads keep [ctot][Cout]
   bool kmajor() const { return !c3 && cout % 32 == 0; }
-  int64_t w_off = 0, b_off = 0;
-  int64_t wh_off = -1;       // 3x3 K-major layers: second copy packed for conv_halo_kernel, [Cout][ctot/16][9][16]
+  int64_t b_off = 0;
   int64_t wf_off = -1;       // 2x2 layers behind a nearest upsample: the four sub-pixel phases, pre-summed weights,
                              //     phase (py,px) at wf_off + fold_phase_off(py,px): [Cout][ntaps_p * ctot], 9*ctot*cout in all
-  int64_t ww_off = -1;       // ... the F(2,3)-along-x transformed copy for conv_wino_kernel, [Cout][ctot/8][12][8]
-  int64_t wfx_off = -1;      // 2x2 layers after an upsample: the phase-summed weights as bf16 hi / mid for conv_foldx3_kernel,
-                             //     [Cout][ctot/16][9 (tap, phase) steps][plane][16] bf16
-  int64_t wf4_off = -1;      // 2x2 layers behind a nearest upsample: the four planes of the difference form (conv_fold4_impl.h) S = ((W00 + W01) + W10) +
-                             //     W11, Sx = W01 + W11, Sy = W10 + W11, W11 as [Cout/32][ctot/8][plane 4][K half][32][4]: 4*ctot*cout in all
-  int64_t w43_off = -1;      // ... the F(4,3)-along-x transformed copy for conv_wino43_kernel, [Cout][ctot/8][3 dy][6 nu][8]
-  int64_t w2d_off = -1;      // has_w2d layers: the nested F(4,3)x x F(2,3)y copy for conv_wino2d_kernel,
-                             //     [Cout/32][ctot/8][mu 4][nu 6][K half][32][4] (24 values per (ci, co): 2.67x the kernel)
-  int64_t wx_off = -1;       // ... and the transformed copy split into bf16 hi / mid for conv_winox3_kernel,
-                             //     [Cout][ctot/16][dy][j][h][plane][16] bf16 (nu = 2h + j)
-  int64_t ws_off = -1;       // ... and the bf16x6 copy for conv_halo_split_kernel, [Cout][ctot/16][9][3][16] bf16
-                             //     (offset in floats; 1.5 floats per weight)
   bool has_halo() const { return kmajor() && kh == 3 && kw == 3; }
   bool has_fold() const { return kmajor() && kh == 2 && kw == 2; }
   // conv_wino2d_kernel against the best 1-D F(4,3) tile of the same run (tools/w2d_bench.hip, profiles/r04_w2d_vs_w43.log): 16-30 %
@@ -255,6 +231,25 @@ std::string predictor_prefix(const film_config& c, int level);   // pyramid_flow
 int predictor_index(const film_config& c, int level);
 int validate_config(film_t* h, const film_config& c);
 void build_layers(film_t* h);
+
+// The per-op codes plan_json and the tune-cache signatures have always carried for a conv op's family: "c3", "halo", "split"
+// (1 bf16x6, 2 bf16x3) and "wino" (1 F(2,3), 2 bf16x3 F(2,3), 3 F(4,3), 4 nested F(4,3) x F(2,3)).
+struct FamilyCodes { int c3 = 0, halo = 0, split = 0, wino = 0; };
+inline FamilyCodes family_codes(ConvFamily f) {
+  FamilyCodes c;
+  switch (f) {
+    case FAM_C3: c.c3 = 1; break;
+    case FAM_HALO: c.halo = 1; break;
+    case FAM_SPLIT6: c.split = 1; break;
+    case FAM_SPLIT3: case FAM_FOLDX3: c.split = 2; break;
+    case FAM_WINO: c.wino = 1; break;
+    case FAM_WINOX3: c.wino = 2; break;
+    case FAM_W43: c.wino = 3; break;
+    case FAM_W2D: c.wino = 4; break;
+    default: break;
+  }
+  return c;
+}
 
 // ---- film_planner.cpp
 int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles = 0);   // fills P->bufs / ops / arena_floats for (B, H, W) (tiles > 0: sequence plan)

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #define FILM_MAX_SEG 4
 #define FILM_BK 16  // channels per K-step of the implicit GEMM; every concat segment is a multiple
 
@@ -236,14 +238,17 @@ enum Wino43Tile { W43_4x64_T21 = 0, W43_4x64_T12 = 1, W43_4x32_T11 = 2, W43_Q16_
                   /* ids >= 16 carry CONV_TILE_EXT in the tile id (shape = (tile & 15) + 16).  The 32-channel Q8 tile WITH the
                      weight ring: 48 KB of LDS, 152 VGPRs -> three workgroups per CU (flow level 0 conv_0: -7 % against the BG tile) */
                   W43_Q8_8x32_T11_P2 = 16 };
+// this build of the library holds the opt-in kernel families (and Wino43Tile shapes): FILM_EXTRA_FAMILIES=1 (Makefile EXTRA=1)
+#ifdef FILM_EXTRA_FAMILIES
+constexpr bool kExtraFamilies = true;
+#else
+constexpr bool kExtraFamilies = false;
+#endif
 // the Wino43Tile shapes this build of the library instantiates (conv_igemm.hip): all of them with FILM_EXTRA_FAMILIES, seven without
 static inline bool film_w43_shape_built(int sh) {
-#ifdef FILM_EXTRA_FAMILIES
-  return sh >= 0 && sh <= W43_Q8_8x32_T11_P2;
-#else
+  if (kExtraFamilies) return sh >= 0 && sh <= W43_Q8_8x32_T11_P2;
   return sh == W43_Q16_4x64_T21_P2 || sh == W43_Q16_4x32_T11_P2 || sh == W43_Q16_4x64_N1_P2 || sh == W43_Q8_8x64_T21_P2 || sh == W43_Q8_8x64_N1_P2 ||
          sh == W43_Q8_8x32_T11_BG || sh == W43_Q8_8x32_T11_P2;
-#endif
 }
 // conv_wino2d_kernel tiles (CONV_TILE_W2D): one 32-unit MFMA tile (unit = 2 rows x 4 pixels; 8 rows x 32 pixels) x output channels;
 // 64 channels = 8 waves (one workgroup per CU), 32 channels = 4 waves (two per CU).  Same sums: the autotuner picks freely.
@@ -282,6 +287,83 @@ static inline TileShape film_tile_shape(int tile) {
     default: return {128, 32};
   }
 }
+
+// ---- Convolution kernel families --------------------------------------------------------------------------------------------
+// Every convolution op runs on one family (kernels: see the CONV_TILE_* flags above); its tile id = the family's flag bits | shape
+// index [| CONV_TILE_XCD].  Tile ids are an external format (plan and profile JSON, tune caches): the bits above do not change.
+enum ConvFamily { FAM_BUF /* also fold = 2 */, FAM_C3, FAM_W2D, FAM_W43, FAM_FOLD4 /* fold = 3 */,        // the default library
+                  FAM_HALO, FAM_SPLIT6, FAM_SPLIT3, FAM_WINO, FAM_WINOX3, FAM_FOLDX3 /* fold = 2 */,       // FILM_EXTRA_FAMILIES only
+                  CONV_FAMILIES };
+constexpr int CONV_TILE_FAMILY = CONV_TILE_C3 | CONV_TILE_HALO | CONV_TILE_SPLIT | CONV_TILE_WINO | CONV_TILE_X3 | CONV_TILE_FOLDX3 |
+                                 CONV_TILE_F43 | CONV_TILE_W2D | CONV_TILE_FOLD4;
+
+// Float offsets into the packed weights of the layouts a convolution kernel reads (film_layers.cpp), -1: the layer has none.
+// LayerPack and OpDesc (film_internal.h) both carry them; a family's row names the one its kernel reads.
+struct ConvWeights {
+  int64_t w_off = 0;      // K-major [Cout][kh*kw*ctot] (first layer: [48][Cout]); an op's conv_buf_kernel weights (fold = 2: the phases)
+  int64_t wh_off = -1;    // 3x3 K-major layers: the conv_halo_kernel copy, [Cout][ctot/16][9][16]
+  int64_t ws_off = -1;    // ... the bf16x6 copy for conv_halo_split_kernel, [Cout][ctot/16][9][3][16] bf16 (offset in floats; 1.5 floats per weight)
+  int64_t ww_off = -1;    // ... the F(2,3)-along-x transformed copy for conv_wino_kernel, [Cout][ctot/8][12][8]
+  int64_t wx_off = -1;    // ... and that copy split into bf16 hi / mid for conv_winox3_kernel, [Cout][ctot/16][dy][j][h][plane][16] bf16 (nu = 2h + j)
+  int64_t w43_off = -1;   // ... the F(4,3)-along-x transformed copy for conv_wino43_kernel, [Cout][ctot/8][3 dy][6 nu][8]
+  int64_t w2d_off = -1;   // LayerPack::has_w2d() layers: the nested F(4,3)x x F(2,3)y copy for conv_wino2d_kernel,
+                          //     [Cout/32][ctot/8][mu 4][nu 6][K half][32][4] (24 values per (ci, co): 2.67x the kernel)
+  int64_t wfx_off = -1;   // 2x2 layers behind a nearest upsample: the phase-summed weights as bf16 hi / mid for conv_foldx3_kernel,
+                          //     [Cout][ctot/16][9 (tap, phase) steps][plane][16] bf16
+  int64_t wf4_off = -1;   // ... the four planes of the difference form (conv_fold4_impl.h) S = ((W00 + W01) + W10) + W11, Sx = W01 + W11,
+                          //     Sy = W10 + W11, W11 as [Cout/32][ctot/8][plane 4][K half][32][4]: 4*ctot*cout in all
+};
+
+namespace film_internal {   // the autotune candidates of each family (film_engine.cpp)
+struct OpDesc;
+std::vector<int> tile_candidates(const OpDesc&), c3_candidates(const OpDesc&), wino2d_candidates(const OpDesc&), wino43_candidates(const OpDesc&),
+    fold4_candidates(const OpDesc&), halo_candidates(const OpDesc&), wino_candidates(const OpDesc&), winox3_candidates(const OpDesc&),
+    foldx3_candidates(const OpDesc&);
+}  // namespace film_internal
+struct ConvFamilyRow {
+  int flags;                            // tile-id bits: tile & CONV_TILE_FAMILY
+  int64_t ConvWeights::* weights;       // the weight copy its kernel reads
+  int groups;                           // weight layout groups [0, groups) that copy needs packed (film_layers.cpp, build_layers)
+  bool splitk;                          // implements ConvParams::ksplit
+  bool in_default;                      // in the default library (else FILM_EXTRA_FAMILIES only)
+  int fused_shape;                      // >= 0: fuses a 2x2 pool / 1x1 head into its epilogue; this shape carries the RGB head (Cout = 64)
+  std::vector<int> (*candidates)(const film_internal::OpDesc&);
+  int (*default_shape)(int Cout, int64_t M);   // shape before autotuning, M = output pixels of the launch
+};
+
+// default shapes: conv_buf_kernel's largest tile that still gives >= 768 workgroups, conv_halo_split_kernel's
+constexpr int conv_buf_shape(int Cout, int64_t M) {
+  auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * (Cout / bn); };
+  if (Cout % 128 == 0) return blocks(128, 128) >= 768 ? TILE_128x128 : TILE_64x64;
+  if (Cout % 64 == 0) return blocks(256, 64) >= 768 ? TILE_256x64 : TILE_64x64;
+  return blocks(256, 32) >= 768 ? TILE_256x32 : TILE_128x32;
+}
+constexpr int film_split_shape(int Cout, int64_t) { return Cout % 128 == 0 ? HALO_8x128 : Cout % 64 == 0 ? HALO_4x64 : HALO_8x32; }
+
+inline constexpr ConvFamilyRow kConvFamily[CONV_FAMILIES] = {
+  /* FAM_BUF    */ {0, &ConvWeights::w_off, 1, true, true, -1, film_internal::tile_candidates, conv_buf_shape},
+  /* FAM_C3     */ {CONV_TILE_C3, &ConvWeights::w_off, 1, false, true, -1, film_internal::c3_candidates, [](int, int64_t) -> int { return TILE_C3_DIRECT; }},
+  /* FAM_W2D    */ {CONV_TILE_W2D, &ConvWeights::w2d_off, 1, true, true, W2D_8x64, film_internal::wino2d_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? W2D_8x64 : W2D_8x32; }},
+  /* FAM_W43    */ {CONV_TILE_WINO | CONV_TILE_F43, &ConvWeights::w43_off, 1, true, true, W43_Q16_4x64_N1_P2, film_internal::wino43_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? W43_Q16_4x64_T21_P2 : W43_Q16_4x32_T11_P2; }},
+  /* FAM_FOLD4  */ {CONV_TILE_FOLD4, &ConvWeights::wf4_off, 1, true, true, -1, film_internal::fold4_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? F4_4x64 : F4_4x32; }},
+  /* FAM_HALO   */ {CONV_TILE_HALO, &ConvWeights::wh_off, 3, false, false, -1, film_internal::halo_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? HALO_4x64 : HALO_8x32; }},
+  /* FAM_SPLIT6 */ {CONV_TILE_SPLIT, &ConvWeights::ws_off, 4, false, false, -1, film_internal::halo_candidates, film_split_shape},
+  /* FAM_SPLIT3 */ {CONV_TILE_SPLIT | CONV_TILE_X3, &ConvWeights::ws_off, 4, false, false, -1, film_internal::halo_candidates, film_split_shape},
+  /* FAM_WINO   */ {CONV_TILE_WINO, &ConvWeights::ww_off, 2, false, false, -1, film_internal::wino_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? WINO_4x64_W8 : WINO_4x32; }},
+  /* FAM_WINOX3 */ {CONV_TILE_WINO | CONV_TILE_X3, &ConvWeights::wx_off, 4, false, false, -1, film_internal::winox3_candidates, [](int c, int64_t) -> int { return c % 128 == 0 ? WX3_4x128_T22 : c % 64 == 0 ? WX3_4x64_T12 : WX3_4x32_T11; }},
+  /* FAM_FOLDX3 */ {CONV_TILE_FOLDX3, &ConvWeights::wfx_off, 4, false, false, -1, film_internal::foldx3_candidates, [](int, int64_t) -> int { return FX3_4x64; }},
+};
+
+constexpr bool conv_family_built(int f) { return kConvFamily[f].in_default || kExtraFamilies; }
+constexpr int conv_family_of(int tile) {   // -1: no family
+  for (int f = 0; f < CONV_FAMILIES; ++f) if ((tile & CONV_TILE_FAMILY) == kConvFamily[f].flags) return f;
+  return -1;
+}
+// tile id of a shape of family f, and back (Wino43Tile shapes >= 16 go into the low four bits with CONV_TILE_EXT: bit 4 is CONV_TILE_XCD)
+constexpr int conv_tile(int f, int shape, bool xcd) { return kConvFamily[f].flags | (shape & 15) | (shape >= 16 ? CONV_TILE_EXT : 0) | (xcd ? CONV_TILE_XCD : 0); }
+constexpr int conv_tile_shape(int tile) { return (tile & 15) + ((tile & CONV_TILE_EXT) ? 16 : 0); }
+// the tile an op of family f starts from (and keeps without autotuning)
+constexpr int conv_default_tile(int f, int Cout, int64_t M) { return conv_tile(f, kConvFamily[f].default_shape(Cout, M), true); }
 
 hipError_t film_launch_conv(const ConvParams& p, int tile, hipStream_t s);
 hipError_t film_launch_conv_pw(const ConvPwParams& p, hipStream_t s);

@@ -136,7 +136,7 @@ void build_layers(film_t* h) {
     L.w_off = off; off += L.packed_rows() * L.cout; al();
     L.b_off = off; off += L.cout; al();
     if (L.has_fold()) { L.wf_off = off; off += (int64_t)9 * L.ctot() * L.cout; al(); }
-    if (L.has_fold() && L.ctot() % 16 == 0) { L.wf4_off = off; off += (int64_t)4 * L.ctot() * L.cout; al(); }
+    if (L.has_fold() && L.ctot() % 16 == 0 && L.cout % 32 == 0) { L.wf4_off = off; off += (int64_t)4 * L.ctot() * L.cout; al(); }
     if (L.has_halo()) { L.w43_off = off; off += L.packed_rows() * L.cout / 9 * 18; al(); }
     if (L.has_w2d()) { L.w2d_off = off; off += L.packed_rows() * L.cout / 9 * 24; al(); }
   }

@@ -70,23 +70,20 @@ struct Planner {
     return v;
   }
 
-  static int choose_tile(int64_t M, int Cout) {
-    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * (Cout / bn); };
-    int shape;
-    if (Cout % 128 == 0) shape = blocks(128, 128) >= 768 ? TILE_128x128 : TILE_64x64;
-    else if (Cout % 64 == 0) shape = blocks(256, 64) >= 768 ? TILE_256x64 : TILE_64x64;
-    else shape = blocks(256, 32) >= 768 ? TILE_256x32 : TILE_128x32;
-    return shape | CONV_TILE_XCD;
-  }
-
-  static int choose_halo_tile(int Cout) {
-    return (Cout % 64 == 0 ? HALO_4x64 : HALO_8x32) | CONV_TILE_HALO | CONV_TILE_XCD;
-  }
-
   // the weight layout group a kernel family reads must be packed (and on the device) before the plan can run
   void need_groups(int n) {
     if (!h->finalized || n <= h->groups_packed) return;
     if (film_ensure_groups_(h, n) != FILM_OK) { bad = true; bad_msg = h->err; }
+  }
+
+  // The op runs on family `fam` - on conv_buf_kernel where this build of the library lacks it (the default library: film_set_option
+  // refuses the options that ask for the opt-in families; a layer the nested / F(4,3) kernels cannot take runs on the general kernel).
+  // M: the output pixels the default conv_buf_kernel tile is chosen for.
+  void set_family(OpDesc& op, ConvFamily fam, int64_t M) {
+    if (!conv_family_built(fam)) fam = FAM_BUF;
+    op.family = fam;
+    need_groups(kConvFamily[fam].groups);
+    op.tile = conv_default_tile(fam, op.Cout, M);
   }
 
   void conv(const std::string& tag, const std::string& layer, std::vector<SegDesc> segs, View out, int NB, int H,
@@ -103,7 +100,8 @@ struct Planner {
       bad = true;
       bad_msg = "planner: channel mismatch at " + op.tag;
     }
-    op.w_off = L.w_off; op.b_off = L.b_off; op.wh_off = L.wh_off; op.ws_off = L.ws_off; op.ww_off = L.ww_off; op.wx_off = L.wx_off; op.wfx_off = L.wfx_off; op.wf4_off = L.wf4_off; op.w43_off = L.w43_off; op.w2d_off = L.w2d_off;
+    static_cast<ConvWeights&>(op) = L;
+    op.b_off = L.b_off;
     if (h->opt_fold && L.wf_off >= 0 && op.nseg == 1 && segs[0].up && !(H & 1) && !(W & 1)) {
       // nearest x2 + 2x2 'same' conv == four phase convolutions on the low-resolution input: kernel tap (dy, dx) of
       // output (2y+py, 2x+px) reads input ((2y+py+dy)>>1, (2x+px+dx)>>1) = (y + (py&dy), x + (px&dx)), so phase
@@ -119,20 +117,20 @@ struct Planner {
       f.w_off = L.wf_off;
       int64_t rel = 0;
       for (int q = 0; q < 4; ++q) { f.fold_woff[q] = rel; rel += (int64_t)((q >> 1) + 1) * ((q & 1) + 1) * ctot * L.cout; }
-      f.halo = f.split = f.wino = 0;
-      f.tile = choose_tile((int64_t)NB * f.H * f.W * 2, L.cout);
-      if (h->opt_precision == 2 && L.wfx_off >= 0 && L.cout % 64 == 0 && ((int64_t)f.H * f.W >= 2048 || h->opt_halo_all)) {
-        f.split = 2;   // precision mode bf16x3: one halo-staged patch, nine (tap, phase) steps (conv_foldx3_kernel)
-        f.tile = FX3_4x64 | CONV_TILE_FOLDX3 | CONV_TILE_XCD;
-        need_groups(4);
-      }
-      if (f.split == 0 && h->opt_fold4 && h->opt_precision == 0 && L.wf4_off >= 0 && segs[0].v.stride % 4 == 0 && segs[0].v.off % 4 == 0) {
-        // the difference form (conv_fold4_impl.h): four GEMMs over K on I, Dx, Dy, Dxy - 4 multiplies per low-resolution pixel, not 9.
-        // Its own summation family, chosen by the layer alone (every folded layer whose channels come in sixteens)
+      ConvFamily fam = FAM_BUF;
+      if (h->opt_precision == 2 && L.wfx_off >= 0 && L.cout % 64 == 0 && ((int64_t)f.H * f.W >= 2048 || h->opt_halo_all))
+        fam = FAM_FOLDX3;   // precision mode bf16x3: one halo-staged patch, nine (tap, phase) steps (conv_foldx3_kernel)
+      // the difference form (conv_fold4_impl.h): four GEMMs over K on I, Dx, Dy, Dxy - 4 multiplies per low-resolution pixel, not 9.
+      // Its own summation family, chosen by the layer alone (every folded layer whose channels come in sixteens).  conv_fold4_launch's
+      // layout checks: 16-byte aligned input and output pixels, 32-channel blocks, eight output rows in 32-bit offsets.
+      else if (h->opt_fold4 && h->opt_precision == 0 && L.wf4_off >= 0 && segs[0].v.stride % 4 == 0 && segs[0].v.off % 4 == 0 &&
+               out.off % 4 == 0 && out.stride % 4 == 0 && L.cout % 32 == 0 && (int64_t)16 * f.W * std::max(out.stride, L.cout) < (1ll << 31))
+        fam = FAM_FOLD4;
+      set_family(f, fam, (int64_t)NB * f.H * f.W * 2);
+      if (f.family == FAM_FOLD4) {
         f.fold = 3;
         f.w_off = L.wf4_off;
         for (int q = 0; q < 4; ++q) f.fold_woff[q] = 0;
-        f.tile = (L.cout % 64 == 0 ? F4_4x64 : F4_4x32) | CONV_TILE_FOLD4 | CONV_TILE_XCD;
         // split-K like the nested kernel's (below), for deep K on a TINY level: the decoder's coarsest layer of a 256x256 pair (K = 1936 on
         // 16x16 low-resolution pixels = 4 pixel tiles x 16 channel blocks: 64 workgroups of 242 chunks) 0.139 -> 0.048 ms with four K
         // ranges; on the 36x60 level of a 1080p tile (1152 workgroups) every split LOSES (0.589 -> 0.61-0.64 ms), eight 448x256 pairs
@@ -166,14 +164,14 @@ struct Planner {
     bool any_up = false;
     for (int i = 0; i < op.nseg; ++i) any_up |= segs[i].up != 0;
     const int64_t px = (int64_t)H * W;
-    if (h->opt_halo_all)  // tuning / test knob: every eligible 3x3 conv, whatever its size
-      op.halo = L.has_halo() && !any_up;
-    else
-      op.halo = L.has_halo() && !any_up && px >= 8192 &&
-                (ctot >= 768 || (ctot >= 512 && px >= 100000) || L.cout == 32);
+    ConvFamily fam = FAM_BUF;
+    // (opt_halo_all: tuning / test knob, every eligible 3x3 conv, whatever its size)
+    if (L.has_halo() && !any_up && (h->opt_halo_all || (px >= 8192 && (ctot >= 768 || (ctot >= 512 && px >= 100000) || L.cout == 32))))
+      fam = FAM_HALO;
     // precision mode bf16x6: every 3x3 conv that is large enough to be matrix-pipe bound
-    // (op.split: 1 = bf16x6, 2 = bf16x3 - same kernel, two planes and three products)
-    op.split = (h->opt_precision != 0 && L.has_halo() && !any_up && (px >= 2048 || h->opt_halo_all)) ? h->opt_precision : 0;
+    // (bf16x3: same kernel, two planes and three products)
+    if (h->opt_precision != 0 && L.has_halo() && !any_up && (px >= 2048 || h->opt_halo_all))
+      fam = h->opt_precision == 1 ? FAM_SPLIT6 : FAM_SPLIT3;
     // Winograd F(2,3) along x: where the 1.5x MFMA saving survives its LDS / occupancy cost - wide N, large M.
     // In precision mode bf16x3 the same layers run the Winograd form of the split kernel (conv_winox3_kernel).
     // F(4,3) needs the level width to fill its 64-pixel patches (at most 15 % of the last patch of a row empty)
@@ -185,21 +183,21 @@ struct Planner {
     // its split-K, which cuts the few long workgroups of such a layer into enough pieces to fill the chip
     const bool deep_small = L.cout % 128 == 0 && px >= 1024 && px < 8192 && ctot > 1024 && w43_width && h->opt_splitk &&
                             h->opt_wino == 1 && h->opt_precision == 0;
-    op.wino = op.split != 1 && L.ww_off >= 0 && !any_up && h->opt_wino != 0 &&
-              ((L.cout % 128 == 0 && (px >= 8192 || (px >= 2048 && ctot <= 1024))) || (L.cout % 64 == 0 && px >= 30000) ||
-               px >= 100000 || h->opt_wino >= 2 || deep_small);
-    if (op.wino && h->opt_precision == 2 && (op.split == 2 || h->opt_wino >= 2)) {
-      // wino: 1 = fp32 conv_wino_kernel, 2 = conv_winox3_kernel.  The Winograd form wins with the 2 x 2 wave block of
-      // its 128-channel tile (0.88-0.94x the time of conv_halo_split_kernel<..,3> per layer, 427 vs 367 TFLOP/s at
-      // K = 22 032) and loses with the 64-channel tiles (1.08-1.30x: twice the A staging per MFMA) - per-op profiles of
-      // the two plans and tools/retired/conv_bench.hip agree.
-      if (L.cout % 128 == 0 || h->opt_wino >= 2) op.split = 0, op.wino = 2;
-      else if (op.split == 2) op.wino = 0;
+    if (fam != FAM_SPLIT6 && L.ww_off >= 0 && !any_up && h->opt_wino != 0 &&
+        ((L.cout % 128 == 0 && (px >= 8192 || (px >= 2048 && ctot <= 1024))) || (L.cout % 64 == 0 && px >= 30000) ||
+         px >= 100000 || h->opt_wino >= 2 || deep_small)) {
+      if (h->opt_precision == 2 && (fam == FAM_SPLIT3 || h->opt_wino >= 2)) {
+        // bf16x3: conv_winox3_kernel.  The Winograd form wins with the 2 x 2 wave block of its 128-channel tile (0.88-0.94x the
+        // time of conv_halo_split_kernel<..,3> per layer, 427 vs 367 TFLOP/s at K = 22 032) and loses with the 64-channel tiles
+        // (1.08-1.30x: twice the A staging per MFMA) - per-op profiles of the two plans and tools/retired/conv_bench.hip agree.
+        if (L.cout % 128 == 0 || h->opt_wino >= 2) fam = FAM_WINOX3;
+      } else {
+        // fp32: F(4,3) along x (conv_wino43_kernel, 2x fewer MFMAs than direct where F(2,3) has 1.5x) on the levels whose width
+        // fills its 64-pixel patches (the Q16 tiles; at most 15 % of the last patch of a row empty: 960 ... 60, 448, 256 ...), else
+        // F(2,3) (conv_wino_kernel).  "winograd" = 2 / 3 force F(2,3) / F(4,3) onto every eligible layer (tests).
+        fam = h->opt_wino != 2 && w43_width ? FAM_W43 : FAM_WINO;
+      }
     }
-    // fp32: F(4,3) along x (conv_wino43_kernel, 2x fewer MFMAs than direct where F(2,3) has 1.5x) on the levels whose width
-    // fills its 64-pixel patches (the Q16 tiles; at most 15 % of the last patch of a row empty: 960 ... 60, 448, 256 ...); wino = 3.  "winograd" = 2 / 3 force
-    // F(2,3) / F(4,3) onto every eligible layer (tests).
-    if (op.wino == 1 && h->opt_wino != 2 && w43_width) op.wino = 3;
     // Nested F(4,3)x x F(2,3)y (conv_wino2d_kernel, 1.5x fewer MFMAs than the 1-D form): round 4 - EVERY 3x3 layer whose channels come
     // in sixteens (K = 32 ... 2448) on levels of at least opt_w2d_min_px pixels per image (default 1536: eight or more of its 8x32
     // patches per image; below that the 1-D kernel's split-K fills the chip better at batch 1).  A family of its own, a function of the
@@ -217,28 +215,15 @@ struct Planner {
     // profiles/r06_w2d_small_levels_ab.log (256x256 2.43 -> 2.35 ms, eight 448x256 pairs 15.7 -> 15.1, 1080p -0.1 ms).
     const int64_t w2d_tile_px = (int64_t)((H + 7) / 8) * 8 * ((W + 31) / 32) * 32;
     const bool w2d_level = px >= h->opt_w2d_min_px || (h->opt_w2d_small_px > 0 && px >= h->opt_w2d_small_px && px * 100 >= 65 * w2d_tile_px);
-    if (L.w2d_off >= 0 && w2d_layout && !any_up && h->opt_precision == 0 && op.split == 0 &&
+    if (L.w2d_off >= 0 && w2d_layout && !any_up && h->opt_precision == 0 &&
         (h->opt_wino2d == 2 || (h->opt_wino2d == 1 && h->opt_wino == 1 && w2d_level)))
-      op.wino = 4;
-    if (op.split || op.wino) op.halo = 0;
-#ifndef FILM_EXTRA_FAMILIES
-    // default build: the halo / F(2,3) / bf16 split kernels are not in the library (film_set_option refuses the options that ask for
-    // them); a layer the nested / F(4,3) kernels cannot take runs on the general kernel
-    op.halo = 0; op.split = 0;
-    if (op.wino == 1 || op.wino == 2) op.wino = 0;
-#endif
-    need_groups(op.split || op.wino == 2 ? 4 : op.halo ? 3 : op.wino == 1 ? 2 : 1);
-    op.tile = op.wino == 4 ? ((L.cout % 64 == 0 ? W2D_8x64 : W2D_8x32) | CONV_TILE_W2D | CONV_TILE_XCD)
-              : op.wino == 3 ? ((L.cout % 64 == 0 ? W43_Q16_4x64_T21_P2 : W43_Q16_4x32_T11_P2) | CONV_TILE_WINO | CONV_TILE_F43 | CONV_TILE_XCD)
-              : op.wino == 2 ? ((L.cout % 128 == 0 ? WX3_4x128_T22 : L.cout % 64 == 0 ? WX3_4x64_T12 : WX3_4x32_T11) | CONV_TILE_WINO | CONV_TILE_X3 | CONV_TILE_XCD)
-              : op.wino ? ((L.cout % 64 == 0 ? WINO_4x64_W8 : WINO_4x32) | CONV_TILE_WINO | CONV_TILE_XCD)
-              : op.split ? ((L.cout % 128 == 0 ? HALO_8x128 : L.cout % 64 == 0 ? HALO_4x64 : HALO_8x32) | CONV_TILE_SPLIT | (op.split == 2 ? CONV_TILE_X3 : 0) | CONV_TILE_XCD)
-              : op.halo ? choose_halo_tile(L.cout) : choose_tile(M, L.cout);
+      fam = FAM_W2D;
+    set_family(op, fam, M);
     // Split-K for the deep layers of the coarse levels: the whole K loop (up to 1377 steps) of such a layer otherwise runs
     // on a handful of workgroups and IS the latency of the level (0.39 ms per flow-predictor conv_0 at 16 pixels).  The
     // factor depends on the per-image pixel count and the layer only - never on the batch - so results stay independent
     // of the batch size; partial sums are added in split order (no atomics).
-    if (h->opt_splitk && !op.halo && !op.split && !op.wino && !op.c3 && L.kmajor() && px <= 4096) {
+    if (h->opt_splitk && op.family == FAM_BUF && L.kmajor() && px <= 4096) {
       const int nsteps = L.kh * L.kw * ctot / 16;
       // shallow layers: the extra launch costs more than it saves
       int S = nsteps < 128 ? 1 : px <= 64 ? 16 : px <= 256 ? 8 : px <= 1024 ? 4 : nsteps >= 256 ? 2 : 1;
@@ -253,7 +238,7 @@ struct Planner {
     // evenly: a 72x120 level with 512 output channels is 1152 workgroups = 2.25 rounds, the last one on a quarter of
     // the CUs for the full duration of a deep K loop.  Two K ranges double the workgroup count at half the length; the partial sums are added in split order by conv_splitk_reduce_kernel.  Factor from
     // the level size and the layer only.
-    if (h->opt_splitk && op.wino == 3 && L.cout % 4 == 0) {
+    if (h->opt_splitk && op.family == FAM_W43 && L.cout % 4 == 0) {
       // 72x120 level, measured (profiles/r02_per_op_profile.json vs the run before): -10 % on the K = 2448 / 1920 layers,
       // +7..10 % on its K <= 512 layers (reduce kernel + twice the prologues / epilogues) -> deep K only
       // small levels (<= 4096 pixels per image: the 36x60 level of a 1080p tile, the 64x64 level of a 256x256 frame) have
@@ -276,7 +261,7 @@ struct Planner {
     // = 4.5 rounds of the 512 slots and two K ranges gain 2-4 % stand-alone, but nothing in the forward (1.84 -> 1.89, 2.48 -> 2.49-2.53
     // ms per layer with the weights streaming from HBM and the partial sums written and read back: 141 MB for the K = 2448 layer).
     // No layer with a fused pool / 1x1 head is that deep.  Factor from the level size and the layer only - never the batch.
-    if (h->opt_splitk && h->opt_w2d_splitk && op.wino == 4 && L.cout % 4 == 0) {
+    if (h->opt_splitk && h->opt_w2d_splitk && op.family == FAM_W2D && L.cout % 4 == 0) {
       int S = 1;
       if (px <= 4096 && ctot >= 768) S = std::min(4, ctot / 384);
       if (h->opt_w2d_splitk > 1 && px <= 1024 && ctot >= 384) S = std::min(h->opt_w2d_splitk, ctot / 192);   // A/B knob: a higher cap on tiny levels
@@ -408,12 +393,12 @@ struct Planner {
         if (j == 0) {
           const LayerPack& Lp = h->layers[h->layer_idx.at(w0)];
           OpDesc op;
-          op.kind = OP_CONV; op.c3 = 1; op.tag = tg + ":" + w0;
+          op.kind = OP_CONV; op.family = FAM_C3; op.tag = tg + ":" + w0;
           op.nseg = 1; op.seg[0].v = view(img[i], 0, 0, 3);
           op.ksize = 3; op.leaky = 1; op.Cout = k; op.Ctot = 3;
           op.w_off = Lp.w_off; op.b_off = Lp.b_off;
           op.out = tmp; op.NB = NI; op.H = HL(lv); op.W = WL(lv);
-          op.tile = TILE_C3_DIRECT | CONV_TILE_XCD | CONV_TILE_C3;
+          op.tile = conv_default_tile(FAM_C3, k, 0);
           op.flops = 2.0 * NI * HL(lv) * WL(lv) * k * 27; op.bytes = 4.0 * NI * HL(lv) * WL(lv) * (3 + k);
           P->ops.push_back(op);
         } else {
@@ -425,7 +410,7 @@ struct Planner {
         conv(tg, w1, {s1}, dst, NI, HL(lv), WL(lv), true);
         if (j < n - 1) {
           OpDesc& cv = P->ops.back();
-          if ((h->opt_fuse & 8) && cv.kind == OP_CONV && (cv.wino == 3 || cv.wino == 4) && cv.ksplit <= 1 && !(HL(lv) & 1) && !(WL(lv) & 1)) {
+          if ((h->opt_fuse & 8) && cv.kind == OP_CONV && kConvFamily[cv.family].fused_shape >= 0 && cv.ksplit <= 1 && !(HL(lv) & 1) && !(WL(lv) & 1)) {
             // AveragePooling2D in the epilogue of the Winograd kernels (a lane / thread holds both rows of a 2x2 block)
             cv.tag += "+pool";
             cv.out2 = scratch(fx_p, k);
@@ -647,12 +632,12 @@ struct Planner {
       // activation (566 MB per 1080p step) is then neither written nor read back.
       OpDesc& last = P->ops.back();
       const LayerPack& LO = h->layers[h->layer_idx.at("fusion/output_conv")];
-      if ((h->opt_fuse & 16) && last.kind == OP_CONV && (last.wino == 3 || last.wino == 4) && last.Cout == 64 && last.ksplit <= 1 && last.out2.buf < 0 &&
+      if ((h->opt_fuse & 16) && last.kind == OP_CONV && kConvFamily[last.family].fused_shape >= 0 && last.Cout == 64 && last.ksplit <= 1 && last.out2.buf < 0 &&
           LO.cout <= 4 && LO.cin == 64) {
         last.tag += "+output_conv";
         last.pw_out = view(out, 0, 0, 3); last.pw_cout = LO.cout;
         last.w2_off = LO.w_off; last.b2_off = LO.b_off;
-        last.tile = last.wino == 4 ? (W2D_8x64 | CONV_TILE_W2D | CONV_TILE_XCD) : (W43_Q16_4x64_N1_P2 | CONV_TILE_WINO | CONV_TILE_F43 | CONV_TILE_XCD);
+        last.tile = conv_tile(last.family, kConvFamily[last.family].fused_shape, true);
         last.flops += 2.0 * (double)B * H * W * LO.cout * LO.cin;
         last.bytes = 4.0 * (double)B * H * W * (64 + LO.cout);
       } else {
@@ -736,7 +721,7 @@ int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles) {
 int64_t limited_buffer_bytes(const Plan* P) {
   int64_t mx = 1;
   for (const OpDesc& op : P->ops) {
-    if (op.kind != OP_CONV || op.wino == 3 || op.wino == 4) continue;
+    if (op.kind != OP_CONV || op.family == FAM_W43 || op.family == FAM_W2D) continue;
     for (int i = 0; i < op.nseg; ++i) mx = std::max(mx, P->bufs[op.seg[i].v.buf].floats * (int64_t)sizeof(float));
   }
   return mx;
@@ -771,14 +756,15 @@ std::string plan_json(film_t* h, const Plan& P) {
   o << "],\"ops\":[";
   for (size_t i = 0; i < P.ops.size(); ++i) {
     const OpDesc& op = P.ops[i];
+    const FamilyCodes fc = family_codes(op.family);
     o << (i ? "," : "") << "{\"kind\":\"" << kKindName[op.kind] << "\",\"tag\":\"" << op.tag << "\",\"NB\":" << op.NB
       << ",\"H\":" << op.H << ",\"W\":" << op.W << ",\"ksize\":" << op.ksize << ",\"leaky\":" << op.leaky
       << ",\"Cout\":" << op.Cout << ",\"Ctot\":" << op.Ctot << ",\"tile\":" << op.tile << ",\"w_off\":" << op.w_off
-      << ",\"b_off\":" << op.b_off << ",\"wf4_off\":" << op.wf4_off << ",\"wh_off\":" << op.wh_off << ",\"halo\":" << op.halo << ",\"ws_off\":" << op.ws_off << ",\"split\":" << op.split << ",\"ww_off\":" << op.ww_off << ",\"wx_off\":" << op.wx_off << ",\"wfx_off\":" << op.wfx_off << ",\"w43_off\":" << op.w43_off << ",\"w2d_off\":" << op.w2d_off << ",\"wino\":" << op.wino << ",\"fold\":" << op.fold << ",\"ksplit\":" << op.ksplit << ",\"py\":" << op.py
+      << ",\"b_off\":" << op.b_off << ",\"wf4_off\":" << op.wf4_off << ",\"wh_off\":" << op.wh_off << ",\"halo\":" << fc.halo << ",\"ws_off\":" << op.ws_off << ",\"split\":" << fc.split << ",\"ww_off\":" << op.ww_off << ",\"wx_off\":" << op.wx_off << ",\"wfx_off\":" << op.wfx_off << ",\"w43_off\":" << op.w43_off << ",\"w2d_off\":" << op.w2d_off << ",\"wino\":" << fc.wino << ",\"fold\":" << op.fold << ",\"ksplit\":" << op.ksplit << ",\"py\":" << op.py
       << ",\"px\":" << op.px << ",\"ftaps\":" << op.ftaps << ",\"tdy\":[" << op.tdy[0] << "," << op.tdy[1] << "," << op.tdy[2] << "," << op.tdy[3]
       << "],\"tdx\":[" << op.tdx[0] << "," << op.tdx[1] << "," << op.tdx[2] << "," << op.tdx[3] << "]"
       << ",\"fold_woff\":[" << op.fold_woff[0] << "," << op.fold_woff[1] << "," << op.fold_woff[2] << "," << op.fold_woff[3] << "]" << ",\"lane\":" << op.lane << ",\"xdeps\":["
-      << [&] { std::string d; for (size_t q = 0; q < op.xdeps.size(); ++q) d += (q ? "," : "") + std::to_string(op.xdeps[q]); return d; }() << "]" << ",\"w2_off\":" << op.w2_off << ",\"b2_off\":" << op.b2_off << ",\"c3\":" << op.c3
+      << [&] { std::string d; for (size_t q = 0; q < op.xdeps.size(); ++q) d += (q ? "," : "") + std::to_string(op.xdeps[q]); return d; }() << "]" << ",\"w2_off\":" << op.w2_off << ",\"b2_off\":" << op.b2_off << ",\"c3\":" << fc.c3
       << ",\"fscale\":" << op.fscale << ",\"src_brot\":" << op.src_brot << ",\"flow_brot\":" << op.flow_brot << ",\"misc_nb\":" << op.misc_nb << ",\"n\":" << op.n << ",\"flops\":" << op.flops
       << ",\"bytes\":" << op.bytes << ",";
     json_view(o, "in", op.in, P); o << ",";
