@@ -337,7 +337,7 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
   if ((int64_t)2 * B * H * W >= (int64_t)1 << 31) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
   for (auto& p : h->plans)
     if (p->B == B && p->H == H && p->W == W && p->tiles == tiles && (!need_device || p->arena)) { *out = p.get(); p->last_use = ++h->tick; return FILM_OK; }
-  if (need_device)   // a description-only plan of this shape (film_plan_json, unit_buffer_bytes) is superseded, not kept beside the new one
+  if (need_device)   // a description-only plan of this shape (film_plan_json, max_units) is superseded, not kept beside the new one
     for (size_t i = 0; i < h->plans.size(); ++i)
       if (h->plans[i]->B == B && h->plans[i]->H == H && h->plans[i]->W == W && h->plans[i]->tiles == tiles) {
         if (h->last_plan == h->plans[i].get()) h->last_plan = nullptr;
@@ -411,6 +411,63 @@ int copy_out_string(film_t* h, const std::string& s, char* buf, int64_t cap, int
   }
   memcpy(buf, s.c_str(), s.size() + 1);
   return FILM_OK;
+}
+
+// ---- options: one row per key of film_set_option (what each value means: include/film_hip.h; the measurements behind the defaults: beside the
+// opt_* fields in film_internal.h).  A value is range-checked, refused where it needs a kernel family this library does not hold, normalised and
+// stored; the plans carry the op list, the buffer layout, the lanes and the kernel and tile of every op, so a CHANGED value of an option that
+// decides any of those drops them.
+enum OptNorm { AS_IS, BOOL, NONNEG, LOW5 };   // stored: value | value != 0 | max(value, 0) | value & 31
+// a row reads: key, field, norm, drops_plans [, lo, hi, refusal [, family, need_lo, need_hi, family_refusal]]
+struct OptionRow {
+  const char* key;
+  int film_t::*field;   // nullptr: "pack_groups" stores nothing - it packs the weight layout groups 1..value of a finalized handle now
+  OptNorm norm;
+  bool drops_plans;
+  int64_t lo = 0, hi = 0;
+  const char* refusal = nullptr;          // of a value outside lo..hi (nullptr: every value is accepted)
+  ConvFamily family = FAM_BUF;
+  int need_lo = 0, need_hi = 0;
+  const char* family_refusal = nullptr;   // of a stored value in need_lo..need_hi when `family` is not built (nullptr: no such values; %d = the value)
+};
+constexpr OptionRow kOptions[] = {
+    {"graph", &film_t::opt_graph, AS_IS, false, 0, 2, "graph: 0 (one stream, eager), 1 (hipGraph replay) or 2 (two lanes, eager: the default)"},
+    {"profile", &film_t::opt_profile, BOOL, false},
+    {"autotune", &film_t::opt_autotune, BOOL, false},
+    {"max_batch", &film_t::opt_max_batch, NONNEG, false},
+    {"host_overlap", &film_t::opt_host_overlap, BOOL, false},
+    {"tune_ms", &film_t::opt_tune_ms, NONNEG, false},
+    {"splitk", &film_t::opt_splitk, BOOL, true},
+    {"pack_groups", nullptr, AS_IS, false, 1, 4, "pack_groups: 1 .. 4"},
+    {"fuse", &film_t::opt_fuse, LOW5, true},
+    {"fold2x2", &film_t::opt_fold2x2, AS_IS, true, 0, 2, "fold2x2: 0, 1 or 2"},
+    {"planar", &film_t::opt_planar, BOOL, true},
+    {"winograd", &film_t::opt_wino, AS_IS, true, 0, 3, "winograd: 0, 1, 2 or 3", FAM_WINO, 2, 2,
+     "winograd = 2 (F(2,3) kernel on every level) needs a library built with FILM_EXTRA_FAMILIES=1"},
+    {"halo_all", &film_t::opt_halo_all, BOOL, true, 0, 0, nullptr, FAM_HALO, 1, 1, "halo_all needs a library built with FILM_EXTRA_FAMILIES=1"},
+    {"lanes", &film_t::opt_lanes, AS_IS, true, 0, 3, "lanes: 0, 1, 2 or 3"},
+    {"wino2d", &film_t::opt_wino2d, AS_IS, true, 0, 2, "wino2d: 0, 1 or 2"},
+    {"w2d_small_px", &film_t::opt_w2d_small_px, AS_IS, true, 0, 1 << 30, "w2d_small_px: pixels per image, 0 = never"},
+    {"w2d_min_px", &film_t::opt_w2d_min_px, AS_IS, true, 1, 1 << 30, "w2d_min_px: pixels per image"},
+    {"w2d_splitk", &film_t::opt_w2d_splitk, AS_IS, true, 0, 16, "w2d_splitk: 0 (off), 1 (default rule) or 2..16 (A/B: the cap on levels of <= 1024 pixels)"},
+    {"w2d_shape", &film_t::opt_w2d_shape, AS_IS, true, -1, W2D_SHAPES - 1, "w2d_shape: -1 (autotuned) or a Wino2dTile shape index"},
+    {"fold4_shape", &film_t::opt_fold4_shape, AS_IS, true, -1, F4_4x32, "fold4_shape: -1 (autotuned) or a Fold4Tile shape index"},
+    {"w43_shape", &film_t::opt_w43_shape, AS_IS, true, -1, 31, "w43_shape: -1 (autotuned) or a Wino43Tile shape index"},
+    {"precision", &film_t::opt_precision, AS_IS, true, 0, 2, "precision: 0 (f32), 1 (bf16x6) or 2 (bf16x3)", FAM_SPLIT6, 1, 2,
+     "precision %d (bf16 split modes) needs a library built with FILM_EXTRA_FAMILIES=1; this build runs fp32 MFMA only"},
+};
+constexpr bool option_rows_complete() {
+  for (const OptionRow& o : kOptions)
+    if ((o.lo < o.hi) != (o.refusal != nullptr) || ((o.family != FAM_BUF) != (o.family_refusal != nullptr))) return false;
+  return true;
+}
+static_assert(option_rows_complete(), "a row with a range (a family) carries its refusal message, a row without leaves lo = hi (family = FAM_BUF)");
+
+void drop_plans(film_t* h) {
+  if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }   // (forwards may still be running on them)
+  for (auto& p : h->plans) free_plan(p.get());
+  h->plans.clear();
+  h->last_plan = nullptr;
 }
 
 }  // namespace
@@ -497,174 +554,18 @@ const char* film_last_error(const film_t* h) { return h ? h->err.c_str() : g_cre
 
 int film_set_option(film_t* h, const char* key, int64_t value) {
   if (!h || !key) return FILM_ERR_INVALID;
-  if (!strcmp(key, "graph")) {
-    if (value < 0 || value > 2) return fail(h, FILM_ERR_INVALID, "graph: 0 (one stream, eager), 1 (hipGraph replay) or 2 (two lanes, eager: the default)");
-    h->opt_graph = (int)value;
+  for (const OptionRow& o : kOptions) {
+    if (strcmp(key, o.key)) continue;
+    if (o.refusal && (value < o.lo || value > o.hi)) return fail(h, FILM_ERR_INVALID, "%s", o.refusal);
+    const int v = o.norm == BOOL ? value != 0 : o.norm == NONNEG ? (value > 0 ? (int)value : 0) : o.norm == LOW5 ? (int)(value & 31) : (int)value;
+    if (o.family_refusal && v >= o.need_lo && v <= o.need_hi && !conv_family_built(o.family)) return fail(h, FILM_ERR_INVALID, o.family_refusal, v);
+    if (!o.field) return h->finalized ? film_ensure_groups_(h, v) : FILM_OK;
+    if (h->*o.field == v) return FILM_OK;   // (unchanged: the plans, last_plan and the autotuned tiles stay)
+    if (o.drops_plans) drop_plans(h);
+    h->*o.field = v;
+    return FILM_OK;
   }
-  else if (!strcmp(key, "profile")) h->opt_profile = value != 0;
-  else if (!strcmp(key, "autotune")) h->opt_autotune = value != 0;
-  else if (!strcmp(key, "max_batch")) h->opt_max_batch = value > 0 ? (int)value : 0;
-  else if (!strcmp(key, "host_overlap")) h->opt_host_overlap = value != 0;
-  else if (!strcmp(key, "tune_ms")) h->opt_tune_ms = value > 0 ? (int)value : 0;
-  else if (!strcmp(key, "splitk")) {
-    if ((value != 0) != (h->opt_splitk != 0)) {  // plans carry the op list: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_splitk = value != 0;
-    }
-  }
-  else if (!strcmp(key, "pack_groups")) {
-    if (value < 1 || value > 4) return fail(h, FILM_ERR_INVALID, "pack_groups: 1 .. 4");
-    if (h->finalized) { int rc = film_ensure_groups_(h, (int)value); if (rc) return rc; }
-  }
-  else if (!strcmp(key, "fuse")) {
-    if ((int)(value & 31) != h->opt_fuse) {  // plans carry the op list: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_fuse = (int)(value & 31);
-    }
-  }
-  else if (!strcmp(key, "fold2x2")) {
-    if (value < 0 || value > 2) return fail(h, FILM_ERR_INVALID, "fold2x2: 0, 1 or 2");
-    const int fold = value != 0, fold4 = value == 1;
-    if (fold != h->opt_fold || fold4 != h->opt_fold4) {  // plans carry the op list: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_fold = fold;
-      h->opt_fold4 = fold4;
-    }
-  }
-  else if (!strcmp(key, "planar")) {
-    if ((value != 0) != (h->opt_planar != 0)) {  // plans carry the buffer layout: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_planar = value != 0;
-    }
-  }
-  else if (!strcmp(key, "winograd")) {
-    if (value < 0 || value > 3) return fail(h, FILM_ERR_INVALID, "winograd: 0, 1, 2 or 3");
-    if (value == 2 && !conv_family_built(FAM_WINO))
-      return fail(h, FILM_ERR_INVALID, "winograd = 2 (F(2,3) kernel on every level) needs a library built with FILM_EXTRA_FAMILIES=1");
-    if ((int)value != h->opt_wino) {  // plans carry the kernel choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_wino = (int)value;
-    }
-  }
-  else if (!strcmp(key, "halo_all")) {
-    if (value && !conv_family_built(FAM_HALO)) return fail(h, FILM_ERR_INVALID, "halo_all needs a library built with FILM_EXTRA_FAMILIES=1");
-    if ((value != 0) != (h->opt_halo_all != 0)) {  // plans carry the kernel choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_halo_all = value != 0;
-    }
-  }
-  else if (!strcmp(key, "lanes")) {
-    if (value < 0 || value > 3) return fail(h, FILM_ERR_INVALID, "lanes: 0, 1, 2 or 3");
-    if ((int)value != h->opt_lanes) {  // plans carry the lane of every op and the op order: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_lanes = (int)value;
-    }
-  }
-  else if (!strcmp(key, "wino2d")) {
-    if (value < 0 || value > 2) return fail(h, FILM_ERR_INVALID, "wino2d: 0, 1 or 2");
-    if ((int)value != h->opt_wino2d) {  // plans carry the kernel choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_wino2d = (int)value;
-    }
-  }
-  else if (!strcmp(key, "w2d_small_px")) {
-    if (value < 0 || value > (1 << 30)) return fail(h, FILM_ERR_INVALID, "w2d_small_px: pixels per image, 0 = never");
-    if ((int)value != h->opt_w2d_small_px) {  // plans carry the kernel choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_w2d_small_px = (int)value;
-    }
-  }
-  else if (!strcmp(key, "w2d_min_px")) {
-    if (value < 1 || value > (1 << 30)) return fail(h, FILM_ERR_INVALID, "w2d_min_px: pixels per image");
-    if ((int)value != h->opt_w2d_min_px) {  // plans carry the kernel choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_w2d_min_px = (int)value;
-    }
-  }
-  else if (!strcmp(key, "w2d_splitk")) {
-    if (value < 0 || value > 16) return fail(h, FILM_ERR_INVALID, "w2d_splitk: 0 (off), 1 (default rule) or 2..16 (A/B: the cap on levels of <= 1024 pixels)");
-    if ((int)value != h->opt_w2d_splitk) {  // plans carry the split factors: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_w2d_splitk = (int)value;
-    }
-  }
-  else if (!strcmp(key, "w2d_shape")) {
-    if (value < -1 || value >= W2D_SHAPES) return fail(h, FILM_ERR_INVALID, "w2d_shape: -1 (autotuned) or a Wino2dTile shape index");
-    if ((int)value != h->opt_w2d_shape) {  // plans carry the tile choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_w2d_shape = (int)value;
-    }
-  }
-  else if (!strcmp(key, "fold4_shape")) {
-    if (value < -1 || value > F4_4x32) return fail(h, FILM_ERR_INVALID, "fold4_shape: -1 (autotuned) or a Fold4Tile shape index");
-    if ((int)value != h->opt_fold4_shape) {  // plans carry the tile choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_fold4_shape = (int)value;
-    }
-  }
-  else if (!strcmp(key, "w43_shape")) {
-    if (value < -1 || value > 31) return fail(h, FILM_ERR_INVALID, "w43_shape: -1 (autotuned) or a Wino43Tile shape index");
-    if ((int)value != h->opt_w43_shape) {  // plans carry the tile choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_w43_shape = (int)value;
-    }
-  }
-  else if (!strcmp(key, "precision")) {
-    if (value != 0 && value != 1 && value != 2) return fail(h, FILM_ERR_INVALID, "precision: 0 (f32), 1 (bf16x6) or 2 (bf16x3)");
-    if (value && !conv_family_built(FAM_SPLIT6))
-      return fail(h, FILM_ERR_INVALID, "precision %d (bf16 split modes) needs a library built with FILM_EXTRA_FAMILIES=1; this build runs fp32 MFMA only", (int)value);
-    if ((int)value != h->opt_precision) {  // plans carry the kernel choice: drop them
-      if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); (void)hipDeviceSynchronize(); }
-      for (auto& p : h->plans) free_plan(p.get());
-      h->plans.clear();
-      h->last_plan = nullptr;
-      h->opt_precision = (int)value;
-    }
-  }
-  else return fail(h, FILM_ERR_NOTFOUND, "unknown option '%s'", key);
-  return FILM_OK;
+  return fail(h, FILM_ERR_NOTFOUND, "unknown option '%s'", key);
 }
 
 int film_plan_json(film_t* h, int B, int H, int W, char* buf, int64_t cap, int64_t* needed) {
@@ -748,14 +649,41 @@ int64_t arena_budget_bytes(film_t* h) {
   }
   return std::max<int64_t>(cap, 1);
 }
-int64_t unit_buffer_bytes(film_t* h, int H, int W, int* rc, int* max_units) {
+// Most H x W units (`what`: frame pairs / pair-tiles) one model invocation may take: what the plan of ONE unit says about the 4 GiB-per-buffer limit
+// and the workspace budget, then option "max_batch".  A unit that is too large by itself is refused with `advice`.
+int max_units(film_t* h, int H, int W, const char* what, const char* advice, int* units) {
   Plan* P1 = nullptr;
-  *rc = get_plan(h, 1, H, W, false, &P1);
-  if (*rc) return 0;
+  int rc = get_plan(h, 1, H, W, false, &P1);
+  if (rc) return rc;
   const int64_t lim = limited_buffer_bytes(P1);
   const int64_t arena = std::max<int64_t>(1, P1->arena_floats * (int64_t)sizeof(float));
-  *max_units = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxBufferBytes / lim, arena_budget_bytes(h) / arena));
-  return lim;
+  *units = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxBufferBytes / lim, arena_budget_bytes(h) / arena));
+  if (lim > kMaxBufferBytes)
+    return fail(h, FILM_ERR_INVALID, "a %d x %d %s needs a %.1f GB activation buffer in front of a kernel that addresses 4 GiB per "
+                "buffer - %s", H, W, what, lim * 1e-9, advice);
+  if (h->opt_max_batch) *units = std::min(*units, h->opt_max_batch);
+  return FILM_OK;
+}
+// Geometry of a frame cut into block_h x block_w patches, each padded to a multiple of `align` (_pad_to_align, eval/interpolator.py:45-52).
+// The two refusals are the reference's asserts (eval/interpolator.py:84-89), same messages.  tp->B, src, dst and the tile range are the caller's.
+int tile_geometry(film_t* h, int H, int W, int block_h, int block_w, int align, TileMapParams* tp) {
+  const int bh = block_h > 0 ? block_h : 1, bw = block_w > 0 ? block_w : 1;
+  if (H % bh) return fail(h, FILM_ERR_INVALID, "block_height=%d should evenly divide height=%d.", bh, H);
+  if (W % bw) return fail(h, FILM_ERR_INVALID, "block_width=%d should evenly divide width=%d.", bw, W);
+  tp->H = H; tp->W = W; tp->bh = bh; tp->bw = bw; tp->ph = H / bh; tp->pw = W / bw;
+  const int hp = (align > 0 && tp->ph % align) ? align - tp->ph % align : 0;
+  const int wp = (align > 0 && tp->pw % align) ? align - tp->pw % align : 0;
+  tp->TH = tp->ph + hp; tp->TW = tp->pw + wp; tp->oy = hp / 2; tp->ox = wp / 2;
+  return FILM_OK;
+}
+// The handle's staging buffer in HBM (whole frames of the FILM_MEM_HOST entry points), grown on demand.
+int ensure_stage(film_t* h, size_t bytes, hipStream_t s) {
+  if (h->stage_bytes >= bytes) return FILM_OK;
+  if (h->stage) { HIPCHK(h, hipStreamSynchronize(s)); HIPCHK(h, hipFree(h->stage)); h->stage = nullptr; h->stage_bytes = 0; }
+  hipError_t e = hipMalloc(&h->stage, bytes);
+  if (e != hipSuccess) return fail(h, FILM_ERR_NOMEM, "frame staging hipMalloc of %.1f MB failed", bytes * 1e-6);
+  h->stage_bytes = bytes;
+  return FILM_OK;
 }
 // Chunk size for n independent units with at most maxc per invocation: the largest divisor of n in (maxc / 2, maxc] if
 // there is one, so that every invocation runs the SAME cached plan (16 * 2^k tiles of a 4K recursion with maxc = 15 ->
@@ -778,14 +706,9 @@ int film_forward(film_t* h, const float* x0, const float* x1, int B, int H, int 
   if (!h->finalized) return fail(h, FILM_ERR_STATE, "film_finalize has not been called");
   if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
   if (B < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
-  int rc = 0;
   int bmax = 1;
-  const int64_t unit = unit_buffer_bytes(h, H, W, &rc, &bmax);
+  int rc = max_units(h, H, W, "frame", "tile the frame (Interpolator block_shape)", &bmax);
   if (rc) return rc;
-  if (unit > kMaxBufferBytes)
-    return fail(h, FILM_ERR_INVALID, "a %d x %d frame needs a %.1f GB activation buffer in front of a kernel that addresses 4 GiB per "
-                "buffer - tile the frame (Interpolator block_shape)", H, W, unit * 1e-9);
-  if (h->opt_max_batch) bmax = std::min(bmax, h->opt_max_batch);
   const size_t frame = (size_t)H * W * 3;
   int chunk = balanced_chunk(B, bmax);
   for (int b0 = 0; b0 < B;) {  // independent frame pairs: the batch splits with no change in results
@@ -809,36 +732,22 @@ int film_interpolate(film_t* h, const float* x0, const float* x1, int B, int H, 
   if (!h->finalized) return fail(h, FILM_ERR_STATE, "film_finalize has not been called");
   if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
   if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
-  const int bh = block_h > 0 ? block_h : 1, bw = block_w > 0 ? block_w : 1;
-  // the reference's asserts (eval/interpolator.py:84-89), same messages
-  if (H % bh) return fail(h, FILM_ERR_INVALID, "block_height=%d should evenly divide height=%d.", bh, H);
-  if (W % bw) return fail(h, FILM_ERR_INVALID, "block_width=%d should evenly divide width=%d.", bw, W);
   TileMapParams tp{};
-  tp.B = B; tp.H = H; tp.W = W; tp.bh = bh; tp.bw = bw; tp.ph = H / bh; tp.pw = W / bw;
-  const int hp = (align > 0 && tp.ph % align) ? align - tp.ph % align : 0;   // _pad_to_align, eval/interpolator.py:45-52
-  const int wp = (align > 0 && tp.pw % align) ? align - tp.pw % align : 0;
-  tp.TH = tp.ph + hp; tp.TW = tp.pw + wp; tp.oy = hp / 2; tp.ox = wp / 2;
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = 0;
-  int tmax = 1;
-  const int64_t unit = unit_buffer_bytes(h, tp.TH, tp.TW, &rc, &tmax);
+  tp.B = B;
+  int rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
   if (rc) return rc;
-  if (unit > kMaxBufferBytes)
-    return fail(h, FILM_ERR_INVALID, "a %d x %d tile needs a %.1f GB activation buffer in front of a kernel that addresses 4 GiB per "
-                "buffer - use a finer block_shape", tp.TH, tp.TW, unit * 1e-9);
-  const int ntiles = B * bh * bw;
-  if (h->opt_max_batch) tmax = std::min(tmax, h->opt_max_batch);
+  HIPCHK(h, hipSetDevice(h->device));
+  int tmax = 1;
+  rc = max_units(h, tp.TH, tp.TW, "tile", "use a finer block_shape", &tmax);
+  if (rc) return rc;
+  const int ntiles = B * tp.bh * tp.bw;
   hipStream_t s = pick_stream(h, mem_kind, stream);
   const size_t frame_bytes = (size_t)B * H * W * 3 * sizeof(float);
   const float *d0 = x0, *d1 = x1;
   float* dout = out;
   if (mem_kind == FILM_MEM_HOST) {  // stage whole frames in HBM: [x0 | x1 | out]
-    if (h->stage_bytes < 3 * frame_bytes) {
-      if (h->stage) { HIPCHK(h, hipStreamSynchronize(s)); HIPCHK(h, hipFree(h->stage)); h->stage = nullptr; h->stage_bytes = 0; }
-      hipError_t e = hipMalloc(&h->stage, 3 * frame_bytes);
-      if (e != hipSuccess) return fail(h, FILM_ERR_NOMEM, "frame staging hipMalloc of %.1f MB failed", 3 * frame_bytes * 1e-6);
-      h->stage_bytes = 3 * frame_bytes;
-    }
+    rc = ensure_stage(h, 3 * frame_bytes, s);
+    if (rc) return rc;
     float* st = (float*)h->stage;
     const size_t nf = frame_bytes / sizeof(float);
     d0 = st; d1 = st + nf; dout = st + 2 * nf;
@@ -859,16 +768,14 @@ int film_interpolate(film_t* h, const float* x0, const float* x1, int B, int H, 
     rc = get_plan(h, nt, tp.TH, tp.TW, true, &P);
     if (rc == FILM_ERR_NOMEM && nt > 1) { chunk = (nt + 1) / 2; continue; }   // workspace did not fit: smaller chunks
     if (rc) return rc;
-    const Buffer& img0 = P->bufs[P->find("img0")];
-    const Buffer& ob = P->bufs[P->find("out")];
     tp.tile0 = t0; tp.ntiles = nt;
-    tp.src = d0; tp.dst = P->arena + img0.off;
+    tp.src = d0; tp.dst = P->at("img0");
     HIPCHK(h, film_launch_frame_to_tiles(tp, s));
-    tp.src = d1; tp.dst = P->arena + img0.off + (int64_t)nt * tp.TH * tp.TW * 3;
+    tp.src = d1; tp.dst = P->at("img0") + (int64_t)nt * tp.TH * tp.TW * 3;
     HIPCHK(h, film_launch_frame_to_tiles(tp, s));
     rc = run_plan(h, P, s);
     if (rc) return rc;
-    tp.src = P->arena + ob.off; tp.dst = dout;
+    tp.src = P->at("out"); tp.dst = dout;
     HIPCHK(h, film_launch_tiles_to_frame(tp, s));
     t0 += nt;
   }
@@ -904,27 +811,17 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
   if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
   if (F < 2) return fail(h, FILM_ERR_INVALID, "a sequence needs at least 2 frames, got %d", F);
   if (H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
-  const int bh = block_h > 0 ? block_h : 1, bw = block_w > 0 ? block_w : 1;
-  // the reference's asserts (eval/interpolator.py:84-89), same messages
-  if (H % bh) return fail(h, FILM_ERR_INVALID, "block_height=%d should evenly divide height=%d.", bh, H);
-  if (W % bw) return fail(h, FILM_ERR_INVALID, "block_width=%d should evenly divide width=%d.", bw, W);
+  TileMapParams tp{};
+  tp.B = 1;
+  int rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
+  if (rc) return rc;
   if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: film_interpolate_sequence needs a HIP device (no CPU fallback)");
   if (!h->finalized) return fail(h, FILM_ERR_STATE, "film_finalize has not been called");
-  TileMapParams tp{};
-  tp.B = 1; tp.H = H; tp.W = W; tp.bh = bh; tp.bw = bw; tp.ph = H / bh; tp.pw = W / bw;
-  const int hp = (align > 0 && tp.ph % align) ? align - tp.ph % align : 0;   // _pad_to_align, eval/interpolator.py:45-52
-  const int wp = (align > 0 && tp.pw % align) ? align - tp.pw % align : 0;
-  tp.TH = tp.ph + hp; tp.TW = tp.pw + wp; tp.oy = hp / 2; tp.ox = wp / 2;
   HIPCHK(h, hipSetDevice(h->device));
-  int rc = 0;
   int tmax = 1;
-  const int64_t unit = unit_buffer_bytes(h, tp.TH, tp.TW, &rc, &tmax);
+  rc = max_units(h, tp.TH, tp.TW, "tile", "use a finer block_shape", &tmax);
   if (rc) return rc;
-  if (unit > kMaxBufferBytes)
-    return fail(h, FILM_ERR_INVALID, "a %d x %d tile needs a %.1f GB activation buffer in front of a kernel that addresses 4 GiB per "
-                "buffer - use a finer block_shape", tp.TH, tp.TW, unit * 1e-9);
-  if (h->opt_max_batch) tmax = std::min(tmax, h->opt_max_batch);
-  const int n = F - 1, T = bh * bw;
+  const int n = F - 1, T = tp.bh * tp.bw;
   int k = 1, nt = 1;
   sequence_chunk(n, T, tmax, &k, &nt);
   hipStream_t s = pick_stream(h, mem_kind, stream);
@@ -932,13 +829,8 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
   const float* dfr = frames;
   float* dout = out;
   if (mem_kind == FILM_MEM_HOST) {  // stage in HBM: [F frames | F - 1 results], plain upload, work, download
-    const size_t need = (2 * (size_t)F - 1) * frame * sizeof(float);
-    if (h->stage_bytes < need) {
-      if (h->stage) { HIPCHK(h, hipStreamSynchronize(s)); HIPCHK(h, hipFree(h->stage)); h->stage = nullptr; h->stage_bytes = 0; }
-      hipError_t e = hipMalloc(&h->stage, need);
-      if (e != hipSuccess) return fail(h, FILM_ERR_NOMEM, "frame staging hipMalloc of %.1f MB failed", need * 1e-6);
-      h->stage_bytes = need;
-    }
+    rc = ensure_stage(h, (2 * (size_t)F - 1) * frame * sizeof(float), s);
+    if (rc) return rc;
     float* st = (float*)h->stage;
     HIPCHK(h, hipMemcpyAsync(st, frames, (size_t)F * frame * sizeof(float), hipMemcpyHostToDevice, s));
     dfr = st; dout = st + (size_t)F * frame;
@@ -953,26 +845,25 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
       rc = get_plan(h, kk * nn, tp.TH, tp.TW, true, &P, nn);
       if (rc == FILM_ERR_NOMEM && kk * nn > 1) break;
       if (rc) return rc;
-      const Buffer& img0 = P->bufs[P->find("img0")];
-      const Buffer& ob = P->bufs[P->find("out")];
+      float *const img0 = P->at("img0"), *const res = P->at("out");
       TileMapParams q = tp;
       if (nn == T) {   // whole frames: frames j0 .. j0 + kk are consecutive tiles of one frame batch
-        q.tile0 = 0; q.ntiles = (kk + 1) * T; q.src = dfr + (size_t)j0 * frame; q.dst = P->arena + img0.off;
+        q.tile0 = 0; q.ntiles = (kk + 1) * T; q.src = dfr + (size_t)j0 * frame; q.dst = img0;
         HIPCHK(h, film_launch_frame_to_tiles(q, s));
       } else {         // tiles [t0, t0 + nn) of each frame, frame-major
         for (int f = 0; f <= kk; ++f) {
-          q.tile0 = t0; q.ntiles = nn; q.src = dfr + (size_t)(j0 + f) * frame; q.dst = P->arena + img0.off + (int64_t)f * nn * tile_floats;
+          q.tile0 = t0; q.ntiles = nn; q.src = dfr + (size_t)(j0 + f) * frame; q.dst = img0 + (int64_t)f * nn * tile_floats;
           HIPCHK(h, film_launch_frame_to_tiles(q, s));
         }
       }
       rc = run_plan(h, P, s);
       if (rc) return rc;
       if (nn == T) {
-        q.tile0 = 0; q.ntiles = kk * T; q.src = P->arena + ob.off; q.dst = dout + (size_t)j0 * frame;
+        q.tile0 = 0; q.ntiles = kk * T; q.src = res; q.dst = dout + (size_t)j0 * frame;
         HIPCHK(h, film_launch_tiles_to_frame(q, s));
       } else {
         for (int j = 0; j < kk; ++j) {
-          q.tile0 = t0; q.ntiles = nn; q.src = P->arena + ob.off + (int64_t)j * nn * tile_floats; q.dst = dout + (size_t)(j0 + j) * frame;
+          q.tile0 = t0; q.ntiles = nn; q.src = res + (int64_t)j * nn * tile_floats; q.dst = dout + (size_t)(j0 + j) * frame;
           HIPCHK(h, film_launch_tiles_to_frame(q, s));
         }
       }
@@ -1142,8 +1033,6 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
   const size_t nf = frame_bytes / sizeof(float);
   for (hipEvent_t& e : h->pipe_ev)
     if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  const Buffer& img0 = P->bufs[P->find("img0")];
-  const Buffer& ob = P->bufs[P->find("out")];
   LanePipe lp;
   for (size_t i = 0; i < P->ops.size() && lp.head.size() < 2; ++i) {   // the leading main-lane convolutions that read nothing from the side lane
     const OpDesc& op = P->ops[i];
@@ -1159,29 +1048,35 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
   tp.tile0 = 0;
   lp.mid_tail = [&]() -> hipError_t {
     TileMapParams t2 = tp;
-    t2.ntiles = nt / 2; t2.src = P->arena + ob.off; t2.dst = st + 2 * nf;
+    t2.ntiles = nt / 2; t2.src = P->at("out"); t2.dst = st + 2 * nf;
     hipError_t e = film_launch_tiles_to_frame(t2, s);
     if (e == hipSuccess) e = hipEventRecord(h->pipe_ev[1], s);
     return e;
   };
+  // From here on copies and kernels are in flight on both streams: whatever fails, both are drained before the error goes back to the caller,
+  // who may then free or reuse x1 / out (pinned memory makes the copies truly asynchronous).
+  struct Drain {
+    film_t* h; hipStream_t s; bool armed;
+    ~Drain() { if (armed) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamSynchronize(s); } }
+  } drain{h, s, true};
   HIPCHK(h, hipMemcpyAsync(st, x0, frame_bytes, hipMemcpyHostToDevice, s));
-  tp.ntiles = nt; tp.src = st; tp.dst = P->arena + img0.off;
+  tp.ntiles = nt; tp.src = st; tp.dst = P->at("img0");
   HIPCHK(h, film_launch_frame_to_tiles(tp, s));
   HIPCHK(h, hipEventRecord(h->pipe_ev[0], s));
   HIPCHK(h, hipStreamWaitEvent(h->stream2, h->pipe_ev[0], 0));   // (the side stream: behind whatever `s` held before this call, too)
   for (size_t i : lp.head) HIPCHK(h, launch_op(batch_part(P->ops[i], 0, 2), P->arena, h->packed_dev, s));
   HIPCHK(h, hipMemcpyAsync(st + nf, x1, frame_bytes, hipMemcpyHostToDevice, h->stream2));
-  tp.src = st + nf; tp.dst = P->arena + img0.off + (int64_t)nt * tp.TH * tp.TW * 3;
+  tp.src = st + nf; tp.dst = P->at("img0") + (int64_t)nt * tp.TH * tp.TW * 3;
   HIPCHK(h, film_launch_frame_to_tiles(tp, h->stream2));
   HIPCHK(h, hipEventRecord(h->pipe_ev[0], h->stream2));
   HIPCHK(h, hipStreamWaitEvent(s, h->pipe_ev[0], 0));
   const hipError_t le = issue_lanes(h, P, s, false, &lp);
-  if (le != hipSuccess) { (void)hipStreamSynchronize(h->stream2); return fail(h, FILM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(le)); }
+  if (le != hipSuccess) return fail(h, FILM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(le));
   h->last_plan = P;
   const int64_t tile_floats = (int64_t)tp.TH * tp.TW * 3;
   if (lp.tail) {
     TileMapParams t2 = tp;
-    t2.tile0 = nt / 2; t2.ntiles = nt - nt / 2; t2.src = P->arena + ob.off + (int64_t)(nt / 2) * tile_floats; t2.dst = st + 2 * nf;
+    t2.tile0 = nt / 2; t2.ntiles = nt - nt / 2; t2.src = P->at("out") + (int64_t)(nt / 2) * tile_floats; t2.dst = st + 2 * nf;
     HIPCHK(h, film_launch_tiles_to_frame(t2, s));
     const size_t half = frame_bytes / 2;   // (one frame, an even number of block rows: the upper half of the rows)
     HIPCHK(h, hipStreamWaitEvent(h->stream2, h->pipe_ev[1], 0));
@@ -1189,11 +1084,12 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
     HIPCHK(h, hipMemcpyAsync((char*)out + half, (const char*)(st + 2 * nf) + half, frame_bytes - half, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(h->stream2));
   } else {
-    tp.tile0 = 0; tp.ntiles = nt; tp.src = P->arena + ob.off; tp.dst = st + 2 * nf;
+    tp.tile0 = 0; tp.ntiles = nt; tp.src = P->at("out"); tp.dst = st + 2 * nf;
     HIPCHK(h, film_launch_tiles_to_frame(tp, s));
     HIPCHK(h, hipMemcpyAsync(out, st + 2 * nf, frame_bytes, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(h, hipStreamSynchronize(s));
+  drain.armed = false;
   return FILM_OK;
 }
 
@@ -1213,13 +1109,11 @@ int forward_chunk(film_t* h, const float* x0, const float* x1, int B, int H, int
   const size_t in_bytes = (size_t)B * H * W * 3 * sizeof(float);
   const hipMemcpyKind kin = mem_kind == FILM_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   const hipMemcpyKind kout = mem_kind == FILM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  const Buffer& img0 = P->bufs[P->find("img0")];
-  const Buffer& ob = P->bufs[P->find("out")];
-  HIPCHK(h, hipMemcpyAsync(P->arena + img0.off, x0, in_bytes, kin, s));
-  HIPCHK(h, hipMemcpyAsync(P->arena + img0.off + (int64_t)B * H * W * 3, x1, in_bytes, kin, s));
+  HIPCHK(h, hipMemcpyAsync(P->at("img0"), x0, in_bytes, kin, s));
+  HIPCHK(h, hipMemcpyAsync(P->at("img0") + (int64_t)B * H * W * 3, x1, in_bytes, kin, s));
   rc = run_plan(h, P, s);
   if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(out, P->arena + ob.off, in_bytes, kout, s));
+  HIPCHK(h, hipMemcpyAsync(out, P->at("out"), in_bytes, kout, s));
   if (mem_kind == FILM_MEM_HOST) HIPCHK(h, hipStreamSynchronize(s));
   return FILM_OK;
 }

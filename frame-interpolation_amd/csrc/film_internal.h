@@ -139,6 +139,7 @@ struct Plan {
       if (bufs[i].name == n) return (int)i;
     return -1;
   }
+  float* at(const char* name) const { return arena + bufs[find(name)].off; }   // a buffer every plan has ("img0", "out") in the workspace
 };
 
 
@@ -184,8 +185,8 @@ struct film_handle {
   int opt_splitk = 1;     // 1: split-K (ksplit partial sums + ordered reduction) for the deep layers of levels with <= 1024 pixels
   int opt_fuse = 31;       // 1: flow_up fused into the flow-estimator warps, v = res + up into the flow heads (same arithmetic, 12 launches fewer)
   int opt_planar = 1;     // 1: aligned-pyramid levels as three planes (feat0 | feat1 | misc16), each written contiguously by its warp
-  int opt_fold = 1;       // 1: nearest-upsample + 2x2 conv as four sub-pixel phase convolutions (9 taps per 4 outputs)
-  int opt_fold4 = 1;      // (with opt_fold) 1: ... in the difference form on conv_fold4_kernel (4 multiplies per low-resolution pixel instead of 9)
+  int opt_fold2x2 = 1;    // != 0: nearest-upsample + 2x2 conv as four sub-pixel phase convolutions (9 taps per 4 outputs); 1: ... in the difference form
+                          // on conv_fold4_kernel (4 multiplies per low-resolution pixel instead of 9)
   int opt_wino = 1;       // 0: never, 1: Winograd kernels (F(4,3) / F(2,3)) where measured faster (default), 2 / 3: F(2,3) / F(4,3) on every eligible 3x3 conv
   int opt_halo_all = 0;   // 1: halo / split kernels for every eligible 3x3 conv regardless of size (tests, tuning)
   int opt_tune_ms = 0;    // autotune: minimum kernel time spent per candidate (0: two launches)
@@ -199,7 +200,8 @@ struct film_handle {
   int opt_w2d_min_px = 1536; // conv_wino2d_kernel runs the 3x3 layers of levels with at least this many pixels per image (planner rule;
                              // profiles/r04_w2d_min_px_ab.log: 8 or more 8x32 patches per image - 32x56 yes, 32x32 no)
   int opt_w2d_small_px = 256; // ... and of smaller levels down to this many pixels when the level fills >= 65 % of its 8x32 tiles (0: never)
-  int opt_w2d_splitk = 1; // 1: split-K for the nested kernel's K >= 768 layers on levels of <= 4096 pixels, S = min(4, K / 384) (planner rule; option "w2d_splitk" for A/B runs)
+  int opt_w2d_splitk = 1; // >= 1: split-K for the nested kernel's K >= 768 layers on levels of <= 4096 pixels, S = min(4, K / 384); 2..16: and a cap of that many
+                          // K ranges on levels of <= 1024 pixels (planner rule; option "w2d_splitk" for A/B runs)
   int opt_w2d_shape = -1; // tests: >= 0 = every conv_wino2d_kernel op that can run this Wino2dTile shape does
   int opt_fold4_shape = -1; // tests: >= 0 = every conv_fold4_kernel op that can run this Fold4Tile shape does
   int opt_w43_shape = -1; // tests: >= 0 = every conv_wino43_kernel op that can run this Wino43Tile shape does (instead of the autotuned one)

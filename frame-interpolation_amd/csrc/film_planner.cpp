@@ -102,7 +102,7 @@ struct Planner {
     }
     static_cast<ConvWeights&>(op) = L;
     op.b_off = L.b_off;
-    if (h->opt_fold && L.wf_off >= 0 && op.nseg == 1 && segs[0].up && !(H & 1) && !(W & 1)) {
+    if (h->opt_fold2x2 != 0 && L.wf_off >= 0 && op.nseg == 1 && segs[0].up && !(H & 1) && !(W & 1)) {
       // nearest x2 + 2x2 'same' conv == four phase convolutions on the low-resolution input: kernel tap (dy, dx) of
       // output (2y+py, 2x+px) reads input ((2y+py+dy)>>1, (2x+px+dx)>>1) = (y + (py&dy), x + (px&dx)), so phase
       // (0,0) has ONE distinct input pixel, (0,1) and (1,0) two, (1,1) four: 9 taps per 4 outputs instead of 16.
@@ -123,7 +123,7 @@ struct Planner {
       // the difference form (conv_fold4_impl.h): four GEMMs over K on I, Dx, Dy, Dxy - 4 multiplies per low-resolution pixel, not 9.
       // Its own summation family, chosen by the layer alone (every folded layer whose channels come in sixteens).  conv_fold4_launch's
       // layout checks: 16-byte aligned input and output pixels, 32-channel blocks, eight output rows in 32-bit offsets.
-      else if (h->opt_fold4 && h->opt_precision == 0 && L.wf4_off >= 0 && segs[0].v.stride % 4 == 0 && segs[0].v.off % 4 == 0 &&
+      else if (h->opt_fold2x2 == 1 && h->opt_precision == 0 && L.wf4_off >= 0 && segs[0].v.stride % 4 == 0 && segs[0].v.off % 4 == 0 &&
                out.off % 4 == 0 && out.stride % 4 == 0 && L.cout % 32 == 0 && (int64_t)16 * f.W * std::max(out.stride, L.cout) < (1ll << 31))
         fam = FAM_FOLD4;
       set_family(f, fam, (int64_t)NB * f.H * f.W * 2);

@@ -217,9 +217,10 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                  F(4,3) kernel spends 4.5 and the direct convolution 9; fp32 throughout, rounding at the level of the 1-D form).
  *                  0: never.  2: every layer that has the weight copy, on every level (tests).  Drops the cached plans.
  *   "w2d_min_px" n / "w2d_small_px" n  the two level-size thresholds of that rule (A/B runs; a function of the level only - never the batch).
- *   "w2d_splitk" 0/1  1 (default): the nested kernel's K >= 768 layers on levels of <= 4096 pixels per image (the 36x60 level of a 1080p
+ *   "w2d_splitk" 0/1/2..16  1 (default): the nested kernel's K >= 768 layers on levels of <= 4096 pixels per image (the 36x60 level of a 1080p
  *                  tile, the 64x64 level of a 256x256 pair) run as up to four K ranges + the ordered reduction, like "splitk"
- *                  (which also switches it off); factor from the level size and the layer only.  Drops the cached plans.
+ *                  (which also switches it off); factor from the level size and the layer only.  0: never.  n = 2..16 (A/B runs): the
+ *                  same, and the K >= 384 layers on levels of <= 1024 pixels run as up to n K ranges (min(n, K / 192)).  Drops the cached plans.
  *   "w43_shape" n  test knob: every convolution on conv_wino43_kernel that can run tile shape n (Wino43Tile, film_kernels.h)
  *                  does, instead of the autotuned shape; -1 (default) = autotuned.  Results cannot change.  Drops the cached plans.
  *   "w2d_shape" n  the same for conv_wino2d_kernel (Wino2dTile: 0..2 = 8 rows x 32 pixels, 3..5 = 16 x 16 pixels - the latter only on levels it pads no more).

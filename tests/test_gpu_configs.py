@@ -188,6 +188,7 @@ def test_256_against_reference_graph_taps(published):
     g, prov = G.load('256')
     x0, x1 = TI.frame_pair(1, 256, 256, seed=1)
     G.check_inputs(g, x0, x1)
+    eng.set_option('fuse', 31)     # (the default; the end of this test relies on it being the current value)
     aux = eng.forward_with_aux(x0, x1)
     rep = {'image': float(np.abs(aux['image'] - g['image_full']).max()),
            'image_vs_f64_truth': float(np.abs(aux['image'] - g['image_f64']).max()) if 'image_f64' in g.files else 0.0,
@@ -199,6 +200,18 @@ def test_256_against_reference_graph_taps(published):
             rep[f'{d}_res{l}'] = G.diff(g, f'{d}_residual_flow{l}', v)
     print(prov, {k: float(f'{v:.1e}') for k, v in rep.items()})
     assert max(rep.values()) < 2e-4 and rep['image'] < IMAGE_TOL
+    # an option set to the value it has changes nothing: the plan of this forward and its taps stay; another value drops the cached plans
+    from film_hip.engine import FilmError
+    FILM_ERR_STATE = -2            # include/film_hip.h
+    eng.set_option('fuse', 31)
+    assert np.array_equal(eng.tap('out'), aux['image'])
+    try:
+        eng.set_option('fuse', 15)
+        with pytest.raises(FilmError) as ei:
+            eng.tap('out')
+        assert ei.value.code == FILM_ERR_STATE      # no plan has run since
+    finally:
+        eng.set_option('fuse', 31)
 
 
 def test_recursion_T2_tiled_against_reference_order(published, monkeypatch):

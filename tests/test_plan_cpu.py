@@ -354,6 +354,38 @@ def test_executor_option_is_three_valued():
     assert '"graph"   0/1/2' in header and '2 (default)' in header
 
 
+# (key, lowest accepted, highest accepted) of every film_set_option key with a range: the option table of film_engine.cpp and the key list of
+# include/film_hip.h, pinned to each other
+RANGED_OPTIONS = [('graph', 0, 2), ('pack_groups', 1, 4), ('fold2x2', 0, 2), ('winograd', 0, 3), ('lanes', 0, 3), ('wino2d', 0, 2),
+                  ('w2d_small_px', 0, 1 << 30), ('w2d_min_px', 1, 1 << 30), ('w2d_splitk', 0, 16), ('w2d_shape', -1, 5), ('fold4_shape', -1, 1),
+                  ('w43_shape', -1, 31), ('precision', 0, 2)]
+
+
+def test_option_ranges_match_the_header():
+    """Both ends of every ranged option are accepted (or refused for a kernel family the loaded library does not hold, naming FILM_EXTRA_FAMILIES),
+    one below and one above are refused with FILM_ERR_INVALID and a message that starts with the key, an unknown key is FILM_ERR_NOTFOUND, and
+    include/film_hip.h documents every key."""
+    from conftest import has_extra_families
+    from film_hip.engine import FILM_ERR_INVALID, FilmEngine, FilmError
+    from film_hip.options import TINY
+    header = open(os.path.join(ROOT, 'include', 'film_hip.h')).read()
+    eng = FilmEngine(TINY, device=-1)
+    for key, lo, hi in RANGED_OPTIONS:
+        assert f'"{key}"' in header, key
+        for v in (lo, hi):
+            try:
+                eng.set_option(key, v)
+            except FilmError as e:
+                assert not has_extra_families() and e.code == FILM_ERR_INVALID and 'FILM_EXTRA_FAMILIES' in e.msg, (key, v, e.msg)
+        for v in (lo - 1, hi + 1):
+            with pytest.raises(FilmError) as ei:
+                eng.set_option(key, v)
+            assert ei.value.code == FILM_ERR_INVALID and ei.value.msg.startswith(key), (key, v, ei.value.msg)
+    with pytest.raises(FilmError) as ei:
+        eng.set_option('no_such_option', 1)
+    assert ei.value.code == -6 and "unknown option 'no_such_option'" in ei.value.msg     # FILM_ERR_NOTFOUND
+
+
 def test_lane_analysis_orders_every_conflict(tiny_weights):
     """Two-stream replay: for every pair of ops on different lanes that touch overlapping channels of one buffer
     (RAW / WAR / WAW) the later one must be ordered behind the earlier one through the xdeps edges + per-lane
