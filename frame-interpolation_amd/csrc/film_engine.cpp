@@ -436,6 +436,8 @@ constexpr OptionRow kOptions[] = {
     {"autotune", &film_t::opt_autotune, BOOL, false},
     {"max_batch", &film_t::opt_max_batch, NONNEG, false},
     {"host_overlap", &film_t::opt_host_overlap, BOOL, false},
+    {"block_overlap_h", &film_t::opt_block_overlap_h, AS_IS, false, -1, 65535, "block_overlap_h: -1 (what the align padding of a tile holds) or 0 .. 65535 rows"},
+    {"block_overlap_w", &film_t::opt_block_overlap_w, AS_IS, false, -1, 65535, "block_overlap_w: -1 (what the align padding of a tile holds) or 0 .. 65535 columns"},
     {"tune_ms", &film_t::opt_tune_ms, NONNEG, false},
     {"splitk", &film_t::opt_splitk, BOOL, true},
     {"pack_groups", nullptr, AS_IS, false, 1, 4, "pack_groups: 1 .. 4"},
@@ -666,15 +668,34 @@ int max_units(film_t* h, int H, int W, const char* what, const char* advice, int
 }
 // Geometry of a frame cut into block_h x block_w patches, each padded to a multiple of `align` (_pad_to_align, eval/interpolator.py:45-52).
 // The two refusals are the reference's asserts (eval/interpolator.py:84-89), same messages.  tp->B, src, dst and the tile range are the caller's.
+// Options "block_overlap_h" / "block_overlap_w" are resolved here, per axis of nb blocks of p pixels: one block has no overlap; -1 is
+// min(pad0 / 2, p / 2), pad0 = the zero padding of a p-sized patch (the padded tile stays the same); else 2 o <= p is required.  A tile holds
+// e = p + 2 o pixels from film_tile_origin and is padded to `align` like a patch (overlap 0: e = p, the patches of the reference).
 int tile_geometry(film_t* h, int H, int W, int block_h, int block_w, int align, TileMapParams* tp) {
   const int bh = block_h > 0 ? block_h : 1, bw = block_w > 0 ? block_w : 1;
   if (H % bh) return fail(h, FILM_ERR_INVALID, "block_height=%d should evenly divide height=%d.", bh, H);
   if (W % bw) return fail(h, FILM_ERR_INVALID, "block_width=%d should evenly divide width=%d.", bw, W);
   tp->H = H; tp->W = W; tp->bh = bh; tp->bw = bw; tp->ph = H / bh; tp->pw = W / bw;
-  const int hp = (align > 0 && tp->ph % align) ? align - tp->ph % align : 0;
-  const int wp = (align > 0 && tp->pw % align) ? align - tp->pw % align : 0;
-  tp->TH = tp->ph + hp; tp->TW = tp->pw + wp; tp->oy = hp / 2; tp->ox = wp / 2;
+  struct Axis { const char* key; int nb, p, want; int *ov, *e, *T, *off; };
+  const Axis axes[2] = {{"block_overlap_h", bh, tp->ph, h->opt_block_overlap_h, &tp->ovy, &tp->eh, &tp->TH, &tp->oy},
+                        {"block_overlap_w", bw, tp->pw, h->opt_block_overlap_w, &tp->ovx, &tp->ew, &tp->TW, &tp->ox}};
+  for (const Axis& a : axes) {
+    const int pad0 = (align > 0 && a.p % align) ? align - a.p % align : 0;
+    const int o = a.nb == 1 ? 0 : a.want < 0 ? std::min(pad0 / 2, a.p / 2) : a.want;
+    if (2 * (int64_t)o > a.p)
+      return fail(h, FILM_ERR_INVALID, "%s: twice the overlap (%d) must not exceed the patch size %d", a.key, o, a.p);
+    const int e = a.p + 2 * o;
+    const int pad = (align > 0 && e % align) ? align - e % align : 0;
+    *a.ov = o; *a.e = e; *a.T = e + pad; *a.off = pad / 2;
+  }
   return FILM_OK;
+}
+// frame -> tiles and tiles -> frame of the tile range in tp: the reference's patches, or overlapped tiles and their cross-fade
+hipError_t cut_tiles(const TileMapParams& tp, hipStream_t s) {
+  return (tp.ovy | tp.ovx) ? film_launch_frame_to_tiles_overlap(tp, s) : film_launch_frame_to_tiles(tp, s);
+}
+hipError_t join_tiles(const TileMapParams& tp, hipStream_t s) {
+  return (tp.ovy | tp.ovx) ? film_launch_blend_tiles(tp, s) : film_launch_tiles_to_frame(tp, s);
 }
 // The handle's staging buffer in HBM (whole frames of the FILM_MEM_HOST entry points), grown on demand.
 int ensure_stage(film_t* h, size_t bytes, hipStream_t s) {
@@ -751,8 +772,9 @@ int film_interpolate(film_t* h, const float* x0, const float* x1, int B, int H, 
     float* st = (float*)h->stage;
     const size_t nf = frame_bytes / sizeof(float);
     d0 = st; d1 = st + nf; dout = st + 2 * nf;
-    // Host pipeline (round 6): one chunk on the direct two-lane executor - see interpolate_host_pipeline below
-    if (h->opt_host_overlap && !h->opt_profile && h->opt_graph == 2 && h->opt_lanes != 0 && ntiles <= tmax && h->stream2) {
+    // Host pipeline (round 6): one chunk on the direct two-lane executor - see interpolate_host_pipeline below.  It downloads the upper half of
+    // the result before the lower tiles are done; with overlapped tiles that half depends on them, so they take the plain path
+    if (h->opt_host_overlap && !(tp.ovy | tp.ovx) && !h->opt_profile && h->opt_graph == 2 && h->opt_lanes != 0 && ntiles <= tmax && h->stream2) {
       Plan* P = nullptr;
       rc = get_plan(h, ntiles, tp.TH, tp.TW, true, &P);
       if (rc == FILM_OK) return interpolate_host_pipeline(h, P, tp, x0, x1, out, st, frame_bytes, s);
@@ -770,13 +792,13 @@ int film_interpolate(film_t* h, const float* x0, const float* x1, int B, int H, 
     if (rc) return rc;
     tp.tile0 = t0; tp.ntiles = nt;
     tp.src = d0; tp.dst = P->at("img0");
-    HIPCHK(h, film_launch_frame_to_tiles(tp, s));
+    HIPCHK(h, cut_tiles(tp, s));
     tp.src = d1; tp.dst = P->at("img0") + (int64_t)nt * tp.TH * tp.TW * 3;
-    HIPCHK(h, film_launch_frame_to_tiles(tp, s));
+    HIPCHK(h, cut_tiles(tp, s));
     rc = run_plan(h, P, s);
     if (rc) return rc;
     tp.src = P->at("out"); tp.dst = dout;
-    HIPCHK(h, film_launch_tiles_to_frame(tp, s));
+    HIPCHK(h, join_tiles(tp, s));   // (overlapped tiles: chunks add up in tile order on this one stream)
     t0 += nt;
   }
   if (mem_kind == FILM_MEM_HOST) {
@@ -784,6 +806,22 @@ int film_interpolate(film_t* h, const float* x0, const float* x1, int B, int H, 
     HIPCHK(h, hipStreamSynchronize(s));
   }
   return FILM_OK;
+}
+
+int film_tiling_json(film_t* h, int H, int W, int align, int block_h, int block_w, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
+  TileMapParams tp{};
+  int rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
+  if (rc) return rc;
+  std::ostringstream o;
+  o << "{\"overlap_h\":" << tp.ovy << ",\"overlap_w\":" << tp.ovx << ",\"tile_h\":" << tp.eh << ",\"tile_w\":" << tp.ew
+    << ",\"padded_h\":" << tp.TH << ",\"padded_w\":" << tp.TW << ",\"pad_y\":" << tp.oy << ",\"pad_x\":" << tp.ox << ",\"origins_y\":[";
+  for (int i = 0; i < tp.bh; ++i) o << (i ? "," : "") << film_tile_origin(i, tp.ph, tp.ovy, tp.H, tp.eh);
+  o << "],\"origins_x\":[";
+  for (int j = 0; j < tp.bw; ++j) o << (j ? "," : "") << film_tile_origin(j, tp.pw, tp.ovx, tp.W, tp.ew);
+  o << "]}";
+  return copy_out_string(h, o.str(), buf, cap, needed);
 }
 
 // ---- frame sequences ------------------------------------------------------------------------------------------------------------
@@ -849,22 +887,22 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
       TileMapParams q = tp;
       if (nn == T) {   // whole frames: frames j0 .. j0 + kk are consecutive tiles of one frame batch
         q.tile0 = 0; q.ntiles = (kk + 1) * T; q.src = dfr + (size_t)j0 * frame; q.dst = img0;
-        HIPCHK(h, film_launch_frame_to_tiles(q, s));
+        HIPCHK(h, cut_tiles(q, s));
       } else {         // tiles [t0, t0 + nn) of each frame, frame-major
         for (int f = 0; f <= kk; ++f) {
           q.tile0 = t0; q.ntiles = nn; q.src = dfr + (size_t)(j0 + f) * frame; q.dst = img0 + (int64_t)f * nn * tile_floats;
-          HIPCHK(h, film_launch_frame_to_tiles(q, s));
+          HIPCHK(h, cut_tiles(q, s));
         }
       }
       rc = run_plan(h, P, s);
       if (rc) return rc;
       if (nn == T) {
         q.tile0 = 0; q.ntiles = kk * T; q.src = res; q.dst = dout + (size_t)j0 * frame;
-        HIPCHK(h, film_launch_tiles_to_frame(q, s));
-      } else {
+        HIPCHK(h, join_tiles(q, s));
+      } else {         // (overlapped tiles: the ranges of a frame add up in tile order, from its first tile - also after the halving below)
         for (int j = 0; j < kk; ++j) {
           q.tile0 = t0; q.ntiles = nn; q.src = res + (int64_t)j * nn * tile_floats; q.dst = dout + (size_t)(j0 + j) * frame;
-          HIPCHK(h, film_launch_tiles_to_frame(q, s));
+          HIPCHK(h, join_tiles(q, s));
         }
       }
       t0 += nn;

@@ -179,6 +179,10 @@ struct film_handle {
   int opt_graph = 2;
   int opt_profile = 0, opt_autotune = 1;
   int opt_max_batch = 0;  // 0: only the 4 GiB-per-buffer limit
+  // Tiled path: pixels every tile takes from its neighbours on each side of an axis with more than one block; the tiles' results are
+  // cross-faded over the shared pixels (tile_geometry in film_engine.cpp; blend_tiles_kernel).  0 (default): the reference's disjoint
+  // patches.  -1: as much as the tile's align padding holds (the padded tile, and with it the plan, stays the same).
+  int opt_block_overlap_h = 0, opt_block_overlap_w = 0;
   int opt_host_overlap = 1;   // film_interpolate(FILM_MEM_HOST): 1 = the second frame's upload behind the first frame's first layers, the first half of the
                               // result downloaded behind the second half's last layer (film_engine.cpp, "host pipeline"); 0 = copies, then work, then copy
   hipEvent_t pipe_ev[2] = {nullptr, nullptr};   // its two events (second frame in place / first half stitched), lazily created

@@ -197,7 +197,18 @@ struct TileMapParams {
   int TH, TW;        // padded tile
   int oy, ox;        // patch offset inside the tile
   int tile0, ntiles; // tiles [tile0, tile0 + ntiles) of the frame batch are in the tile buffer
+  // Overlapped tiles (options "block_overlap_h" / "block_overlap_w"; read by the *_overlap kernels only): tile (ty, tx) holds the
+  // eh x ew pixels of the frame from (film_tile_origin(ty, ph, ovy, H, eh), film_tile_origin(tx, pw, ovx, W, ew)), at (oy, ox) of
+  // the padded tile.  ovy = ovx = 0: eh = ph, ew = pw, the patches above.
+  int ovy, ovx;      // resolved overlap per axis
+  int eh, ew;        // tile content = ph + 2 ovy x pw + 2 ovx
 };
+// First frame row (column) of overlapped tile i of an axis of n pixels cut into patches of p: the patch grown by o on both sides, moved
+// inwards at the frame's edge so that every tile has e = p + 2 o pixels.
+__host__ __device__ inline int film_tile_origin(int i, int p, int o, int n, int e) {
+  const int s = i * p - o;
+  return s < 0 ? 0 : (s > n - e ? n - e : s);
+}
 
 // Tile id = shape index + CONV_TILE_XCD when the XCD-contiguous block mapping is used.
 enum ConvTile { TILE_128x128 = 0, TILE_256x64 = 1, TILE_256x32 = 2, TILE_64x64 = 3, TILE_128x32 = 4,
@@ -375,6 +386,10 @@ hipError_t film_launch_warp(const WarpParams& p, hipStream_t s);
 hipError_t film_launch_pack_flow(const PackFlowParams& p, hipStream_t s);
 hipError_t film_launch_frame_to_tiles(const TileMapParams& p, hipStream_t s);   // pad + image_to_patches
 hipError_t film_launch_tiles_to_frame(const TileMapParams& p, hipStream_t s);   // crop + patches_to_image
+hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams& p, hipStream_t s);   // the same for overlapped tiles
+// crop + cross-fade of the tiles [tile0, tile0 + ntiles) into the frames: adds to what the tiles below tile0 left in dst, so the
+// launches of one frame go in tile order on one stream
+hipError_t film_launch_blend_tiles(const TileMapParams& p, hipStream_t s);
 // write_image's rounding on the device: dst[i] = uint8(clip(src[i] * 255, 0, 255) + 0.5)  (eval/util.py:51-52)
 hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipStream_t s);
 // fills n floats with a deterministic pseudo-random pattern in [-1, 1) (autotune inputs only)

@@ -561,6 +561,107 @@ __global__ __launch_bounds__(256) void tiles_to_frame_kernel(TileMapParams p) {
   p.dst[(((int64_t)b * p.H + ty * p.ph + y) * p.W + tx * p.pw) * 3 + xc] = v;
 }
 
+// ---- overlapped tiles: every tile carries ovy / ovx pixels of its neighbours, the results are cross-faded ------------------
+// frame_to_tiles_kernel with the tile's content taken from film_tile_origin instead of the patch grid.
+__global__ __launch_bounds__(256) void frame_to_tiles_overlap_kernel(TileMapParams p) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int row = p.TW * 3;
+  const int64_t total = (int64_t)p.ntiles * p.TH * row;
+  if (i >= total) return;
+  const int xc = (int)(i % row);
+  const int64_t r = i / row;
+  const int y = (int)(r % p.TH);
+  const int n = (int)(r / p.TH) + p.tile0;
+  const int b = n / (p.bh * p.bw), t = n % (p.bh * p.bw);
+  const int ty = t / p.bw, tx = t % p.bw;
+  const int sy = y - p.oy, sxc = xc - p.ox * 3;
+  float v = 0.f;
+  if (sy >= 0 && sy < p.eh && sxc >= 0 && sxc < p.ew * 3)
+    v = p.src[(((int64_t)b * p.H + film_tile_origin(ty, p.ph, p.ovy, p.H, p.eh) + sy) * p.W + film_tile_origin(tx, p.pw, p.ovx, p.W, p.ew)) * 3 + sxc];
+  p.dst[i] = v;
+}
+
+// Cross-fade weight (before normalisation) of tile i of an axis at frame position y: the distance to the nearest INTERIOR edge of
+// the tile, counted from 1; an edge on the frame's border does not limit it; 0 outside the tile.  *s = the tile's origin.
+__device__ __forceinline__ float fade_weight(int i, int y, int nb, int p, int o, int n, int e, int* s) {
+  if (i < 0 || i >= nb) return 0.f;
+  *s = film_tile_origin(i, p, o, n, e);
+  if (y < *s || y >= *s + e) return 0.f;
+  int a = 1 << 30;
+  if (*s > 0) a = min(a, y - *s + 1);
+  if (*s + e < n) a = min(a, *s + e - y);
+  return (float)a;
+}
+
+// thread = one float of rows [y0, y0 + ny) of frames [b0, b0 + nfr).  A pixel of block (ky, kx) is covered by tiles of the block
+// rows ky - 1 .. ky + 1 and columns kx - 1 .. kx + 1 only (2 * overlap <= patch).  Over the covering tiles in row-major order:
+// acc = (wy * wx) * v for the first, acc = acc + (wy * wx) * v for the others, wy = a_i(y) / sum_i a_i(y) (one float32 operation
+// each, no fma: this file is built with -ffp-contract=off).  Covering tiles below tile0 were added by an earlier launch - the sum
+// goes on from dst; tiles from tile0 + ntiles on are left to a later one.
+__global__ __launch_bounds__(256) void blend_tiles_kernel(TileMapParams p, int b0, int nfr, int y0, int ny) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int row = p.W * 3;
+  if (i >= (int64_t)nfr * ny * row) return;
+  const int xc = (int)(i % row);
+  const int64_t r = i / row;
+  const int y = y0 + (int)(r % ny);
+  const int b = b0 + (int)(r / ny);
+  const int x = xc / 3, c = xc - 3 * x;
+  const int ky = y / p.ph, kx = x / p.pw;
+  float ay[3], ax[3];
+  int sy[3] = {0, 0, 0}, sx[3] = {0, 0, 0};
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    ay[d] = fade_weight(ky - 1 + d, y, p.bh, p.ph, p.ovy, p.H, p.eh, &sy[d]);
+    ax[d] = fade_weight(kx - 1 + d, x, p.bw, p.pw, p.ovx, p.W, p.ew, &sx[d]);
+  }
+  const float sum_y = (ay[0] + ay[1]) + ay[2], sum_x = (ax[0] + ax[1]) + ax[2];   // (integers below 2^31: exact)
+  const int64_t o = (((int64_t)b * p.H + y) * p.W) * 3 + xc;
+  const int first = b * p.bh * p.bw;
+  float acc = 0.f;
+  bool have = false, mine = false;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy) {
+    if (ay[dy] == 0.f) continue;
+    const float wy = ay[dy] / sum_y;
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      if (ax[dx] == 0.f) continue;
+      const int n = first + (ky - 1 + dy) * p.bw + (kx - 1 + dx);
+      if (n >= p.tile0 + p.ntiles) continue;
+      if (n < p.tile0) {
+        if (!have) { acc = p.dst[o]; have = true; }
+        continue;
+      }
+      const float w = wy * (ax[dx] / sum_x);
+      const float v = p.src[(((int64_t)(n - p.tile0) * p.TH + p.oy + (y - sy[dy])) * p.TW + p.ox + (x - sx[dx])) * 3 + c];
+      const float t = w * v;
+      acc = have ? acc + t : t;
+      have = true; mine = true;
+    }
+  }
+  if (mine) p.dst[o] = acc;
+}
+
+hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams& p, hipStream_t s) {
+  hipLaunchKernelGGL(frame_to_tiles_overlap_kernel, dim3(blocks_for((int64_t)p.ntiles * p.TH * p.TW * 3)), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t film_launch_blend_tiles(const TileMapParams& p, hipStream_t s) {
+  if (p.ntiles <= 0) return hipSuccess;
+  // the frames the tile range touches; within one frame only the rows of its block rows
+  const int T = p.bh * p.bw, last = p.tile0 + p.ntiles - 1;
+  const int b0 = p.tile0 / T, nfr = last / T - b0 + 1;
+  int y0 = 0, y1 = p.H;
+  if (nfr == 1) {
+    y0 = film_tile_origin((p.tile0 % T) / p.bw, p.ph, p.ovy, p.H, p.eh);
+    y1 = film_tile_origin((last % T) / p.bw, p.ph, p.ovy, p.H, p.eh) + p.eh;
+  }
+  hipLaunchKernelGGL(blend_tiles_kernel, dim3(blocks_for((int64_t)nfr * (y1 - y0) * p.W * 3)), dim3(256), 0, s, p, b0, nfr, y0, y1 - y0);
+  return hipGetLastError();
+}
+
 hipError_t film_launch_frame_to_tiles(const TileMapParams& p, hipStream_t s) {
   hipLaunchKernelGGL(frame_to_tiles_kernel, dim3(blocks_for((int64_t)p.ntiles * p.TH * p.TW * 3)), dim3(256), 0, s, p);
   return hipGetLastError();

@@ -179,6 +179,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--align', type=int, default=64, help='If >1, pad the input size so it is evenly divisible by this value.')
     ap.add_argument('--block_height', type=int, default=1)
     ap.add_argument('--block_width', type=int, default=1)
+    ap.add_argument('--block_overlap_height', type=int, default=0,
+                    help='(extension) rows every patch takes from its neighbours, results cross-faded; 0: disjoint patches, -1: what the align padding holds.')
+    ap.add_argument('--block_overlap_width', type=int, default=0, help='(extension) the same for columns.')
     ap.add_argument('--device', type=int, default=0, help='HIP device ordinal.')
     ap.add_argument('--precision', type=int, default=0, choices=[0, 1, 2], help='engine precision mode: 0 fp32 MFMA, 1 bf16x6, 2 bf16x3.')
     ap.add_argument('--metrics_device', default='cpu', choices=['cpu', 'gpu'],
@@ -194,7 +197,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     if not triplets:
         print(f'no image triplets under {args.triplet_dir}', file=sys.stderr)
         return 1
-    it = interpolator_lib.Interpolator(args.model_path, args.align, [args.block_height, args.block_width], device=args.device, precision=args.precision)
+    overlap = (args.block_overlap_height, args.block_overlap_width)
+    it = interpolator_lib.Interpolator(args.model_path, args.align, [args.block_height, args.block_width], device=args.device, precision=args.precision,
+                                       **({'block_overlap': overlap} if any(overlap) else {}))
     totals = run_evaluation(it, triplets, args.output_dir, args.max_examples, args.metrics, args.output_frames,
                             args.model_path, args.triplet_dir, metrics_device=args.metrics_device, batch_size=args.batch_size,
                             io_workers=args.io_workers)

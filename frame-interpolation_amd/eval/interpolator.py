@@ -98,7 +98,7 @@ class Interpolator:
                align: Optional[int] = None,
                block_shape: Optional[List[int]] = None,
                *, device: int = 0, options: Optional[Options] = None,
-               weights=None, precision: int = 0, engine: Optional[FilmEngine] = None) -> None:
+               weights=None, precision: int = 0, engine: Optional[FilmEngine] = None, block_overlap=0) -> None:
     """Loads the weights of a saved model into a HIP engine.
 
     Args:
@@ -113,6 +113,10 @@ class Interpolator:
         (film_set_option "precision", include/film_hip.h).
       engine: (extension) an engine that already holds its weights (a rank that received them by broadcast,
         film_hip.sharding.sharded_interpolator); model_path and weights are then ignored.
+      block_overlap: (extension) pixels every tile of the block_shape path takes from its neighbours, an int for both axes or
+        (height, width); the tiles' results are cross-faded, which removes the step along the patch borders.  -1 = what the align
+        padding of a tile holds (no extra work).  An engine option like precision (film_set_option "block_overlap_h" / "_w",
+        include/film_hip.h): 0 (default, the reference's disjoint patches) leaves the engine as it is.
     """
     self._options = options or PUBLISHED
     if engine is not None:
@@ -130,6 +134,8 @@ class Interpolator:
         self._engine.set_weights(weights)
     if precision:
       self._engine.set_option('precision', int(precision))
+    if np.any(np.asarray(block_overlap) != 0):
+      self._engine.set_block_overlap(block_overlap)
     self._align = align or None
     self._block_shape = block_shape or None
 

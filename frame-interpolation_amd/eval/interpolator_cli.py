@@ -52,6 +52,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--block_width', type=int, default=1, help='Number of patches along width.')
     ap.add_argument('--precision', type=int, default=0, choices=[0, 1, 2],
                     help='(extension) engine precision mode: 0 fp32 MFMA, 1 bf16x6, 2 bf16x3.')
+    ap.add_argument('--block_overlap_height', type=int, default=0,
+                    help='(extension) rows every patch takes from its neighbours; the patches\' results are cross-faded (no step along the '
+                         'patch borders).  0: disjoint patches (default); -1: what the align padding of a patch holds.')
+    ap.add_argument('--block_overlap_width', type=int, default=0, help='(extension) the same for columns.')
     ap.add_argument('--sequence_window', type=int, default=0,
                     help='(extension) 0: one input pair at a time (default).  K >= 2: windows of K consecutive input frames, one feature '
                          'extraction per frame and recursion depth (film_interpolate_sequence); same files.')
@@ -153,9 +157,10 @@ def plan_work(directories: List[str], world: int, rank: int):
     return False, out
 
 
-def tile_mode(n_pairs: int, world: int, ntiles: int) -> bool:
-    """A directory's pairs cannot occupy every rank but its tiles can: shard the tiles of each pair instead."""
-    return world > 1 and ntiles > 1 and 0 < n_pairs < world
+def tile_mode(n_pairs: int, world: int, ntiles: int, overlapped: bool = False) -> bool:
+    """A directory's pairs cannot occupy every rank but its tiles can: shard the tiles of each pair instead - unless the tiles
+    overlap (--block_overlap_*: they are blended in every generation, TileShardedRecursion refuses; the pairs are sharded)."""
+    return world > 1 and ntiles > 1 and 0 < n_pairs < world and not overlapped
 
 
 def process_directory_tile_sharded(directory: str, driver, args, rank: int) -> int:
@@ -224,9 +229,11 @@ def main(argv=None) -> None:
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     block = [args.block_height, args.block_width]
+    overlap = (args.block_overlap_height, args.block_overlap_width)
     directories = [d for d in sorted(glob.glob(args.pattern)) if os.path.isdir(d)]
     if world == 1:
-        it = interpolator_lib.Interpolator(args.model_path, args.align, block, precision=args.precision)
+        it = interpolator_lib.Interpolator(args.model_path, args.align, block, precision=args.precision,
+                                           **({'block_overlap': overlap} if any(overlap) else {}))
         for directory in directories:
             n = process_directory(directory, it, args)
             print(f'{directory}: {n} frames')
@@ -246,11 +253,12 @@ def main(argv=None) -> None:
     # rank works, so the collective timeout is a day, not the 10-minute default of the NCCL watchdog
     dist.init_process_group(backend='nccl', rank=rank, world_size=world, device_id=dev,
                             timeout=datetime.timedelta(hours=24))
-    it = sharded_interpolator(args.model_path, args.align, block, dist, local_rank, precision=args.precision)
+    it = sharded_interpolator(args.model_path, args.align, block, dist, local_rank, precision=args.precision, block_overlap=overlap)
     whole, work = plan_work(directories, world, rank)
     ntiles = max(1, args.block_height) * max(1, args.block_width)
     pairs_of = {d: max(0, len(list_input_frames(d)) - 1) for d in directories}
-    tiled_dirs = [] if whole else [d for d in directories if tile_mode(pairs_of[d], world, ntiles)]
+    overlapped = any(o != 0 and nb > 1 for o, nb in zip(overlap, block))
+    tiled_dirs = [] if whole else [d for d in directories if tile_mode(pairs_of[d], world, ntiles, overlapped)]
     # stale frames are removed by rank 0 before anybody writes (a directory's pairs may be spread over ranks) - only in
     # directories that are in the work list (the single-rank path leaves directories with < 2 inputs untouched)
     if rank == 0 and not whole:

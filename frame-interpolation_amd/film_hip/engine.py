@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = (
     'film_interpolate',
     'film_set_option', 'film_profile_json', 'film_plan_json', 'film_get_tap', 'film_crc32c', 'film_version',
     'film_export_tune', 'film_import_tune', 'film_to_uint8', 'film_load_bundle', 'film_bcast_weights',
-    'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics')
+    'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json')
 
 _lib = None
 
@@ -101,6 +101,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_plan_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_sequence_plan_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
                                             ctypes.c_int64, i64p]
+    lib.film_tiling_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
+                                     ctypes.c_int64, i64p]
     lib.film_get_tap.argtypes = [vp, cp, fp, ctypes.c_int64, i64p]
     lib.film_crc32c.argtypes = [ctypes.c_uint32, vp, ctypes.c_int64]
     lib.film_crc32c.restype = ctypes.c_uint32
@@ -428,6 +430,21 @@ class FilmEngine:
 
     def set_option(self, key: str, value: int) -> None:
         self._check(self._lib.film_set_option(self._h, key.encode(), int(value)))
+        if key in ('block_overlap_h', 'block_overlap_w'):
+            self._block_overlap = tuple(int(value) if key == k else o
+                                        for k, o in zip(('block_overlap_h', 'block_overlap_w'), self.block_overlap))
+
+    @property
+    def block_overlap(self) -> Tuple[int, int]:
+        """The (height, width) values of options "block_overlap_h" / "block_overlap_w" as last set (0: disjoint patches; -1: what the
+        align padding holds); what they resolve to for a frame size: tiling()."""
+        return getattr(self, '_block_overlap', (0, 0))
+
+    def set_block_overlap(self, block_overlap) -> None:
+        """block_overlap: an int for both axes or (height, width) - sets the two options."""
+        oh, ow = (block_overlap, block_overlap) if np.isscalar(block_overlap) else block_overlap
+        self.set_option('block_overlap_h', int(oh))
+        self.set_option('block_overlap_w', int(ow))
 
     # -- introspection ------------------------------------------------------------------------
     def _json_call(self, fn, *args) -> dict:
@@ -443,6 +460,12 @@ class FilmEngine:
     def sequence_plan(self, n_pairs: int, tiles: int, h: int, w: int) -> dict:
         """film_sequence_plan_json: the plan film_interpolate_sequence runs for n_pairs consecutive pairs of `tiles` h x w tiles."""
         return self._json_call(self._lib.film_sequence_plan_json, n_pairs, tiles, h, w)
+
+    def tiling(self, h: int, w: int, align: Optional[int] = None, block_shape=None) -> dict:
+        """film_tiling_json: the tile geometry of an h x w frame with the engine's current block_overlap options (resolved overlap,
+        tile content and padded size, pad offsets, tile origins per axis); refuses what the compute calls refuse.  Needs no GPU."""
+        bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
+        return self._json_call(self._lib.film_tiling_json, int(h), int(w), int(align or 0), bh, bw)
 
     def profile(self) -> dict:
         return self._json_call(self._lib.film_profile_json)

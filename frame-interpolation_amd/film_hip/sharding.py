@@ -66,9 +66,10 @@ def share_tune(engine, dist, src: int = 0) -> None:
         engine.import_tune(objs[0])
 
 
-def sharded_interpolator(model_path, align, block_shape, dist, local_rank: int, precision: int = 0, options=None):
+def sharded_interpolator(model_path, align, block_shape, dist, local_rank: int, precision: int = 0, options=None, *, block_overlap=0):
     """eval.interpolator.Interpolator of this rank's GPU: rank 0 reads + packs the weights of `model_path`, every
-    other rank receives the packed blob by broadcast (RCCL over xGMI) instead of reading and repacking."""
+    other rank receives the packed blob by broadcast (RCCL over xGMI) instead of reading and repacking.
+    block_overlap: as for Interpolator, set on every rank's engine."""
     import torch
     from eval.interpolator import Interpolator
     from .engine import FilmEngine
@@ -79,7 +80,8 @@ def sharded_interpolator(model_path, align, block_shape, dist, local_rank: int, 
     it, err = None, None
     if rank == 0:
         try:
-            it = Interpolator(model_path, align, block_shape, device=local_rank, options=opt, precision=precision)
+            it = Interpolator(model_path, align, block_shape, device=local_rank, options=opt, precision=precision,
+                              block_overlap=block_overlap)
         except Exception as e:   # noqa: BLE001 - the other ranks must not be left waiting in the broadcast
             err = e
     ok = torch.tensor([0 if err is not None else 1], dtype=torch.int32, device=dev)
@@ -91,7 +93,7 @@ def sharded_interpolator(model_path, align, block_shape, dist, local_rank: int, 
     engine = it.engine if rank == 0 else FilmEngine(opt, device=local_rank)
     broadcast_weights(engine, dist, src=0, device=dev)
     if rank != 0:
-        it = Interpolator('', align, block_shape, options=opt, precision=precision, engine=engine)
+        it = Interpolator('', align, block_shape, options=opt, precision=precision, engine=engine, block_overlap=block_overlap)
     return it
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -145,9 +147,19 @@ class TileShardedRecursion:
     the other ranks.  batch_fn: see recurse_tiles (DeviceInterpolator(engine, align).batch on GPUs).  No collective
     before the final gather; with one rank this is the tiled Interpolator path run tile-wise (bit-identical, test)."""
 
-    def __init__(self, batch_fn, block_shape: List[int], dist=None, dst: int = 0, collective_at_world1: bool = False):
+    def __init__(self, batch_fn, block_shape: List[int], dist=None, dst: int = 0, collective_at_world1: bool = False, engine=None):
         self.batch_fn = batch_fn
         self.block_shape = [int(block_shape[0]), int(block_shape[1])]
+        # Overlapped tiles (engine option block_overlap) are blended after EVERY generation, so a tile of a generated frame depends on its
+        # neighbours' parents too: a tile-local recursion tree is a different computation.  `engine`: the FilmEngine behind batch_fn
+        # (default: the one of a DeviceInterpolator's bound method).  A requested overlap (-1 included: what it resolves to is known per
+        # frame size only) on an axis with more than one block is refused
+        if engine is None:
+            engine = getattr(getattr(batch_fn, '__self__', None), '_engine', None)
+        overlap = getattr(engine, 'block_overlap', (0, 0))
+        if any(o != 0 and nb > 1 for o, nb in zip(overlap, self.block_shape)):
+            raise ValueError(f'TileShardedRecursion keeps a tile\'s whole recursion on one rank, which is not what block_overlap = '
+                             f'{tuple(overlap)} computes (tiles are blended in every generation): shard the frame pairs instead')
         # collective_at_world1: tests drive the gather through the process group even when it has a single rank
         self.dist = dist if (dist is not None and dist.is_initialized() and
                              (dist.get_world_size() > 1 or collective_at_world1)) else None

@@ -54,10 +54,13 @@ class DeviceInterpolator:
     """Interpolator.__call__ semantics (eval/interpolator.py:178-209) on frames that already live
     in HBM: float32 CUDA(=HIP) tensors in, float32 CUDA tensor out, no host round trip.
 
-    Asynchronous on the current torch stream."""
+    Asynchronous on the current torch stream.  block_overlap (an int or (height, width); -1 = what the align padding holds): overlapped,
+    cross-faded tiles - an option of the ENGINE (eval.interpolator.Interpolator), so 0 (default) leaves the engine as it is."""
 
-    def __init__(self, engine: FilmEngine, align: Optional[int] = None, block_shape: Optional[List[int]] = None):
+    def __init__(self, engine: FilmEngine, align: Optional[int] = None, block_shape: Optional[List[int]] = None, *, block_overlap=0):
         self._engine = engine
+        if block_overlap not in (0, (0, 0), [0, 0]):
+            engine.set_block_overlap(block_overlap)
         self._align = align or None
         self._block_shape = block_shape or None
 

@@ -230,8 +230,28 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                  results do not change
  *   "host_overlap" 0/1  1 (default): film_interpolate with FILM_MEM_HOST pipelines its copies with the work - the second frame is uploaded
  *                  while the first layers run on the first frame's tiles, the upper half of the result is downloaded while the last layer
- *                  computes the lower half (one frame, an even number of block rows); 0: upload, work, download.  Same bits. */
+ *                  computes the lower half (one frame, an even number of block rows); 0: upload, work, download.  Same bits.
+ *                  (Not taken with overlapped tiles, whose upper half depends on the lower tiles: upload, work, download.)
+ *   "block_overlap_h" o / "block_overlap_w" o  (extension; -1 .. 65535, default 0 = the reference's disjoint patches, today's kernels)
+ *                  the tiled path of film_interpolate / film_interpolate_sequence, per axis of nb blocks of p = n / nb pixels:
+ *                  every tile takes o pixels of its neighbours on both sides and the tiles' results are cross-faded over the
+ *                  shared pixels, so that no step is left along the patch borders.  nb == 1: no overlap.  -1 ("free"):
+ *                  o = min(pad0 / 2, p / 2), pad0 = the zero padding `align` gives a p-sized patch - the padded tile and the
+ *                  plan stay the same.  Otherwise 2 o <= p, else the compute calls and film_tiling_json return FILM_ERR_INVALID.
+ *                  Tile i holds the e = p + 2 o pixels from s_i = clamp(i p - o, 0, n - e) (tiles at the frame's edge reach 2 o
+ *                  inwards), padded to `align` like a patch.  Weight of tile i at position y inside it: a_i(y) = the distance to
+ *                  its nearest interior edge (y - s_i + 1, s_i + e - y; an edge on the frame's border does not limit it),
+ *                  normalised in float32, w_i(y) = a_i(y) / sum_i a_i(y).  A pixel = sum over the covering tiles (i, j) in
+ *                  row-major order of (wy_i * wx_j) * value, float32, one rounding per operation, no fused multiply-add;
+ *                  independent of how the tiles are chunked.  Does not drop the cached plans (their key carries the tile size). */
 int film_set_option(film_t* h, const char* key, int64_t value);
+
+/* The tile geometry film_interpolate / film_interpolate_sequence use for H x W frames with these arguments and the handle's current
+ * "block_overlap_h" / "block_overlap_w" as JSON (buf / capacity / needed as film_plan_json; works on plan-only handles):
+ * "overlap_h", "overlap_w" (resolved), "tile_h", "tile_w" (tile content), "padded_h", "padded_w" (the H x W of the plan),
+ * "pad_y", "pad_x" (content offset inside the padded tile), "origins_y", "origins_x" (first frame row / column of every tile row /
+ * column).  Same refusals as the compute calls (block divisibility, overlap larger than half a patch). */
+int film_tiling_json(film_t* h, int H, int W, int align, int block_h, int block_w, char* buf, int64_t capacity, int64_t* needed);
 
 /* Autotune choices across processes.  film_export_tune writes text (buf / capacity / needed as film_plan_json): a header
  * line with the library version, then "<conv shape signature>\t<tile id>" per shape this handle measured or imported.
