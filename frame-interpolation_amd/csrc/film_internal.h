@@ -2,8 +2,9 @@
 // internal functions that cross file boundaries.  Nothing here is part of the C-ABI (include/film_hip.h).
 //
 //   film_engine.cpp   C-ABI entry points, options, executor (launch, autotune, hipGraph capture, profiling), chunking
-//   film_planner.cpp  Planner: the graph of models/film_net/interpolator.py:89-207 as an op list over one workspace arena,
-//                     kernel-family decisions, the two-lane dependency analysis, film_plan_json's text
+//   film_planner.cpp  the kernel decisions (family and split-K factor of a convolution: plain_conv_family / folded_conv_family / conv_ksplit),
+//                     Planner: the graph of models/film_net/interpolator.py:89-207 as an op list over one workspace arena, one member
+//                     function per stage; the two-lane dependency analysis; film_plan_json's text
 //   film_layers.cpp   the layer table (weight names, shapes, channel permutations) and the kernel-layout packer
 #pragma once
 #include <hip/hip_runtime.h>
@@ -67,7 +68,7 @@ struct OpDesc : ConvWeights {
   SegDesc seg[FILM_MAX_SEG];
   int nseg = 0;
   int ksize = 1, leaky = 0, Cout = 0, Ctot = 0, tile = 0;
-  ConvFamily family = FAM_BUF;        // conv: the kernel family (Planner::conv); tile carries its flag bits
+  ConvFamily family = FAM_BUF;        // conv: the kernel family (plain_conv_family / folded_conv_family, film_planner.cpp); tile carries its flag bits
   int64_t b_off = 0;
   int64_t w2_off = 0, b2_off = 0;     // flow_head: second 1x1 conv
   int ksplit = 1;                     // conv (conv_buf_kernel): split-K factor, partial sums at part_off (film_kernels.h)
@@ -142,6 +143,15 @@ struct Plan {
   float* at(const char* name) const { return arena + bufs[find(name)].off; }   // a buffer every plan has ("img0", "out") in the workspace
 };
 
+// The bits of option "fuse" (film_handle::opt_fuse; include/film_hip.h): small-launch fusion, identical arithmetic and bit-identical results
+enum FuseBit {
+  FUSE_FLOW_UP = 1,    // tf.image.resize(2 * v) of the flow estimator inside the warp kernels that consume it
+  FUSE_FLOW_ADD = 2,   // v = residual + upsampled flow inside the flow-head kernels
+  FUSE_MISC16 = 4,     // the warped images and the half flows of the t = 0.5 stage (the sixteen miscellaneous channels of an aligned level)
+                       // inside the second feature warp of the level
+  FUSE_POOL = 8,       // AveragePooling2D of the sub-extractor stages in the epilogue of the convolution in front of it
+  FUSE_RGB_HEAD = 16,  // the RGB head (1x1 convolution, fusion.py:138-140) in the epilogue of the last decoder layer
+};
 
 }  // namespace film_internal
 
@@ -187,7 +197,7 @@ struct film_handle {
                               // result downloaded behind the second half's last layer (film_engine.cpp, "host pipeline"); 0 = copies, then work, then copy
   hipEvent_t pipe_ev[2] = {nullptr, nullptr};   // its two events (second frame in place / first half stitched), lazily created
   int opt_splitk = 1;     // 1: split-K (ksplit partial sums + ordered reduction) for the deep layers of levels with <= 1024 pixels
-  int opt_fuse = 31;       // 1: flow_up fused into the flow-estimator warps, v = res + up into the flow heads (same arithmetic, 12 launches fewer)
+  int opt_fuse = 31;      // FuseBit mask: flow_up fused into the flow-estimator warps, v = res + up into the flow heads, ... (same arithmetic, 12 launches fewer)
   int opt_planar = 1;     // 1: aligned-pyramid levels as three planes (feat0 | feat1 | misc16), each written contiguously by its warp
   int opt_fold2x2 = 1;    // != 0: nearest-upsample + 2x2 conv as four sub-pixel phase convolutions (9 taps per 4 outputs); 1: ... in the difference form
                           // on conv_fold4_kernel (4 multiplies per low-resolution pixel instead of 9)

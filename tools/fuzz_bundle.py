@@ -8,12 +8,8 @@ from somewhere else.  Plan-only handles: runs without a GPU.  Test infrastructur
 
 Under AddressSanitizer (the host translation units compile with g++; the kernel launchers are never reached from a plan-only handle):
 
-  cd frame-interpolation_amd/csrc && for f in film_bundle film_engine film_layers film_planner; do \\
-      g++ -std=c++17 -O1 -g -fsanitize=address -fno-omit-frame-pointer -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \\
-          -DFILM_SRC_ID='"asan"' -c $f.cpp -o /tmp/asan/$f.o; done
-  (stubs for the 12 undefined film_launch_* symbols: `int s(void) __asm__("<mangled name>"); int s(void) { abort(); }` each)
-  g++ -shared -fPIC -fsanitize=address -o /tmp/asan/libfilm_hip_asan.so /tmp/asan/*.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
-  FILM_NO_TORCH=1 FILM_HIP_LIB=/tmp/asan/libfilm_hip_asan.so ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 \\
+  tools/sanitize/build_host.sh address /tmp/asan      (every csrc/*.cpp + aborting stubs for what lives in the .hip units)
+  FILM_NO_TORCH=1 FILM_HIP_LIB=/tmp/asan/libfilm_hip_address.so ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 \\
       LD_PRELOAD="$(g++ -print-file-name=libasan.so) $(g++ -print-file-name=libstdc++.so.6)" python tools/fuzz_bundle.py 7 150 0
   (libstdc++ in LD_PRELOAD: ASan's __cxa_throw interceptor must find the real one when the process starts; python does not link it)
 

@@ -20,3 +20,6 @@ STUB(hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams&, hipStre
 STUB(hipError_t film_launch_blend_tiles(const TileMapParams&, hipStream_t))
 STUB(hipError_t film_launch_to_uint8(const float*, uint8_t*, int64_t, hipStream_t))
 STUB(hipError_t film_launch_fill_random(float*, int64_t, uint32_t, hipStream_t))
+// metrics_kernels.hip (film_image_metrics refuses a plan-only handle before it reaches either)
+STUB(void film_metrics_layout(MetricsParams&))
+STUB(hipError_t film_launch_image_metrics(const MetricsParams&, hipStream_t))
