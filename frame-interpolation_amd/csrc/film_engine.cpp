@@ -1193,5 +1193,54 @@ int film_get_tap(film_t* h, const char* name, float* dst, int64_t cap, int64_t d
   return FILM_OK;
 }
 
+// ---- Debug / tests: one planned launch on a workspace the caller controls (include/film_hip.h) ------------------------------------------
+namespace {
+int debug_plan(film_t* h, int B, int H, int W, int tiles, Plan** P) {
+  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle has no device");
+  if (!h->finalized) return fail(h, FILM_ERR_STATE, "weights are not finalized");
+  if (tiles < 0 || (tiles > 0 && B % tiles)) return fail(h, FILM_ERR_INVALID, "tiles must be 0 (pair plan) or divide B (sequence plan)");
+  HIPCHK(h, hipSetDevice(h->device));
+  return get_plan(h, B, H, W, true, P, tiles);
+}
+}  // namespace
+
+int film_debug_arena(film_t* h, int B, int H, int W, int tiles, int64_t offset, int64_t count, float* data, int write) {
+  if (!h) return FILM_ERR_INVALID;
+  if (!data || offset < 0 || count < 0) return fail(h, FILM_ERR_INVALID, "film_debug_arena: NULL data or a negative range");
+  Plan* P = nullptr;
+  int rc = debug_plan(h, B, H, W, tiles, &P);
+  if (rc) return rc;
+  if (offset > P->arena_floats || count > P->arena_floats - offset)
+    return fail(h, FILM_ERR_INVALID, "film_debug_arena: floats %lld .. %lld leave the workspace of %lld floats", (long long)offset,
+                (long long)(offset + count), (long long)P->arena_floats);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (count > 0) {
+    if (write) HIPCHK(h, hipMemcpy(P->arena + offset, data, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
+    else HIPCHK(h, hipMemcpy(data, P->arena + offset, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  h->last_plan = P;
+  return FILM_OK;
+}
+
+int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int candidate, int* n_candidates) {
+  if (!h) return FILM_ERR_INVALID;
+  Plan* P = nullptr;
+  int rc = debug_plan(h, B, H, W, tiles, &P);
+  if (rc) return rc;
+  if (index < 0 || (size_t)index >= P->ops.size())
+    return fail(h, FILM_ERR_INVALID, "film_debug_run_op: op %d of a plan of %zu ops", index, P->ops.size());
+  OpDesc op = P->ops[(size_t)index];
+  std::vector<int> cands;
+  if (op.kind == OP_CONV) cands = conv_candidates(op);
+  if (n_candidates) *n_candidates = (int)cands.size();
+  if (candidate < -1 || candidate >= (int)cands.size())   // (a non-conv op has no candidates: -1 only)
+    return fail(h, FILM_ERR_INVALID, "film_debug_run_op: candidate %d of op %d ('%s'), which has %zu", candidate, index, op.tag.c_str(), cands.size());
+  if (candidate >= 0) op.tile = cands[(size_t)candidate];
+  HIPCHK(h, launch_op(op, P->arena, h->packed_dev, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->last_plan = P;
+  return FILM_OK;
+}
+
 }  // extern "C"
 

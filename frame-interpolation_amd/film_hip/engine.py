@@ -52,7 +52,8 @@ EXPORTED_SYMBOLS = (
     'film_interpolate',
     'film_set_option', 'film_profile_json', 'film_plan_json', 'film_get_tap', 'film_crc32c', 'film_version',
     'film_export_tune', 'film_import_tune', 'film_to_uint8', 'film_load_bundle', 'film_bcast_weights',
-    'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json')
+    'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json',
+    'film_debug_arena', 'film_debug_run_op')
 
 _lib = None
 
@@ -115,6 +116,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_bcast_weights.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp]
     lib.film_image_metrics.argtypes = [vp, fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_double, fp, ctypes.c_int, vp]
+    lib.film_debug_arena.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, fp, ctypes.c_int]
+    lib.film_debug_run_op.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_int)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ('film_destroy',):
@@ -477,6 +481,28 @@ class FilmEngine:
         out = np.empty(shape, dtype=np.float32)
         self._check(self._lib.film_get_tap(self._h, name.encode(), out.ctypes.data, out.size, dims))
         return out
+
+    # -- debug / tests: one planned launch on a workspace the caller controls ---------------------------------
+    def debug_arena_write(self, key, offset: int, data: np.ndarray) -> None:
+        """film_debug_arena, host -> workspace: key = (B, H, W) or (B, H, W, tiles) of the device plan, data float32."""
+        b, h, w, tiles = (tuple(key) + (0,))[:4]
+        a = np.ascontiguousarray(data, dtype=np.float32)
+        self._check(self._lib.film_debug_arena(self._h, b, h, w, tiles, int(offset), a.size, a.ctypes.data, 1))
+
+    def debug_arena_read(self, key, offset: int, count: int) -> np.ndarray:
+        """film_debug_arena, workspace -> host: `count` floats from float offset `offset`."""
+        b, h, w, tiles = (tuple(key) + (0,))[:4]
+        out = np.empty(int(count), np.float32)
+        self._check(self._lib.film_debug_arena(self._h, b, h, w, tiles, int(offset), out.size, out.ctypes.data, 0))
+        return out
+
+    def debug_run_op(self, key, index: int, candidate: int = -1) -> int:
+        """film_debug_run_op: launches op `index` of the plan once (candidate -1: the plan's tile, k >= 0: entry k of the op's
+        autotune candidate list) and returns the length of that list (0 for ops that are no convolutions)."""
+        b, h, w, tiles = (tuple(key) + (0,))[:4]
+        n = ctypes.c_int(0)
+        self._check(self._lib.film_debug_run_op(self._h, b, h, w, tiles, int(index), int(candidate), ctypes.byref(n)))
+        return n.value
 
     def forward_with_aux(self, x0: np.ndarray, x1: np.ndarray) -> Dict[str, object]:
         """The reference model's output dictionary with `use_aux_outputs` on (models/film_net/interpolator.py:

@@ -284,6 +284,22 @@ int film_sequence_plan_json(film_t* h, int n_pairs, int tiles_per_frame, int H, 
  * models/film_net/interpolator.py:191-199. */
 int film_get_tap(film_t* h, const char* name, float* dst, int64_t capacity_floats, int64_t dims[4]);
 
+/* Debug / tests: ONE planned kernel launch on a workspace the caller controls (tests/op_harness.py, tests/test_ops_gpu.py).  Both take
+ * the plan key (B, H, W, tiles): tiles = 0 for the plan of film_forward / film_interpolate, > 0 for the sequence plan of B / tiles pairs
+ * of `tiles` tiles (film_sequence_plan_json).  Both create the device plan as a forward would (workspace, autotune when the option is
+ * on) and make it the plan film_get_tap reads.  FILM_ERR_NO_DEVICE on plan-only handles, FILM_ERR_STATE before film_finalize.
+ * Neither is on the forward path.
+ * film_debug_arena: copies `count` floats at float offset `offset` of that plan's workspace ("arena_floats" and every "off" of
+ * film_plan_json) to the host array `data` (write == 0) or from it (write != 0), after the handle's stream has drained.
+ * FILM_ERR_INVALID when the range leaves the workspace. */
+int film_debug_arena(film_t* h, int B, int H, int W, int tiles, int64_t offset, int64_t count, float* data, int write);
+/* film_debug_run_op: launches op `index` ("ops" of film_plan_json) of that plan once on the handle's stream and synchronises.
+ * candidate == -1 runs the tile the plan holds; candidate == k >= 0 runs entry k of the autotune candidate list of the op's kernel
+ * family for this op - the only way to choose a tile, so a shape the family's own rule excludes cannot be launched.  *n_candidates
+ * (may be NULL) receives the length of that list: 0 for an op that is no convolution, which accepts -1 only.  FILM_ERR_INVALID: no
+ * such op, no such candidate. */
+int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int candidate, int* n_candidates);
+
 /* The per-image evaluation metrics of the benchmark loop on the device: the reference's losses/losses.py:72-113 (l1, l2, psnr, ssim
  * of eval/eval_cli.py:160-170), restated in frame-interpolation_amd/eval/metrics.py, whose arithmetic the kernels follow (float32
  * differences for l1 / l2, float64 differences for psnr, float64 SSIM: 11-tap Gaussian window, sigma 1.5, 'VALID', k1 0.01, k2 0.03).
