@@ -1,6 +1,6 @@
 // conv_foldx3_impl.h -- OPT-IN precision mode "bf16x3" for the decoder's nearest-x2 upsample + 2x2 'same' convolution
 // (fusion.py:133-135), in its sub-pixel form: output (2y+py, 2x+px) = sum over the taps (a, b), a <= py, b <= px, of
-// in(y+a, x+b) * Wsum[py][px][a][b]  -  nine (tap, phase) products per four outputs (film_engine.cpp sums the kernel
+// in(y+a, x+b) * Wsum[py][px][a][b]  -  nine (tap, phase) products per four outputs (film_layers.cpp sums the kernel
 // taps that read the same input pixel at film_finalize).  The fp32 path runs the four phases as four gathers of
 // conv_buf_kernel; here ONE halo-staged patch of the low-resolution input serves all nine products:
 //

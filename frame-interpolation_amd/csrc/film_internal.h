@@ -1,7 +1,11 @@
 // film_internal.h -- what the translation units of libfilm_hip.so share: the plan / op / layer / handle structures and the
 // internal functions that cross file boundaries.  Nothing here is part of the C-ABI (include/film_hip.h).
 //
-//   film_engine.cpp   C-ABI entry points, options, executor (launch, autotune, hipGraph capture, profiling), chunking
+//   film_engine.cpp   C-ABI entry points: handle lifetime, the option table, the JSON queries, tiling and chunking of film_forward /
+//                     film_interpolate / film_interpolate_sequence, the host-buffer pipeline, taps, the debug entry points
+//   film_exec.cpp     the executor: launch of one op, the two-lane issue, run_plan (eager, hipGraph capture / replay, profiling)
+//   film_tune.cpp     the tile candidates of each kernel family, the autotuner, the tune cache as text
+//   film_plans.cpp    the plan cache with its workspace arenas and eviction, the units-per-invocation limits
 //   film_planner.cpp  the kernel decisions (family and split-K factor of a convolution: plain_conv_family / folded_conv_family / conv_ksplit),
 //                     Planner: the graph of models/film_net/interpolator.py:89-207 as an op list over one workspace arena, one member
 //                     function per stage; the two-lane dependency analysis; film_plan_json's text
@@ -266,6 +270,33 @@ inline FamilyCodes family_codes(ConvFamily f) {
   }
   return c;
 }
+
+// ---- film_engine.cpp
+int copy_out_string(film_t* h, const std::string& s, char* buf, int64_t cap, int64_t* needed);   // a text result of the C-ABI, or its size
+
+// ---- film_exec.cpp
+hipError_t launch_op(const OpDesc& op, float* arena, const float* wts, hipStream_t s);
+bool batch_splittable(const OpDesc& op, int nparts);
+OpDesc batch_part(const OpDesc& op, int part, int nparts);
+// Hooks of film_interpolate's host-buffer pipeline into the two-lane issue (see there): `head` = the leading main-lane convolutions that run per
+// input frame (part 0 = the tiles of x0 - launched by the caller BEFORE the second frame's upload; issue_lanes launches part 1), `tail` = the
+// last op (the decoder's last layer + RGB head) runs as two tile halves with `mid_tail` between them (stitch + download of the first half).
+struct LanePipe {
+  std::vector<size_t> head;
+  bool tail = false;
+  std::function<hipError_t()> mid_tail;
+};
+hipError_t issue_lanes(film_t* h, Plan* P, hipStream_t main, bool capturing, const LanePipe* lp = nullptr);
+int run_plan(film_t* h, Plan* P, hipStream_t s);
+
+// ---- film_tune.cpp (the nine *_candidates of kConvFamily: film_kernels.h)
+std::vector<int> conv_candidates(const OpDesc& op);
+int autotune_plan(film_t* h, Plan* P);
+
+// ---- film_plans.cpp
+int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles = 0);
+void drop_plans(film_t* h);   // waits for the device, then frees every cached plan
+int max_units(film_t* h, int H, int W, const char* what, const char* advice, int* units);
 
 // ---- film_planner.cpp
 int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles = 0);   // fills P->bufs / ops / arena_floats for (B, H, W) (tiles > 0: sequence plan)

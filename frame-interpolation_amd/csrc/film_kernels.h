@@ -325,7 +325,7 @@ struct ConvWeights {
                           //     Sy = W10 + W11, W11 as [Cout/32][ctot/8][plane 4][K half][32][4]: 4*ctot*cout in all
 };
 
-namespace film_internal {   // the autotune candidates of each family (film_engine.cpp)
+namespace film_internal {   // the autotune candidates of each family (film_tune.cpp)
 struct OpDesc;
 std::vector<int> tile_candidates(const OpDesc&), c3_candidates(const OpDesc&), wino2d_candidates(const OpDesc&), wino43_candidates(const OpDesc&),
     fold4_candidates(const OpDesc&), halo_candidates(const OpDesc&), wino_candidates(const OpDesc&), winox3_candidates(const OpDesc&),

@@ -1,0 +1,137 @@
+// film_plans.cpp -- the handle's plan cache: get_plan builds, tunes and keeps plans with their workspace arenas and evicts the least
+// recently used; max_units says how many units one model invocation may take under the buffer and workspace limits.
+#include "film_internal.h"
+
+namespace film_internal {
+namespace {
+void free_plan(Plan* p) {
+  if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
+  if (p->graph) (void)hipGraphDestroy(p->graph);
+  for (auto e : p->ev) (void)hipEventDestroy(e);
+  for (auto e : p->lane_ev) if (e) (void)hipEventDestroy(e);
+  if (p->arena) (void)hipFree(p->arena);
+}
+
+// Plan `index` leaves the cache with everything it holds on the device.  Work that may still run on it is the caller's to wait for.
+void forget_plan(film_t* h, size_t index) {
+  if (h->last_plan == h->plans[index].get()) h->last_plan = nullptr;
+  free_plan(h->plans[index].get());
+  h->plans.erase(h->plans.begin() + index);
+}
+
+constexpr int64_t kMaxBufferBytes = 0xFFF00000ll;
+// One model invocation also keeps its workspace below this (a fifth of the HBM): 15 tiles of 960x576, one untiled 4K frame
+constexpr int64_t kMaxArenaBytes = 64ll << 30;
+// ... and below 60 % of the HBM this handle could get right now (free memory + what its own cached plans hold): other
+// ranks' handles, torch's allocator or a smaller part may share the device.
+int64_t arena_budget_bytes(film_t* h) {
+  int64_t cap = kMaxArenaBytes;
+  if (!h->plan_only) {
+    size_t fr = 0, tot = 0;
+    if (hipSetDevice(h->device) == hipSuccess && hipMemGetInfo(&fr, &tot) == hipSuccess) {
+      int64_t held = 0;
+      for (auto& p : h->plans) if (p->arena) held += p->arena_floats * (int64_t)sizeof(float);
+      cap = std::min<int64_t>(cap, ((int64_t)fr + held) / 10 * 6);
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  return std::max<int64_t>(cap, 1);
+}
+}  // namespace
+
+void drop_plans(film_t* h) {
+  if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }   // (forwards may still be running on them)
+  while (!h->plans.empty()) forget_plan(h, h->plans.size() - 1);
+}
+
+// Plans are cached per (B, H, W, tiles): tiles = 0 for pair plans, > 0 for sequence plans (Plan::tiles) - the two kinds never
+// stand in for each other.  Both count toward the three device plans kept alive.
+int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles) {
+  const int div = 1 << (h->cfg.pyramid_levels - 1);
+  if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
+  if (H % div || W % div)
+    return fail(h, FILM_ERR_INVALID, "input height and width (%d x %d) must be divisible by %d = 2^(pyramid_levels-1); "
+                "pad first (Interpolator align)", H, W, div);
+  // tfa dense_image_warp needs a >= 2x2 grid at every warped level
+  const int wl = std::max(h->cfg.pyramid_levels - 2, h->cfg.fusion_pyramid_levels - 1);
+  if ((H >> wl) < 2 || (W >> wl) < 2)
+    return fail(h, FILM_ERR_INVALID, "input %d x %d too small: warped pyramid level %d would be smaller than 2x2", H, W, wl);
+  if ((int64_t)2 * B * H * W >= (int64_t)1 << 31) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
+  for (auto& p : h->plans)
+    if (p->B == B && p->H == H && p->W == W && p->tiles == tiles && (!need_device || p->arena)) { *out = p.get(); p->last_use = ++h->tick; return FILM_OK; }
+  if (need_device)   // a description-only plan of this shape (film_plan_json, max_units) is superseded, not kept beside the new one
+    for (size_t i = 0; i < h->plans.size(); ++i)
+      if (h->plans[i]->B == B && h->plans[i]->H == H && h->plans[i]->W == W && h->plans[i]->tiles == tiles) { forget_plan(h, i); break; }
+  std::unique_ptr<Plan> P(new Plan);
+  int rc = plan_build(h, P.get(), B, H, W, tiles);
+  if (rc) return rc;
+  if (need_device) {
+    // keep at most 3 device plans alive (workspaces are GBs at 1080p tiles)
+    size_t alive = 0;
+    for (auto& p : h->plans) alive += p->arena != nullptr;
+    while (alive >= 3) {
+      size_t victim = h->plans.size();
+      for (size_t i = 0; i < h->plans.size(); ++i)
+        if (h->plans[i]->arena && (victim == h->plans.size() || h->plans[i]->last_use < h->plans[victim]->last_use)) victim = i;
+      if (victim == h->plans.size()) break;
+      // a graph launch of the victim on the caller's stream may still be running (device-resident callers are
+      // asynchronous): its graph, events and workspace must outlive it
+      (void)hipSetDevice(h->device);
+      (void)hipDeviceSynchronize();
+      forget_plan(h, victim);
+      --alive;
+    }
+    hipError_t e = hipMalloc(&P->arena, (size_t)P->arena_floats * sizeof(float));
+    if (e != hipSuccess && alive > 0) {   // out of memory: give back the other plans' workspaces and try once more
+      (void)hipGetLastError();
+      (void)hipDeviceSynchronize();
+      for (size_t i = h->plans.size(); i-- > 0;)
+        if (h->plans[i]->arena) forget_plan(h, i);   // (last_plan is one of them: only a plan that ran is remembered)
+      e = hipMalloc(&P->arena, (size_t)P->arena_floats * sizeof(float));
+    }
+    if (e != hipSuccess) {
+      P->arena = nullptr;
+      return fail(h, FILM_ERR_NOMEM, "workspace hipMalloc of %.1f MB failed: %s", P->arena_floats * 4e-6, hipGetErrorString(e));
+    }
+    HIPCHK(h, hipMemsetAsync(P->arena, 0, (size_t)P->arena_floats * sizeof(float), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->opt_autotune && h->finalized) {
+      int trc = autotune_plan(h, P.get());
+      if (trc) { free_plan(P.get()); return trc; }
+    }
+  }
+  // test knobs: one tile shape for every F(4,3) / nested-Winograd / conv_fold4_kernel op it fits (same bits as any other, by construction)
+  const std::pair<ConvFamily, int> forced[] = {{FAM_W43, h->opt_w43_shape}, {FAM_W2D, h->opt_w2d_shape}, {FAM_FOLD4, h->opt_fold4_shape}};
+  for (const auto& [fam, shape] : forced) {
+    if (shape < 0) continue;
+    for (OpDesc& op : P->ops) {
+      if (op.kind != OP_CONV || op.family != fam) continue;
+      const std::vector<int> cands = conv_candidates(op);
+      const int want = conv_tile(fam, shape, true);
+      if (std::find(cands.begin(), cands.end(), want) != cands.end()) op.tile = want;
+    }
+  }
+  P->last_use = ++h->tick;
+  *out = P.get();
+  h->plans.push_back(std::move(P));
+  return FILM_OK;
+}
+
+// Most H x W units (`what`: frame pairs / pair-tiles) one model invocation may take: what the plan of ONE unit says about the 4 GiB-per-buffer limit
+// and the workspace budget, then option "max_batch".  A unit that is too large by itself is refused with `advice`.
+int max_units(film_t* h, int H, int W, const char* what, const char* advice, int* units) {
+  Plan* P1 = nullptr;
+  int rc = get_plan(h, 1, H, W, false, &P1);
+  if (rc) return rc;
+  const int64_t lim = limited_buffer_bytes(P1);
+  const int64_t arena = std::max<int64_t>(1, P1->arena_floats * (int64_t)sizeof(float));
+  *units = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxBufferBytes / lim, arena_budget_bytes(h) / arena));
+  if (lim > kMaxBufferBytes)
+    return fail(h, FILM_ERR_INVALID, "a %d x %d %s needs a %.1f GB activation buffer in front of a kernel that addresses 4 GiB per "
+                "buffer - %s", H, W, what, lim * 1e-9, advice);
+  if (h->opt_max_batch) *units = std::min(*units, h->opt_max_batch);
+  return FILM_OK;
+}
+
+}  // namespace film_internal

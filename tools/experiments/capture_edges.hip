@@ -1,5 +1,5 @@
 // capture_edges.hip -- which edges does hipStreamBeginCapture record when one captured stream's events are waited for by
-// another?  (Development tool; found while debugging stale t = 0.5 warps under the two-lane graph, see film_engine.cpp.)
+// another?  (Development tool; found while debugging stale t = 0.5 warps under the two-lane graph, see issue_lanes in film_exec.cpp.)
 //   hipcc --offload-arch=gfx950 tools/experiments/capture_edges.hip -o tools/bin/capture_edges && tools/bin/capture_edges
 #include <hip/hip_runtime.h>
 #include <cstdio>
