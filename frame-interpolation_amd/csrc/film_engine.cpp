@@ -1,5 +1,5 @@
 // film_engine.cpp -- C-ABI (include/film_hip.h) of the MI355X FILM inference engine: handle lifetime, the option table, the JSON queries,
-// tiling, staging and chunking of film_forward / film_interpolate / film_interpolate_sequence, the host-buffer pipeline, film_get_tap and the
+// tiling, staging and chunking of film_forward / film_interpolate / film_interpolate_sequence, the host-buffer pipeline, the frame streams (film_stream_*), film_get_tap and the
 // debug entry points.  The executor lives in film_exec.cpp, the autotuner in film_tune.cpp, the plan cache in film_plans.cpp, the planner in
 // film_planner.cpp, the layer table and the weight packer in film_layers.cpp, the shared structures in film_internal.h.
 // There is no CPU execution path here: plan-only handles (device = -1) can pack weights and describe
@@ -312,6 +312,30 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
   return FILM_OK;
 }
 
+// ---- frame streams (film_stream_*; the contract: include/film_hip.h) ----
+size_t pix_bytes(int pix) { return pix == FILM_PIX_U8 ? 1 : sizeof(float); }
+// The stream's device buffers go back and it is closed.  Work that may still use them is the caller's to wait for.
+void stream_free(film_t* h) {
+  FilmStream& fs = h->fs;
+  for (void* p : {fs.keep, (void*)fs.result, (void*)fs.result8})
+    if (p) (void)hipFree(p);
+  fs = FilmStream{};
+}
+// what of a TileMapParams tile_geometry decides: the same values cut the same tiles
+bool same_geometry(const TileMapParams& a, const TileMapParams& b) {
+  const int va[] = {a.H, a.W, a.bh, a.bw, a.ph, a.pw, a.TH, a.TW, a.oy, a.ox, a.ovy, a.ovx, a.eh, a.ew};
+  const int vb[] = {b.H, b.W, b.bh, b.bw, b.ph, b.pw, b.TH, b.TW, b.oy, b.ox, b.ovy, b.ovx, b.eh, b.ew};
+  return std::equal(std::begin(va), std::end(va), std::begin(vb));
+}
+// The frame the stream keeps -> its tiles in half `slot` of the plan's img0 (an 8-bit frame is dequantised by the cut itself)
+hipError_t stream_cut(const FilmStream& fs, TileMapParams tp, const Plan* P, int slot, hipStream_t s) {
+  tp.tile0 = 0; tp.ntiles = tp.bh * tp.bw;
+  tp.src = (const float*)fs.keep;
+  tp.dst = P->at("img0") + (int64_t)slot * tp.ntiles * tp.TH * tp.TW * 3;
+  if (fs.pix != FILM_PIX_U8) return cut_tiles(tp, s);
+  return (tp.ovy | tp.ovx) ? film_launch_frame_to_tiles_overlap_u8(tp, (const uint8_t*)fs.keep, s) : film_launch_frame_to_tiles_u8(tp, (const uint8_t*)fs.keep, s);
+}
+
 // The plan film_debug_arena / film_debug_run_op work on ("Debug / tests" in include/film_hip.h: one planned launch on a workspace the caller controls)
 int debug_plan(film_t* h, int B, int H, int W, int tiles, Plan** P) {
   if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle has no device");
@@ -387,6 +411,7 @@ int film_create(film_t** out, int device, const film_config* cfg) {
 void film_destroy(film_t* h) {
   if (!h) return;
   drop_plans(h);   // (waits first: forwards may still be running on the caller's stream and on the side lane, and what they use must outlive them)
+  stream_free(h);
   if (h->packed_dev) (void)hipFree(h->packed_dev);
   if (h->stage) (void)hipFree(h->stage);
   if (h->metrics_buf) (void)hipFree(h->metrics_buf);
@@ -569,6 +594,135 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
     }
   }
   return st.finish();
+}
+
+int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (tiles < 1) return fail(h, FILM_ERR_INVALID, "tiles must be positive");
+  if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the half of the frame buffers the pushed frame fills)");
+  if (tiles >= 1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
+  Plan* P = nullptr;
+  int rc = get_plan(h, tiles, H, W, false, &P, tiles, true);
+  if (rc) return rc;
+  return copy_out_string(h, plan_json(h, *P->orientation(slot)), buf, cap, needed);
+}
+
+int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix) {
+  if (!h) return FILM_ERR_INVALID;
+  if (h->fs.open) return fail(h, FILM_ERR_STATE, "a stream is already open on this handle (one per handle: close it, or create another handle)");
+  if (pix != FILM_PIX_F32 && pix != FILM_PIX_U8) return fail(h, FILM_ERR_INVALID, "bad pix: FILM_PIX_F32 (0) or FILM_PIX_U8 (1)");
+  if (H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
+  TileMapParams tp{};
+  tp.B = 1;
+  int rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
+  if (rc == FILM_OK) rc = need_device(h, "film_stream_open");
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  int tmax = 1;
+  rc = max_units(h, tp.TH, tp.TW, "tile", "use a finer block_shape", &tmax);
+  if (rc) return rc;
+  const int T = tp.bh * tp.bw;
+  // a stream neither chunks a frame nor halves on out-of-memory: the carried features of ALL tiles live in one plan
+  if (T > tmax)
+    return fail(h, FILM_ERR_INVALID, "a stream runs the whole frame in one model invocation: its %d tiles of %d x %d exceed the %d tiles one invocation "
+                "may take (64 GiB / 60 %% of the free HBM of workspace, 4 GiB per 32-bit addressed buffer, \"max_batch\") - use a finer block_shape", T, tp.TH, tp.TW, tmax);
+  Plan* P = nullptr;
+  rc = get_plan(h, T, tp.TH, tp.TW, true, &P, T, true);   // (built and tuned now; FILM_ERR_NOMEM when the workspace does not fit)
+  if (rc) return rc;
+  FilmStream& fs = h->fs;
+  const size_t nv = (size_t)H * W * 3;
+  hipError_t e = hipMalloc(&fs.keep, (nv * pix_bytes(pix) + 3) & ~(size_t)3);   // (whole 32-bit words: the 8-bit cut reads aligned words)
+  if (e == hipSuccess) e = hipMalloc((void**)&fs.result, nv * sizeof(float));
+  if (e == hipSuccess && pix == FILM_PIX_U8) e = hipMalloc((void**)&fs.result8, nv);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    stream_free(h);
+    return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's frame buffers (%.1f MB) failed", nv * (pix_bytes(pix) + 5) * 1e-6);
+  }
+  fs.open = true;
+  fs.H = H; fs.W = W; fs.align = align; fs.block_h = block_h; fs.block_w = block_w; fs.pix = pix;
+  return FILM_OK;
+}
+
+int film_stream_reset(film_t* h) {
+  if (!h) return FILM_ERR_INVALID;
+  if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  h->fs.primed = false;
+  return FILM_OK;
+}
+
+int film_stream_close(film_t* h) {
+  if (!h) return FILM_ERR_INVALID;
+  if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();   // (device-resident pushes are asynchronous: what they read must outlive them)
+  stream_free(h);
+  return FILM_OK;
+}
+
+int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int mem_kind, void* stream) {
+  if (!h) return FILM_ERR_INVALID;
+  FilmStream& fs = h->fs;
+  if (!fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  hipStream_t s = pick_stream(h, mem_kind == FILM_MEM_DEVICE ? FILM_MEM_DEVICE : FILM_MEM_HOST, stream);
+  // Whatever fails from here on: the stream forgets its carried frame (as after film_stream_reset), and both streams are drained before
+  // the error goes back to the caller, who may then free or reuse `frame` / `mid`.
+  struct Unprime {
+    film_t* h; hipStream_t s; bool armed;
+    ~Unprime() {
+      if (!armed) return;
+      h->fs.primed = false;
+      (void)hipStreamSynchronize(h->stream2);
+      (void)hipStreamSynchronize(s);
+    }
+  } unprime{h, s, true};
+  if (produced) *produced = 0;
+  if (!frame || !produced || (fs.primed && !mid)) return fail(h, FILM_ERR_INVALID, "NULL argument");
+  if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
+  HIPCHK(h, hipSetDevice(h->device));
+  TileMapParams tp{};
+  tp.B = 1;
+  int rc = tile_geometry(h, fs.H, fs.W, fs.block_h, fs.block_w, fs.align, &tp);   // ("block_overlap_*" as they are NOW)
+  if (rc) return rc;
+  const int T = tp.bh * tp.bw;
+  Plan* P0 = nullptr;
+  rc = get_plan(h, T, tp.TH, tp.TW, true, &P0, T, true);
+  if (rc) return rc;
+  const bool host = mem_kind == FILM_MEM_HOST;
+  const size_t nv = (size_t)fs.H * fs.W * 3;
+  if (fs.primed && (fs.plan_id != P0->id || !same_geometry(fs.geo, tp))) {
+    // the plan that held the previous frame's pyramids was evicted or dropped since (or the tiles changed): extract that frame again
+    // from the stream's own copy, where it was - the same ops on the same values, the same bits
+    Plan* R = P0->orientation(fs.slot);
+    HIPCHK(h, stream_cut(fs, tp, R, fs.slot, s));
+    if ((rc = run_plan(h, R, s, R->n_extract))) return rc;
+  }
+  const int slot = fs.primed ? 1 - fs.slot : 0;
+  Plan* P = P0->orientation(slot);
+  HIPCHK(h, hipMemcpyAsync(fs.keep, frame, nv * pix_bytes(fs.pix), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  HIPCHK(h, stream_cut(fs, tp, P, slot, s));
+  if (!fs.primed) {
+    if ((rc = run_plan(h, P, s, P->n_extract))) return rc;
+  } else {
+    if ((rc = run_plan(h, P, s))) return rc;
+    // joined in float32 by the kernels of film_interpolate, then quantised by film_to_uint8's kernel for an 8-bit stream
+    float* joined = (fs.pix == FILM_PIX_F32 && !host) ? (float*)mid : fs.result;
+    TileMapParams j = tp;
+    j.tile0 = 0; j.ntiles = T; j.src = P->at("out"); j.dst = joined;
+    HIPCHK(h, join_tiles(j, s));
+    if (fs.pix == FILM_PIX_U8) {
+      uint8_t* q = host ? fs.result8 : (uint8_t*)mid;
+      HIPCHK(h, film_launch_to_uint8(joined, q, (int64_t)nv, s));
+      if (host) HIPCHK(h, hipMemcpyAsync(mid, q, nv, hipMemcpyDeviceToHost, s));
+    } else if (host) {
+      HIPCHK(h, hipMemcpyAsync(mid, joined, nv * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+  }
+  if (host) HIPCHK(h, hipStreamSynchronize(s));
+  *produced = fs.primed ? 1 : 0;
+  fs.primed = true; fs.slot = slot; fs.plan_id = P0->id; fs.geo = tp;
+  unprime.armed = false;
+  return FILM_OK;
 }
 
 int film_get_tap(film_t* h, const char* name, float* dst, int64_t cap, int64_t dims[4]) {

@@ -164,10 +164,12 @@ hipError_t issue_lanes(film_t* h, Plan* P, hipStream_t main, bool capturing, con
 }
 
 // Executes the plan on stream s (inputs already in the plan's img0 buffer, result left in its out buffer).
-int run_plan(film_t* h, Plan* P, hipStream_t s) {
+// n_ops < the plan's op count: only its first n_ops ops, in plan order on `s` alone (the pushed frame's extraction of a stream plan's first call).
+int run_plan(film_t* h, Plan* P, hipStream_t s, size_t n_ops) {
   const int B = P->B, H = P->H, W = P->W;
+  const bool prefix = n_ops < P->ops.size();
   if (h->opt_profile) {
-    const size_t n = P->ops.size();
+    const size_t n = std::min(n_ops, P->ops.size());
     while (P->ev.size() < n + 1) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); P->ev.push_back(e); }
     HIPCHK(h, hipEventRecord(P->ev[0], s));
     for (size_t i = 0; i < n; ++i) {
@@ -196,6 +198,8 @@ int run_plan(film_t* h, Plan* P, hipStream_t s) {
     }
     o << "},\"ops\":[" << ops.str() << "]}";
     h->profile_json = o.str();
+  } else if (prefix) {
+    for (size_t i = 0; i < n_ops; ++i) HIPCHK(h, launch_op(P->ops[i], P->arena, h->packed_dev, s));
   } else if (h->opt_graph == 1) {
     if (!P->graph_exec) {
       // capture on the handle's own stream, replay on whichever stream the caller wants

@@ -130,6 +130,15 @@ struct Plan {
   // 0: a pair plan (img0 = [x0 tiles | x1 tiles], 2B images); > 0: a sequence plan over B / tiles consecutive frame pairs of `tiles`
   // tiles each (img0 = B + tiles images, frame-major: image f * tiles + t; pair-tile p reads images p and p + tiles)
   int tiles = 0;
+  // A stream plan (film_stream_*): the sequence plan of ONE pair of `tiles` tiles (B == tiles, img0 = 2 tiles images) whose two frame
+  // halves take turns.  slot = the half the pushed frame fills - its image pyramid and feature ops, NB = tiles, are ops [0, n_extract) -
+  // the other half holds what the push before left there: the pair's earlier frame.  The cached plan is the slot-0 orientation; `twin`
+  // is the slot-1 one over the SAME buffers and workspace (it owns no arena).  -1: not a stream plan.
+  int slot = -1;
+  size_t n_extract = 0;
+  std::unique_ptr<Plan> twin;
+  Plan* orientation(int s) { return s == slot ? this : twin.get(); }
+  uint64_t id = 0;           // unique per handle and build: a stream tells a rebuilt plan (its carried features are gone) from the one it filled
   std::vector<Buffer> bufs;
   std::vector<OpDesc> ops;
   int64_t arena_floats = 0;
@@ -159,7 +168,23 @@ enum FuseBit {
 
 }  // namespace film_internal
 
+// film_stream_*: the one open stream of a handle.  The carried frame's pyramids live in the stream plan's workspace; `keep` is the
+// stream's own copy of that frame (in its pixel type), from which they are rebuilt when the plan was evicted or dropped in between.
+struct FilmStream {
+  bool open = false;
+  int H = 0, W = 0, align = 0, block_h = 0, block_w = 0, pix = 0;
+  void* keep = nullptr;             // the last pushed frame [H][W][3], float32 or bytes
+  float* result = nullptr;          // the joined float32 mid-frame of a host or 8-bit push
+  unsigned char* result8 = nullptr; // ... quantised, of an 8-bit host push
+  bool primed = false;              // `keep` holds a frame
+  int slot = 0;                     // the half of the plan's frame buffers it was extracted into ...
+  uint64_t plan_id = 0;             // ... of this plan (Plan::id) ...
+  TileMapParams geo{};              // ... cut with this geometry (block_overlap_* may change between pushes)
+};
+
 struct film_handle {
+  FilmStream fs;
+  uint64_t plan_ids = 0;
   void* stage = nullptr;       // device staging of whole frames for film_interpolate(FILM_MEM_HOST)
   size_t stage_bytes = 0;
   void* metrics_buf = nullptr;  // film_image_metrics: partials + results (+ the images with FILM_MEM_HOST), grown on demand
@@ -287,19 +312,20 @@ struct LanePipe {
   std::function<hipError_t()> mid_tail;
 };
 hipError_t issue_lanes(film_t* h, Plan* P, hipStream_t main, bool capturing, const LanePipe* lp = nullptr);
-int run_plan(film_t* h, Plan* P, hipStream_t s);
+int run_plan(film_t* h, Plan* P, hipStream_t s, size_t n_ops = SIZE_MAX);   // n_ops < the plan's: its first n_ops ops only, on `s` alone
 
 // ---- film_tune.cpp (the nine *_candidates of kConvFamily: film_kernels.h)
 std::vector<int> conv_candidates(const OpDesc& op);
 int autotune_plan(film_t* h, Plan* P);
 
 // ---- film_plans.cpp
-int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles = 0);
+int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles = 0, bool stream = false);   // stream: B == tiles
 void drop_plans(film_t* h);   // waits for the device, then frees every cached plan
 int max_units(film_t* h, int H, int W, const char* what, const char* advice, int* units);
 
 // ---- film_planner.cpp
-int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles = 0);   // fills P->bufs / ops / arena_floats for (B, H, W) (tiles > 0: sequence plan)
+// fills P->bufs / ops / arena_floats for (B, H, W) (tiles > 0: sequence plan; slot >= 0: that orientation of a stream plan, B == tiles)
+int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles = 0, int slot = -1);
 int64_t limited_buffer_bytes(const Plan* P);                // largest buffer a kernel with whole-buffer 32-bit offsets reads
 std::string plan_json(film_t* h, const Plan& P);
 

@@ -387,6 +387,10 @@ hipError_t film_launch_pack_flow(const PackFlowParams& p, hipStream_t s);
 hipError_t film_launch_frame_to_tiles(const TileMapParams& p, hipStream_t s);   // pad + image_to_patches
 hipError_t film_launch_tiles_to_frame(const TileMapParams& p, hipStream_t s);   // crop + patches_to_image
 hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams& p, hipStream_t s);   // the same for overlapped tiles
+// The two cuts on an 8-bit frame [B][H][W][3] of bytes (film_stream_push, FILM_PIX_U8): `src` replaces p.src, the tile buffer receives
+// float32(byte) / 255.0f, correctly rounded (= numpy's astype(float32) / 255), padding stays zero.  A thread handles twelve bytes of a row.
+hipError_t film_launch_frame_to_tiles_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s);
+hipError_t film_launch_frame_to_tiles_overlap_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s);
 // crop + cross-fade of the tiles [tile0, tile0 + ntiles) into the frames: adds to what the tiles below tile0 left in dst, so the
 // launches of one frame go in tile order on one stream
 hipError_t film_launch_blend_tiles(const TileMapParams& p, hipStream_t s);

@@ -9,6 +9,10 @@
 // A sequence plan (tiles > 0) runs F - 1 consecutive pairs of F frames: the image pyramids and the extractor run once per
 // frame (B + tiles images), every op that reaches the other image of a pair is emitted per direction with that image one
 // pointer offset of `tiles` images away, and the flow estimator (2B) and the decoder (B) are the pair plan's.
+// A stream plan (slot = 0 / 1) is the sequence plan of ONE pair whose two frame halves take turns between calls: the per-image stages
+// run on the `tiles` images of half `slot` only - the frame just pushed, the pair's later one - and come first in the op list
+// (Plan::n_extract of them); the other half holds what the call before left there, the pair's earlier frame.  Both orientations
+// lay out the same buffers at the same offsets and emit the same ops but for those image offsets.
 // Top down: the kernel decisions (plain_conv_family / folded_conv_family / conv_ksplit: pure functions of a convolution's shape, its buffers'
 // layout and the options - never of timing or the batch size), the Planner (a helper per op kind, a member per stage of the graph,
 // Planner::build their sequence), the cross-lane dependencies of the two-stream replay (analyze_lanes), a plan as JSON (film_plan_json).
@@ -194,7 +198,9 @@ struct Planner {
   // what the stages of build() share: the frame geometry ...
   int B = 0, T = 0, H0 = 0, W0 = 0;   // pair-tiles, tiles per frame of a sequence plan (0: pair plan), frame size
   int NL = 0, FL = 0;                 // pyramid levels, fusion (decoder) levels
-  int N2 = 0, NI = 0, o1 = 0;         // 2B; images of the per-image stages (image pyramids, feature extractor); image 1 of pair-tile b is image b + o1
+  int N2 = 0, NI = 0;                 // 2B; images in the per-image buffers (image pyramids, features, extractor scratch)
+  int i0 = 0, i1 = 0;                 // image 0 / image 1 of pair-tile b is image b + i0 / b + i1 of those buffers
+  int NE = 0, e0 = 0;                 // the per-image stages run on images [e0, e0 + NE): all NI of them, or (stream plan) the pushed frame's
   bool seq = false;
   std::vector<int> fc, ff;            // feature channels / decoder filters per level
   int HL(int l) const { return H0 >> l; }
@@ -226,6 +232,9 @@ struct Planner {
   static View sub(View v, int coff, int C) { v.off += coff; v.C = C; return v; }
   // scratch view: reinterpret the start of a scratch buffer as [*][*][*][C]
   View scratch(int buf, int C) const { return View{buf, P->bufs[buf].off, C, C}; }
+  // ... of the extractor subtree at level i: the images the per-image stages run on start e0 images of the subtree's FIRST stage (its
+  // largest use: `per_image` floats each) into the region, whatever the stage - half way with the second frame of a stream plan
+  View fx_scratch(int buf, int C, int64_t per_image) const { View v = scratch(buf, C); v.off += e0 * per_image; return v; }
   static SegDesc seg(View v, int up = 0) { SegDesc s; s.v = v; s.up = up; return s; }
   const LayerPack& layer(const std::string& name) const { return h->layers[h->layer_idx.at(name)]; }
   void to_lane(size_t first_op, int lane) { for (size_t q = first_op; q < P->ops.size(); ++q) P->ops[q].lane = lane; }
@@ -380,7 +389,7 @@ struct Planner {
   // image pyramids (util.py:23-45), both images as one batch of 2B (sequence: every frame once)
   void emit_image_pyramids() {
     for (int l = 0; l + 1 < NL; ++l) {
-      pool("image_pyramid_l" + std::to_string(l + 1), view(img[l], 0, 0, 3), view(img[l + 1], 0, 0, 3), NI, HL(l), WL(l));
+      pool("image_pyramid_l" + std::to_string(l + 1), view(img[l], e0, 0, 3), view(img[l + 1], e0, 0, 3), NE, HL(l), WL(l));
       // on the side stream: the level-0 subtree (main stream) reads img[0] only and starts at once; six 6-us launches less in front of it
       // (256x256: 2.31 -> 2.28 ms per step, 1080p: -0.1 ms; profiles/r06_pool_lane_ab.log)
       P->ops.back().lane = 1;
@@ -392,24 +401,25 @@ struct Planner {
     const film_config& c = h->cfg;
     const int n = std::min(NL - i, c.sub_levels);
     const size_t first_op = P->ops.size();
+    const int64_t a_img = (int64_t)HL(i) * WL(i) * c.filters, p_img = (int64_t)HL(i + 1) * WL(i + 1) * c.filters;   // scratch floats per image
     for (int j = 0; j < n; ++j) {
       const int lv = i + j, k = c.filters << j;
       const std::string tg = "feat_s" + std::to_string(i) + "_" + std::to_string(j);
       const std::string w0 = "feat_net/sub_extractor/cfeat_conv_" + std::to_string(2 * j);
       const std::string w1 = "feat_net/sub_extractor/cfeat_conv_" + std::to_string(2 * j + 1);
-      View tmp = scratch(fx_a[i], k);
-      if (j == 0) conv_c3(tg, w0, view(img[i], 0, 0, 3), tmp, NI, HL(lv), WL(lv));
-      else conv(tg, w0, {seg(scratch(fx_p[i], k >> 1))}, tmp, NI, HL(lv), WL(lv), true);
-      View dst = view(feat[lv], 0, slot_offset(c, j), k);
-      conv(tg, w1, {seg(tmp)}, dst, NI, HL(lv), WL(lv), true);
+      View tmp = fx_scratch(fx_a[i], k, a_img);
+      if (j == 0) conv_c3(tg, w0, view(img[i], e0, 0, 3), tmp, NE, HL(lv), WL(lv));
+      else conv(tg, w0, {seg(fx_scratch(fx_p[i], k >> 1, p_img))}, tmp, NE, HL(lv), WL(lv), true);
+      View dst = view(feat[lv], e0, slot_offset(c, j), k);
+      conv(tg, w1, {seg(tmp)}, dst, NE, HL(lv), WL(lv), true);
       if (j == n - 1) continue;
       OpDesc& cv = P->ops.back();
       if ((h->opt_fuse & FUSE_POOL) && cv.kind == OP_CONV && kConvFamily[cv.family].fused_shape >= 0 && cv.ksplit <= 1 && !(HL(lv) & 1) && !(WL(lv) & 1)) {
         // AveragePooling2D in the epilogue of the Winograd kernels (a lane / thread holds both rows of a 2x2 block)
         cv.tag += "+pool";
-        cv.out2 = scratch(fx_p[i], k);
+        cv.out2 = fx_scratch(fx_p[i], k, p_img);
       } else
-        pool(tg + ":pool", dst, scratch(fx_p[i], k), NI, HL(lv), WL(lv));
+        pool(tg + ":pool", dst, fx_scratch(fx_p[i], k, p_img), NE, HL(lv), WL(lv));
     }
     // every subtree but the level-0 one (75 % of the extractor's FLOPs) goes to the side stream: they and the coarse
     // flow levels that need only them are small, latency-bound launches that hide under the level-0 subtree
@@ -452,7 +462,7 @@ struct Planner {
       // Sequence plan: one launch per direction, the other image's features one offset of T images away (no batch rotation).
       for (int d = 0; d < (seq ? 2 : 1); ++d) {
         if (seq)
-          warp(tg + ":warp_d" + std::to_string(d), view(feat[l], d ? 0 : T, 0, fc[l]), view(vup[l], d * B, 0, 2),
+          warp(tg + ":warp_d" + std::to_string(d), view(feat[l], d ? i0 : i1, 0, fc[l]), view(vup[l], d * B, 0, 2),
                view(warped[l], d * B, 0, fc[l]), B, Hl, Wl, 1.f);
         else {
           warp(tg + ":warp_d01", view(feat[l], 0, 0, fc[l]), view(vup[l], 0, 0, 2), view(warped[l], 0, 0, fc[l]), N2, Hl, Wl, 1.f);
@@ -475,11 +485,11 @@ struct Planner {
       if (coarsest) { sb.boff = B; sb.bmod = N2; }   // the other image's features
       conv(tg, prefix + "/conv_0", {sa, sb}, cur, N2, Hl, Wl, true);
     } else {
-      // [features of image a | (warped) features of image b] per direction d: a = image p + d T, b = image p + (1 - d) T
+      // [features of image a | (warped) features of image b] per direction d: a = image d of pair-tile p, b = its image 1 - d
       // (coarsest level) or warped[d B + p]; the two halves of the output are the 2B batch of the pair plan
       for (int d = 0; d < 2; ++d) {
-        SegDesc a = seg(view(feat[l], d * T, 0, fc[l]));
-        SegDesc b = seg(coarsest ? view(feat[l], (1 - d) * T, 0, fc[l]) : view(warped[l], d * B, 0, fc[l]));
+        SegDesc a = seg(view(feat[l], d ? i1 : i0, 0, fc[l]));
+        SegDesc b = seg(coarsest ? view(feat[l], d ? i0 : i1, 0, fc[l]) : view(warped[l], d * B, 0, fc[l]));
         View o = cur;
         o.off += (int64_t)d * B * Hl * Wl * nf;
         conv(tg + ":d" + std::to_string(d), prefix + "/conv_0", {a, b}, o, B, Hl, Wl, true);
@@ -543,10 +553,10 @@ struct Planner {
     for (int s = 0; s < 2; ++s) {
       View fl = view(v[l], (1 - s) * B, 0, 2);
       if (!pair)
-        warp(tg + ":warp_feat" + std::to_string(s), view(feat[l], s * o1, 0, fc[l]), fl,
+        warp(tg + ":warp_feat" + std::to_string(s), view(feat[l], s ? i1 : i0, 0, fc[l]), fl,
              aligned_part(aligned[l], s, fc[l]), B, HL(l), WL(l), 0.5f);
       if (!misc16)
-        warp(tg + ":warp_img" + std::to_string(s), view(img[l], s * o1, 0, 3), fl,
+        warp(tg + ":warp_img" + std::to_string(s), view(img[l], s ? i1 : i0, 0, 3), fl,
              sub(aligned_part(aligned[l], 2, fc[l]), 3 * s, 3), B, HL(l), WL(l), 0.5f, false);
     }
     if (misc16) {
@@ -608,20 +618,27 @@ struct Planner {
     }
   }
 
-  int build(int B_, int H_, int W_, int T_) {
+  int build(int B_, int H_, int W_, int T_, int slot) {
     const film_config& c = h->cfg;
     B = B_; H0 = H_; W0 = W_; T = T_;
     NL = c.pyramid_levels; FL = c.fusion_pyramid_levels;
     seq = T > 0;
     N2 = 2 * B;
     NI = seq ? B + T : N2;
-    o1 = seq ? T : B;
+    i0 = 0; i1 = seq ? T : B;
+    NE = NI; e0 = 0;
+    if (slot >= 0) {   // stream plan: the pushed frame (the pair's image 1) is extracted into half `slot`, image 0 waits in the other half
+      if (slot > 1 || B != T) return fail(h, FILM_ERR_INVALID, "a stream plan has slot 0 or 1 and one pair of its tiles");
+      i0 = (1 - slot) * T; i1 = slot * T;
+      NE = T; e0 = i1;
+    }
     fc = feature_channels(c);
     ff = fusion_filters(c);
-    P->B = B; P->H = H0; P->W = W0; P->tiles = T;
+    P->B = B; P->H = H0; P->W = W0; P->tiles = T; P->slot = slot;
     add_buffers();
     emit_image_pyramids();
     for (int i = 0; i < NL; ++i) emit_extractor(i);
+    P->n_extract = P->ops.size();
     for (int l = NL - 1; l >= 0; --l) emit_flow(l);
     // Option "lanes" >= 2 (NOT the default - measured 2 % slower, see opt_lanes), large frames: the COARSE decoder levels (>= 2) join the side stream right behind the
     // aligned levels they read - fusion level i only needs aligned[i], aligned[i + 1] / the level above, i.e. the flow
@@ -704,9 +721,9 @@ struct Planner {
 
 }  // namespace
 
-int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles) {
+int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles, int slot) {
   Planner pl{h, P};
-  return pl.build(B, H, W, tiles);
+  return pl.build(B, H, W, tiles, slot);
 }
 
 // The conv kernels other than conv_wino43_kernel address their inputs with 32-bit byte offsets from the start of the
@@ -776,7 +793,8 @@ std::string plan_json(film_t* h, const Plan& P) {
   std::ostringstream o;
   JsonObject j{o};
   j.num("B", P.B); j.num("H", P.H); j.num("W", P.W);
-  if (P.tiles > 0) { j.str("kind", "sequence"); j.num("n_pairs", P.B / P.tiles); j.num("tiles", P.tiles); }
+  if (P.slot >= 0) { j.str("kind", "stream"); j.num("tiles", P.tiles); j.num("slot", P.slot); j.num("n_extract", P.n_extract); }
+  else if (P.tiles > 0) { j.str("kind", "sequence"); j.num("n_pairs", P.B / P.tiles); j.num("tiles", P.tiles); }
   j.num("arena_floats", P.arena_floats); j.num("offset32_buffer_bytes", limited_buffer_bytes(&P)); j.num("packed_floats", h->packed_floats);
   j.objects("buffers", P.bufs.data(), P.bufs.size(), [](JsonObject& e, const Buffer& b) {
     e.str("name", b.name); e.num("off", b.off); e.num("N", b.N); e.num("H", b.H); e.num("W", b.W); e.num("C", b.C); e.num("floats", b.floats); e.num("planar", b.planar);

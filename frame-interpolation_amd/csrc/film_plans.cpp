@@ -5,6 +5,7 @@
 namespace film_internal {
 namespace {
 void free_plan(Plan* p) {
+  if (p->twin) { p->twin->arena = nullptr; free_plan(p->twin.get()); }   // (the other orientation of a stream plan works on this plan's arena)
   if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
   if (p->graph) (void)hipGraphDestroy(p->graph);
   for (auto e : p->ev) (void)hipEventDestroy(e);
@@ -14,7 +15,7 @@ void free_plan(Plan* p) {
 
 // Plan `index` leaves the cache with everything it holds on the device.  Work that may still run on it is the caller's to wait for.
 void forget_plan(film_t* h, size_t index) {
-  if (h->last_plan == h->plans[index].get()) h->last_plan = nullptr;
+  if (h->last_plan == h->plans[index].get() || (h->last_plan && h->last_plan == h->plans[index]->twin.get())) h->last_plan = nullptr;
   free_plan(h->plans[index].get());
   h->plans.erase(h->plans.begin() + index);
 }
@@ -45,9 +46,11 @@ void drop_plans(film_t* h) {
   while (!h->plans.empty()) forget_plan(h, h->plans.size() - 1);
 }
 
-// Plans are cached per (B, H, W, tiles): tiles = 0 for pair plans, > 0 for sequence plans (Plan::tiles) - the two kinds never
-// stand in for each other.  Both count toward the three device plans kept alive.
-int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles) {
+// Plans are cached per (B, H, W, tiles, stream): tiles = 0 for pair plans, > 0 for sequence plans (Plan::tiles), stream for the
+// stream plan of `tiles` tiles (Plan::slot >= 0: both orientations, one cache entry, one workspace) - the kinds never stand in
+// for each other.  All count toward the three device plans kept alive.
+int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles, bool stream) {
+  const auto same = [&](const Plan& p) { return p.B == B && p.H == H && p.W == W && p.tiles == tiles && (p.slot >= 0) == stream; };
   const int div = 1 << (h->cfg.pyramid_levels - 1);
   if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
   if (H % div || W % div)
@@ -59,13 +62,23 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
     return fail(h, FILM_ERR_INVALID, "input %d x %d too small: warped pyramid level %d would be smaller than 2x2", H, W, wl);
   if ((int64_t)2 * B * H * W >= (int64_t)1 << 31) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
   for (auto& p : h->plans)
-    if (p->B == B && p->H == H && p->W == W && p->tiles == tiles && (!need_device || p->arena)) { *out = p.get(); p->last_use = ++h->tick; return FILM_OK; }
+    if (same(*p) && (!need_device || p->arena)) { *out = p.get(); p->last_use = ++h->tick; return FILM_OK; }
   if (need_device)   // a description-only plan of this shape (film_plan_json, max_units) is superseded, not kept beside the new one
     for (size_t i = 0; i < h->plans.size(); ++i)
-      if (h->plans[i]->B == B && h->plans[i]->H == H && h->plans[i]->W == W && h->plans[i]->tiles == tiles) { forget_plan(h, i); break; }
+      if (same(*h->plans[i])) { forget_plan(h, i); break; }
   std::unique_ptr<Plan> P(new Plan);
-  int rc = plan_build(h, P.get(), B, H, W, tiles);
+  int rc = plan_build(h, P.get(), B, H, W, tiles, stream ? 0 : -1);
   if (rc) return rc;
+  P->id = ++h->plan_ids;
+  if (stream) {
+    P->twin.reset(new Plan);
+    Plan& Q = *P->twin;
+    if ((rc = plan_build(h, &Q, B, H, W, tiles, 1))) return rc;
+    bool alike = Q.arena_floats == P->arena_floats && Q.bufs.size() == P->bufs.size() && Q.n_extract == P->n_extract;
+    for (size_t i = 0; alike && i < Q.bufs.size(); ++i) alike = Q.bufs[i].name == P->bufs[i].name && Q.bufs[i].off == P->bufs[i].off && Q.bufs[i].floats == P->bufs[i].floats;
+    if (!alike) return fail(h, FILM_ERR_INVALID, "planner: the two orientations of a stream plan lay out different workspaces");
+    Q.id = P->id;
+  }
   if (need_device) {
     // keep at most 3 device plans alive (workspaces are GBs at 1080p tiles)
     size_t alive = 0;
@@ -96,8 +109,10 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
     }
     HIPCHK(h, hipMemsetAsync(P->arena, 0, (size_t)P->arena_floats * sizeof(float), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (P->twin) P->twin->arena = P->arena;
     if (h->opt_autotune && h->finalized) {
       int trc = autotune_plan(h, P.get());
+      if (trc == FILM_OK && P->twin) trc = autotune_plan(h, P->twin.get());   // (its shapes are the first orientation's: nothing is measured again)
       if (trc) { free_plan(P.get()); return trc; }
     }
   }
@@ -105,11 +120,14 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
   const std::pair<ConvFamily, int> forced[] = {{FAM_W43, h->opt_w43_shape}, {FAM_W2D, h->opt_w2d_shape}, {FAM_FOLD4, h->opt_fold4_shape}};
   for (const auto& [fam, shape] : forced) {
     if (shape < 0) continue;
-    for (OpDesc& op : P->ops) {
-      if (op.kind != OP_CONV || op.family != fam) continue;
-      const std::vector<int> cands = conv_candidates(op);
-      const int want = conv_tile(fam, shape, true);
-      if (std::find(cands.begin(), cands.end(), want) != cands.end()) op.tile = want;
+    for (Plan* R : {P.get(), P->twin.get()}) {
+      if (!R) continue;
+      for (OpDesc& op : R->ops) {
+        if (op.kind != OP_CONV || op.family != fam) continue;
+        const std::vector<int> cands = conv_candidates(op);
+        const int want = conv_tile(fam, shape, true);
+        if (std::find(cands.begin(), cands.end(), want) != cands.end()) op.tile = want;
+      }
     }
   }
   P->last_use = ++h->tick;

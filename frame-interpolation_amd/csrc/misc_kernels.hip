@@ -581,6 +581,73 @@ __global__ __launch_bounds__(256) void frame_to_tiles_overlap_kernel(TileMapPara
   p.dst[i] = v;
 }
 
+// ---- the two cuts on an 8-bit frame (film_stream_push, FILM_PIX_U8) ------------------------------------------------------------
+// float32(byte) / 255.0f for every byte value, divided on the HOST (IEEE, = numpy's astype(float32) / 255 and eval/util.py read_image): the
+// kernel looks the quotient up, so no device division and no reciprocal decides a bit.  Passed by value (1 KB of kernel arguments).
+struct U8Table { float v[256]; };
+
+// frame_to_tiles_kernel / frame_to_tiles_overlap_kernel (OVERLAP) on a frame of bytes: p.src points at uint8 [B][H][W][3].  thread = twelve
+// consecutive values (four pixels) of one row of the tile buffer, the same tile-row-major order as the float kernels.  A group that lies
+// wholly inside the tile's content is read as the three or four ALIGNED 32-bit words that hold its twelve bytes (a row of W * 3 bytes
+// starts at any byte offset; every word read holds at least one byte of the group, so none lies outside the frame's pages) and shifted
+// into place; a group that touches the padding or the end of the row goes byte by byte.  Padding is written as zeros; the twelve floats
+// leave as three 16-byte stores where the row pitch allows.
+template <bool OVERLAP>
+__global__ __launch_bounds__(256) void frame_u8_to_tiles_kernel(TileMapParams p, U8Table tab) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = tab.v[threadIdx.x];
+  __syncthreads();
+  const int row = p.TW * 3;
+  const int groups = (row + 11) / 12;
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (int64_t)p.ntiles * p.TH * groups) return;
+  const int xc0 = (int)(g % groups) * 12;
+  const int64_t r = g / groups;               // row of the tile buffer
+  const int y = (int)(r % p.TH);
+  const int n = (int)(r / p.TH) + p.tile0;
+  const int b = n / (p.bh * p.bw), t = n % (p.bh * p.bw);
+  const int ty = t / p.bw, tx = t % p.bw;
+  const int ch = OVERLAP ? p.eh : p.ph, cw3 = (OVERLAP ? p.ew : p.pw) * 3;   // the tile's content: rows, values per row
+  const int sy = y - p.oy, s0 = xc0 - p.ox * 3;                              // content row, content value of the group's first value
+  float v[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) v[j] = 0.f;   // tf.image.pad_to_bounding_box pads with zeros
+  if (sy >= 0 && sy < ch && s0 + 12 > 0 && s0 < cw3) {
+    const int fy = (OVERLAP ? film_tile_origin(ty, p.ph, p.ovy, p.H, p.eh) : ty * p.ph) + sy;
+    const int fx = OVERLAP ? film_tile_origin(tx, p.pw, p.ovx, p.W, p.ew) : tx * p.pw;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(p.src) + (((int64_t)b * p.H + fy) * p.W + fx) * 3;   // content value 0 of this row
+    if (s0 >= 0 && s0 + 12 <= cw3) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(src + s0);
+      const uint32_t* wp = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+      const unsigned sh = (unsigned)(a & 3) * 8;
+      uint32_t w[3] = {wp[0], wp[1], wp[2]};
+      if (sh) {
+        const uint32_t w3 = wp[3];
+        w[0] = (w[0] >> sh) | (w[1] << (32 - sh));
+        w[1] = (w[1] >> sh) | (w[2] << (32 - sh));
+        w[2] = (w[2] >> sh) | (w3 << (32 - sh));
+      }
+#pragma unroll
+      for (int j = 0; j < 12; ++j) v[j] = lut[(w[j >> 2] >> ((j & 3) * 8)) & 255u];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 12; ++j) {
+        const int sxc = s0 + j;
+        if (sxc >= 0 && sxc < cw3) v[j] = lut[src[sxc]];
+      }
+    }
+  }
+  float* d = p.dst + r * row + xc0;
+  if (xc0 + 12 <= row && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(d)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 12; ++j)
+      if (xc0 + j < row) d[j] = v[j];
+  }
+}
+
 // Cross-fade weight (before normalisation) of tile i of an axis at frame position y: the distance to the nearest INTERIOR edge of
 // the tile, counted from 1; an edge on the frame's border does not limit it; 0 outside the tile.  *s = the tile's origin.
 __device__ __forceinline__ float fade_weight(int i, int y, int nb, int p, int o, int n, int e, int* s) {
@@ -666,6 +733,24 @@ hipError_t film_launch_frame_to_tiles(const TileMapParams& p, hipStream_t s) {
   hipLaunchKernelGGL(frame_to_tiles_kernel, dim3(blocks_for((int64_t)p.ntiles * p.TH * p.TW * 3)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
+
+namespace {
+template <bool OVERLAP> hipError_t launch_frame_u8_to_tiles(TileMapParams p, const uint8_t* src, hipStream_t s) {
+  static const U8Table tab = [] {
+    U8Table t;
+    for (int i = 0; i < 256; ++i) t.v[i] = (float)i / 255.0f;
+    return t;
+  }();
+  if (p.ntiles <= 0) return hipSuccess;
+  p.src = reinterpret_cast<const float*>(src);
+  const int64_t groups = (int64_t)p.ntiles * p.TH * ((p.TW * 3 + 11) / 12);
+  hipLaunchKernelGGL(frame_u8_to_tiles_kernel<OVERLAP>, dim3(blocks_for(groups)), dim3(256), 0, s, p, tab);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t film_launch_frame_to_tiles_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s) { return launch_frame_u8_to_tiles<false>(p, src, s); }
+hipError_t film_launch_frame_to_tiles_overlap_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s) { return launch_frame_u8_to_tiles<true>(p, src, s); }
 
 hipError_t film_launch_tiles_to_frame(const TileMapParams& p, hipStream_t s) {
   hipLaunchKernelGGL(tiles_to_frame_kernel, dim3(blocks_for((int64_t)p.ntiles * p.ph * p.pw * 3)), dim3(256), 0, s, p);

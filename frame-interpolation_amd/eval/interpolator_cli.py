@@ -59,6 +59,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--sequence_window', type=int, default=0,
                     help='(extension) 0: one input pair at a time (default).  K >= 2: windows of K consecutive input frames, one feature '
                          'extraction per frame and recursion depth (film_interpolate_sequence); same files.')
+    ap.add_argument('--stream', action='store_true', default=False,
+                    help='(extension) with --times_to_interpolate 1: decode the frames as bytes and push them one by one through an 8-bit frame '
+                         'stream (film_stream_*: one feature extraction per frame, one byte per value over PCIe); same files.')
     ap.add_argument('--output_video', action='store_true', default=False,
                     help='If true, creates a video of the frames in the interpolated_frames/ subdirectory')
     return ap
@@ -113,7 +116,10 @@ def write_video_uint8(path: str, frames: List[np.ndarray], fps: int) -> None:
 
 
 def pairs_to_files(inputs: List[str], first: int, end: int, n_pairs: int, it, args, frames_dir: str, keep: bool = False):
-    """The device pipeline for input pairs [first, end): one pair at a time, or in windows of --sequence_window input frames."""
+    """The device pipeline for input pairs [first, end): one pair at a time, in windows of --sequence_window input frames, or
+    (--stream) frame by frame through a stream primed with the range's first frame."""
+    if getattr(args, 'stream', False):
+        return util.interpolate_stream_to_files(inputs, first, end, n_pairs, it, frames_dir, keep=keep)
     window = getattr(args, 'sequence_window', 0)
     if window:
         return util.interpolate_windows_to_files(inputs, first, end, n_pairs, args.times_to_interpolate, it, frames_dir, window, keep=keep)
@@ -223,6 +229,10 @@ def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
     if args.sequence_window != 0 and args.sequence_window < 2:
         raise SystemExit(f'--sequence_window: 0 (off) or at least 2 frames, got {args.sequence_window}')
+    if args.stream and args.times_to_interpolate != 1:
+        raise SystemExit(f'--stream doubles the frame rate: it needs --times_to_interpolate 1, got {args.times_to_interpolate}')
+    if args.stream and args.sequence_window:
+        raise SystemExit('--stream and --sequence_window are two ways to extract every frame once: give one of them')
     if args.output_video:
         util.get_ffmpeg_path()
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -258,7 +268,8 @@ def main(argv=None) -> None:
     ntiles = max(1, args.block_height) * max(1, args.block_width)
     pairs_of = {d: max(0, len(list_input_frames(d)) - 1) for d in directories}
     overlapped = any(o != 0 and nb > 1 for o, nb in zip(overlap, block))
-    tiled_dirs = [] if whole else [d for d in directories if tile_mode(pairs_of[d], world, ntiles, overlapped)]
+    # (--stream keeps the pair split: every rank streams its own pair range, primed with the range's first frame)
+    tiled_dirs = [] if whole or args.stream else [d for d in directories if tile_mode(pairs_of[d], world, ntiles, overlapped)]
     # stale frames are removed by rank 0 before anybody writes (a directory's pairs may be spread over ranks) - only in
     # directories that are in the work list (the single-rank path leaves directories with < 2 inputs untouched)
     if rank == 0 and not whole:

@@ -35,6 +35,12 @@ def read_image(filename: str) -> np.ndarray:
     return rgb.astype(np.float32) / _UINT8_MAX_F
 
 
+def read_image_uint8(filename: str) -> np.ndarray:
+    """8-bit sRGB file -> uint8 [H,W,3]: read_image without the conversion to float32 (read_image(f) == read_image_uint8(f) / 255)."""
+    with _pil().open(filename) as im:
+        return np.asarray(im.convert('RGB'), dtype=np.uint8)
+
+
 def to_uint8(image: np.ndarray) -> np.ndarray:
     """clip(x*255, 0, 255) + 0.5, truncated to uint8 - the reference's rounding (eval/util.py:51-52)."""
     scaled = np.clip(image * _UINT8_MAX_F, 0.0, _UINT8_MAX_F)
@@ -128,6 +134,61 @@ def interpolate_pairs_to_files(inputs: List[str], first: int, end: int, n_pairs:
             raise
         finally:
             stream.close()
+            engine.save_tune_cache()
+    return written, ([kept[i] for i in sorted(kept)] if kept is not None else None)
+
+
+def interpolate_stream_to_files(inputs: List[str], first: int, end: int, n_pairs: int, interpolator: 'interpolator_lib.Interpolator',
+                                frames_dir: str, keep: bool = False, workers: Optional[int] = None):
+    """interpolate_pairs_to_files for times_to_interpolate == 1 through a frame stream (eval/interpolator_cli.py --stream): the input
+    frames [first, end] are decoded as bytes (no float32 frame on the host), pushed one by one through an 8-bit stream
+    (Interpolator.open_stream(pix='u8'): one byte per value each way, one feature extraction per frame) and the mid-frames come back
+    as bytes; decoding and PNG encoding run on a thread pool beside the pushes.  An input frame is written as decoded:
+    to_uint8(u8 / 255) == u8 for every byte value.  Same file names and bytes as interpolate_pairs_to_files; same return value; None
+    for an Interpolator that is not HIP-backed."""
+    engine = getattr(interpolator, 'engine', None)
+    if engine is None or engine.device < 0 or os.environ.get('FILM_HOST_RECURSION') == '1':
+        return None
+    import concurrent.futures
+    nw = workers or max(2, min(32, (os.cpu_count() or 4)))
+    kept = {} if keep else None
+    written = 0
+    with concurrent.futures.ThreadPoolExecutor(max_workers=nw) as enc:
+        pending = []
+
+        def emit(index: int, pixels: np.ndarray) -> None:
+            nonlocal written
+            if kept is not None:
+                kept[index] = pixels
+            pending.append(enc.submit(write_image_uint8, f'{frames_dir}/frame_{index:03d}.png', pixels))
+            written += 1
+
+        reads = {}
+        stream = None
+        try:
+            reads = {i: enc.submit(read_image_uint8, inputs[i]) for i in range(first, min(first + 2, end + 1))} if end > first else {}
+            for i in range(first, end + 1 if end > first else first):
+                px = reads.pop(i).result()
+                if i + 2 <= end:
+                    reads[i + 2] = enc.submit(read_image_uint8, inputs[i + 2])     # decode ahead of the push
+                if stream is None:      # (the first frame of the range primes the stream: it produces nothing)
+                    stream = interpolator.open_stream(px.shape[0], px.shape[1], pix='u8')
+                mid = stream.push(px)
+                if mid is not None:
+                    emit(2 * i - 1, mid)
+                if i < end or i == n_pairs:     # the owner of the last pair also writes the final input frame
+                    emit(2 * i, px)
+            for fu in pending:
+                fu.result()
+        except BaseException:
+            for fu in pending:
+                fu.cancel()
+            for fu in reads.values():
+                fu.cancel()
+            raise
+        finally:
+            if stream is not None:
+                stream.close()
             engine.save_tune_cache()
     return written, ([kept[i] for i in sorted(kept)] if kept is not None else None)
 

@@ -24,7 +24,12 @@ LIB_PATH = os.environ.get('FILM_HIP_LIB') or os.path.join(
 FILM_MEM_HOST = 0
 FILM_MEM_DEVICE = 1
 FILM_ERR_INVALID = -1
+FILM_ERR_STATE = -2
 FILM_ERR_NO_DEVICE = -3
+FILM_ERR_NOMEM = -5
+# pixel types of a frame stream (film_stream_open)
+FILM_PIX_F32, FILM_PIX_U8 = 0, 1
+PIX = {'f32': (FILM_PIX_F32, np.float32), 'u8': (FILM_PIX_U8, np.uint8)}
 # film_image_metrics flags (include/film_hip.h); METRIC_FLAGS maps the metric names of eval/metrics.py to them
 FILM_METRIC_L1, FILM_METRIC_L2, FILM_METRIC_PSNR, FILM_METRIC_SSIM, FILM_METRIC_CLIP = 1, 2, 4, 8, 16
 METRIC_FLAGS = {'l1': FILM_METRIC_L1, 'l2': FILM_METRIC_L2, 'psnr': FILM_METRIC_PSNR, 'ssim': FILM_METRIC_SSIM}
@@ -53,7 +58,8 @@ EXPORTED_SYMBOLS = (
     'film_set_option', 'film_profile_json', 'film_plan_json', 'film_get_tap', 'film_crc32c', 'film_version',
     'film_export_tune', 'film_import_tune', 'film_to_uint8', 'film_load_bundle', 'film_bcast_weights',
     'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json',
-    'film_debug_arena', 'film_debug_run_op')
+    'film_debug_arena', 'film_debug_run_op',
+    'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json')
 
 _lib = None
 
@@ -119,6 +125,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_debug_arena.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, fp, ctypes.c_int]
     lib.film_debug_run_op.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(ctypes.c_int)]
+    lib.film_stream_open.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.film_stream_push.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp]
+    lib.film_stream_reset.argtypes = [vp]
+    lib.film_stream_close.argtypes = [vp]
+    lib.film_stream_plan_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ('film_destroy',):
@@ -155,6 +166,66 @@ def _cfg_struct(opt: Options) -> _Config:
         c.flow_convs[i] = a
         c.flow_filters[i] = b
     return c
+
+
+class FilmStream:
+    """One open frame stream of an engine (film_stream_*; FilmEngine.open_stream): push() one frame at a time and get the mid-frame
+    between it and the frame pushed before - bit-identical to interpolate_frames(previous, frame) - with one feature extraction per
+    frame.  Frames and results are [H,W,3] float32 ('f32') or uint8 ('u8': x = u8 / 255, result = eval.util.to_uint8's bytes).
+    One stream per engine at a time; use it as a context manager or close() it."""
+
+    def __init__(self, engine: 'FilmEngine', h: int, w: int, align: Optional[int], block_shape, pix: str):
+        if pix not in PIX:
+            raise ValueError(f"pix must be 'f32' or 'u8', got {pix!r}")
+        self._eng = engine
+        self.shape = (int(h), int(w), 3)
+        self.pix = pix
+        self._code, self.dtype = PIX[pix]
+        bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
+        engine._check(engine._lib.film_stream_open(engine._h, int(h), int(w), int(align or 0), bh, bw, self._code))
+        self._open = True
+
+    def push(self, frame: np.ndarray, out: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
+        """frame: [H,W,3] host array of the stream's dtype.  None for the first frame after open / reset, else the mid-frame
+        (a new array, or `out`: a writable C-contiguous array of the frame's shape and dtype)."""
+        a = np.asarray(frame)
+        if a.dtype != self.dtype or a.shape != self.shape:
+            raise ValueError(f'expected a {np.dtype(self.dtype).name} array of shape {self.shape}, got {a.dtype} {a.shape}')
+        a = np.ascontiguousarray(a)
+        if out is None:
+            out = np.empty(self.shape, self.dtype)
+        elif out.dtype != self.dtype or out.shape != self.shape or not out.flags['C_CONTIGUOUS'] or not out.flags['WRITEABLE']:
+            raise ValueError(f'out must be a writable C-contiguous {np.dtype(self.dtype).name} array of shape {self.shape}')
+        produced = ctypes.c_int(0)
+        eng = self._eng
+        eng._check(eng._lib.film_stream_push(eng._h, a.ctypes.data, out.ctypes.data, ctypes.byref(produced), FILM_MEM_HOST, None))
+        eng.save_tune_cache()
+        return out if produced.value else None
+
+    def push_device(self, ptr_in: int, ptr_out: int, stream: Optional[int] = None) -> bool:
+        """Device-resident push: raw device pointers to [H,W,3] of the stream's pixel type, asynchronous on `stream`.
+        Returns whether ptr_out receives a mid-frame (False for the first frame after open / reset; ptr_out may then be 0)."""
+        produced = ctypes.c_int(0)
+        eng = self._eng
+        eng._check(eng._lib.film_stream_push(eng._h, ctypes.c_void_p(ptr_in), ctypes.c_void_p(ptr_out) if ptr_out else None,
+                                             ctypes.byref(produced), FILM_MEM_DEVICE, ctypes.c_void_p(stream) if stream else None))
+        return bool(produced.value)
+
+    def reset(self) -> None:
+        """Forgets the carried frame (scene cut, seek): the next push produces nothing."""
+        self._eng._check(self._eng._lib.film_stream_reset(self._eng._h))
+
+    def close(self) -> None:
+        if self._open and getattr(self._eng, '_h', None) is not None and self._eng._h.value:
+            self._open = False
+            self._eng._check(self._eng._lib.film_stream_close(self._eng._h))
+        self._open = False
+
+    def __enter__(self) -> 'FilmStream':
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
 
 
 class FilmEngine:
@@ -387,6 +458,10 @@ class FilmEngine:
                                                         ctypes.c_void_p(out_ptr), FILM_MEM_DEVICE,
                                                         ctypes.c_void_p(stream) if stream else None))
 
+    def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32') -> FilmStream:
+        """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix 'f32' | 'u8'."""
+        return FilmStream(self, h, w, align, block_shape, pix)
+
     @staticmethod
     def _metric_flags(names, clip: bool) -> int:
         unknown = [n for n in names if n not in METRIC_FLAGS]
@@ -464,6 +539,10 @@ class FilmEngine:
     def sequence_plan(self, n_pairs: int, tiles: int, h: int, w: int) -> dict:
         """film_sequence_plan_json: the plan film_interpolate_sequence runs for n_pairs consecutive pairs of `tiles` h x w tiles."""
         return self._json_call(self._lib.film_sequence_plan_json, n_pairs, tiles, h, w)
+
+    def stream_plan(self, tiles: int, h: int, w: int, slot: int) -> dict:
+        """film_stream_plan_json: the plan a stream of `tiles` h x w tiles runs when the pushed frame fills half `slot` (0 / 1)."""
+        return self._json_call(self._lib.film_stream_plan_json, int(tiles), int(h), int(w), int(slot))
 
     def tiling(self, h: int, w: int, align: Optional[int] = None, block_shape=None) -> dict:
         """film_tiling_json: the tile geometry of an h x w frame with the engine's current block_overlap options (resolved overlap,

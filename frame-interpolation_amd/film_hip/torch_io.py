@@ -50,6 +50,35 @@ def patches_to_image(patches: torch.Tensor, block_shape: List[int]) -> torch.Ten
     return patches.reshape(bh, bw, ph, pw, c).permute(0, 2, 1, 3, 4).reshape(1, bh * ph, bw * pw, c).contiguous()
 
 
+class DeviceStream:
+    """A frame stream on frames that already live in HBM (DeviceInterpolator.stream): push(frame) takes a [H,W,3] CUDA tensor, float32
+    or uint8 as opened, and returns the mid-frame between it and the frame pushed before as a new tensor of the same kind - None for
+    the first frame after opening or reset().  Asynchronous on the current torch stream."""
+
+    def __init__(self, engine: FilmEngine, h: int, w: int, align, block_shape, pix: str):
+        self._stream = engine.open_stream(h, w, align=align, block_shape=block_shape, pix=pix)
+        self._dtype = torch.uint8 if pix == 'u8' else torch.float32
+
+    def push(self, frame: torch.Tensor) -> Optional[torch.Tensor]:
+        assert frame.is_cuda and frame.dtype == self._dtype and tuple(frame.shape) == self._stream.shape
+        frame = frame.contiguous()
+        out = torch.empty_like(frame)
+        stream = torch.cuda.current_stream(frame.device).cuda_stream
+        return out if self._stream.push_device(frame.data_ptr(), out.data_ptr(), stream) else None
+
+    def reset(self) -> None:
+        self._stream.reset()
+
+    def close(self) -> None:
+        self._stream.close()
+
+    def __enter__(self) -> 'DeviceStream':
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
 class DeviceInterpolator:
     """Interpolator.__call__ semantics (eval/interpolator.py:178-209) on frames that already live
     in HBM: float32 CUDA(=HIP) tensors in, float32 CUDA tensor out, no host round trip.
@@ -97,6 +126,12 @@ class DeviceInterpolator:
         self._engine.interpolate_sequence_device(frames.data_ptr(), f, h, w, out.data_ptr(), align=self._align,
                                                  block_shape=bs if bs is not None and bs[0] * bs[1] > 1 else None, stream=stream)
         return out
+
+    def stream(self, h: int, w: int, pix: str = 'f32') -> DeviceStream:
+        """Extension: a frame stream of h x w frames (film_stream_*), padded / tiled like batch(): push one CUDA tensor at a time, float32
+        or ('u8') uint8, and get the mid-frame with the frame before - bit-identical to batch(previous, frame), one extraction per frame."""
+        bs = self._block_shape
+        return DeviceStream(self._engine, h, w, self._align, bs if bs is not None and bs[0] * bs[1] > 1 else None, pix)
 
     def __call__(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         if self._block_shape is not None and self._block_shape[0] * self._block_shape[1] > 1:

@@ -150,6 +150,43 @@ int film_interpolate(film_t* h, const float* x0, const float* x1, int B, int H, 
 int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int W, int align, int block_h, int block_w,
                               float* out, int mem_kind, void* stream);
 
+/* Frame STREAMS: film_interpolate for a caller that receives its frames one at a time (a player, a transcoder, a capture card).  The
+ * caller pushes one frame and gets the mid-frame between it and the frame pushed before; the earlier frame's image pyramid and feature
+ * pyramid are read where that push left them, so every frame is extracted once (film_interpolate extracts every inner frame twice)
+ * and nothing is copied between pushes: a stream plan holds the two frames of a pair in two slots that take turns.
+ *   film_stream_open   H x W frames, align / block_h / block_w as for film_interpolate (same padding, tiling, "block_overlap_*",
+ *                      refusals).  pix: FILM_PIX_F32 or FILM_PIX_U8.  ONE open stream per handle (a second open: FILM_ERR_STATE);
+ *                      several streams = several handles, as for threads.  Builds (and autotunes) the plan, so the pushes are steady.
+ *                      The whole frame must fit ONE model invocation: more tiles than the limits of film_interpolate allow (today a
+ *                      4K frame cut 4 x 4 would run as two chunks of 8) is FILM_ERR_INVALID with the limit in the message - use a finer
+ *                      block shape - and a workspace that cannot be allocated is FILM_ERR_NOMEM: a stream neither chunks a frame
+ *                      nor halves on out-of-memory.  Plan-only handle: FILM_ERR_NO_DEVICE; before film_finalize: FILM_ERR_STATE.
+ *   film_stream_push   frame [H,W,3] in, mid [H,W,3] out, both of the stream's pixel type.  The first push after open / reset sets
+ *                      *produced = 0 and only cuts the frame into its tiles and runs the image pyramid and the feature extractor
+ *                      (`mid` is not touched and may be NULL); every later push sets *produced = 1 and writes `mid`, bit-identical
+ *                      to film_interpolate(previous frame, frame, 1, H, W, align, block_h, block_w) under the handle's current
+ *                      options - with FILM_PIX_U8 to film_to_uint8 of that call on the frames u8 / 255.0f, byte for byte.
+ *                      mem_kind / stream as for film_interpolate; FILM_MEM_HOST is upload, work, download ("host_overlap" does not
+ *                      apply) and moves one byte per value each way with FILM_PIX_U8.  Results never depend on what else the handle
+ *                      did between two pushes: the stream keeps its own device copy of the previous frame and extracts it again,
+ *                      silently and with the same bits, when its plan was evicted or dropped meanwhile.  After a push that fails
+ *                      the stream is as after film_stream_reset, and both of the handle's streams are drained before the error returns.
+ *   film_stream_reset  forgets the carried frame (scene cut, seek): the next push produces nothing.
+ *   film_stream_close  frees the stream's buffers (film_destroy closes an open stream too).
+ * push / reset / close without an open stream: FILM_ERR_STATE.
+ *   film_stream_plan_json  the stream plan of `tiles` (padded) H x W tiles in orientation `slot` (0 / 1: the half of the frame buffers
+ *                      the pushed frame fills; pushes alternate) as film_plan_json text with "kind":"stream", "tiles", "slot",
+ *                      "n_extract": B = tiles, img0 / the feature buffers hold 2 * tiles images, ops [0, n_extract) are the pushed
+ *                      frame's image pyramid and extractor (all a first push runs), the rest is the sequence plan of one pair with the
+ *                      earlier frame at image (1 - slot) * tiles.  Both orientations list the same buffers.  Works on plan-only handles. */
+#define FILM_PIX_F32 0   /* frames and results float32 [H,W,3], as everywhere else */
+#define FILM_PIX_U8  1   /* frames and results uint8 [H,W,3]: x = u8 / 255.0f (IEEE, = read_image), result = film_to_uint8's rule */
+int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix);
+int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int mem_kind, void* stream);
+int film_stream_reset(film_t* h);
+int film_stream_close(film_t* h);
+int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* buf, int64_t capacity, int64_t* needed);
+
 /* Execution options.  Keys:
  *   "autotune" 0/1 time every distinct conv shape of a new plan with each fitting tile shape and keep
  *                  the fastest (default 1; cannot change results - same k-ordered fma chain per output)
@@ -231,9 +268,10 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *   "host_overlap" 0/1  1 (default): film_interpolate with FILM_MEM_HOST pipelines its copies with the work - the second frame is uploaded
  *                  while the first layers run on the first frame's tiles, the upper half of the result is downloaded while the last layer
  *                  computes the lower half (one frame, an even number of block rows); 0: upload, work, download.  Same bits.
+ *                  (film_interpolate only: film_interpolate_sequence and film_stream_push always upload, work, download.)
  *                  (Not taken with overlapped tiles, whose upper half depends on the lower tiles: upload, work, download.)
  *   "block_overlap_h" o / "block_overlap_w" o  (extension; -1 .. 65535, default 0 = the reference's disjoint patches, today's kernels)
- *                  the tiled path of film_interpolate / film_interpolate_sequence, per axis of nb blocks of p = n / nb pixels:
+ *                  the tiled path of film_interpolate / film_interpolate_sequence / film_stream_push, per axis of nb blocks of p = n / nb pixels:
  *                  every tile takes o pixels of its neighbours on both sides and the tiles' results are cross-faded over the
  *                  shared pixels, so that no step is left along the patch borders.  nb == 1: no overlap.  -1 ("free"):
  *                  o = min(pad0 / 2, p / 2), pad0 = the zero padding `align` gives a p-sized patch - the padded tile and the

@@ -17,6 +17,8 @@ STUB(hipError_t film_launch_pack_flow(const PackFlowParams&, hipStream_t))
 STUB(hipError_t film_launch_frame_to_tiles(const TileMapParams&, hipStream_t))
 STUB(hipError_t film_launch_tiles_to_frame(const TileMapParams&, hipStream_t))
 STUB(hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams&, hipStream_t))
+STUB(hipError_t film_launch_frame_to_tiles_u8(const TileMapParams&, const uint8_t*, hipStream_t))
+STUB(hipError_t film_launch_frame_to_tiles_overlap_u8(const TileMapParams&, const uint8_t*, hipStream_t))
 STUB(hipError_t film_launch_blend_tiles(const TileMapParams&, hipStream_t))
 STUB(hipError_t film_launch_to_uint8(const float*, uint8_t*, int64_t, hipStream_t))
 STUB(hipError_t film_launch_fill_random(float*, int64_t, uint32_t, hipStream_t))

@@ -1,0 +1,184 @@
+"""Milliseconds per steady-state push of a frame stream (film_stream_*) against the per-pair film_interpolate call of a BASELINE checkout
+(e.g. the parent commit, built), alternating on one box in one session, and against this tree's film_interpolate_sequence.
+
+  python tools/stream_bench.py --baseline-root <checkout of the commit to compare with, built> [--rounds 3] [--out LOG]
+
+A round = one fresh worker process per tree, baseline first: the baseline worker times `pair` (film_interpolate, device-resident, one
+pair per call - what a frame-by-frame caller had before), this tree's worker times `pair` too (the two agree unless the trees differ
+in what a pair call runs: their difference over the rounds IS the box's spread), then `push_f32` / `push_u8` (a steady-state push,
+device-resident), `sequence` (film_interpolate_sequence over a long sequence, per generated frame) and, at the first point, the
+host-buffer calls `host_pair` (film_interpolate on numpy arrays, as bench.py's host_buffers), `host_push_f32`, `host_push_u8`.
+Every measurement: untimed warm-up calls (plan build, autotune, first launches), then --reps timed windows of `n` calls, each
+ended by a device synchronise; the window's ms per call is one sample.  Each tree keeps its autotune choices in a file of its own
+under --scratch, so that the rounds of a tree run the same tiles.  The report gives mean and range over all samples of a
+measurement and, per round, push - baseline pair.  Outputs of push_f32 and the pair call are compared bit for bit in the worker.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (name, height, width, align, block_shape, calls per timed window, frames of the sequence run)
+POINTS = [
+    ('1080p 2x2', 1080, 1920, 64, (2, 2), 30, 16),
+    ('448x256', 256, 448, 64, None, 200, 32),
+    ('256x256', 256, 256, 64, None, 200, 32),
+]
+
+
+def _frames(f, h, w, seed=0):
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    base = rng.random((h, w, 3), dtype=np.float32)
+    return np.clip(np.stack([np.roll(base, (2 * i, -3 * i), axis=(0, 1)) for i in range(f)]), 0, 1).astype(np.float32)
+
+
+def worker(root, reps, quick):
+    """Times what the checkout at `root` offers; prints one JSON line."""
+    for p in (root, os.path.join(root, 'frame-interpolation_amd')):
+        sys.path.insert(0, p)
+    import numpy as np
+    import torch
+    from film_hip import weights as W
+    from film_hip.engine import FilmEngine
+    from film_hip.options import PUBLISHED
+    from film_hip.torch_io import DeviceInterpolator
+    eng = FilmEngine(PUBLISHED, device=0)
+    eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
+    has_stream = hasattr(eng, 'open_stream')
+    out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {}}
+
+    def timed(call, n, warm=3):
+        for _ in range(warm):
+            call()
+        torch.cuda.synchronize()
+        samples = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                call()
+            torch.cuda.synchronize()
+            samples.append((time.perf_counter() - t0) * 1e3 / n)
+        return [round(s, 4) for s in samples]
+
+    for pi, (name, h, w, align, block, n, fseq) in enumerate(POINTS):
+        if quick and pi == 0:
+            continue
+        res = {}
+        it = DeviceInterpolator(eng, align=align, block_shape=list(block) if block else None)
+        fr = _frames(4, h, w)
+        x = [torch.from_numpy(f).cuda() for f in fr]
+        x8 = [torch.from_numpy((f * 255 + 0.5).astype(np.uint8)).cuda() for f in fr]
+        state = {'i': 0}
+
+        def nxt(m):      # the next frame index, round robin
+            state['i'] = (state['i'] + 1) % m
+            return state['i']
+
+        def pair():
+            i = nxt(3)
+            return it.batch(x[i][None], x[i + 1][None])
+
+        res['pair'] = timed(pair, n)
+        if has_stream:
+            want = it.batch(x[0][None], x[1][None])[0]
+            with it.stream(h, w, 'f32') as st:
+                st.push(x[0])
+                res['identical'] = bool(torch.equal(st.push(x[1]), want))
+                res['push_f32'] = timed(lambda: st.push(x[nxt(4)]), n)
+            with it.stream(h, w, 'u8') as st:
+                st.push(x8[0])
+                res['push_u8'] = timed(lambda: st.push(x8[nxt(4)]), n)
+            seq = torch.from_numpy(_frames(fseq, h, w)).cuda()
+            res['sequence'] = [round(s / (fseq - 1), 4) for s in timed(lambda: it.sequence(seq), max(1, n // (fseq - 1)), warm=2)]
+            if pi == 0 or quick and pi == 1:
+                f8 = [(f * 255 + 0.5).astype(np.uint8) for f in fr]
+                hn = max(5, n // 3)
+                res['host_pair'] = timed(lambda: eng.interpolate_frames(fr[:1], fr[1:2], align=align, block_shape=block), hn, warm=2)
+                with eng.open_stream(h, w, align=align, block_shape=block, pix='f32') as st:
+                    st.push(fr[0])
+                    res['host_push_f32'] = timed(lambda: st.push(fr[nxt(4)]), hn, warm=2)
+                with eng.open_stream(h, w, align=align, block_shape=block, pix='u8') as st:
+                    st.push(f8[0])
+                    res['host_push_u8'] = timed(lambda: st.push(f8[nxt(4)]), hn, warm=2)
+            del seq
+        out['points'][name] = res
+        del x, x8
+        torch.cuda.empty_cache()
+    eng.save_tune_cache()
+    eng.close()
+    print('STREAM_BENCH ' + json.dumps(out), flush=True)
+
+
+def _run_worker(root, reps, quick, tune_file):
+    env = dict(os.environ, FILM_TUNE_CACHE=tune_file)
+    cmd = [sys.executable, os.path.abspath(__file__), '--worker', root, '--reps', str(reps)] + (['--quick'] if quick else [])
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)   # (a hung worker ends the run: nothing is started behind it)
+    for line in p.stdout.splitlines():
+        if line.startswith('STREAM_BENCH '):
+            return json.loads(line[len('STREAM_BENCH '):])
+    raise SystemExit(f'worker for {root} failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}')
+
+
+def _stat(v):
+    return f'{statistics.mean(v):8.3f} [{min(v):8.3f} .. {max(v):8.3f}]'
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--baseline-root', default=None, help='a built checkout of the commit to compare with (its film_interpolate is the baseline)')
+    ap.add_argument('--rounds', type=int, default=3, help='alternations baseline / this tree (fresh processes)')
+    ap.add_argument('--reps', type=int, default=3, help='timed windows per measurement and round')
+    ap.add_argument('--quick', action='store_true', help='without the 1080p point')
+    ap.add_argument('--scratch', default=os.path.join(HERE, 'tools', 'scratch'), help='where the per-tree autotune caches go')
+    ap.add_argument('--out', default=None, help='also append the report to this file')
+    ap.add_argument('--worker', default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args(argv)
+    if args.worker:
+        return worker(args.worker, args.reps, args.quick)
+    os.makedirs(args.scratch, exist_ok=True)
+    trees = ([('baseline', os.path.abspath(args.baseline_root))] if args.baseline_root else []) + [('this', HERE)]
+    runs = {k: [] for k, _ in trees}
+    for r in range(args.rounds):
+        for k, root in trees:
+            runs[k].append(_run_worker(root, args.reps, args.quick, os.path.join(args.scratch, f'stream_bench_tune_{k}.txt')))
+            print(f'# round {r + 1}/{args.rounds} {k}: done', flush=True)
+    this = runs['this']
+    lines = [f'# tools/stream_bench.py  this = {this[0]["version"]}' + (f'  baseline = {runs["baseline"][0]["version"]}' if args.baseline_root else '') +
+             f'  {this[0]["device"]}  rounds={args.rounds} reps={args.reps}',
+             '# ms per call, device-resident unless "host": mean [min .. max] over rounds x reps windows']
+    for name, *_ in POINTS:
+        if name not in this[0]['points']:
+            continue
+        lines.append(f'{name}:')
+        pts = [r['points'][name] for r in this]
+        base = [r['points'][name] for r in runs.get('baseline', [])]
+        if base:
+            lines.append(f'  {"baseline pair":<16} {_stat([s for p in base for s in p["pair"]])}')
+        for key in ('pair', 'push_f32', 'push_u8', 'sequence', 'host_pair', 'host_push_f32', 'host_push_u8'):
+            if key in pts[0]:
+                lines.append(f'  {key:<16} {_stat([s for p in pts for s in p[key]])}' + ('   (per generated frame)' if key == 'sequence' else ''))
+        lines.append(f'  push_f32 == pair, bit for bit: {all(p["identical"] for p in pts)}')
+        if base:
+            bm = [statistics.mean(p['pair']) for p in base]
+            spread = max(bm) - min(bm)
+            for key in ('pair', 'push_f32', 'push_u8'):
+                d = [statistics.mean(p[key]) - b for p, b in zip(pts, bm)]
+                lines.append(f'  {key + " - baseline pair":<28} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms')
+            lines.append(f'  spread of the baseline pair call over the rounds (max - min of the round means): {spread:.3f} ms')
+    lines.append('# raw: ' + json.dumps(runs))
+    print('\n'.join(lines), flush=True)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    if not all(p['identical'] for r in this for p in r['points'].values()):
+        raise SystemExit('a push differs from the pair call')
+
+
+if __name__ == '__main__':
+    main()
