@@ -119,6 +119,13 @@ hipError_t cut_tiles(const TileMapParams& tp, hipStream_t s) {
 hipError_t join_tiles(const TileMapParams& tp, hipStream_t s) {
   return (tp.ovy | tp.ovx) ? film_launch_blend_tiles(tp, s) : film_launch_tiles_to_frame(tp, s);
 }
+// cut_tiles on a frame batch of pixel type `pix`: tp.src points at float32 or, with FILM_PIX_U8, at bytes that the cut itself dequantises
+// (whole aligned 32-bit words: the 8-bit kernels read such words)
+hipError_t cut_tiles_pix(const TileMapParams& tp, int pix, hipStream_t s) {
+  if (pix != FILM_PIX_U8) return cut_tiles(tp, s);
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(tp.src);
+  return (tp.ovy | tp.ovx) ? film_launch_frame_to_tiles_overlap_u8(tp, src, s) : film_launch_frame_to_tiles_u8(tp, src, s);
+}
 // The handle's staging buffer in HBM (whole frames of the FILM_MEM_HOST entry points), grown on demand.
 int ensure_stage(film_t* h, size_t bytes, hipStream_t s) {
   if (h->stage_bytes >= bytes) return FILM_OK;
@@ -332,8 +339,7 @@ hipError_t stream_cut(const FilmStream& fs, TileMapParams tp, const Plan* P, int
   tp.tile0 = 0; tp.ntiles = tp.bh * tp.bw;
   tp.src = (const float*)fs.keep;
   tp.dst = P->at("img0") + (int64_t)slot * tp.ntiles * tp.TH * tp.TW * 3;
-  if (fs.pix != FILM_PIX_U8) return cut_tiles(tp, s);
-  return (tp.ovy | tp.ovx) ? film_launch_frame_to_tiles_overlap_u8(tp, (const uint8_t*)fs.keep, s) : film_launch_frame_to_tiles_u8(tp, (const uint8_t*)fs.keep, s);
+  return cut_tiles_pix(tp, fs.pix, s);
 }
 
 // The plan film_debug_arena / film_debug_run_op work on ("Debug / tests" in include/film_hip.h: one planned launch on a workspace the caller controls)
@@ -796,6 +802,36 @@ int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int 
   HIPCHK(h, launch_op(op, P->arena, h->packed_dev, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->last_plan = P;
+  return FILM_OK;
+}
+
+int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h,
+                        int block_w, int tile0, int ntiles, void* stream) {
+  // (the arguments and the geometry are checked before the device: a plan-only handle reports them like a device handle does)
+  if (!h) return FILM_ERR_INVALID;
+  if (!frames_dev || !tiles_dev) return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: NULL argument");
+  if (mode != 0 && mode != 1) return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: bad mode %d: 0 (cut) or 1 (join)", mode);
+  if (pix != FILM_PIX_F32 && pix != FILM_PIX_U8) return fail(h, FILM_ERR_INVALID, "bad pix: FILM_PIX_F32 (0) or FILM_PIX_U8 (1)");
+  if (mode == 1 && pix == FILM_PIX_U8) return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: a join writes float32 frames (FILM_PIX_U8 is for the cut only)");
+  if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
+  TileMapParams tp{};
+  tp.B = B;
+  int rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
+  if (rc) return rc;
+  const int64_t total = (int64_t)B * tp.bh * tp.bw;
+  if (ntiles < 1 || tile0 < 0 || (int64_t)tile0 + ntiles > total)
+    return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: tiles [%d, %lld) are no range of the %lld tiles of the batch", tile0,
+                (long long)tile0 + ntiles, (long long)total);
+  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: film_debug_tile_map needs a HIP device (no CPU fallback)");
+  HIPCHK(h, hipSetDevice(h->device));
+  tp.tile0 = tile0; tp.ntiles = ntiles;
+  if (mode == 0) {
+    tp.src = static_cast<const float*>(frames_dev); tp.dst = tiles_dev;
+    HIPCHK(h, cut_tiles_pix(tp, pix, (hipStream_t)stream));
+  } else {
+    tp.src = tiles_dev; tp.dst = static_cast<float*>(frames_dev);
+    HIPCHK(h, join_tiles(tp, (hipStream_t)stream));
+  }
   return FILM_OK;
 }
 

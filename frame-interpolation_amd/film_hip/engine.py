@@ -58,7 +58,7 @@ EXPORTED_SYMBOLS = (
     'film_set_option', 'film_profile_json', 'film_plan_json', 'film_get_tap', 'film_crc32c', 'film_version',
     'film_export_tune', 'film_import_tune', 'film_to_uint8', 'film_load_bundle', 'film_bcast_weights',
     'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json',
-    'film_debug_arena', 'film_debug_run_op',
+    'film_debug_arena', 'film_debug_run_op', 'film_debug_tile_map',
     'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json')
 
 _lib = None
@@ -125,6 +125,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_debug_arena.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, fp, ctypes.c_int]
     lib.film_debug_run_op.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(ctypes.c_int)]
+    lib.film_debug_tile_map.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     lib.film_stream_open.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.film_stream_push.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp]
     lib.film_stream_reset.argtypes = [vp]
@@ -582,6 +584,18 @@ class FilmEngine:
         n = ctypes.c_int(0)
         self._check(self._lib.film_debug_run_op(self._h, b, h, w, tiles, int(index), int(candidate), ctypes.byref(n)))
         return n.value
+
+    def debug_tile_map(self, mode: str, frames_ptr: int, tiles_ptr: int, b: int, h: int, w: int, align: Optional[int], block_shape,
+                       tile0: int, ntiles: int, u8: bool = False, stream: Optional[int] = None) -> None:
+        """film_debug_tile_map: ONE cut (mode 'cut': frames -> tiles) or join ('join': tiles -> frames) of tiles [tile0, tile0 + ntiles)
+        of b frames [b,h,w,3] on device pointers the caller owns, with the geometry of tiling(h, w, align, block_shape); tile n sits at
+        index n - tile0 of the tile buffer.  u8 (cut only): the frames are bytes in a 4-byte aligned allocation of whole 32-bit words.
+        Asynchronous on `stream` (default stream when None)."""
+        bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
+        self._check(self._lib.film_debug_tile_map(self._h, {'cut': 0, 'join': 1}[mode], FILM_PIX_U8 if u8 else FILM_PIX_F32,
+                                                  ctypes.c_void_p(frames_ptr), ctypes.c_void_p(tiles_ptr), int(b), int(h), int(w),
+                                                  int(align or 0), bh, bw, int(tile0), int(ntiles),
+                                                  ctypes.c_void_p(stream) if stream else None))
 
     def forward_with_aux(self, x0: np.ndarray, x1: np.ndarray) -> Dict[str, object]:
         """The reference model's output dictionary with `use_aux_outputs` on (models/film_net/interpolator.py:

@@ -337,6 +337,22 @@ int film_debug_arena(film_t* h, int B, int H, int W, int tiles, int64_t offset, 
  * (may be NULL) receives the length of that list: 0 for an op that is no convolution, which accepts -1 only.  FILM_ERR_INVALID: no
  * such op, no such candidate. */
 int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int candidate, int* n_candidates);
+/* film_debug_tile_map: ONE cut (mode 0: frames -> tiles) or ONE join (mode 1: tiles -> frames) of tiles [tile0, tile0 + ntiles) of a batch of
+ * B frames [B,H,W,3], on buffers the caller owns (tests/test_tile_map_gpu.py) - the kernels every tiled film_interpolate /
+ * film_interpolate_sequence / film_stream_push moves its pixels with, reached through the same dispatch.  The geometry is what those calls
+ * resolve for (H, W, align, block_h, block_w) and the handle's current "block_overlap_*" (film_tiling_json describes it), with the same refusals.
+ * frames_dev: the frame batch, a DEVICE pointer: float32 with FILM_PIX_F32; with FILM_PIX_U8 (cut only) bytes that the cut dequantises as
+ * u8 / 255.0f - the pointer must then be 4-byte aligned and its allocation a whole number of 32-bit words, as the stream's own frame buffer
+ * is: the kernel reads the aligned words that hold a row's bytes.  tiles_dev: DEVICE float32 [ntiles][padded_h][padded_w][3]; tile n of the
+ * batch is at index n - tile0.  A cut writes all of tiles_dev[0, ntiles) (+0.0 in the padding) and nothing else.  A join writes only frame
+ * pixels that a tile of the range covers: with overlap 0 the patches of the range; with an overlap the cross-fade - a range that starts
+ * behind a pixel's first covering tile goes on from the value in the frame, so the ranges of a frame are applied in tile order.
+ * Asynchronous on `stream` (a hipStream_t; NULL: the default stream).  Needs a device but no weights and no film_finalize; builds no plan and
+ * touches no workspace.  FILM_ERR_INVALID (checked first, so also on a plan-only handle): a NULL pointer, mode not 0 / 1, pix not
+ * FILM_PIX_F32 / FILM_PIX_U8, FILM_PIX_U8 with a join, B, H or W < 1, the refusals of the geometry, ntiles < 1 or a range outside
+ * [0, B * block_h * block_w).  Then FILM_ERR_NO_DEVICE on a plan-only handle.  Not on any forward path. */
+int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h,
+                        int block_w, int tile0, int ntiles, void* stream);
 
 /* The per-image evaluation metrics of the benchmark loop on the device: the reference's losses/losses.py:72-113 (l1, l2, psnr, ssim
  * of eval/eval_cli.py:160-170), restated in frame-interpolation_amd/eval/metrics.py, whose arithmetic the kernels follow (float32

@@ -167,6 +167,32 @@ def test_u8_stream_equals_quantised_float_stream(published, h, w, align, block):
             assert np.array_equal(got[j], util.to_uint8(pairs[j - 1])), (mem, j)
 
 
+@pytest.mark.parametrize('overlap', [(8, 8), (-1, -1)])
+def test_u8_stream_with_overlapped_tiles(published, overlap):
+    """The production route into frame_u8_to_tiles_kernel<true> (stream_cut with FILM_PIX_U8 and an overlap): 256 x 256 in 2 x 2
+    overlapped tiles, align 96.  The bytes == util.to_uint8 of film_interpolate on u8 / 255 with the same overlap, from host and from
+    device memory."""
+    from eval import util
+    opt, weights, eng = published
+    u8 = _frames_u8(3, 256, 256, seed=91)
+    x = u8.astype(np.float32) / 255
+    eng.set_block_overlap(overlap)
+    try:
+        til = eng.tiling(256, 256, align=96, block_shape=(2, 2))
+        assert til['overlap_h'] == til['overlap_w'] == (8 if overlap[0] > 0 else 32) and til['padded_h'] == 192
+        pairs = eng.interpolate_frames(x[:-1], x[1:], align=96, block_shape=(2, 2))
+        got = {mem: _push_all(eng, u8, 96, (2, 2), mem, pix='u8') for mem in ('host', 'device')}
+    finally:
+        eng.set_block_overlap(0)
+    plain = eng.interpolate_frames(x[:1], x[1:2], align=96, block_shape=(2, 2))
+    assert not np.array_equal(util.to_uint8(plain[0]), util.to_uint8(pairs[0]))      # (the overlap was in force)
+    for mem in ('host', 'device'):
+        assert got[mem][0] is None
+        for j in (1, 2):
+            assert got[mem][j].dtype == np.uint8 and got[mem][j].shape == (256, 256, 3)
+            assert np.array_equal(got[mem][j], util.to_uint8(pairs[j - 1])), (mem, j)
+
+
 def test_stream_is_independent_of_other_calls(published):
     """Between pushes: three other shapes through film_interpolate (the stream's plan is evicted: three device plans are kept) and
     "fuse" 31 -> 0 -> 31 (every plan is dropped).  The next pushes still equal the pair calls - the stream extracts the frame it kept."""
