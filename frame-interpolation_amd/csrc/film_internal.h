@@ -9,7 +9,7 @@
 //   film_planner.cpp  the kernel decisions (family and split-K factor of a convolution: plain_conv_family / folded_conv_family / conv_ksplit),
 //                     Planner: the graph of models/film_net/interpolator.py:89-207 as an op list over one workspace arena, one member
 //                     function per stage; the two-lane dependency analysis; film_plan_json's text
-//   film_layers.cpp   the layer table (weight names, shapes, channel permutations) and the kernel-layout packer
+//   film_layers.cpp   the layer table (weight names, shapes, channel permutations), the table of weight layouts and their packer
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -108,10 +108,10 @@ struct LayerPack : ConvWeights {   // (+ the offsets of its weight layouts)
   // [Cout][kh*kw*ctot] with k = tap*ctot + channel; the 1x1 heads keep [ctot][Cout]
   bool kmajor() const { return !c3 && cout % 32 == 0; }
   int64_t b_off = 0;
-  int64_t wf_off = -1;       // 2x2 layers behind a nearest upsample: the four sub-pixel phases, pre-summed weights,
-                             //     phase (py,px) at wf_off + fold_phase_off(py,px): [Cout][ntaps_p * ctot], 9*ctot*cout in all
+  int64_t wf_off = -1;       // 2x2 layers behind a nearest upsample: the four sub-pixel phases, pre-summed weights (fill_wf, film_layers.cpp)
   bool has_halo() const { return kmajor() && kh == 3 && kw == 3; }
   bool has_fold() const { return kmajor() && kh == 2 && kw == 2; }
+  bool has_fold4() const { return has_fold() && ctot() % 16 == 0 && cout % 32 == 0; }   // ... with the difference-form copy (conv_fold4_impl.h)
   // conv_wino2d_kernel against the best 1-D F(4,3) tile of the same run (tools/w2d_bench.hip, profiles/r04_w2d_vs_w43.log): 16-30 %
   // faster on EVERY 3x3 layer of the 1080p plan, K = 32 ... 2448 (round 3's kernel lost below K = 208: its four-round epilogue of dword
   // stores cost 26 000 cycles per workgroup) - every 3x3 layer whose channels come in sixteens and thirty-twos carries the copy
@@ -198,7 +198,7 @@ struct film_handle {
   std::vector<film_internal::LayerPack> layers;
   std::map<std::string, int> layer_idx;
   int64_t packed_floats = 0;          // floats of the PACKED PREFIX (groups [0, groups_packed)); group_end[3] = all layouts
-  int64_t group_end[4] = {0, 0, 0, 0};  // end offset of layout group g (see film_create): 0 base, 1 F(2,3), 2 halo, 3 bf16 splits
+  int64_t group_end[4] = {0, 0, 0, 0};  // end offset of weight layout group g (the groups: kLayouts, film_layers.cpp)
   int groups_packed = 0;
   std::vector<float> packed_host;
   float* packed_dev = nullptr;
@@ -276,6 +276,7 @@ std::string predictor_prefix(const film_config& c, int level);   // pyramid_flow
 int predictor_index(const film_config& c, int level);
 int validate_config(film_t* h, const film_config& c);
 void build_layers(film_t* h);
+int layout_groups(int64_t ConvWeights::* copy);   // the weight layout groups [0, n) that must be packed before a kernel can read `copy`
 
 // The per-op codes plan_json and the tune-cache signatures have always carried for a conv op's family: "c3", "halo", "split"
 // (1 bf16x6, 2 bf16x3) and "wino" (1 F(2,3), 2 bf16x3 F(2,3), 3 F(4,3), 4 nested F(4,3) x F(2,3)).

@@ -31,10 +31,7 @@ struct ConvParams {
   ConvSeg seg[FILM_MAX_SEG];
   int nseg;
   int ksize;          // 1, 2, 3; TF 'same': pad_before = (ksize-1)/2, rest after
-  const float* w;     // conv_buf_kernel: packed [Cout][ksize*ksize*Ctot] (K contiguous per output channel);
-                      // conv_wino_kernel: [Cout][Ctot/8][12][8] (F(2,3)-transformed along x);
-                      // conv_halo_kernel: [Cout][Ctot/16][9][16]; conv_halo_split_kernel: [Cout][Ctot/16][9][3][16] bf16;
-                      // conv_igemm_kernel first-layer mode: [48][Cout]
+  const float* w;     // the copy of the layer's weights that the kernel family reads (ConvFamilyRow::weights; layouts: kLayouts, film_layers.cpp)
   const float* bias;  // [Cout]
   float* out;         // [NB][H][W][ostride], first output channel
   int ostride;
@@ -308,7 +305,7 @@ enum ConvFamily { FAM_BUF /* also fold = 2 */, FAM_C3, FAM_W2D, FAM_W43, FAM_FOL
 constexpr int CONV_TILE_FAMILY = CONV_TILE_C3 | CONV_TILE_HALO | CONV_TILE_SPLIT | CONV_TILE_WINO | CONV_TILE_X3 | CONV_TILE_FOLDX3 |
                                  CONV_TILE_F43 | CONV_TILE_W2D | CONV_TILE_FOLD4;
 
-// Float offsets into the packed weights of the layouts a convolution kernel reads (film_layers.cpp), -1: the layer has none.
+// Float offsets into the packed weights of the layouts a convolution kernel reads (kLayouts, film_layers.cpp), -1: the layer has none.
 // LayerPack and OpDesc (film_internal.h) both carry them; a family's row names the one its kernel reads.
 struct ConvWeights {
   int64_t w_off = 0;      // K-major [Cout][kh*kw*ctot] (first layer: [48][Cout]); an op's conv_buf_kernel weights (fold = 2: the phases)
@@ -317,12 +314,9 @@ struct ConvWeights {
   int64_t ww_off = -1;    // ... the F(2,3)-along-x transformed copy for conv_wino_kernel, [Cout][ctot/8][12][8]
   int64_t wx_off = -1;    // ... and that copy split into bf16 hi / mid for conv_winox3_kernel, [Cout][ctot/16][dy][j][h][plane][16] bf16 (nu = 2h + j)
   int64_t w43_off = -1;   // ... the F(4,3)-along-x transformed copy for conv_wino43_kernel, [Cout][ctot/8][3 dy][6 nu][8]
-  int64_t w2d_off = -1;   // LayerPack::has_w2d() layers: the nested F(4,3)x x F(2,3)y copy for conv_wino2d_kernel,
-                          //     [Cout/32][ctot/8][mu 4][nu 6][K half][32][4] (24 values per (ci, co): 2.67x the kernel)
-  int64_t wfx_off = -1;   // 2x2 layers behind a nearest upsample: the phase-summed weights as bf16 hi / mid for conv_foldx3_kernel,
-                          //     [Cout][ctot/16][9 (tap, phase) steps][plane][16] bf16
-  int64_t wf4_off = -1;   // ... the four planes of the difference form (conv_fold4_impl.h) S = ((W00 + W01) + W10) + W11, Sx = W01 + W11,
-                          //     Sy = W10 + W11, W11 as [Cout/32][ctot/8][plane 4][K half][32][4]: 4*ctot*cout in all
+  int64_t w2d_off = -1;   // LayerPack::has_w2d() layers: the nested F(4,3)x x F(2,3)y copy for conv_wino2d_kernel, [Cout/32][ctot/8][mu 4][nu 6][K half][32][4]
+  int64_t wfx_off = -1;   // 2x2 layers behind a nearest upsample: the phase-summed weights as bf16 hi / mid for conv_foldx3_kernel
+  int64_t wf4_off = -1;   // ... the four planes S, Sx, Sy, W11 of the difference form for conv_fold4_kernel, [Cout/32][ctot/8][plane 4][K half][32][4]
 };
 
 namespace film_internal {   // the autotune candidates of each family (film_tune.cpp)
@@ -334,7 +328,6 @@ std::vector<int> tile_candidates(const OpDesc&), c3_candidates(const OpDesc&), w
 struct ConvFamilyRow {
   int flags;                            // tile-id bits: tile & CONV_TILE_FAMILY
   int64_t ConvWeights::* weights;       // the weight copy its kernel reads
-  int groups;                           // weight layout groups [0, groups) that copy needs packed (film_layers.cpp, build_layers)
   bool splitk;                          // implements ConvParams::ksplit
   bool in_default;                      // in the default library (else FILM_EXTRA_FAMILIES only)
   int fused_shape;                      // >= 0: fuses a 2x2 pool / 1x1 head into its epilogue; this shape carries the RGB head (Cout = 64)
@@ -352,17 +345,17 @@ constexpr int conv_buf_shape(int Cout, int64_t M) {
 constexpr int film_split_shape(int Cout, int64_t) { return Cout % 128 == 0 ? HALO_8x128 : Cout % 64 == 0 ? HALO_4x64 : HALO_8x32; }
 
 inline constexpr ConvFamilyRow kConvFamily[CONV_FAMILIES] = {
-  /* FAM_BUF    */ {0, &ConvWeights::w_off, 1, true, true, -1, film_internal::tile_candidates, conv_buf_shape},
-  /* FAM_C3     */ {CONV_TILE_C3, &ConvWeights::w_off, 1, false, true, -1, film_internal::c3_candidates, [](int, int64_t) -> int { return TILE_C3_DIRECT; }},
-  /* FAM_W2D    */ {CONV_TILE_W2D, &ConvWeights::w2d_off, 1, true, true, W2D_8x64, film_internal::wino2d_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? W2D_8x64 : W2D_8x32; }},
-  /* FAM_W43    */ {CONV_TILE_WINO | CONV_TILE_F43, &ConvWeights::w43_off, 1, true, true, W43_Q16_4x64_N1_P2, film_internal::wino43_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? W43_Q16_4x64_T21_P2 : W43_Q16_4x32_T11_P2; }},
-  /* FAM_FOLD4  */ {CONV_TILE_FOLD4, &ConvWeights::wf4_off, 1, true, true, -1, film_internal::fold4_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? F4_4x64 : F4_4x32; }},
-  /* FAM_HALO   */ {CONV_TILE_HALO, &ConvWeights::wh_off, 3, false, false, -1, film_internal::halo_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? HALO_4x64 : HALO_8x32; }},
-  /* FAM_SPLIT6 */ {CONV_TILE_SPLIT, &ConvWeights::ws_off, 4, false, false, -1, film_internal::halo_candidates, film_split_shape},
-  /* FAM_SPLIT3 */ {CONV_TILE_SPLIT | CONV_TILE_X3, &ConvWeights::ws_off, 4, false, false, -1, film_internal::halo_candidates, film_split_shape},
-  /* FAM_WINO   */ {CONV_TILE_WINO, &ConvWeights::ww_off, 2, false, false, -1, film_internal::wino_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? WINO_4x64_W8 : WINO_4x32; }},
-  /* FAM_WINOX3 */ {CONV_TILE_WINO | CONV_TILE_X3, &ConvWeights::wx_off, 4, false, false, -1, film_internal::winox3_candidates, [](int c, int64_t) -> int { return c % 128 == 0 ? WX3_4x128_T22 : c % 64 == 0 ? WX3_4x64_T12 : WX3_4x32_T11; }},
-  /* FAM_FOLDX3 */ {CONV_TILE_FOLDX3, &ConvWeights::wfx_off, 4, false, false, -1, film_internal::foldx3_candidates, [](int, int64_t) -> int { return FX3_4x64; }},
+  /* FAM_BUF    */ {0, &ConvWeights::w_off, true, true, -1, film_internal::tile_candidates, conv_buf_shape},
+  /* FAM_C3     */ {CONV_TILE_C3, &ConvWeights::w_off, false, true, -1, film_internal::c3_candidates, [](int, int64_t) -> int { return TILE_C3_DIRECT; }},
+  /* FAM_W2D    */ {CONV_TILE_W2D, &ConvWeights::w2d_off, true, true, W2D_8x64, film_internal::wino2d_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? W2D_8x64 : W2D_8x32; }},
+  /* FAM_W43    */ {CONV_TILE_WINO | CONV_TILE_F43, &ConvWeights::w43_off, true, true, W43_Q16_4x64_N1_P2, film_internal::wino43_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? W43_Q16_4x64_T21_P2 : W43_Q16_4x32_T11_P2; }},
+  /* FAM_FOLD4  */ {CONV_TILE_FOLD4, &ConvWeights::wf4_off, true, true, -1, film_internal::fold4_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? F4_4x64 : F4_4x32; }},
+  /* FAM_HALO   */ {CONV_TILE_HALO, &ConvWeights::wh_off, false, false, -1, film_internal::halo_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? HALO_4x64 : HALO_8x32; }},
+  /* FAM_SPLIT6 */ {CONV_TILE_SPLIT, &ConvWeights::ws_off, false, false, -1, film_internal::halo_candidates, film_split_shape},
+  /* FAM_SPLIT3 */ {CONV_TILE_SPLIT | CONV_TILE_X3, &ConvWeights::ws_off, false, false, -1, film_internal::halo_candidates, film_split_shape},
+  /* FAM_WINO   */ {CONV_TILE_WINO, &ConvWeights::ww_off, false, false, -1, film_internal::wino_candidates, [](int c, int64_t) -> int { return c % 64 == 0 ? WINO_4x64_W8 : WINO_4x32; }},
+  /* FAM_WINOX3 */ {CONV_TILE_WINO | CONV_TILE_X3, &ConvWeights::wx_off, false, false, -1, film_internal::winox3_candidates, [](int c, int64_t) -> int { return c % 128 == 0 ? WX3_4x128_T22 : c % 64 == 0 ? WX3_4x64_T12 : WX3_4x32_T11; }},
+  /* FAM_FOLDX3 */ {CONV_TILE_FOLDX3, &ConvWeights::wfx_off, false, false, -1, film_internal::foldx3_candidates, [](int, int64_t) -> int { return FX3_4x64; }},
 };
 
 constexpr bool conv_family_built(int f) { return kConvFamily[f].in_default || kExtraFamilies; }

@@ -78,6 +78,245 @@ std::vector<int> aligned_perm(int C) {
   return p;
 }
 
+// ---- Weight layouts: the transforms, the fill function of every copy, and the ONE table of the copies (kLayouts) ----
+namespace {
+// float -> bfloat16, round to nearest even (what v_cvt_pk_bf16_f32 does; weights are finite)
+inline uint16_t bf16_rne(float x) {
+  uint32_t u;
+  memcpy(&u, &x, 4);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+inline float bf16_to_float(uint16_t b) {
+  const uint32_t u = (uint32_t)b << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+// x as N bf16 planes (hi, mid[, lo]) `stride` apart: each the nearest bf16 of what the planes before it leave of x (conv_split4 on the device)
+template <int N> inline void bf16_split(float x, uint16_t* d, int stride) {
+  for (int p = 0; p < N; ++p) {
+    const uint16_t b = bf16_rne(x);
+    d[p * stride] = b;
+    x = x - bf16_to_float(b);
+  }
+}
+// Winograd kernel transforms of three taps g0 g1 g2, the results `stride` apart: F(4,3) -> 6 values, F(2,3) -> 4 values
+inline void wino43_taps(float g0, float g1, float g2, float* u, int stride) {
+  const float e = g0 * (1.f / 24.f) + g2 * (1.f / 6.f), o = g1 * (1.f / 12.f);
+  u[0] = g0 * 0.25f;
+  u[stride] = -((g0 + g2) + g1) * (1.f / 6.f);
+  u[2 * stride] = -((g0 + g2) - g1) * (1.f / 6.f);
+  u[3 * stride] = e + o; u[4 * stride] = e - o;
+  u[5 * stride] = g2;
+}
+inline void wino23_taps(float g0, float g1, float g2, float* u, int stride) {
+  u[0] = g0; u[stride] = ((g0 + g2) + g1) * 0.5f; u[2 * stride] = ((g0 + g2) - g1) * 0.5f; u[3 * stride] = g2;
+}
+// The HWIO row (`cout` contiguous floats) of kernel tap `tap` and INTERNAL input channel ci; nullptr: a zero (padding) channel
+inline const float* hwio_row(const LayerPack& L, const float* src, int tap, size_t ci) {
+  const int ref = L.perm[ci];
+  return ref < 0 ? nullptr : src + ((size_t)tap * L.cin + ref) * L.cout;
+}
+inline float at(const float* row, int co) { return row ? row[co] : 0.f; }
+
+// The three walks over a K-major layer that the copies share.  Each hands f weights of ONE output channel co in [co0, co1): an output
+// channel owns disjoint ranges of every copy, which lets the packing threads share the blob.  f(co, tap, kc, v): the 16 weights of kernel tap
+// `tap`, input channels [16 kc, 16 kc + 16) - the 16 source rows stay in L1 while every output channel receives its 16 k values
+template <class F> void for_each_k16(const LayerPack& L, const float* src, int co0, int co1, F f) {
+  for (int tap = 0; tap < L.kh * L.kw; ++tap)
+    for (size_t kc = 0; kc < (size_t)L.ctot() / 16; ++kc) {
+      const float* rows[16];
+      for (int j = 0; j < 16; ++j) rows[j] = hwio_row(L, src, tap, kc * 16 + j);
+      for (int co = co0; co < co1; ++co) {
+        float v[16];
+        for (int j = 0; j < 16; ++j) v[j] = at(rows[j], co);
+        f(co, tap, kc, v);
+      }
+    }
+}
+// f(co, dy, kc, g): g[dx][j] = the three taps of kernel row dy of a 3x3 layer, input channels [8 kc, 8 kc + 8)
+template <class F> void for_each_row_k8(const LayerPack& L, const float* src, int co0, int co1, F f) {
+  for (int dy = 0; dy < 3; ++dy)
+    for (size_t kc = 0; kc < (size_t)L.ctot() / 8; ++kc) {
+      const float* rows[3][8];
+      for (int dx = 0; dx < 3; ++dx)
+        for (int j = 0; j < 8; ++j) rows[dx][j] = hwio_row(L, src, dy * 3 + dx, kc * 8 + j);
+      for (int co = co0; co < co1; ++co) {
+        float g[3][8];
+        for (int dx = 0; dx < 3; ++dx)
+          for (int j = 0; j < 8; ++j) g[dx][j] = at(rows[dx][j], co);
+        f(co, dy, kc, g);
+      }
+    }
+}
+// Sub-pixel phases of upsample + 2x2.  f(co, ci, py, px, a, b, w): w = the weight of output phase (py, px) for the low-resolution tap
+// (a, b), a <= py, b <= px = the kernel taps (dy, dx) that read that pixel, (py & dy) == a and (px & dx) == b, summed in raster order.
+// Padding channels are skipped: their weights stay zero.
+template <class F> void for_each_fold_weight(const LayerPack& L, const float* src, int co0, int co1, F f) {
+  for (int py = 0; py < 2; ++py)
+    for (int px = 0; px < 2; ++px)
+      for (int a = 0; a <= py; ++a)
+        for (int b = 0; b <= px; ++b)
+          for (int ci = 0; ci < L.ctot(); ++ci) {
+            const float* rows[4];
+            for (int tp = 0; tp < 4; ++tp) rows[tp] = hwio_row(L, src, tp, ci);
+            if (!rows[0]) continue;
+            for (int co = co0; co < co1; ++co) {
+              float acc = 0.f;
+              for (int dy = 0; dy < 2; ++dy)
+                for (int dx = 0; dx < 2; ++dx)
+                  if ((py & dy) == a && (px & dx) == b) acc += rows[dy * 2 + dx][co];
+              f(co, ci, py, px, a, b, acc);
+            }
+          }
+}
+
+// ---- the fill functions: output channels [co0, co1) of one copy (dst = its first float) from the HWIO kernel (bias: from the bias).
+// The copies that are not per-channel (first layer, 1x1 heads, bias) are packed once, by the caller of co0 == 0.
+void fill_bias(const LayerPack& L, const float*, const float* bias, float* dst, int co0, int) { if (co0 == 0) memcpy(dst, bias, sizeof(float) * L.cout); }
+// K-major [Cout][kh*kw*ctot], k = tap * ctot + channel.  First layer: [12 tap slots][4][Cout], 1x1 heads: [ctot][Cout] - whole rows
+void fill_w(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const int ct = L.ctot();
+  if (L.kmajor()) {
+    const size_t ktot = (size_t)L.kh * L.kw * ct;
+    for_each_k16(L, src, co0, co1, [&](int co, int tap, size_t kc, const float* v) { memcpy(dst + (size_t)co * ktot + (size_t)tap * ct + kc * 16, v, 16 * sizeof(float)); });
+  } else if (co0 == 0) {
+    for (int tap = 0; tap < L.kh * L.kw; ++tap)
+      for (int ci = 0; ci < ct; ++ci)
+        if (const float* row = hwio_row(L, src, tap, ci)) memcpy(dst + ((size_t)tap * (L.c3 ? 4 : ct) + ci) * L.cout, row, sizeof(float) * L.cout);
+  }
+}
+// conv_halo_kernel: [Cout][ctot/16][9][16]
+void fill_wh(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t nkc = (size_t)L.ctot() / 16;
+  for_each_k16(L, src, co0, co1, [&](int co, int tap, size_t kc, const float* v) { memcpy(dst + (((size_t)co * nkc + kc) * 9 + tap) * 16, v, 16 * sizeof(float)); });
+}
+// conv_halo_split_kernel: the same cells as three bf16 planes, [Cout][ctot/16][9][3][16] bf16
+void fill_ws(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t nkc = (size_t)L.ctot() / 16;
+  for_each_k16(L, src, co0, co1, [&](int co, int tap, size_t kc, const float* v) {
+    uint16_t* d = reinterpret_cast<uint16_t*>(dst) + (((size_t)co * nkc + kc) * 9 + tap) * 48;
+    for (int j = 0; j < 16; ++j) bf16_split<3>(v[j], d + j, 16);
+  });
+}
+// the four phases one behind the other, phase (py, px): [Cout][ntaps * ctot], tap t = a * (px + 1) + b; 1 + 2 + 2 + 4 = 9 taps in all
+void fill_wf(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t ct = L.ctot();
+  for_each_fold_weight(L, src, co0, co1, [&](int co, int ci, int py, int px, int a, int b, float w) {
+    static const int kTapsBefore[4] = {0, 1, 3, 5};
+    dst[(kTapsBefore[py * 2 + px] * L.cout + (size_t)co * (py + 1) * (px + 1) + a * (px + 1) + b) * ct + ci] = w;
+  });
+}
+// conv_foldx3_kernel: the phase weights as bf16 hi / mid, [Cout][ctot/16][9 (tap, phase) steps][plane][16] bf16
+void fill_wfx(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t nkc = (size_t)L.ctot() / 16;
+  // step of (tap a*2+b, phase py*2+px) in the kernel's order (taps 00 00 00 | 00 01 01 | 10 10 11)
+  static const int kFoldStep[4][4] = {{0, 1, 2, 3}, {-1, 4, -1, 5}, {-1, -1, 6, 7}, {-1, -1, -1, 8}};
+  for_each_fold_weight(L, src, co0, co1, [&](int co, int ci, int py, int px, int a, int b, float w) {
+    bf16_split<2>(w, reinterpret_cast<uint16_t*>(dst) + (((size_t)co * nkc + ci / 16) * 9 + kFoldStep[a * 2 + b][py * 2 + px]) * 32 + ci % 16, 16);
+  });
+}
+// conv_fold4_kernel, the difference form of upsample + 2x2: [Cout/32][ctot/8][plane 4][K half][32][4], planes S = ((W00 + W01) + W10) + W11,
+// Sx = W01 + W11, Sy = W10 + W11, W11 (padding channels: zero rows)
+void fill_wf4(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t nk8 = (size_t)L.ctot() / 8;
+  for (int ci = 0; ci < L.ctot(); ++ci) {
+    const float* rows[4];
+    for (int tp = 0; tp < 4; ++tp) rows[tp] = hwio_row(L, src, tp, ci);
+    for (int co = co0; co < co1; ++co) {
+      const float w[4] = {at(rows[0], co), at(rows[1], co), at(rows[2], co), at(rows[3], co)};
+      const float pl[4] = {((w[0] + w[1]) + w[2]) + w[3], w[1] + w[3], w[2] + w[3], w[3]};
+      for (int q = 0; q < 4; ++q)
+        dst[((((size_t)(co / 32) * nk8 + ci / 8) * 4 + q) * 2 + (ci % 8) / 4) * 128 + (co % 32) * 4 + ci % 4] = pl[q];
+    }
+  }
+}
+// conv_wino43_kernel: F(4,3) along x, [Cout][ctot/8][3 dy][6 nu][8]
+void fill_w43(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t nk8 = (size_t)L.ctot() / 8;
+  for_each_row_k8(L, src, co0, co1, [&](int co, int dy, size_t kc, const float (*g)[8]) {
+    for (int j = 0; j < 8; ++j) wino43_taps(g[0][j], g[1][j], g[2][j], dst + (((size_t)co * nk8 + kc) * 3 + dy) * 48 + j, 8);
+  });
+}
+// conv_wino_kernel: F(2,3) along x, [Cout][ctot/8][nu * 3 + dy][8]
+void fill_ww(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t nk8 = (size_t)L.ctot() / 8;
+  for_each_row_k8(L, src, co0, co1, [&](int co, int dy, size_t kc, const float (*g)[8]) {
+    for (int j = 0; j < 8; ++j) wino23_taps(g[0][j], g[1][j], g[2][j], dst + (((size_t)co * nk8 + kc) * 12 + dy) * 8 + j, 24);
+  });
+}
+// conv_winox3_kernel: the same transformed weights as bf16 hi / mid, [Cout][ctot/16][dy][j][h][plane][16] bf16 (nu = 2h + j)
+void fill_wx(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t nk16 = (size_t)L.ctot() / 16;
+  for_each_row_k8(L, src, co0, co1, [&](int co, int dy, size_t kc, const float (*g)[8]) {
+    float u[4][8];
+    for (int j = 0; j < 8; ++j) wino23_taps(g[0][j], g[1][j], g[2][j], &u[0][j], 8);
+    for (int nu = 0; nu < 4; ++nu) {
+      uint16_t* d = reinterpret_cast<uint16_t*>(dst) + ((((size_t)co * nk16 + kc / 2) * 3 + dy) * 2 + (nu & 1)) * 64 + (nu >> 1) * 32 + (kc & 1) * 8;
+      for (int j = 0; j < 8; ++j) bf16_split<2>(u[nu][j], d + j, 16);
+    }
+  });
+}
+// conv_wino2d_kernel: U[mu][nu] = F(2,3) along dy of the F(4,3)-along-dx transformed kernel rows (the u of the w43 copy),
+// [Cout/32][ctot/8][mu 4][nu 6][K half][32][4]
+void fill_w2d(const LayerPack& L, const float* src, const float*, float* dst, int co0, int co1) {
+  const size_t nk8 = (size_t)L.ctot() / 8;
+  for (size_t kc = 0; kc < nk8; ++kc) {
+    const float* rows[9][8];
+    for (int tap = 0; tap < 9; ++tap)
+      for (int j = 0; j < 8; ++j) rows[tap][j] = hwio_row(L, src, tap, kc * 8 + j);
+    for (int co = co0; co < co1; ++co)
+      for (int j = 0; j < 8; ++j) {
+        float u[3][6], U[4];
+        for (int dy = 0; dy < 3; ++dy) wino43_taps(at(rows[dy * 3][j], co), at(rows[dy * 3 + 1][j], co), at(rows[dy * 3 + 2][j], co), u[dy], 1);
+        for (int nu = 0; nu < 6; ++nu) {
+          wino23_taps(u[0][nu], u[1][nu], u[2][nu], U, 1);
+          for (int mu = 0; mu < 4; ++mu)
+            dst[(((((size_t)(co / 32) * nk8 + kc) * 4 + mu) * 6 + nu) * 2 + j / 4) * 128 + (co % 32) * 4 + j % 4] = U[mu];
+        }
+      }
+  }
+}
+
+// THE table of weight layouts: one row per copy of a layer's weights in the packed blob.  The copies lie in four contiguous GROUPS, packed
+// and uploaded on demand (film_finalize: what the options need at once; the planner: the group of the copy a kernel family reads,
+// layout_groups, when a plan first needs it), so that the default fp32 path neither builds nor broadcasts the copies it never reads:
+//   0 = what the default plan runs on: K-major / first-layer / 1x1 layouts + biases, both forms of the upsample + 2x2 layers, the F(4,3)
+//       and nested Winograd copies (3.1x the parameters);  1 = F(2,3) copy (conv_wino_kernel: levels narrower than the F(4,3) patches);
+//   2 = halo copy (conv_halo_kernel: option winograd = 0 / halo_all);  3 = bf16 split copies (precision modes bf16x6 / bf16x3).
+// Within a group the copies follow each other layer by layer, within a layer in row order, each from a multiple of four floats.  Offsets
+// are an external format (plan JSON); tests/plan_interp.py restates every layout independently.
+struct WeightLayout {
+  int64_t LayerPack::* off;                // receives the copy's offset in the blob (floats; -1: the layer has no such copy)
+  int group;
+  bool (LayerPack::*has)() const;          // the layers that have the copy; nullptr: all
+  int64_t (*floats)(const LayerPack&);
+  void (*fill)(const LayerPack& L, const float* kernel, const float* bias, float* dst, int co0, int co1);
+  bool on(const LayerPack& L) const { return !has || (L.*has)(); }
+};
+int64_t weights_of(const LayerPack& L) { return (int64_t)L.ctot() * L.cout; }   // per kernel tap
+const WeightLayout kLayouts[] = {
+  {&LayerPack::w_off, 0, nullptr, [](const LayerPack& L) { return L.packed_rows() * L.cout; }, fill_w},
+  {&LayerPack::b_off, 0, nullptr, [](const LayerPack& L) { return (int64_t)L.cout; }, fill_bias},
+  {&LayerPack::wf_off, 0, &LayerPack::has_fold, [](const LayerPack& L) { return 9 * weights_of(L); }, fill_wf},
+  {&LayerPack::wf4_off, 0, &LayerPack::has_fold4, [](const LayerPack& L) { return 4 * weights_of(L); }, fill_wf4},
+  {&LayerPack::w43_off, 0, &LayerPack::has_halo, [](const LayerPack& L) { return 3 * 6 * weights_of(L); }, fill_w43},
+  {&LayerPack::w2d_off, 0, &LayerPack::has_w2d, [](const LayerPack& L) { return 4 * 6 * weights_of(L); }, fill_w2d},
+  {&LayerPack::ww_off, 1, &LayerPack::has_halo, [](const LayerPack& L) { return 3 * 4 * weights_of(L); }, fill_ww},
+  {&LayerPack::wh_off, 2, &LayerPack::has_halo, [](const LayerPack& L) { return 9 * weights_of(L); }, fill_wh},
+  {&LayerPack::wfx_off, 3, &LayerPack::has_fold, [](const LayerPack& L) { return 9 * weights_of(L); }, fill_wfx},               // 2 bf16 = 1 float
+  {&LayerPack::ws_off, 3, &LayerPack::has_halo, [](const LayerPack& L) { return (9 * weights_of(L) * 3 + 1) / 2; }, fill_ws},   // 3 bf16 = 1.5
+  {&LayerPack::wx_off, 3, &LayerPack::has_halo, [](const LayerPack& L) { return 3 * 4 * weights_of(L); }, fill_wx},
+};
+}  // namespace
+
+int layout_groups(int64_t ConvWeights::* copy) {
+  for (const WeightLayout& r : kLayouts)
+    if (r.off == static_cast<int64_t LayerPack::*>(copy)) return r.group + 1;
+  return 1;
+}
+
 void build_layers(film_t* h) {
   const film_config& c = h->cfg;
   h->layers.clear();
@@ -123,61 +362,21 @@ void build_layers(film_t* h) {
     add("fusion/convs_" + std::to_string(i) + "_2", 3, 3, ff[i], ff[i], identity_perm(ff[i]));
   }
   add("fusion/output_conv", 1, 1, ff[0], 3, identity_perm(ff[0]));
-  // Weight layouts in four contiguous GROUPS, packed on demand (film_finalize packs group 0; the planner asks for the
-  // others when a plan first needs them) so that the default fp32 path neither builds nor broadcasts the copies it never
-  // reads:  0 = what the default plan runs on: K-major / first-layer / 1x1 layouts + biases, the phase-summed 2x2
-  //             layers, the F(4,3) copy                                                     (3.1x the parameters)
-  //         1 = F(2,3) copy (conv_wino_kernel: levels narrower than the F(4,3) patches)
-  //         2 = halo copy (conv_halo_kernel: option winograd = 0 / halo_all)
-  //         3 = bf16 split copies (precision modes bf16x6 / bf16x3)
+  // offsets: group by group, layer by layer, in the order of the table's rows
   int64_t off = 0;
-  auto al = [&]() { off = (off + 3) & ~int64_t(3); };
-  for (auto& L : h->layers) {
-    L.w_off = off; off += L.packed_rows() * L.cout; al();
-    L.b_off = off; off += L.cout; al();
-    if (L.has_fold()) { L.wf_off = off; off += (int64_t)9 * L.ctot() * L.cout; al(); }
-    if (L.has_fold() && L.ctot() % 16 == 0 && L.cout % 32 == 0) { L.wf4_off = off; off += (int64_t)4 * L.ctot() * L.cout; al(); }
-    if (L.has_halo()) { L.w43_off = off; off += L.packed_rows() * L.cout / 9 * 18; al(); }
-    if (L.has_w2d()) { L.w2d_off = off; off += L.packed_rows() * L.cout / 9 * 24; al(); }
+  for (int g = 0; g < 4; ++g) {
+    for (auto& L : h->layers)
+      for (const WeightLayout& r : kLayouts)
+        if (r.group == g && r.on(L)) { L.*r.off = off; off = (off + r.floats(L) + 3) & ~int64_t(3); }
+    h->group_end[g] = off;
   }
-  h->group_end[0] = off;
-  for (auto& L : h->layers)
-    if (L.has_halo()) { L.ww_off = off; off += L.packed_rows() * L.cout / 9 * 12; al(); }
-  h->group_end[1] = off;
-  for (auto& L : h->layers)
-    if (L.has_halo()) { L.wh_off = off; off += L.packed_rows() * L.cout; al(); }
-  h->group_end[2] = off;
-  for (auto& L : h->layers) {
-    if (L.has_fold()) { L.wfx_off = off; off += (int64_t)9 * L.ctot() * L.cout; al(); }
-    if (L.has_halo()) {
-      L.ws_off = off; off += (L.packed_rows() * L.cout * 3 + 1) / 2; al();
-      L.wx_off = off; off += L.packed_rows() * L.cout / 9 * 12; al();
-    }
-  }
-  h->group_end[3] = off;
   h->packed_floats = 0;
   h->groups_packed = 0;
 }
 
-
 }  // namespace film_internal
 
 using namespace film_internal;
-
-// float -> bfloat16, round to nearest even (what v_cvt_pk_bf16_f32 does; weights are finite)
-static inline uint16_t bf16_rne(float x) {
-  uint32_t u;
-  memcpy(&u, &x, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float bf16_to_float(uint16_t b) {
-  const uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
 
 extern "C" {
 
@@ -246,204 +445,6 @@ static int upload_packed(film_t* h, int64_t from, int64_t to) {
   return FILM_OK;
 }
 
-// Packs the layouts of `group` of layer L for the output channels [co0, co1) (the unit of work of the packing threads;
-// every output channel owns disjoint ranges of every layout).  Layers without a per-channel layout (first layer, 1x1
-// heads) and the biases are handled by the caller of co0 == 0.
-static void pack_layer_group(film_t* h, const LayerPack& L, int group, int co0, int co1) {
-  const float* src = h->host_w.at(L.name + "/kernel").data.data();
-  float* const base = h->packed_host.data();
-  const int ct = L.ctot();
-  if (group == 0 && co0 == 0) {
-    memcpy(base + L.b_off, h->host_w.at(L.name + "/bias").data.data(), sizeof(float) * L.cout);
-    float* dst = base + L.w_off;
-    if (L.c3) {
-      for (int tap = 0; tap < 9; ++tap)
-        for (int c = 0; c < 3; ++c)
-          memcpy(dst + ((size_t)tap * 4 + c) * L.cout, src + ((size_t)tap * 3 + c) * L.cout, sizeof(float) * L.cout);
-    } else if (!L.kmajor()) {
-      for (int tap = 0; tap < L.kh * L.kw; ++tap)
-        for (int ci = 0; ci < ct; ++ci) {
-          const int ref = L.perm[ci];
-          if (ref < 0) continue;  // zero row (padding channel)
-          memcpy(dst + ((size_t)tap * ct + ci) * L.cout, src + ((size_t)tap * L.cin + ref) * L.cout, sizeof(float) * L.cout);
-        }
-    }
-  }
-  if (!L.kmajor()) return;
-  const int ntap = L.kh * L.kw;
-  const size_t ktot = (size_t)ntap * ct;
-  const size_t nkc = (size_t)ct / 16;
-  // ---- K-major copy (group 0), halo copy (group 2), bf16x6 planes (group 3): one pass per (tap, 16-channel chunk); the
-  // 16 source rows (each `cout` contiguous floats) stay in L1 while every output channel receives its 16 k values
-  float* dk = group == 0 ? base + L.w_off : nullptr;
-  float* dh = group == 2 && L.wh_off >= 0 ? base + L.wh_off : nullptr;
-  uint16_t* ds = group == 3 && L.ws_off >= 0 ? reinterpret_cast<uint16_t*>(base + L.ws_off) : nullptr;
-  if (dk || dh || ds)
-    for (int tap = 0; tap < ntap; ++tap)
-      for (size_t kc = 0; kc < nkc; ++kc) {
-        const float* rows[16];
-        for (int j = 0; j < 16; ++j) {
-          const int ref = L.perm[kc * 16 + j];
-          rows[j] = ref < 0 ? nullptr : src + ((size_t)tap * L.cin + ref) * L.cout;  // nullptr: zero (padding) channel
-        }
-        for (int co = co0; co < co1; ++co) {
-          float v[16];
-          for (int j = 0; j < 16; ++j) v[j] = rows[j] ? rows[j][co] : 0.f;
-          if (dk) memcpy(dk + (size_t)co * ktot + (size_t)tap * ct + kc * 16, v, sizeof(v));
-          if (dh) memcpy(dh + (((size_t)co * nkc + kc) * 9 + tap) * 16, v, sizeof(v));
-          if (ds) {  // exact 3-way bf16 split, round-to-nearest-even pieces (same as conv_split4 on the device)
-            uint16_t* d = ds + (((size_t)co * nkc + kc) * 9 + tap) * 48;
-            for (int j = 0; j < 16; ++j) {
-              const uint16_t hb = bf16_rne(v[j]);
-              const float r = v[j] - bf16_to_float(hb);
-              const uint16_t mb = bf16_rne(r);
-              const float q = r - bf16_to_float(mb);
-              d[j] = hb; d[16 + j] = mb; d[32 + j] = bf16_rne(q);
-            }
-          }
-        }
-      }
-  // ---- sub-pixel phases of upsample + 2x2: weights of the taps that read the same input pixel, summed (fp32: group 0;
-  // bf16 hi / mid for conv_foldx3_kernel: group 3)
-  if (L.wf_off >= 0 && (group == 0 || group == 3)) {
-    float* df = base + L.wf_off;
-    uint16_t* dfx = reinterpret_cast<uint16_t*>(base + L.wfx_off);
-    const size_t nk16f = (size_t)ct / 16;
-    // step of (tap a*2+b, phase py*2+px) in conv_foldx3_kernel's order (taps 00 00 00 | 00 01 01 | 10 10 11)
-    static const int kFoldStep[4][4] = {{0, 1, 2, 3}, {-1, 4, -1, 5}, {-1, -1, 6, 7}, {-1, -1, -1, 8}};
-    for (int py = 0; py < 2; ++py)
-      for (int px = 0; px < 2; ++px) {
-        const int nt = (py + 1) * (px + 1);
-        const size_t kph = (size_t)nt * ct;
-        int t = 0;
-        for (int a = 0; a <= py; ++a)
-          for (int b = 0; b <= px; ++b, ++t)
-            for (int ci = 0; ci < ct; ++ci) {
-              const int ref = L.perm[ci];
-              if (ref < 0) continue;
-              for (int co = co0; co < co1; ++co) {
-                float acc = 0.f;  // kernel taps (dy, dx) with (py & dy) == a and (px & dx) == b, in raster order
-                for (int dy = 0; dy < 2; ++dy)
-                  for (int dx = 0; dx < 2; ++dx)
-                    if ((py & dy) == a && (px & dx) == b) acc += src[((size_t)(dy * 2 + dx) * L.cin + ref) * L.cout + co];
-                if (group == 0) df[(size_t)co * kph + (size_t)t * ct + ci] = acc;
-                else {
-                  const int step = kFoldStep[a * 2 + b][py * 2 + px];
-                  uint16_t* d = dfx + (((size_t)co * nk16f + ci / 16) * 9 + step) * 32 + ci % 16;
-                  const uint16_t hb = bf16_rne(acc);
-                  d[0] = hb;
-                  d[16] = bf16_rne(acc - bf16_to_float(hb));
-                }
-              }
-            }
-        df += kph * L.cout;
-      }
-  }
-  // ---- difference form of upsample + 2x2 (group 0; conv_fold4_impl.h): [Cout/32][chunk8][plane 4][K half][32][4], planes S = ((W00 + W01) +
-  // W10) + W11, Sx = W01 + W11, Sy = W10 + W11, W11 (padding channels: zero rows)
-  if (group == 0 && L.wf4_off >= 0) {
-    float* d4 = base + L.wf4_off;
-    const size_t nk8 = (size_t)ct / 8;
-    for (int ci = 0; ci < ct; ++ci) {
-      const int ref = L.perm[ci];
-      for (int co = co0; co < co1; ++co) {
-        float w[4] = {0.f, 0.f, 0.f, 0.f};
-        if (ref >= 0)
-          for (int tp = 0; tp < 4; ++tp) w[tp] = src[((size_t)tp * L.cin + ref) * L.cout + co];
-        const float pl[4] = {((w[0] + w[1]) + w[2]) + w[3], w[1] + w[3], w[2] + w[3], w[3]};
-        for (int q = 0; q < 4; ++q)
-          d4[((((size_t)(co / 32) * nk8 + ci / 8) * 4 + q) * 2 + (ci % 8) / 4) * 128 + (co % 32) * 4 + ci % 4] = pl[q];
-      }
-    }
-  }
-  // ---- nested Winograd copy (group 0, deep-K layers): U[mu][nu] = the F(2,3) transform along dy of the F(4,3)-transformed
-  // kernel rows u_nu(dy) (the same u as the w43 copy), [Cout/32][chunk8][mu 4][nu 6][K half][32][4]
-  if (group == 0 && L.w2d_off >= 0) {
-    float* d2 = base + L.w2d_off;
-    const size_t nk8 = (size_t)ct / 8;
-    for (size_t kc = 0; kc < nk8; ++kc) {
-      const float* rows[3][3][8];
-      for (int dy = 0; dy < 3; ++dy)
-        for (int dx = 0; dx < 3; ++dx)
-          for (int j = 0; j < 8; ++j) {
-            const int ref = L.perm[kc * 8 + j];
-            rows[dy][dx][j] = ref < 0 ? nullptr : src + ((size_t)(dy * 3 + dx) * L.cin + ref) * L.cout;
-          }
-      for (int co = co0; co < co1; ++co)
-        for (int j = 0; j < 8; ++j) {
-          float u[3][6];
-          for (int dy = 0; dy < 3; ++dy) {
-            const float g0 = rows[dy][0][j] ? rows[dy][0][j][co] : 0.f, g1 = rows[dy][1][j] ? rows[dy][1][j][co] : 0.f,
-                        g2 = rows[dy][2][j] ? rows[dy][2][j][co] : 0.f;
-            const float e = g0 * (1.f / 24.f) + g2 * (1.f / 6.f), o = g1 * (1.f / 12.f);
-            u[dy][0] = g0 * 0.25f;
-            u[dy][1] = -((g0 + g2) + g1) * (1.f / 6.f);
-            u[dy][2] = -((g0 + g2) - g1) * (1.f / 6.f);
-            u[dy][3] = e + o;
-            u[dy][4] = e - o;
-            u[dy][5] = g2;
-          }
-          for (int nu = 0; nu < 6; ++nu) {
-            const float U[4] = {u[0][nu], ((u[0][nu] + u[2][nu]) + u[1][nu]) * 0.5f, ((u[0][nu] + u[2][nu]) - u[1][nu]) * 0.5f, u[2][nu]};
-            for (int mu = 0; mu < 4; ++mu)
-              d2[(((((size_t)(co / 32) * nk8 + kc) * 4 + mu) * 6 + nu) * 2 + j / 4) * 128 + (co % 32) * 4 + j % 4] = U[mu];
-          }
-        }
-    }
-  }
-  // ---- Winograd copies along x: F(4,3) [Cout][chunk8][dy][nu 6][8] (group 0), F(2,3) [Cout][chunk8][nu*3+dy][8]
-  // (u0 = g0, u1 = ((g0+g2)+g1)/2, u2 = ((g0+g2)-g1)/2, u3 = g2; group 1) and its bf16 hi / mid planes (group 3)
-  if (L.ww_off >= 0 && (group == 0 || group == 1 || group == 3)) {
-    float* dw = base + L.ww_off;
-    uint16_t* dx3 = reinterpret_cast<uint16_t*>(base + L.wx_off);
-    float* d43 = base + L.w43_off;
-    const size_t nk8 = (size_t)ct / 8, nk16 = (size_t)ct / 16;
-    for (int dy = 0; dy < 3; ++dy)
-      for (size_t kc = 0; kc < nk8; ++kc) {
-        const float* rows[3][8];
-        for (int dx = 0; dx < 3; ++dx)
-          for (int j = 0; j < 8; ++j) {
-            const int ref = L.perm[kc * 8 + j];
-            rows[dx][j] = ref < 0 ? nullptr : src + ((size_t)(dy * 3 + dx) * L.cin + ref) * L.cout;
-          }
-        for (int co = co0; co < co1; ++co) {
-          float g[3][8];
-          for (int dx = 0; dx < 3; ++dx)
-            for (int j = 0; j < 8; ++j) g[dx][j] = rows[dx][j] ? rows[dx][j][co] : 0.f;
-          if (group == 0) {
-            float* d = d43 + ((((size_t)co * nk8 + kc) * 3 + dy) * 6) * 8;
-            for (int j = 0; j < 8; ++j) {
-              const float g0 = g[0][j], g1 = g[1][j], g2 = g[2][j];
-              const float e = g0 * (1.f / 24.f) + g2 * (1.f / 6.f), o = g1 * (1.f / 12.f);
-              d[0 * 8 + j] = g0 * 0.25f;
-              d[1 * 8 + j] = -((g0 + g2) + g1) * (1.f / 6.f);
-              d[2 * 8 + j] = -((g0 + g2) - g1) * (1.f / 6.f);
-              d[3 * 8 + j] = e + o;
-              d[4 * 8 + j] = e - o;
-              d[5 * 8 + j] = g2;
-            }
-            continue;
-          }
-          float u[4][8];
-          for (int j = 0; j < 8; ++j) {
-            const float g0 = g[0][j], g1 = g[1][j], g2 = g[2][j];
-            u[0][j] = g0; u[1][j] = ((g0 + g2) + g1) * 0.5f; u[2][j] = ((g0 + g2) - g1) * 0.5f; u[3][j] = g2;
-          }
-          for (int nu = 0; nu < 4; ++nu) {
-            if (group == 1) { memcpy(dw + (((size_t)co * nk8 + kc) * 12 + nu * 3 + dy) * 8, u[nu], sizeof(u[nu])); continue; }
-            // the same transformed weights as nearest bf16 hi / mid planes (nu = 2h + j)
-            uint16_t* d = dx3 + ((((size_t)co * nk16 + kc / 2) * 3 + dy) * 2 + (nu & 1)) * 64 + (nu >> 1) * 32 + (kc & 1) * 8;
-            for (int j = 0; j < 8; ++j) {
-              const uint16_t hb = bf16_rne(u[nu][j]);
-              d[j] = hb;
-              d[16 + j] = bf16_rne(u[nu][j] - bf16_to_float(hb));
-            }
-          }
-        }
-      }
-  }
-}
-
 // Packs layout groups [h->groups_packed, n) from the HWIO tensors (kept on the host) and uploads them.  Work items =
 // (layer, 32 output channels), pulled from an atomic counter by up to 32 threads: 137.7 MB of parameters into the
 // default group 0 in well under a second on the hosts this runs on (it took 7 s single-threaded for every layout).
@@ -454,14 +455,19 @@ int film_ensure_groups_(film_t* h, int n) {
     if (!h->host_w.count(L.name + "/kernel") || !h->host_w.count(L.name + "/bias")) return fail(h, FILM_ERR_STATE, "missing weight '%s'", L.name.c_str());
   const int64_t from = h->groups_packed ? h->group_end[h->groups_packed - 1] : 0, to = h->group_end[n - 1];
   h->packed_host.resize((size_t)to, 0.f);
-  struct Item { const LayerPack* L; int co0, co1; };
+  struct Item { const LayerPack* L; const float *kernel, *bias; int co0, co1; };
   std::vector<Item> items;
   for (const LayerPack& L : h->layers)
-    for (int co = 0; co < L.cout; co += 32) items.push_back({&L, co, std::min(L.cout, co + 32)});
+    for (int co = 0; co < L.cout; co += 32)
+      items.push_back({&L, h->host_w.at(L.name + "/kernel").data.data(), h->host_w.at(L.name + "/bias").data.data(), co, std::min(L.cout, co + 32)});
   for (int g = h->groups_packed; g < n; ++g) {
     std::atomic<size_t> next{0};
-    auto worker = [&]() {
-      for (size_t i; (i = next.fetch_add(1)) < items.size();) pack_layer_group(h, *items[i].L, g, items[i].co0, items[i].co1);
+    auto worker = [&]() {   // an item: every copy of group g that the layer has, for the item's output channels
+      for (size_t i; (i = next.fetch_add(1)) < items.size();) {
+        const Item& it = items[i];
+        for (const WeightLayout& r : kLayouts)
+          if (r.group == g && r.on(*it.L)) r.fill(*it.L, it.kernel, it.bias, h->packed_host.data() + it.L->*r.off, it.co0, it.co1);
+      }
     };
     const unsigned nth = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
     std::vector<std::thread> pool;
@@ -477,9 +483,10 @@ int film_ensure_groups_(film_t* h, int n) {
 // layout groups the current options need at once (the planner asks for more when a plan needs them)
 static int groups_for_options(const film_t* h) {
   int n = 1;
-  if (h->opt_wino == 2) n = std::max(n, 2);
-  if (h->opt_wino == 0 || h->opt_halo_all) n = std::max(n, 3);
-  if (h->opt_precision) n = 4;
+  auto runs = [&](ConvFamily f) { n = std::max(n, layout_groups(kConvFamily[f].weights)); };
+  if (h->opt_wino == 2) runs(FAM_WINO);
+  if (h->opt_wino == 0 || h->opt_halo_all) runs(FAM_HALO);
+  if (h->opt_precision) runs(FAM_SPLIT6);
   return n;
 }
 
@@ -615,6 +622,5 @@ int film_export_layouts(film_t* h, float* dst, int64_t cap, int64_t* n) {
   memcpy(dst, h->packed_host.data(), (size_t)h->packed_floats * sizeof(float));
   return FILM_OK;
 }
-
 
 }  // extern "C"

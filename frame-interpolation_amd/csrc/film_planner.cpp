@@ -251,7 +251,7 @@ struct Planner {
   void set_family(OpDesc& op, ConvFamily fam, int64_t M) {
     if (!conv_family_built(fam)) fam = FAM_BUF;
     op.family = fam;
-    need_groups(kConvFamily[fam].groups);
+    need_groups(layout_groups(kConvFamily[fam].weights));
     op.tile = conv_default_tile(fam, op.Cout, M);
   }
 

@@ -219,8 +219,8 @@ int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* bu
  *                  (2-16 partial sums over K ranges, added in split order by a second kernel: deterministic, and the
  *                  factor depends on the level size and the layer only, never on the batch); it is what bounds the
  *                  latency of small frames.  Changing it drops the cached plans.
- *   "pack_groups" n  pack (and upload) the weight layout groups 1..n now: 1 default fp32 layouts, 2 + F(2,3) copy, 3 + halo
- *                  copy, 4 + bf16 split copies (normally packed on demand)
+ *   "pack_groups" n  pack (and upload) the first n of the four weight layout groups now (normally packed on demand; the groups:
+ *                  kLayouts in csrc/film_layers.cpp)
  *   "fuse"    bits 31 (default): small-launch fusion, identical arithmetic and bit-identical results.  1: tf.image.resize(2 * v)
  *                  of the flow estimator inside the warp kernels that consume it; 2: v = residual + upsampled flow inside
  *                  the flow-head kernels; 4: the warped images and the half flows of the t = 0.5 stage (the sixteen miscellaneous

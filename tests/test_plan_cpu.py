@@ -123,6 +123,71 @@ def test_packing_permutes_fusion_inputs(tiny_weights):
     assert np.array_equal(packed[:, :, 2 * C + 16:], ref[:, :, 10 + 2 * C:])           # net
 
 
+def _closed_form_weights(opt):
+    """Weights that depend on nothing but the layer index and the element index (no numpy generator: the digests below must not
+    depend on numpy's version): a 32-bit integer hash of i mapped to [-0.5, 0.5) for the kernels, (j * 97 + li) % 251 / 251 for the biases."""
+    from film_hip import weights as W
+    u = np.uint64
+    out = {}
+    for li, (name, shape, _) in enumerate(W.weight_specs(opt)):
+        x = (np.arange(int(np.prod(shape)), dtype=u) * u(2654435761) + u(li * 40503 + 12345)) & u(0xFFFFFFFF)
+        x ^= x >> u(15)
+        x = (x * u(2246822519)) & u(0xFFFFFFFF)
+        x ^= x >> u(13)
+        out[name + '/kernel'] = ((x >> u(8)).astype(np.float32) / np.float32(2 ** 24) - np.float32(0.5)).reshape(shape)
+        out[name + '/bias'] = ((np.arange(shape[3], dtype=u) * u(97) + u(li)) % u(251)).astype(np.float32) / np.float32(251)
+    return out
+
+
+# floats of the layout blob after film_finalize and after "pack_groups" 2, 3, 4, and the sha256 of those four prefixes of the final blob,
+# of the closed-form weights above: recorded from the library as it was before the packer was rewritten around its layout table
+LAYOUT_DIGESTS = {
+    'TINY': ((6161280, 7482240, 8472960, 11565696),
+             ('ec357b384e8ccd3383502d724d12540719c85427c2ee4e6ad456b6e2323353fa', '66b24469742878839ff49d804a29f10cf6e58655d30de18308b88389b5dd84ce',
+              '50f244bb08b7420aad31cf76efdb8d0f08346a4d112a3eb37fc013c59f0a7b04', '3f547d10bb560fda8db85b10acf733a4b4ccd898246e95b9cacbf416ac866a48')),
+    'TINY96': ((37900800, 45697536, 51545088, 70629120),
+               ('3e25d35a22cf1fea3b510c083ed70a646b0dff665dbc5c24680e5b94b95e4c3c', '6fa64bd992256fb539538e3a1168ccf1b8cac58d71491b38bd2116be52be000b',
+                '8abcee031cc293a0a95e9e1229999623cd964125e17aa82fc58f0714a796a704', 'a5de480072c369ba1643b904f1a16218458d4173cd2a75c78d462837e5de38a9')),
+    'PUBLISHED': ((188669444, 228396548, 258191876, 353081348),
+                  ('eaf751e936eab4b0b5a48f5fb23a8cf38358b8b1b5846b61390174d249e405cf', '0cb449cd6ca37aea70c53c81c9e5dcd41c1298b68064695ba6eca26236eea479',
+                   '43afa0527dc44152aeadf519f80314de8de5979655928ca4467469e661043b0d', '1f9b7e0a7486795676c8296f9d47e66a2c5b65be35ceec064f7490dcede2fd5b')),
+}
+
+
+@pytest.mark.parametrize('cfg', sorted(LAYOUT_DIGESTS))
+def test_layout_blob_is_byte_for_byte_what_it_was(cfg):
+    """Every weight layout of every group, at its offset, bit for bit: offsets are an external format (plan JSON, plan_interp.py) and a wrong
+    float in a layout shows far from its cause.  TINY, TINY with 96 filters and the published net between them reach every layout: first
+    layer, 1x1 heads, permuted fusion inputs with zero rows, 2x2 layers with and without the difference-form copy, 3x3 layers of 32 / 96 /
+    64..512 channels."""
+    import dataclasses
+    import hashlib
+    from film_hip import options as O
+    from film_hip.engine import FilmEngine
+    opt = dataclasses.replace(O.TINY, filters=96) if cfg == 'TINY96' else getattr(O, cfg)
+    eng = FilmEngine(opt, device=-1)
+    eng.set_weights(_closed_form_weights(opt))
+
+    def packed_floats():
+        n = ctypes.c_int64()
+        eng._check(eng._lib.film_export_layouts(eng._h, None, 0, ctypes.byref(n)))
+        return n.value
+    sizes = [packed_floats()]
+    for g in (2, 3, 4):
+        eng.set_option('pack_groups', g)
+        sizes.append(packed_floats())
+    blob = eng.export_layouts()
+    eng.close()
+    assert blob.size == sizes[3]
+    view, sha, digests, at = memoryview(blob).cast('B'), hashlib.sha256(), [], 0
+    for n in sizes:
+        sha.update(view[4 * at:4 * n])
+        digests.append(sha.copy().hexdigest())
+        at = n
+    print(cfg, sizes, digests)
+    assert (tuple(sizes), tuple(digests)) == LAYOUT_DIGESTS[cfg]
+
+
 @pytest.mark.parametrize('b,h,w', [(1, 32, 32), (2, 32, 48), (1, 64, 40)])
 def test_plan_interpreter_matches_oracle_tiny(tiny_weights, b, h, w):
     from film_hip import weights as W
