@@ -1,8 +1,8 @@
 // conv_buf_impl.h -- implicit-GEMM convolution, register-staged, with the leanest K loop we could build.
 //
-// Same mapping as tools/retired/conv_igemm_impl.h (M = output pixels, N = Cout, K walked in 16-channel steps over
+// Same mapping as round 1's conv_igemm_kernel, which left the tree in round 5 (M = output pixels, N = Cout, K walked in 16-channel steps over
 // (tap, concat segment, chunk); fp32 v_mfma_f32_32x32x2_f32; bias + leaky_relu epilogue).  Measured on MI355X
-// (tools/retired/conv_bench.hip + rocprofv3 PMC): every non-MFMA vector instruction issued inside the K loop costs
+// (conv_bench.hip, gone since round 5, + rocprofv3 PMC; profiles/HISTORY.md 4.1): every non-MFMA vector instruction issued inside the K loop costs
 // matrix-pipe time that the co-resident waves do not win back, while the memory system is nowhere near a limit
 // (gathers from one pixel run exactly as fast).  So this kernel spends no VALU instruction per K-step:
 //
@@ -19,44 +19,7 @@
 //   * two register stages + two LDS stages: the loads of step s+2 are issued before the MFMAs of step s, the
 //     registers of step s+1 go to LDS after them, one barrier per step.
 #pragma once
-#include <atomic>
-#include <type_traits>
-#include <utility>
-
-#include "film_kernels.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float bf4 __attribute__((ext_vector_type(4)));
-typedef int bi4 __attribute__((ext_vector_type(4)));
-
-enum : int {
-  CONV_B_XCD_M = 4,  // XCD-contiguous block mapping (each XCD walks a contiguous range of M tiles)
-};
-
-// raw buffer resource over [p, p + 4 GiB): stride 0, num_records = 0xFFFFFFFF bytes, gfx9 dword3 for raw
-// 32-bit access.  A lane whose offset is 0xFFFFFFFF fails the bounds check and loads zeros.
-typedef __amdgpu_buffer_rsrc_t conv_rsrc_t;
-__device__ __forceinline__ conv_rsrc_t conv_make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, -1, 0x00020000);
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the function ON the current device and is idempotent: set on the first launch
-// per (kernel instantiation, device).  The "already set" flags are atomics (relaxed is enough: a second thread that misses the flag
-// only repeats the call) - several handles on several host threads may launch the same instantiation (include/film_hip.h).
-struct ConvLdsAttrFlags { std::atomic<bool> set[64]; };
-inline hipError_t conv_allow_dynamic_lds(const void* kern, ConvLdsAttrFlags& flags, int bytes) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const bool tracked = dev >= 0 && dev < 64;
-  if (tracked && flags.set[dev].load(std::memory_order_relaxed)) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess && tracked) flags.set[dev].store(true, std::memory_order_relaxed);
-  return e;
-}
-
-__device__ __forceinline__ bf4 conv_buf_load(conv_rsrc_t rsrc, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(bf4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0));
-}
+#include "conv_common.h"
 
 template <int BM, int BN, int WGM, int WGN, int FLAGS>
 __global__ __launch_bounds__(WGM* WGN * 64) void conv_buf_kernel(ConvParams p) {
@@ -79,17 +42,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_buf_kernel(ConvParams p) {
   const int wm = wv / WGN, wn = wv % WGN;
 
   int bx = blockIdx.x, by = blockIdx.y;
-  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) {
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int nwg = nbx * nby;
-    const int lin = by * nbx + bx;
-    const int xcd = lin & 7, idx = lin >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int nl = base + idx;
-    bx = nl / nby;
-    by = nl - bx * nby;
-  }
+  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) conv_xcd_remap(bx, by);
   const int m0 = bx * BM;
   const int n0 = by * BN;
 
@@ -261,7 +214,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_buf_kernel(ConvParams p) {
             acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[kq][nt][j], a[kq][mt][j], acc[mt][nt], 0, 0, 0);   // A = weights: C^T, the same sums
   };
 
-  // ---- two-step prefetch pipeline (see tools/retired/conv_igemm_impl.h for the reasoning behind the shape of this loop) --
+  // ---- two-step prefetch pipeline (profiles/HISTORY.md 4.1 has the reasoning behind the shape of this loop) --
   setup_seg();
   setup_tap();
   load_global(sx);  // step 0
@@ -310,7 +263,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_buf_kernel(ConvParams p) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           float u = v[c] + p.bias[n + c];
-          if (p.leaky) u = u > 0.f ? u : 0.2f * u;
+          if (p.leaky) u = leaky02(u);
           v[c] = u;
         }
         *reinterpret_cast<bf4*>(p.out + opix * p.ostride + n) = v;
@@ -321,14 +274,8 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_buf_kernel(ConvParams p) {
 template <int BM, int BN, int WGM, int WGN, int FLAGS>
 hipError_t conv_buf_launch(const ConvParams& p, hipStream_t s) {
   constexpr size_t lds = 2 * (size_t)(BM + BN) * 16 * sizeof(float);
-  auto kern = conv_buf_kernel<BM, BN, WGM, WGN, FLAGS>;
-  if constexpr (lds > 64 * 1024) {
-    static ConvLdsAttrFlags attr_flags;   // one per kernel instantiation (this launcher is a template)
-    if (const hipError_t e = conv_allow_dynamic_lds(reinterpret_cast<const void*>(kern), attr_flags, (int)lds); e != hipSuccess) return e;
-  }
   if (p.ksplit > 1 && p.fold) return hipErrorInvalidValue;
   if (p.ksplit > 1 ? (p.Cout % 4 || (reinterpret_cast<uintptr_t>(p.part) & 15)) : (p.ostride % 4 || (reinterpret_cast<uintptr_t>(p.out) & 15))) return hipErrorInvalidValue;   // dwordx4 stores
   dim3 grid((p.M + BM - 1) / BM, p.Cout / BN, p.fold == 2 ? 4 : (p.ksplit > 1 ? p.ksplit : 1));
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, p);
-  return hipGetLastError();
+  return conv_launch<conv_buf_kernel<BM, BN, WGM, WGN, FLAGS>>(grid, dim3(WGM * WGN * 64), lds, s, p);
 }

@@ -16,7 +16,7 @@
 // k ascends (tap, channel) in one fma chain per output, like the kernel it replaces.  COUT = the 64 or 32 output channels of a
 // workgroup; blockIdx.z walks the channel blocks of a wider first layer (filters = 96, 128, ...: any multiple of 32).
 #pragma once
-#include "conv_buf_impl.h"
+#include "conv_common.h"
 
 template <int COUT, int ROWS>
 __global__ __launch_bounds__(256) void conv_c3_kernel(ConvParams p) {
@@ -116,6 +116,5 @@ hipError_t conv_c3_launch(const ConvParams& p, hipStream_t s) {
   constexpr int ROWS = 8;
   if (p.nseg != 1 || p.ksize != 3 || p.Cout % COUT || p.seg[0].C != 3 || p.ksplit > 1) return hipErrorInvalidValue;
   const int ntx = (p.W + 127) / 128, nty = (p.H + ROWS - 1) / ROWS;
-  hipLaunchKernelGGL((conv_c3_kernel<COUT, ROWS>), dim3((unsigned)(ntx * nty), (unsigned)p.NB, (unsigned)(p.Cout / COUT)), dim3(256), 0, s, p);
-  return hipGetLastError();
+  return conv_launch<conv_c3_kernel<COUT, ROWS>>(dim3((unsigned)(ntx * nty), (unsigned)p.NB, (unsigned)(p.Cout / COUT)), dim3(256), 0, s, p);
 }

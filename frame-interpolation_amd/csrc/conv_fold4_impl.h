@@ -27,12 +27,9 @@
 //
 // Needs one input segment with C % 16 == 0 (16-byte aligned pixels), Cout % (32 NCT) == 0, a 16-byte aligned output slice.
 #pragma once
-#include "conv_buf_impl.h"
+#include "conv_common.h"
 
 enum { F4_DBG_TIME = 8192 };   // tools only: wave 0 of every workgroup stamps s_memtime like W2D_DBG_TIME (p.part[workgroup * 16 ..])
-
-template <class F, int... G>
-__device__ __forceinline__ void f4_for_each(F&& f, std::integer_sequence<int, G...>) { (f(std::integral_constant<int, G>{}), ...); }
 
 template <int NCT, int FLAGS>
 __global__ __launch_bounds__(256, 2) void conv_fold4_kernel(ConvParams p) {
@@ -74,12 +71,6 @@ __global__ __launch_bounds__(256, 2) void conv_fold4_kernel(ConvParams p) {
     aS0ptr = reinterpret_cast<const float*>((uintptr_t)q0);
     aWptr = reinterpret_cast<const float*>((uintptr_t)q1);
   }
-  auto udiv = [](unsigned x, unsigned magic) -> unsigned {   // x / d by the launcher's reciprocal; magic = 0: d = 1
-    unsigned q;
-    const unsigned h = __umulhi(x, magic);
-    asm("s_cmp_eq_u32 %2, 0\n\ts_cselect_b32 %0, %1, %3" : "=s"(q) : "s"(x), "s"(magic), "s"(h) : "scc");
-    return q;
-  };
   int bx = blockIdx.x, by = blockIdx.y;
   if constexpr ((FLAGS & CONV_B_XCD_M) != 0) {
     const int nbx = aGx, nby = aGy;
@@ -89,26 +80,21 @@ __global__ __launch_bounds__(256, 2) void conv_fold4_kernel(ConvParams p) {
     const int q = nwg >> 3, r = nwg & 7;
     const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     const int nl = base + idx;
-    bx = (int)udiv((unsigned)nl, a_nby);
+    bx = (int)conv_udiv((unsigned)nl, a_nby);
     by = nl - bx * nby;
   }
   const int ntx = ntx_;
-  const int img = (int)udiv((unsigned)bx, a_tpi);
+  const int img = (int)conv_udiv((unsigned)bx, a_tpi);
   const int trem = bx - img * tpi_;
-  const int trow = (int)udiv((unsigned)trem, a_ntx);
+  const int trow = (int)conv_udiv((unsigned)trem, a_ntx);
   const int y0 = trow * TH, x0 = (trem - trow * ntx) * PXW;
   const int n0 = by * BN;
 
-  auto uniform_ptr = [](const float* q) -> const float* {
-    const unsigned long long v = (unsigned long long)(uintptr_t)q;
-    return reinterpret_cast<const float*>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-                                                        (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v)));
-  };
   // ---- DMA side: request n of this wave fills slots 64 * (wv + NW n) ... + 63 of a stage; lane -> (halo row, pixel, piece) -----
   int be = img + aS0boff;
   if (aS0bmod && be >= aS0bmod) be -= aS0bmod;
   const int spix = (be * aH + y0) * aW;   // (a launch has fewer than 2^31 pixels: the launcher checks)
-  const conv_rsrc_t rrsrc = conv_make_rsrc(uniform_ptr(aS0ptr + (long long)spix * aS0stride));
+  const conv_rsrc_t rrsrc = conv_make_rsrc(conv_uniform_ptr(aS0ptr + (long long)spix * aS0stride));
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float*)smem;
   unsigned rvoff[IPW];
   {
@@ -145,7 +131,7 @@ __global__ __launch_bounds__(256, 2) void conv_fold4_kernel(ConvParams p) {
 
   // ---- weights: [Cout / 32][chunk][plane 4][K half][32][4] floats; every wave of the workgroup reads the slabs of the NCT tiles -----
   const int nkc = aCtot / 8, nsc = sc1 - sc0, kc0 = 2 * sc0, kc1 = 2 * sc1;
-  const conv_rsrc_t brsrc = conv_make_rsrc(uniform_ptr(aWptr));
+  const conv_rsrc_t brsrc = conv_make_rsrc(conv_uniform_ptr(aWptr));
   const unsigned bvoff = (unsigned)((half * 32 + l31) * 16);
   const unsigned tstep = (unsigned)nkc * 4096u;   // bytes between two 32-channel tiles
   auto slab = [&](int kc) { return (unsigned)(by * NCT * nkc + (kc < nkc ? kc : nkc - 1)) * 4096u; };
@@ -253,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void conv_fold4_kernel(ConvParams p) {
       }
       __builtin_amdgcn_sched_barrier(0);
     };
-    f4_for_each(gap, std::make_integer_sequence<int, NG>{});
+    conv_for_each(gap, std::make_integer_sequence<int, NG>{});
     if constexpr (H == 1) {
       st_s = st_n;
       st_n = st_n + 1 == NS ? 0 : st_n + 1;
@@ -383,16 +369,10 @@ hipError_t conv_fold4_launch(const ConvParams& p, hipStream_t s) {
   dim3 grid((unsigned)(p.NB * ntx * nty), p.Cout / BN, (unsigned)(p.ksplit > 1 ? p.ksplit : 1));
   ConvParams q = p;   // + the reciprocals of the workgroup decomposition (conv_wino2d_launch's): ceil(2^32 / d), exact for x d < 2^32; 0 = the divisor is 1
   bool exact = true;
-  auto magic = [&exact](unsigned long long d, unsigned long long xmax) -> unsigned {
-    if (d <= 1) return 0u;
-    if (xmax * d >= (1ull << 32)) { exact = false; return 0u; }
-    return (unsigned)(((1ull << 32) + d - 1) / d);
-  };
-  q.mg_nby = magic(grid.y, (unsigned long long)grid.x * grid.y);
-  q.mg_tpi = magic((unsigned long long)ntx * nty, (unsigned long long)grid.x + 1);
-  q.mg_ntx = magic(ntx, (unsigned long long)ntx * nty);
+  q.mg_nby = conv_magic(grid.y, (unsigned long long)grid.x * grid.y, exact);
+  q.mg_tpi = conv_magic((unsigned long long)ntx * nty, (unsigned long long)grid.x + 1, exact);
+  q.mg_ntx = conv_magic(ntx, (unsigned long long)ntx * nty, exact);
   q.tl_ntx = ntx; q.tl_tpi = ntx * nty;
   if (!exact) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((conv_fold4_kernel<NCT, FLAGS>), grid, dim3(256), lds, s, q);
-  return hipGetLastError();
+  return conv_launch<conv_fold4_kernel<NCT, FLAGS>>(grid, dim3(256), lds, s, q);
 }

@@ -45,17 +45,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, WGM* WGN <= 4 ? 2 : 1) void conv_fol
   const int wm = wv / WGN, wn = wv % WGN;
 
   int bx = blockIdx.x, by = blockIdx.y;
-  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) {
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int nwg = nbx * nby;
-    const int lin = by * nbx + bx;
-    const int xcd = lin & 7, idx = lin >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int nl = base + idx;
-    bx = nl / nby;
-    by = nl - bx * nby;
-  }
+  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) conv_xcd_remap(bx, by);
   const int ntx = (p.W + 31) >> 5, nty = (p.H + TH - 1) / TH;   // p.H, p.W: the low-resolution grid
   const int img = bx / (ntx * nty);
   const int trem = bx - img * (ntx * nty);
@@ -196,9 +186,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, WGM* WGN <= 4 ? 2 : 1) void conv_fol
           for (int nt = 0; nt < TN; ++nt)
             acc[Q][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[SLOT][PA[k]][mt], b[PB[k]][nt], acc[Q][mt][nt], 0, 0, 0);
     };
-    step(std::integral_constant<int, 0>{});
-    step(std::integral_constant<int, 1>{});
-    step(std::integral_constant<int, 2>{});
+    conv_for_each(step, std::make_integer_sequence<int, 3>{});
   };
 
   // ---- pipeline: three stages per chunk, one barrier each; the weights of stage s+2 are requested in front of the
@@ -225,9 +213,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, WGM* WGN <= 4 ? 2 : 1) void conv_fol
       if constexpr (ST == 1) store_a(a_stage ^ 1);
       __syncthreads();
     };
-    stage(std::integral_constant<int, 0>{});
-    stage(std::integral_constant<int, 1>{});
-    stage(std::integral_constant<int, 2>{});
+    conv_for_each(stage, std::make_integer_sequence<int, 3>{});
     a_stage ^= 1;
     a_stage_u = a_stage * (A_STAGE / 16);
   }
@@ -251,7 +237,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, WGM* WGN <= 4 ? 2 : 1) void conv_fol
           const int x = x0 + (r & 3) + 8 * (r >> 2) + 4 * half;
           if (x < p.W) {
             float v = acc[q][mt][nt][r] + bv;
-            if (p.leaky) v = v > 0.f ? v : 0.2f * v;
+            if (p.leaky) v = leaky02(v);
             p.out[(rowbase + 2 * x + (q & 1)) * p.ostride + n] = v;
           }
         }
@@ -264,14 +250,8 @@ template <int TH, int BN, int WGM, int WGN, int FLAGS>
 hipError_t conv_foldx3_launch(const ConvParams& p, hipStream_t s) {
   constexpr size_t lds = 2 * 2 * (size_t)(TH + 1) * 33 * 32 + 3 * 3 * 2 * (size_t)BN * 32;
   static_assert(lds <= 160 * 1024, "LDS");
-  auto kern = conv_foldx3_kernel<TH, BN, WGM, WGN, FLAGS>;
-  if constexpr (lds > 64 * 1024) {
-    static ConvLdsAttrFlags attr_flags;   // one per kernel instantiation (this launcher is a template)
-    if (const hipError_t e = conv_allow_dynamic_lds(reinterpret_cast<const void*>(kern), attr_flags, (int)lds); e != hipSuccess) return e;
-  }
   if (p.nseg != 1 || p.seg[0].up) return hipErrorInvalidValue;
   const int ntx = (p.W + 31) / 32, nty = (p.H + TH - 1) / TH;
   dim3 grid((unsigned)(p.NB * ntx * nty), p.Cout / BN);
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, p);
-  return hipGetLastError();
+  return conv_launch<conv_foldx3_kernel<TH, BN, WGM, WGN, FLAGS>>(grid, dim3(WGM * WGN * 64), lds, s, p);
 }

@@ -18,7 +18,7 @@
 //     in, masked stores on the way out.
 //   * segments with nearest-upsampled input (the 2x2 convs) and kernel sizes other than 3 stay on conv_buf_kernel.
 #pragma once
-#include "conv_buf_impl.h"
+#include "conv_common.h"
 
 template <int TH, int BN, int WGM, int WGN, int FLAGS>
 __global__ __launch_bounds__(WGM* WGN * 64) void conv_halo_kernel(ConvParams p) {
@@ -45,17 +45,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_halo_kernel(ConvParams p) 
   const int wm = wv / WGN, wn = wv % WGN;
 
   int bx = blockIdx.x, by = blockIdx.y;
-  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) {
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int nwg = nbx * nby;
-    const int lin = by * nbx + bx;
-    const int xcd = lin & 7, idx = lin >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int nl = base + idx;
-    bx = nl / nby;
-    by = nl - bx * nby;
-  }
+  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) conv_xcd_remap(bx, by);
   const int ntx = (p.W + 31) >> 5, nty = (p.H + TH - 1) / TH;
   const int img = bx / (ntx * nty);
   const int trem = bx - img * (ntx * nty);
@@ -231,15 +221,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_halo_kernel(ConvParams p) 
       if constexpr (TAP == 8) store_a(a_off ? 0 : 1);
       __syncthreads();
     };
-    step(std::integral_constant<int, 0>{});
-    step(std::integral_constant<int, 1>{});
-    step(std::integral_constant<int, 2>{});
-    step(std::integral_constant<int, 3>{});
-    step(std::integral_constant<int, 4>{});
-    step(std::integral_constant<int, 5>{});
-    step(std::integral_constant<int, 6>{});
-    step(std::integral_constant<int, 7>{});
-    step(std::integral_constant<int, 8>{});
+    conv_for_each(step, std::make_integer_sequence<int, 9>{});
     next_chunk(kc + 2);
     a_off = a_off ? 0 : A_STAGE;
 #pragma unroll
@@ -262,7 +244,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_halo_kernel(ConvParams p) 
         const int x = x0 + (r & 3) + 8 * (r >> 2) + 4 * half;
         if (x < p.W) {
           float v = acc[mt][nt][r] + bv;
-          if (p.leaky) v = v > 0.f ? v : 0.2f * v;
+          if (p.leaky) v = leaky02(v);
           p.out[(rowbase + x) * p.ostride + n] = v;
         }
       }
@@ -273,13 +255,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_halo_kernel(ConvParams p) 
 template <int TH, int BN, int WGM, int WGN, int FLAGS>
 hipError_t conv_halo_launch(const ConvParams& p, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)(TH + 2) * 40 * 16 + 3 * (size_t)BN * 16) * sizeof(float);
-  auto kern = conv_halo_kernel<TH, BN, WGM, WGN, FLAGS>;
-  if constexpr (lds > 64 * 1024) {
-    static ConvLdsAttrFlags attr_flags;   // one per kernel instantiation (this launcher is a template)
-    if (const hipError_t e = conv_allow_dynamic_lds(reinterpret_cast<const void*>(kern), attr_flags, (int)lds); e != hipSuccess) return e;
-  }
   const int ntx = (p.W + 31) / 32, nty = (p.H + TH - 1) / TH;
   dim3 grid((unsigned)(p.NB * ntx * nty), p.Cout / BN);
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, p);
-  return hipGetLastError();
+  return conv_launch<conv_halo_kernel<TH, BN, WGM, WGN, FLAGS>>(grid, dim3(WGM * WGN * 64), lds, s, p);
 }

@@ -24,7 +24,7 @@
 //                      instead of the 9 of the sub-pixel fold on conv_buf_kernel.
 //   conv_c3_impl.h     the 3-channel first layer (K = 27): no LDS, weights in registers.
 // (conv_igemm_impl.h, the first-generation kernel that ran the first layer of configurations with filters other than 32 / 64 until
-// round 4, is under tools/retired/.)
+// round 4, left the tree in round 5.)
 // The default library instantiates only the families a default plan can select: conv_wino2d / conv_wino43 / conv_fold4 / conv_buf / conv_c3.
 // FILM_EXTRA_FAMILIES=1 at build time (film_hip/build.py, Makefile EXTRA=1) adds the ones behind opt-in options: the bf16 split
 // precision modes (conv_split / conv_winox3 / conv_foldx3) and the F(2,3) / halo fp32 kernels (options winograd = 2, halo_all).

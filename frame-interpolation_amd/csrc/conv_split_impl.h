@@ -8,7 +8,7 @@
 //                                                                         (worst case 2^-15; measured rms 4.4e-6, mean 1e-9: zero mean)
 // Six (three) bf16 MFMAs of 32 cycles replace eight fp32 MFMAs of 64 cycles per 16 K: 2.67x (5.3x) the matrix
 // rate.  bf16x6 is fp32-level accurate (max |delta| 2.8e-5 on outputs of O(10) against the fp32 kernels,
-// tools/retired/conv_bench.hip: the same as between two fp32 kernels that sum K in a different order); bf16x3 stages only
+// conv_bench.hip, which left the tree in round 5 - profiles/r01_conv_bench_split.log: the same as between two fp32 kernels that sum K in a different order); bf16x3 stages only
 // the hi and mid planes (2/3 of the LDS and of the split VALU work).  Measured speed of bf16x6: 1.45-1.65x - at
 // 68 % MFMA-pipe occupancy the bf16 matrix pipe is power limited (clock 1.9 GHz), like every dense bf16 GEMM on
 // this part.
@@ -21,7 +21,7 @@
 //     r+24 would collide otherwise); writes: 4 rows x 32 contiguous bytes per 16-lane ds_write_b64 group.  (The first
 //     version used 112-byte [row][plane] rows: conflict-free reads, but 20-29 % conflict cycles from the stores.)
 #pragma once
-#include "conv_buf_impl.h"
+#include "conv_common.h"
 
 typedef __bf16 sbf8 __attribute__((ext_vector_type(8)));
 typedef unsigned su4 __attribute__((ext_vector_type(4)));
@@ -102,17 +102,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_halo_split_kernel(ConvPara
   const int wm = wv / WGN, wn = wv % WGN;
 
   int bx = blockIdx.x, by = blockIdx.y;
-  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) {
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int nwg = nbx * nby;
-    const int lin = by * nbx + bx;
-    const int xcd = lin & 7, idx = lin >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int nl = base + idx;
-    bx = nl / nby;
-    by = nl - bx * nby;
-  }
+  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) conv_xcd_remap(bx, by);
   const int ntx = (p.W + 31) >> 5, nty = (p.H + TH - 1) / TH;
   const int img = bx / (ntx * nty);
   const int trem = bx - img * (ntx * nty);
@@ -280,15 +270,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_halo_split_kernel(ConvPara
       if constexpr (TAP == 8) store_a(a_stage ^ 1);
       __syncthreads();
     };
-    step(std::integral_constant<int, 0>{});
-    step(std::integral_constant<int, 1>{});
-    step(std::integral_constant<int, 2>{});
-    step(std::integral_constant<int, 3>{});
-    step(std::integral_constant<int, 4>{});
-    step(std::integral_constant<int, 5>{});
-    step(std::integral_constant<int, 6>{});
-    step(std::integral_constant<int, 7>{});
-    step(std::integral_constant<int, 8>{});
+    conv_for_each(step, std::make_integer_sequence<int, 9>{});
     next_chunk(kc + 2);
     a_stage ^= 1;
     a_stage_u = a_stage * (A_STAGE / 16);
@@ -308,7 +290,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_halo_split_kernel(ConvPara
         const int x = x0 + (r & 3) + 8 * (r >> 2) + 4 * half;
         if (x < p.W) {
           float v = acc[mt][nt][r] + bv;
-          if (p.leaky) v = v > 0.f ? v : 0.2f * v;
+          if (p.leaky) v = leaky02(v);
           p.out[(rowbase + x) * p.ostride + n] = v;
         }
       }
@@ -320,13 +302,7 @@ template <int TH, int BN, int WGM, int WGN, int NPROD, int FLAGS>
 hipError_t conv_halo_split_launch(const ConvParams& p, hipStream_t s) {
   constexpr size_t npl = NPROD > 3 ? 3 : 2;
   constexpr size_t lds = 2 * npl * (size_t)(TH + 2) * 34 * 32 + 3 * npl * (size_t)BN * 32;
-  auto kern = conv_halo_split_kernel<TH, BN, WGM, WGN, NPROD, FLAGS>;
-  if constexpr (lds > 64 * 1024) {
-    static ConvLdsAttrFlags attr_flags;   // one per kernel instantiation (this launcher is a template)
-    if (const hipError_t e = conv_allow_dynamic_lds(reinterpret_cast<const void*>(kern), attr_flags, (int)lds); e != hipSuccess) return e;
-  }
   const int ntx = (p.W + 31) / 32, nty = (p.H + TH - 1) / TH;
   dim3 grid((unsigned)(p.NB * ntx * nty), p.Cout / BN);
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, p);
-  return hipGetLastError();
+  return conv_launch<conv_halo_split_kernel<TH, BN, WGM, WGN, NPROD, FLAGS>>(grid, dim3(WGM * WGN * 64), lds, s, p);
 }

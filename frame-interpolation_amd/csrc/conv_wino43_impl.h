@@ -32,14 +32,14 @@
 //     (slot = dy), requested three stages ahead in registers; one barrier per dy stage = 3*4*TM*TN MFMAs per wave;
 //   * fragment registers triple buffered over the nu steps: the ds_reads of step s+1 are issued before the MFMAs of s.
 #pragma once
-#include "conv_buf_impl.h"
+#include "conv_common.h"
 
 enum { W43_F_PF2 = 32768,      // activation loads requested TWO chunks ahead (second register set): ~4 stages of load-to-use distance
        W43_F_BG = 65536 };     // weight fragments straight from global memory (L1 / L2) into registers, requested two stages
                                // ahead: no weight ring in LDS (36 KB instead of 54 KB for the 32-channel tile = FOUR workgroups
                                // per CU), no weight stores, two barriers per chunk instead of three
 // (Rounds 2-3 carried experiment flags here - wave priorities around the MFMA groups (-1..-3 %), persistent workgroups that request
-// the next pair's loads in front of the epilogue (no gain), timing ablations - driven by tools/retired/conv_bench.hip; their
+// the next pair's loads in front of the epilogue (no gain), timing ablations - driven by conv_bench.hip, which left the tree in round 5; their
 // measurements are in profiles/HISTORY.md 9 and profiles/r0[23]_*; the code went with round 4.)
 
 template <int TH, int BN, int TM, int TN, int FLAGS, int QW = 32, int NH = 2>
@@ -337,9 +337,7 @@ __global__ __launch_bounds__(((TH * QW / 32) / TM) * (BN / (32 * TN)) * 64 * NH,
       // first read (the fragment prefetch at the end of dy = 2)
       if constexpr (!BG || DY != 2) __syncthreads();
     };
-    stage(std::integral_constant<int, 0>{});
-    stage(std::integral_constant<int, 1>{});
-    stage(std::integral_constant<int, 2>{});
+    conv_for_each(stage, std::make_integer_sequence<int, 3>{});
     next_chunk(kc + (PF2 ? 3 : 2));
     a_stage ^= 1;
     a_cur = a_next;
@@ -409,7 +407,7 @@ __global__ __launch_bounds__(((TH * QW / 32) / TM) * (BN / (32 * TN)) * 64 * NH,
               continue;
             }
             v += bv;
-            if (p.leaky) v = v > 0.f ? v : 0.2f * v;
+            if (p.leaky) v = leaky02(v);
             val[r] = v;
             if (y < p.H && x < p.W) p.out[(((size_t)cimg * p.H + y) * p.W + x) * p.ostride + n] = v;
           }
@@ -468,7 +466,7 @@ __global__ __launch_bounds__(((TH * QW / 32) / TM) * (BN / (32 * TN)) * 64 * NH,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         o[j] += bv;
-        if (p.leaky) o[j] = o[j] > 0.f ? o[j] : 0.2f * o[j];
+        if (p.leaky) o[j] = leaky02(o[j]);
       }
       if (y < p.H) {
         const size_t rowbase = ((size_t)cimg * p.H + y) * p.W;
@@ -497,7 +495,7 @@ __global__ __launch_bounds__(((TH * QW / 32) / TM) * (BN / (32 * TN)) * 64 * NH,
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           float v = o[j] + bv;
-          if (p.leaky) v = v > 0.f ? v : 0.2f * v;
+          if (p.leaky) v = leaky02(v);
           tile[(pxl + j) * 65 + ng * 32 + l31] = v;
         }
       }
@@ -552,13 +550,7 @@ hipError_t conv_wino43_launch(const ConvParams& p, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)(TH + 2) * 6 * QW * 8 + ((FLAGS & W43_F_BG) != 0 ? 0 : 3 * 6 * (size_t)BN * 8)) * sizeof(float);
   constexpr int NT = ((TH * QW / 32) / TM) * (BN / (32 * TN)) * 64 * NH;
   static_assert(lds <= 160 * 1024, "LDS");
-  auto kern = conv_wino43_kernel<TH, BN, TM, TN, FLAGS, QW, NH>;
-  if constexpr (lds > 64 * 1024) {
-    static ConvLdsAttrFlags attr_flags;   // one per kernel instantiation (this launcher is a template)
-    if (const hipError_t e = conv_allow_dynamic_lds(reinterpret_cast<const void*>(kern), attr_flags, (int)lds); e != hipSuccess) return e;
-  }
   const int ntx = (p.W + 4 * QW - 1) / (4 * QW), nty = (p.H + TH - 1) / TH;
   dim3 grid((unsigned)(p.NB * ntx * nty), p.Cout / BN, (unsigned)(p.ksplit > 1 ? p.ksplit : 1));
-  hipLaunchKernelGGL(kern, grid, dim3(NT), lds, s, p);
-  return hipGetLastError();
+  return conv_launch<conv_wino43_kernel<TH, BN, TM, TN, FLAGS, QW, NH>>(grid, dim3(NT), lds, s, p);
 }

@@ -12,14 +12,14 @@
 //   * a workgroup owns TH rows x 64 pixels (32 pairs = one 32-row MFMA tile per row) x BN output channels;
 //   * K chunks of EIGHT channels: the (TH+2) halo rows of a chunk are transformed ONCE on the way into LDS, image
 //     [halo row][nu][pair][8 channels] = 32-byte rows whose two 16-byte K-halves are swapped when bit 3 of the row is
-//     set (conflict-free ds_read_b128 / ds_write_b128).  With 16-channel chunks (tools/experiments/
-//     conv_wino16_impl.h) the image is 48 KB per stage and only ONE 8-wave workgroup fits a CU; with 8 it is 24 KB and
+//     set (conflict-free ds_read_b128 / ds_write_b128).  With 16-channel chunks (conv_wino16_impl.h, an
+//     experiment that left the tree in round 2) the image is 48 KB per stage and only ONE 8-wave workgroup fits a CU; with 8 it is 24 KB and
 //     two fit (4 waves per SIMD): +3...14 % (166-192 vs 146-179 TFLOP/s in direct-conv FLOPs);
 //   * weights [Cout][chunk][nu*3 + dy][8]; a B stage holds the six (nu, dy) steps of two nu planes, double buffered:
 //     one barrier per 6 x 4 MFMAs per wave;
 //   * accumulators: 4 (nu) x TN tiles per output row; the output transform runs on them in the epilogue.
 #pragma once
-#include "conv_buf_impl.h"
+#include "conv_common.h"
 
 template <int TH, int BN, int WGM, int WGN, int FLAGS>
 __global__ __launch_bounds__(WGM* WGN * 64) void conv_wino_kernel(ConvParams p) {
@@ -46,17 +46,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_wino_kernel(ConvParams p) 
   const int wm = wv / WGN, wn = wv % WGN;
 
   int bx = blockIdx.x, by = blockIdx.y;
-  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) {
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int nwg = nbx * nby;
-    const int lin = by * nbx + bx;
-    const int xcd = lin & 7, idx = lin >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int nl = base + idx;
-    bx = nl / nby;
-    by = nl - bx * nby;
-  }
+  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) conv_xcd_remap(bx, by);
   const int ntx = (p.W + 63) >> 6, nty = (p.H + TH - 1) / TH;
   const int img = bx / (ntx * nty);
   const int trem = bx - img * (ntx * nty);
@@ -244,7 +234,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_wino_kernel(ConvParams p) 
         const float m0 = acc[mt][0][nt][r], m1 = acc[mt][1][nt][r], m2 = acc[mt][2][nt][r], m3 = acc[mt][3][nt][r];
         float e = (m0 + m1) + m2 + bv;
         float o = (m1 - m2) - m3 + bv;
-        if (p.leaky) { e = e > 0.f ? e : 0.2f * e; o = o > 0.f ? o : 0.2f * o; }
+        if (p.leaky) { e = leaky02(e); o = leaky02(o); }
         if (x < p.W) p.out[(rowbase + x) * p.ostride + n] = e;
         if (x + 1 < p.W) p.out[(rowbase + x + 1) * p.ostride + n] = o;
       }
@@ -255,13 +245,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_wino_kernel(ConvParams p) 
 template <int TH, int BN, int WGM, int WGN, int FLAGS>
 hipError_t conv_wino_launch(const ConvParams& p, hipStream_t s) {
   constexpr size_t lds = (2 * (size_t)(TH + 2) * 4 * 32 * 8 + 2 * 6 * (size_t)BN * 8) * sizeof(float);
-  auto kern = conv_wino_kernel<TH, BN, WGM, WGN, FLAGS>;
-  if constexpr (lds > 64 * 1024) {
-    static ConvLdsAttrFlags attr_flags;   // one per kernel instantiation (this launcher is a template)
-    if (const hipError_t e = conv_allow_dynamic_lds(reinterpret_cast<const void*>(kern), attr_flags, (int)lds); e != hipSuccess) return e;
-  }
   const int ntx = (p.W + 63) / 64, nty = (p.H + TH - 1) / TH;
   dim3 grid((unsigned)(p.NB * ntx * nty), p.Cout / BN);
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, p);
-  return hipGetLastError();
+  return conv_launch<conv_wino_kernel<TH, BN, WGM, WGN, FLAGS>>(grid, dim3(WGM * WGN * 64), lds, s, p);
 }

@@ -49,17 +49,7 @@ __global__ __launch_bounds__((TH / TM) * (BN / (32 * TN)) * 128) void conv_winox
   const int rg = pw / NG, ng = pw % NG;
 
   int bx = blockIdx.x, by = blockIdx.y;
-  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) {
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int nwg = nbx * nby;
-    const int lin = by * nbx + bx;
-    const int xcd = lin & 7, idx = lin >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int nl = base + idx;
-    bx = nl / nby;
-    by = nl - bx * nby;
-  }
+  if constexpr ((FLAGS & CONV_B_XCD_M) != 0) conv_xcd_remap(bx, by);
   const int ntx = (p.W + 63) >> 6, nty = (p.H + TH - 1) / TH;
   const int img = bx / (ntx * nty);
   const int trem = bx - img * (ntx * nty);
@@ -222,43 +212,26 @@ __global__ __launch_bounds__((TH / TM) * (BN / (32 * TN)) * 128) void conv_winox
   next_chunk(1);
   __syncthreads();
   fetch(std::integral_constant<int, 0>{}, a_cur);
-  if constexpr ((FLAGS & 64) != 0) fetch(std::integral_constant<int, 1>{}, a_cur);
   int a_stage = 0;
   for (int kc = 0; kc < nkc; ++kc) {
     const int s0 = kc * 6;
     const int a_next = a_ad + (a_stage ^ 1) * (A_STAGE / 16);
     auto stage = [&](auto st_c) {
       constexpr int ST = decltype(st_c)::value;
-      // FLAGS 64 / 128 / 256 / 512: timing ablations of tools/retired/conv_bench.hip (no fragment reads / no A item staging /
-      // no weight staging / no barriers) - wrong results, never instantiated by the engine
-      if constexpr ((FLAGS & 256) == 0) load_b(s0 + ST + 3, (ST + 1) & 1);
-      if constexpr ((FLAGS & 128) == 0) if constexpr ((ST & 1) == 0 && ST / 2 < AH) load_item(ST / 2);
-      if constexpr ((FLAGS & 64) == 0) fetch(std::integral_constant<int, (ST + 1) % 6>{}, ST == 5 ? a_next : a_cur);
+      load_b(s0 + ST + 3, (ST + 1) & 1);
+      if constexpr ((ST & 1) == 0 && ST / 2 < AH) load_item(ST / 2);
+      fetch(std::integral_constant<int, (ST + 1) % 6>{}, ST == 5 ? a_next : a_cur);
       __builtin_amdgcn_sched_barrier(0);
       compute(st_c);
       // The item's transform + split VALU work is left to the compiler's own placement: forced into an even
-      // interleave with the MFMAs (sched_group_barrier, one MFMA + 6 VALU) the kernel is 8 % slower.
-      if constexpr ((FLAGS & 1024) != 0) __builtin_amdgcn_sched_barrier(0);   // A/B: VALU strictly behind the MFMAs
-      if constexpr ((FLAGS & 128) == 0 && (ST & 1) == 1 && ST / 2 < AH) {
-        store_item(ST / 2, a_stage ^ 1);
-        if constexpr ((FLAGS & 2048) != 0) {   // A/B: forced even interleave
-#pragma unroll
-          for (int g = 0; g < 3 * TM * TN; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 64 / (3 * TM * TN) + 1, 0);
-          }
-        }
-      }
+      // interleave with the MFMAs (sched_group_barrier, one MFMA + 6 VALU) the kernel is 8 % slower.  (The flags of that A/B and of the
+      // timing ablations - no fragment reads / A item staging / weight staging / barriers - went with conv_bench.hip in round 5.)
+      if constexpr ((ST & 1) == 1 && ST / 2 < AH) store_item(ST / 2, a_stage ^ 1);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr ((FLAGS & 256) == 0) store_b((ST + 2) % 3, ST & 1);
-      if constexpr ((FLAGS & 512) == 0) __syncthreads();
+      store_b((ST + 2) % 3, ST & 1);
+      __syncthreads();
     };
-    stage(std::integral_constant<int, 0>{});
-    stage(std::integral_constant<int, 1>{});
-    stage(std::integral_constant<int, 2>{});
-    stage(std::integral_constant<int, 3>{});
-    stage(std::integral_constant<int, 4>{});
-    stage(std::integral_constant<int, 5>{});
+    conv_for_each(stage, std::make_integer_sequence<int, 6>{});
     next_chunk(kc + 2);
     a_stage ^= 1;
     a_cur = a_next;
@@ -296,7 +269,7 @@ __global__ __launch_bounds__((TH / TM) * (BN / (32 * TN)) * 128) void conv_winox
           float v = H == 0 ? (acc[mt][0][nt][r] + acc[mt][1][nt][r]) + got      // (m0 + m1) + m2
                            : (got - acc[mt][0][nt][r]) - acc[mt][1][nt][r];     // (m1 - m2) - m3
           v += bv;
-          if (p.leaky) v = v > 0.f ? v : 0.2f * v;
+          if (p.leaky) v = leaky02(v);
           if (x < p.W) p.out[(rowbase + x) * p.ostride + n] = v;
         }
       }
@@ -311,13 +284,7 @@ hipError_t conv_winox3_launch(const ConvParams& p, hipStream_t s) {
   constexpr size_t lds = 2 * 2 * (size_t)(TH + 2) * 4 * 32 * 32 + 3 * 4 * (size_t)BN * 32;
   constexpr int NT = (TH / TM) * (BN / (32 * TN)) * 128;
   static_assert(lds <= 160 * 1024, "LDS");
-  auto kern = conv_winox3_kernel<TH, BN, TM, TN, FLAGS>;
-  if constexpr (lds > 64 * 1024) {
-    static ConvLdsAttrFlags attr_flags;   // one per kernel instantiation (this launcher is a template)
-    if (const hipError_t e = conv_allow_dynamic_lds(reinterpret_cast<const void*>(kern), attr_flags, (int)lds); e != hipSuccess) return e;
-  }
   const int ntx = (p.W + 63) / 64, nty = (p.H + TH - 1) / TH;
   dim3 grid((unsigned)(p.NB * ntx * nty), p.Cout / BN);
-  hipLaunchKernelGGL(kern, grid, dim3(NT), lds, s, p);
-  return hipGetLastError();
+  return conv_launch<conv_winox3_kernel<TH, BN, TM, TN, FLAGS>>(grid, dim3(NT), lds, s, p);
 }

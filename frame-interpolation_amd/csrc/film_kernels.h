@@ -58,8 +58,9 @@ struct ConvParams {
   // K loop (up to 1080 steps) otherwise runs on a handful of workgroups.
   int ksplit;
   float* part;
-  // conv_wino2d_kernel with W2D_F_CHAIN: consecutive pixel tiles one workgroup walks (>= 1; conv_wino2d_impl.h, "chained tiles")
-  int chain;
+  // Unused: it was the tile count of conv_wino2d_kernel's chained-tile variant, whose code is gone.  The field keeps its place, and that kernel's
+  // argument batch still loads it, because taking it out moves mg_* / tl_* and renumbers the kernel's scalar registers: to go with a measured A/B.
+  int unused_chain;
   // conv_wino2d_kernel, filled by ITS LAUNCHER (callers leave them 0): ceil(2^32 / d) for d = tiles per image, tiles per row, channel blocks of
   // the grid - the workgroup -> (image, tile row, tile column, channel block) decomposition then costs three s_mul_hi_u32 instead of three
   // 40-instruction integer divisions in front of the first DMA request (0: divide; conv_wino2d_impl.h, "prologue diet")

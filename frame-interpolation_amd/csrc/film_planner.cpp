@@ -98,7 +98,7 @@ ConvFamily plain_conv_family(const ConvSite& s, const film_t& o) {
       // bf16x3: the same layers run the Winograd form of the split kernel, conv_winox3_kernel.  It wins with the 2 x 2 wave block of
       // its 128-channel tile (0.88-0.94x the time of conv_halo_split_kernel<..,3> per layer, 427 vs 367 TFLOP/s at K = 22 032) and
       // loses with the 64-channel tiles (1.08-1.30x: twice the A staging per MFMA) - per-op profiles of the two plans and
-      // tools/retired/conv_bench.hip agree.  The 64-channel layers go on to rule 4.
+      // conv_bench.hip (it left the tree in round 5; profiles/r01_conv_bench_x3.log) agree.  The 64-channel layers go on to rule 4.
       if (L.cout % 128 == 0 || o.opt_wino >= 2) return FAM_WINOX3;
     } else {
       // fp32: F(4,3) along x (conv_wino43_kernel, 2x fewer MFMAs than direct where F(2,3) has 1.5x) on the levels whose width
@@ -110,7 +110,7 @@ ConvFamily plain_conv_family(const ConvSite& s, const film_t& o) {
   // 4. Precision mode bf16x3 on the split kernel
   if (split) return FAM_SPLIT3;
   // 5. Halo staging pays where K is deep (traffic bound) or N is too narrow to amortise the per-tap A gather; measured in
-  // tools/retired/conv_bench.hip.
+  // conv_bench.hip (it left the tree in round 5; profiles/HISTORY.md 4.1).
   if (L.has_halo() && !s.any_up && (o.opt_halo_all || (px >= 8192 && (ctot >= 768 || (ctot >= 512 && px >= 100000) || L.cout == 32))))
     return FAM_HALO;
   return FAM_BUF;

@@ -13,6 +13,7 @@
 #include <map>
 #include <vector>
 
+#include "../frame-interpolation_amd/csrc/conv_buf_impl.h"
 #include "../frame-interpolation_amd/csrc/conv_fold4_impl.h"
 
 #define CK(x)                                                                              \

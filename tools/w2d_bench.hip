@@ -1,7 +1,7 @@
-// w2d_bench.hip -- micro-benchmark + bit-identity check of the nested-Winograd kernel conv_wino2d_kernel (its tiles against each other;
-// the W2D_F_XFIRST variants keep the summation order - and the bits - of round 3's kernel, which left the tree in round 5) and of its
-// split-K form against the unsplit result, with the 1-D F(4,3) kernel as the timing reference, on the layer shapes they run in a 1080p
-// 2x2-tiled forward, plus a two-segment input with a batch remap and ragged levels.  Development tool (lean sibling of conv_bench.hip: compiles in a minute), not part of the product library.
+// w2d_bench.hip -- micro-benchmark + bit-identity check of the nested-Winograd kernel conv_wino2d_kernel (the six library tiles and their
+// extended-epilogue instantiations against each other) and of its split-K form against the unsplit result, with the 1-D F(4,3) kernel as the
+// timing reference, on the layer shapes they run in a 1080p 2x2-tiled forward, plus a two-segment input with a batch remap and ragged levels;
+// and the W2D_DBG_TIME instantiations (tools/w2d_idle_budget.py).  Development tool, not part of the product library.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/w2d_bench.hip -o tools/bin/w2d_bench
 //   tools/bin/w2d_bench [reps] [shape index | -1] [variant substring[,substring...]]
@@ -94,12 +94,11 @@ __global__ void maxdiff_kernel(const float* a, const float* b, size_t n, float* 
 }
 
 typedef hipError_t (*LaunchFn)(const ConvParams&, hipStream_t);
-// fam 3: split-K (its own sums: the distance from family 1 is printed, never counted as a mismatch);
-// fam 0: the bits of round 3's kernel (the W2D_F_XFIRST order; reference = the first variant run); fam 1: conv_wino2d_kernel's own family (reference = the
-// first fam-1 variant run; its distance from family 0 is printed); fam -1: timing ablation (wrong on purpose); fam 2: the 1-D F(4,3)
-// kernel conv_wino43_kernel (its own weights and sums: timing reference, distance from family 0 printed)
+// fam 1: conv_wino2d_kernel (reference = the first such variant run; every other one must match it bit for bit); fam 3: split-K (its own
+// sums: the distance from family 1 is printed, never counted as a mismatch); fam 2: the 1-D F(4,3) kernel conv_wino43_kernel (its own weights
+// and sums: timing reference, distance from family 1 printed); fam -1: W2D_DBG_TIME (p.part holds the stamps; the output is not compared)
 struct Variant { const char* name; int bn; int fam; LaunchFn fn; };
-#define W2N(NAME, BN, FL) {"w2d " NAME, BN, ((FL) & 0x3F00) ? -1 : ((FL) & W2D_F_XFIRST) ? 0 : 1, conv_wino2d_launch<BN, FL>}
+#define W2N(NAME, BN, FL) {"w2d " NAME, BN, ((FL) & W2D_DBG_TIME) ? -1 : 1, conv_wino2d_launch<BN, FL>}
 // split-K: conv_wino2d_kernel with S K ranges (blockIdx.z) + the ordered reduction (the engine's conv_splitk_reduce_kernel, restated)
 static float* g_part = nullptr;
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ out,
@@ -132,48 +131,18 @@ static hipError_t w2d_split(const ConvParams& p0, hipStream_t st) {
   return hipGetLastError();
 }
 #define W2S(NAME, BN, S) {"w2d " NAME, BN, 3, w2d_split<BN, S>}
-// chained tiles (W2D_F_CHAIN): CH consecutive pixel tiles per workgroup, NS stages; the same sums as the unchained kernel
-template <int BN, int NS, int CH, int FL>
-static hipError_t w2d_chain(const ConvParams& p0, hipStream_t st) {
-  ConvParams p = p0;
-  p.chain = CH;
-  return conv_wino2d_launch<BN, 4 | W2D_F_CHAIN | FL, NS>(p, st);
-}
-#define W2C(NAME, BN, NS, CH) {"w2d " NAME, BN, 1, w2d_chain<BN, NS, CH, 0>}
-// occupancy experiment: the unchained two-stage tile with EXTRA KB of dynamic LDS it does not use
-template <int EXTRA_KB>
-static hipError_t w2d_ns2_lds(const ConvParams& p, hipStream_t st) {
-  conv_wino2d_debug_extra_lds() = EXTRA_KB * 1024;
-  const hipError_t e = conv_wino2d_launch<32, 4, 2>(p, st);
-  conv_wino2d_debug_extra_lds() = 0;
-  return e;
-}
 #define W43(NAME, BN, ...) {"w43 " NAME, BN, 2, conv_wino43_launch<__VA_ARGS__>}
 static Variant variants[] = {
-    W43("q16 4x64 t21 p2", 64, 4, 64, 2, 1, 4 | W43_F_PF2, 16), W43("q16 4x64 n1 p2", 64, 4, 64, 1, 1, 4 | W43_F_PF2, 16, 1), W43("q8 8x64 t21 p2", 64, 8, 64, 2, 1, 4 | W43_F_PF2, 8),
-    W43("q8 8x64 n1 p2", 64, 8, 64, 1, 1, 4 | W43_F_PF2, 8, 1), W43("q16 4x32 bg", 32, 4, 32, 1, 1, 4 | W43_F_BG, 16), W43("q8 8x32 bg", 32, 8, 32, 1, 1, 4 | W43_F_BG, 8), W43("q8 8x32 p2", 32, 8, 32, 1, 1, 4 | W43_F_PF2, 8),
-    W2N("64 xf", 64, 4 | W2D_F_XFIRST), W2N("32 xf", 32, 4 | W2D_F_XFIRST),
     W2N("64", 64, 4), W2N("32", 32, 4), W2N("64 plain", 64, 0), W2N("32 plain", 32, 0),
-    W2S("64 split2", 64, 2), W2S("32 split2", 32, 2), W2S("64 split3", 64, 3), W2S("32 split3", 32, 3), W2S("64 split4", 64, 4), W2S("32 split4", 32, 4),
-    W2C("32 ns2 ch1", 32, 2, 1), W2C("32 ns2 ch2", 32, 2, 2), W2C("32 ns2 ch4", 32, 2, 4), W2C("32 ns2 ch8", 32, 2, 8),
-    W2C("64 ns3 ch1", 64, 3, 1), W2C("64 ns3 ch2", 64, 3, 2), W2C("64 ns3 ch4", 64, 3, 4), W2C("64 ns3 ch8", 64, 3, 8),
     {"w2d 32 ns2 plain", 32, 1, conv_wino2d_launch<32, 4, 2>},
+    {"w2d 32 ns2 sq", 32, 1, conv_wino2d_launch<32, 4 | W2D_F_SQ, 2>}, {"w2d 32 ns3 sq", 32, 1, conv_wino2d_launch<32, 4 | W2D_F_SQ, 3>}, {"w2d 64 ns3 sq", 64, 1, conv_wino2d_launch<64, 4 | W2D_F_SQ, 3>},
     {"w2d 32 ns2 xe", 32, 1, conv_wino2d_launch<32, 4 | W2D_F_XEPI, 2>}, {"w2d 32 ns2 sq xe", 32, 1, conv_wino2d_launch<32, 4 | W2D_F_SQ | W2D_F_XEPI, 2>},
     {"w2d 64 ns3 xe", 64, 1, conv_wino2d_launch<64, 4 | W2D_F_XEPI, 3>},
-    {"w2d 32 ns2 e1", 32, 1, conv_wino2d_launch<32, 4 | W2D_F_EPI1, 2>}, {"w2d 32 ns2 sq e1", 32, 1, conv_wino2d_launch<32, 4 | W2D_F_SQ | W2D_F_EPI1, 2>},
-    {"w2d 64 ns3 e1", 64, 1, conv_wino2d_launch<64, 4 | W2D_F_EPI1, 3>}, {"w2d 64 ns3 sq e1", 64, 1, conv_wino2d_launch<64, 4 | W2D_F_SQ | W2D_F_EPI1, 3>},
-    {"w2d 32 ns2 sq", 32, 1, conv_wino2d_launch<32, 4 | W2D_F_SQ, 2>}, {"w2d 32 ns3 sq", 32, 1, conv_wino2d_launch<32, 4 | W2D_F_SQ, 3>}, {"w2d 64 ns3 sq", 64, 1, conv_wino2d_launch<64, 4 | W2D_F_SQ, 3>},
-    {"w2d 32 ns2 lds+24", 32, 1, w2d_ns2_lds<24>}, {"w2d 32 ns2 lds+30", 32, 1, w2d_ns2_lds<30>}, {"w2d 32 ns2 lds+32", 32, 1, w2d_ns2_lds<32>},
+    W2S("64 split2", 64, 2), W2S("32 split2", 32, 2), W2S("64 split3", 64, 3), W2S("32 split3", 32, 3), W2S("64 split4", 64, 4), W2S("32 split4", 32, 4),
+    W43("q16 4x64 t21 p2", 64, 4, 64, 2, 1, 4 | W43_F_PF2, 16), W43("q16 4x64 n1 p2", 64, 4, 64, 1, 1, 4 | W43_F_PF2, 16, 1), W43("q8 8x64 t21 p2", 64, 8, 64, 2, 1, 4 | W43_F_PF2, 8),
+    W43("q8 8x64 n1 p2", 64, 8, 64, 1, 1, 4 | W43_F_PF2, 8, 1), W43("q16 4x32 bg", 32, 4, 32, 1, 1, 4 | W43_F_BG, 16), W43("q8 8x32 bg", 32, 8, 32, 1, 1, 4 | W43_F_BG, 8), W43("q8 8x32 p2", 32, 8, 32, 1, 1, 4 | W43_F_PF2, 8),
     W2N("64 time", 64, 4 | W2D_DBG_TIME), W2N("32 time", 32, 4 | W2D_DBG_TIME),
     {"w2d 32 ns2 time", 32, -1, conv_wino2d_launch<32, 4 | W2D_DBG_TIME, 2>},
-    {"w2d 32 ns2 ch4 time", 32, -1, w2d_chain<32, 2, 4, W2D_DBG_TIME>}, {"w2d 64 ns3 ch4 time", 64, -1, w2d_chain<64, 3, 4, W2D_DBG_TIME>},
-    W2N("64 abl-noxf", 64, 4 | W2D_DBG_NOXF), W2N("32 abl-noxf", 32, 4 | W2D_DBG_NOXF),
-    W2N("64 abl-nodma", 64, 4 | W2D_DBG_NODMA), W2N("32 abl-nodma", 32, 4 | W2D_DBG_NODMA),
-    W2N("64 abl-nob", 64, 4 | W2D_DBG_NOB), W2N("32 abl-nob", 32, 4 | W2D_DBG_NOB),
-    W2N("64 abl-nobar", 64, 4 | W2D_DBG_NOBAR), W2N("32 abl-nobar", 32, 4 | W2D_DBG_NOBAR),
-    W2N("64 abl-nord", 64, 4 | W2D_DBG_NORD | W2D_DBG_NOXF), W2N("32 abl-nord", 32, 4 | W2D_DBG_NORD | W2D_DBG_NOXF),
-    W2N("64 abl-mfma", 64, 4 | W2D_DBG_NORD | W2D_DBG_NOXF | W2D_DBG_NODMA | W2D_DBG_NOB | W2D_DBG_NOBAR),
-    W2N("32 abl-mfma", 32, 4 | W2D_DBG_NORD | W2D_DBG_NOXF | W2D_DBG_NODMA | W2D_DBG_NOB | W2D_DBG_NOBAR),
 };
 
 // C2 > 0: the input is two segments, [C - C2 channels of buffer A | C2 channels of buffer B read with the batch halves swapped]
@@ -228,14 +197,13 @@ int main(int argc, char** argv) {
     const int C1 = sh.C - sh.C2;
     const int strideA = C1 + 16, strideB = sh.C2 ? sh.C2 + 32 : 0;   // the segments are channel slices of wider buffers
     const size_t n_a = M * strideA, n_b = M * strideB, n_w = (size_t)9 * sh.C * sh.Cout, n_out = M * sh.Cout;
-    float *d_a, *d_bb = nullptr, *d_w, *d_w2d, *d_w43, *d_b, *d_out, *d_ref, *d_ref1, *d_md;
+    float *d_a, *d_bb = nullptr, *d_w, *d_w2d, *d_w43, *d_b, *d_out, *d_ref, *d_md;
     CK(hipMalloc(&d_a, n_a * 4));
     if (n_b) CK(hipMalloc(&d_bb, n_b * 4));
     CK(hipMalloc(&d_w, n_w * 4));
     CK(hipMalloc(&d_w2d, n_w * 4 * 24 / 9 + 64));
     CK(hipMalloc(&d_w43, n_w * 4 * 18 / 9 + 64));
     CK(hipMalloc(&d_ref, n_out * 4));
-    CK(hipMalloc(&d_ref1, n_out * 4));
     CK(hipMalloc(&d_md, 4));
     CK(hipMalloc(&g_part, n_out * 4 * 4));
     CK(hipMalloc(&d_b, sh.Cout * 4));
@@ -260,7 +228,7 @@ int main(int argc, char** argv) {
     p.NB = sh.NB; p.H = sh.H; p.W = sh.W; p.Cout = sh.Cout; p.Ctot = sh.C; p.leaky = 1; p.M = (int)M;
     const double flops = 2.0 * M * sh.Cout * 9 * sh.C;
     printf("== %d %s  (%.1f GFLOP direct)\n", shape_idx, sh.name, flops * 1e-9);
-    bool have_ref[2] = {false, false};
+    bool have_ref = false;
     for (const Variant& v : variants) {
       if (sh.Cout % v.bn) continue;
       if (only_variant) {   // comma-separated substrings: any match
@@ -292,18 +260,13 @@ int main(int argc, char** argv) {
         CK(hipStreamSynchronize(st));
         return md;
       };
-      const int fam = v.fam < 0 ? 1 : v.fam == 3 ? 1 : v.fam;   // (ablations are variants of the y-first loop)
-      float* const refs[2] = {d_ref, d_ref1};
-      if (v.fam == 3) {
-        if (have_ref[1]) fam_dist = diff_to(d_ref1);
-      } else if (v.fam == 2) {
-        if (have_ref[0]) fam_dist = diff_to(d_ref);
-      } else if (v.fam >= 0 && !have_ref[fam]) {
-        have_ref[fam] = true;
-        CK(hipMemcpyAsync(refs[fam], d_out, n_out * 4, hipMemcpyDeviceToDevice, st));
+      if (v.fam == 2 || v.fam == 3) {
+        if (have_ref) fam_dist = diff_to(d_ref);
+      } else if (v.fam == 1 && !have_ref) {
+        have_ref = true;
+        CK(hipMemcpyAsync(d_ref, d_out, n_out * 4, hipMemcpyDeviceToDevice, st));
         CK(hipStreamSynchronize(st));
-        if (fam == 1 && have_ref[0]) fam_dist = diff_to(d_ref);
-      } else if (have_ref[fam]) maxdiff = diff_to(refs[fam]);
+      } else if (v.fam == 1) maxdiff = diff_to(d_ref);
       float best = 1e30f, tot = 0;
       for (int r = 0; r < reps; ++r) {
         CK(hipEventRecord(e0, st));
@@ -355,17 +318,16 @@ int main(int argc, char** argv) {
                v.name, sh.name, sh.NB, sh.H, sh.W, sh.C, sh.Cout, v.bn, nwg, pro / nwg, loop / nwg, wait / nwg, epi / nwg, life / nwg, cus.size(), span_max, span_avg, busy_avg, n_min, n_max, ghz, best);
         // busy share of one CU slot: follow the workgroups that ran on the CU of workgroup 0 (same hw_id CU/SE bits and XCC)
       }
-      const bool abl = v.fam < 0;
-      if (!abl && maxdiff != 0.f) ++bad;
-      if (v.fam == 3 && have_ref[1] && !(fam_dist < 1e-2f)) ++bad;   // a split-K result far from the unsplit one (wrong range / cursor)
+      if (maxdiff != 0.f) ++bad;
+      if (v.fam == 3 && have_ref && !(fam_dist < 1e-2f)) ++bad;   // a split-K result far from the unsplit one (wrong range / cursor)
       printf("   %-24s  min %8.3f ms  avg %8.3f ms  %7.1f TF/s direct-eq  %s max|d| %.2e", v.name, best, tot / reps, flops / best * 1e-9,
-             abl ? "(ablation)" : v.fam == 3 ? "split-K family" : v.fam == 2 ? "1-D family" : maxdiff == 0.f ? (fam ? "bit-identical (family 1)" : "bit-identical (family 0)") : "MISMATCH", maxdiff);
-      if (fam_dist >= 0.f) printf("   [vs family %d: max|d| %.2e, checksum %.6e]", v.fam == 3 ? 1 : 0, fam_dist, sum);
+             v.fam < 0 ? "(instrumented)" : v.fam == 3 ? "split-K family" : v.fam == 2 ? "1-D family" : maxdiff == 0.f ? "bit-identical (family 1)" : "MISMATCH", maxdiff);
+      if (fam_dist >= 0.f) printf("   [vs family 1: max|d| %.2e, checksum %.6e]", fam_dist, sum);
       printf("\n");
       fflush(stdout);
     }
     CK(hipFree(d_tm)); CK(hipFree(g_part)); g_part = nullptr;
-    CK(hipFree(d_a)); if (d_bb) CK(hipFree(d_bb)); CK(hipFree(d_w)); CK(hipFree(d_w2d)); CK(hipFree(d_w43)); CK(hipFree(d_ref)); CK(hipFree(d_ref1)); CK(hipFree(d_md)); CK(hipFree(d_b)); CK(hipFree(d_out));
+    CK(hipFree(d_a)); if (d_bb) CK(hipFree(d_bb)); CK(hipFree(d_w)); CK(hipFree(d_w2d)); CK(hipFree(d_w43)); CK(hipFree(d_ref)); CK(hipFree(d_md)); CK(hipFree(d_b)); CK(hipFree(d_out));
   }
   printf("mismatches: %d\n", bad);
   return bad ? 1 : 0;
