@@ -119,11 +119,35 @@ hipError_t cut_tiles(const TileMapParams& tp, hipStream_t s) {
 hipError_t join_tiles(const TileMapParams& tp, hipStream_t s) {
   return (tp.ovy | tp.ovx) ? film_launch_blend_tiles(tp, s) : film_launch_tiles_to_frame(tp, s);
 }
-// cut_tiles on a frame batch of pixel type `pix`: tp.src points at float32 or, with FILM_PIX_U8, at bytes that the cut itself dequantises
-// (whole aligned 32-bit words: the 8-bit kernels read such words)
+// The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the 4:2:0 layouts.
+int pix_layout(int pix) { return pix & 0xff; }
+bool pix_is_yuv(int pix) { return pix_layout(pix) == FILM_PIX_I420 || pix_layout(pix) == FILM_PIX_NV12; }
+// FILM_OK, or the refusal of a pix value for H x W frames (include/film_hip.h, film_stream_open)
+int check_pix(film_t* h, int pix, int H, int W) {
+  const int layout = pix_layout(pix), flags = pix & ~0xff;
+  if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !pix_is_yuv(pix))
+    return fail(h, FILM_ERR_INVALID, "bad pix layout %d: FILM_PIX_F32 (0), FILM_PIX_U8 (1), FILM_PIX_I420 (16) or FILM_PIX_NV12 (17)", layout);
+  if (flags & ~(FILM_YUV_BT601 | FILM_YUV_FULL))
+    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: unknown bits 0x%x set (flags: FILM_YUV_BT601 0x100, FILM_YUV_FULL 0x400)", (unsigned)pix,
+                (unsigned)(flags & ~(FILM_YUV_BT601 | FILM_YUV_FULL)));
+  if (flags && !pix_is_yuv(pix))
+    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: the colour flags belong to FILM_PIX_I420 / FILM_PIX_NV12, not to an RGB layout", (unsigned)pix);
+  if (pix_is_yuv(pix) && H > 0 && W > 0 && ((H | W) & 1))
+    return fail(h, FILM_ERR_INVALID, "pix: 4:2:0 needs even sizes, got %d x %d", H, W);
+  return FILM_OK;
+}
+// bytes of one H x W frame of pixel type `pix`
+size_t frame_bytes(int pix, int H, int W) {
+  const size_t px = (size_t)H * W;
+  return pix_is_yuv(pix) ? px + px / 2 : pix_layout(pix) == FILM_PIX_U8 ? px * 3 : px * 3 * sizeof(float);
+}
+// cut_tiles on a frame batch of pixel type `pix`: tp.src points at float32 or, with FILM_PIX_U8 and the 4:2:0 layouts, at bytes that the
+// cut itself converts (whole aligned 32-bit words: the 8-bit kernels read such words)
 hipError_t cut_tiles_pix(const TileMapParams& tp, int pix, hipStream_t s) {
-  if (pix != FILM_PIX_U8) return cut_tiles(tp, s);
+  if (pix_layout(pix) == FILM_PIX_F32) return cut_tiles(tp, s);
   const uint8_t* src = reinterpret_cast<const uint8_t*>(tp.src);
+  if (pix_is_yuv(pix))
+    return film_launch_yuv420_to_tiles(tp, src, pix_layout(pix) == FILM_PIX_NV12, (pix & FILM_YUV_BT601) != 0, (pix & FILM_YUV_FULL) != 0, s);
   return (tp.ovy | tp.ovx) ? film_launch_frame_to_tiles_overlap_u8(tp, src, s) : film_launch_frame_to_tiles_u8(tp, src, s);
 }
 // The handle's staging buffer in HBM (whole frames of the FILM_MEM_HOST entry points), grown on demand.
@@ -320,7 +344,6 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
 }
 
 // ---- frame streams (film_stream_*; the contract: include/film_hip.h) ----
-size_t pix_bytes(int pix) { return pix == FILM_PIX_U8 ? 1 : sizeof(float); }
 // The stream's device buffers go back and it is closed.  Work that may still use them is the caller's to wait for.
 void stream_free(film_t* h) {
   FilmStream& fs = h->fs;
@@ -361,6 +384,12 @@ extern "C" {
 int film_to_uint8(const float* src, unsigned char* dst, int64_t n, void* stream) {
   if (n < 0 || (n > 0 && (!src || !dst))) return FILM_ERR_INVALID;
   return film_launch_to_uint8(src, dst, n, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
+}
+
+int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream) {
+  if (!src || !dst || H < 1 || W < 1 || !pix_is_yuv(pix) || check_pix(nullptr, pix, H, W) != FILM_OK) return FILM_ERR_INVALID;
+  return film_launch_rgb_to_yuv420(src, static_cast<uint8_t*>(dst), H, W, pix_layout(pix) == FILM_PIX_NV12, (pix & FILM_YUV_BT601) != 0,
+                                   (pix & FILM_YUV_FULL) != 0, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
 }
 
 #ifndef FILM_SRC_ID
@@ -616,11 +645,12 @@ int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* bu
 int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix) {
   if (!h) return FILM_ERR_INVALID;
   if (h->fs.open) return fail(h, FILM_ERR_STATE, "a stream is already open on this handle (one per handle: close it, or create another handle)");
-  if (pix != FILM_PIX_F32 && pix != FILM_PIX_U8) return fail(h, FILM_ERR_INVALID, "bad pix: FILM_PIX_F32 (0) or FILM_PIX_U8 (1)");
+  int rc = check_pix(h, pix, H, W);
+  if (rc) return rc;
   if (H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
   TileMapParams tp{};
   tp.B = 1;
-  int rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
+  rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
   if (rc == FILM_OK) rc = need_device(h, "film_stream_open");
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->device));
@@ -637,13 +667,14 @@ int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_
   if (rc) return rc;
   FilmStream& fs = h->fs;
   const size_t nv = (size_t)H * W * 3;
-  hipError_t e = hipMalloc(&fs.keep, (nv * pix_bytes(pix) + 3) & ~(size_t)3);   // (whole 32-bit words: the 8-bit cut reads aligned words)
+  const size_t fb = frame_bytes(pix, H, W);
+  hipError_t e = hipMalloc(&fs.keep, (fb + 3) & ~(size_t)3);   // (whole 32-bit words: the 8-bit cuts read aligned words)
   if (e == hipSuccess) e = hipMalloc((void**)&fs.result, nv * sizeof(float));
-  if (e == hipSuccess && pix == FILM_PIX_U8) e = hipMalloc((void**)&fs.result8, nv);
+  if (e == hipSuccess && pix_layout(pix) != FILM_PIX_F32) e = hipMalloc((void**)&fs.result8, fb);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     stream_free(h);
-    return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's frame buffers (%.1f MB) failed", nv * (pix_bytes(pix) + 5) * 1e-6);
+    return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's frame buffers (%.1f MB) failed", (2 * fb + nv * sizeof(float)) * 1e-6);
   }
   fs.open = true;
   fs.H = H; fs.W = W; fs.align = align; fs.block_h = block_h; fs.block_w = block_w; fs.pix = pix;
@@ -705,21 +736,27 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
   }
   const int slot = fs.primed ? 1 - fs.slot : 0;
   Plan* P = P0->orientation(slot);
-  HIPCHK(h, hipMemcpyAsync(fs.keep, frame, nv * pix_bytes(fs.pix), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  const size_t fb = frame_bytes(fs.pix, fs.H, fs.W);
+  HIPCHK(h, hipMemcpyAsync(fs.keep, frame, fb, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
   HIPCHK(h, stream_cut(fs, tp, P, slot, s));
   if (!fs.primed) {
     if ((rc = run_plan(h, P, s, P->n_extract))) return rc;
   } else {
     if ((rc = run_plan(h, P, s))) return rc;
-    // joined in float32 by the kernels of film_interpolate, then quantised by film_to_uint8's kernel for an 8-bit stream
+    // joined in float32 by the kernels of film_interpolate, then quantised by film_to_uint8's kernel for an 8-bit RGB stream, by
+    // film_to_yuv420's for a 4:2:0 stream
     float* joined = (fs.pix == FILM_PIX_F32 && !host) ? (float*)mid : fs.result;
     TileMapParams j = tp;
     j.tile0 = 0; j.ntiles = T; j.src = P->at("out"); j.dst = joined;
     HIPCHK(h, join_tiles(j, s));
-    if (fs.pix == FILM_PIX_U8) {
+    if (fs.pix != FILM_PIX_F32) {
       uint8_t* q = host ? fs.result8 : (uint8_t*)mid;
-      HIPCHK(h, film_launch_to_uint8(joined, q, (int64_t)nv, s));
-      if (host) HIPCHK(h, hipMemcpyAsync(mid, q, nv, hipMemcpyDeviceToHost, s));
+      if (pix_is_yuv(fs.pix))
+        HIPCHK(h, film_launch_rgb_to_yuv420(joined, q, fs.H, fs.W, pix_layout(fs.pix) == FILM_PIX_NV12, (fs.pix & FILM_YUV_BT601) != 0,
+                                            (fs.pix & FILM_YUV_FULL) != 0, s));
+      else
+        HIPCHK(h, film_launch_to_uint8(joined, q, (int64_t)nv, s));
+      if (host) HIPCHK(h, hipMemcpyAsync(mid, q, fb, hipMemcpyDeviceToHost, s));
     } else if (host) {
       HIPCHK(h, hipMemcpyAsync(mid, joined, nv * sizeof(float), hipMemcpyDeviceToHost, s));
     }
@@ -832,6 +869,32 @@ int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* t
     tp.src = tiles_dev; tp.dst = static_cast<float*>(frames_dev);
     HIPCHK(h, join_tiles(tp, (hipStream_t)stream));
   }
+  return FILM_OK;
+}
+
+int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h, int block_w,
+                       int tile0, int ntiles, void* stream) {
+  // (as film_debug_tile_map: the arguments and the geometry are checked before the device)
+  if (!h) return FILM_ERR_INVALID;
+  if (!frames_dev || !tiles_dev) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: NULL argument");
+  if (!pix_is_yuv(pix)) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: bad pix layout %d: FILM_PIX_I420 (16) or FILM_PIX_NV12 (17)", pix_layout(pix));
+  int rc = check_pix(h, pix, H, W);
+  if (rc) return rc;
+  if (reinterpret_cast<uintptr_t>(frames_dev) & 3) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: the frames of a 4:2:0 pix must be 4-byte aligned");
+  if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
+  TileMapParams tp{};
+  tp.B = B;
+  rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
+  if (rc) return rc;
+  const int64_t total = (int64_t)B * tp.bh * tp.bw;
+  if (ntiles < 1 || tile0 < 0 || (int64_t)tile0 + ntiles > total)
+    return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: tiles [%d, %lld) are no range of the %lld tiles of the batch", tile0,
+                (long long)tile0 + ntiles, (long long)total);
+  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: film_debug_yuv_cut needs a HIP device (no CPU fallback)");
+  HIPCHK(h, hipSetDevice(h->device));
+  tp.tile0 = tile0; tp.ntiles = ntiles;
+  tp.src = static_cast<const float*>(frames_dev); tp.dst = tiles_dev;
+  HIPCHK(h, cut_tiles_pix(tp, pix, (hipStream_t)stream));
   return FILM_OK;
 }
 

@@ -172,10 +172,10 @@ enum FuseBit {
 // stream's own copy of that frame (in its pixel type), from which they are rebuilt when the plan was evicted or dropped in between.
 struct FilmStream {
   bool open = false;
-  int H = 0, W = 0, align = 0, block_h = 0, block_w = 0, pix = 0;
-  void* keep = nullptr;             // the last pushed frame [H][W][3], float32 or bytes
+  int H = 0, W = 0, align = 0, block_h = 0, block_w = 0, pix = 0;   // pix: a FILM_PIX_* layout plus, for 4:2:0, the FILM_YUV_* flags
+  void* keep = nullptr;             // the last pushed frame: [H][W][3] float32 or bytes, or the H * W * 3 / 2 bytes of a 4:2:0 frame
   float* result = nullptr;          // the joined float32 mid-frame of a host or 8-bit push
-  unsigned char* result8 = nullptr; // ... quantised, of an 8-bit host push
+  unsigned char* result8 = nullptr; // ... quantised (RGB bytes or a 4:2:0 frame), of an 8-bit host push
   bool primed = false;              // `keep` holds a frame
   int slot = 0;                     // the half of the plan's frame buffers it was extracted into ...
   uint64_t plan_id = 0;             // ... of this plan (Plan::id) ...

@@ -385,6 +385,11 @@ hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams& p, hipStream_
 // float32(byte) / 255.0f, correctly rounded (= numpy's astype(float32) / 255), padding stays zero.  A thread handles twelve bytes of a row.
 hipError_t film_launch_frame_to_tiles_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s);
 hipError_t film_launch_frame_to_tiles_overlap_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s);
+// Both cuts on a batch of 8-bit Y'CbCr 4:2:0 frames (FILM_PIX_I420 / FILM_PIX_NV12; H and W even): frame b is the H * W * 3 / 2 bytes at
+// src + b * H * W * 3 / 2; overlapped tiles when p.ovy | p.ovx.  bt601 / full: the colour matrix and range (include/film_hip.h).
+hipError_t film_launch_yuv420_to_tiles(TileMapParams p, const uint8_t* src, bool nv12, bool bt601, bool full, hipStream_t s);
+// float32 [H][W][3] -> one 4:2:0 frame of H * W * 3 / 2 bytes (clip, matrix, 2 x 2 box mean of the chroma, quantisation)
+hipError_t film_launch_rgb_to_yuv420(const float* src, uint8_t* dst, int H, int W, bool nv12, bool bt601, bool full, hipStream_t s);
 // crop + cross-fade of the tiles [tile0, tile0 + ntiles) into the frames: adds to what the tiles below tile0 left in dst, so the
 // launches of one frame go in tile order on one stream
 hipError_t film_launch_blend_tiles(const TileMapParams& p, hipStream_t s);

@@ -28,8 +28,20 @@ FILM_ERR_STATE = -2
 FILM_ERR_NO_DEVICE = -3
 FILM_ERR_NOMEM = -5
 # pixel types of a frame stream (film_stream_open)
-FILM_PIX_F32, FILM_PIX_U8 = 0, 1
-PIX = {'f32': (FILM_PIX_F32, np.float32), 'u8': (FILM_PIX_U8, np.uint8)}
+FILM_PIX_F32, FILM_PIX_U8, FILM_PIX_I420, FILM_PIX_NV12 = 0, 1, 16, 17
+PIX = {'f32': (FILM_PIX_F32, np.float32), 'u8': (FILM_PIX_U8, np.uint8), 'i420': (FILM_PIX_I420, np.uint8), 'nv12': (FILM_PIX_NV12, np.uint8)}
+# colour flags of the 4:2:0 pixel types (added to the layout code)
+FILM_YUV_BT601, FILM_YUV_FULL = 0x100, 0x400
+YUV_MATRIX = {'bt709': 0, 'bt601': FILM_YUV_BT601}
+
+
+def pix_code(pix: str, matrix: str = 'bt709', full_range: bool = False) -> int:
+    """The `pix` argument of the C-ABI: the layout code of `pix` plus the colour flags (which only the 4:2:0 layouts accept)."""
+    if pix not in PIX:
+        raise ValueError(f'pix must be one of {sorted(PIX)}, got {pix!r}')
+    if matrix not in YUV_MATRIX:
+        raise ValueError(f"matrix must be 'bt709' or 'bt601', got {matrix!r}")
+    return PIX[pix][0] | YUV_MATRIX[matrix] | (FILM_YUV_FULL if full_range else 0)
 # film_image_metrics flags (include/film_hip.h); METRIC_FLAGS maps the metric names of eval/metrics.py to them
 FILM_METRIC_L1, FILM_METRIC_L2, FILM_METRIC_PSNR, FILM_METRIC_SSIM, FILM_METRIC_CLIP = 1, 2, 4, 8, 16
 METRIC_FLAGS = {'l1': FILM_METRIC_L1, 'l2': FILM_METRIC_L2, 'psnr': FILM_METRIC_PSNR, 'ssim': FILM_METRIC_SSIM}
@@ -59,7 +71,8 @@ EXPORTED_SYMBOLS = (
     'film_export_tune', 'film_import_tune', 'film_to_uint8', 'film_load_bundle', 'film_bcast_weights',
     'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json',
     'film_debug_arena', 'film_debug_run_op', 'film_debug_tile_map',
-    'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json')
+    'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json',
+    'film_to_yuv420', 'film_debug_yuv_cut')
 
 _lib = None
 
@@ -127,6 +140,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                                       ctypes.POINTER(ctypes.c_int)]
     lib.film_debug_tile_map.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
+    lib.film_to_yuv420.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
+    lib.film_debug_yuv_cut.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     lib.film_stream_open.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.film_stream_push.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp]
     lib.film_stream_reset.argtypes = [vp]
@@ -173,22 +189,24 @@ def _cfg_struct(opt: Options) -> _Config:
 class FilmStream:
     """One open frame stream of an engine (film_stream_*; FilmEngine.open_stream): push() one frame at a time and get the mid-frame
     between it and the frame pushed before - bit-identical to interpolate_frames(previous, frame) - with one feature extraction per
-    frame.  Frames and results are [H,W,3] float32 ('f32') or uint8 ('u8': x = u8 / 255, result = eval.util.to_uint8's bytes).
+    frame.  Frames and results are [H,W,3] float32 ('f32') or uint8 ('u8': x = u8 / 255, result = eval.util.to_uint8's bytes), or
+    8-bit Y'CbCr 4:2:0 frames ('i420', 'nv12') as uint8 [H * 3 // 2, W]: the Y plane, then the Cb and Cr planes (I420) or the plane of
+    CbCr pairs (NV12), with `matrix` 'bt709' | 'bt601' and limited or full range (the arithmetic: include/film_hip.h).
     One stream per engine at a time; use it as a context manager or close() it."""
 
-    def __init__(self, engine: 'FilmEngine', h: int, w: int, align: Optional[int], block_shape, pix: str):
-        if pix not in PIX:
-            raise ValueError(f"pix must be 'f32' or 'u8', got {pix!r}")
+    def __init__(self, engine: 'FilmEngine', h: int, w: int, align: Optional[int], block_shape, pix: str, matrix: str = 'bt709',
+                 full_range: bool = False):
+        self._code = pix_code(pix, matrix, full_range)
         self._eng = engine
-        self.shape = (int(h), int(w), 3)
+        self.shape = (int(h) * 3 // 2, int(w)) if pix in ('i420', 'nv12') else (int(h), int(w), 3)
         self.pix = pix
-        self._code, self.dtype = PIX[pix]
+        self.dtype = PIX[pix][1]
         bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
         engine._check(engine._lib.film_stream_open(engine._h, int(h), int(w), int(align or 0), bh, bw, self._code))
         self._open = True
 
     def push(self, frame: np.ndarray, out: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
-        """frame: [H,W,3] host array of the stream's dtype.  None for the first frame after open / reset, else the mid-frame
+        """frame: host array of the stream's shape and dtype.  None for the first frame after open / reset, else the mid-frame
         (a new array, or `out`: a writable C-contiguous array of the frame's shape and dtype)."""
         a = np.asarray(frame)
         if a.dtype != self.dtype or a.shape != self.shape:
@@ -205,7 +223,7 @@ class FilmStream:
         return out if produced.value else None
 
     def push_device(self, ptr_in: int, ptr_out: int, stream: Optional[int] = None) -> bool:
-        """Device-resident push: raw device pointers to [H,W,3] of the stream's pixel type, asynchronous on `stream`.
+        """Device-resident push: raw device pointers to one frame of the stream's pixel type each, asynchronous on `stream`.
         Returns whether ptr_out receives a mid-frame (False for the first frame after open / reset; ptr_out may then be 0)."""
         produced = ctypes.c_int(0)
         eng = self._eng
@@ -460,9 +478,11 @@ class FilmEngine:
                                                         ctypes.c_void_p(out_ptr), FILM_MEM_DEVICE,
                                                         ctypes.c_void_p(stream) if stream else None))
 
-    def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32') -> FilmStream:
-        """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix 'f32' | 'u8'."""
-        return FilmStream(self, h, w, align, block_shape, pix)
+    def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32', matrix: str = 'bt709',
+                    full_range: bool = False) -> FilmStream:
+        """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix 'f32' | 'u8' |
+        'i420' | 'nv12', the latter two (8-bit 4:2:0, h and w even) with the colour `matrix` 'bt709' | 'bt601' and limited or full range."""
+        return FilmStream(self, h, w, align, block_shape, pix, matrix, full_range)
 
     @staticmethod
     def _metric_flags(names, clip: bool) -> int:
@@ -508,6 +528,14 @@ class FilmEngine:
         rc = self._lib.film_to_uint8(ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), int(n), ctypes.c_void_p(stream) if stream else None)
         if rc != 0:
             raise FilmError(rc, 'film_to_uint8 failed')
+
+    def to_yuv420_device(self, src_ptr: int, dst_ptr: int, h: int, w: int, pix: str = 'i420', matrix: str = 'bt709',
+                         full_range: bool = False, stream: Optional[int] = None) -> None:
+        """film_to_yuv420: h x w x 3 device floats -> one 4:2:0 frame of h * w * 3 // 2 device bytes ('i420' | 'nv12'), asynchronous."""
+        rc = self._lib.film_to_yuv420(ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), int(h), int(w), pix_code(pix, matrix, full_range),
+                                      ctypes.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise FilmError(rc, 'film_to_yuv420 failed')
 
     def set_option(self, key: str, value: int) -> None:
         self._check(self._lib.film_set_option(self._h, key.encode(), int(value)))
@@ -596,6 +624,15 @@ class FilmEngine:
                                                   ctypes.c_void_p(frames_ptr), ctypes.c_void_p(tiles_ptr), int(b), int(h), int(w),
                                                   int(align or 0), bh, bw, int(tile0), int(ntiles),
                                                   ctypes.c_void_p(stream) if stream else None))
+
+    def debug_yuv_cut(self, frames_ptr: int, tiles_ptr: int, b: int, h: int, w: int, align: Optional[int], block_shape, tile0: int,
+                      ntiles: int, pix: str = 'i420', matrix: str = 'bt709', full_range: bool = False, stream: Optional[int] = None) -> None:
+        """film_debug_yuv_cut: ONE cut of tiles [tile0, tile0 + ntiles) of b 4:2:0 frames (h * w * 3 // 2 bytes each, in a 4-byte aligned
+        allocation of whole 32-bit words) into float32 RGB tiles, with the geometry of tiling(h, w, align, block_shape)."""
+        bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
+        self._check(self._lib.film_debug_yuv_cut(self._h, pix_code(pix, matrix, full_range), ctypes.c_void_p(frames_ptr),
+                                                 ctypes.c_void_p(tiles_ptr), int(b), int(h), int(w), int(align or 0), bh, bw, int(tile0),
+                                                 int(ntiles), ctypes.c_void_p(stream) if stream else None))
 
     def forward_with_aux(self, x0: np.ndarray, x1: np.ndarray) -> Dict[str, object]:
         """The reference model's output dictionary with `use_aux_outputs` on (models/film_net/interpolator.py:

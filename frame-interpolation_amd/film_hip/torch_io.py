@@ -52,12 +52,12 @@ def patches_to_image(patches: torch.Tensor, block_shape: List[int]) -> torch.Ten
 
 class DeviceStream:
     """A frame stream on frames that already live in HBM (DeviceInterpolator.stream): push(frame) takes a [H,W,3] CUDA tensor, float32
-    or uint8 as opened, and returns the mid-frame between it and the frame pushed before as a new tensor of the same kind - None for
+    or uint8 as opened (a 4:2:0 stream: uint8 [H * 3 // 2, W]), and returns the mid-frame between it and the frame pushed before as a new tensor of the same kind - None for
     the first frame after opening or reset().  Asynchronous on the current torch stream."""
 
-    def __init__(self, engine: FilmEngine, h: int, w: int, align, block_shape, pix: str):
-        self._stream = engine.open_stream(h, w, align=align, block_shape=block_shape, pix=pix)
-        self._dtype = torch.uint8 if pix == 'u8' else torch.float32
+    def __init__(self, engine: FilmEngine, h: int, w: int, align, block_shape, pix: str, matrix: str = 'bt709', full_range: bool = False):
+        self._stream = engine.open_stream(h, w, align=align, block_shape=block_shape, pix=pix, matrix=matrix, full_range=full_range)
+        self._dtype = torch.float32 if pix == 'f32' else torch.uint8
 
     def push(self, frame: torch.Tensor) -> Optional[torch.Tensor]:
         assert frame.is_cuda and frame.dtype == self._dtype and tuple(frame.shape) == self._stream.shape
@@ -127,11 +127,12 @@ class DeviceInterpolator:
                                                  block_shape=bs if bs is not None and bs[0] * bs[1] > 1 else None, stream=stream)
         return out
 
-    def stream(self, h: int, w: int, pix: str = 'f32') -> DeviceStream:
+    def stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False) -> DeviceStream:
         """Extension: a frame stream of h x w frames (film_stream_*), padded / tiled like batch(): push one CUDA tensor at a time, float32
-        or ('u8') uint8, and get the mid-frame with the frame before - bit-identical to batch(previous, frame), one extraction per frame."""
+        or ('u8') uint8, and get the mid-frame with the frame before - bit-identical to batch(previous, frame), one extraction per frame.
+        'i420' / 'nv12': 8-bit 4:2:0 frames as uint8 [h * 3 // 2, w] tensors, converted inside the cut and the quantisation."""
         bs = self._block_shape
-        return DeviceStream(self._engine, h, w, self._align, bs if bs is not None and bs[0] * bs[1] > 1 else None, pix)
+        return DeviceStream(self._engine, h, w, self._align, bs if bs is not None and bs[0] * bs[1] > 1 else None, pix, matrix, full_range)
 
     def __call__(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         if self._block_shape is not None and self._block_shape[0] * self._block_shape[1] > 1:

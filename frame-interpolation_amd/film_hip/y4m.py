@@ -1,0 +1,161 @@
+"""Reader and writer of YUV4MPEG2 (.y4m) streams of 8-bit 4:2:0 frames - the frames a 4:2:0 frame stream takes (film_stream_open with
+FILM_PIX_I420: FilmEngine.open_stream(pix='i420')), so that video goes in and out without PNGs and without ffmpeg.
+
+A stream is one header line, "YUV4MPEG2" and space-separated tokens - W<width> H<height> F<num>:<den> I<interlacing> A<n>:<d>
+C<colour space> X<anything> ... - then per frame a line "FRAME[ <parameters>]" and the payload: Y [H][W], Cb [H/2][W/2], Cr [H/2][W/2],
+which is the I420 layout.  A frame is handed on as one uint8 array [H * 3 // 2, W] (FilmStream.shape).
+
+Accepted: 8-bit C420, C420jpeg, C420mpeg2, C420paldv (no C token means 420) - the three differ in where the chroma samples sit, which
+the engine's box treatment (include/film_hip.h) does not tell apart; Ip, I? or no I token.  Refused, with the token in the message:
+4:2:2, 4:4:4, mono, 10-bit and deeper, interlaced material, odd sizes.  XCOLORRANGE=FULL marks full-range samples.
+"""
+from __future__ import annotations
+
+from typing import BinaryIO, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+MAGIC = b'YUV4MPEG2'
+FRAME = b'FRAME'
+C420 = ('420', '420jpeg', '420mpeg2', '420paldv')
+_MAX_LINE = 4096
+
+
+class Y4MError(ValueError):
+    pass
+
+
+def _read_exact(f: BinaryIO, n: int) -> bytes:
+    """n bytes, or fewer at the end of the stream (a pipe hands out short reads)."""
+    parts, got = [], 0
+    while got < n:
+        b = f.read(n - got)
+        if not b:
+            break
+        parts.append(b)
+        got += len(b)
+    return b''.join(parts)
+
+
+def _read_line(f: BinaryIO) -> bytes:
+    """One line without its newline; b'' at the end of the stream."""
+    out = bytearray()
+    while len(out) <= _MAX_LINE:
+        c = f.read(1)
+        if not c:
+            if out:
+                raise Y4MError(f'truncated: the stream ends inside the line {bytes(out[:40])!r}')
+            return b''
+        if c == b'\n':
+            return bytes(out)
+        out += c
+    raise Y4MError(f'a line of more than {_MAX_LINE} bytes: not a YUV4MPEG2 stream')
+
+
+def double_rate(tokens: Sequence[str]) -> List[str]:
+    """The header tokens with the numerator of the F token doubled (twice the frames in the same time); everything else as it is."""
+    out = []
+    for t in tokens:
+        if t[:1] == 'F' and ':' in t:
+            num, den = t[1:].split(':', 1)
+            t = f'F{int(num) * 2}:{den}'
+        out.append(t)
+    return out
+
+
+def parse_header(line: bytes) -> Tuple[int, int, List[str]]:
+    """(width, height, tokens) of a header line; the refusals of this module."""
+    parts = line.decode('ascii', 'replace').split()
+    if not parts or parts[0] != MAGIC.decode():
+        raise Y4MError(f'not a YUV4MPEG2 stream: it starts with {line[:16]!r}')
+    tokens = parts[1:]
+    w = h = None
+    for t in tokens:
+        key, val = t[:1], t[1:]
+        if key == 'W' or key == 'H':
+            if not val.isdigit() or int(val) < 1:
+                raise Y4MError(f'bad size token {t!r}')
+            if key == 'W':
+                w = int(val)
+            else:
+                h = int(val)
+        elif key == 'C' and val not in C420:
+            raise Y4MError(f'colour space token {t!r}: only 8-bit 4:2:0 ({", ".join("C" + c for c in C420)}) is read - no 4:2:2, 4:4:4, '
+                           'mono, 10-bit or deeper')
+        elif key == 'I' and val not in ('p', '?'):
+            raise Y4MError(f'interlacing token {t!r}: only progressive material (Ip, I? or no I token) is read')
+    if w is None or h is None:
+        raise Y4MError('the header names no W / H')
+    if (w | h) & 1:
+        raise Y4MError(f'tokens W{w} H{h}: a 4:2:0 frame stream needs even sizes')
+    return w, h, tokens
+
+
+class Y4MReader:
+    """Iterates over the frames of a YUV4MPEG2 stream (a binary file object) as uint8 arrays [H * 3 // 2, W]."""
+
+    def __init__(self, f: BinaryIO):
+        self._f = f
+        line = _read_line(f)
+        if not line:
+            raise Y4MError('empty stream: no YUV4MPEG2 header')
+        self.width, self.height, self.tokens = parse_header(line)
+        self.frame_bytes = self.width * self.height * 3 // 2
+        self.frames_read = 0
+
+    @property
+    def full_range(self) -> bool:
+        return any(t.upper() == 'XCOLORRANGE=FULL' for t in self.tokens)
+
+    @property
+    def rate(self) -> Optional[Tuple[int, int]]:
+        for t in self.tokens:
+            if t[:1] == 'F' and ':' in t:
+                num, den = t[1:].split(':', 1)
+                return int(num), int(den)
+        return None
+
+    def read_frame(self) -> Optional[np.ndarray]:
+        """The next frame, or None at the end of the stream; Y4MError when the stream ends inside a frame."""
+        line = _read_line(self._f)
+        if not line:
+            return None
+        if line != FRAME and not line.startswith(FRAME + b' '):
+            raise Y4MError(f'frame {self.frames_read}: expected a FRAME line, got {line[:40]!r}')
+        data = _read_exact(self._f, self.frame_bytes)
+        if len(data) != self.frame_bytes:
+            raise Y4MError(f'truncated: frame {self.frames_read} has {len(data)} of {self.frame_bytes} bytes')
+        self.frames_read += 1
+        return np.frombuffer(data, np.uint8).reshape(self.height * 3 // 2, self.width)
+
+    def __iter__(self) -> Iterator[np.ndarray]:
+        while True:
+            fr = self.read_frame()
+            if fr is None:
+                return
+            yield fr
+
+
+class Y4MWriter:
+    """Writes a YUV4MPEG2 stream: the header from `tokens` (as Y4MReader.tokens; W and H among them, checked like a reader's), then
+    one frame per write()."""
+
+    def __init__(self, f: BinaryIO, tokens: Sequence[str]):
+        self._f = f
+        self.tokens = list(tokens)
+        self.width, self.height, _ = parse_header(' '.join([MAGIC.decode()] + self.tokens).encode('ascii'))
+        self.frames_written = 0
+        f.write(b' '.join([MAGIC] + [t.encode('ascii') for t in self.tokens]) + b'\n')
+
+    def write(self, frame: np.ndarray) -> None:
+        a = np.ascontiguousarray(frame)
+        if a.dtype != np.uint8 or a.shape != (self.height * 3 // 2, self.width):
+            raise ValueError(f'expected a uint8 array of shape {(self.height * 3 // 2, self.width)}, got {a.dtype} {a.shape}')
+        self._f.write(FRAME + b'\n')
+        self._f.write(a.tobytes())
+        self.frames_written += 1
+
+
+def header_tokens(width: int, height: int, rate: Tuple[int, int] = (30, 1), full_range: bool = False, colour: str = '420jpeg') -> List[str]:
+    """Tokens of a progressive 8-bit 4:2:0 stream with square pixels."""
+    return [f'W{width}', f'H{height}', f'F{rate[0]}:{rate[1]}', 'Ip', 'A1:1', f'C{colour}'] + (['XCOLORRANGE=FULL'] if full_range else [])

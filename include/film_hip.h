@@ -155,17 +155,18 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  * pyramid are read where that push left them, so every frame is extracted once (film_interpolate extracts every inner frame twice)
  * and nothing is copied between pushes: a stream plan holds the two frames of a pair in two slots that take turns.
  *   film_stream_open   H x W frames, align / block_h / block_w as for film_interpolate (same padding, tiling, "block_overlap_*",
- *                      refusals).  pix: FILM_PIX_F32 or FILM_PIX_U8.  ONE open stream per handle (a second open: FILM_ERR_STATE);
+ *                      refusals).  pix: a pixel type below (a layout, for the 4:2:0 layouts plus colour flags).  ONE open stream per handle (a second open: FILM_ERR_STATE);
  *                      several streams = several handles, as for threads.  Builds (and autotunes) the plan, so the pushes are steady.
  *                      The whole frame must fit ONE model invocation: more tiles than the limits of film_interpolate allow (today a
  *                      4K frame cut 4 x 4 would run as two chunks of 8) is FILM_ERR_INVALID with the limit in the message - use a finer
  *                      block shape - and a workspace that cannot be allocated is FILM_ERR_NOMEM: a stream neither chunks a frame
  *                      nor halves on out-of-memory.  Plan-only handle: FILM_ERR_NO_DEVICE; before film_finalize: FILM_ERR_STATE.
- *   film_stream_push   frame [H,W,3] in, mid [H,W,3] out, both of the stream's pixel type.  The first push after open / reset sets
+ *   film_stream_push   frame [H,W,3] in, mid [H,W,3] out, both of the stream's pixel type (a 4:2:0 stream: H * W * 3 / 2 bytes each).  The first push after open / reset sets
  *                      *produced = 0 and only cuts the frame into its tiles and runs the image pyramid and the feature extractor
  *                      (`mid` is not touched and may be NULL); every later push sets *produced = 1 and writes `mid`, bit-identical
  *                      to film_interpolate(previous frame, frame, 1, H, W, align, block_h, block_w) under the handle's current
- *                      options - with FILM_PIX_U8 to film_to_uint8 of that call on the frames u8 / 255.0f, byte for byte.
+ *                      options - with FILM_PIX_U8 to film_to_uint8 of that call on the frames u8 / 255.0f, byte for byte; with a 4:2:0
+ *                      pixel type to film_to_yuv420 of that call on the frames converted by "In" below, byte for byte.
  *                      mem_kind / stream as for film_interpolate; FILM_MEM_HOST is upload, work, download ("host_overlap" does not
  *                      apply) and moves one byte per value each way with FILM_PIX_U8.  Results never depend on what else the handle
  *                      did between two pushes: the stream keeps its own device copy of the previous frame and extracts it again,
@@ -181,6 +182,34 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                      earlier frame at image (1 - slot) * tiles.  Both orientations list the same buffers.  Works on plan-only handles. */
 #define FILM_PIX_F32 0   /* frames and results float32 [H,W,3], as everywhere else */
 #define FILM_PIX_U8  1   /* frames and results uint8 [H,W,3]: x = u8 / 255.0f (IEEE, = read_image), result = film_to_uint8's rule */
+/* 8-bit Y'CbCr 4:2:0 frames: the conversion in is fused into the tile cut, the conversion out into the quantisation, so such a frame
+ * crosses PCIe as 1.5 bytes per pixel each way and the caller needs no colour kernels of its own.  `pix` = a layout in bits 0-7 plus
+ * colour flags.  FILM_ERR_INVALID, with "pix" in the message: any other bit set; a colour flag together with FILM_PIX_F32 / FILM_PIX_U8;
+ * an odd H or W with a 4:2:0 layout (4:2:0 needs even sizes).  Device pointers to 4:2:0 frames must be 4-byte aligned (as for
+ * FILM_PIX_U8: the cut reads the aligned 32-bit words that hold a row's bytes, none of which lies outside the allocation rounded up to
+ * whole words). */
+#define FILM_PIX_I420   16      /* Y[H][W], Cb[H/2][W/2], Cr[H/2][W/2], contiguous: H*W*3/2 bytes */
+#define FILM_PIX_NV12   17      /* Y[H][W], CbCr[H/2][W/2][2] interleaved: H*W*3/2 bytes */
+#define FILM_YUV_BT601  0x100   /* matrix: absent = BT.709 */
+#define FILM_YUV_FULL   0x400   /* range: absent = limited (16..235 / 16..240) */
+/* The 4:2:0 arithmetic.  Every operation is float32 with one rounding, no fused multiply-add.  (Kr, Kb) = (0.2126, 0.0722) for BT.709,
+ * (0.299, 0.114) for BT.601, Kg = 1 - Kr - Kb; every constant below is computed from them in double and rounded to float32 once.
+ *   In (bytes -> RGB).  Per-byte tables, IEEE division on the host: limited range y[v] = (float(v) - 16) / 219, c[v] = (float(v) - 128) / 224;
+ *     full range y[v] = float(v) / 255, c[v] = (float(v) - 128) / 255.  Pixel (y, x) takes the chroma sample (y >> 1, x >> 1): chroma is
+ *     treated as centre-sited and replicated.  With y = y[Y], cb = c[Cb], cr = c[Cr]:
+ *       R = y + a_r * cr              a_r = 2 (1 - Kr)
+ *       B = y + a_b * cb              a_b = 2 (1 - Kb)
+ *       G = (y - g_b * cb) - g_r * cr     g_b = 2 Kb (1 - Kb) / Kg, g_r = 2 Kr (1 - Kr) / Kg
+ *     each then clipped: max(., 0) followed by min(., 1).
+ *   Out (RGB -> bytes).  Per channel x = min(max(v, 0), 1) (write_image's clip), then
+ *       Yf  = (kr * R + kg * G) + kb * B              kr, kg, kb = float32(Kr), float32(Kg), float32(Kb)
+ *       cbf = (B - Yf) * s_b          s_b = 0.5 / (1 - Kb)
+ *       crf = (R - Yf) * s_r          s_r = 0.5 / (1 - Kr)
+ *     chroma of the 2 x 2 block (j, k): m = ((c[2j][2k] + c[2j][2k+1]) + (c[2j+1][2k] + c[2j+1][2k+1])) * 0.25
+ *     q(v) = uint8(min(max(v, 0), 255) + 0.5);  limited: Y = q(Yf * 219 + 16), C = q(m * 224 + 128);  full: Y = q(Yf * 255), C = q(m * 255 + 128).
+ *   Replicate in and box mean out are inverse to each other: a frame whose RGB stays inside the gamut returns byte for byte.
+ *   Not provided: 10-bit (P010) and 4:2:2 / 4:4:4 layouts; sited bilinear chroma (MPEG-2 left siting - the box treatment is consistent in
+ *   and out); 4:2:0 frames on film_interpolate / film_interpolate_sequence themselves (film_to_yuv420 converts their results). */
 int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix);
 int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int mem_kind, void* stream);
 int film_stream_reset(film_t* h);
@@ -353,6 +382,12 @@ int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int 
  * [0, B * block_h * block_w).  Then FILM_ERR_NO_DEVICE on a plan-only handle.  Not on any forward path. */
 int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h,
                         int block_w, int tile0, int ntiles, void* stream);
+/* film_debug_yuv_cut: ONE cut of a batch of B 4:2:0 frames (frame b at byte b * H * W * 3 / 2 of frames_dev, a 4-byte aligned DEVICE
+ * pointer into an allocation of whole 32-bit words) into float32 RGB tiles: film_debug_tile_map mode 0 with pix = FILM_PIX_I420 /
+ * FILM_PIX_NV12 plus colour flags - same geometry, same tile buffer, same refusals (and those of `pix` above), reached through the
+ * dispatch a 4:2:0 stream's push cuts with (tests/test_yuv_gpu.py).  Not on any forward path. */
+int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h, int block_w,
+                       int tile0, int ntiles, void* stream);
 
 /* The per-image evaluation metrics of the benchmark loop on the device: the reference's losses/losses.py:72-113 (l1, l2, psnr, ssim
  * of eval/eval_cli.py:160-170), restated in frame-interpolation_amd/eval/metrics.py, whose arithmetic the kernels follow (float32
@@ -377,6 +412,13 @@ int film_image_metrics(film_t* h, const float* pred, const float* ref, int B, in
  * src (float32) and dst (uint8) are DEVICE pointers to n values; asynchronous on `stream` (NULL: the default stream) of the
  * current device.  The frames of a recursion then cross PCIe as 1 byte per value instead of 4.  Returns FILM_OK or a negative error. */
 int film_to_uint8(const float* src, unsigned char* dst, int64_t n, void* stream);
+
+/* "Out" of the 4:2:0 arithmetic above on the device: src float32 [H][W][3] -> dst, one frame of H * W * 3 / 2 bytes in the layout and
+ * colour setting `pix` names (FILM_PIX_I420 / FILM_PIX_NV12 plus flags).  DEVICE pointers, any alignment of dst (whole 32-bit words are
+ * stored where it allows); asynchronous on `stream` (NULL: the default stream) of the current device, like film_to_uint8.  What a 4:2:0
+ * stream's push quantises its result with; results of film_interpolate / film_interpolate_sequence leave as 4:2:0 through it too.
+ * FILM_ERR_INVALID: a NULL pointer, H or W < 1 or odd, pix no 4:2:0 pixel type. */
+int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream);
 
 /* The variable-restore half of `tf.compat.v2.saved_model.load(model_path)` (reference eval/interpolator.py:148): reads the
  * checkpoint of a Keras SavedModel - `<path>/variables/variables.index` + `.data-0000N-of-0000M`, written by model.save()

@@ -6,8 +6,11 @@
 A round = one fresh worker process per tree, baseline first: the baseline worker times `pair` (film_interpolate, device-resident, one
 pair per call - what a frame-by-frame caller had before), this tree's worker times `pair` too (the two agree unless the trees differ
 in what a pair call runs: their difference over the rounds IS the box's spread), then `push_f32` / `push_u8` (a steady-state push,
-device-resident), `sequence` (film_interpolate_sequence over a long sequence, per generated frame) and, at the first point, the
-host-buffer calls `host_pair` (film_interpolate on numpy arrays, as bench.py's host_buffers), `host_push_f32`, `host_push_u8`.
+device-resident), `push_i420` / `push_nv12` (the same on 8-bit 4:2:0 frames, where the tree has them), `sequence`
+(film_interpolate_sequence over a long sequence, per generated frame) and, at the first point, the host-buffer calls `host_pair`
+(film_interpolate on numpy arrays, as bench.py's host_buffers), `host_push_f32`, `host_push_u8`, `host_push_i420`, `host_push_nv12`.
+The 4:2:0 rows are compared with the BASELINE's `push_u8` / `host_push_u8` (what such a caller had before: RGB bytes), whose spread
+over the rounds is reported next to them.  --rows / --points restrict a run to some measurements.
 Every measurement: untimed warm-up calls (plan build, autotune, first launches), then --reps timed windows of `n` calls, each
 ended by a device synchronise; the window's ms per call is one sample.  Each tree keeps its autotune choices in a file of its own
 under --scratch, so that the rounds of a tree run the same tiles.  The report gives mean and range over all samples of a
@@ -38,19 +41,22 @@ def _frames(f, h, w, seed=0):
     return np.clip(np.stack([np.roll(base, (2 * i, -3 * i), axis=(0, 1)) for i in range(f)]), 0, 1).astype(np.float32)
 
 
-def worker(root, reps, quick):
-    """Times what the checkout at `root` offers; prints one JSON line."""
+def worker(root, reps, quick, rows=None, points=None):
+    """Times what the checkout at `root` offers (of `rows` / `points`, when given); prints one JSON line."""
     for p in (root, os.path.join(root, 'frame-interpolation_amd')):
         sys.path.insert(0, p)
     import numpy as np
     import torch
     from film_hip import weights as W
+    from film_hip import engine as engine_mod
     from film_hip.engine import FilmEngine
     from film_hip.options import PUBLISHED
     from film_hip.torch_io import DeviceInterpolator
     eng = FilmEngine(PUBLISHED, device=0)
     eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
     has_stream = hasattr(eng, 'open_stream')
+    has_yuv = 'i420' in getattr(engine_mod, 'PIX', {})
+    want = lambda key: rows is None or key in rows      # noqa: E731
     out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {}}
 
     def timed(call, n, warm=3):
@@ -67,7 +73,7 @@ def worker(root, reps, quick):
         return [round(s, 4) for s in samples]
 
     for pi, (name, h, w, align, block, n, fseq) in enumerate(POINTS):
-        if quick and pi == 0:
+        if (quick and pi == 0) or (points is not None and name not in points):
             continue
         res = {}
         it = DeviceInterpolator(eng, align=align, block_shape=list(block) if block else None)
@@ -84,29 +90,45 @@ def worker(root, reps, quick):
             i = nxt(3)
             return it.batch(x[i][None], x[i + 1][None])
 
-        res['pair'] = timed(pair, n)
+        if want('pair'):
+            res['pair'] = timed(pair, n)
         if has_stream:
-            want = it.batch(x[0][None], x[1][None])[0]
+            ref = it.batch(x[0][None], x[1][None])[0]
             with it.stream(h, w, 'f32') as st:
                 st.push(x[0])
-                res['identical'] = bool(torch.equal(st.push(x[1]), want))
-                res['push_f32'] = timed(lambda: st.push(x[nxt(4)]), n)
-            with it.stream(h, w, 'u8') as st:
-                st.push(x8[0])
-                res['push_u8'] = timed(lambda: st.push(x8[nxt(4)]), n)
-            seq = torch.from_numpy(_frames(fseq, h, w)).cuda()
-            res['sequence'] = [round(s / (fseq - 1), 4) for s in timed(lambda: it.sequence(seq), max(1, n // (fseq - 1)), warm=2)]
+                res['identical'] = bool(torch.equal(st.push(x[1]), ref))
+                if want('push_f32'):
+                    res['push_f32'] = timed(lambda: st.push(x[nxt(4)]), n)
+            if want('push_u8'):
+                with it.stream(h, w, 'u8') as st:
+                    st.push(x8[0])
+                    res['push_u8'] = timed(lambda: st.push(x8[nxt(4)]), n)
+            yuv = {}
+            if has_yuv and h % 2 == 0 and w % 2 == 0:      # the frames as 4:2:0, converted by the engine itself
+                for pix in ('i420', 'nv12'):
+                    yuv[pix] = [torch.empty((h * 3 // 2, w), dtype=torch.uint8, device='cuda') for _ in x]
+                    for src, dst in zip(x, yuv[pix]):
+                        eng.to_yuv420_device(src.data_ptr(), dst.data_ptr(), h, w, pix)
+                    torch.cuda.synchronize()
+                    if want('push_' + pix):
+                        with it.stream(h, w, pix) as st:
+                            st.push(yuv[pix][0])
+                            res['push_' + pix] = timed(lambda: st.push(yuv[pix][nxt(4)]), n)
+            if want('sequence'):
+                seq = torch.from_numpy(_frames(fseq, h, w)).cuda()
+                res['sequence'] = [round(s / (fseq - 1), 4) for s in timed(lambda: it.sequence(seq), max(1, n // (fseq - 1)), warm=2)]
+                del seq
             if pi == 0 or quick and pi == 1:
                 f8 = [(f * 255 + 0.5).astype(np.uint8) for f in fr]
                 hn = max(5, n // 3)
-                res['host_pair'] = timed(lambda: eng.interpolate_frames(fr[:1], fr[1:2], align=align, block_shape=block), hn, warm=2)
-                with eng.open_stream(h, w, align=align, block_shape=block, pix='f32') as st:
-                    st.push(fr[0])
-                    res['host_push_f32'] = timed(lambda: st.push(fr[nxt(4)]), hn, warm=2)
-                with eng.open_stream(h, w, align=align, block_shape=block, pix='u8') as st:
-                    st.push(f8[0])
-                    res['host_push_u8'] = timed(lambda: st.push(f8[nxt(4)]), hn, warm=2)
-            del seq
+                if want('host_pair'):
+                    res['host_pair'] = timed(lambda: eng.interpolate_frames(fr[:1], fr[1:2], align=align, block_shape=block), hn, warm=2)
+                for pix, frames in [('f32', fr), ('u8', f8)] + [(p, [t.cpu().numpy() for t in v]) for p, v in yuv.items()]:
+                    if want('host_push_' + pix):
+                        with eng.open_stream(h, w, align=align, block_shape=block, pix=pix) as st:
+                            st.push(frames[0])
+                            res['host_push_' + pix] = timed(lambda: st.push(frames[nxt(4)]), hn, warm=2)
+            del yuv
         out['points'][name] = res
         del x, x8
         torch.cuda.empty_cache()
@@ -115,9 +137,10 @@ def worker(root, reps, quick):
     print('STREAM_BENCH ' + json.dumps(out), flush=True)
 
 
-def _run_worker(root, reps, quick, tune_file):
+def _run_worker(root, reps, quick, tune_file, rows=None, points=None):
     env = dict(os.environ, FILM_TUNE_CACHE=tune_file)
     cmd = [sys.executable, os.path.abspath(__file__), '--worker', root, '--reps', str(reps)] + (['--quick'] if quick else [])
+    cmd += (['--rows', ','.join(rows)] if rows else []) + (['--points', ','.join(points)] if points else [])
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)   # (a hung worker ends the run: nothing is started behind it)
     for line in p.stdout.splitlines():
         if line.startswith('STREAM_BENCH '):
@@ -137,16 +160,20 @@ def main(argv=None):
     ap.add_argument('--quick', action='store_true', help='without the 1080p point')
     ap.add_argument('--scratch', default=os.path.join(HERE, 'tools', 'scratch'), help='where the per-tree autotune caches go')
     ap.add_argument('--out', default=None, help='also append the report to this file')
+    ap.add_argument('--rows', default=None, help='comma-separated measurements to take (default: all), e.g. push_u8,push_i420,host_push_u8')
+    ap.add_argument('--points', default=None, help='comma-separated points to run (default: all), e.g. "1080p 2x2"')
     ap.add_argument('--worker', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    rows = args.rows.split(',') if args.rows else None
+    points = args.points.split(',') if args.points else None
     if args.worker:
-        return worker(args.worker, args.reps, args.quick)
+        return worker(args.worker, args.reps, args.quick, rows, points)
     os.makedirs(args.scratch, exist_ok=True)
     trees = ([('baseline', os.path.abspath(args.baseline_root))] if args.baseline_root else []) + [('this', HERE)]
     runs = {k: [] for k, _ in trees}
     for r in range(args.rounds):
         for k, root in trees:
-            runs[k].append(_run_worker(root, args.reps, args.quick, os.path.join(args.scratch, f'stream_bench_tune_{k}.txt')))
+            runs[k].append(_run_worker(root, args.reps, args.quick, os.path.join(args.scratch, f'stream_bench_tune_{k}.txt'), rows, points))
             print(f'# round {r + 1}/{args.rounds} {k}: done', flush=True)
     this = runs['this']
     lines = [f'# tools/stream_bench.py  this = {this[0]["version"]}' + (f'  baseline = {runs["baseline"][0]["version"]}' if args.baseline_root else '') +
@@ -158,25 +185,35 @@ def main(argv=None):
         lines.append(f'{name}:')
         pts = [r['points'][name] for r in this]
         base = [r['points'][name] for r in runs.get('baseline', [])]
-        if base:
-            lines.append(f'  {"baseline pair":<16} {_stat([s for p in base for s in p["pair"]])}')
-        for key in ('pair', 'push_f32', 'push_u8', 'sequence', 'host_pair', 'host_push_f32', 'host_push_u8'):
+        for key in ('pair', 'push_u8', 'host_push_u8'):
+            if base and key in base[0]:
+                lines.append(f'  {"baseline " + key:<22} {_stat([s for p in base for s in p[key]])}')
+        for key in ('pair', 'push_f32', 'push_u8', 'push_i420', 'push_nv12', 'sequence', 'host_pair', 'host_push_f32', 'host_push_u8',
+                    'host_push_i420', 'host_push_nv12'):
             if key in pts[0]:
-                lines.append(f'  {key:<16} {_stat([s for p in pts for s in p[key]])}' + ('   (per generated frame)' if key == 'sequence' else ''))
-        lines.append(f'  push_f32 == pair, bit for bit: {all(p["identical"] for p in pts)}')
-        if base:
+                lines.append(f'  {key:<22} {_stat([s for p in pts for s in p[key]])}' + ('   (per generated frame)' if key == 'sequence' else ''))
+        lines.append(f'  push_f32 == pair, bit for bit: {all(p.get("identical", True) for p in pts)}')
+        if base and 'pair' in base[0]:
             bm = [statistics.mean(p['pair']) for p in base]
             spread = max(bm) - min(bm)
             for key in ('pair', 'push_f32', 'push_u8'):
-                d = [statistics.mean(p[key]) - b for p, b in zip(pts, bm)]
-                lines.append(f'  {key + " - baseline pair":<28} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms')
+                if key in pts[0]:
+                    d = [statistics.mean(p[key]) - b for p, b in zip(pts, bm)]
+                    lines.append(f'  {key + " - baseline pair":<36} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms')
             lines.append(f'  spread of the baseline pair call over the rounds (max - min of the round means): {spread:.3f} ms')
+        # the 4:2:0 pushes against what the baseline offers such a caller: its 8-bit RGB push
+        for mine, theirs in [(f'{pre}push_{pix}', f'{pre}push_u8') for pre in ('', 'host_') for pix in ('i420', 'nv12')]:
+            if base and theirs in base[0] and mine in pts[0]:
+                bm = [statistics.mean(p[theirs]) for p in base]
+                d = [statistics.mean(p[mine]) - b for p, b in zip(pts, bm)]
+                lines.append(f'  {mine + " - baseline " + theirs:<36} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms'
+                             f'   (baseline {theirs}: round means {" ".join(f"{b:.3f}" for b in bm)}, spread {max(bm) - min(bm):.3f} ms)')
     lines.append('# raw: ' + json.dumps(runs))
     print('\n'.join(lines), flush=True)
     if args.out:
         with open(args.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')
-    if not all(p['identical'] for r in this for p in r['points'].values()):
+    if not all(p.get('identical', True) for r in this for p in r['points'].values()):
         raise SystemExit('a push differs from the pair call')
 
 
