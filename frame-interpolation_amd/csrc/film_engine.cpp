@@ -112,13 +112,6 @@ int tile_geometry(film_t* h, int H, int W, int block_h, int block_w, int align, 
   }
   return FILM_OK;
 }
-// frame -> tiles and tiles -> frame of the tile range in tp: the reference's patches, or overlapped tiles and their cross-fade
-hipError_t cut_tiles(const TileMapParams& tp, hipStream_t s) {
-  return (tp.ovy | tp.ovx) ? film_launch_frame_to_tiles_overlap(tp, s) : film_launch_frame_to_tiles(tp, s);
-}
-hipError_t join_tiles(const TileMapParams& tp, hipStream_t s) {
-  return (tp.ovy | tp.ovx) ? film_launch_blend_tiles(tp, s) : film_launch_tiles_to_frame(tp, s);
-}
 // The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the 4:2:0 layouts.
 int pix_layout(int pix) { return pix & 0xff; }
 bool pix_is_yuv(int pix) { return pix_layout(pix) == FILM_PIX_I420 || pix_layout(pix) == FILM_PIX_NV12; }
@@ -140,15 +133,6 @@ int check_pix(film_t* h, int pix, int H, int W) {
 size_t frame_bytes(int pix, int H, int W) {
   const size_t px = (size_t)H * W;
   return pix_is_yuv(pix) ? px + px / 2 : pix_layout(pix) == FILM_PIX_U8 ? px * 3 : px * 3 * sizeof(float);
-}
-// cut_tiles on a frame batch of pixel type `pix`: tp.src points at float32 or, with FILM_PIX_U8 and the 4:2:0 layouts, at bytes that the
-// cut itself converts (whole aligned 32-bit words: the 8-bit kernels read such words)
-hipError_t cut_tiles_pix(const TileMapParams& tp, int pix, hipStream_t s) {
-  if (pix_layout(pix) == FILM_PIX_F32) return cut_tiles(tp, s);
-  const uint8_t* src = reinterpret_cast<const uint8_t*>(tp.src);
-  if (pix_is_yuv(pix))
-    return film_launch_yuv420_to_tiles(tp, src, pix_layout(pix) == FILM_PIX_NV12, (pix & FILM_YUV_BT601) != 0, (pix & FILM_YUV_FULL) != 0, s);
-  return (tp.ovy | tp.ovx) ? film_launch_frame_to_tiles_overlap_u8(tp, src, s) : film_launch_frame_to_tiles_u8(tp, src, s);
 }
 // The handle's staging buffer in HBM (whole frames of the FILM_MEM_HOST entry points), grown on demand.
 int ensure_stage(film_t* h, size_t bytes, hipStream_t s) {
@@ -234,13 +218,13 @@ int run_chunk(film_t* h, Plan* P, TileMapParams tp, const std::vector<Cut>& cuts
   const int64_t tile_floats = (int64_t)tp.TH * tp.TW * 3;
   for (const Cut& c : cuts) {
     tp.tile0 = c.tile0; tp.ntiles = c.ntiles; tp.src = c.frames; tp.dst = P->at("img0") + c.slot * tile_floats;
-    HIPCHK(h, cut_tiles(tp, s));
+    HIPCHK(h, film_launch_cut_tiles(tp, FILM_PIX_F32, s));
   }
   int rc = run_plan(h, P, s);
   if (rc) return rc;
   for (const Join& j : joins) {   // (overlapped tiles: the joins of a frame add up in tile order on this one stream, chunk after chunk)
     tp.tile0 = j.tile0; tp.ntiles = j.ntiles; tp.src = P->at("out") + j.slot * tile_floats; tp.dst = j.frames;
-    HIPCHK(h, join_tiles(tp, s));
+    HIPCHK(h, film_launch_join_tiles(tp, s));
   }
   return FILM_OK;
 }
@@ -299,7 +283,7 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
   lp.mid_tail = [&]() -> hipError_t {
     TileMapParams t2 = tp;
     t2.ntiles = nt / 2; t2.src = P->at("out"); t2.dst = st + 2 * nf;
-    hipError_t e = film_launch_tiles_to_frame(t2, s);
+    hipError_t e = film_launch_join_tiles(t2, s);
     if (e == hipSuccess) e = hipEventRecord(h->pipe_ev[1], s);
     return e;
   };
@@ -311,13 +295,13 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
   } drain{h, s, true};
   HIPCHK(h, hipMemcpyAsync(st, x0, frame_bytes, hipMemcpyHostToDevice, s));
   tp.ntiles = nt; tp.src = st; tp.dst = P->at("img0");
-  HIPCHK(h, film_launch_frame_to_tiles(tp, s));
+  HIPCHK(h, film_launch_cut_tiles(tp, FILM_PIX_F32, s));
   HIPCHK(h, hipEventRecord(h->pipe_ev[0], s));
   HIPCHK(h, hipStreamWaitEvent(h->stream2, h->pipe_ev[0], 0));   // (the side stream: behind whatever `s` held before this call, too)
   for (size_t i : lp.head) HIPCHK(h, launch_op(batch_part(P->ops[i], 0, 2), P->arena, h->packed_dev, s));
   HIPCHK(h, hipMemcpyAsync(st + nf, x1, frame_bytes, hipMemcpyHostToDevice, h->stream2));
   tp.src = st + nf; tp.dst = P->at("img0") + (int64_t)nt * tp.TH * tp.TW * 3;
-  HIPCHK(h, film_launch_frame_to_tiles(tp, h->stream2));
+  HIPCHK(h, film_launch_cut_tiles(tp, FILM_PIX_F32, h->stream2));
   HIPCHK(h, hipEventRecord(h->pipe_ev[0], h->stream2));
   HIPCHK(h, hipStreamWaitEvent(s, h->pipe_ev[0], 0));
   const hipError_t le = issue_lanes(h, P, s, false, &lp);
@@ -327,7 +311,7 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
   if (lp.tail) {
     TileMapParams t2 = tp;
     t2.tile0 = nt / 2; t2.ntiles = nt - nt / 2; t2.src = P->at("out") + (int64_t)(nt / 2) * tile_floats; t2.dst = st + 2 * nf;
-    HIPCHK(h, film_launch_tiles_to_frame(t2, s));
+    HIPCHK(h, film_launch_join_tiles(t2, s));
     const size_t half = frame_bytes / 2;   // (one frame, an even number of block rows: the upper half of the rows)
     HIPCHK(h, hipStreamWaitEvent(h->stream2, h->pipe_ev[1], 0));
     HIPCHK(h, hipMemcpyAsync(out, st + 2 * nf, half, hipMemcpyDeviceToHost, h->stream2));
@@ -335,7 +319,7 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
     HIPCHK(h, hipStreamSynchronize(h->stream2));
   } else {
     tp.tile0 = 0; tp.ntiles = nt; tp.src = P->at("out"); tp.dst = st + 2 * nf;
-    HIPCHK(h, film_launch_tiles_to_frame(tp, s));
+    HIPCHK(h, film_launch_join_tiles(tp, s));
     HIPCHK(h, hipMemcpyAsync(out, st + 2 * nf, frame_bytes, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(h, hipStreamSynchronize(s));
@@ -362,7 +346,7 @@ hipError_t stream_cut(const FilmStream& fs, TileMapParams tp, const Plan* P, int
   tp.tile0 = 0; tp.ntiles = tp.bh * tp.bw;
   tp.src = (const float*)fs.keep;
   tp.dst = P->at("img0") + (int64_t)slot * tp.ntiles * tp.TH * tp.TW * 3;
-  return cut_tiles_pix(tp, fs.pix, s);
+  return film_launch_cut_tiles(tp, fs.pix, s);
 }
 
 // The plan film_debug_arena / film_debug_run_op work on ("Debug / tests" in include/film_hip.h: one planned launch on a workspace the caller controls)
@@ -372,6 +356,33 @@ int debug_plan(film_t* h, int B, int H, int W, int tiles, Plan** P) {
   if (tiles < 0 || (tiles > 0 && B % tiles)) return fail(h, FILM_ERR_INVALID, "tiles must be 0 (pair plan) or divide B (sequence plan)");
   HIPCHK(h, hipSetDevice(h->device));
   return get_plan(h, B, H, W, true, P, tiles);
+}
+
+// What film_debug_tile_map and film_debug_yuv_cut (`fn`) share behind their own argument checks: ONE cut (mode 0) or join (mode 1) of tiles
+// [tile0, tile0 + ntiles) through the launchers every entry point uses.  The geometry and the range are checked before the device: a
+// plan-only handle reports them like a device handle does.
+int debug_tile_map(film_t* h, const char* fn, int mode, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h,
+                   int block_w, int tile0, int ntiles, hipStream_t s) {
+  if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
+  TileMapParams tp{};
+  tp.B = B;
+  int rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
+  if (rc) return rc;
+  const int64_t total = (int64_t)B * tp.bh * tp.bw;
+  if (ntiles < 1 || tile0 < 0 || (int64_t)tile0 + ntiles > total)
+    return fail(h, FILM_ERR_INVALID, "%s: tiles [%d, %lld) are no range of the %lld tiles of the batch", fn, tile0, (long long)tile0 + ntiles,
+                (long long)total);
+  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: %s needs a HIP device (no CPU fallback)", fn);
+  HIPCHK(h, hipSetDevice(h->device));
+  tp.tile0 = tile0; tp.ntiles = ntiles;
+  if (mode == 0) {
+    tp.src = static_cast<const float*>(frames_dev); tp.dst = tiles_dev;
+    HIPCHK(h, film_launch_cut_tiles(tp, pix, s));
+  } else {
+    tp.src = tiles_dev; tp.dst = static_cast<float*>(frames_dev);
+    HIPCHK(h, film_launch_join_tiles(tp, s));
+  }
+  return FILM_OK;
 }
 
 }  // namespace
@@ -388,8 +399,7 @@ int film_to_uint8(const float* src, unsigned char* dst, int64_t n, void* stream)
 
 int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream) {
   if (!src || !dst || H < 1 || W < 1 || !pix_is_yuv(pix) || check_pix(nullptr, pix, H, W) != FILM_OK) return FILM_ERR_INVALID;
-  return film_launch_rgb_to_yuv420(src, static_cast<uint8_t*>(dst), H, W, pix_layout(pix) == FILM_PIX_NV12, (pix & FILM_YUV_BT601) != 0,
-                                   (pix & FILM_YUV_FULL) != 0, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
+  return film_launch_rgb_to_yuv420(src, static_cast<uint8_t*>(dst), H, W, pix, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
 }
 
 #ifndef FILM_SRC_ID
@@ -748,12 +758,11 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
     float* joined = (fs.pix == FILM_PIX_F32 && !host) ? (float*)mid : fs.result;
     TileMapParams j = tp;
     j.tile0 = 0; j.ntiles = T; j.src = P->at("out"); j.dst = joined;
-    HIPCHK(h, join_tiles(j, s));
+    HIPCHK(h, film_launch_join_tiles(j, s));
     if (fs.pix != FILM_PIX_F32) {
       uint8_t* q = host ? fs.result8 : (uint8_t*)mid;
       if (pix_is_yuv(fs.pix))
-        HIPCHK(h, film_launch_rgb_to_yuv420(joined, q, fs.H, fs.W, pix_layout(fs.pix) == FILM_PIX_NV12, (fs.pix & FILM_YUV_BT601) != 0,
-                                            (fs.pix & FILM_YUV_FULL) != 0, s));
+        HIPCHK(h, film_launch_rgb_to_yuv420(joined, q, fs.H, fs.W, fs.pix, s));
       else
         HIPCHK(h, film_launch_to_uint8(joined, q, (int64_t)nv, s));
       if (host) HIPCHK(h, hipMemcpyAsync(mid, q, fb, hipMemcpyDeviceToHost, s));
@@ -844,58 +853,23 @@ int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int 
 
 int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h,
                         int block_w, int tile0, int ntiles, void* stream) {
-  // (the arguments and the geometry are checked before the device: a plan-only handle reports them like a device handle does)
   if (!h) return FILM_ERR_INVALID;
   if (!frames_dev || !tiles_dev) return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: NULL argument");
   if (mode != 0 && mode != 1) return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: bad mode %d: 0 (cut) or 1 (join)", mode);
   if (pix != FILM_PIX_F32 && pix != FILM_PIX_U8) return fail(h, FILM_ERR_INVALID, "bad pix: FILM_PIX_F32 (0) or FILM_PIX_U8 (1)");
   if (mode == 1 && pix == FILM_PIX_U8) return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: a join writes float32 frames (FILM_PIX_U8 is for the cut only)");
-  if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
-  TileMapParams tp{};
-  tp.B = B;
-  int rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
-  if (rc) return rc;
-  const int64_t total = (int64_t)B * tp.bh * tp.bw;
-  if (ntiles < 1 || tile0 < 0 || (int64_t)tile0 + ntiles > total)
-    return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: tiles [%d, %lld) are no range of the %lld tiles of the batch", tile0,
-                (long long)tile0 + ntiles, (long long)total);
-  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: film_debug_tile_map needs a HIP device (no CPU fallback)");
-  HIPCHK(h, hipSetDevice(h->device));
-  tp.tile0 = tile0; tp.ntiles = ntiles;
-  if (mode == 0) {
-    tp.src = static_cast<const float*>(frames_dev); tp.dst = tiles_dev;
-    HIPCHK(h, cut_tiles_pix(tp, pix, (hipStream_t)stream));
-  } else {
-    tp.src = tiles_dev; tp.dst = static_cast<float*>(frames_dev);
-    HIPCHK(h, join_tiles(tp, (hipStream_t)stream));
-  }
-  return FILM_OK;
+  return debug_tile_map(h, "film_debug_tile_map", mode, pix, frames_dev, tiles_dev, B, H, W, align, block_h, block_w, tile0, ntiles, (hipStream_t)stream);
 }
 
 int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h, int block_w,
                        int tile0, int ntiles, void* stream) {
-  // (as film_debug_tile_map: the arguments and the geometry are checked before the device)
   if (!h) return FILM_ERR_INVALID;
   if (!frames_dev || !tiles_dev) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: NULL argument");
   if (!pix_is_yuv(pix)) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: bad pix layout %d: FILM_PIX_I420 (16) or FILM_PIX_NV12 (17)", pix_layout(pix));
   int rc = check_pix(h, pix, H, W);
   if (rc) return rc;
   if (reinterpret_cast<uintptr_t>(frames_dev) & 3) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: the frames of a 4:2:0 pix must be 4-byte aligned");
-  if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
-  TileMapParams tp{};
-  tp.B = B;
-  rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
-  if (rc) return rc;
-  const int64_t total = (int64_t)B * tp.bh * tp.bw;
-  if (ntiles < 1 || tile0 < 0 || (int64_t)tile0 + ntiles > total)
-    return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: tiles [%d, %lld) are no range of the %lld tiles of the batch", tile0,
-                (long long)tile0 + ntiles, (long long)total);
-  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: film_debug_yuv_cut needs a HIP device (no CPU fallback)");
-  HIPCHK(h, hipSetDevice(h->device));
-  tp.tile0 = tile0; tp.ntiles = ntiles;
-  tp.src = static_cast<const float*>(frames_dev); tp.dst = tiles_dev;
-  HIPCHK(h, cut_tiles_pix(tp, pix, (hipStream_t)stream));
-  return FILM_OK;
+  return debug_tile_map(h, "film_debug_yuv_cut", 0, pix, frames_dev, tiles_dev, B, H, W, align, block_h, block_w, tile0, ntiles, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,8 @@
 
 #include <vector>
 
+#include "../../include/film_hip.h"   // FILM_PIX_*, FILM_YUV_*: the `pix` of the frame I/O launchers
+
 #define FILM_MAX_SEG 4
 #define FILM_BK 16  // channels per K-step of the implicit GEMM; every concat segment is a multiple
 
@@ -195,7 +197,7 @@ struct TileMapParams {
   int TH, TW;        // padded tile
   int oy, ox;        // patch offset inside the tile
   int tile0, ntiles; // tiles [tile0, tile0 + ntiles) of the frame batch are in the tile buffer
-  // Overlapped tiles (options "block_overlap_h" / "block_overlap_w"; read by the *_overlap kernels only): tile (ty, tx) holds the
+  // Overlapped tiles (options "block_overlap_h" / "block_overlap_w"; read by the overlapped cuts and the cross-fade only): tile (ty, tx) holds the
   // eh x ew pixels of the frame from (film_tile_origin(ty, ph, ovy, H, eh), film_tile_origin(tx, pw, ovx, W, ew)), at (oy, ox) of
   // the padded tile.  ovy = ovx = 0: eh = ph, ew = pw, the patches above.
   int ovy, ovx;      // resolved overlap per axis
@@ -378,23 +380,18 @@ hipError_t film_launch_flow_up(const FlowUpParams& p, hipStream_t s);
 hipError_t film_launch_flow_add(const FlowAddParams& p, hipStream_t s);
 hipError_t film_launch_warp(const WarpParams& p, hipStream_t s);
 hipError_t film_launch_pack_flow(const PackFlowParams& p, hipStream_t s);
-hipError_t film_launch_frame_to_tiles(const TileMapParams& p, hipStream_t s);   // pad + image_to_patches
-hipError_t film_launch_tiles_to_frame(const TileMapParams& p, hipStream_t s);   // crop + patches_to_image
-hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams& p, hipStream_t s);   // the same for overlapped tiles
-// The two cuts on an 8-bit frame [B][H][W][3] of bytes (film_stream_push, FILM_PIX_U8): `src` replaces p.src, the tile buffer receives
-// float32(byte) / 255.0f, correctly rounded (= numpy's astype(float32) / 255), padding stays zero.  A thread handles twelve bytes of a row.
-hipError_t film_launch_frame_to_tiles_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s);
-hipError_t film_launch_frame_to_tiles_overlap_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s);
-// Both cuts on a batch of 8-bit Y'CbCr 4:2:0 frames (FILM_PIX_I420 / FILM_PIX_NV12; H and W even): frame b is the H * W * 3 / 2 bytes at
-// src + b * H * W * 3 / 2; overlapped tiles when p.ovy | p.ovx.  bt601 / full: the colour matrix and range (include/film_hip.h).
-hipError_t film_launch_yuv420_to_tiles(TileMapParams p, const uint8_t* src, bool nv12, bool bt601, bool full, hipStream_t s);
-// float32 [H][W][3] -> one 4:2:0 frame of H * W * 3 / 2 bytes (clip, matrix, 2 x 2 box mean of the chroma, quantisation)
-hipError_t film_launch_rgb_to_yuv420(const float* src, uint8_t* dst, int H, int W, bool nv12, bool bt601, bool full, hipStream_t s);
-// crop + cross-fade of the tiles [tile0, tile0 + ntiles) into the frames: adds to what the tiles below tile0 left in dst, so the
-// launches of one frame go in tile order on one stream
-hipError_t film_launch_blend_tiles(const TileMapParams& p, hipStream_t s);
+// frame_kernels.hip: frame I/O.  `pix` is the public value (include/film_hip.h): a layout in bits 0-7 plus FILM_YUV_BT601 / FILM_YUV_FULL for the
+// 4:2:0 layouts; the launchers decode it.  Overlapped tiles and their cross-fade when p.ovy | p.ovx.
+// pad + image_to_patches of tiles [tile0, tile0 + ntiles): p.src is float32 [B][H][W][3] (FILM_PIX_F32), or bytes that the cut converts - [B][H][W][3]
+// (FILM_PIX_U8: float32(byte) / 255.0f, correctly rounded) or 4:2:0 frames of H * W * 3 / 2 bytes each (FILM_PIX_I420 / NV12; H and W even).
+hipError_t film_launch_cut_tiles(const TileMapParams& p, int pix, hipStream_t s);
+// crop + patches_to_image, or crop + cross-fade.  The cross-fade adds to what the tiles below tile0 left in dst, so the launches of one
+// frame go in tile order on one stream.
+hipError_t film_launch_join_tiles(const TileMapParams& p, hipStream_t s);
 // write_image's rounding on the device: dst[i] = uint8(clip(src[i] * 255, 0, 255) + 0.5)  (eval/util.py:51-52)
 hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipStream_t s);
+// float32 [H][W][3] -> one 4:2:0 frame of H * W * 3 / 2 bytes (clip, matrix, 2 x 2 box mean of the chroma, quantisation)
+hipError_t film_launch_rgb_to_yuv420(const float* src, uint8_t* dst, int H, int W, int pix, hipStream_t s);
 // fills n floats with a deterministic pseudo-random pattern in [-1, 1) (autotune inputs only)
 hipError_t film_launch_fill_random(float* dst, int64_t n, uint32_t seed, hipStream_t s);
 

@@ -10,11 +10,9 @@
 //
 // This file is compiled with -ffp-contract=off: the reference evaluates every lerp as separate
 // multiply / add tensor ops (one rounding each), so a*b+c must not become an fma here.
-#include "film_kernels.h"
+#include "conv_common.h"   // leaky02
 
 namespace {
-
-__device__ __forceinline__ float leaky02(float v) { return v > 0.f ? v : 0.2f * v; }
 
 // ------------------------------------------------------------------------------------------------
 // conv_pw: thread = pixel, all COUT (<= 16) outputs in registers; weights broadcast from LDS.
@@ -166,22 +164,15 @@ __device__ __forceinline__ void axis_x2(int o, int n, int& lo, int& hi, float& t
   t = src - f;
 }
 
-__global__ __launch_bounds__(256) void flow_up_kernel(FlowUpParams p) {
-  const int Ho = p.h * 2, Wo = p.w * 2;
-  const int64_t total = (int64_t)p.NB * Ho * Wo;
-  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (pix >= total) return;
-  const int x = (int)(pix % Wo);
-  const int64_t t2 = pix / Wo;
-  const int y = (int)(t2 % Ho);
-  const int64_t b = t2 / Ho;
+// Pixel (y, x) of image b of the result [NB][2h][2w][2] from the coarse flow `in` [NB][h][w][2].
+__device__ __forceinline__ float2 flow_up_at(const float* in, int64_t b, int h, int w, int y, int x) {
   int ylo, yhi, xlo, xhi;
   float ty, tx;
-  axis_x2(y, p.h, ylo, yhi, ty);
-  axis_x2(x, p.w, xlo, xhi, tx);
-  const float2* img = reinterpret_cast<const float2*>(p.in) + b * p.h * p.w;
-  float2 tl = img[(int64_t)ylo * p.w + xlo], tr = img[(int64_t)ylo * p.w + xhi];
-  float2 bl = img[(int64_t)yhi * p.w + xlo], br = img[(int64_t)yhi * p.w + xhi];
+  axis_x2(y, h, ylo, yhi, ty);
+  axis_x2(x, w, xlo, xhi, tx);
+  const float2* img = reinterpret_cast<const float2*>(in) + b * h * w;
+  const float2 tl = img[(int64_t)ylo * w + xlo], tr = img[(int64_t)ylo * w + xhi];
+  const float2 bl = img[(int64_t)yhi * w + xlo], br = img[(int64_t)yhi * w + xhi];
   float2 o;
   {
     const float a = 2.f * tl.x, bq = 2.f * tr.x, c = 2.f * bl.x, d = 2.f * br.x;
@@ -193,7 +184,19 @@ __global__ __launch_bounds__(256) void flow_up_kernel(FlowUpParams p) {
     const float top = a + (bq - a) * tx, bot = c + (d - c) * tx;
     o.y = top + (bot - top) * ty;
   }
-  reinterpret_cast<float2*>(p.out)[pix] = o;
+  return o;
+}
+
+__global__ __launch_bounds__(256) void flow_up_kernel(FlowUpParams p) {
+  const int Ho = p.h * 2, Wo = p.w * 2;
+  const int64_t total = (int64_t)p.NB * Ho * Wo;
+  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= total) return;
+  const int x = (int)(pix % Wo);
+  const int64_t t2 = pix / Wo;
+  const int y = (int)(t2 % Ho);
+  const int64_t b = t2 / Ho;
+  reinterpret_cast<float2*>(p.out)[pix] = flow_up_at(p.in, b, p.h, p.w, y, x);
 }
 
 __global__ __launch_bounds__(256) void flow_add_kernel(FlowAddParams p) {
@@ -223,30 +226,11 @@ __device__ __forceinline__ float lerp3(float tl, float tr, float bl, float br, f
 }
 
 // Flow of output pixel (y, x) of image b.  Either read from p.flow, or - fused resize - computed from the coarser
-// level's flow p.coarse [NB][H/2][W/2][2] exactly as flow_up_kernel does (bilinear x2 of 2*v, half-pixel centres);
+// level's flow p.coarse [NB][H/2][W/2][2] by flow_up_kernel's own flow_up_at (bilinear x2 of 2*v, half-pixel centres);
 // the caller stores it to p.flow_out once per pixel.
 __device__ __forceinline__ float2 warp_flow_at(const WarpParams& p, int64_t b, int y, int x) {
   if (p.coarse == nullptr) return reinterpret_cast<const float2*>(p.flow)[(b * p.H + y) * p.W + x];
-  const int h = p.H >> 1, w = p.W >> 1;
-  int ylo, yhi, xlo, xhi;
-  float ty, tx;
-  axis_x2(y, h, ylo, yhi, ty);
-  axis_x2(x, w, xlo, xhi, tx);
-  const float2* img = reinterpret_cast<const float2*>(p.coarse) + b * h * w;
-  const float2 tl = img[(int64_t)ylo * w + xlo], tr = img[(int64_t)ylo * w + xhi];
-  const float2 bl = img[(int64_t)yhi * w + xlo], br = img[(int64_t)yhi * w + xhi];
-  float2 o;
-  {
-    const float a = 2.f * tl.x, bq = 2.f * tr.x, c = 2.f * bl.x, d = 2.f * br.x;
-    const float top = a + (bq - a) * tx, bot = c + (d - c) * tx;
-    o.x = top + (bot - top) * ty;
-  }
-  {
-    const float a = 2.f * tl.y, bq = 2.f * tr.y, c = 2.f * bl.y, d = 2.f * br.y;
-    const float top = a + (bq - a) * tx, bot = c + (d - c) * tx;
-    o.y = top + (bot - top) * ty;
-  }
-  return o;
+  return flow_up_at(p.coarse, b, p.H >> 1, p.W >> 1, y, x);
 }
 
 // grid = (feature workgroups of a row band + misc workgroups, row bands of WARP_ROWS, images).
@@ -436,25 +420,6 @@ __global__ __launch_bounds__(256) void fill_random_kernel(float* dst, int64_t n,
   }
 }
 
-// eval/util.py:51-52 (write_image): clip(x * 255, 0, 255) + 0.5, truncated to uint8 - the same float32 operations in the same order
-// (no fused multiply-add: the file is built with -ffp-contract=off), four values per thread
-__global__ __launch_bounds__(256) void to_uint8_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, int64_t n) {
-  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i >= n) return;
-  auto cv = [](float x) -> uint32_t {
-    float v = x * 255.f;
-    v = v < 0.f ? 0.f : v;      // np.clip = minimum(maximum(x, 0), 255)
-    v = v > 255.f ? 255.f : v;
-    return (uint32_t)(v + 0.5f);
-  };
-  if (i + 3 < n && ((reinterpret_cast<uintptr_t>(src + i) & 15) == 0) && ((reinterpret_cast<uintptr_t>(dst + i) & 3) == 0)) {
-    const float4 v = *reinterpret_cast<const float4*>(src + i);
-    *reinterpret_cast<uint32_t*>(dst + i) = cv(v.x) | (cv(v.y) << 8) | (cv(v.z) << 16) | (cv(v.w) << 24);
-  } else {
-    for (int64_t k = i; k < n && k < i + 4; ++k) dst[k] = (uint8_t)cv(src[k]);
-  }
-}
-
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -520,495 +485,6 @@ hipError_t film_launch_warp(const WarpParams& p, hipStream_t s) {
 
 hipError_t film_launch_pack_flow(const PackFlowParams& p, hipStream_t s) {
   hipLaunchKernelGGL(pack_flow_kernel, dim3(blocks_for(p.npix)), dim3(256), 0, s, p);
-  return hipGetLastError();
-}
-
-// ---- Interpolator.__call__ data movement ----------------------------------------------------------------
-// thread = one float of the tile buffer (frame_to_tiles) / of the frame (tiles_to_frame); both sides are
-// contiguous in x*3+c, so consecutive threads read and write consecutive floats of a row.
-__global__ __launch_bounds__(256) void frame_to_tiles_kernel(TileMapParams p) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int row = p.TW * 3;
-  const int64_t total = (int64_t)p.ntiles * p.TH * row;
-  if (i >= total) return;
-  const int xc = (int)(i % row);
-  const int64_t r = i / row;
-  const int y = (int)(r % p.TH);
-  const int n = (int)(r / p.TH) + p.tile0;
-  const int b = n / (p.bh * p.bw), t = n % (p.bh * p.bw);
-  const int ty = t / p.bw, tx = t % p.bw;
-  const int sy = y - p.oy, sxc = xc - p.ox * 3;
-  float v = 0.f;  // tf.image.pad_to_bounding_box pads with zeros
-  if (sy >= 0 && sy < p.ph && sxc >= 0 && sxc < p.pw * 3)
-    v = p.src[(((int64_t)b * p.H + ty * p.ph + sy) * p.W + tx * p.pw) * 3 + sxc];
-  p.dst[i] = v;
-}
-
-__global__ __launch_bounds__(256) void tiles_to_frame_kernel(TileMapParams p) {
-  // thread = one float of the patches [tile0, tile0 + ntiles) as they lie in the frame
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int row = p.pw * 3;
-  const int64_t total = (int64_t)p.ntiles * p.ph * row;
-  if (i >= total) return;
-  const int xc = (int)(i % row);
-  const int64_t r = i / row;
-  const int y = (int)(r % p.ph);
-  const int ln = (int)(r / p.ph);
-  const int n = ln + p.tile0;
-  const int b = n / (p.bh * p.bw), t = n % (p.bh * p.bw);
-  const int ty = t / p.bw, tx = t % p.bw;
-  const float v = p.src[(((int64_t)ln * p.TH + p.oy + y) * p.TW + p.ox) * 3 + xc];
-  p.dst[(((int64_t)b * p.H + ty * p.ph + y) * p.W + tx * p.pw) * 3 + xc] = v;
-}
-
-// ---- overlapped tiles: every tile carries ovy / ovx pixels of its neighbours, the results are cross-faded ------------------
-// frame_to_tiles_kernel with the tile's content taken from film_tile_origin instead of the patch grid.
-__global__ __launch_bounds__(256) void frame_to_tiles_overlap_kernel(TileMapParams p) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int row = p.TW * 3;
-  const int64_t total = (int64_t)p.ntiles * p.TH * row;
-  if (i >= total) return;
-  const int xc = (int)(i % row);
-  const int64_t r = i / row;
-  const int y = (int)(r % p.TH);
-  const int n = (int)(r / p.TH) + p.tile0;
-  const int b = n / (p.bh * p.bw), t = n % (p.bh * p.bw);
-  const int ty = t / p.bw, tx = t % p.bw;
-  const int sy = y - p.oy, sxc = xc - p.ox * 3;
-  float v = 0.f;
-  if (sy >= 0 && sy < p.eh && sxc >= 0 && sxc < p.ew * 3)
-    v = p.src[(((int64_t)b * p.H + film_tile_origin(ty, p.ph, p.ovy, p.H, p.eh) + sy) * p.W + film_tile_origin(tx, p.pw, p.ovx, p.W, p.ew)) * 3 + sxc];
-  p.dst[i] = v;
-}
-
-// ---- the two cuts on an 8-bit frame (film_stream_push, FILM_PIX_U8) ------------------------------------------------------------
-// float32(byte) / 255.0f for every byte value, divided on the HOST (IEEE, = numpy's astype(float32) / 255 and eval/util.py read_image): the
-// kernel looks the quotient up, so no device division and no reciprocal decides a bit.  Passed by value (1 KB of kernel arguments).
-struct U8Table { float v[256]; };
-
-// frame_to_tiles_kernel / frame_to_tiles_overlap_kernel (OVERLAP) on a frame of bytes: p.src points at uint8 [B][H][W][3].  thread = twelve
-// consecutive values (four pixels) of one row of the tile buffer, the same tile-row-major order as the float kernels.  A group that lies
-// wholly inside the tile's content is read as the three or four ALIGNED 32-bit words that hold its twelve bytes (a row of W * 3 bytes
-// starts at any byte offset; every word read holds at least one byte of the group, so none lies outside the frame's pages) and shifted
-// into place; a group that touches the padding or the end of the row goes byte by byte.  Padding is written as zeros; the twelve floats
-// leave as three 16-byte stores where the row pitch allows.
-template <bool OVERLAP>
-__global__ __launch_bounds__(256) void frame_u8_to_tiles_kernel(TileMapParams p, U8Table tab) {
-  __shared__ float lut[256];
-  lut[threadIdx.x] = tab.v[threadIdx.x];
-  __syncthreads();
-  const int row = p.TW * 3;
-  const int groups = (row + 11) / 12;
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= (int64_t)p.ntiles * p.TH * groups) return;
-  const int xc0 = (int)(g % groups) * 12;
-  const int64_t r = g / groups;               // row of the tile buffer
-  const int y = (int)(r % p.TH);
-  const int n = (int)(r / p.TH) + p.tile0;
-  const int b = n / (p.bh * p.bw), t = n % (p.bh * p.bw);
-  const int ty = t / p.bw, tx = t % p.bw;
-  const int ch = OVERLAP ? p.eh : p.ph, cw3 = (OVERLAP ? p.ew : p.pw) * 3;   // the tile's content: rows, values per row
-  const int sy = y - p.oy, s0 = xc0 - p.ox * 3;                              // content row, content value of the group's first value
-  float v[12];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) v[j] = 0.f;   // tf.image.pad_to_bounding_box pads with zeros
-  if (sy >= 0 && sy < ch && s0 + 12 > 0 && s0 < cw3) {
-    const int fy = (OVERLAP ? film_tile_origin(ty, p.ph, p.ovy, p.H, p.eh) : ty * p.ph) + sy;
-    const int fx = OVERLAP ? film_tile_origin(tx, p.pw, p.ovx, p.W, p.ew) : tx * p.pw;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(p.src) + (((int64_t)b * p.H + fy) * p.W + fx) * 3;   // content value 0 of this row
-    if (s0 >= 0 && s0 + 12 <= cw3) {
-      const uintptr_t a = reinterpret_cast<uintptr_t>(src + s0);
-      const uint32_t* wp = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-      const unsigned sh = (unsigned)(a & 3) * 8;
-      uint32_t w[3] = {wp[0], wp[1], wp[2]};
-      if (sh) {
-        const uint32_t w3 = wp[3];
-        w[0] = (w[0] >> sh) | (w[1] << (32 - sh));
-        w[1] = (w[1] >> sh) | (w[2] << (32 - sh));
-        w[2] = (w[2] >> sh) | (w3 << (32 - sh));
-      }
-#pragma unroll
-      for (int j = 0; j < 12; ++j) v[j] = lut[(w[j >> 2] >> ((j & 3) * 8)) & 255u];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 12; ++j) {
-        const int sxc = s0 + j;
-        if (sxc >= 0 && sxc < cw3) v[j] = lut[src[sxc]];
-      }
-    }
-  }
-  float* d = p.dst + r * row + xc0;
-  if (xc0 + 12 <= row && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(d)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 12; ++j)
-      if (xc0 + j < row) d[j] = v[j];
-  }
-}
-
-// ---- 8-bit Y'CbCr 4:2:0 frames (FILM_PIX_I420 / FILM_PIX_NV12; the arithmetic: include/film_hip.h, "The 4:2:0 arithmetic") -----------
-// Everything a colour setting (matrix x range) decides, computed on the HOST: the per-byte tables with IEEE division, the coefficients
-// in double from (Kr, Kb) and rounded to float32 once.  Passed by value (2 KB of kernel arguments).
-struct YuvTables {
-  float y[256], c[256];                  // in: luma and chroma value of every byte
-  float a_r, a_b, g_b, g_r;              // in: R = y + a_r cr, B = y + a_b cb, G = (y - g_b cb) - g_r cr
-  float kr, kg, kb, s_b, s_r;            // out: Yf = (kr R + kg G) + kb B, cbf = (B - Yf) s_b, crf = (R - Yf) s_r
-  float y_scale, y_off, c_scale;         // out: Y = q(Yf y_scale + y_off), C = q(m c_scale + 128)
-};
-
-namespace {
-// n <= 7 bytes from p as the low bytes of a 64-bit value, read as the one or two ALIGNED 32-bit words that hold them: every word read
-// holds at least one of the bytes asked for
-__device__ __forceinline__ uint64_t load_bytes_aligned(const uint8_t* p, int n) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const uint32_t* wp = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-  const unsigned off = (unsigned)(a & 3);
-  uint64_t v = wp[0];
-  if (off + (unsigned)n > 4) v |= (uint64_t)wp[1] << 32;
-  return v >> (off * 8);
-}
-__device__ __forceinline__ float clip01(float v) {
-  v = v < 0.f ? 0.f : v;      // max(v, 0) then min(v, 1)
-  return v > 1.f ? 1.f : v;
-}
-}  // namespace
-
-// The two cuts of frame_u8_to_tiles_kernel on a 4:2:0 frame batch: p.src points at bytes, frame b at b * H * W * 3 / 2, its Y plane
-// [H][W] first, then Cb [H/2][W/2] and Cr [H/2][W/2] (I420) or CbCr [H/2][W/2][2] (NV12).  thread = four pixels (twelve floats) of one row
-// of the tile buffer.  Pixel (fy, fx) of the FRAME takes the chroma sample (fy >> 1, fx >> 1): origins and patch sizes may be odd, so
-// the pairing follows the frame coordinate.  A group wholly inside the tile's content reads its four Y bytes and its two or three chroma
-// samples per plane as aligned 32-bit words (load_bytes_aligned); a group that touches the padding or the row's end goes byte by byte.
-template <bool OVERLAP, bool NV12>
-__global__ __launch_bounds__(256) void frame_yuv420_to_tiles_kernel(TileMapParams p, YuvTables tab) {
-  __shared__ float ly[256], lc[256];
-  ly[threadIdx.x] = tab.y[threadIdx.x];
-  lc[threadIdx.x] = tab.c[threadIdx.x];
-  __syncthreads();
-  const int row = p.TW * 3;
-  const int groups = (p.TW + 3) / 4;
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= (int64_t)p.ntiles * p.TH * groups) return;
-  const int xp0 = (int)(g % groups) * 4;      // first pixel of the group in the tile row
-  const int64_t r = g / groups;               // row of the tile buffer
-  const int y = (int)(r % p.TH);
-  const int n = (int)(r / p.TH) + p.tile0;
-  const int b = n / (p.bh * p.bw), t = n % (p.bh * p.bw);
-  const int ty = t / p.bw, tx = t % p.bw;
-  const int ch = OVERLAP ? p.eh : p.ph, cw = OVERLAP ? p.ew : p.pw;   // the tile's content: rows, pixels per row
-  const int sy = y - p.oy, s0 = xp0 - p.ox;                           // content row, content pixel of the group's first pixel
-  float v[12];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) v[j] = 0.f;   // tf.image.pad_to_bounding_box pads with zeros
-  if (sy >= 0 && sy < ch && s0 + 4 > 0 && s0 < cw) {
-    const int fy = (OVERLAP ? film_tile_origin(ty, p.ph, p.ovy, p.H, p.eh) : ty * p.ph) + sy;
-    const int fx = (OVERLAP ? film_tile_origin(tx, p.pw, p.ovx, p.W, p.ew) : tx * p.pw) + s0;   // frame column of the group's first pixel
-    const int64_t plane = (int64_t)p.H * p.W;
-    const uint8_t* yrow = reinterpret_cast<const uint8_t*>(p.src) + (int64_t)b * (plane + plane / 2) + (int64_t)fy * p.W;
-    const uint8_t* frame0 = yrow - (int64_t)fy * p.W;
-    const int hw = p.W >> 1;
-    // NV12: one row of Cb Cr pairs; I420: a Cb row and, H/2 * W/2 bytes further on, the Cr row
-    const uint8_t* crow = frame0 + plane + (int64_t)(fy >> 1) * (NV12 ? p.W : hw);
-    const int64_t cr_off = NV12 ? 1 : plane / 4;
-    uint32_t yb[4], cbb[4], crb[4];
-    bool have[4];
-    if (s0 >= 0 && s0 + 4 <= cw) {
-      const uint32_t yw = (uint32_t)load_bytes_aligned(yrow + fx, 4);
-      const int c0 = fx >> 1, nc = ((fx + 3) >> 1) - c0 + 1;      // two chroma samples per plane, three from an odd column
-      uint32_t cbs[3], crs[3];
-      if (NV12) {
-        const uint64_t w = load_bytes_aligned(crow + 2 * c0, 2 * nc);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { cbs[k] = (uint32_t)(w >> (16 * k)) & 255u; crs[k] = (uint32_t)(w >> (16 * k + 8)) & 255u; }
-      } else {
-        const uint32_t wb = (uint32_t)load_bytes_aligned(crow + c0, nc), wr = (uint32_t)load_bytes_aligned(crow + cr_off + c0, nc);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { cbs[k] = (wb >> (8 * k)) & 255u; crs[k] = (wr >> (8 * k)) & 255u; }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int k = ((fx + j) >> 1) - c0;
-        yb[j] = (yw >> (8 * j)) & 255u;
-        cbb[j] = k == 0 ? cbs[0] : k == 1 ? cbs[1] : cbs[2];
-        crb[j] = k == 0 ? crs[0] : k == 1 ? crs[1] : crs[2];
-        have[j] = true;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        have[j] = s0 + j >= 0 && s0 + j < cw;
-        yb[j] = cbb[j] = crb[j] = 0;
-        if (have[j]) {
-          const int c = (fx + j) >> 1;
-          yb[j] = yrow[fx + j];
-          cbb[j] = NV12 ? crow[2 * c] : crow[c];
-          crb[j] = NV12 ? crow[2 * c + 1] : crow[cr_off + c];
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (!have[j]) continue;
-      const float yv = ly[yb[j]], cb = lc[cbb[j]], cr = lc[crb[j]];
-      v[3 * j] = clip01(yv + tab.a_r * cr);
-      v[3 * j + 1] = clip01((yv - tab.g_b * cb) - tab.g_r * cr);
-      v[3 * j + 2] = clip01(yv + tab.a_b * cb);
-    }
-  }
-  const int xc0 = xp0 * 3;
-  float* d = p.dst + r * row + xc0;
-  if (xc0 + 12 <= row && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(d)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 12; ++j)
-      if (xc0 + j < row) d[j] = v[j];
-  }
-}
-
-// float32 frame [H][W][3] -> the planes of one 4:2:0 frame (film_to_yuv420; the quantisation of a 4:2:0 stream's push).  thread = 2 rows x
-// 8 pixels: sixteen Y bytes and four chroma samples per plane, which leave as whole 32-bit words (two per Y row; one each for Cb and Cr,
-// or two of CbCr pairs) where the block is complete and the address allows, byte by byte otherwise.  H and W are even.
-template <bool NV12>
-__global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, int H, int W, YuvTables tab) {
-  const int bpr = (W + 7) / 8;      // blocks per row pair
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (int64_t)(H / 2) * bpr) return;
-  const int x0 = (int)(i % bpr) * 8, y0 = (int)(i / bpr) * 2;
-  const int np = min(8, W - x0);    // pixels of the block per row: even
-  auto q = [](float v) -> uint32_t {
-    v = v < 0.f ? 0.f : v;
-    v = v > 255.f ? 255.f : v;
-    return (uint32_t)(v + 0.5f);
-  };
-  uint32_t yq[2][8], cbq[4], crq[4];
-  float cbf[2][8], crf[2][8];
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy) {
-    const float* s = src + ((int64_t)(y0 + dy) * W + x0) * 3;
-    float px[24];
-    if (np == 8 && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const float4 f = reinterpret_cast<const float4*>(s)[k];
-        px[4 * k] = f.x; px[4 * k + 1] = f.y; px[4 * k + 2] = f.z; px[4 * k + 3] = f.w;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 24; ++k) px[k] = k < np * 3 ? s[k] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float R = clip01(px[3 * j]), G = clip01(px[3 * j + 1]), B = clip01(px[3 * j + 2]);
-      const float Yf = (tab.kr * R + tab.kg * G) + tab.kb * B;
-      cbf[dy][j] = (B - Yf) * tab.s_b;
-      crf[dy][j] = (R - Yf) * tab.s_r;
-      yq[dy][j] = q(Yf * tab.y_scale + tab.y_off);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float mb = ((cbf[0][2 * k] + cbf[0][2 * k + 1]) + (cbf[1][2 * k] + cbf[1][2 * k + 1])) * 0.25f;
-    const float mr = ((crf[0][2 * k] + crf[0][2 * k + 1]) + (crf[1][2 * k] + crf[1][2 * k + 1])) * 0.25f;
-    cbq[k] = q(mb * tab.c_scale + 128.f);
-    crq[k] = q(mr * tab.c_scale + 128.f);
-  }
-  const int64_t plane = (int64_t)H * W;
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy) {
-    uint8_t* d = dst + (int64_t)(y0 + dy) * W + x0;
-    if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
-      reinterpret_cast<uint32_t*>(d)[0] = yq[dy][0] | (yq[dy][1] << 8) | (yq[dy][2] << 16) | (yq[dy][3] << 24);
-      reinterpret_cast<uint32_t*>(d)[1] = yq[dy][4] | (yq[dy][5] << 8) | (yq[dy][6] << 16) | (yq[dy][7] << 24);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (j < np) d[j] = (uint8_t)yq[dy][j];
-    }
-  }
-  if (NV12) {
-    uint8_t* d = dst + plane + (int64_t)(y0 >> 1) * W + x0;
-    if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
-      reinterpret_cast<uint32_t*>(d)[0] = cbq[0] | (crq[0] << 8) | (cbq[1] << 16) | (crq[1] << 24);
-      reinterpret_cast<uint32_t*>(d)[1] = cbq[2] | (crq[2] << 8) | (cbq[3] << 16) | (crq[3] << 24);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (2 * k < np) { d[2 * k] = (uint8_t)cbq[k]; d[2 * k + 1] = (uint8_t)crq[k]; }
-    }
-  } else {
-    uint8_t* db = dst + plane + (int64_t)(y0 >> 1) * (W >> 1) + (x0 >> 1);
-    uint8_t* dr = db + plane / 4;
-    if (np == 8 && (reinterpret_cast<uintptr_t>(db) & 3) == 0 && (reinterpret_cast<uintptr_t>(dr) & 3) == 0) {
-      *reinterpret_cast<uint32_t*>(db) = cbq[0] | (cbq[1] << 8) | (cbq[2] << 16) | (cbq[3] << 24);
-      *reinterpret_cast<uint32_t*>(dr) = crq[0] | (crq[1] << 8) | (crq[2] << 16) | (crq[3] << 24);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (2 * k < np) { db[k] = (uint8_t)cbq[k]; dr[k] = (uint8_t)crq[k]; }
-    }
-  }
-}
-
-// Cross-fade weight (before normalisation) of tile i of an axis at frame position y: the distance to the nearest INTERIOR edge of
-// the tile, counted from 1; an edge on the frame's border does not limit it; 0 outside the tile.  *s = the tile's origin.
-__device__ __forceinline__ float fade_weight(int i, int y, int nb, int p, int o, int n, int e, int* s) {
-  if (i < 0 || i >= nb) return 0.f;
-  *s = film_tile_origin(i, p, o, n, e);
-  if (y < *s || y >= *s + e) return 0.f;
-  int a = 1 << 30;
-  if (*s > 0) a = min(a, y - *s + 1);
-  if (*s + e < n) a = min(a, *s + e - y);
-  return (float)a;
-}
-
-// thread = one float of rows [y0, y0 + ny) of frames [b0, b0 + nfr).  A pixel of block (ky, kx) is covered by tiles of the block
-// rows ky - 1 .. ky + 1 and columns kx - 1 .. kx + 1 only (2 * overlap <= patch).  Over the covering tiles in row-major order:
-// acc = (wy * wx) * v for the first, acc = acc + (wy * wx) * v for the others, wy = a_i(y) / sum_i a_i(y) (one float32 operation
-// each, no fma: this file is built with -ffp-contract=off).  Covering tiles below tile0 were added by an earlier launch - the sum
-// goes on from dst; tiles from tile0 + ntiles on are left to a later one.
-__global__ __launch_bounds__(256) void blend_tiles_kernel(TileMapParams p, int b0, int nfr, int y0, int ny) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int row = p.W * 3;
-  if (i >= (int64_t)nfr * ny * row) return;
-  const int xc = (int)(i % row);
-  const int64_t r = i / row;
-  const int y = y0 + (int)(r % ny);
-  const int b = b0 + (int)(r / ny);
-  const int x = xc / 3, c = xc - 3 * x;
-  const int ky = y / p.ph, kx = x / p.pw;
-  float ay[3], ax[3];
-  int sy[3] = {0, 0, 0}, sx[3] = {0, 0, 0};
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    ay[d] = fade_weight(ky - 1 + d, y, p.bh, p.ph, p.ovy, p.H, p.eh, &sy[d]);
-    ax[d] = fade_weight(kx - 1 + d, x, p.bw, p.pw, p.ovx, p.W, p.ew, &sx[d]);
-  }
-  const float sum_y = (ay[0] + ay[1]) + ay[2], sum_x = (ax[0] + ax[1]) + ax[2];   // (integers below 2^31: exact)
-  const int64_t o = (((int64_t)b * p.H + y) * p.W) * 3 + xc;
-  const int first = b * p.bh * p.bw;
-  float acc = 0.f;
-  bool have = false, mine = false;
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy) {
-    if (ay[dy] == 0.f) continue;
-    const float wy = ay[dy] / sum_y;
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      if (ax[dx] == 0.f) continue;
-      const int n = first + (ky - 1 + dy) * p.bw + (kx - 1 + dx);
-      if (n >= p.tile0 + p.ntiles) continue;
-      if (n < p.tile0) {
-        if (!have) { acc = p.dst[o]; have = true; }
-        continue;
-      }
-      const float w = wy * (ax[dx] / sum_x);
-      const float v = p.src[(((int64_t)(n - p.tile0) * p.TH + p.oy + (y - sy[dy])) * p.TW + p.ox + (x - sx[dx])) * 3 + c];
-      const float t = w * v;
-      acc = have ? acc + t : t;
-      have = true; mine = true;
-    }
-  }
-  if (mine) p.dst[o] = acc;
-}
-
-hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(frame_to_tiles_overlap_kernel, dim3(blocks_for((int64_t)p.ntiles * p.TH * p.TW * 3)), dim3(256), 0, s, p);
-  return hipGetLastError();
-}
-
-hipError_t film_launch_blend_tiles(const TileMapParams& p, hipStream_t s) {
-  if (p.ntiles <= 0) return hipSuccess;
-  // the frames the tile range touches; within one frame only the rows of its block rows
-  const int T = p.bh * p.bw, last = p.tile0 + p.ntiles - 1;
-  const int b0 = p.tile0 / T, nfr = last / T - b0 + 1;
-  int y0 = 0, y1 = p.H;
-  if (nfr == 1) {
-    y0 = film_tile_origin((p.tile0 % T) / p.bw, p.ph, p.ovy, p.H, p.eh);
-    y1 = film_tile_origin((last % T) / p.bw, p.ph, p.ovy, p.H, p.eh) + p.eh;
-  }
-  hipLaunchKernelGGL(blend_tiles_kernel, dim3(blocks_for((int64_t)nfr * (y1 - y0) * p.W * 3)), dim3(256), 0, s, p, b0, nfr, y0, y1 - y0);
-  return hipGetLastError();
-}
-
-hipError_t film_launch_frame_to_tiles(const TileMapParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(frame_to_tiles_kernel, dim3(blocks_for((int64_t)p.ntiles * p.TH * p.TW * 3)), dim3(256), 0, s, p);
-  return hipGetLastError();
-}
-
-namespace {
-template <bool OVERLAP> hipError_t launch_frame_u8_to_tiles(TileMapParams p, const uint8_t* src, hipStream_t s) {
-  static const U8Table tab = [] {
-    U8Table t;
-    for (int i = 0; i < 256; ++i) t.v[i] = (float)i / 255.0f;
-    return t;
-  }();
-  if (p.ntiles <= 0) return hipSuccess;
-  p.src = reinterpret_cast<const float*>(src);
-  const int64_t groups = (int64_t)p.ntiles * p.TH * ((p.TW * 3 + 11) / 12);
-  hipLaunchKernelGGL(frame_u8_to_tiles_kernel<OVERLAP>, dim3(blocks_for(groups)), dim3(256), 0, s, p, tab);
-  return hipGetLastError();
-}
-}  // namespace
-
-hipError_t film_launch_frame_to_tiles_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s) { return launch_frame_u8_to_tiles<false>(p, src, s); }
-hipError_t film_launch_frame_to_tiles_overlap_u8(const TileMapParams& p, const uint8_t* src, hipStream_t s) { return launch_frame_u8_to_tiles<true>(p, src, s); }
-
-namespace {
-// The tables of one colour setting (include/film_hip.h, "The 4:2:0 arithmetic"): built once per setting, on the host.
-YuvTables make_yuv_tables(bool bt601, bool full) {
-  YuvTables t;
-  const double Kr = bt601 ? 0.299 : 0.2126, Kb = bt601 ? 0.114 : 0.0722, Kg = 1.0 - Kr - Kb;
-  for (int i = 0; i < 256; ++i) {
-    t.y[i] = full ? (float)i / 255.0f : ((float)i - 16.0f) / 219.0f;
-    t.c[i] = ((float)i - 128.0f) / (full ? 255.0f : 224.0f);
-  }
-  t.a_r = (float)(2.0 * (1.0 - Kr)); t.a_b = (float)(2.0 * (1.0 - Kb));
-  t.g_b = (float)(2.0 * Kb * (1.0 - Kb) / Kg); t.g_r = (float)(2.0 * Kr * (1.0 - Kr) / Kg);
-  t.kr = (float)Kr; t.kg = (float)Kg; t.kb = (float)Kb;
-  t.s_b = (float)(0.5 / (1.0 - Kb)); t.s_r = (float)(0.5 / (1.0 - Kr));
-  t.y_scale = full ? 255.0f : 219.0f; t.y_off = full ? 0.0f : 16.0f; t.c_scale = full ? 255.0f : 224.0f;
-  return t;
-}
-const YuvTables& yuv_tables(bool bt601, bool full) {
-  static const YuvTables all[4] = {make_yuv_tables(false, false), make_yuv_tables(false, true), make_yuv_tables(true, false), make_yuv_tables(true, true)};
-  return all[(bt601 ? 2 : 0) + (full ? 1 : 0)];
-}
-}  // namespace
-
-hipError_t film_launch_yuv420_to_tiles(TileMapParams p, const uint8_t* src, bool nv12, bool bt601, bool full, hipStream_t s) {
-  if (p.ntiles <= 0) return hipSuccess;
-  if ((p.H | p.W) & 1) return hipErrorInvalidValue;
-  p.src = reinterpret_cast<const float*>(src);
-  const YuvTables& tab = yuv_tables(bt601, full);
-  const dim3 grid(blocks_for((int64_t)p.ntiles * p.TH * ((p.TW + 3) / 4))), block(256);
-  const bool ov = (p.ovy | p.ovx) != 0;
-  if (ov && nv12) hipLaunchKernelGGL((frame_yuv420_to_tiles_kernel<true, true>), grid, block, 0, s, p, tab);
-  else if (ov) hipLaunchKernelGGL((frame_yuv420_to_tiles_kernel<true, false>), grid, block, 0, s, p, tab);
-  else if (nv12) hipLaunchKernelGGL((frame_yuv420_to_tiles_kernel<false, true>), grid, block, 0, s, p, tab);
-  else hipLaunchKernelGGL((frame_yuv420_to_tiles_kernel<false, false>), grid, block, 0, s, p, tab);
-  return hipGetLastError();
-}
-
-hipError_t film_launch_rgb_to_yuv420(const float* src, uint8_t* dst, int H, int W, bool nv12, bool bt601, bool full, hipStream_t s) {
-  if (H <= 0 || W <= 0 || ((H | W) & 1)) return hipErrorInvalidValue;
-  const YuvTables& tab = yuv_tables(bt601, full);
-  const dim3 grid(blocks_for((int64_t)(H / 2) * ((W + 7) / 8))), block(256);
-  if (nv12) hipLaunchKernelGGL(rgb_to_yuv420_kernel<true>, grid, block, 0, s, src, dst, H, W, tab);
-  else hipLaunchKernelGGL(rgb_to_yuv420_kernel<false>, grid, block, 0, s, src, dst, H, W, tab);
-  return hipGetLastError();
-}
-
-hipError_t film_launch_tiles_to_frame(const TileMapParams& p, hipStream_t s) {
-  hipLaunchKernelGGL(tiles_to_frame_kernel, dim3(blocks_for((int64_t)p.ntiles * p.ph * p.pw * 3)), dim3(256), 0, s, p);
-  return hipGetLastError();
-}
-
-hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(to_uint8_kernel, dim3(blocks_for((n + 3) / 4)), dim3(256), 0, s, src, dst, n);
   return hipGetLastError();
 }
 

@@ -66,7 +66,7 @@ def test_designed_data():
 
 # every kernel instance and branch that the cases together must reach (names: tile_map_ref.branches)
 ALL_BRANCHES = {
-    'frame_to_tiles_kernel', 'frame_to_tiles_overlap_kernel', 'frame_u8_to_tiles_kernel<false>', 'frame_u8_to_tiles_kernel<true>',
+    'frame_to_tiles_kernel<false>', 'frame_to_tiles_kernel<true>', 'frame_u8_to_tiles_kernel<false>', 'frame_u8_to_tiles_kernel<true>',
     'tiles_to_frame_kernel', 'blend_tiles_kernel',
     'u8 fast path, aligned words', 'u8 fast path, shifted words', 'u8 byte path', 'u8 padding group',
     'u8 vector stores', 'u8 scalar stores, partial group', 'u8 scalar stores, unaligned group',
@@ -194,8 +194,20 @@ def test_tile_map_entry_point_is_declared_exported_and_refuses():
     mapfile = open(os.path.join(ROOT, 'frame-interpolation_amd', 'csrc', 'film_hip.map')).read()
     assert re.search(r'\bfilm_debug_tile_map;', mapfile) and 'film_debug_tile_map' in engine.EXPORTED_SYMBOLS
     assert engine.load_library().film_debug_tile_map is not None
-    src = open(os.path.join(ROOT, 'frame-interpolation_amd', 'csrc', 'film_engine.cpp')).read()
-    assert src.count('film_launch_frame_to_tiles_overlap_u8(') == 1 and src.count('film_launch_frame_to_tiles_u8(') == 1      # ONE dispatch
+    # ONE dispatch: the five cut launchers of old are gone from csrc/, and in frame_kernels.hip only film_launch_cut_tiles launches a cut kernel
+    csrc = os.path.join(ROOT, 'frame-interpolation_amd', 'csrc')
+    old = ('film_launch_frame_to_tiles', 'film_launch_frame_to_tiles_overlap', 'film_launch_frame_to_tiles_u8',
+           'film_launch_frame_to_tiles_overlap_u8', 'film_launch_yuv420_to_tiles')
+    for name in sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))):
+        text = open(os.path.join(csrc, name)).read()
+        assert not [o for o in old if re.search(r'\b' + o + r'\b', text)], name
+    src = open(os.path.join(csrc, 'frame_kernels.hip')).read()
+    assert src.count('hipLaunchKernelGGL(') == 1 and '<<<' not in src          # launch_units, behind the kernels, is how this file launches
+    cut_kernel = r'\bframe_(?:u8_|yuv420_)?to_tiles_kernel\b'
+    host = re.split(r'^(?=hipError_t film_launch_\w+\()', src[src.index('hipLaunchKernelGGL('):], flags=re.M)
+    named = {re.match(r'hipError_t (\w+)\(', f).group(1): len(re.findall(cut_kernel, f)) for f in host[1:]}
+    assert named == {'film_launch_cut_tiles': 2 + 2 + 4, 'film_launch_join_tiles': 0, 'film_launch_to_uint8': 0, 'film_launch_rgb_to_yuv420': 0}
+    assert not re.search(cut_kernel, host[0])
 
     eng = FilmEngine(TINY, device=-1)
     lib, h = eng._lib, eng._h

@@ -1,5 +1,5 @@
-"""GPU tests of the kernels that move pixels between frames and tiles (csrc/misc_kernels.hip: frame_to_tiles_kernel,
-frame_to_tiles_overlap_kernel, frame_u8_to_tiles_kernel<false / true>, tiles_to_frame_kernel, blend_tiles_kernel), each launched ALONE
+"""GPU tests of the kernels that move pixels between frames and tiles (csrc/frame_kernels.hip: frame_to_tiles_kernel<false / true>,
+frame_u8_to_tiles_kernel<false / true>, tiles_to_frame_kernel, blend_tiles_kernel), each launched ALONE
 through film_debug_tile_map on designed data: torch device tensors with guard bands, distinct finite floats of both signs and two
 magnitudes (every byte value in every channel for the 8-bit frames), against the numpy restatement tests/tile_map_ref.py.  Every
 comparison is on the bits: the cuts and the plain join are copies, the 8-bit cut a table lookup, the blend a fixed sequence of float32
@@ -110,7 +110,7 @@ def test_one_plan_serves_two_frame_sizes_with_other_pad_offsets():
         want = fresh.interpolate_frames(b0, b1, align=64, block_shape=(2, 2))
         assert np.isfinite(first).all() and np.isfinite(second).all()
         assert np.array_equal(second.view(np.uint32), want.view(np.uint32)), float(np.abs(second - want).max())
-        # and back, on the chunked path this time (cut_tiles / join_tiles instead of the host pipeline's own launches): the first size on
+        # and back, on the chunked path this time (run_chunk's cuts and joins instead of the host pipeline's own): the first size on
         # the plan the second one used, then the second again
         both.set_option('host_overlap', 0)
         again = both.interpolate_frames(a0, a1, align=64, block_shape=(2, 2))

@@ -1,4 +1,4 @@
-"""Numpy restatement of the frame <-> tile kernels (csrc/misc_kernels.hip: frame_to_tiles_kernel, frame_to_tiles_overlap_kernel,
+"""Numpy restatement of the frame <-> tile kernels (csrc/frame_kernels.hip: frame_to_tiles_kernel<false / true>,
 frame_u8_to_tiles_kernel<false / true>, tiles_to_frame_kernel, blend_tiles_kernel) and the comparison that tests/test_tile_map_gpu.py
 runs film_debug_tile_map through.  The arithmetic is specified to the bit (include/film_hip.h, "block_overlap_h"; the comment above
 blend_tiles_kernel), so every comparison here is on uint32 views.
@@ -390,7 +390,7 @@ def branches(case, geo, mode, u8, tile0, ntiles):
     ov = bool(g.ovy | g.ovx)
     out = set()
     if mode == 'cut' and not u8:
-        out.add('frame_to_tiles_overlap_kernel' if ov else 'frame_to_tiles_kernel')
+        out.add(f'frame_to_tiles_kernel<{"true" if ov else "false"}>')
     elif mode == 'cut':
         out.add(f'frame_u8_to_tiles_kernel<{"true" if ov else "false"}>')
         row = g.TW * 3

@@ -1,6 +1,6 @@
 """Numpy restatement of the 8-bit Y'CbCr 4:2:0 arithmetic of include/film_hip.h ("The 4:2:0 arithmetic"): the per-byte tables, the
-conversion in (bytes -> float32 RGB, what frame_yuv420_to_tiles_kernel fuses into the tile cut), the conversion out (float32 RGB ->
-bytes, rgb_to_yuv420_kernel), I420 <-> NV12, and the cut of a 4:2:0 frame batch into tiles over the geometry film_tiling_json reports.
+conversion in (bytes -> float32 RGB, what frame_yuv420_to_tiles_kernel of csrc/frame_kernels.hip fuses into the tile cut), the conversion
+out (float32 RGB -> bytes, rgb_to_yuv420_kernel there), I420 <-> NV12, and the cut of a 4:2:0 frame batch into tiles over the geometry film_tiling_json reports.
 Every operation is float32 with one rounding (numpy does not fuse), so every comparison against the kernels is on the bits.
 
 A frame is a uint8 array [H * 3 // 2, W]: rows [0, H) are the Y plane; the H * W / 2 bytes behind it are Cb [H/2][W/2] then

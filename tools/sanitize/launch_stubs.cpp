@@ -14,13 +14,10 @@ STUB(hipError_t film_launch_flow_up(const FlowUpParams&, hipStream_t))
 STUB(hipError_t film_launch_flow_add(const FlowAddParams&, hipStream_t))
 STUB(hipError_t film_launch_warp(const WarpParams&, hipStream_t))
 STUB(hipError_t film_launch_pack_flow(const PackFlowParams&, hipStream_t))
-STUB(hipError_t film_launch_frame_to_tiles(const TileMapParams&, hipStream_t))
-STUB(hipError_t film_launch_tiles_to_frame(const TileMapParams&, hipStream_t))
-STUB(hipError_t film_launch_frame_to_tiles_overlap(const TileMapParams&, hipStream_t))
-STUB(hipError_t film_launch_frame_to_tiles_u8(const TileMapParams&, const uint8_t*, hipStream_t))
-STUB(hipError_t film_launch_frame_to_tiles_overlap_u8(const TileMapParams&, const uint8_t*, hipStream_t))
-STUB(hipError_t film_launch_blend_tiles(const TileMapParams&, hipStream_t))
+STUB(hipError_t film_launch_cut_tiles(const TileMapParams&, int, hipStream_t))
+STUB(hipError_t film_launch_join_tiles(const TileMapParams&, hipStream_t))
 STUB(hipError_t film_launch_to_uint8(const float*, uint8_t*, int64_t, hipStream_t))
+STUB(hipError_t film_launch_rgb_to_yuv420(const float*, uint8_t*, int, int, int, hipStream_t))
 STUB(hipError_t film_launch_fill_random(float*, int64_t, uint32_t, hipStream_t))
 // metrics_kernels.hip (film_image_metrics refuses a plan-only handle before it reaches either)
 STUB(void film_metrics_layout(MetricsParams&))
