@@ -61,6 +61,7 @@ constexpr OptionRow kOptions[] = {
     {"host_overlap", &film_t::opt_host_overlap, BOOL, false},
     {"block_overlap_h", &film_t::opt_block_overlap_h, AS_IS, false, -1, 65535, "block_overlap_h: -1 (what the align padding of a tile holds) or 0 .. 65535 rows"},
     {"block_overlap_w", &film_t::opt_block_overlap_w, AS_IS, false, -1, 65535, "block_overlap_w: -1 (what the align padding of a tile holds) or 0 .. 65535 columns"},
+    {"scene_cut", &film_t::opt_scene_cut, AS_IS, false, 0, 1000, "scene_cut: 0 (off) or 1 .. 1000 permille of the histogram distance"},
     {"tune_ms", &film_t::opt_tune_ms, NONNEG, false},
     {"splitk", &film_t::opt_splitk, BOOL, true},
     {"pack_groups", nullptr, AS_IS, false, 1, 4, "pack_groups: 1 .. 4"},
@@ -331,8 +332,9 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
 // The stream's device buffers go back and it is closed.  Work that may still use them is the caller's to wait for.
 void stream_free(film_t* h) {
   FilmStream& fs = h->fs;
-  for (void* p : {fs.keep, (void*)fs.result, (void*)fs.result8})
+  for (void* p : {fs.keep, (void*)fs.result, (void*)fs.result8, (void*)fs.hist_dev})
     if (p) (void)hipFree(p);
+  if (fs.hist_pin) (void)hipHostFree(fs.hist_pin);
   fs = FilmStream{};
 }
 // what of a TileMapParams tile_geometry decides: the same values cut the same tiles
@@ -347,6 +349,29 @@ hipError_t stream_cut(const FilmStream& fs, TileMapParams tp, const Plan* P, int
   tp.src = (const float*)fs.keep;
   tp.dst = P->at("img0") + (int64_t)slot * tp.ntiles * tp.TH * tp.TW * 3;
   return film_launch_cut_tiles(tp, fs.pix, s);
+}
+
+// samples of one H x W frame of pixel type `pix` (S of "Scene cuts", include/film_hip.h)
+int64_t frame_samples(int pix, int H, int W) { return pix_is_yuv(pix) ? (int64_t)H * W * 3 / 2 : (int64_t)H * W * 3; }
+// Option "scene_cut" = k > 0: the histogram of the frame in fs.keep, taken on `s`, downloaded and waited for; *cut = the rule's verdict
+// against the carried histogram when the stream is primed and has one.  The new histogram becomes the carried one (valid once the push succeeds).
+int stream_scene_cut(film_t* h, hipStream_t s, int k, bool* cut) {
+  FilmStream& fs = h->fs;
+  constexpr size_t bytes = FILM_HIST_BINS * sizeof(uint32_t);
+  if (!fs.hist_dev) HIPCHK(h, hipMalloc((void**)&fs.hist_dev, bytes));
+  if (!fs.hist_pin) HIPCHK(h, hipHostMalloc((void**)&fs.hist_pin, bytes, hipHostMallocDefault));
+  HIPCHK(h, film_launch_frame_histogram(fs.keep, fs.H, fs.W, fs.pix, fs.hist_dev, s));
+  HIPCHK(h, hipMemcpyAsync(fs.hist_pin, fs.hist_dev, bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  if (fs.primed && fs.hist_valid) {
+    int64_t D = 0;
+    for (int i = 0; i < FILM_HIST_BINS; ++i) D += std::llabs((int64_t)fs.hist_pin[i] - (int64_t)fs.hist_prev[i]);
+    fs.cut_distance = D;
+    *cut = 1000 * D >= (int64_t)k * 2 * frame_samples(fs.pix, fs.H, fs.W);
+  }
+  fs.hist_valid = false;   // (until the push has succeeded)
+  std::copy(fs.hist_pin, fs.hist_pin + FILM_HIST_BINS, fs.hist_prev);
+  return FILM_OK;
 }
 
 // The plan film_debug_arena / film_debug_run_op work on ("Debug / tests" in include/film_hip.h: one planned launch on a workspace the caller controls)
@@ -395,6 +420,13 @@ extern "C" {
 int film_to_uint8(const float* src, unsigned char* dst, int64_t n, void* stream) {
   if (n < 0 || (n > 0 && (!src || !dst))) return FILM_ERR_INVALID;
   return film_launch_to_uint8(src, dst, n, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
+}
+
+int film_frame_histogram(const void* frame_dev, int H, int W, int pix, uint32_t* hist_dev, void* stream) {
+  if (!frame_dev || !hist_dev || H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31) || check_pix(nullptr, pix, H, W) != FILM_OK ||
+      (reinterpret_cast<uintptr_t>(frame_dev) & 3))
+    return FILM_ERR_INVALID;
+  return film_launch_frame_histogram(frame_dev, H, W, pix, hist_dev, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
 }
 
 int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream) {
@@ -695,6 +727,17 @@ int film_stream_reset(film_t* h) {
   if (!h) return FILM_ERR_INVALID;
   if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
   h->fs.primed = false;
+  h->fs.hist_valid = false;
+  return FILM_OK;
+}
+
+int film_stream_cut_info(film_t* h, int64_t* distance, int64_t* samples, int* cut) {
+  if (!h) return FILM_ERR_INVALID;
+  const FilmStream& fs = h->fs;
+  if (!fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  if (distance) *distance = fs.cut_distance;
+  if (samples) *samples = frame_samples(fs.pix, fs.H, fs.W);
+  if (cut) *cut = fs.cut;
   return FILM_OK;
 }
 
@@ -719,11 +762,13 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
     ~Unprime() {
       if (!armed) return;
       h->fs.primed = false;
+      h->fs.hist_valid = false;
       (void)hipStreamSynchronize(h->stream2);
       (void)hipStreamSynchronize(s);
     }
   } unprime{h, s, true};
   if (produced) *produced = 0;
+  fs.cut_distance = -1; fs.cut = 0;
   if (!frame || !produced || (fs.primed && !mid)) return fail(h, FILM_ERR_INVALID, "NULL argument");
   if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
   HIPCHK(h, hipSetDevice(h->device));
@@ -744,12 +789,17 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
     HIPCHK(h, stream_cut(fs, tp, R, fs.slot, s));
     if ((rc = run_plan(h, R, s, R->n_extract))) return rc;
   }
-  const int slot = fs.primed ? 1 - fs.slot : 0;
-  Plan* P = P0->orientation(slot);
   const size_t fb = frame_bytes(fs.pix, fs.H, fs.W);
   HIPCHK(h, hipMemcpyAsync(fs.keep, frame, fb, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  // option "scene_cut": a cut is film_stream_reset followed by this push - the frame starts a new scene in slot 0, extraction only
+  const int scene_k = h->opt_scene_cut;
+  bool cut = false;
+  if (scene_k > 0 && (rc = stream_scene_cut(h, s, scene_k, &cut))) return rc;
+  const bool primed = fs.primed && !cut;
+  const int slot = primed ? 1 - fs.slot : 0;
+  Plan* P = P0->orientation(slot);
   HIPCHK(h, stream_cut(fs, tp, P, slot, s));
-  if (!fs.primed) {
+  if (!primed) {
     if ((rc = run_plan(h, P, s, P->n_extract))) return rc;
   } else {
     if ((rc = run_plan(h, P, s))) return rc;
@@ -771,8 +821,9 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
     }
   }
   if (host) HIPCHK(h, hipStreamSynchronize(s));
-  *produced = fs.primed ? 1 : 0;
+  *produced = primed ? 1 : 0;
   fs.primed = true; fs.slot = slot; fs.plan_id = P0->id; fs.geo = tp;
+  fs.hist_valid = scene_k > 0; fs.cut = cut ? 1 : 0;
   unprime.armed = false;
   return FILM_OK;
 }

@@ -180,6 +180,13 @@ struct FilmStream {
   int slot = 0;                     // the half of the plan's frame buffers it was extracted into ...
   uint64_t plan_id = 0;             // ... of this plan (Plan::id) ...
   TileMapParams geo{};              // ... cut with this geometry (block_overlap_* may change between pushes)
+  // option "scene_cut" (include/film_hip.h, "Scene cuts"); the two buffers are allocated by the first push that needs them
+  uint32_t* hist_dev = nullptr;     // the 768 counters of the frame in `keep` ...
+  uint32_t* hist_pin = nullptr;     // ... downloaded here (pinned host memory)
+  uint32_t hist_prev[768] = {};     // the previous frame's histogram, on the host: a dropped plan does not touch it
+  bool hist_valid = false;          // hist_prev is the histogram of the frame in `keep`
+  int64_t cut_distance = -1;        // film_stream_cut_info: D of the last push (-1: no comparison made) ...
+  int cut = 0;                      // ... and whether it was treated as a cut
 };
 
 struct film_handle {
@@ -222,6 +229,7 @@ struct film_handle {
   // cross-faded over the shared pixels (tile_geometry in film_engine.cpp; blend_tiles_kernel).  0 (default): the reference's disjoint
   // patches.  -1: as much as the tile's align padding holds (the padded tile, and with it the plan, stays the same).
   int opt_block_overlap_h = 0, opt_block_overlap_w = 0;
+  int opt_scene_cut = 0;      // film_stream_push: permille of the histogram distance from which a pair of frames is a scene cut (0: off)
   int opt_host_overlap = 1;   // film_interpolate(FILM_MEM_HOST): 1 = the second frame's upload behind the first frame's first layers, the first half of the
                               // result downloaded behind the second half's last layer (film_engine.cpp, "host pipeline"); 0 = copies, then work, then copy
   hipEvent_t pipe_ev[2] = {nullptr, nullptr};   // its two events (second frame in place / first half stitched), lazily created

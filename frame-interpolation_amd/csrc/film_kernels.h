@@ -392,6 +392,15 @@ hipError_t film_launch_join_tiles(const TileMapParams& p, hipStream_t s);
 hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipStream_t s);
 // float32 [H][W][3] -> one 4:2:0 frame of H * W * 3 / 2 bytes (clip, matrix, 2 x 2 box mean of the chroma, quantisation)
 hipError_t film_launch_rgb_to_yuv420(const float* src, uint8_t* dst, int H, int W, int pix, hipStream_t s);
+// The sample histogram of one frame (include/film_hip.h, "Scene cuts"): hist[p * 256 + v] = the samples of plane p with 8-bit code v.  The launcher
+// zeroes the 768 counters first: a call overwrites.  `frame` is 4-byte aligned and its allocation a whole number of 32-bit words (as for the 8-bit
+// cuts).  A lane reads FILM_HIST_VEC_BYTES per step; the grid is min(what the frame needs, FILM_HIST_WG_PER_CU workgroups per compute unit) of
+// FILM_HIST_THREADS lanes with a grid-stride loop, so one pass of the full grid covers CUs * WG_PER_CU * THREADS * VEC_BYTES bytes.
+#define FILM_HIST_BINS 768
+#define FILM_HIST_THREADS 256
+#define FILM_HIST_WG_PER_CU 2
+#define FILM_HIST_VEC_BYTES 16
+hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix, uint32_t* hist, hipStream_t s);
 // fills n floats with a deterministic pseudo-random pattern in [-1, 1) (autotune inputs only)
 hipError_t film_launch_fill_random(float* dst, int64_t n, uint32_t seed, hipStream_t s);
 

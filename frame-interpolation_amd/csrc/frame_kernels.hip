@@ -1,5 +1,5 @@
 // frame_kernels.hip -- frame I/O: the kernels that move pixels between the caller's frames and the tiles a plan works on (gfx950, wave64).
-// None of them is an op of a plan; film_engine.cpp calls the four launchers at the end of this file.
+// None of them is an op of a plan; film_engine.cpp calls the four launchers at the end of this file and film_launch_frame_histogram, which stands beside its kernel.
 //
 //   frame_to_tiles<OVERLAP>             _pad_to_align + image_to_patches, float32 frames    eval/interpolator.py:30-63, :66-104
 //   frame_u8_to_tiles<OVERLAP>          the same on 8-bit RGB frames: float32(byte) / 255   eval/util.py read_image
@@ -8,6 +8,7 @@
 //   blend_tiles                         crop + cross-fade of overlapped tiles               include/film_hip.h, "block_overlap_h"
 //   to_uint8                            clip(x * 255, 0, 255) + 0.5, truncated              eval/util.py:51-52 (write_image)
 //   rgb_to_yuv420<NV12>                 float32 RGB -> the planes of one 4:2:0 frame        include/film_hip.h, "The 4:2:0 arithmetic"
+//   frame_histogram<LAYOUT>             3 x 256 counters of a frame's 8-bit sample codes    include/film_hip.h, "Scene cuts"
 //
 // OVERLAP: the tile's content is the patch grown by the overlap, from film_tile_origin (options "block_overlap_h" / "block_overlap_w").
 //
@@ -16,6 +17,10 @@
 #include "film_kernels.h"
 
 namespace {
+
+// how every kernel of this file is launched ("host", below)
+template <class... P, class... A>
+hipError_t launch_units(void (*kernel)(P...), int64_t units, hipStream_t s, const A&... args);
 
 // ---- what the cuts share -------------------------------------------------------------------------------------------------------
 // Row r of the tile buffer: its row y inside the padded tile, and the tile's frame b and block (ty, tx) of that frame.
@@ -419,8 +424,105 @@ __global__ __launch_bounds__(256) void blend_tiles_kernel(TileMapParams p, int b
   if (mine) p.dst[o] = acc;
 }
 
+// ---- the per-frame sample histogram (film_frame_histogram; include/film_hip.h, "Scene cuts") ----------------------------------------------
+// hist[p][v] += the samples of plane p with 8-bit code v, over the n elements of one frame: bytes (LAYOUT = FILM_PIX_U8 / I420 / NV12) or
+// floats (FILM_PIX_F32, whose code is film_to_uint8's byte).  `plane` = H * W, the bytes of the Y plane of a 4:2:0 frame.
+//   loads     The frame is walked in the ALIGNED 16-byte vectors that hold it, one vector per lane and step of a grid-stride loop: a
+//             vector that lies wholly inside the frame is one 16-byte load; the first vector of a frame that does not start on a 16-byte
+//             boundary and the last partial one are read as the 32-bit words that hold at least one element of the frame (the pointer is
+//             4-byte aligned, so only the last word can be partial: the allocation-in-whole-words contract of the 8-bit cuts), and count
+//             only the elements of the frame.
+//   planes    interleaved RGB: element index mod 3; I420: three consecutive ranges; NV12: the Y range, then Cb at even and Cr at odd offsets.
+//   counting  LDS integer atomics into HIST_COPIES sub-histograms per workgroup, laid out [bin][copy] with copy = lane & 7: eight
+//             neighbouring lanes never share an address, a flat picture (every lane on one bin) meets 8-way instead of 64-way same-address
+//             serialisation, and the copies of a bin lie in eight consecutive banks.
+//   flush     a workgroup adds its non-zero bins to the 768 global counters with integer atomicAdd: the sums do not depend on the grid or
+//             the arrival order.  hist is zeroed by the launcher.
+constexpr int HIST_COPIES = 8;
+template <int LAYOUT>
+__global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(const void* __restrict__ frame, int64_t n, int64_t plane, uint32_t* __restrict__ hist) {
+  constexpr bool F32 = LAYOUT == FILM_PIX_F32;
+  constexpr int EPV = F32 ? 4 : 16;   // elements per 16-byte vector
+  constexpr int EPW = EPV / 4;        // ... per 32-bit word
+  __shared__ uint32_t sub[FILM_HIST_BINS * HIST_COPIES];
+  for (int i = threadIdx.x; i < FILM_HIST_BINS * HIST_COPIES; i += FILM_HIST_THREADS) sub[i] = 0;
+  __syncthreads();
+  const uintptr_t a = reinterpret_cast<uintptr_t>(frame);
+  const uint4* base = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(frame) - (a & 15));   // (pointer arithmetic: the loads stay global loads)
+  const int head = (int)(a & 15) / (F32 ? 4 : 1);   // elements of vector 0 in front of the frame
+  const int64_t nvec = (head + n + EPV - 1) / EPV;
+  const int copy = threadIdx.x & (HIST_COPIES - 1);
+  for (int64_t v = (int64_t)blockIdx.x * FILM_HIST_THREADS + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * FILM_HIST_THREADS) {
+    const int64_t e0 = v * EPV - head;   // the frame element at position 0 of the vector (negative in the head)
+    const bool whole = e0 >= 0 && e0 + EPV <= n;
+    uint32_t w[4];
+    if (whole) {
+      const uint4 q = base[v];
+      w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+    } else {
+      const uint32_t* wp = reinterpret_cast<const uint32_t*>(base + v);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int64_t ek = e0 + k * EPW;   // word k holds elements [ek, ek + EPW)
+        w[k] = (ek + EPW > 0 && ek < n) ? wp[k] : 0u;
+      }
+    }
+    // what decides the plane of position j, as small integers
+    const int c0 = (int)(((uint32_t)v % 3u + (uint32_t)(18 - head)) % 3u);           // RGB: channel of position 0 = (EPV v - head) mod 3, EPV mod 3 = 1 (v < 2^29)
+    const int d1 = (int)min((int64_t)EPV, max((int64_t)0, plane - e0));              // 4:2:0: positions below d1 are Y ...
+    const int d2 = (int)min((int64_t)EPV, max((int64_t)0, plane + plane / 4 - e0));  // ... I420: below d2 Cb, from d2 on Cr
+    const int par = (int)((e0 - plane) & 1);                                         // NV12: parity of position 0 inside the CbCr plane
+#pragma unroll
+    for (int j = 0; j < EPV; ++j) {
+      if (!whole && (e0 + j < 0 || e0 + j >= n)) continue;
+      uint32_t code;
+      if (F32) code = quant255(__uint_as_float(w[j]) * 255.f) & 255u;   // film_to_uint8's operations (& 255: a NaN stays inside the bins)
+      else code = (w[j / 4] >> ((j & 3) * 8)) & 255u;
+      int p;
+      if (LAYOUT == FILM_PIX_I420) p = (j >= d1) + (j >= d2);
+      else if (LAYOUT == FILM_PIX_NV12) p = j < d1 ? 0 : 1 + ((par + j) & 1);
+      else { p = c0 + j % 3; p = p >= 3 ? p - 3 : p; }
+      atomicAdd(&sub[(p * 256 + (int)code) * HIST_COPIES + copy], 1u);
+    }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < FILM_HIST_BINS; b += FILM_HIST_THREADS) {
+    uint32_t sum = 0;
+#pragma unroll
+    for (int c = 0; c < HIST_COPIES; ++c) sum += sub[b * HIST_COPIES + c];
+    if (sum) atomicAdd(&hist[b], sum);
+  }
+}
+
+}  // namespace
+
+// One frame's histogram: zeroes the 768 counters, then counts.  At most FILM_HIST_WG_PER_CU workgroups per compute unit, fewer for a frame
+// that has fewer vectors; the grid-stride loop takes the rest.  (The launcher stands beside its kernel; launch_units: "host" below.)
+hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix, uint32_t* hist, hipStream_t s) {
+  const int layout = pix & 0xff;   // (the colour flags do not enter)
+  const bool yuv = layout == FILM_PIX_I420 || layout == FILM_PIX_NV12;
+  if (!frame || !hist || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(frame) & 3)) return hipErrorInvalidValue;
+  if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !yuv) return hipErrorInvalidValue;
+  if (yuv && ((H | W) & 1)) return hipErrorInvalidValue;
+  const int64_t plane = (int64_t)H * W, n = yuv ? plane + plane / 2 : plane * 3;
+  int dev = 0, cus = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e == hipSuccess) e = hipMemsetAsync(hist, 0, FILM_HIST_BINS * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  const int epv = layout == FILM_PIX_F32 ? 4 : 16;
+  const int64_t nvec = (n + epv - 1) / epv + 1;   // (+ 1: a frame that starts inside a vector)
+  const int64_t grid = std::min<int64_t>((int64_t)std::max(cus, 1) * FILM_HIST_WG_PER_CU, (nvec + FILM_HIST_THREADS - 1) / FILM_HIST_THREADS);
+  auto kernel = layout == FILM_PIX_F32 ? frame_histogram_kernel<FILM_PIX_F32> : layout == FILM_PIX_U8 ? frame_histogram_kernel<FILM_PIX_U8>
+              : layout == FILM_PIX_I420 ? frame_histogram_kernel<FILM_PIX_I420> : frame_histogram_kernel<FILM_PIX_NV12>;
+  static_assert(FILM_HIST_THREADS == 256, "launch_units starts workgroups of 256");
+  return launch_units(kernel, grid * FILM_HIST_THREADS, s, frame, n, plane, hist);   // `grid` workgroups
+}
+
+namespace {
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-// every kernel of this file: one thread per unit, 256 per workgroup
+// every other kernel of this file: one thread per unit, 256 per workgroup (frame_histogram_kernel: one workgroup per 256 units)
 template <class... P, class... A>
 hipError_t launch_units(void (*kernel)(P...), int64_t units, hipStream_t s, const A&... args) {
   hipLaunchKernelGGL(kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, args...);

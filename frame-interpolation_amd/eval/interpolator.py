@@ -172,16 +172,20 @@ class Interpolator:
     bs = self._block_shape if self._block_shape is not None and np.prod(self._block_shape) > 1 else None
     return self._engine.interpolate_sequence(frames, align=self._align, block_shape=bs)
 
-  def open_stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False):
+  def open_stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False, scene_cut: int = 0):
     """(extension) A frame stream of h x w frames (film_hip.engine.FilmStream; film_stream_*): push() one frame at a time and get
     the mid-frame between it and the one pushed before, bit-identical to self(previous, frame, dt) with align, block_shape and
     block_overlap as set, with one feature extraction per frame.  pix 'f32': float32 frames, not clipped; 'u8': uint8 frames in
     and util.to_uint8's bytes out; 'i420' / 'nv12': 8-bit Y'CbCr 4:2:0 frames as uint8 [h * 3 // 2, w] in and out, with the colour
-    `matrix` ('bt709' | 'bt601') and limited or full range.  One stream per Interpolator at a time."""
+    `matrix` ('bt709' | 'bt601') and limited or full range.  scene_cut (0 .. 1000 permille): non-zero sets the engine option "scene_cut"
+    (include/film_hip.h) before the stream opens - a push that the histogram rule calls a scene cut then returns None like a first push,
+    FilmStream.cut_info() tells why; an engine option like block_overlap, so it stays set; 0 (default) leaves the engine as it is.
+    One stream per Interpolator at a time."""
     if self._align is not None:
       assert self._align > 0, 'align must be a positive number.'
     bs = self._block_shape if self._block_shape is not None and np.prod(self._block_shape) > 1 else None
-    return self._engine.open_stream(h, w, align=self._align, block_shape=bs, pix=pix, matrix=matrix, full_range=full_range)
+    return self._engine.open_stream(h, w, align=self._align, block_shape=bs, pix=pix, matrix=matrix, full_range=full_range,
+                                    scene_cut=scene_cut)
 
   def __call__(self, x0: np.ndarray, x1: np.ndarray,
                dt: np.ndarray) -> np.ndarray:

@@ -7,6 +7,11 @@ per frame), no PNGs, no ffmpeg, a few frames of memory.
   python -m eval.video_cli --model_path <model dir> --input in.y4m --output out.y4m
   ffmpeg -i a.mp4 -f yuv4mpegpipe - | python -m eval.video_cli --model_path <model dir> --input - --output - | ffmpeg -i - b.mp4
 
+--scene_cut PERMILLE (default 0: off) lets the engine look for scene cuts (film_set_option "scene_cut", include/film_hip.h: the distance
+of consecutive frames' sample histograms, in permille of its maximum): across a cut no mid-frame is generated and the frame before the
+cut is written a second time instead (a frame hold), so the output keeps its 2 n - 1 frames at a uniform rate.  No value is recommended:
+the detector's hit and miss rates on real footage are unmeasured.
+
 The output header keeps the input's tokens with the frame rate (F) doubled.  What is read: film_hip/y4m.py (8-bit 4:2:0, progressive).
 """
 import argparse
@@ -33,20 +38,34 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--matrix', choices=['bt709', 'bt601'], default='bt709', help="The Y'CbCr matrix of the video.")
     ap.add_argument('--full_range', action='store_true', default=None,
                     help='Full-range samples (0..255); default: what the header says (XCOLORRANGE=FULL), else limited range.')
+    ap.add_argument('--scene_cut', type=int, default=0, metavar='PERMILLE',
+                    help='Treat a pair of frames whose histogram distance reaches this many permille (1..1000) as a scene cut: the frame '
+                         'before the cut is held instead of a mid-frame.  0 (default): off.  No value is recommended (unmeasured on footage).')
     return ap
 
 
-def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', full_range: Optional[bool] = None) -> int:
+def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', full_range: Optional[bool] = None, scene_cut: int = 0,
+                      cuts: Optional[list] = None) -> int:
     """Streams reader's frames through an I420 stream of `it` (an eval.interpolator.Interpolator) and writes the doubled video to the
-    binary file object `out`.  Returns the number of frames written.  One input frame and one mid-frame are alive at a time."""
+    binary file object `out`.  Returns the number of frames written.  One input frame and one mid-frame are alive at a time (two input
+    frames with scene_cut).  scene_cut > 0 (permille, engine option "scene_cut"): a push after the first that returns no mid-frame is
+    a scene cut - the previous input frame is written again in the mid-frame's place; `cuts` (a list) receives the index of every input
+    frame that starts a new scene."""
     full = reader.full_range if full_range is None else bool(full_range)
     writer = y4m.Y4MWriter(out, y4m.double_rate(reader.tokens))
-    with it.open_stream(reader.height, reader.width, pix='i420', matrix=matrix, full_range=full) as st:
-        for frame in reader:
+    with it.open_stream(reader.height, reader.width, pix='i420', matrix=matrix, full_range=full,
+                        **({'scene_cut': int(scene_cut)} if scene_cut else {})) as st:
+        prev = None
+        for i, frame in enumerate(reader):
             mid = st.push(frame)
             if mid is not None:
                 writer.write(mid)
+            elif scene_cut and prev is not None:
+                writer.write(prev)      # a frame hold across the cut
+                if cuts is not None:
+                    cuts.append(i)
             writer.write(frame)
+            prev = frame if scene_cut else None
     return writer.frames_written
 
 
@@ -60,7 +79,8 @@ def main(argv=None) -> int:
                                            **({'block_overlap': overlap} if any(overlap) else {}))
         fout = sys.stdout.buffer if args.output == '-' else open(args.output, 'wb')
         try:
-            n = double_frame_rate(it, reader, fout, args.matrix, args.full_range)
+            cuts = []
+            n = double_frame_rate(it, reader, fout, args.matrix, args.full_range, args.scene_cut, cuts)
             fout.flush()
         finally:
             if fout is not sys.stdout.buffer:
@@ -68,7 +88,8 @@ def main(argv=None) -> int:
     finally:
         if fin is not sys.stdin.buffer:
             fin.close()
-    print(f'{args.input}: {reader.frames_read} frames in, {n} frames out', file=sys.stderr)
+    print(f'{args.input}: {reader.frames_read} frames in, {n} frames out' +
+          (f', {len(cuts)} scene cuts' + (f' (the first at input frame {cuts[0]})' if cuts else '') if args.scene_cut else ''), file=sys.stderr)
     return n
 
 

@@ -72,7 +72,7 @@ EXPORTED_SYMBOLS = (
     'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json',
     'film_debug_arena', 'film_debug_run_op', 'film_debug_tile_map',
     'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json',
-    'film_to_yuv420', 'film_debug_yuv_cut')
+    'film_to_yuv420', 'film_debug_yuv_cut', 'film_frame_histogram', 'film_stream_cut_info')
 
 _lib = None
 
@@ -148,6 +148,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_stream_reset.argtypes = [vp]
     lib.film_stream_close.argtypes = [vp]
     lib.film_stream_plan_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
+    lib.film_frame_histogram.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+    lib.film_stream_cut_info.argtypes = [vp, i64p, i64p, ctypes.POINTER(ctypes.c_int)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ('film_destroy',):
@@ -186,12 +188,25 @@ def _cfg_struct(opt: Options) -> _Config:
     return c
 
 
+def frame_histogram_device(ptr: int, h: int, w: int, hist_ptr: int, pix: str = 'u8', matrix: str = 'bt709', full_range: bool = False,
+                           stream: Optional[int] = None) -> None:
+    """film_frame_histogram: the 3 x 256 sample histogram (include/film_hip.h, "Scene cuts") of ONE h x w device frame of pixel type `pix`
+    into 768 device uint32 at hist_ptr (overwritten), asynchronous on `stream` of the current device.  ptr must be 4-byte aligned and an
+    8-bit frame lie in an allocation of whole 32-bit words.  Needs no engine."""
+    rc = load_library().film_frame_histogram(ctypes.c_void_p(ptr), int(h), int(w), pix_code(pix, matrix, full_range), ctypes.c_void_p(hist_ptr),
+                                             ctypes.c_void_p(stream) if stream else None)
+    if rc != 0:
+        raise FilmError(rc, 'film_frame_histogram failed')
+
+
 class FilmStream:
     """One open frame stream of an engine (film_stream_*; FilmEngine.open_stream): push() one frame at a time and get the mid-frame
     between it and the frame pushed before - bit-identical to interpolate_frames(previous, frame) - with one feature extraction per
     frame.  Frames and results are [H,W,3] float32 ('f32') or uint8 ('u8': x = u8 / 255, result = eval.util.to_uint8's bytes), or
     8-bit Y'CbCr 4:2:0 frames ('i420', 'nv12') as uint8 [H * 3 // 2, W]: the Y plane, then the Cb and Cr planes (I420) or the plane of
     CbCr pairs (NV12), with `matrix` 'bt709' | 'bt601' and limited or full range (the arithmetic: include/film_hip.h).
+    With the engine option "scene_cut" > 0 (FilmEngine.open_stream(scene_cut=...)) a push that the histogram rule calls a scene cut returns
+    None / False like a first push, and cut_info() tells the two apart.
     One stream per engine at a time; use it as a context manager or close() it."""
 
     def __init__(self, engine: 'FilmEngine', h: int, w: int, align: Optional[int], block_shape, pix: str, matrix: str = 'bt709',
@@ -207,7 +222,8 @@ class FilmStream:
 
     def push(self, frame: np.ndarray, out: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
         """frame: host array of the stream's shape and dtype.  None for the first frame after open / reset, else the mid-frame
-        (a new array, or `out`: a writable C-contiguous array of the frame's shape and dtype)."""
+        (a new array, or `out`: a writable C-contiguous array of the frame's shape and dtype).  None too for a frame that option
+        "scene_cut" found to start a new scene (`out` is then left as it was)."""
         a = np.asarray(frame)
         if a.dtype != self.dtype or a.shape != self.shape:
             raise ValueError(f'expected a {np.dtype(self.dtype).name} array of shape {self.shape}, got {a.dtype} {a.shape}')
@@ -224,7 +240,8 @@ class FilmStream:
 
     def push_device(self, ptr_in: int, ptr_out: int, stream: Optional[int] = None) -> bool:
         """Device-resident push: raw device pointers to one frame of the stream's pixel type each, asynchronous on `stream`.
-        Returns whether ptr_out receives a mid-frame (False for the first frame after open / reset; ptr_out may then be 0)."""
+        Returns whether ptr_out receives a mid-frame (False for the first frame after open / reset; ptr_out may then be 0 - and for a
+        scene cut found by option "scene_cut", which leaves ptr_out untouched)."""
         produced = ctypes.c_int(0)
         eng = self._eng
         eng._check(eng._lib.film_stream_push(eng._h, ctypes.c_void_p(ptr_in), ctypes.c_void_p(ptr_out) if ptr_out else None,
@@ -234,6 +251,13 @@ class FilmStream:
     def reset(self) -> None:
         """Forgets the carried frame (scene cut, seek): the next push produces nothing."""
         self._eng._check(self._eng._lib.film_stream_reset(self._eng._h))
+
+    def cut_info(self) -> Tuple[int, int, int]:
+        """film_stream_cut_info: (distance, samples, cut) of the last push - the histogram distance D to the frame before (-1: no
+        comparison was made), the samples S of one frame, and 1 if the push was treated as a scene cut."""
+        d, n, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
+        self._eng._check(self._eng._lib.film_stream_cut_info(self._eng._h, ctypes.byref(d), ctypes.byref(n), ctypes.byref(c)))
+        return d.value, n.value, c.value
 
     def close(self) -> None:
         if self._open and getattr(self._eng, '_h', None) is not None and self._eng._h.value:
@@ -479,10 +503,20 @@ class FilmEngine:
                                                         ctypes.c_void_p(stream) if stream else None))
 
     def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32', matrix: str = 'bt709',
-                    full_range: bool = False) -> FilmStream:
+                    full_range: bool = False, scene_cut: int = 0) -> FilmStream:
         """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix 'f32' | 'u8' |
-        'i420' | 'nv12', the latter two (8-bit 4:2:0, h and w even) with the colour `matrix` 'bt709' | 'bt601' and limited or full range."""
+        'i420' | 'nv12', the latter two (8-bit 4:2:0, h and w even) with the colour `matrix` 'bt709' | 'bt601' and limited or full range.
+        scene_cut: 0 .. 1000 permille; non-zero sets the engine option "scene_cut" (include/film_hip.h) before the stream opens - a handle
+        option like block_overlap, so it STAYS set for later streams of this engine until set_option('scene_cut', 0); 0 (default) leaves
+        the engine as it is."""
+        if scene_cut:
+            self.set_option('scene_cut', int(scene_cut))
         return FilmStream(self, h, w, align, block_shape, pix, matrix, full_range)
+
+    def frame_histogram_device(self, ptr: int, h: int, w: int, hist_ptr: int, pix: str = 'u8', matrix: str = 'bt709', full_range: bool = False,
+                               stream: Optional[int] = None) -> None:
+        """film_frame_histogram on raw device pointers (the module function frame_histogram_device: the call needs no handle)."""
+        frame_histogram_device(ptr, h, w, hist_ptr, pix, matrix, full_range, stream)
 
     @staticmethod
     def _metric_flags(names, clip: bool) -> int:

@@ -11,7 +11,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .engine import FilmEngine
+from .engine import FilmEngine, frame_histogram_device
 
 
 def pinned_frame(shape) -> 'np.ndarray':
@@ -50,13 +50,34 @@ def patches_to_image(patches: torch.Tensor, block_shape: List[int]) -> torch.Ten
     return patches.reshape(bh, bw, ph, pw, c).permute(0, 2, 1, 3, 4).reshape(1, bh * ph, bw * pw, c).contiguous()
 
 
+def frame_histogram(frame: torch.Tensor, pix: str = 'u8') -> torch.Tensor:
+    """film_frame_histogram of one CUDA frame: [H,W,3] uint8 ('u8') or float32 ('f32'), or an 8-bit 4:2:0 frame as uint8 [H * 3 // 2, W]
+    ('i420' | 'nv12') -> int64 [3, 256] on the frame's device: the number of samples of every plane with every 8-bit code (include/film_hip.h,
+    "Scene cuts").  Asynchronous on the current torch stream."""
+    assert frame.is_cuda and frame.dtype == (torch.float32 if pix == 'f32' else torch.uint8)
+    frame = frame.contiguous()
+    if pix in ('i420', 'nv12'):
+        assert frame.dim() == 2 and frame.shape[0] % 3 == 0
+        h, w = frame.shape[0] * 2 // 3, frame.shape[1]
+    else:
+        assert frame.dim() == 3 and frame.shape[-1] == 3
+        h, w = frame.shape[0], frame.shape[1]
+    hist = torch.empty((3, 256), dtype=torch.int32, device=frame.device)
+    with torch.cuda.device(frame.device):
+        frame_histogram_device(frame.data_ptr(), h, w, hist.data_ptr(), pix, stream=torch.cuda.current_stream(frame.device).cuda_stream)
+    return hist.to(torch.int64)      # (counts stay below 2^31: H * W < 2^31)
+
+
 class DeviceStream:
     """A frame stream on frames that already live in HBM (DeviceInterpolator.stream): push(frame) takes a [H,W,3] CUDA tensor, float32
     or uint8 as opened (a 4:2:0 stream: uint8 [H * 3 // 2, W]), and returns the mid-frame between it and the frame pushed before as a new tensor of the same kind - None for
-    the first frame after opening or reset().  Asynchronous on the current torch stream."""
+    the first frame after opening or reset(), and for a frame that the engine option "scene_cut" found to start a new scene.  Asynchronous on the
+    current torch stream (with "scene_cut" > 0 a push waits for the frame's histogram: include/film_hip.h)."""
 
-    def __init__(self, engine: FilmEngine, h: int, w: int, align, block_shape, pix: str, matrix: str = 'bt709', full_range: bool = False):
-        self._stream = engine.open_stream(h, w, align=align, block_shape=block_shape, pix=pix, matrix=matrix, full_range=full_range)
+    def __init__(self, engine: FilmEngine, h: int, w: int, align, block_shape, pix: str, matrix: str = 'bt709', full_range: bool = False,
+                 scene_cut: int = 0):
+        self._stream = engine.open_stream(h, w, align=align, block_shape=block_shape, pix=pix, matrix=matrix, full_range=full_range,
+                                          scene_cut=scene_cut)
         self._dtype = torch.float32 if pix == 'f32' else torch.uint8
 
     def push(self, frame: torch.Tensor) -> Optional[torch.Tensor]:
@@ -68,6 +89,10 @@ class DeviceStream:
 
     def reset(self) -> None:
         self._stream.reset()
+
+    def cut_info(self):
+        """FilmStream.cut_info: (distance, samples, cut) of the last push (engine option "scene_cut")."""
+        return self._stream.cut_info()
 
     def close(self) -> None:
         self._stream.close()
@@ -127,12 +152,14 @@ class DeviceInterpolator:
                                                  block_shape=bs if bs is not None and bs[0] * bs[1] > 1 else None, stream=stream)
         return out
 
-    def stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False) -> DeviceStream:
+    def stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False, scene_cut: int = 0) -> DeviceStream:
         """Extension: a frame stream of h x w frames (film_stream_*), padded / tiled like batch(): push one CUDA tensor at a time, float32
         or ('u8') uint8, and get the mid-frame with the frame before - bit-identical to batch(previous, frame), one extraction per frame.
-        'i420' / 'nv12': 8-bit 4:2:0 frames as uint8 [h * 3 // 2, w] tensors, converted inside the cut and the quantisation."""
+        'i420' / 'nv12': 8-bit 4:2:0 frames as uint8 [h * 3 // 2, w] tensors, converted inside the cut and the quantisation.
+        scene_cut (0 .. 1000 permille): non-zero sets the ENGINE option "scene_cut" before the stream opens, and it stays set (like block_overlap)."""
         bs = self._block_shape
-        return DeviceStream(self._engine, h, w, self._align, bs if bs is not None and bs[0] * bs[1] > 1 else None, pix, matrix, full_range)
+        return DeviceStream(self._engine, h, w, self._align, bs if bs is not None and bs[0] * bs[1] > 1 else None, pix, matrix, full_range,
+                            scene_cut)
 
     def __call__(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         if self._block_shape is not None and self._block_shape[0] * self._block_shape[1] > 1:

@@ -173,6 +173,10 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                      silently and with the same bits, when its plan was evicted or dropped meanwhile.  After a push that fails
  *                      the stream is as after film_stream_reset, and both of the handle's streams are drained before the error returns.
  *   film_stream_reset  forgets the carried frame (scene cut, seek): the next push produces nothing.
+ *   film_stream_cut_info  what the last push found with option "scene_cut" (below, "Scene cuts"): *distance = D between the pushed frame and
+ *                      the one before, or -1 when no comparison was made (the option is 0, the first frame, the push after a reset or after a
+ *                      failed push, the first push after the option was turned on); *samples = S of one frame; *cut = 1 when the push
+ *                      was treated as a scene cut, else 0.  NULL outputs are skipped.
  *   film_stream_close  frees the stream's buffers (film_destroy closes an open stream too).
  * push / reset / close without an open stream: FILM_ERR_STATE.
  *   film_stream_plan_json  the stream plan of `tiles` (padded) H x W tiles in orientation `slot` (0 / 1: the half of the frame buffers
@@ -209,7 +213,31 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *     q(v) = uint8(min(max(v, 0), 255) + 0.5);  limited: Y = q(Yf * 219 + 16), C = q(m * 224 + 128);  full: Y = q(Yf * 255), C = q(m * 255 + 128).
  *   Replicate in and box mean out are inverse to each other: a frame whose RGB stays inside the gamut returns byte for byte.
  *   Not provided: 10-bit (P010) and 4:2:2 / 4:4:4 layouts; sited bilinear chroma (MPEG-2 left siting - the box treatment is consistent in
- *   and out); 4:2:0 frames on film_interpolate / film_interpolate_sequence themselves (film_to_yuv420 converts their results). */
+ *   and out); 4:2:0 frames on film_interpolate / film_interpolate_sequence themselves (film_to_yuv420 converts their results).
+ * Scene cuts.  Across a cut a stream would interpolate between two unrelated pictures.  The engine offers an exact per-frame statistic
+ * computed where the frame already lies, an integer decision rule, and a stream that resets itself (option "scene_cut").  Integers only.
+ *   Histogram of a frame: uint32_t hist[3][256], hist[p][v] = the number of samples of plane p with 8-bit code v.
+ *     FILM_PIX_U8     plane c = the bytes frame[y][x][c].
+ *     FILM_PIX_F32    plane c = the byte film_to_uint8 stores for frame[y][x][c]: uint8(clip(x * 255, 0, 255) + 0.5), the same float32
+ *                     operations in the same order.
+ *     FILM_PIX_I420 / FILM_PIX_NV12   plane 0 = the Y bytes (H * W samples), planes 1 and 2 = the Cb and Cr bytes (H/2 * W/2 samples each).
+ *                     The colour flags are validated as everywhere else and otherwise ignored: the statistic is about the stored codes.
+ *     Every plane sums to its sample count.  S = the samples of one frame: 3 H W for RGB, 3 H W / 2 for 4:2:0.
+ *   Distance: D = sum over p, v of |h1[p][v] - h0[p][v]|, an int64 with 0 <= D <= 2 S; the score is D / (2 S).  Moving content leaves it
+ *     at 0 (a permutation of the samples has the same histogram); two frames with no code in common give 1.
+ *   Rule: with "scene_cut" = k, 1 <= k <= 1000 (permille), a pair of frames is a cut iff 1000 D >= k * 2 S, compared in 64-bit integers.
+ *     k = 0 (default) turns the feature off.
+ *   NO default threshold is recommended: the detector's hit and miss rates on real footage are UNMEASURED (no footage was available when
+ *   this was written) - choose k on your own material.  What a global histogram cannot see: two scenes with alike histograms (a cut
+ *   between them is missed); fades and dissolves (every step is small); flashes (one bright frame reads as two cuts).
+ *   film_frame_histogram: the histogram of ONE H x W frame of pixel type `pix`, like film_to_uint8 / film_to_yuv420 on DEVICE pointers and
+ *     without a handle: asynchronous on `stream` (NULL: the default stream) of the current device.  hist_dev receives 768 uint32_t
+ *     ([3][256]); the call overwrites them - it never accumulates.  frame_dev must be 4-byte aligned and, for the 8-bit types, lie in an
+ *     allocation of whole 32-bit words (as for the 8-bit cuts: the last partial word is read, only the frame's bytes are counted).
+ *     FILM_ERR_INVALID: a NULL pointer, H or W < 1, H * W >= 2^31, a pix the stream entry points refuse (odd sizes with 4:2:0 included),
+ *     a frame_dev that is not 4-byte aligned. */
+int film_frame_histogram(const void* frame_dev, int H, int W, int pix, uint32_t* hist_dev, void* stream);
+int film_stream_cut_info(film_t* h, int64_t* distance, int64_t* samples, int* cut);
 int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix);
 int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int mem_kind, void* stream);
 int film_stream_reset(film_t* h);
@@ -310,7 +338,17 @@ int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* bu
  *                  its nearest interior edge (y - s_i + 1, s_i + e - y; an edge on the frame's border does not limit it),
  *                  normalised in float32, w_i(y) = a_i(y) / sum_i a_i(y).  A pixel = sum over the covering tiles (i, j) in
  *                  row-major order of (wy_i * wx_j) * value, float32, one rounding per operation, no fused multiply-add;
- *                  independent of how the tiles are chunked.  Does not drop the cached plans (their key carries the tile size). */
+ *                  independent of how the tiles are chunked.  Does not drop the cached plans (their key carries the tile size).
+ *   "scene_cut" k  (extension; 0 .. 1000 permille, default 0 = off, today's pushes: no launch, copy, allocation or wait is added)  read at
+ *                  every film_stream_push, like "block_overlap_*".  k > 0: after the frame has reached the stream's own copy the push
+ *                  takes its histogram there (film_frame_histogram's kernel), downloads the 3 KB and WAITS for them - so also a
+ *                  device-resident push blocks the calling thread until the histogram is back - and compares it with the previous
+ *                  frame's ("Scene cuts" above: cut iff 1000 D >= k * 2 S).  No cut: the push goes on as always.  Cut: the push behaves
+ *                  exactly as film_stream_reset followed by this push - *produced = 0, `mid` is not touched, only the extraction runs
+ *                  (no flow estimator, no fusion) - and the next push interpolates inside the new scene.  No comparison is made on the
+ *                  first frame, after film_stream_reset, after a failed push, and on the first push after the option was turned on.
+ *                  film_stream_cut_info reports what the last push found.  No threshold is recommended: see "Scene cuts".  Does not
+ *                  drop the cached plans. */
 int film_set_option(film_t* h, const char* key, int64_t value);
 
 /* The tile geometry film_interpolate / film_interpolate_sequence use for H x W frames with these arguments and the handle's current

@@ -11,6 +11,12 @@ device-resident), `push_i420` / `push_nv12` (the same on 8-bit 4:2:0 frames, whe
 (film_interpolate on numpy arrays, as bench.py's host_buffers), `host_push_f32`, `host_push_u8`, `host_push_i420`, `host_push_nv12`.
 The 4:2:0 rows are compared with the BASELINE's `push_u8` / `host_push_u8` (what such a caller had before: RGB bytes), whose spread
 over the rounds is reported next to them.  --rows / --points restrict a run to some measurements.
+--scene_cut adds, at the first point and for `u8` and `i420`, device-resident and host buffers, what option "scene_cut" costs (trees
+without the option skip them): `*_sc1000` - the steady-state push with scene_cut = 1000, which never cuts on the bench frames (rolled
+copies of one picture: D = 0 for RGB, a fraction of a percent of 2 S for 4:2:0, whose chroma is averaged after the roll) but pays the histogram kernel, the 3 KB download and the wait; `*_cut` - a push that IS a cut (scene_cut = 1,
+alternating a frame and its halved codes: extraction only); `*_first` - a first push (reset() + push, scene_cut = 0), what a cut should cost;
+and `hist <layout> <size> <data>` - frame_histogram_kernel alone (film_frame_histogram, hip events around 50 calls, microseconds per call)
+at 1080p and 4K on random bytes and on a constant frame, beside the frame's bytes over the measured HBM copy rate (6.29 TB/s).
 Every measurement: untimed warm-up calls (plan build, autotune, first launches), then --reps timed windows of `n` calls, each
 ended by a device synchronise; the window's ms per call is one sample.  Each tree keeps its autotune choices in a file of its own
 under --scratch, so that the rounds of a tree run the same tiles.  The report gives mean and range over all samples of a
@@ -41,7 +47,7 @@ def _frames(f, h, w, seed=0):
     return np.clip(np.stack([np.roll(base, (2 * i, -3 * i), axis=(0, 1)) for i in range(f)]), 0, 1).astype(np.float32)
 
 
-def worker(root, reps, quick, rows=None, points=None):
+def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
     """Times what the checkout at `root` offers (of `rows` / `points`, when given); prints one JSON line."""
     for p in (root, os.path.join(root, 'frame-interpolation_amd')):
         sys.path.insert(0, p)
@@ -56,6 +62,7 @@ def worker(root, reps, quick, rows=None, points=None):
     eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
     has_stream = hasattr(eng, 'open_stream')
     has_yuv = 'i420' in getattr(engine_mod, 'PIX', {})
+    has_scene = scene_cut and hasattr(engine_mod, 'frame_histogram_device')
     want = lambda key: rows is None or key in rows      # noqa: E731
     out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {}}
 
@@ -128,19 +135,102 @@ def worker(root, reps, quick, rows=None, points=None):
                         with eng.open_stream(h, w, align=align, block_shape=block, pix=pix) as st:
                             st.push(frames[0])
                             res['host_push_' + pix] = timed(lambda: st.push(frames[nxt(4)]), hn, warm=2)
+            if has_scene and pi == 0 and has_yuv:
+                res.update(scene_rows(eng, it, timed, nxt, h, w, align, block, n, x8, yuv['i420']))
             del yuv
         out['points'][name] = res
         del x, x8
         torch.cuda.empty_cache()
+    if has_scene:
+        out['histogram_us'] = histogram_alone()
     eng.save_tune_cache()
     eng.close()
     print('STREAM_BENCH ' + json.dumps(out), flush=True)
 
 
-def _run_worker(root, reps, quick, tune_file, rows=None, points=None):
+def scene_rows(eng, it, timed, nxt, h, w, align, block, n, x8, i420):
+    """The --scene_cut rows of one point: see the module text.  x8 / i420: the bench frames as CUDA tensors."""
+    res = {}
+    hn = max(5, n // 3)
+    for pix, dev in (('u8', x8), ('i420', i420)):
+        other = dev[0] // 2                         # no histogram in common with the bench frames: every push of the pair is a cut
+        host, host_other = [t.cpu().numpy() for t in dev], other.cpu().numpy()
+        try:
+            with it.stream(h, w, pix, scene_cut=1000) as st:
+                st.push(dev[0])
+                res[f'push_{pix}_sc1000'] = timed(lambda: st.push(dev[nxt(4)]), n)
+                assert st.cut_info()[0] >= 0 and st.cut_info()[2] == 0, (pix, st.cut_info())      # (compared, and no cut: rolled copies of one picture)
+            with it.stream(h, w, pix, scene_cut=1) as st:
+                st.push(dev[0])
+                flip = {'i': 0}
+
+                def cut_push():
+                    flip['i'] ^= 1
+                    return st.push(other if flip['i'] else dev[0])
+                res[f'push_{pix}_cut'] = timed(cut_push, n)
+                assert st.cut_info()[2] == 1, (pix, st.cut_info())
+            eng.set_option('scene_cut', 0)
+            with it.stream(h, w, pix) as st:
+                def first_push():
+                    st.reset()
+                    return st.push(dev[0])
+                res[f'push_{pix}_first'] = timed(first_push, n)
+            with eng.open_stream(h, w, align=align, block_shape=block, pix=pix, scene_cut=1000) as st:
+                st.push(host[0])
+                res[f'host_push_{pix}_sc1000'] = timed(lambda: st.push(host[nxt(4)]), hn, warm=2)
+            with eng.open_stream(h, w, align=align, block_shape=block, pix=pix, scene_cut=1) as st:
+                st.push(host[0])
+                flip = {'i': 0}
+
+                def host_cut_push():
+                    flip['i'] ^= 1
+                    return st.push(host_other if flip['i'] else host[0])
+                res[f'host_push_{pix}_cut'] = timed(host_cut_push, hn, warm=2)
+            eng.set_option('scene_cut', 0)
+            with eng.open_stream(h, w, align=align, block_shape=block, pix=pix) as st:
+                def host_first_push():
+                    st.reset()
+                    return st.push(host[0])
+                res[f'host_push_{pix}_first'] = timed(host_first_push, hn, warm=2)
+        finally:
+            eng.set_option('scene_cut', 0)
+    return res
+
+
+def histogram_alone(calls=50, reps=3):
+    """frame_histogram_kernel alone: {"<layout> <size> <data>": [microseconds per call, ...]} from hip events around `calls` calls."""
+    import torch
+    from film_hip.torch_io import frame_histogram
+    from film_hip.engine import frame_histogram_device
+    out = {}
+    hist = torch.empty(768, dtype=torch.int32, device='cuda')
+    for size, (h, w) in (('1080p', (1080, 1920)), ('4K', (2160, 3840))):
+        for pix in ('u8', 'i420', 'nv12', 'f32'):
+            shape = (h * 3 // 2, w) if pix in ('i420', 'nv12') else (h, w, 3)
+            for data in ('random', 'constant'):
+                if pix == 'f32':
+                    fr = torch.rand(shape, device='cuda') if data == 'random' else torch.full(shape, 0.5, device='cuda')
+                else:
+                    fr = torch.randint(0, 256, shape, dtype=torch.uint8, device='cuda') if data == 'random' else torch.full(shape, 16, dtype=torch.uint8, device='cuda')
+                assert int(frame_histogram(fr, pix).sum()) == fr.numel()
+                s = torch.cuda.current_stream().cuda_stream
+                samples = []
+                for _ in range(reps + 1):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(calls):
+                        frame_histogram_device(fr.data_ptr(), h, w, hist.data_ptr(), pix, stream=s)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    samples.append(round(e0.elapsed_time(e1) * 1e3 / calls, 2))
+                out[f'{pix} {size} {data}'] = samples[1:] + [fr.numel() * fr.element_size()]      # (the first window warms up; last entry: the frame's bytes)
+    return out
+
+
+def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False):
     env = dict(os.environ, FILM_TUNE_CACHE=tune_file)
     cmd = [sys.executable, os.path.abspath(__file__), '--worker', root, '--reps', str(reps)] + (['--quick'] if quick else [])
-    cmd += (['--rows', ','.join(rows)] if rows else []) + (['--points', ','.join(points)] if points else [])
+    cmd += (['--rows', ','.join(rows)] if rows else []) + (['--points', ','.join(points)] if points else []) + (['--scene_cut'] if scene_cut else [])
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)   # (a hung worker ends the run: nothing is started behind it)
     for line in p.stdout.splitlines():
         if line.startswith('STREAM_BENCH '):
@@ -162,18 +252,19 @@ def main(argv=None):
     ap.add_argument('--out', default=None, help='also append the report to this file')
     ap.add_argument('--rows', default=None, help='comma-separated measurements to take (default: all), e.g. push_u8,push_i420,host_push_u8')
     ap.add_argument('--points', default=None, help='comma-separated points to run (default: all), e.g. "1080p 2x2"')
+    ap.add_argument('--scene_cut', action='store_true', help='add the cost of option "scene_cut" and of its histogram kernel alone (see above)')
     ap.add_argument('--worker', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     rows = args.rows.split(',') if args.rows else None
     points = args.points.split(',') if args.points else None
     if args.worker:
-        return worker(args.worker, args.reps, args.quick, rows, points)
+        return worker(args.worker, args.reps, args.quick, rows, points, args.scene_cut)
     os.makedirs(args.scratch, exist_ok=True)
     trees = ([('baseline', os.path.abspath(args.baseline_root))] if args.baseline_root else []) + [('this', HERE)]
     runs = {k: [] for k, _ in trees}
     for r in range(args.rounds):
         for k, root in trees:
-            runs[k].append(_run_worker(root, args.reps, args.quick, os.path.join(args.scratch, f'stream_bench_tune_{k}.txt'), rows, points))
+            runs[k].append(_run_worker(root, args.reps, args.quick, os.path.join(args.scratch, f'stream_bench_tune_{k}.txt'), rows, points, args.scene_cut))
             print(f'# round {r + 1}/{args.rounds} {k}: done', flush=True)
     this = runs['this']
     lines = [f'# tools/stream_bench.py  this = {this[0]["version"]}' + (f'  baseline = {runs["baseline"][0]["version"]}' if args.baseline_root else '') +
@@ -208,6 +299,30 @@ def main(argv=None):
                 d = [statistics.mean(p[mine]) - b for p, b in zip(pts, bm)]
                 lines.append(f'  {mine + " - baseline " + theirs:<36} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms'
                              f'   (baseline {theirs}: round means {" ".join(f"{b:.3f}" for b in bm)}, spread {max(bm) - min(bm):.3f} ms)')
+        # option "scene_cut": what the histogram and its wait add to a steady push, a push that is a cut beside a first push
+        for pre in ('', 'host_'):
+            for pix in ('u8', 'i420'):
+                plain, sc, cut, first = (f'{pre}push_{pix}{suf}' for suf in ('', '_sc1000', '_cut', '_first'))
+                if sc not in pts[0]:
+                    continue
+                for key in (sc, cut, first):
+                    lines.append(f'  {key:<22} {_stat([s for p in pts for s in p[key]])}')
+                if plain in pts[0]:
+                    d = [statistics.mean(p[sc]) - statistics.mean(p[plain]) for p in pts]
+                    lines.append(f'  {sc + " - " + plain:<36} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms   (scene_cut = 1000 against 0, this tree)')
+                    if base and plain in base[0]:
+                        bm = [statistics.mean(p[plain]) for p in base]
+                        d0 = [statistics.mean(p[plain]) - b for p, b in zip(pts, bm)]
+                        lines.append(f'  {plain + " - baseline " + plain:<36} per round: {" ".join(f"{v:+.3f}" for v in d0)}   mean {statistics.mean(d0):+.3f} ms'
+                                     f'   (scene_cut = 0; baseline round means {" ".join(f"{b:.3f}" for b in bm)}, spread {max(bm) - min(bm):.3f} ms)')
+                d = [statistics.mean(p[cut]) - statistics.mean(p[first]) for p in pts]
+                lines.append(f'  {cut + " - " + first:<36} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms')
+    if 'histogram_us' in this[0]:
+        lines.append('frame_histogram_kernel alone (memset + kernel per call), microseconds per call: mean [min .. max]; the frame\'s bytes / 6.29 TB/s beside it')
+        for key in this[0]['histogram_us']:
+            v = [s for r in this for s in r['histogram_us'][key][:-1]]
+            nbytes = this[0]['histogram_us'][key][-1]
+            lines.append(f'  {key:<22} {_stat(v)} us   {nbytes / 1e6:7.2f} MB   {nbytes / 6.29e12 * 1e6:6.2f} us at the HBM rate')
     lines.append('# raw: ' + json.dumps(runs))
     print('\n'.join(lines), flush=True)
     if args.out:
