@@ -115,17 +115,19 @@ int tile_geometry(film_t* h, int H, int W, int block_h, int block_w, int align, 
 }
 // The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the 4:2:0 layouts.
 int pix_layout(int pix) { return pix & 0xff; }
-bool pix_is_yuv(int pix) { return pix_layout(pix) == FILM_PIX_I420 || pix_layout(pix) == FILM_PIX_NV12; }
+bool pix_is_yuv10(int pix) { return pix_layout(pix) == FILM_PIX_I010 || pix_layout(pix) == FILM_PIX_P010; }   // 16-bit samples
+bool pix_is_yuv(int pix) { return pix_layout(pix) == FILM_PIX_I420 || pix_layout(pix) == FILM_PIX_NV12 || pix_is_yuv10(pix); }
 // FILM_OK, or the refusal of a pix value for H x W frames (include/film_hip.h, film_stream_open)
 int check_pix(film_t* h, int pix, int H, int W) {
   const int layout = pix_layout(pix), flags = pix & ~0xff;
   if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !pix_is_yuv(pix))
-    return fail(h, FILM_ERR_INVALID, "bad pix layout %d: FILM_PIX_F32 (0), FILM_PIX_U8 (1), FILM_PIX_I420 (16) or FILM_PIX_NV12 (17)", layout);
+    return fail(h, FILM_ERR_INVALID, "bad pix layout %d: FILM_PIX_F32 (0), FILM_PIX_U8 (1), FILM_PIX_I420 (16), FILM_PIX_NV12 (17), FILM_PIX_I010 (32) or FILM_PIX_P010 (33)",
+                layout);
   if (flags & ~(FILM_YUV_BT601 | FILM_YUV_FULL))
     return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: unknown bits 0x%x set (flags: FILM_YUV_BT601 0x100, FILM_YUV_FULL 0x400)", (unsigned)pix,
                 (unsigned)(flags & ~(FILM_YUV_BT601 | FILM_YUV_FULL)));
   if (flags && !pix_is_yuv(pix))
-    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: the colour flags belong to FILM_PIX_I420 / FILM_PIX_NV12, not to an RGB layout", (unsigned)pix);
+    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: the colour flags belong to the 4:2:0 layouts, not to an RGB layout", (unsigned)pix);
   if (pix_is_yuv(pix) && H > 0 && W > 0 && ((H | W) & 1))
     return fail(h, FILM_ERR_INVALID, "pix: 4:2:0 needs even sizes, got %d x %d", H, W);
   return FILM_OK;
@@ -133,7 +135,7 @@ int check_pix(film_t* h, int pix, int H, int W) {
 // bytes of one H x W frame of pixel type `pix`
 size_t frame_bytes(int pix, int H, int W) {
   const size_t px = (size_t)H * W;
-  return pix_is_yuv(pix) ? px + px / 2 : pix_layout(pix) == FILM_PIX_U8 ? px * 3 : px * 3 * sizeof(float);
+  return pix_is_yuv10(pix) ? px * 3 : pix_is_yuv(pix) ? px + px / 2 : pix_layout(pix) == FILM_PIX_U8 ? px * 3 : px * 3 * sizeof(float);
 }
 // The handle's staging buffer in HBM (whole frames of the FILM_MEM_HOST entry points), grown on demand.
 int ensure_stage(film_t* h, size_t bytes, hipStream_t s) {
@@ -431,7 +433,8 @@ int film_frame_histogram(const void* frame_dev, int H, int W, int pix, uint32_t*
 
 int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream) {
   if (!src || !dst || H < 1 || W < 1 || !pix_is_yuv(pix) || check_pix(nullptr, pix, H, W) != FILM_OK) return FILM_ERR_INVALID;
-  return film_launch_rgb_to_yuv420(src, static_cast<uint8_t*>(dst), H, W, pix, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
+  if (pix_is_yuv10(pix) && (reinterpret_cast<uintptr_t>(dst) & 1)) return FILM_ERR_INVALID;   // (16-bit samples)
+  return film_launch_rgb_to_yuv420(src, dst, H, W, pix, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
 }
 
 #ifndef FILM_SRC_ID
@@ -804,17 +807,17 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
   } else {
     if ((rc = run_plan(h, P, s))) return rc;
     // joined in float32 by the kernels of film_interpolate, then quantised by film_to_uint8's kernel for an 8-bit RGB stream, by
-    // film_to_yuv420's for a 4:2:0 stream
+    // film_to_yuv420's for a 4:2:0 stream (8-bit or 10-bit)
     float* joined = (fs.pix == FILM_PIX_F32 && !host) ? (float*)mid : fs.result;
     TileMapParams j = tp;
     j.tile0 = 0; j.ntiles = T; j.src = P->at("out"); j.dst = joined;
     HIPCHK(h, film_launch_join_tiles(j, s));
     if (fs.pix != FILM_PIX_F32) {
-      uint8_t* q = host ? fs.result8 : (uint8_t*)mid;
+      void* q = host ? (void*)fs.result8 : mid;
       if (pix_is_yuv(fs.pix))
         HIPCHK(h, film_launch_rgb_to_yuv420(joined, q, fs.H, fs.W, fs.pix, s));
       else
-        HIPCHK(h, film_launch_to_uint8(joined, q, (int64_t)nv, s));
+        HIPCHK(h, film_launch_to_uint8(joined, static_cast<uint8_t*>(q), (int64_t)nv, s));
       if (host) HIPCHK(h, hipMemcpyAsync(mid, q, fb, hipMemcpyDeviceToHost, s));
     } else if (host) {
       HIPCHK(h, hipMemcpyAsync(mid, joined, nv * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -916,7 +919,8 @@ int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, i
                        int tile0, int ntiles, void* stream) {
   if (!h) return FILM_ERR_INVALID;
   if (!frames_dev || !tiles_dev) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: NULL argument");
-  if (!pix_is_yuv(pix)) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: bad pix layout %d: FILM_PIX_I420 (16) or FILM_PIX_NV12 (17)", pix_layout(pix));
+  if (!pix_is_yuv(pix))
+    return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: bad pix layout %d: FILM_PIX_I420 (16), FILM_PIX_NV12 (17), FILM_PIX_I010 (32) or FILM_PIX_P010 (33)", pix_layout(pix));
   int rc = check_pix(h, pix, H, W);
   if (rc) return rc;
   if (reinterpret_cast<uintptr_t>(frames_dev) & 3) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: the frames of a 4:2:0 pix must be 4-byte aligned");

@@ -175,7 +175,7 @@ struct FilmStream {
   int H = 0, W = 0, align = 0, block_h = 0, block_w = 0, pix = 0;   // pix: a FILM_PIX_* layout plus, for 4:2:0, the FILM_YUV_* flags
   void* keep = nullptr;             // the last pushed frame: [H][W][3] float32 or bytes, or the H * W * 3 / 2 bytes of a 4:2:0 frame
   float* result = nullptr;          // the joined float32 mid-frame of a host or 8-bit push
-  unsigned char* result8 = nullptr; // ... quantised (RGB bytes or a 4:2:0 frame), of an 8-bit host push
+  unsigned char* result8 = nullptr; // ... quantised (RGB bytes or a 4:2:0 frame, 8-bit or 10-bit), of a host push that is not float32
   bool primed = false;              // `keep` holds a frame
   int slot = 0;                     // the half of the plan's frame buffers it was extracted into ...
   uint64_t plan_id = 0;             // ... of this plan (Plan::id) ...

@@ -383,15 +383,17 @@ hipError_t film_launch_pack_flow(const PackFlowParams& p, hipStream_t s);
 // frame_kernels.hip: frame I/O.  `pix` is the public value (include/film_hip.h): a layout in bits 0-7 plus FILM_YUV_BT601 / FILM_YUV_FULL for the
 // 4:2:0 layouts; the launchers decode it.  Overlapped tiles and their cross-fade when p.ovy | p.ovx.
 // pad + image_to_patches of tiles [tile0, tile0 + ntiles): p.src is float32 [B][H][W][3] (FILM_PIX_F32), or bytes that the cut converts - [B][H][W][3]
-// (FILM_PIX_U8: float32(byte) / 255.0f, correctly rounded) or 4:2:0 frames of H * W * 3 / 2 bytes each (FILM_PIX_I420 / NV12; H and W even).
+// (FILM_PIX_U8: float32(byte) / 255.0f, correctly rounded) or 4:2:0 frames of H * W * 3 / 2 bytes each (FILM_PIX_I420 / NV12; H and W even),
+// or 10-bit 4:2:0 frames of H * W * 3 / 2 little-endian uint16 samples each (FILM_PIX_I010 / P010; H and W even, the pointer 4-byte aligned).
 hipError_t film_launch_cut_tiles(const TileMapParams& p, int pix, hipStream_t s);
 // crop + patches_to_image, or crop + cross-fade.  The cross-fade adds to what the tiles below tile0 left in dst, so the launches of one
 // frame go in tile order on one stream.
 hipError_t film_launch_join_tiles(const TileMapParams& p, hipStream_t s);
 // write_image's rounding on the device: dst[i] = uint8(clip(src[i] * 255, 0, 255) + 0.5)  (eval/util.py:51-52)
 hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipStream_t s);
-// float32 [H][W][3] -> one 4:2:0 frame of H * W * 3 / 2 bytes (clip, matrix, 2 x 2 box mean of the chroma, quantisation)
-hipError_t film_launch_rgb_to_yuv420(const float* src, uint8_t* dst, int H, int W, int pix, hipStream_t s);
+// float32 [H][W][3] -> one 4:2:0 frame of H * W * 3 / 2 samples (clip, matrix, 2 x 2 box mean of the chroma, quantisation): bytes for
+// FILM_PIX_I420 / NV12, uint16 for FILM_PIX_I010 / P010 (dst then 2-byte aligned, else hipErrorInvalidValue)
+hipError_t film_launch_rgb_to_yuv420(const float* src, void* dst, int H, int W, int pix, hipStream_t s);
 // The sample histogram of one frame (include/film_hip.h, "Scene cuts"): hist[p * 256 + v] = the samples of plane p with 8-bit code v.  The launcher
 // zeroes the 768 counters first: a call overwrites.  `frame` is 4-byte aligned and its allocation a whole number of 32-bit words (as for the 8-bit
 // cuts).  A lane reads FILM_HIST_VEC_BYTES per step; the grid is min(what the frame needs, FILM_HIST_WG_PER_CU workgroups per compute unit) of

@@ -4,10 +4,12 @@
 //   frame_to_tiles<OVERLAP>             _pad_to_align + image_to_patches, float32 frames    eval/interpolator.py:30-63, :66-104
 //   frame_u8_to_tiles<OVERLAP>          the same on 8-bit RGB frames: float32(byte) / 255   eval/util.py read_image
 //   frame_yuv420_to_tiles<OVERLAP,NV12> the same on 8-bit 4:2:0 frames (I420 / NV12)        include/film_hip.h, "The 4:2:0 arithmetic"
+//   frame_yuv10_to_tiles<OVERLAP,P010>  the same on 10-bit 4:2:0 frames (I010 / P010)           include/film_hip.h, "The 10-bit 4:2:0 arithmetic"
 //   tiles_to_frame                      crop + patches_to_image                             eval/interpolator.py:107-126, :192-206
 //   blend_tiles                         crop + cross-fade of overlapped tiles               include/film_hip.h, "block_overlap_h"
 //   to_uint8                            clip(x * 255, 0, 255) + 0.5, truncated              eval/util.py:51-52 (write_image)
 //   rgb_to_yuv420<NV12>                 float32 RGB -> the planes of one 4:2:0 frame        include/film_hip.h, "The 4:2:0 arithmetic"
+//   rgb_to_yuv10<P010>                  float32 RGB -> the planes of one 10-bit 4:2:0 frame  include/film_hip.h, "The 10-bit 4:2:0 arithmetic"
 //   frame_histogram<LAYOUT>             3 x 256 counters of a frame's 8-bit sample codes    include/film_hip.h, "Scene cuts"
 //
 // OVERLAP: the tile's content is the patch grown by the overlap, from film_tile_origin (options "block_overlap_h" / "block_overlap_w").
@@ -268,6 +270,136 @@ __global__ __launch_bounds__(256) void frame_yuv420_to_tiles_kernel(TileMapParam
   }   // (own text: see frame_u8_to_tiles_kernel)
 }
 
+// ---- 10-bit Y'CbCr 4:2:0 frames (FILM_PIX_I010 / FILM_PIX_P010; the arithmetic: include/film_hip.h, "The 10-bit 4:2:0 arithmetic") ----
+// What a colour setting decides.  The coefficients are YuvTables' (the same matrices); the codes are 10 bits wide.  The two 1024-entry
+// tables of quotients would be 8 KB - more than a kernel's argument block holds - so there are none: the cut DIVIDES on the device,
+// (float(v) - sub) / div with the divisor a kernel argument.  hipcc's fp32 division is correctly rounded by default
+// (-fhip-fp32-correctly-rounded-divide-sqrt: the v_div_scale / v_div_fmas / v_div_fixup sequence) and this library is built without
+// fast-math and without contraction, so the quotient has the bits of the host's IEEE division; no quotient here is subnormal.  Chosen over
+// device-resident tables copied into LDS by every workgroup: no per-device allocation for launchers that have no handle to own it, no
+// 8 KB LDS fill per workgroup for ten look-ups per thread, and nothing an input word could index.
+struct Yuv10Consts {
+  float y_sub, y_div, c_div;             // in: y = (float(v) - y_sub) / y_div, c = (float(v) - 512) / c_div
+  float a_r, a_b, g_b, g_r;              // in: as YuvTables
+  float kr, kg, kb, s_b, s_r;            // out: as YuvTables
+  float y_scale, y_off, c_scale;         // out: Y = q10(Yf y_scale + y_off), C = q10(m c_scale + 512)
+};
+
+// the 10-bit code of a stored 16-bit word: I010 keeps it in bits 0-9 (the upper six are ignored), P010 in bits 6-15 (the lower six are)
+template <bool P010> __device__ __forceinline__ uint32_t code10(uint32_t w) { return P010 ? (w & 0xffffu) >> 6 : w & 1023u; }
+// the out quantiser: clip(v, 0, 1023) + 0.5, truncated
+__device__ __forceinline__ uint32_t quant1023(float v) {
+  v = v < 0.f ? 0.f : v;
+  v = v > 1023.f ? 1023.f : v;
+  return (uint32_t)(v + 0.5f);
+}
+// n <= 4 16-bit samples from p (2-byte aligned) as the low words of a 64-bit value, read as the one, two or three ALIGNED 32-bit words
+// that hold them: every word read holds at least one of the samples asked for
+__device__ __forceinline__ uint64_t load_samples_aligned(const uint16_t* p, int n) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  const uint32_t* wp = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+  const unsigned off = (unsigned)(a >> 1) & 1u;   // samples in front of p in its word
+  uint64_t v = wp[0];
+  if (off + (unsigned)n > 2) v |= (uint64_t)wp[1] << 32;
+  if (off) {
+    v >>= 16;
+    if ((unsigned)n > 3) v |= (uint64_t)wp[2] << 48;
+  }
+  return v;
+}
+
+// frame_yuv420_to_tiles_kernel on 10-bit frames: p.src points at little-endian uint16 samples, frame b at sample b * H * W * 3 / 2, its
+// Y plane [H][W] first, then Cb [H/2][W/2] and Cr [H/2][W/2] (I010) or CbCr [H/2][W/2][2] (P010).  thread = four pixels (twelve floats) of
+// one row of the tile buffer; pixel (fy, fx) of the FRAME takes the chroma sample (fy >> 1, fx >> 1).  A group wholly inside the tile's
+// content reads its four Y samples as the two or three aligned 32-bit words that hold them and its two or three chroma samples per plane
+// the same way (I010) or as the two or three aligned words that ARE its CbCr pairs (P010: a pair never straddles a word, W being even);
+// a group that touches the padding or the row's end goes sample by sample.
+template <bool OVERLAP, bool P010>
+__global__ __launch_bounds__(256) void frame_yuv10_to_tiles_kernel(TileMapParams p, Yuv10Consts k) {
+  const int row = p.TW * 3;
+  const int groups = (p.TW + 3) / 4;
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (int64_t)p.ntiles * p.TH * groups) return;
+  const int xp0 = (int)(g % groups) * 4;      // first pixel of the group in the tile row
+  const int64_t r = g / groups;               // row of the tile buffer
+  using C = TileContent<OVERLAP>;
+  int y, b, ty, tx;
+  tile_row(p, r, y, b, ty, tx);
+  const int ch = C::rows(p), cw = C::cols(p);                         // the tile's content: rows, pixels per row
+  const int sy = y - p.oy, s0 = xp0 - p.ox;                           // content row, content pixel of the group's first pixel
+  float v[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) v[j] = 0.f;   // tf.image.pad_to_bounding_box pads with zeros
+  if (sy >= 0 && sy < ch && s0 + 4 > 0 && s0 < cw) {
+    const int fy = C::row0(p, ty) + sy;
+    const int fx = C::col0(p, tx) + s0;   // frame column of the group's first pixel
+    const int64_t plane = (int64_t)p.H * p.W;
+    const uint16_t* frame0 = reinterpret_cast<const uint16_t*>(p.src) + (int64_t)b * (plane + plane / 2);
+    const uint16_t* yrow = frame0 + (int64_t)fy * p.W;
+    const int hw = p.W >> 1;
+    // P010: one row of Cb Cr pairs; I010: a Cb row and, H/2 * W/2 samples further on, the Cr row
+    const uint16_t* crow = frame0 + plane + (int64_t)(fy >> 1) * (P010 ? p.W : hw);
+    const int64_t cr_off = P010 ? 1 : plane / 4;
+    uint32_t yb[4], cbb[4], crb[4];
+    bool have[4];
+    if (s0 >= 0 && s0 + 4 <= cw) {
+      const uint64_t yw = load_samples_aligned(yrow + fx, 4);
+      const int c0 = fx >> 1, nc = ((fx + 3) >> 1) - c0 + 1;      // two chroma samples per plane, three from an odd column
+      uint32_t cbs[3], crs[3];
+      if (P010) {
+        const uint32_t* cwp = reinterpret_cast<const uint32_t*>(crow) + c0;   // (4-byte aligned: the frame is, and H * W and W are even)
+        const uint32_t w0 = cwp[0], w1 = cwp[1], w2 = nc > 2 ? cwp[2] : 0u;
+        cbs[0] = w0 & 0xffffu; crs[0] = w0 >> 16;
+        cbs[1] = w1 & 0xffffu; crs[1] = w1 >> 16;
+        cbs[2] = w2 & 0xffffu; crs[2] = w2 >> 16;
+      } else {
+        const uint64_t wb = load_samples_aligned(crow + c0, nc), wr = load_samples_aligned(crow + cr_off + c0, nc);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { cbs[q] = (uint32_t)(wb >> (16 * q)) & 0xffffu; crs[q] = (uint32_t)(wr >> (16 * q)) & 0xffffu; }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int q = ((fx + j) >> 1) - c0;
+        yb[j] = (uint32_t)(yw >> (16 * j)) & 0xffffu;
+        cbb[j] = q == 0 ? cbs[0] : q == 1 ? cbs[1] : cbs[2];
+        crb[j] = q == 0 ? crs[0] : q == 1 ? crs[1] : crs[2];
+        have[j] = true;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        have[j] = s0 + j >= 0 && s0 + j < cw;
+        yb[j] = cbb[j] = crb[j] = 0;
+        if (have[j]) {
+          const int c = (fx + j) >> 1;
+          yb[j] = yrow[fx + j];
+          cbb[j] = P010 ? crow[2 * c] : crow[c];
+          crb[j] = P010 ? crow[2 * c + 1] : crow[cr_off + c];
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (!have[j]) continue;
+      const float yv = ((float)code10<P010>(yb[j]) - k.y_sub) / k.y_div;
+      const float cb = ((float)code10<P010>(cbb[j]) - 512.f) / k.c_div, cr = ((float)code10<P010>(crb[j]) - 512.f) / k.c_div;
+      v[3 * j] = clip01(yv + k.a_r * cr);
+      v[3 * j + 1] = clip01((yv - k.g_b * cb) - k.g_r * cr);
+      v[3 * j + 2] = clip01(yv + k.a_b * cb);
+    }
+  }
+  const int xc0 = xp0 * 3;
+  float* d = p.dst + r * row + xc0;
+  if (xc0 + 12 <= row && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(d)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 12; ++j)
+      if (xc0 + j < row) d[j] = v[j];
+  }   // (own text: see frame_u8_to_tiles_kernel)
+}
+
 // ---- the two ways out to 8 bits ---------------------------------------------------------------------------------------------------
 // eval/util.py:51-52 (write_image): clip(x * 255, 0, 255) + 0.5, truncated to uint8 - the same float32 operations in the same order
 // (no fused multiply-add: the file is built with -ffp-contract=off), four values per thread
@@ -361,6 +493,89 @@ __global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const float* __restr
   }
 }
 
+// rgb_to_yuv420_kernel for 10-bit frames (film_to_yuv420 with FILM_PIX_I010 / P010; the quantisation of a 10-bit stream's push): dst points at
+// uint16 samples, 2-byte aligned.  thread = 2 rows x 8 pixels: sixteen Y samples and four chroma samples per plane, which leave as whole
+// 32-bit words (four per Y row; two each for Cb and Cr, or four CbCr pairs) where the block is complete and the address allows, sample by
+// sample otherwise.  I010 stores the code, P010 the code << 6: the ignored bits are written as zero.  H and W are even.
+template <bool P010>
+__global__ __launch_bounds__(256) void rgb_to_yuv10_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int H, int W, Yuv10Consts k) {
+  constexpr int SH = P010 ? 6 : 0;
+  const int bpr = (W + 7) / 8;      // blocks per row pair
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)(H / 2) * bpr) return;
+  const int x0 = (int)(i % bpr) * 8, y0 = (int)(i / bpr) * 2;
+  const int np = min(8, W - x0);    // pixels of the block per row: even
+  uint32_t yq[2][8], cbq[4], crq[4];
+  float cbf[2][8], crf[2][8];
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy) {
+    const float* s = src + ((int64_t)(y0 + dy) * W + x0) * 3;
+    float px[24];
+    if (np == 8 && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+#pragma unroll
+      for (int q = 0; q < 6; ++q) {
+        const float4 f = reinterpret_cast<const float4*>(s)[q];
+        px[4 * q] = f.x; px[4 * q + 1] = f.y; px[4 * q + 2] = f.z; px[4 * q + 3] = f.w;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 24; ++q) px[q] = q < np * 3 ? s[q] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float R = clip01(px[3 * j]), G = clip01(px[3 * j + 1]), B = clip01(px[3 * j + 2]);
+      const float Yf = (k.kr * R + k.kg * G) + k.kb * B;
+      cbf[dy][j] = (B - Yf) * k.s_b;
+      crf[dy][j] = (R - Yf) * k.s_r;
+      yq[dy][j] = quant1023(Yf * k.y_scale + k.y_off) << SH;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float mb = ((cbf[0][2 * q] + cbf[0][2 * q + 1]) + (cbf[1][2 * q] + cbf[1][2 * q + 1])) * 0.25f;
+    const float mr = ((crf[0][2 * q] + crf[0][2 * q + 1]) + (crf[1][2 * q] + crf[1][2 * q + 1])) * 0.25f;
+    cbq[q] = quant1023(mb * k.c_scale + 512.f) << SH;
+    crq[q] = quant1023(mr * k.c_scale + 512.f) << SH;
+  }
+  const int64_t plane = (int64_t)H * W;
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy) {
+    uint16_t* d = dst + (int64_t)(y0 + dy) * W + x0;
+    if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t*>(d)[q] = yq[dy][2 * q] | (yq[dy][2 * q + 1] << 16);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < np) d[j] = (uint16_t)yq[dy][j];
+    }
+  }
+  if (P010) {
+    uint16_t* d = dst + plane + (int64_t)(y0 >> 1) * W + x0;
+    if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t*>(d)[q] = cbq[q] | (crq[q] << 16);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (2 * q < np) { d[2 * q] = (uint16_t)cbq[q]; d[2 * q + 1] = (uint16_t)crq[q]; }
+    }
+  } else {
+    uint16_t* db = dst + plane + (int64_t)(y0 >> 1) * (W >> 1) + (x0 >> 1);
+    uint16_t* dr = db + plane / 4;
+    if (np == 8 && (reinterpret_cast<uintptr_t>(db) & 3) == 0 && (reinterpret_cast<uintptr_t>(dr) & 3) == 0) {
+      reinterpret_cast<uint32_t*>(db)[0] = cbq[0] | (cbq[1] << 16);
+      reinterpret_cast<uint32_t*>(db)[1] = cbq[2] | (cbq[3] << 16);
+      reinterpret_cast<uint32_t*>(dr)[0] = crq[0] | (crq[1] << 16);
+      reinterpret_cast<uint32_t*>(dr)[1] = crq[2] | (crq[3] << 16);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (2 * q < np) { db[q] = (uint16_t)cbq[q]; dr[q] = (uint16_t)crq[q]; }
+    }
+  }
+}
+
 // ---- overlapped tiles: every tile carries ovy / ovx pixels of its neighbours, the results are cross-faded ------------------
 // Cross-fade weight (before normalisation) of tile i of an axis at frame position y: the distance to the nearest INTERIOR edge of
 // the tile, counted from 1; an edge on the frame's border does not limit it; 0 outside the tile.  *s = the tile's origin.
@@ -433,6 +648,9 @@ __global__ __launch_bounds__(256) void blend_tiles_kernel(TileMapParams p, int b
 //             4-byte aligned, so only the last word can be partial: the allocation-in-whole-words contract of the 8-bit cuts), and count
 //             only the elements of the frame.
 //   planes    interleaved RGB: element index mod 3; I420: three consecutive ranges; NV12: the Y range, then Cb at even and Cr at odd offsets.
+//   10 bits   LAYOUT = FILM_PIX_I010 / P010: the elements are 16-bit samples, eight per vector and two per word (n and `plane` count samples;
+//             the pointer is 4-byte aligned and n is even, so no word is partial); planes as I420 / NV12; a sample counts in bin code >> 2,
+//             the code being bits 0-9 (I010) or 6-15 (P010) of the word.
 //   counting  LDS integer atomics into HIST_COPIES sub-histograms per workgroup, laid out [bin][copy] with copy = lane & 7: eight
 //             neighbouring lanes never share an address, a flat picture (every lane on one bin) meets 8-way instead of 64-way same-address
 //             serialisation, and the copies of a bin lie in eight consecutive banks.
@@ -442,14 +660,15 @@ constexpr int HIST_COPIES = 8;
 template <int LAYOUT>
 __global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(const void* __restrict__ frame, int64_t n, int64_t plane, uint32_t* __restrict__ hist) {
   constexpr bool F32 = LAYOUT == FILM_PIX_F32;
-  constexpr int EPV = F32 ? 4 : 16;   // elements per 16-byte vector
+  constexpr bool U16 = LAYOUT == FILM_PIX_I010 || LAYOUT == FILM_PIX_P010;   // 10-bit samples in 16-bit words: the code counted is v >> 2
+  constexpr int EPV = F32 ? 4 : U16 ? 8 : 16;   // elements per 16-byte vector
   constexpr int EPW = EPV / 4;        // ... per 32-bit word
   __shared__ uint32_t sub[FILM_HIST_BINS * HIST_COPIES];
   for (int i = threadIdx.x; i < FILM_HIST_BINS * HIST_COPIES; i += FILM_HIST_THREADS) sub[i] = 0;
   __syncthreads();
   const uintptr_t a = reinterpret_cast<uintptr_t>(frame);
   const uint4* base = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(frame) - (a & 15));   // (pointer arithmetic: the loads stay global loads)
-  const int head = (int)(a & 15) / (F32 ? 4 : 1);   // elements of vector 0 in front of the frame
+  const int head = (int)(a & 15) / (F32 ? 4 : U16 ? 2 : 1);   // elements of vector 0 in front of the frame
   const int64_t nvec = (head + n + EPV - 1) / EPV;
   const int copy = threadIdx.x & (HIST_COPIES - 1);
   for (int64_t v = (int64_t)blockIdx.x * FILM_HIST_THREADS + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * FILM_HIST_THREADS) {
@@ -477,10 +696,12 @@ __global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(cons
       if (!whole && (e0 + j < 0 || e0 + j >= n)) continue;
       uint32_t code;
       if (F32) code = quant255(__uint_as_float(w[j]) * 255.f) & 255u;   // film_to_uint8's operations (& 255: a NaN stays inside the bins)
+      else if (LAYOUT == FILM_PIX_I010) code = (w[j / 2] >> ((j & 1) * 16 + 2)) & 255u;    // (w & 1023) >> 2
+      else if (LAYOUT == FILM_PIX_P010) code = (w[j / 2] >> ((j & 1) * 16 + 8)) & 255u;    // (w >> 6) >> 2
       else code = (w[j / 4] >> ((j & 3) * 8)) & 255u;
       int p;
-      if (LAYOUT == FILM_PIX_I420) p = (j >= d1) + (j >= d2);
-      else if (LAYOUT == FILM_PIX_NV12) p = j < d1 ? 0 : 1 + ((par + j) & 1);
+      if (LAYOUT == FILM_PIX_I420 || LAYOUT == FILM_PIX_I010) p = (j >= d1) + (j >= d2);
+      else if (LAYOUT == FILM_PIX_NV12 || LAYOUT == FILM_PIX_P010) p = j < d1 ? 0 : 1 + ((par + j) & 1);
       else { p = c0 + j % 3; p = p >= 3 ? p - 3 : p; }
       atomicAdd(&sub[(p * 256 + (int)code) * HIST_COPIES + copy], 1u);
     }
@@ -500,7 +721,8 @@ __global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(cons
 // that has fewer vectors; the grid-stride loop takes the rest.  (The launcher stands beside its kernel; launch_units: "host" below.)
 hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix, uint32_t* hist, hipStream_t s) {
   const int layout = pix & 0xff;   // (the colour flags do not enter)
-  const bool yuv = layout == FILM_PIX_I420 || layout == FILM_PIX_NV12;
+  const bool yuv16 = layout == FILM_PIX_I010 || layout == FILM_PIX_P010;
+  const bool yuv = layout == FILM_PIX_I420 || layout == FILM_PIX_NV12 || yuv16;
   if (!frame || !hist || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(frame) & 3)) return hipErrorInvalidValue;
   if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !yuv) return hipErrorInvalidValue;
   if (yuv && ((H | W) & 1)) return hipErrorInvalidValue;
@@ -510,11 +732,12 @@ hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix,
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (e == hipSuccess) e = hipMemsetAsync(hist, 0, FILM_HIST_BINS * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
-  const int epv = layout == FILM_PIX_F32 ? 4 : 16;
+  const int epv = layout == FILM_PIX_F32 ? 4 : yuv16 ? 8 : 16;
   const int64_t nvec = (n + epv - 1) / epv + 1;   // (+ 1: a frame that starts inside a vector)
   const int64_t grid = std::min<int64_t>((int64_t)std::max(cus, 1) * FILM_HIST_WG_PER_CU, (nvec + FILM_HIST_THREADS - 1) / FILM_HIST_THREADS);
   auto kernel = layout == FILM_PIX_F32 ? frame_histogram_kernel<FILM_PIX_F32> : layout == FILM_PIX_U8 ? frame_histogram_kernel<FILM_PIX_U8>
-              : layout == FILM_PIX_I420 ? frame_histogram_kernel<FILM_PIX_I420> : frame_histogram_kernel<FILM_PIX_NV12>;
+              : layout == FILM_PIX_I420 ? frame_histogram_kernel<FILM_PIX_I420> : layout == FILM_PIX_NV12 ? frame_histogram_kernel<FILM_PIX_NV12>
+              : layout == FILM_PIX_I010 ? frame_histogram_kernel<FILM_PIX_I010> : frame_histogram_kernel<FILM_PIX_P010>;
   static_assert(FILM_HIST_THREADS == 256, "launch_units starts workgroups of 256");
   return launch_units(kernel, grid * FILM_HIST_THREADS, s, frame, n, plane, hist);   // `grid` workgroups
 }
@@ -559,6 +782,18 @@ const YuvTables& yuv_tables(int pix) {
   return all[((pix & FILM_YUV_BT601) ? 2 : 0) + ((pix & FILM_YUV_FULL) ? 1 : 0)];
 }
 int pix_layout(int pix) { return pix & 0xff; }
+bool pix_is_yuv10(int pix) { return pix_layout(pix) == FILM_PIX_I010 || pix_layout(pix) == FILM_PIX_P010; }
+// The same for a 10-bit layout (include/film_hip.h, "The 10-bit 4:2:0 arithmetic"): the matrix constants are those of the 8-bit tables.
+Yuv10Consts yuv10_consts(int pix) {
+  const YuvTables& t = yuv_tables(pix);
+  const bool full = (pix & FILM_YUV_FULL) != 0;
+  Yuv10Consts k;
+  k.y_sub = full ? 0.0f : 64.0f; k.y_div = full ? 1023.0f : 876.0f; k.c_div = full ? 1023.0f : 896.0f;
+  k.a_r = t.a_r; k.a_b = t.a_b; k.g_b = t.g_b; k.g_r = t.g_r;
+  k.kr = t.kr; k.kg = t.kg; k.kb = t.kb; k.s_b = t.s_b; k.s_r = t.s_r;
+  k.y_scale = full ? 1023.0f : 876.0f; k.y_off = full ? 0.0f : 64.0f; k.c_scale = full ? 1023.0f : 896.0f;
+  return k;
+}
 
 }  // namespace
 
@@ -569,6 +804,13 @@ hipError_t film_launch_cut_tiles(const TileMapParams& p, int pix, hipStream_t s)
   const int layout = pix_layout(pix);
   if (layout == FILM_PIX_F32) return launch_units(ov ? frame_to_tiles_kernel<true> : frame_to_tiles_kernel<false>, (int64_t)p.ntiles * p.TH * p.TW * 3, s, p);
   if (p.ntiles <= 0) return hipSuccess;
+  if (pix_is_yuv10(pix)) {
+    if ((p.H | p.W) & 1) return hipErrorInvalidValue;
+    const bool p010 = layout == FILM_PIX_P010;
+    return launch_units(ov ? (p010 ? frame_yuv10_to_tiles_kernel<true, true> : frame_yuv10_to_tiles_kernel<true, false>)
+                           : (p010 ? frame_yuv10_to_tiles_kernel<false, true> : frame_yuv10_to_tiles_kernel<false, false>),
+                        (int64_t)p.ntiles * p.TH * ((p.TW + 3) / 4), s, p, yuv10_consts(pix));
+  }
   if (layout != FILM_PIX_I420 && layout != FILM_PIX_NV12)
     return launch_units(ov ? frame_u8_to_tiles_kernel<true> : frame_u8_to_tiles_kernel<false>, (int64_t)p.ntiles * p.TH * ((p.TW * 3 + 11) / 12), s, p, u8_table());
   if ((p.H | p.W) & 1) return hipErrorInvalidValue;
@@ -597,8 +839,13 @@ hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipSt
   return launch_units(to_uint8_kernel, (n + 3) / 4, s, src, dst, n);
 }
 
-hipError_t film_launch_rgb_to_yuv420(const float* src, uint8_t* dst, int H, int W, int pix, hipStream_t s) {
+hipError_t film_launch_rgb_to_yuv420(const float* src, void* dst, int H, int W, int pix, hipStream_t s) {
   if (H <= 0 || W <= 0 || ((H | W) & 1)) return hipErrorInvalidValue;
-  return launch_units(pix_layout(pix) == FILM_PIX_NV12 ? rgb_to_yuv420_kernel<true> : rgb_to_yuv420_kernel<false>, (int64_t)(H / 2) * ((W + 7) / 8), s, src, dst, H, W,
-                      yuv_tables(pix));
+  if (pix_is_yuv10(pix)) {
+    if (reinterpret_cast<uintptr_t>(dst) & 1) return hipErrorInvalidValue;
+    return launch_units(pix_layout(pix) == FILM_PIX_P010 ? rgb_to_yuv10_kernel<true> : rgb_to_yuv10_kernel<false>, (int64_t)(H / 2) * ((W + 7) / 8), s, src,
+                        static_cast<uint16_t*>(dst), H, W, yuv10_consts(pix));
+  }
+  return launch_units(pix_layout(pix) == FILM_PIX_NV12 ? rgb_to_yuv420_kernel<true> : rgb_to_yuv420_kernel<false>, (int64_t)(H / 2) * ((W + 7) / 8), s, src,
+                      static_cast<uint8_t*>(dst), H, W, yuv_tables(pix));
 }

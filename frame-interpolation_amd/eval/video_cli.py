@@ -1,7 +1,8 @@
 r"""Doubles the frame rate of a YUV4MPEG2 (.y4m) video: n frames in, 2 n - 1 frames out - every input frame verbatim, with the
 mid-frame of each consecutive pair between them.  Video in, video out: the frames stay 8-bit Y'CbCr 4:2:0 from the file to the GPU and
 back (a frame stream with pix 'i420': the colour conversion runs inside the engine's tile cut and quantisation, one feature extraction
-per frame), no PNGs, no ffmpeg, a few frames of memory.
+per frame), no PNGs, no ffmpeg, a few frames of memory.  A 10-bit stream (C420p10, `ffmpeg -pix_fmt yuv420p10le`) stays 10-bit the same
+way (pix 'i010'): no flag is needed, the header says it.
 
   cd frame-interpolation_amd
   python -m eval.video_cli --model_path <model dir> --input in.y4m --output out.y4m
@@ -12,7 +13,7 @@ of consecutive frames' sample histograms, in permille of its maximum): across a 
 cut is written a second time instead (a frame hold), so the output keeps its 2 n - 1 frames at a uniform rate.  No value is recommended:
 the detector's hit and miss rates on real footage are unmeasured.
 
-The output header keeps the input's tokens with the frame rate (F) doubled.  What is read: film_hip/y4m.py (8-bit 4:2:0, progressive).
+The output header keeps the input's tokens with the frame rate (F) doubled.  What is read: film_hip/y4m.py (8-bit and 10-bit 4:2:0, progressive).
 """
 import argparse
 import sys
@@ -37,7 +38,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--block_overlap_width', type=int, default=0, help='The same for columns.')
     ap.add_argument('--matrix', choices=['bt709', 'bt601'], default='bt709', help="The Y'CbCr matrix of the video.")
     ap.add_argument('--full_range', action='store_true', default=None,
-                    help='Full-range samples (0..255); default: what the header says (XCOLORRANGE=FULL), else limited range.')
+                    help='Full-range samples (0..255, 10-bit: 0..1023); default: what the header says (XCOLORRANGE=FULL), else limited range.')
     ap.add_argument('--scene_cut', type=int, default=0, metavar='PERMILLE',
                     help='Treat a pair of frames whose histogram distance reaches this many permille (1..1000) as a scene cut: the frame '
                          'before the cut is held instead of a mid-frame.  0 (default): off.  No value is recommended (unmeasured on footage).')
@@ -46,14 +47,14 @@ def build_parser() -> argparse.ArgumentParser:
 
 def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', full_range: Optional[bool] = None, scene_cut: int = 0,
                       cuts: Optional[list] = None) -> int:
-    """Streams reader's frames through an I420 stream of `it` (an eval.interpolator.Interpolator) and writes the doubled video to the
+    """Streams reader's frames through an I420 stream (I010 for a 10-bit reader) of `it` (an eval.interpolator.Interpolator) and writes the doubled video to the
     binary file object `out`.  Returns the number of frames written.  One input frame and one mid-frame are alive at a time (two input
     frames with scene_cut).  scene_cut > 0 (permille, engine option "scene_cut"): a push after the first that returns no mid-frame is
     a scene cut - the previous input frame is written again in the mid-frame's place; `cuts` (a list) receives the index of every input
     frame that starts a new scene."""
     full = reader.full_range if full_range is None else bool(full_range)
     writer = y4m.Y4MWriter(out, y4m.double_rate(reader.tokens))
-    with it.open_stream(reader.height, reader.width, pix='i420', matrix=matrix, full_range=full,
+    with it.open_stream(reader.height, reader.width, pix='i010' if getattr(reader, 'depth', 8) == 10 else 'i420', matrix=matrix, full_range=full,
                         **({'scene_cut': int(scene_cut)} if scene_cut else {})) as st:
         prev = None
         for i, frame in enumerate(reader):
@@ -73,7 +74,7 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     fin = sys.stdin.buffer if args.input == '-' else open(args.input, 'rb')
     try:
-        reader = y4m.Y4MReader(fin)       # (the header's refusals come before the model is loaded)
+        reader = y4m.Y4MReader(fin, depths=(8, 10))       # (the header's refusals come before the model is loaded)
         overlap = (args.block_overlap_height, args.block_overlap_width)
         it = interpolator_lib.Interpolator(args.model_path, args.align, [args.block_height, args.block_width],
                                            **({'block_overlap': overlap} if any(overlap) else {}))

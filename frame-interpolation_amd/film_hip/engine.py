@@ -28,8 +28,10 @@ FILM_ERR_STATE = -2
 FILM_ERR_NO_DEVICE = -3
 FILM_ERR_NOMEM = -5
 # pixel types of a frame stream (film_stream_open)
-FILM_PIX_F32, FILM_PIX_U8, FILM_PIX_I420, FILM_PIX_NV12 = 0, 1, 16, 17
-PIX = {'f32': (FILM_PIX_F32, np.float32), 'u8': (FILM_PIX_U8, np.uint8), 'i420': (FILM_PIX_I420, np.uint8), 'nv12': (FILM_PIX_NV12, np.uint8)}
+FILM_PIX_F32, FILM_PIX_U8, FILM_PIX_I420, FILM_PIX_NV12, FILM_PIX_I010, FILM_PIX_P010 = 0, 1, 16, 17, 32, 33
+PIX = {'f32': (FILM_PIX_F32, np.float32), 'u8': (FILM_PIX_U8, np.uint8), 'i420': (FILM_PIX_I420, np.uint8), 'nv12': (FILM_PIX_NV12, np.uint8),
+       'i010': (FILM_PIX_I010, np.uint16), 'p010': (FILM_PIX_P010, np.uint16)}
+YUV420 = ('i420', 'nv12', 'i010', 'p010')      # the 4:2:0 layouts: a frame is an array [H * 3 // 2, W] of samples
 # colour flags of the 4:2:0 pixel types (added to the layout code)
 FILM_YUV_BT601, FILM_YUV_FULL = 0x100, 0x400
 YUV_MATRIX = {'bt709': 0, 'bt601': FILM_YUV_BT601}
@@ -192,7 +194,7 @@ def frame_histogram_device(ptr: int, h: int, w: int, hist_ptr: int, pix: str = '
                            stream: Optional[int] = None) -> None:
     """film_frame_histogram: the 3 x 256 sample histogram (include/film_hip.h, "Scene cuts") of ONE h x w device frame of pixel type `pix`
     into 768 device uint32 at hist_ptr (overwritten), asynchronous on `stream` of the current device.  ptr must be 4-byte aligned and an
-    8-bit frame lie in an allocation of whole 32-bit words.  Needs no engine."""
+    8-bit frame lie in an allocation of whole 32-bit words.  A 10-bit sample ('i010' | 'p010') counts in the bin of its code >> 2.  Needs no engine."""
     rc = load_library().film_frame_histogram(ctypes.c_void_p(ptr), int(h), int(w), pix_code(pix, matrix, full_range), ctypes.c_void_p(hist_ptr),
                                              ctypes.c_void_p(stream) if stream else None)
     if rc != 0:
@@ -204,7 +206,8 @@ class FilmStream:
     between it and the frame pushed before - bit-identical to interpolate_frames(previous, frame) - with one feature extraction per
     frame.  Frames and results are [H,W,3] float32 ('f32') or uint8 ('u8': x = u8 / 255, result = eval.util.to_uint8's bytes), or
     8-bit Y'CbCr 4:2:0 frames ('i420', 'nv12') as uint8 [H * 3 // 2, W]: the Y plane, then the Cb and Cr planes (I420) or the plane of
-    CbCr pairs (NV12), with `matrix` 'bt709' | 'bt601' and limited or full range (the arithmetic: include/film_hip.h).
+    CbCr pairs (NV12), with `matrix` 'bt709' | 'bt601' and limited or full range (the arithmetic: include/film_hip.h); or 10-bit 4:2:0
+    frames ('i010': the code in bits 0-9, = yuv420p10le; 'p010': the code in bits 6-15) as uint16 [H * 3 // 2, W] with the same planes.
     With the engine option "scene_cut" > 0 (FilmEngine.open_stream(scene_cut=...)) a push that the histogram rule calls a scene cut returns
     None / False like a first push, and cut_info() tells the two apart.
     One stream per engine at a time; use it as a context manager or close() it."""
@@ -213,7 +216,7 @@ class FilmStream:
                  full_range: bool = False):
         self._code = pix_code(pix, matrix, full_range)
         self._eng = engine
-        self.shape = (int(h) * 3 // 2, int(w)) if pix in ('i420', 'nv12') else (int(h), int(w), 3)
+        self.shape = (int(h) * 3 // 2, int(w)) if pix in YUV420 else (int(h), int(w), 3)
         self.pix = pix
         self.dtype = PIX[pix][1]
         bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
@@ -505,7 +508,8 @@ class FilmEngine:
     def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32', matrix: str = 'bt709',
                     full_range: bool = False, scene_cut: int = 0) -> FilmStream:
         """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix 'f32' | 'u8' |
-        'i420' | 'nv12', the latter two (8-bit 4:2:0, h and w even) with the colour `matrix` 'bt709' | 'bt601' and limited or full range.
+        'i420' | 'nv12' | 'i010' | 'p010', the latter four (8-bit and 10-bit 4:2:0, h and w even) with the colour `matrix` 'bt709' | 'bt601' and
+        limited or full range.
         scene_cut: 0 .. 1000 permille; non-zero sets the engine option "scene_cut" (include/film_hip.h) before the stream opens - a handle
         option like block_overlap, so it STAYS set for later streams of this engine until set_option('scene_cut', 0); 0 (default) leaves
         the engine as it is."""
@@ -565,7 +569,8 @@ class FilmEngine:
 
     def to_yuv420_device(self, src_ptr: int, dst_ptr: int, h: int, w: int, pix: str = 'i420', matrix: str = 'bt709',
                          full_range: bool = False, stream: Optional[int] = None) -> None:
-        """film_to_yuv420: h x w x 3 device floats -> one 4:2:0 frame of h * w * 3 // 2 device bytes ('i420' | 'nv12'), asynchronous."""
+        """film_to_yuv420: h x w x 3 device floats -> one 4:2:0 frame of h * w * 3 // 2 device bytes ('i420' | 'nv12') or 16-bit words ('i010' |
+        'p010': dst_ptr 2-byte aligned), asynchronous."""
         rc = self._lib.film_to_yuv420(ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), int(h), int(w), pix_code(pix, matrix, full_range),
                                       ctypes.c_void_p(stream) if stream else None)
         if rc != 0:
@@ -661,7 +666,7 @@ class FilmEngine:
 
     def debug_yuv_cut(self, frames_ptr: int, tiles_ptr: int, b: int, h: int, w: int, align: Optional[int], block_shape, tile0: int,
                       ntiles: int, pix: str = 'i420', matrix: str = 'bt709', full_range: bool = False, stream: Optional[int] = None) -> None:
-        """film_debug_yuv_cut: ONE cut of tiles [tile0, tile0 + ntiles) of b 4:2:0 frames (h * w * 3 // 2 bytes each, in a 4-byte aligned
+        """film_debug_yuv_cut: ONE cut of tiles [tile0, tile0 + ntiles) of b 4:2:0 frames (h * w * 3 // 2 samples each, in a 4-byte aligned
         allocation of whole 32-bit words) into float32 RGB tiles, with the geometry of tiling(h, w, align, block_shape)."""
         bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
         self._check(self._lib.film_debug_yuv_cut(self._h, pix_code(pix, matrix, full_range), ctypes.c_void_p(frames_ptr),

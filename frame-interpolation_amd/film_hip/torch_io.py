@@ -11,7 +11,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .engine import FilmEngine, frame_histogram_device
+from .engine import PIX, YUV420, FilmEngine, frame_histogram_device
 
 
 def pinned_frame(shape) -> 'np.ndarray':
@@ -50,13 +50,22 @@ def patches_to_image(patches: torch.Tensor, block_shape: List[int]) -> torch.Ten
     return patches.reshape(bh, bw, ph, pw, c).permute(0, 2, 1, 3, 4).reshape(1, bh * ph, bw * pw, c).contiguous()
 
 
+def pix_dtypes(pix: str):
+    """The torch dtypes a frame of pixel type `pix` may have.  A 10-bit frame is 16-bit words: torch.int16 is taken as a bit pattern, and
+    torch.uint16 where the installed torch has it."""
+    if PIX[pix][1].__name__ == 'uint16':
+        return (torch.int16,) + ((torch.uint16,) if hasattr(torch, 'uint16') else ())
+    return (torch.float32,) if pix == 'f32' else (torch.uint8,)
+
+
 def frame_histogram(frame: torch.Tensor, pix: str = 'u8') -> torch.Tensor:
     """film_frame_histogram of one CUDA frame: [H,W,3] uint8 ('u8') or float32 ('f32'), or an 8-bit 4:2:0 frame as uint8 [H * 3 // 2, W]
-    ('i420' | 'nv12') -> int64 [3, 256] on the frame's device: the number of samples of every plane with every 8-bit code (include/film_hip.h,
-    "Scene cuts").  Asynchronous on the current torch stream."""
-    assert frame.is_cuda and frame.dtype == (torch.float32 if pix == 'f32' else torch.uint8)
+    ('i420' | 'nv12'), or a 10-bit one as int16 / uint16 [H * 3 // 2, W] ('i010' | 'p010': bin = code >> 2) -> int64 [3, 256] on the frame's
+    device: the number of samples of every plane with every 8-bit code (include/film_hip.h, "Scene cuts").  Asynchronous on the current
+    torch stream."""
+    assert frame.is_cuda and frame.dtype in pix_dtypes(pix)
     frame = frame.contiguous()
-    if pix in ('i420', 'nv12'):
+    if pix in YUV420:
         assert frame.dim() == 2 and frame.shape[0] % 3 == 0
         h, w = frame.shape[0] * 2 // 3, frame.shape[1]
     else:
@@ -70,7 +79,7 @@ def frame_histogram(frame: torch.Tensor, pix: str = 'u8') -> torch.Tensor:
 
 class DeviceStream:
     """A frame stream on frames that already live in HBM (DeviceInterpolator.stream): push(frame) takes a [H,W,3] CUDA tensor, float32
-    or uint8 as opened (a 4:2:0 stream: uint8 [H * 3 // 2, W]), and returns the mid-frame between it and the frame pushed before as a new tensor of the same kind - None for
+    or uint8 as opened (a 4:2:0 stream: uint8 [H * 3 // 2, W]; a 10-bit one: int16 or uint16 of that shape), and returns the mid-frame between it and the frame pushed before as a new tensor of the same kind - None for
     the first frame after opening or reset(), and for a frame that the engine option "scene_cut" found to start a new scene.  Asynchronous on the
     current torch stream (with "scene_cut" > 0 a push waits for the frame's histogram: include/film_hip.h)."""
 
@@ -78,10 +87,10 @@ class DeviceStream:
                  scene_cut: int = 0):
         self._stream = engine.open_stream(h, w, align=align, block_shape=block_shape, pix=pix, matrix=matrix, full_range=full_range,
                                           scene_cut=scene_cut)
-        self._dtype = torch.float32 if pix == 'f32' else torch.uint8
+        self._dtypes = pix_dtypes(pix)
 
     def push(self, frame: torch.Tensor) -> Optional[torch.Tensor]:
-        assert frame.is_cuda and frame.dtype == self._dtype and tuple(frame.shape) == self._stream.shape
+        assert frame.is_cuda and frame.dtype in self._dtypes and tuple(frame.shape) == self._stream.shape
         frame = frame.contiguous()
         out = torch.empty_like(frame)
         stream = torch.cuda.current_stream(frame.device).cuda_stream
@@ -156,6 +165,8 @@ class DeviceInterpolator:
         """Extension: a frame stream of h x w frames (film_stream_*), padded / tiled like batch(): push one CUDA tensor at a time, float32
         or ('u8') uint8, and get the mid-frame with the frame before - bit-identical to batch(previous, frame), one extraction per frame.
         'i420' / 'nv12': 8-bit 4:2:0 frames as uint8 [h * 3 // 2, w] tensors, converted inside the cut and the quantisation.
+        'i010' / 'p010': 10-bit 4:2:0 frames as 16-bit tensors of that shape - torch.int16 (taken as a bit pattern) or torch.uint16 where
+        the installed torch has it; the mid-frame comes back in the dtype that was pushed.
         scene_cut (0 .. 1000 permille): non-zero sets the ENGINE option "scene_cut" before the stream opens, and it stays set (like block_overlap)."""
         bs = self._block_shape
         return DeviceStream(self._engine, h, w, self._align, bs if bs is not None and bs[0] * bs[1] > 1 else None, pix, matrix, full_range,

@@ -1,13 +1,17 @@
-"""Reader and writer of YUV4MPEG2 (.y4m) streams of 8-bit 4:2:0 frames - the frames a 4:2:0 frame stream takes (film_stream_open with
-FILM_PIX_I420: FilmEngine.open_stream(pix='i420')), so that video goes in and out without PNGs and without ffmpeg.
+"""Reader and writer of YUV4MPEG2 (.y4m) streams of 8-bit and 10-bit 4:2:0 frames - the frames a 4:2:0 frame stream takes (film_stream_open
+with FILM_PIX_I420 / FILM_PIX_I010: FilmEngine.open_stream(pix='i420' | 'i010')), so that video goes in and out without PNGs and without ffmpeg.
 
 A stream is one header line, "YUV4MPEG2" and space-separated tokens - W<width> H<height> F<num>:<den> I<interlacing> A<n>:<d>
 C<colour space> X<anything> ... - then per frame a line "FRAME[ <parameters>]" and the payload: Y [H][W], Cb [H/2][W/2], Cr [H/2][W/2],
-which is the I420 layout.  A frame is handed on as one uint8 array [H * 3 // 2, W] (FilmStream.shape).
+which is the I420 layout.  A frame is handed on as one uint8 array [H * 3 // 2, W] (FilmStream.shape).  C420p10 (what
+`ffmpeg -pix_fmt yuv420p10le` pipes) holds the same planes with one little-endian 16-bit word per sample, the 10-bit code in bits 0-9 - the
+I010 layout; such a frame is handed on as one uint16 array [H * 3 // 2, W], and only by a reader opened with depths=(8, 10): a caller
+written for uint8 arrays never receives uint16 by surprise.
 
 Accepted: 8-bit C420, C420jpeg, C420mpeg2, C420paldv (no C token means 420) - the three differ in where the chroma samples sit, which
 the engine's box treatment (include/film_hip.h) does not tell apart; Ip, I? or no I token.  Refused, with the token in the message:
-4:2:2, 4:4:4, mono, 10-bit and deeper, interlaced material, odd sizes.  XCOLORRANGE=FULL marks full-range samples.
+4:2:2, 4:4:4, mono, 12-bit and deeper (and 10-bit by a reader that was not asked for it), interlaced material, odd sizes.
+XCOLORRANGE=FULL marks full-range samples.
 """
 from __future__ import annotations
 
@@ -18,6 +22,7 @@ import numpy as np
 MAGIC = b'YUV4MPEG2'
 FRAME = b'FRAME'
 C420 = ('420', '420jpeg', '420mpeg2', '420paldv')
+C420_10 = ('420p10',)      # 10-bit 4:2:0, little-endian 16-bit words
 _MAX_LINE = 4096
 
 
@@ -63,8 +68,11 @@ def double_rate(tokens: Sequence[str]) -> List[str]:
     return out
 
 
-def parse_header(line: bytes) -> Tuple[int, int, List[str]]:
-    """(width, height, tokens) of a header line; the refusals of this module."""
+def parse_header(line: bytes, depths: Sequence[int] = (8,)) -> Tuple[int, int, List[str]]:
+    """(width, height, tokens) of a header line; the refusals of this module.  depths: the sample depths the caller takes, 8 and / or 10."""
+    if not depths or any(d not in (8, 10) for d in depths):
+        raise ValueError(f'depths must name 8 and / or 10, got {depths!r}')
+    colours = (C420 if 8 in depths else ()) + (C420_10 if 10 in depths else ())
     parts = line.decode('ascii', 'replace').split()
     if not parts or parts[0] != MAGIC.decode():
         raise Y4MError(f'not a YUV4MPEG2 stream: it starts with {line[:16]!r}')
@@ -79,7 +87,13 @@ def parse_header(line: bytes) -> Tuple[int, int, List[str]]:
                 w = int(val)
             else:
                 h = int(val)
-        elif key == 'C' and val not in C420:
+        elif key == 'C' and val not in colours:
+            if val in C420 + C420_10:
+                raise Y4MError(f'colour space token {t!r}: this reader was opened for {" / ".join(str(d) for d in depths)}-bit samples '
+                               f'(depths={tuple(depths)!r})')
+            if 10 in depths:
+                raise Y4MError(f'colour space token {t!r}: only 4:2:0 with 8-bit or 10-bit samples ({", ".join("C" + c for c in C420 + C420_10)}) '
+                               'is read - no 4:2:2, 4:4:4, mono, 12-bit or deeper')
             raise Y4MError(f'colour space token {t!r}: only 8-bit 4:2:0 ({", ".join("C" + c for c in C420)}) is read - no 4:2:2, 4:4:4, '
                            'mono, 10-bit or deeper')
         elif key == 'I' and val not in ('p', '?'):
@@ -91,16 +105,23 @@ def parse_header(line: bytes) -> Tuple[int, int, List[str]]:
     return w, h, tokens
 
 
-class Y4MReader:
-    """Iterates over the frames of a YUV4MPEG2 stream (a binary file object) as uint8 arrays [H * 3 // 2, W]."""
+def depth_of(tokens: Sequence[str]) -> int:
+    """The sample depth the (accepted) tokens of a header name: 10 for C420p10, else 8."""
+    return 10 if any(t[:1] == 'C' and t[1:] in C420_10 for t in tokens) else 8
 
-    def __init__(self, f: BinaryIO):
+
+class Y4MReader:
+    """Iterates over the frames of a YUV4MPEG2 stream (a binary file object) as uint8 arrays [H * 3 // 2, W].  depths=(8, 10) also takes
+    C420p10 streams, whose frames are uint16 arrays of that shape (decoded from little-endian bytes); `depth` says which it is."""
+
+    def __init__(self, f: BinaryIO, depths: Sequence[int] = (8,)):
         self._f = f
         line = _read_line(f)
         if not line:
             raise Y4MError('empty stream: no YUV4MPEG2 header')
-        self.width, self.height, self.tokens = parse_header(line)
-        self.frame_bytes = self.width * self.height * 3 // 2
+        self.width, self.height, self.tokens = parse_header(line, depths)
+        self.depth = depth_of(self.tokens)
+        self.frame_bytes = self.width * self.height * 3 // 2 * (2 if self.depth == 10 else 1)
         self.frames_read = 0
 
     @property
@@ -126,6 +147,8 @@ class Y4MReader:
         if len(data) != self.frame_bytes:
             raise Y4MError(f'truncated: frame {self.frames_read} has {len(data)} of {self.frame_bytes} bytes')
         self.frames_read += 1
+        if self.depth == 10:
+            return np.frombuffer(data, '<u2').astype(np.uint16, copy=False).reshape(self.height * 3 // 2, self.width)
         return np.frombuffer(data, np.uint8).reshape(self.height * 3 // 2, self.width)
 
     def __iter__(self) -> Iterator[np.ndarray]:
@@ -138,24 +161,26 @@ class Y4MReader:
 
 class Y4MWriter:
     """Writes a YUV4MPEG2 stream: the header from `tokens` (as Y4MReader.tokens; W and H among them, checked like a reader's), then
-    one frame per write()."""
+    one frame per write(): uint8 arrays, or uint16 arrays (written as little-endian words) when the tokens say C420p10."""
 
     def __init__(self, f: BinaryIO, tokens: Sequence[str]):
         self._f = f
         self.tokens = list(tokens)
-        self.width, self.height, _ = parse_header(' '.join([MAGIC.decode()] + self.tokens).encode('ascii'))
+        self.width, self.height, _ = parse_header(' '.join([MAGIC.decode()] + self.tokens).encode('ascii'), (8, 10))
+        self.depth = depth_of(self.tokens)
         self.frames_written = 0
         f.write(b' '.join([MAGIC] + [t.encode('ascii') for t in self.tokens]) + b'\n')
 
     def write(self, frame: np.ndarray) -> None:
         a = np.ascontiguousarray(frame)
-        if a.dtype != np.uint8 or a.shape != (self.height * 3 // 2, self.width):
-            raise ValueError(f'expected a uint8 array of shape {(self.height * 3 // 2, self.width)}, got {a.dtype} {a.shape}')
+        want = np.uint16 if self.depth == 10 else np.uint8
+        if a.dtype != want or a.shape != (self.height * 3 // 2, self.width):
+            raise ValueError(f'expected a {np.dtype(want).name} array of shape {(self.height * 3 // 2, self.width)}, got {a.dtype} {a.shape}')
         self._f.write(FRAME + b'\n')
-        self._f.write(a.tobytes())
+        self._f.write(a.astype('<u2', copy=False).tobytes() if self.depth == 10 else a.tobytes())
         self.frames_written += 1
 
 
 def header_tokens(width: int, height: int, rate: Tuple[int, int] = (30, 1), full_range: bool = False, colour: str = '420jpeg') -> List[str]:
-    """Tokens of a progressive 8-bit 4:2:0 stream with square pixels."""
+    """Tokens of a progressive 4:2:0 stream with square pixels: 8-bit, or 10-bit with colour='420p10'."""
     return [f'W{width}', f'H{height}', f'F{rate[0]}:{rate[1]}', 'Ip', 'A1:1', f'C{colour}'] + (['XCOLORRANGE=FULL'] if full_range else [])

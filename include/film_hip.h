@@ -161,7 +161,7 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                      4K frame cut 4 x 4 would run as two chunks of 8) is FILM_ERR_INVALID with the limit in the message - use a finer
  *                      block shape - and a workspace that cannot be allocated is FILM_ERR_NOMEM: a stream neither chunks a frame
  *                      nor halves on out-of-memory.  Plan-only handle: FILM_ERR_NO_DEVICE; before film_finalize: FILM_ERR_STATE.
- *   film_stream_push   frame [H,W,3] in, mid [H,W,3] out, both of the stream's pixel type (a 4:2:0 stream: H * W * 3 / 2 bytes each).  The first push after open / reset sets
+ *   film_stream_push   frame [H,W,3] in, mid [H,W,3] out, both of the stream's pixel type (a 4:2:0 stream: H * W * 3 / 2 samples each - bytes, or 16-bit words for the 10-bit layouts).  The first push after open / reset sets
  *                      *produced = 0 and only cuts the frame into its tiles and runs the image pyramid and the feature extractor
  *                      (`mid` is not touched and may be NULL); every later push sets *produced = 1 and writes `mid`, bit-identical
  *                      to film_interpolate(previous frame, frame, 1, H, W, align, block_h, block_w) under the handle's current
@@ -194,8 +194,14 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  * whole words). */
 #define FILM_PIX_I420   16      /* Y[H][W], Cb[H/2][W/2], Cr[H/2][W/2], contiguous: H*W*3/2 bytes */
 #define FILM_PIX_NV12   17      /* Y[H][W], CbCr[H/2][W/2][2] interleaved: H*W*3/2 bytes */
+/* 10-bit Y'CbCr 4:2:0 frames: the same planes with one little-endian uint16 per sample, H * W * 3 bytes a frame - what a hardware decoder hands over
+ * for HEVC Main10, AV1 and VP9 profile 2 (P010) and what `ffmpeg -pix_fmt yuv420p10le` pipes (I010).  Same flags, same refusals (even sizes; any other bit;
+ * device pointers 4-byte aligned); fused into the cut and the quantisation like the 8-bit layouts ("The 10-bit 4:2:0 arithmetic" below).  The transfer
+ * function (PQ, HLG, gamma) is not the engine's business: the network sees the non-linear samples it was given. */
+#define FILM_PIX_I010   32      /* Y[H][W], Cb[H/2][W/2], Cr[H/2][W/2], little-endian uint16, code in bits 0-9 (= yuv420p10le, Y4M C420p10): H*W*3 bytes */
+#define FILM_PIX_P010   33      /* Y[H][W], CbCr[H/2][W/2][2], little-endian uint16, code in bits 6-15 (what VCN / VA-API / D3D decoders emit): H*W*3 bytes */
 #define FILM_YUV_BT601  0x100   /* matrix: absent = BT.709 */
-#define FILM_YUV_FULL   0x400   /* range: absent = limited (16..235 / 16..240) */
+#define FILM_YUV_FULL   0x400   /* range: absent = limited (8-bit 16..235 / 16..240, 10-bit 64..940 / 64..960) */
 /* The 4:2:0 arithmetic.  Every operation is float32 with one rounding, no fused multiply-add.  (Kr, Kb) = (0.2126, 0.0722) for BT.709,
  * (0.299, 0.114) for BT.601, Kg = 1 - Kr - Kb; every constant below is computed from them in double and rounded to float32 once.
  *   In (bytes -> RGB).  Per-byte tables, IEEE division on the host: limited range y[v] = (float(v) - 16) / 219, c[v] = (float(v) - 128) / 224;
@@ -212,8 +218,20 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *     chroma of the 2 x 2 block (j, k): m = ((c[2j][2k] + c[2j][2k+1]) + (c[2j+1][2k] + c[2j+1][2k+1])) * 0.25
  *     q(v) = uint8(min(max(v, 0), 255) + 0.5);  limited: Y = q(Yf * 219 + 16), C = q(m * 224 + 128);  full: Y = q(Yf * 255), C = q(m * 255 + 128).
  *   Replicate in and box mean out are inverse to each other: a frame whose RGB stays inside the gamut returns byte for byte.
- *   Not provided: 10-bit (P010) and 4:2:2 / 4:4:4 layouts; sited bilinear chroma (MPEG-2 left siting - the box treatment is consistent in
- *   and out); 4:2:0 frames on film_interpolate / film_interpolate_sequence themselves (film_to_yuv420 converts their results).
+ * The 10-bit 4:2:0 arithmetic (FILM_PIX_I010 / FILM_PIX_P010).  The matrix constants, the operation order, the replicated chroma in, the 2 x 2 box
+ * mean out in the same summation order and the places of the clips are those of the 8-bit arithmetic above; every operation is float32 with one
+ * rounding, no fused multiply-add.  Only the codes change.
+ *   Code of a stored word w.  I010: v = w & 1023 (the upper six bits are ignored).  P010: v = w >> 6 (the lower six bits are ignored).  0 <= v <= 1023
+ *     for every word.
+ *   In (words -> RGB).  IEEE float32 division: limited range y[v] = (float(v) - 64) / 876, c[v] = (float(v) - 512) / 896; full range
+ *     y[v] = float(v) / 1023, c[v] = (float(v) - 512) / 1023.  Then R, G, B as above.
+ *   Out (RGB -> words).  Yf, cbf, crf and m as above; q10(x) = uint16(min(max(x, 0), 1023) + 0.5);  limited: Y = q10(Yf * 876 + 64),
+ *     C = q10(m * 896 + 512);  full: Y = q10(Yf * 1023), C = q10(m * 1023 + 512).  I010 stores the code, P010 stores code << 6: the ignored bits
+ *     are written as zero.
+ *   A frame whose decoded RGB stays inside the gamut returns code for code (tests/test_yuv10_cpu.py checks it for all four colour settings).
+ *   Not provided (at either depth): 12-bit and deeper samples; 4:2:2 / 4:4:4 layouts; a BT.2020 matrix (no flag bit selects one: 0x200 / 0x800 and every other bit stay
+ *   refused); sited bilinear chroma (MPEG-2 left siting - the box treatment is consistent in and out); 4:2:0 frames on film_interpolate /
+ *   film_interpolate_sequence themselves (film_to_yuv420 converts their results).
  * Scene cuts.  Across a cut a stream would interpolate between two unrelated pictures.  The engine offers an exact per-frame statistic
  * computed where the frame already lies, an integer decision rule, and a stream that resets itself (option "scene_cut").  Integers only.
  *   Histogram of a frame: uint32_t hist[3][256], hist[p][v] = the number of samples of plane p with 8-bit code v.
@@ -222,6 +240,8 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                     operations in the same order.
  *     FILM_PIX_I420 / FILM_PIX_NV12   plane 0 = the Y bytes (H * W samples), planes 1 and 2 = the Cb and Cr bytes (H/2 * W/2 samples each).
  *                     The colour flags are validated as everywhere else and otherwise ignored: the statistic is about the stored codes.
+ *     FILM_PIX_I010 / FILM_PIX_P010   the same planes and sample counts; a sample with 10-bit code v counts in bin v >> 2, so the [3][256]
+ *                     layout, S and the rule below do not change.
  *     Every plane sums to its sample count.  S = the samples of one frame: 3 H W for RGB, 3 H W / 2 for 4:2:0.
  *   Distance: D = sum over p, v of |h1[p][v] - h0[p][v]|, an int64 with 0 <= D <= 2 S; the score is D / (2 S).  Moving content leaves it
  *     at 0 (a permutation of the samples has the same histogram); two frames with no code in common give 1.
@@ -233,7 +253,8 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *   film_frame_histogram: the histogram of ONE H x W frame of pixel type `pix`, like film_to_uint8 / film_to_yuv420 on DEVICE pointers and
  *     without a handle: asynchronous on `stream` (NULL: the default stream) of the current device.  hist_dev receives 768 uint32_t
  *     ([3][256]); the call overwrites them - it never accumulates.  frame_dev must be 4-byte aligned and, for the 8-bit types, lie in an
- *     allocation of whole 32-bit words (as for the 8-bit cuts: the last partial word is read, only the frame's bytes are counted).
+ *     allocation of whole 32-bit words (as for the 8-bit cuts: the last partial word is read, only the frame's bytes are counted; a 10-bit frame is
+ *     whole words).
  *     FILM_ERR_INVALID: a NULL pointer, H or W < 1, H * W >= 2^31, a pix the stream entry points refuse (odd sizes with 4:2:0 included),
  *     a frame_dev that is not 4-byte aligned. */
 int film_frame_histogram(const void* frame_dev, int H, int W, int pix, uint32_t* hist_dev, void* stream);
@@ -420,9 +441,9 @@ int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int 
  * [0, B * block_h * block_w).  Then FILM_ERR_NO_DEVICE on a plan-only handle.  Not on any forward path. */
 int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h,
                         int block_w, int tile0, int ntiles, void* stream);
-/* film_debug_yuv_cut: ONE cut of a batch of B 4:2:0 frames (frame b at byte b * H * W * 3 / 2 of frames_dev, a 4-byte aligned DEVICE
- * pointer into an allocation of whole 32-bit words) into float32 RGB tiles: film_debug_tile_map mode 0 with pix = FILM_PIX_I420 /
- * FILM_PIX_NV12 plus colour flags - same geometry, same tile buffer, same refusals (and those of `pix` above), reached through the
+/* film_debug_yuv_cut: ONE cut of a batch of B 4:2:0 frames (frame b at byte b * H * W * 3 / 2 of frames_dev - b * H * W * 3 for a 10-bit layout -,
+ * a 4-byte aligned DEVICE pointer into an allocation of whole 32-bit words) into float32 RGB tiles: film_debug_tile_map mode 0 with pix =
+ * FILM_PIX_I420 / FILM_PIX_NV12 / FILM_PIX_I010 / FILM_PIX_P010 plus colour flags - same geometry, same tile buffer, same refusals (and those of `pix` above), reached through the
  * dispatch a 4:2:0 stream's push cuts with (tests/test_yuv_gpu.py).  Not on any forward path. */
 int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h, int block_w,
                        int tile0, int ntiles, void* stream);
@@ -451,8 +472,9 @@ int film_image_metrics(film_t* h, const float* pred, const float* ref, int B, in
  * current device.  The frames of a recursion then cross PCIe as 1 byte per value instead of 4.  Returns FILM_OK or a negative error. */
 int film_to_uint8(const float* src, unsigned char* dst, int64_t n, void* stream);
 
-/* "Out" of the 4:2:0 arithmetic above on the device: src float32 [H][W][3] -> dst, one frame of H * W * 3 / 2 bytes in the layout and
- * colour setting `pix` names (FILM_PIX_I420 / FILM_PIX_NV12 plus flags).  DEVICE pointers, any alignment of dst (whole 32-bit words are
+/* "Out" of the 4:2:0 arithmetic above on the device: src float32 [H][W][3] -> dst, one frame of H * W * 3 / 2 samples in the layout and
+ * colour setting `pix` names (FILM_PIX_I420 / FILM_PIX_NV12: bytes; FILM_PIX_I010 / FILM_PIX_P010: 16-bit words; plus flags).  DEVICE pointers, any
+ * alignment of dst for the 8-bit layouts, 2-byte alignment for the 10-bit ones (else FILM_ERR_INVALID; whole 32-bit words are
  * stored where it allows); asynchronous on `stream` (NULL: the default stream) of the current device, like film_to_uint8.  What a 4:2:0
  * stream's push quantises its result with; results of film_interpolate / film_interpolate_sequence leave as 4:2:0 through it too.
  * FILM_ERR_INVALID: a NULL pointer, H or W < 1 or odd, pix no 4:2:0 pixel type. */

@@ -6,11 +6,14 @@
 A round = one fresh worker process per tree, baseline first: the baseline worker times `pair` (film_interpolate, device-resident, one
 pair per call - what a frame-by-frame caller had before), this tree's worker times `pair` too (the two agree unless the trees differ
 in what a pair call runs: their difference over the rounds IS the box's spread), then `push_f32` / `push_u8` (a steady-state push,
-device-resident), `push_i420` / `push_nv12` (the same on 8-bit 4:2:0 frames, where the tree has them), `sequence`
+device-resident), `push_i420` / `push_nv12` (the same on 8-bit 4:2:0 frames, where the tree has them), `push_i010` / `push_p010` (10-bit
+4:2:0 frames, where the tree has them), `sequence`
 (film_interpolate_sequence over a long sequence, per generated frame) and, at the first point, the host-buffer calls `host_pair`
-(film_interpolate on numpy arrays, as bench.py's host_buffers), `host_push_f32`, `host_push_u8`, `host_push_i420`, `host_push_nv12`.
-The 4:2:0 rows are compared with the BASELINE's `push_u8` / `host_push_u8` (what such a caller had before: RGB bytes), whose spread
-over the rounds is reported next to them.  --rows / --points restrict a run to some measurements.
+(film_interpolate on numpy arrays, as bench.py's host_buffers), `host_push_f32`, `host_push_u8`, `host_push_i420`, `host_push_nv12`,
+`host_push_i010`, `host_push_p010`.
+The 8-bit 4:2:0 rows are compared with the BASELINE's `push_u8` / `host_push_u8` (what such a caller had before: RGB bytes), the 10-bit rows
+with the BASELINE's `push_i420` / `host_push_i420` (what such a caller had before: the frames truncated to 8 bits), whose spread over the
+rounds is reported next to them.  --rows / --points restrict a run to some measurements.
 --scene_cut adds, at the first point and for `u8` and `i420`, device-resident and host buffers, what option "scene_cut" costs (trees
 without the option skip them): `*_sc1000` - the steady-state push with scene_cut = 1000, which never cuts on the bench frames (rolled
 copies of one picture: D = 0 for RGB, a fraction of a percent of 2 S for 4:2:0, whose chroma is averaged after the roll) but pays the histogram kernel, the 3 KB download and the wait; `*_cut` - a push that IS a cut (scene_cut = 1,
@@ -62,6 +65,7 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
     eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
     has_stream = hasattr(eng, 'open_stream')
     has_yuv = 'i420' in getattr(engine_mod, 'PIX', {})
+    has_yuv10 = 'i010' in getattr(engine_mod, 'PIX', {})
     has_scene = scene_cut and hasattr(engine_mod, 'frame_histogram_device')
     want = lambda key: rows is None or key in rows      # noqa: E731
     out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {}}
@@ -112,8 +116,10 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
                     res['push_u8'] = timed(lambda: st.push(x8[nxt(4)]), n)
             yuv = {}
             if has_yuv and h % 2 == 0 and w % 2 == 0:      # the frames as 4:2:0, converted by the engine itself
-                for pix in ('i420', 'nv12'):
-                    yuv[pix] = [torch.empty((h * 3 // 2, w), dtype=torch.uint8, device='cuda') for _ in x]
+                for pix in ('i420', 'nv12') + (('i010', 'p010') if has_yuv10 else ()):
+                    if not (want('push_' + pix) or want('host_push_' + pix) or (pix == 'i420' and has_scene and pi == 0)):
+                        continue
+                    yuv[pix] = [torch.empty((h * 3 // 2, w), dtype=torch.int16 if pix in ('i010', 'p010') else torch.uint8, device='cuda') for _ in x]
                     for src, dst in zip(x, yuv[pix]):
                         eng.to_yuv420_device(src.data_ptr(), dst.data_ptr(), h, w, pix)
                     torch.cuda.synchronize()
@@ -130,7 +136,8 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
                 hn = max(5, n // 3)
                 if want('host_pair'):
                     res['host_pair'] = timed(lambda: eng.interpolate_frames(fr[:1], fr[1:2], align=align, block_shape=block), hn, warm=2)
-                for pix, frames in [('f32', fr), ('u8', f8)] + [(p, [t.cpu().numpy() for t in v]) for p, v in yuv.items()]:
+                for pix, frames in [('f32', fr), ('u8', f8)] + [(p, [t.cpu().numpy().view(np.uint16 if t.dtype == torch.int16 else np.uint8) for t in v])
+                                                               for p, v in yuv.items()]:
                     if want('host_push_' + pix):
                         with eng.open_stream(h, w, align=align, block_shape=block, pix=pix) as st:
                             st.push(frames[0])
@@ -201,15 +208,18 @@ def histogram_alone(calls=50, reps=3):
     """frame_histogram_kernel alone: {"<layout> <size> <data>": [microseconds per call, ...]} from hip events around `calls` calls."""
     import torch
     from film_hip.torch_io import frame_histogram
-    from film_hip.engine import frame_histogram_device
+    from film_hip.engine import PIX, frame_histogram_device
     out = {}
     hist = torch.empty(768, dtype=torch.int32, device='cuda')
     for size, (h, w) in (('1080p', (1080, 1920)), ('4K', (2160, 3840))):
-        for pix in ('u8', 'i420', 'nv12', 'f32'):
-            shape = (h * 3 // 2, w) if pix in ('i420', 'nv12') else (h, w, 3)
+        for pix in ('u8', 'i420', 'nv12', 'f32') + (('i010', 'p010') if 'i010' in PIX else ()):
+            shape = (h * 3 // 2, w) if pix in ('i420', 'nv12', 'i010', 'p010') else (h, w, 3)
             for data in ('random', 'constant'):
                 if pix == 'f32':
                     fr = torch.rand(shape, device='cuda') if data == 'random' else torch.full(shape, 0.5, device='cuda')
+                elif pix in ('i010', 'p010'):      # 10-bit codes in 16-bit words (int16 as a bit pattern), P010's in bits 6-15
+                    fr = torch.randint(0, 1024, shape, dtype=torch.int32, device='cuda') if data == 'random' else torch.full(shape, 64, dtype=torch.int32, device='cuda')
+                    fr = (((fr << 6) + 32768) % 65536 - 32768 if pix == 'p010' else fr).to(torch.int16)
                 else:
                     fr = torch.randint(0, 256, shape, dtype=torch.uint8, device='cuda') if data == 'random' else torch.full(shape, 16, dtype=torch.uint8, device='cuda')
                 assert int(frame_histogram(fr, pix).sum()) == fr.numel()
@@ -276,11 +286,11 @@ def main(argv=None):
         lines.append(f'{name}:')
         pts = [r['points'][name] for r in this]
         base = [r['points'][name] for r in runs.get('baseline', [])]
-        for key in ('pair', 'push_u8', 'host_push_u8'):
+        for key in ('pair', 'push_u8', 'push_i420', 'host_push_u8', 'host_push_i420'):
             if base and key in base[0]:
                 lines.append(f'  {"baseline " + key:<22} {_stat([s for p in base for s in p[key]])}')
-        for key in ('pair', 'push_f32', 'push_u8', 'push_i420', 'push_nv12', 'sequence', 'host_pair', 'host_push_f32', 'host_push_u8',
-                    'host_push_i420', 'host_push_nv12'):
+        for key in ('pair', 'push_f32', 'push_u8', 'push_i420', 'push_nv12', 'push_i010', 'push_p010', 'sequence', 'host_pair', 'host_push_f32',
+                    'host_push_u8', 'host_push_i420', 'host_push_nv12', 'host_push_i010', 'host_push_p010'):
             if key in pts[0]:
                 lines.append(f'  {key:<22} {_stat([s for p in pts for s in p[key]])}' + ('   (per generated frame)' if key == 'sequence' else ''))
         lines.append(f'  push_f32 == pair, bit for bit: {all(p.get("identical", True) for p in pts)}')
@@ -293,7 +303,11 @@ def main(argv=None):
                     lines.append(f'  {key + " - baseline pair":<36} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms')
             lines.append(f'  spread of the baseline pair call over the rounds (max - min of the round means): {spread:.3f} ms')
         # the 4:2:0 pushes against what the baseline offers such a caller: its 8-bit RGB push
-        for mine, theirs in [(f'{pre}push_{pix}', f'{pre}push_u8') for pre in ('', 'host_') for pix in ('i420', 'nv12')]:
+        # ... and the 10-bit pushes against its 8-bit 4:2:0 push (such a caller had to truncate to 8 bits); this tree's own 8-bit pushes
+        # against the baseline's show that the 8-bit paths are unchanged
+        for mine, theirs in [(f'{pre}push_{pix}', f'{pre}push_u8') for pre in ('', 'host_') for pix in ('i420', 'nv12')] + \
+                            [(f'{pre}push_{pix}', f'{pre}push_i420') for pre in ('', 'host_') for pix in ('i010', 'p010')] + \
+                            ([(f'{pre}push_{pix}', f'{pre}push_{pix}') for pre in ('', 'host_') for pix in ('u8', 'i420')] if 'push_i010' in pts[0] or 'host_push_i010' in pts[0] else []):
             if base and theirs in base[0] and mine in pts[0]:
                 bm = [statistics.mean(p[theirs]) for p in base]
                 d = [statistics.mean(p[mine]) - b for p, b in zip(pts, bm)]
