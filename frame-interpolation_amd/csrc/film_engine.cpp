@@ -113,10 +113,8 @@ int tile_geometry(film_t* h, int H, int W, int block_h, int block_w, int align, 
   }
   return FILM_OK;
 }
-// The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the 4:2:0 layouts.
-int pix_layout(int pix) { return pix & 0xff; }
-bool pix_is_yuv10(int pix) { return pix_layout(pix) == FILM_PIX_I010 || pix_layout(pix) == FILM_PIX_P010; }   // 16-bit samples
-bool pix_is_yuv(int pix) { return pix_layout(pix) == FILM_PIX_I420 || pix_layout(pix) == FILM_PIX_NV12 || pix_is_yuv10(pix); }
+// The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the 4:2:0 layouts (pix_layout,
+// pix_is_yuv, pix_is_yuv10, pix_sample_bytes: film_kernels.h).
 // FILM_OK, or the refusal of a pix value for H x W frames (include/film_hip.h, film_stream_open)
 int check_pix(film_t* h, int pix, int H, int W) {
   const int layout = pix_layout(pix), flags = pix & ~0xff;
@@ -132,11 +130,9 @@ int check_pix(film_t* h, int pix, int H, int W) {
     return fail(h, FILM_ERR_INVALID, "pix: 4:2:0 needs even sizes, got %d x %d", H, W);
   return FILM_OK;
 }
-// bytes of one H x W frame of pixel type `pix`
-size_t frame_bytes(int pix, int H, int W) {
-  const size_t px = (size_t)H * W;
-  return pix_is_yuv10(pix) ? px * 3 : pix_is_yuv(pix) ? px + px / 2 : pix_layout(pix) == FILM_PIX_U8 ? px * 3 : px * 3 * sizeof(float);
-}
+// samples of one H x W frame of pixel type `pix` (S of "Scene cuts", include/film_hip.h), and its bytes
+int64_t frame_samples(int pix, int H, int W) { return pix_is_yuv(pix) ? (int64_t)H * W * 3 / 2 : (int64_t)H * W * 3; }
+size_t frame_bytes(int pix, int H, int W) { return (size_t)frame_samples(pix, H, W) * pix_sample_bytes(pix); }
 // The handle's staging buffer in HBM (whole frames of the FILM_MEM_HOST entry points), grown on demand.
 int ensure_stage(film_t* h, size_t bytes, hipStream_t s) {
   if (h->stage_bytes >= bytes) return FILM_OK;
@@ -353,8 +349,6 @@ hipError_t stream_cut(const FilmStream& fs, TileMapParams tp, const Plan* P, int
   return film_launch_cut_tiles(tp, fs.pix, s);
 }
 
-// samples of one H x W frame of pixel type `pix` (S of "Scene cuts", include/film_hip.h)
-int64_t frame_samples(int pix, int H, int W) { return pix_is_yuv(pix) ? (int64_t)H * W * 3 / 2 : (int64_t)H * W * 3; }
 // Option "scene_cut" = k > 0: the histogram of the frame in fs.keep, taken on `s`, downloaded and waited for; *cut = the rule's verdict
 // against the carried histogram when the stream is primed and has one.  The new histogram becomes the carried one (valid once the push succeeds).
 int stream_scene_cut(film_t* h, hipStream_t s, int k, bool* cut) {

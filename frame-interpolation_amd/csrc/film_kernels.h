@@ -382,6 +382,12 @@ hipError_t film_launch_warp(const WarpParams& p, hipStream_t s);
 hipError_t film_launch_pack_flow(const PackFlowParams& p, hipStream_t s);
 // frame_kernels.hip: frame I/O.  `pix` is the public value (include/film_hip.h): a layout in bits 0-7 plus FILM_YUV_BT601 / FILM_YUV_FULL for the
 // 4:2:0 layouts; the launchers decode it.  Overlapped tiles and their cross-fade when p.ovy | p.ovx.
+// What a pix value says, for the launchers, film_engine.cpp and the host-only build alike: its layout, 4:2:0 or not, 10-bit 4:2:0 or not, and the
+// bytes of one sample (float32 for FILM_PIX_F32 and for what check_pix refuses anyway).
+inline int pix_layout(int pix) { return pix & 0xff; }
+inline bool pix_is_yuv10(int pix) { return pix_layout(pix) == FILM_PIX_I010 || pix_layout(pix) == FILM_PIX_P010; }   // 16-bit samples
+inline bool pix_is_yuv(int pix) { return pix_layout(pix) == FILM_PIX_I420 || pix_layout(pix) == FILM_PIX_NV12 || pix_is_yuv10(pix); }
+inline int pix_sample_bytes(int pix) { return pix_is_yuv10(pix) ? 2 : pix_is_yuv(pix) || pix_layout(pix) == FILM_PIX_U8 ? 1 : (int)sizeof(float); }
 // pad + image_to_patches of tiles [tile0, tile0 + ntiles): p.src is float32 [B][H][W][3] (FILM_PIX_F32), or bytes that the cut converts - [B][H][W][3]
 // (FILM_PIX_U8: float32(byte) / 255.0f, correctly rounded) or 4:2:0 frames of H * W * 3 / 2 bytes each (FILM_PIX_I420 / NV12; H and W even),
 // or 10-bit 4:2:0 frames of H * W * 3 / 2 little-endian uint16 samples each (FILM_PIX_I010 / P010; H and W even, the pointer 4-byte aligned).

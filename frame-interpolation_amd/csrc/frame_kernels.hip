@@ -3,19 +3,23 @@
 //
 //   frame_to_tiles<OVERLAP>             _pad_to_align + image_to_patches, float32 frames    eval/interpolator.py:30-63, :66-104
 //   frame_u8_to_tiles<OVERLAP>          the same on 8-bit RGB frames: float32(byte) / 255   eval/util.py read_image
-//   frame_yuv420_to_tiles<OVERLAP,NV12> the same on 8-bit 4:2:0 frames (I420 / NV12)        include/film_hip.h, "The 4:2:0 arithmetic"
-//   frame_yuv10_to_tiles<OVERLAP,P010>  the same on 10-bit 4:2:0 frames (I010 / P010)           include/film_hip.h, "The 10-bit 4:2:0 arithmetic"
-//   tiles_to_frame                      crop + patches_to_image                             eval/interpolator.py:107-126, :192-206
+//   frame_yuv_to_tiles<OVERLAP,LAYOUT>  the same on 4:2:0 frames (I420 / NV12 / I010 / P010)  include/film_hip.h, "The 4:2:0 arithmetic", "The 10-bit ..."
+//   tiles_to_frame                    crop + patches_to_image                             eval/interpolator.py:107-126, :192-206
 //   blend_tiles                         crop + cross-fade of overlapped tiles               include/film_hip.h, "block_overlap_h"
 //   to_uint8                            clip(x * 255, 0, 255) + 0.5, truncated              eval/util.py:51-52 (write_image)
-//   rgb_to_yuv420<NV12>                 float32 RGB -> the planes of one 4:2:0 frame        include/film_hip.h, "The 4:2:0 arithmetic"
-//   rgb_to_yuv10<P010>                  float32 RGB -> the planes of one 10-bit 4:2:0 frame  include/film_hip.h, "The 10-bit 4:2:0 arithmetic"
-//   frame_histogram<LAYOUT>             3 x 256 counters of a frame's 8-bit sample codes    include/film_hip.h, "Scene cuts"
+//   rgb_to_yuv<LAYOUT>                  float32 RGB -> the planes of one 4:2:0 frame        the same two sections
+//   frame_histogram<LAYOUT>            3 x 256 counters of a frame's 8-bit sample codes    include/film_hip.h, "Scene cuts"
 //
 // OVERLAP: the tile's content is the patch grown by the overlap, from film_tile_origin (options "block_overlap_h" / "block_overlap_w").
+// LAYOUT: a FILM_PIX_* value.  The 4:2:0 cut and quantiser are written once over Yuv420<LAYOUT>, which states what a layout decides: the sample
+// type and how many fit a 32-bit word, planar or semi-planar chroma, where the code sits in a sample, the largest code and the chroma midpoint,
+// the constants the kernels take and the aligned multi-sample load.  What only one depth does stands behind `if constexpr`: the 8-bit LDS tables
+// against the 10-bit division, and P010's direct reads of its CbCr pair words.
 //
 // This file is compiled with -ffp-contract=off, like misc_kernels.hip: the cross-fade, the colour matrices and the quantisers are specified
 // as separate multiply / add operations (one rounding each), so a*b+c must not become an fma here.
+#include <type_traits>
+
 #include "film_kernels.h"
 
 namespace {
@@ -58,10 +62,10 @@ __device__ __forceinline__ float clip01(float v) {
   v = v < 0.f ? 0.f : v;      // max(v, 0) then min(v, 1)
   return v > 1.f ? 1.f : v;
 }
-// the quantiser of both ways out: clip(v, 0, 255) + 0.5, truncated (np.clip = minimum(maximum(x, 0), 255))
-__device__ __forceinline__ uint32_t quant255(float v) {
+// the quantiser of every way out: clip(v, 0, MAX) + 0.5, truncated (np.clip = minimum(maximum(x, 0), MAX)); MAX = 255, or 1023 for 10-bit codes
+template <int MAX> __device__ __forceinline__ uint32_t quantise(float v) {
   v = v < 0.f ? 0.f : v;
-  v = v > 255.f ? 255.f : v;
+  v = v > (float)MAX ? (float)MAX : v;
   return (uint32_t)(v + 0.5f);
 }
 
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(256) void frame_u8_to_tiles_kernel(TileMapParams p,
       }
     }
   }
-  // (the store tail is frame_yuv420_to_tiles_kernel's too, each in its own text: behind a shared __device__ function both kernels' branch layout changes)
+  // (the store tail is frame_yuv_to_tiles_kernel's too, each in its own text: behind a shared __device__ function both kernels' branch layout changes)
   float* d = p.dst + r * row + xc0;
   if (xc0 + 12 <= row && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
 #pragma unroll
@@ -168,131 +172,32 @@ __global__ __launch_bounds__(256) void frame_u8_to_tiles_kernel(TileMapParams p,
   }
 }
 
-// ---- 8-bit Y'CbCr 4:2:0 frames (FILM_PIX_I420 / FILM_PIX_NV12; the arithmetic: include/film_hip.h, "The 4:2:0 arithmetic") -----------
-// Everything a colour setting (matrix x range) decides, computed on the HOST: the per-byte tables with IEEE division, the coefficients
-// in double from (Kr, Kb) and rounded to float32 once.  Passed by value (2 KB of kernel arguments).
-struct YuvTables {
-  float y[256], c[256];                  // in: luma and chroma value of every byte
+// ---- Y'CbCr 4:2:0 frames (the arithmetic: include/film_hip.h, "The 4:2:0 arithmetic" and "The 10-bit 4:2:0 arithmetic") ---------------
+// The twelve floats every 4:2:0 kernel's constants end with: the nine coefficients of a colour matrix, computed on the HOST in double from
+// (Kr, Kb) and rounded to float32 once, and the two scales and the offset of the way out (those of the depth: 219 / 16 / 224 or 876 / 64 / 896).
+struct YuvMatrix {
   float a_r, a_b, g_b, g_r;              // in: R = y + a_r cr, B = y + a_b cb, G = (y - g_b cb) - g_r cr
   float kr, kg, kb, s_b, s_r;            // out: Yf = (kr R + kg G) + kb B, cbf = (B - Yf) s_b, crf = (R - Yf) s_r
-  float y_scale, y_off, c_scale;         // out: Y = q(Yf y_scale + y_off), C = q(m c_scale + 128)
+  float y_scale, y_off, c_scale;         // out: Y = q(Yf y_scale + y_off), C = q(m c_scale + mid)
 };
-
-// frame_u8_to_tiles_kernel on a 4:2:0 frame batch: p.src points at bytes, frame b at b * H * W * 3 / 2, its Y plane
-// [H][W] first, then Cb [H/2][W/2] and Cr [H/2][W/2] (I420) or CbCr [H/2][W/2][2] (NV12).  thread = four pixels (twelve floats) of one row
-// of the tile buffer.  Pixel (fy, fx) of the FRAME takes the chroma sample (fy >> 1, fx >> 1): origins and patch sizes may be odd, so
-// the pairing follows the frame coordinate.  A group wholly inside the tile's content reads its four Y bytes and its two or three chroma
-// samples per plane as aligned 32-bit words (load_bytes_aligned); a group that touches the padding or the row's end goes byte by byte.
-template <bool OVERLAP, bool NV12>
-__global__ __launch_bounds__(256) void frame_yuv420_to_tiles_kernel(TileMapParams p, YuvTables tab) {
-  __shared__ float ly[256], lc[256];
-  ly[threadIdx.x] = tab.y[threadIdx.x];
-  lc[threadIdx.x] = tab.c[threadIdx.x];
-  __syncthreads();
-  const int row = p.TW * 3;
-  const int groups = (p.TW + 3) / 4;
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= (int64_t)p.ntiles * p.TH * groups) return;
-  const int xp0 = (int)(g % groups) * 4;      // first pixel of the group in the tile row
-  const int64_t r = g / groups;               // row of the tile buffer
-  using C = TileContent<OVERLAP>;
-  int y, b, ty, tx;
-  tile_row(p, r, y, b, ty, tx);
-  const int ch = C::rows(p), cw = C::cols(p);                         // the tile's content: rows, pixels per row
-  const int sy = y - p.oy, s0 = xp0 - p.ox;                           // content row, content pixel of the group's first pixel
-  float v[12];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) v[j] = 0.f;   // tf.image.pad_to_bounding_box pads with zeros
-  if (sy >= 0 && sy < ch && s0 + 4 > 0 && s0 < cw) {
-    const int fy = C::row0(p, ty) + sy;
-    const int fx = C::col0(p, tx) + s0;   // frame column of the group's first pixel
-    const int64_t plane = (int64_t)p.H * p.W;
-    const uint8_t* yrow = reinterpret_cast<const uint8_t*>(p.src) + (int64_t)b * (plane + plane / 2) + (int64_t)fy * p.W;
-    const uint8_t* frame0 = yrow - (int64_t)fy * p.W;
-    const int hw = p.W >> 1;
-    // NV12: one row of Cb Cr pairs; I420: a Cb row and, H/2 * W/2 bytes further on, the Cr row
-    const uint8_t* crow = frame0 + plane + (int64_t)(fy >> 1) * (NV12 ? p.W : hw);
-    const int64_t cr_off = NV12 ? 1 : plane / 4;
-    uint32_t yb[4], cbb[4], crb[4];
-    bool have[4];
-    if (s0 >= 0 && s0 + 4 <= cw) {
-      const uint32_t yw = (uint32_t)load_bytes_aligned(yrow + fx, 4);
-      const int c0 = fx >> 1, nc = ((fx + 3) >> 1) - c0 + 1;      // two chroma samples per plane, three from an odd column
-      uint32_t cbs[3], crs[3];
-      if (NV12) {
-        const uint64_t w = load_bytes_aligned(crow + 2 * c0, 2 * nc);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { cbs[k] = (uint32_t)(w >> (16 * k)) & 255u; crs[k] = (uint32_t)(w >> (16 * k + 8)) & 255u; }
-      } else {
-        const uint32_t wb = (uint32_t)load_bytes_aligned(crow + c0, nc), wr = (uint32_t)load_bytes_aligned(crow + cr_off + c0, nc);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { cbs[k] = (wb >> (8 * k)) & 255u; crs[k] = (wr >> (8 * k)) & 255u; }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int k = ((fx + j) >> 1) - c0;
-        yb[j] = (yw >> (8 * j)) & 255u;
-        cbb[j] = k == 0 ? cbs[0] : k == 1 ? cbs[1] : cbs[2];
-        crb[j] = k == 0 ? crs[0] : k == 1 ? crs[1] : crs[2];
-        have[j] = true;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        have[j] = s0 + j >= 0 && s0 + j < cw;
-        yb[j] = cbb[j] = crb[j] = 0;
-        if (have[j]) {
-          const int c = (fx + j) >> 1;
-          yb[j] = yrow[fx + j];
-          cbb[j] = NV12 ? crow[2 * c] : crow[c];
-          crb[j] = NV12 ? crow[2 * c + 1] : crow[cr_off + c];
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (!have[j]) continue;
-      const float yv = ly[yb[j]], cb = lc[cbb[j]], cr = lc[crb[j]];
-      v[3 * j] = clip01(yv + tab.a_r * cr);
-      v[3 * j + 1] = clip01((yv - tab.g_b * cb) - tab.g_r * cr);
-      v[3 * j + 2] = clip01(yv + tab.a_b * cb);
-    }
-  }
-  const int xc0 = xp0 * 3;
-  float* d = p.dst + r * row + xc0;
-  if (xc0 + 12 <= row && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(d)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 12; ++j)
-      if (xc0 + j < row) d[j] = v[j];
-  }   // (own text: see frame_u8_to_tiles_kernel)
-}
-
-// ---- 10-bit Y'CbCr 4:2:0 frames (FILM_PIX_I010 / FILM_PIX_P010; the arithmetic: include/film_hip.h, "The 10-bit 4:2:0 arithmetic") ----
-// What a colour setting decides.  The coefficients are YuvTables' (the same matrices); the codes are 10 bits wide.  The two 1024-entry
-// tables of quotients would be 8 KB - more than a kernel's argument block holds - so there are none: the cut DIVIDES on the device,
+// 8 bits: the luma and chroma value of every byte, divided on the HOST with IEEE division.  Passed by value (2 KB of kernel arguments).
+struct YuvTables {
+  float y[256], c[256];
+  YuvMatrix m;
+};
+// 10 bits: y = (float(v) - y_sub) / y_div, c = (float(v) - 512) / c_div.  The two 1024-entry tables of quotients would be 8 KB - more than a kernel's argument block holds - so there are none: the cut DIVIDES on the device,
 // (float(v) - sub) / div with the divisor a kernel argument.  hipcc's fp32 division is correctly rounded by default
 // (-fhip-fp32-correctly-rounded-divide-sqrt: the v_div_scale / v_div_fmas / v_div_fixup sequence) and this library is built without
 // fast-math and without contraction, so the quotient has the bits of the host's IEEE division; no quotient here is subnormal.  Chosen over
 // device-resident tables copied into LDS by every workgroup: no per-device allocation for launchers that have no handle to own it, no
 // 8 KB LDS fill per workgroup for ten look-ups per thread, and nothing an input word could index.
 struct Yuv10Consts {
-  float y_sub, y_div, c_div;             // in: y = (float(v) - y_sub) / y_div, c = (float(v) - 512) / c_div
-  float a_r, a_b, g_b, g_r;              // in: as YuvTables
-  float kr, kg, kb, s_b, s_r;            // out: as YuvTables
-  float y_scale, y_off, c_scale;         // out: Y = q10(Yf y_scale + y_off), C = q10(m c_scale + 512)
+  float y_sub, y_div, c_div;
+  YuvMatrix m;
 };
+const YuvTables& yuv_tables(int pix);   // ("host", below)
+Yuv10Consts yuv10_consts(int pix);
 
-// the 10-bit code of a stored 16-bit word: I010 keeps it in bits 0-9 (the upper six are ignored), P010 in bits 6-15 (the lower six are)
-template <bool P010> __device__ __forceinline__ uint32_t code10(uint32_t w) { return P010 ? (w & 0xffffu) >> 6 : w & 1023u; }
-// the out quantiser: clip(v, 0, 1023) + 0.5, truncated
-__device__ __forceinline__ uint32_t quant1023(float v) {
-  v = v < 0.f ? 0.f : v;
-  v = v > 1023.f ? 1023.f : v;
-  return (uint32_t)(v + 0.5f);
-}
 // n <= 4 16-bit samples from p (2-byte aligned) as the low words of a 64-bit value, read as the one, two or three ALIGNED 32-bit words
 // that hold them: every word read holds at least one of the samples asked for
 __device__ __forceinline__ uint64_t load_samples_aligned(const uint16_t* p, int n) {
@@ -308,14 +213,50 @@ __device__ __forceinline__ uint64_t load_samples_aligned(const uint16_t* p, int 
   return v;
 }
 
-// frame_yuv420_to_tiles_kernel on 10-bit frames: p.src points at little-endian uint16 samples, frame b at sample b * H * W * 3 / 2, its
-// Y plane [H][W] first, then Cb [H/2][W/2] and Cr [H/2][W/2] (I010) or CbCr [H/2][W/2][2] (P010).  thread = four pixels (twelve floats) of
-// one row of the tile buffer; pixel (fy, fx) of the FRAME takes the chroma sample (fy >> 1, fx >> 1).  A group wholly inside the tile's
-// content reads its four Y samples as the two or three aligned 32-bit words that hold them and its two or three chroma samples per plane
-// the same way (I010) or as the two or three aligned words that ARE its CbCr pairs (P010: a pair never straddles a word, W being even);
-// a group that touches the padding or the row's end goes sample by sample.
-template <bool OVERLAP, bool P010>
-__global__ __launch_bounds__(256) void frame_yuv10_to_tiles_kernel(TileMapParams p, Yuv10Consts k) {
+// What a 4:2:0 layout decides, for the one cut and the one quantiser below.  A frame is H * W * 3 / 2 samples: its Y plane [H][W] first, then
+// Cb [H/2][W/2] and Cr [H/2][W/2] (I420, I010) or CbCr [H/2][W/2][2] (NV12, P010).  A sample is a byte, or a little-endian 16-bit word that
+// keeps its 10-bit code in bits 0-9 (I010: the upper six are ignored) or in bits 6-15 (P010: the lower six are).
+template <int LAYOUT> struct Yuv420 {
+  static_assert(LAYOUT == FILM_PIX_I420 || LAYOUT == FILM_PIX_NV12 || LAYOUT == FILM_PIX_I010 || LAYOUT == FILM_PIX_P010, "a 4:2:0 layout");
+  static constexpr int PIX = LAYOUT;
+  static constexpr bool WIDE = LAYOUT == FILM_PIX_I010 || LAYOUT == FILM_PIX_P010;                  // 10-bit codes in 16-bit samples
+  static constexpr bool SEMI_PLANAR = LAYOUT == FILM_PIX_NV12 || LAYOUT == FILM_PIX_P010;
+  using Sample = std::conditional_t<WIDE, uint16_t, uint8_t>;
+  using Consts = std::conditional_t<WIDE, Yuv10Consts, YuvTables>;       // the kernels' constants
+  static constexpr int BITS = 8 * (int)sizeof(Sample), PER_WORD = 32 / BITS;   // of a stored sample; samples per 32-bit word
+  static constexpr uint32_t MASK = (1u << BITS) - 1;
+  static constexpr int SHIFT = LAYOUT == FILM_PIX_P010 ? 6 : 0;          // where the code sits in the sample; what the quantiser shifts by
+  static constexpr int QMAX = WIDE ? 1023 : 255, MID = WIDE ? 512 : 128;  // the largest code, the chroma midpoint
+  static __device__ __forceinline__ uint32_t code(uint32_t w) { return ((w & MASK) >> SHIFT) & (uint32_t)QMAX; }
+  // n samples from p as the low samples of a 64-bit value, read as the aligned 32-bit words that hold them
+  static __device__ __forceinline__ uint64_t load(const Sample* p, int n) {
+    if constexpr (WIDE) return load_samples_aligned(p, n);
+    else return load_bytes_aligned(p, n);
+  }
+  static Consts consts(int pix) {
+    if constexpr (WIDE) return yuv10_consts(pix);
+    else return yuv_tables(pix);
+  }
+};
+
+// frame_u8_to_tiles_kernel on a 4:2:0 frame batch: p.src points at samples, frame b at sample b * H * W * 3 / 2 (10 bits: 4-byte aligned).
+// thread = four pixels (twelve floats) of one row of the tile buffer.  Pixel (fy, fx) of the FRAME takes the chroma sample (fy >> 1, fx >> 1):
+// origins and patch sizes may be odd, so the pairing follows the frame coordinate.  A group wholly inside the tile's content reads its four
+// Y samples and its two or three chroma samples per plane as aligned 32-bit words (Yuv420::load), P010 as the two or three aligned words that
+// ARE its CbCr pairs (a pair never straddles a word, W being even); a group that touches the padding or the row's end goes sample by sample.
+// 8 bits look the luma and chroma values up in the two tables (copied to LDS); 10 bits divide (Yuv10Consts) and declare no LDS.
+template <bool OVERLAP, int LAYOUT>
+__global__ __launch_bounds__(256) void frame_yuv_to_tiles_kernel(TileMapParams p, typename Yuv420<LAYOUT>::Consts k) {
+  using L = Yuv420<LAYOUT>;
+  using Sample = typename L::Sample;
+  const float *ly = nullptr, *lc = nullptr;
+  if constexpr (!L::WIDE) {
+    __shared__ float lut_y[256], lut_c[256];
+    lut_y[threadIdx.x] = k.y[threadIdx.x];
+    lut_c[threadIdx.x] = k.c[threadIdx.x];
+    __syncthreads();
+    ly = lut_y; lc = lut_c;
+  }
   const int row = p.TW * 3;
   const int groups = (p.TW + 3) / 4;
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -334,33 +275,37 @@ __global__ __launch_bounds__(256) void frame_yuv10_to_tiles_kernel(TileMapParams
     const int fy = C::row0(p, ty) + sy;
     const int fx = C::col0(p, tx) + s0;   // frame column of the group's first pixel
     const int64_t plane = (int64_t)p.H * p.W;
-    const uint16_t* frame0 = reinterpret_cast<const uint16_t*>(p.src) + (int64_t)b * (plane + plane / 2);
-    const uint16_t* yrow = frame0 + (int64_t)fy * p.W;
+    const Sample* frame0 = reinterpret_cast<const Sample*>(p.src) + (int64_t)b * (plane + plane / 2);
+    const Sample* yrow = frame0 + (int64_t)fy * p.W;
     const int hw = p.W >> 1;
-    // P010: one row of Cb Cr pairs; I010: a Cb row and, H/2 * W/2 samples further on, the Cr row
-    const uint16_t* crow = frame0 + plane + (int64_t)(fy >> 1) * (P010 ? p.W : hw);
-    const int64_t cr_off = P010 ? 1 : plane / 4;
+    // semi-planar: one row of Cb Cr pairs; planar: a Cb row and, H/2 * W/2 samples further on, the Cr row
+    const Sample* crow = frame0 + plane + (int64_t)(fy >> 1) * (L::SEMI_PLANAR ? p.W : hw);
+    const int64_t cr_off = L::SEMI_PLANAR ? 1 : plane / 4;
     uint32_t yb[4], cbb[4], crb[4];
     bool have[4];
     if (s0 >= 0 && s0 + 4 <= cw) {
-      const uint64_t yw = load_samples_aligned(yrow + fx, 4);
+      const uint64_t yw = L::load(yrow + fx, 4);
       const int c0 = fx >> 1, nc = ((fx + 3) >> 1) - c0 + 1;      // two chroma samples per plane, three from an odd column
       uint32_t cbs[3], crs[3];
-      if (P010) {
+      if constexpr (LAYOUT == FILM_PIX_P010) {
         const uint32_t* cwp = reinterpret_cast<const uint32_t*>(crow) + c0;   // (4-byte aligned: the frame is, and H * W and W are even)
         const uint32_t w0 = cwp[0], w1 = cwp[1], w2 = nc > 2 ? cwp[2] : 0u;
         cbs[0] = w0 & 0xffffu; crs[0] = w0 >> 16;
         cbs[1] = w1 & 0xffffu; crs[1] = w1 >> 16;
         cbs[2] = w2 & 0xffffu; crs[2] = w2 >> 16;
-      } else {
-        const uint64_t wb = load_samples_aligned(crow + c0, nc), wr = load_samples_aligned(crow + cr_off + c0, nc);
+      } else if constexpr (L::SEMI_PLANAR) {
+        const uint64_t w = L::load(crow + 2 * c0, 2 * nc);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) { cbs[q] = (uint32_t)(wb >> (16 * q)) & 0xffffu; crs[q] = (uint32_t)(wr >> (16 * q)) & 0xffffu; }
+        for (int q = 0; q < 3; ++q) { cbs[q] = (uint32_t)(w >> (2 * L::BITS * q)) & L::MASK; crs[q] = (uint32_t)(w >> (2 * L::BITS * q + L::BITS)) & L::MASK; }
+      } else {
+        const uint64_t wb = L::load(crow + c0, nc), wr = L::load(crow + cr_off + c0, nc);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { cbs[q] = (uint32_t)(wb >> (L::BITS * q)) & L::MASK; crs[q] = (uint32_t)(wr >> (L::BITS * q)) & L::MASK; }
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int q = ((fx + j) >> 1) - c0;
-        yb[j] = (uint32_t)(yw >> (16 * j)) & 0xffffu;
+        yb[j] = (uint32_t)(yw >> (L::BITS * j)) & L::MASK;
         cbb[j] = q == 0 ? cbs[0] : q == 1 ? cbs[1] : cbs[2];
         crb[j] = q == 0 ? crs[0] : q == 1 ? crs[1] : crs[2];
         have[j] = true;
@@ -373,19 +318,24 @@ __global__ __launch_bounds__(256) void frame_yuv10_to_tiles_kernel(TileMapParams
         if (have[j]) {
           const int c = (fx + j) >> 1;
           yb[j] = yrow[fx + j];
-          cbb[j] = P010 ? crow[2 * c] : crow[c];
-          crb[j] = P010 ? crow[2 * c + 1] : crow[cr_off + c];
+          cbb[j] = L::SEMI_PLANAR ? crow[2 * c] : crow[c];
+          crb[j] = L::SEMI_PLANAR ? crow[2 * c + 1] : crow[cr_off + c];
         }
       }
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (!have[j]) continue;
-      const float yv = ((float)code10<P010>(yb[j]) - k.y_sub) / k.y_div;
-      const float cb = ((float)code10<P010>(cbb[j]) - 512.f) / k.c_div, cr = ((float)code10<P010>(crb[j]) - 512.f) / k.c_div;
-      v[3 * j] = clip01(yv + k.a_r * cr);
-      v[3 * j + 1] = clip01((yv - k.g_b * cb) - k.g_r * cr);
-      v[3 * j + 2] = clip01(yv + k.a_b * cb);
+      float yv, cb, cr;
+      if constexpr (L::WIDE) {
+        yv = ((float)L::code(yb[j]) - k.y_sub) / k.y_div;
+        cb = ((float)L::code(cbb[j]) - (float)L::MID) / k.c_div; cr = ((float)L::code(crb[j]) - (float)L::MID) / k.c_div;
+      } else {
+        yv = ly[yb[j]]; cb = lc[cbb[j]]; cr = lc[crb[j]];
+      }
+      v[3 * j] = clip01(yv + k.m.a_r * cr);
+      v[3 * j + 1] = clip01((yv - k.m.g_b * cb) - k.m.g_r * cr);
+      v[3 * j + 2] = clip01(yv + k.m.a_b * cb);
     }
   }
   const int xc0 = xp0 * 3;
@@ -408,98 +358,33 @@ __global__ __launch_bounds__(256) void to_uint8_kernel(const float* __restrict__
   if (i >= n) return;
   if (i + 3 < n && ((reinterpret_cast<uintptr_t>(src + i) & 15) == 0) && ((reinterpret_cast<uintptr_t>(dst + i) & 3) == 0)) {
     const float4 v = *reinterpret_cast<const float4*>(src + i);
-    *reinterpret_cast<uint32_t*>(dst + i) = quant255(v.x * 255.f) | (quant255(v.y * 255.f) << 8) | (quant255(v.z * 255.f) << 16) | (quant255(v.w * 255.f) << 24);
+    *reinterpret_cast<uint32_t*>(dst + i) = quantise<255>(v.x * 255.f) | (quantise<255>(v.y * 255.f) << 8) | (quantise<255>(v.z * 255.f) << 16) | (quantise<255>(v.w * 255.f) << 24);
   } else {
-    for (int64_t k = i; k < n && k < i + 4; ++k) dst[k] = (uint8_t)quant255(src[k] * 255.f);
+    for (int64_t k = i; k < n && k < i + 4; ++k) dst[k] = (uint8_t)quantise<255>(src[k] * 255.f);
   }
 }
 
-// float32 frame [H][W][3] -> the planes of one 4:2:0 frame (film_to_yuv420; the quantisation of a 4:2:0 stream's push).  thread = 2 rows x
-// 8 pixels: sixteen Y bytes and four chroma samples per plane, which leave as whole 32-bit words (two per Y row; one each for Cb and Cr,
-// or two of CbCr pairs) where the block is complete and the address allows, byte by byte otherwise.  H and W are even.
-template <bool NV12>
-__global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst, int H, int W, YuvTables tab) {
-  const int bpr = (W + 7) / 8;      // blocks per row pair
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (int64_t)(H / 2) * bpr) return;
-  const int x0 = (int)(i % bpr) * 8, y0 = (int)(i / bpr) * 2;
-  const int np = min(8, W - x0);    // pixels of the block per row: even
-  uint32_t yq[2][8], cbq[4], crq[4];
-  float cbf[2][8], crf[2][8];
+// N quantised samples of PER_WORD = 4 (bytes) or 2 (16-bit) to a 32-bit word, in memory order, as the N / PER_WORD whole words at d (4-byte aligned)
+template <int PER_WORD, int N>
+__device__ __forceinline__ void store_sample_words(void* d, const uint32_t (&q)[N]) {
 #pragma unroll
-  for (int dy = 0; dy < 2; ++dy) {
-    const float* s = src + ((int64_t)(y0 + dy) * W + x0) * 3;
-    float px[24];
-    if (np == 8 && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+  for (int w = 0; w < N / PER_WORD; ++w) {
+    uint32_t word = q[w * PER_WORD];
 #pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const float4 f = reinterpret_cast<const float4*>(s)[k];
-        px[4 * k] = f.x; px[4 * k + 1] = f.y; px[4 * k + 2] = f.z; px[4 * k + 3] = f.w;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 24; ++k) px[k] = k < np * 3 ? s[k] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float R = clip01(px[3 * j]), G = clip01(px[3 * j + 1]), B = clip01(px[3 * j + 2]);
-      const float Yf = (tab.kr * R + tab.kg * G) + tab.kb * B;
-      cbf[dy][j] = (B - Yf) * tab.s_b;
-      crf[dy][j] = (R - Yf) * tab.s_r;
-      yq[dy][j] = quant255(Yf * tab.y_scale + tab.y_off);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float mb = ((cbf[0][2 * k] + cbf[0][2 * k + 1]) + (cbf[1][2 * k] + cbf[1][2 * k + 1])) * 0.25f;
-    const float mr = ((crf[0][2 * k] + crf[0][2 * k + 1]) + (crf[1][2 * k] + crf[1][2 * k + 1])) * 0.25f;
-    cbq[k] = quant255(mb * tab.c_scale + 128.f);
-    crq[k] = quant255(mr * tab.c_scale + 128.f);
-  }
-  const int64_t plane = (int64_t)H * W;
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy) {
-    uint8_t* d = dst + (int64_t)(y0 + dy) * W + x0;
-    if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
-      reinterpret_cast<uint32_t*>(d)[0] = yq[dy][0] | (yq[dy][1] << 8) | (yq[dy][2] << 16) | (yq[dy][3] << 24);
-      reinterpret_cast<uint32_t*>(d)[1] = yq[dy][4] | (yq[dy][5] << 8) | (yq[dy][6] << 16) | (yq[dy][7] << 24);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (j < np) d[j] = (uint8_t)yq[dy][j];
-    }
-  }
-  if (NV12) {
-    uint8_t* d = dst + plane + (int64_t)(y0 >> 1) * W + x0;
-    if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
-      reinterpret_cast<uint32_t*>(d)[0] = cbq[0] | (crq[0] << 8) | (cbq[1] << 16) | (crq[1] << 24);
-      reinterpret_cast<uint32_t*>(d)[1] = cbq[2] | (crq[2] << 8) | (cbq[3] << 16) | (crq[3] << 24);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (2 * k < np) { d[2 * k] = (uint8_t)cbq[k]; d[2 * k + 1] = (uint8_t)crq[k]; }
-    }
-  } else {
-    uint8_t* db = dst + plane + (int64_t)(y0 >> 1) * (W >> 1) + (x0 >> 1);
-    uint8_t* dr = db + plane / 4;
-    if (np == 8 && (reinterpret_cast<uintptr_t>(db) & 3) == 0 && (reinterpret_cast<uintptr_t>(dr) & 3) == 0) {
-      *reinterpret_cast<uint32_t*>(db) = cbq[0] | (cbq[1] << 8) | (cbq[2] << 16) | (cbq[3] << 24);
-      *reinterpret_cast<uint32_t*>(dr) = crq[0] | (crq[1] << 8) | (crq[2] << 16) | (crq[3] << 24);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (2 * k < np) { db[k] = (uint8_t)cbq[k]; dr[k] = (uint8_t)crq[k]; }
-    }
+    for (int i = 1; i < PER_WORD; ++i) word |= q[w * PER_WORD + i] << (i * (32 / PER_WORD));
+    reinterpret_cast<uint32_t*>(d)[w] = word;
   }
 }
 
-// rgb_to_yuv420_kernel for 10-bit frames (film_to_yuv420 with FILM_PIX_I010 / P010; the quantisation of a 10-bit stream's push): dst points at
-// uint16 samples, 2-byte aligned.  thread = 2 rows x 8 pixels: sixteen Y samples and four chroma samples per plane, which leave as whole
-// 32-bit words (four per Y row; two each for Cb and Cr, or four CbCr pairs) where the block is complete and the address allows, sample by
-// sample otherwise.  I010 stores the code, P010 the code << 6: the ignored bits are written as zero.  H and W are even.
-template <bool P010>
-__global__ __launch_bounds__(256) void rgb_to_yuv10_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int H, int W, Yuv10Consts k) {
-  constexpr int SH = P010 ? 6 : 0;
+// float32 frame [H][W][3] -> the planes of one 4:2:0 frame (film_to_yuv420; the quantisation of a 4:2:0 stream's push): dst points at samples
+// (10 bits: 2-byte aligned).  thread = 2 rows x 8 pixels: sixteen Y samples and four chroma samples per plane, which leave as whole 32-bit words
+// where the block is complete and the address allows, sample by sample otherwise.  A sample is the code << Yuv420::SHIFT: the bits a 10-bit
+// layout ignores are written as zero.  H and W are even.
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const float* __restrict__ src, typename Yuv420<LAYOUT>::Sample* __restrict__ dst, int H, int W,
+                                                         typename Yuv420<LAYOUT>::Consts k) {
+  using L = Yuv420<LAYOUT>;
+  using Sample = typename L::Sample;
   const int bpr = (W + 7) / 8;      // blocks per row pair
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (int64_t)(H / 2) * bpr) return;
@@ -524,54 +409,51 @@ __global__ __launch_bounds__(256) void rgb_to_yuv10_kernel(const float* __restri
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float R = clip01(px[3 * j]), G = clip01(px[3 * j + 1]), B = clip01(px[3 * j + 2]);
-      const float Yf = (k.kr * R + k.kg * G) + k.kb * B;
-      cbf[dy][j] = (B - Yf) * k.s_b;
-      crf[dy][j] = (R - Yf) * k.s_r;
-      yq[dy][j] = quant1023(Yf * k.y_scale + k.y_off) << SH;
+      const float Yf = (k.m.kr * R + k.m.kg * G) + k.m.kb * B;
+      cbf[dy][j] = (B - Yf) * k.m.s_b;
+      crf[dy][j] = (R - Yf) * k.m.s_r;
+      yq[dy][j] = quantise<L::QMAX>(Yf * k.m.y_scale + k.m.y_off) << L::SHIFT;
     }
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const float mb = ((cbf[0][2 * q] + cbf[0][2 * q + 1]) + (cbf[1][2 * q] + cbf[1][2 * q + 1])) * 0.25f;
     const float mr = ((crf[0][2 * q] + crf[0][2 * q + 1]) + (crf[1][2 * q] + crf[1][2 * q + 1])) * 0.25f;
-    cbq[q] = quant1023(mb * k.c_scale + 512.f) << SH;
-    crq[q] = quant1023(mr * k.c_scale + 512.f) << SH;
+    cbq[q] = quantise<L::QMAX>(mb * k.m.c_scale + (float)L::MID) << L::SHIFT;
+    crq[q] = quantise<L::QMAX>(mr * k.m.c_scale + (float)L::MID) << L::SHIFT;
   }
   const int64_t plane = (int64_t)H * W;
 #pragma unroll
   for (int dy = 0; dy < 2; ++dy) {
-    uint16_t* d = dst + (int64_t)(y0 + dy) * W + x0;
+    Sample* d = dst + (int64_t)(y0 + dy) * W + x0;
     if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t*>(d)[q] = yq[dy][2 * q] | (yq[dy][2 * q + 1] << 16);
+      store_sample_words<L::PER_WORD>(d, yq[dy]);
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        if (j < np) d[j] = (uint16_t)yq[dy][j];
+        if (j < np) d[j] = (Sample)yq[dy][j];
     }
   }
-  if (P010) {
-    uint16_t* d = dst + plane + (int64_t)(y0 >> 1) * W + x0;
+  if constexpr (L::SEMI_PLANAR) {
+    Sample* d = dst + plane + (int64_t)(y0 >> 1) * W + x0;
     if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) reinterpret_cast<uint32_t*>(d)[q] = cbq[q] | (crq[q] << 16);
+      const uint32_t pairs[8] = {cbq[0], crq[0], cbq[1], crq[1], cbq[2], crq[2], cbq[3], crq[3]};
+      store_sample_words<L::PER_WORD>(d, pairs);
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        if (2 * q < np) { d[2 * q] = (uint16_t)cbq[q]; d[2 * q + 1] = (uint16_t)crq[q]; }
+        if (2 * q < np) { d[2 * q] = (Sample)cbq[q]; d[2 * q + 1] = (Sample)crq[q]; }
     }
   } else {
-    uint16_t* db = dst + plane + (int64_t)(y0 >> 1) * (W >> 1) + (x0 >> 1);
-    uint16_t* dr = db + plane / 4;
+    Sample* db = dst + plane + (int64_t)(y0 >> 1) * (W >> 1) + (x0 >> 1);
+    Sample* dr = db + plane / 4;
     if (np == 8 && (reinterpret_cast<uintptr_t>(db) & 3) == 0 && (reinterpret_cast<uintptr_t>(dr) & 3) == 0) {
-      reinterpret_cast<uint32_t*>(db)[0] = cbq[0] | (cbq[1] << 16);
-      reinterpret_cast<uint32_t*>(db)[1] = cbq[2] | (cbq[3] << 16);
-      reinterpret_cast<uint32_t*>(dr)[0] = crq[0] | (crq[1] << 16);
-      reinterpret_cast<uint32_t*>(dr)[1] = crq[2] | (crq[3] << 16);
+      store_sample_words<L::PER_WORD>(db, cbq);
+      store_sample_words<L::PER_WORD>(dr, crq);
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        if (2 * q < np) { db[q] = (uint16_t)cbq[q]; dr[q] = (uint16_t)crq[q]; }
+        if (2 * q < np) { db[q] = (Sample)cbq[q]; dr[q] = (Sample)crq[q]; }
     }
   }
 }
@@ -695,7 +577,7 @@ __global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(cons
     for (int j = 0; j < EPV; ++j) {
       if (!whole && (e0 + j < 0 || e0 + j >= n)) continue;
       uint32_t code;
-      if (F32) code = quant255(__uint_as_float(w[j]) * 255.f) & 255u;   // film_to_uint8's operations (& 255: a NaN stays inside the bins)
+      if (F32) code = quantise<255>(__uint_as_float(w[j]) * 255.f) & 255u;  // film_to_uint8's operations (& 255: a NaN stays inside the bins)
       else if (LAYOUT == FILM_PIX_I010) code = (w[j / 2] >> ((j & 1) * 16 + 2)) & 255u;    // (w & 1023) >> 2
       else if (LAYOUT == FILM_PIX_P010) code = (w[j / 2] >> ((j & 1) * 16 + 8)) & 255u;    // (w >> 6) >> 2
       else code = (w[j / 4] >> ((j & 3) * 8)) & 255u;
@@ -720,9 +602,8 @@ __global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(cons
 // One frame's histogram: zeroes the 768 counters, then counts.  At most FILM_HIST_WG_PER_CU workgroups per compute unit, fewer for a frame
 // that has fewer vectors; the grid-stride loop takes the rest.  (The launcher stands beside its kernel; launch_units: "host" below.)
 hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix, uint32_t* hist, hipStream_t s) {
-  const int layout = pix & 0xff;   // (the colour flags do not enter)
-  const bool yuv16 = layout == FILM_PIX_I010 || layout == FILM_PIX_P010;
-  const bool yuv = layout == FILM_PIX_I420 || layout == FILM_PIX_NV12 || yuv16;
+  const int layout = pix_layout(pix);   // (the colour flags do not enter)
+  const bool yuv = pix_is_yuv(pix);
   if (!frame || !hist || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(frame) & 3)) return hipErrorInvalidValue;
   if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !yuv) return hipErrorInvalidValue;
   if (yuv && ((H | W) & 1)) return hipErrorInvalidValue;
@@ -732,7 +613,7 @@ hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix,
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (e == hipSuccess) e = hipMemsetAsync(hist, 0, FILM_HIST_BINS * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
-  const int epv = layout == FILM_PIX_F32 ? 4 : yuv16 ? 8 : 16;
+  const int epv = FILM_HIST_VEC_BYTES / pix_sample_bytes(pix);
   const int64_t nvec = (n + epv - 1) / epv + 1;   // (+ 1: a frame that starts inside a vector)
   const int64_t grid = std::min<int64_t>((int64_t)std::max(cus, 1) * FILM_HIST_WG_PER_CU, (nvec + FILM_HIST_THREADS - 1) / FILM_HIST_THREADS);
   auto kernel = layout == FILM_PIX_F32 ? frame_histogram_kernel<FILM_PIX_F32> : layout == FILM_PIX_U8 ? frame_histogram_kernel<FILM_PIX_U8>
@@ -769,11 +650,12 @@ YuvTables make_yuv_tables(bool bt601, bool full) {
     t.y[i] = full ? (float)i / 255.0f : ((float)i - 16.0f) / 219.0f;
     t.c[i] = ((float)i - 128.0f) / (full ? 255.0f : 224.0f);
   }
-  t.a_r = (float)(2.0 * (1.0 - Kr)); t.a_b = (float)(2.0 * (1.0 - Kb));
-  t.g_b = (float)(2.0 * Kb * (1.0 - Kb) / Kg); t.g_r = (float)(2.0 * Kr * (1.0 - Kr) / Kg);
-  t.kr = (float)Kr; t.kg = (float)Kg; t.kb = (float)Kb;
-  t.s_b = (float)(0.5 / (1.0 - Kb)); t.s_r = (float)(0.5 / (1.0 - Kr));
-  t.y_scale = full ? 255.0f : 219.0f; t.y_off = full ? 0.0f : 16.0f; t.c_scale = full ? 255.0f : 224.0f;
+  YuvMatrix& m = t.m;
+  m.a_r = (float)(2.0 * (1.0 - Kr)); m.a_b = (float)(2.0 * (1.0 - Kb));
+  m.g_b = (float)(2.0 * Kb * (1.0 - Kb) / Kg); m.g_r = (float)(2.0 * Kr * (1.0 - Kr) / Kg);
+  m.kr = (float)Kr; m.kg = (float)Kg; m.kb = (float)Kb;
+  m.s_b = (float)(0.5 / (1.0 - Kb)); m.s_r = (float)(0.5 / (1.0 - Kr));
+  m.y_scale = full ? 255.0f : 219.0f; m.y_off = full ? 0.0f : 16.0f; m.c_scale = full ? 255.0f : 224.0f;
   return t;
 }
 // the tables of a public pix value (its FILM_YUV_* flags)
@@ -781,18 +663,25 @@ const YuvTables& yuv_tables(int pix) {
   static const YuvTables all[4] = {make_yuv_tables(false, false), make_yuv_tables(false, true), make_yuv_tables(true, false), make_yuv_tables(true, true)};
   return all[((pix & FILM_YUV_BT601) ? 2 : 0) + ((pix & FILM_YUV_FULL) ? 1 : 0)];
 }
-int pix_layout(int pix) { return pix & 0xff; }
-bool pix_is_yuv10(int pix) { return pix_layout(pix) == FILM_PIX_I010 || pix_layout(pix) == FILM_PIX_P010; }
-// The same for a 10-bit layout (include/film_hip.h, "The 10-bit 4:2:0 arithmetic"): the matrix constants are those of the 8-bit tables.
+// The same for a 10-bit layout (include/film_hip.h, "The 10-bit 4:2:0 arithmetic"): the matrix is that of the 8-bit tables, the scales are 10-bit.
 Yuv10Consts yuv10_consts(int pix) {
-  const YuvTables& t = yuv_tables(pix);
   const bool full = (pix & FILM_YUV_FULL) != 0;
   Yuv10Consts k;
   k.y_sub = full ? 0.0f : 64.0f; k.y_div = full ? 1023.0f : 876.0f; k.c_div = full ? 1023.0f : 896.0f;
-  k.a_r = t.a_r; k.a_b = t.a_b; k.g_b = t.g_b; k.g_r = t.g_r;
-  k.kr = t.kr; k.kg = t.kg; k.kb = t.kb; k.s_b = t.s_b; k.s_r = t.s_r;
-  k.y_scale = full ? 1023.0f : 876.0f; k.y_off = full ? 0.0f : 64.0f; k.c_scale = full ? 1023.0f : 896.0f;
+  k.m = yuv_tables(pix).m;
+  k.m.y_scale = full ? 1023.0f : 876.0f; k.m.y_off = full ? 0.0f : 64.0f; k.m.c_scale = full ? 1023.0f : 896.0f;
   return k;
+}
+
+// f(Yuv420<LAYOUT>()) for the 4:2:0 layout of a pix value: how both launchers below choose their kernel instance
+template <class F> hipError_t with_yuv_layout(int pix, F f) {
+  switch (pix_layout(pix)) {
+    case FILM_PIX_I420: return f(Yuv420<FILM_PIX_I420>());
+    case FILM_PIX_NV12: return f(Yuv420<FILM_PIX_NV12>());
+    case FILM_PIX_I010: return f(Yuv420<FILM_PIX_I010>());
+    case FILM_PIX_P010: return f(Yuv420<FILM_PIX_P010>());
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace
@@ -801,23 +690,16 @@ Yuv10Consts yuv10_consts(int pix) {
 // 8-bit kernels read such words).
 hipError_t film_launch_cut_tiles(const TileMapParams& p, int pix, hipStream_t s) {
   const bool ov = (p.ovy | p.ovx) != 0;
-  const int layout = pix_layout(pix);
-  if (layout == FILM_PIX_F32) return launch_units(ov ? frame_to_tiles_kernel<true> : frame_to_tiles_kernel<false>, (int64_t)p.ntiles * p.TH * p.TW * 3, s, p);
+  if (pix_layout(pix) == FILM_PIX_F32) return launch_units(ov ? frame_to_tiles_kernel<true> : frame_to_tiles_kernel<false>, (int64_t)p.ntiles * p.TH * p.TW * 3, s, p);
   if (p.ntiles <= 0) return hipSuccess;
-  if (pix_is_yuv10(pix)) {
-    if ((p.H | p.W) & 1) return hipErrorInvalidValue;
-    const bool p010 = layout == FILM_PIX_P010;
-    return launch_units(ov ? (p010 ? frame_yuv10_to_tiles_kernel<true, true> : frame_yuv10_to_tiles_kernel<true, false>)
-                           : (p010 ? frame_yuv10_to_tiles_kernel<false, true> : frame_yuv10_to_tiles_kernel<false, false>),
-                        (int64_t)p.ntiles * p.TH * ((p.TW + 3) / 4), s, p, yuv10_consts(pix));
-  }
-  if (layout != FILM_PIX_I420 && layout != FILM_PIX_NV12)
+  if (!pix_is_yuv(pix))
     return launch_units(ov ? frame_u8_to_tiles_kernel<true> : frame_u8_to_tiles_kernel<false>, (int64_t)p.ntiles * p.TH * ((p.TW * 3 + 11) / 12), s, p, u8_table());
   if ((p.H | p.W) & 1) return hipErrorInvalidValue;
-  const bool nv12 = layout == FILM_PIX_NV12;
-  return launch_units(ov ? (nv12 ? frame_yuv420_to_tiles_kernel<true, true> : frame_yuv420_to_tiles_kernel<true, false>)
-                         : (nv12 ? frame_yuv420_to_tiles_kernel<false, true> : frame_yuv420_to_tiles_kernel<false, false>),
-                      (int64_t)p.ntiles * p.TH * ((p.TW + 3) / 4), s, p, yuv_tables(pix));
+  return with_yuv_layout(pix, [&](auto l) {
+    using L = decltype(l);
+    return launch_units(ov ? frame_yuv_to_tiles_kernel<true, L::PIX> : frame_yuv_to_tiles_kernel<false, L::PIX>, (int64_t)p.ntiles * p.TH * ((p.TW + 3) / 4), s, p,
+                        L::consts(pix));
+  });
 }
 
 hipError_t film_launch_join_tiles(const TileMapParams& p, hipStream_t s) {
@@ -841,11 +723,9 @@ hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipSt
 
 hipError_t film_launch_rgb_to_yuv420(const float* src, void* dst, int H, int W, int pix, hipStream_t s) {
   if (H <= 0 || W <= 0 || ((H | W) & 1)) return hipErrorInvalidValue;
-  if (pix_is_yuv10(pix)) {
-    if (reinterpret_cast<uintptr_t>(dst) & 1) return hipErrorInvalidValue;
-    return launch_units(pix_layout(pix) == FILM_PIX_P010 ? rgb_to_yuv10_kernel<true> : rgb_to_yuv10_kernel<false>, (int64_t)(H / 2) * ((W + 7) / 8), s, src,
-                        static_cast<uint16_t*>(dst), H, W, yuv10_consts(pix));
-  }
-  return launch_units(pix_layout(pix) == FILM_PIX_NV12 ? rgb_to_yuv420_kernel<true> : rgb_to_yuv420_kernel<false>, (int64_t)(H / 2) * ((W + 7) / 8), s, src,
-                      static_cast<uint8_t*>(dst), H, W, yuv_tables(pix));
+  if (pix_is_yuv10(pix) && (reinterpret_cast<uintptr_t>(dst) & 1)) return hipErrorInvalidValue;
+  return with_yuv_layout(pix, [&](auto l) {
+    using L = decltype(l);
+    return launch_units(rgb_to_yuv_kernel<L::PIX>, (int64_t)(H / 2) * ((W + 7) / 8), s, src, static_cast<typename L::Sample*>(dst), H, W, L::consts(pix));
+  });
 }

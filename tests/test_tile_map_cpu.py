@@ -203,10 +203,12 @@ def test_tile_map_entry_point_is_declared_exported_and_refuses():
         assert not [o for o in old if re.search(r'\b' + o + r'\b', text)], name
     src = open(os.path.join(csrc, 'frame_kernels.hip')).read()
     assert src.count('hipLaunchKernelGGL(') == 1 and '<<<' not in src          # launch_units, behind the kernels, is how this file launches
-    cut_kernel = r'\bframe_(?:u8_|yuv420_)?to_tiles_kernel\b'
+    cut_kernel = r'\bframe_(?:u8_|yuv_)?to_tiles_kernel\b'
+    assert not re.search(r'\bframe_(?!to_|u8_to_|yuv_to_)\w*to_tiles_kernel\b', src)          # (the three cut kernels are all there are)
     host = re.split(r'^(?=hipError_t film_launch_\w+\()', src[src.index('hipLaunchKernelGGL('):], flags=re.M)
     named = {re.match(r'hipError_t (\w+)\(', f).group(1): len(re.findall(cut_kernel, f)) for f in host[1:]}
-    assert named == {'film_launch_cut_tiles': 2 + 2 + 4, 'film_launch_join_tiles': 0, 'film_launch_to_uint8': 0, 'film_launch_rgb_to_yuv420': 0}
+    # float32, u8 and 4:2:0 (every layout through one helper): each named with and without overlap
+    assert named == {'film_launch_cut_tiles': 2 + 2 + 2, 'film_launch_join_tiles': 0, 'film_launch_to_uint8': 0, 'film_launch_rgb_to_yuv420': 0}
     assert not re.search(cut_kernel, host[0])
 
     eng = FilmEngine(TINY, device=-1)

@@ -167,12 +167,12 @@ def test_cut_equals_frame_conversion_then_float_cut(case, geos):
 
 
 ALL_BRANCHES = {
-    'frame_yuv10_to_tiles_kernel<false, false>', 'frame_yuv10_to_tiles_kernel<false, true>', 'frame_yuv10_to_tiles_kernel<true, false>',
-    'frame_yuv10_to_tiles_kernel<true, true>', 'odd row origin', 'odd column origin', 'word path, Y in two aligned words',
+    'frame_yuv_to_tiles_kernel<false, FILM_PIX_I010>', 'frame_yuv_to_tiles_kernel<false, FILM_PIX_P010>', 'frame_yuv_to_tiles_kernel<true, FILM_PIX_I010>',
+    'frame_yuv_to_tiles_kernel<true, FILM_PIX_P010>', 'odd row origin', 'odd column origin', 'word path, Y in two aligned words',
     'word path, Y across three words', 'word path, even column: two chroma samples', 'word path, odd column: three chroma samples',
     'word path, chroma in one word', 'word path, chroma across two words', 'word path, two CbCr pair words', 'word path, three CbCr pair words',
     'sample path', 'padding group', 'vector stores', 'scalar stores'}
-ALL_OUT_BRANCHES = {'rgb_to_yuv10_kernel<false>', 'rgb_to_yuv10_kernel<true>', 'vector loads', 'scalar loads', 'Y word stores', 'Y sample stores',
+ALL_OUT_BRANCHES = {'rgb_to_yuv_kernel<FILM_PIX_I010>', 'rgb_to_yuv_kernel<FILM_PIX_P010>', 'vector loads', 'scalar loads', 'Y word stores', 'Y sample stores',
                     'chroma word stores', 'chroma sample stores'}
 OUT_SIZES = [(2, 2), (16, 18), (30, 50)]       # what tests/test_yuv10_gpu.py runs film_to_yuv420 on
 OUT_OFFSETS = (0, 2)                           # ... with dst 4-byte aligned and 2 bytes behind that
@@ -192,7 +192,7 @@ def test_the_cases_reach_every_instance_and_branch(geos):
     union = set().union(*seen.values())
     assert union == ALL_BRANCHES, (sorted(ALL_BRANCHES - union), sorted(union - ALL_BRANCHES))
     assert 'odd column origin' in seen['y1-30x50-b3x2'] and 'odd row origin' not in seen['y1-30x50-b3x2']
-    assert {'odd column origin', 'odd row origin', 'frame_yuv10_to_tiles_kernel<true, true>'} <= seen['y2-30x50-b3x2-ov3x5']
+    assert {'odd column origin', 'odd row origin', 'frame_yuv_to_tiles_kernel<true, FILM_PIX_P010>'} <= seen['y2-30x50-b3x2-ov3x5']
     assert not seen['y3-16x16'] & {'sample path', 'padding group', 'scalar stores', 'word path, Y across three words'}       # the pure fast path
     assert not any(b.startswith('word path') for b in seen['y4-2x2'])
     assert 'scalar stores' in seen['y6-12x22-b1x2-noalign']

@@ -161,11 +161,11 @@ def test_cut_equals_frame_conversion_then_float_cut(case, geos):
 
 
 ALL_BRANCHES = {
-    'frame_yuv420_to_tiles_kernel<false, false>', 'frame_yuv420_to_tiles_kernel<false, true>', 'frame_yuv420_to_tiles_kernel<true, false>',
-    'frame_yuv420_to_tiles_kernel<true, true>', 'odd row origin', 'odd column origin', 'word path, Y in one aligned word',
+    'frame_yuv_to_tiles_kernel<false, FILM_PIX_I420>', 'frame_yuv_to_tiles_kernel<false, FILM_PIX_NV12>', 'frame_yuv_to_tiles_kernel<true, FILM_PIX_I420>',
+    'frame_yuv_to_tiles_kernel<true, FILM_PIX_NV12>', 'odd row origin', 'odd column origin', 'word path, Y in one aligned word',
     'word path, Y across two words', 'word path, even column: two chroma samples', 'word path, odd column: three chroma samples',
     'word path, chroma in one word', 'word path, chroma across two words', 'byte path', 'padding group', 'vector stores', 'scalar stores'}
-ALL_OUT_BRANCHES = {'rgb_to_yuv420_kernel<false>', 'rgb_to_yuv420_kernel<true>', 'vector loads', 'scalar loads', 'Y word stores', 'Y byte stores',
+ALL_OUT_BRANCHES = {'rgb_to_yuv_kernel<FILM_PIX_I420>', 'rgb_to_yuv_kernel<FILM_PIX_NV12>', 'vector loads', 'scalar loads', 'Y word stores', 'Y byte stores',
                     'chroma word stores', 'chroma byte stores'}
 OUT_SIZES = [(2, 2), (16, 18), (30, 50)]       # what tests/test_yuv_gpu.py runs film_to_yuv420 on
 
@@ -184,7 +184,7 @@ def test_the_cases_reach_every_instance_and_branch(geos):
     union = set().union(*seen.values())
     assert union == ALL_BRANCHES, (sorted(ALL_BRANCHES - union), sorted(union - ALL_BRANCHES))
     assert 'odd column origin' in seen['y1-30x50-b3x2'] and 'odd row origin' not in seen['y1-30x50-b3x2']
-    assert {'odd column origin', 'odd row origin', 'frame_yuv420_to_tiles_kernel<true, true>'} <= seen['y2-30x50-b3x2-ov3x5']
+    assert {'odd column origin', 'odd row origin', 'frame_yuv_to_tiles_kernel<true, FILM_PIX_NV12>'} <= seen['y2-30x50-b3x2-ov3x5']
     assert not seen['y3-16x16'] & {'byte path', 'padding group', 'scalar stores', 'word path, Y across two words'}       # the pure fast path
     assert not any(b.startswith('word path') for b in seen['y4-2x2'])
     assert 'scalar stores' in seen['y6-12x22-b1x2-noalign']
