@@ -61,6 +61,7 @@ constexpr OptionRow kOptions[] = {
     {"host_overlap", &film_t::opt_host_overlap, BOOL, false},
     {"block_overlap_h", &film_t::opt_block_overlap_h, AS_IS, false, -1, 65535, "block_overlap_h: -1 (what the align padding of a tile holds) or 0 .. 65535 rows"},
     {"block_overlap_w", &film_t::opt_block_overlap_w, AS_IS, false, -1, 65535, "block_overlap_w: -1 (what the align padding of a tile holds) or 0 .. 65535 columns"},
+    {"stream_times", &film_t::opt_stream_times, AS_IS, false, 1, 6, "stream_times: 1 .. 6 (a primed push of a stream opened with T writes 2^T - 1 frames)"},
     {"scene_cut", &film_t::opt_scene_cut, AS_IS, false, 0, 1000, "scene_cut: 0 (off) or 1 .. 1000 permille of the histogram distance"},
     {"tune_ms", &film_t::opt_tune_ms, NONNEG, false},
     {"splitk", &film_t::opt_splitk, BOOL, true},
@@ -341,12 +342,33 @@ bool same_geometry(const TileMapParams& a, const TileMapParams& b) {
   const int vb[] = {b.H, b.W, b.bh, b.bw, b.ph, b.pw, b.TH, b.TW, b.oy, b.ox, b.ovy, b.ovx, b.eh, b.ew};
   return std::equal(std::begin(va), std::end(va), std::begin(vb));
 }
-// The frame the stream keeps -> its tiles in half `slot` of the plan's img0 (an 8-bit frame is dequantised by the cut itself)
-hipError_t stream_cut(const FilmStream& fs, TileMapParams tp, const Plan* P, int slot, hipStream_t s) {
+// A frame of pixel type `pix` -> its tiles in slot `slot` of the plan's img0 (an 8-bit frame is dequantised by the cut itself)
+hipError_t stream_cut(const void* frame, int pix, TileMapParams tp, const Plan* P, int slot, hipStream_t s) {
   tp.tile0 = 0; tp.ntiles = tp.bh * tp.bw;
-  tp.src = (const float*)fs.keep;
+  tp.src = (const float*)frame;
   tp.dst = P->at("img0") + (int64_t)slot * tp.ntiles * tp.TH * tp.TW * 3;
-  return film_launch_cut_tiles(tp, fs.pix, s);
+  return film_launch_cut_tiles(tp, pix, s);
+}
+
+// The steps of ONE primed push of a "stream_times" = T stream whose input frame lands in slot `slot` (0 / 1; the frame before waits in the
+// other one), in execution order - the reference's recursion (eval/util.py, _recursive_generator) depth first.  A step runs the pair
+// (frame in slot `left`, frame in slot `right`) - with `extract`, behind the extraction of the right frame, which no step has extracted
+// before - and yields the frame at position `index` of the 2^T - 1 between the two inputs (1-based, temporal order), a depth-`depth`
+// mid-frame.  feed >= 0: the result is cut, as float32, into slot `feed` = 1 + depth, where its two children find it: the left child
+// (left, feed) extracts it, the right child (feed, right) reads what the left one extracted.  The deepest mids are fed nowhere.
+struct StreamStep { int left, right, extract, index, depth, feed; };
+void stream_steps(int T, int left, int right, bool extract, int depth, int index, std::vector<StreamStep>* v) {
+  const int feed = depth < T ? 1 + depth : -1;
+  v->push_back({left, right, extract ? 1 : 0, index, depth, feed});
+  if (feed < 0) return;
+  const int half = 1 << (T - depth - 1);
+  stream_steps(T, left, feed, true, depth + 1, index - half, v);
+  stream_steps(T, feed, right, false, depth + 1, index + half, v);
+}
+std::vector<StreamStep> stream_schedule(int T, int slot) {
+  std::vector<StreamStep> v;
+  stream_steps(T, 1 - slot, slot, true, 1, 1 << (T - 1), &v);
+  return v;
 }
 
 // Option "scene_cut" = k > 0: the histogram of the frame in fs.keep, taken on `s`, downloaded and waited for; *cut = the rule's verdict
@@ -676,9 +698,39 @@ int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* bu
   if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the half of the frame buffers the pushed frame fills)");
   if (tiles >= 1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
   Plan* P = nullptr;
-  int rc = get_plan(h, tiles, H, W, false, &P, tiles, true);
+  int rc = get_plan(h, tiles, H, W, false, &P, tiles, 2);
   if (rc) return rc;
   return copy_out_string(h, plan_json(h, *P->orientation(slot)), buf, cap, needed);
+}
+
+int film_stream_pair_plan_json(film_t* h, int tiles, int H, int W, int times, int left, int right, int extract, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (tiles < 1) return fail(h, FILM_ERR_INVALID, "tiles must be positive");
+  if (times < 1 || times > 6) return fail(h, FILM_ERR_INVALID, "times must be 1 .. 6 (option \"stream_times\")");
+  if (left < 0 || right < 0 || left > times || right > times || left == right)
+    return fail(h, FILM_ERR_INVALID, "left and right must be two different slots of 0 .. %d (times + 1 frame slots)", times);
+  if (tiles >= 1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
+  Plan *P = nullptr, *Q = nullptr;
+  int rc = get_plan(h, tiles, H, W, false, &P, tiles, times + 1);
+  if (rc == FILM_OK) rc = plan_orientation(h, P, left, right, extract != 0, &Q);
+  if (rc) return rc;
+  return copy_out_string(h, plan_json(h, *Q, true), buf, cap, needed);
+}
+
+int film_stream_schedule_json(film_t* h, int times, int slot, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (times < 1 || times > 6) return fail(h, FILM_ERR_INVALID, "times must be 1 .. 6 (option \"stream_times\")");
+  if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the slot the pushed frame fills)");
+  std::ostringstream o;
+  o << "{\"times\":" << times << ",\"slot\":" << slot << ",\"slots\":" << times + 1 << ",\"produced\":" << (1 << times) - 1 << ",\"steps\":[";
+  const std::vector<StreamStep> steps = stream_schedule(times, slot);
+  for (size_t i = 0; i < steps.size(); ++i) {
+    const StreamStep& t = steps[i];
+    o << (i ? "," : "") << "{\"left\":" << t.left << ",\"right\":" << t.right << ",\"extract\":" << t.extract << ",\"index\":" << t.index
+      << ",\"depth\":" << t.depth << ",\"feed\":" << t.feed << "}";
+  }
+  o << "]}";
+  return copy_out_string(h, o.str(), buf, cap, needed);
 }
 
 int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix) {
@@ -701,21 +753,28 @@ int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_
   if (T > tmax)
     return fail(h, FILM_ERR_INVALID, "a stream runs the whole frame in one model invocation: its %d tiles of %d x %d exceed the %d tiles one invocation "
                 "may take (64 GiB / 60 %% of the free HBM of workspace, 4 GiB per 32-bit addressed buffer, \"max_batch\") - use a finer block_shape", T, tp.TH, tp.TW, tmax);
+  const int times = h->opt_stream_times;   // fixed for this stream's life
   Plan* P = nullptr;
-  rc = get_plan(h, T, tp.TH, tp.TW, true, &P, T, true);   // (built and tuned now; FILM_ERR_NOMEM when the workspace does not fit)
+  rc = get_plan(h, T, tp.TH, tp.TW, true, &P, T, times + 1);   // (built and tuned now; FILM_ERR_NOMEM when the workspace does not fit)
   if (rc) return rc;
   FilmStream& fs = h->fs;
   const size_t nv = (size_t)H * W * 3;
   const size_t fb = frame_bytes(pix, H, W);
+  // a primed push leaves n frames: a host push downloads each as soon as it is there and waits once, so each has a place of its own -
+  // float32 streams in `result`, the others (whose float32 frame is only joined, quantised and fed back) in `result8`
+  const size_t n = ((size_t)1 << times) - 1;
+  const bool f32 = pix_layout(pix) == FILM_PIX_F32;
+  const size_t rbytes = (f32 ? n : 1) * nv * sizeof(float), qbytes = f32 ? 0 : n * fb;
   hipError_t e = hipMalloc(&fs.keep, (fb + 3) & ~(size_t)3);   // (whole 32-bit words: the 8-bit cuts read aligned words)
-  if (e == hipSuccess) e = hipMalloc((void**)&fs.result, nv * sizeof(float));
-  if (e == hipSuccess && pix_layout(pix) != FILM_PIX_F32) e = hipMalloc((void**)&fs.result8, fb);
+  if (e == hipSuccess) e = hipMalloc((void**)&fs.result, rbytes);
+  if (e == hipSuccess && !f32) e = hipMalloc((void**)&fs.result8, qbytes);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     stream_free(h);
-    return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's frame buffers (%.1f MB) failed", (2 * fb + nv * sizeof(float)) * 1e-6);
+    return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's frame buffers (%.1f MB, stream_times = %d) failed", (fb + rbytes + qbytes) * 1e-6, times);
   }
   fs.open = true;
+  fs.times = times;
   fs.H = H; fs.W = W; fs.align = align; fs.block_h = block_h; fs.block_w = block_w; fs.pix = pix;
   return FILM_OK;
 }
@@ -775,15 +834,16 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
   if (rc) return rc;
   const int T = tp.bh * tp.bw;
   Plan* P0 = nullptr;
-  rc = get_plan(h, T, tp.TH, tp.TW, true, &P0, T, true);
+  rc = get_plan(h, T, tp.TH, tp.TW, true, &P0, T, fs.times + 1);
   if (rc) return rc;
   const bool host = mem_kind == FILM_MEM_HOST;
   const size_t nv = (size_t)fs.H * fs.W * 3;
   if (fs.primed && (fs.plan_id != P0->id || !same_geometry(fs.geo, tp))) {
     // the plan that held the previous frame's pyramids was evicted or dropped since (or the tiles changed): extract that frame again
     // from the stream's own copy, where it was - the same ops on the same values, the same bits
-    Plan* R = P0->orientation(fs.slot);
-    HIPCHK(h, stream_cut(fs, tp, R, fs.slot, s));
+    Plan* R = nullptr;
+    if ((rc = plan_orientation(h, P0, 1 - fs.slot, fs.slot, true, &R))) return rc;
+    HIPCHK(h, stream_cut(fs.keep, fs.pix, tp, R, fs.slot, s));
     if ((rc = run_plan(h, R, s, R->n_extract))) return rc;
   }
   const size_t fb = frame_bytes(fs.pix, fs.H, fs.W);
@@ -794,31 +854,44 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
   if (scene_k > 0 && (rc = stream_scene_cut(h, s, scene_k, &cut))) return rc;
   const bool primed = fs.primed && !cut;
   const int slot = primed ? 1 - fs.slot : 0;
-  Plan* P = P0->orientation(slot);
-  HIPCHK(h, stream_cut(fs, tp, P, slot, s));
+  Plan* P = nullptr;
+  if ((rc = plan_orientation(h, P0, 1 - slot, slot, true, &P))) return rc;
+  HIPCHK(h, stream_cut(fs.keep, fs.pix, tp, P, slot, s));
+  int made = 0;
   if (!primed) {
     if ((rc = run_plan(h, P, s, P->n_extract))) return rc;
   } else {
-    if ((rc = run_plan(h, P, s))) return rc;
-    // joined in float32 by the kernels of film_interpolate, then quantised by film_to_uint8's kernel for an 8-bit RGB stream, by
-    // film_to_yuv420's for a 4:2:0 stream (8-bit or 10-bit)
-    float* joined = (fs.pix == FILM_PIX_F32 && !host) ? (float*)mid : fs.result;
-    TileMapParams j = tp;
-    j.tile0 = 0; j.ntiles = T; j.src = P->at("out"); j.dst = joined;
-    HIPCHK(h, film_launch_join_tiles(j, s));
-    if (fs.pix != FILM_PIX_F32) {
-      void* q = host ? (void*)fs.result8 : mid;
-      if (pix_is_yuv(fs.pix))
-        HIPCHK(h, film_launch_rgb_to_yuv420(joined, q, fs.H, fs.W, fs.pix, s));
-      else
-        HIPCHK(h, film_launch_to_uint8(joined, static_cast<uint8_t*>(q), (int64_t)nv, s));
-      if (host) HIPCHK(h, hipMemcpyAsync(mid, q, fb, hipMemcpyDeviceToHost, s));
-    } else if (host) {
-      HIPCHK(h, hipMemcpyAsync(mid, joined, nv * sizeof(float), hipMemcpyDeviceToHost, s));
+    // One pair run per generated frame, in the order of stream_schedule (times = 1: the one pair of the two inputs).  Each result is
+    // joined in float32 by the kernels of film_interpolate - straight into its place in `mid` for a device float32 stream - then
+    // quantised into its place by film_to_uint8's kernel for an 8-bit RGB stream, by film_to_yuv420's for a 4:2:0 stream (8-bit or
+    // 10-bit); a result that has children is cut from the float32 frame - never from the quantised one - into its slot by the float cut.
+    struct AppendProfile { film_t* h; ~AppendProfile() { h->profile_append = false; } } append{h};
+    const bool f32 = fs.pix == FILM_PIX_F32;
+    for (const StreamStep& t : stream_schedule(fs.times, slot)) {
+      Plan* Q = nullptr;
+      if ((rc = plan_orientation(h, P0, t.left, t.right, t.extract != 0, &Q)) || (rc = run_plan(h, Q, s))) return rc;
+      h->profile_append = true;   // (option "profile": the runs of this push add up)
+      const size_t k = (size_t)t.index - 1;
+      float* joined = !f32 ? fs.result : host ? fs.result + k * nv : (float*)mid + k * nv;
+      TileMapParams j = tp;
+      j.tile0 = 0; j.ntiles = T; j.src = Q->at("out"); j.dst = joined;
+      HIPCHK(h, film_launch_join_tiles(j, s));
+      if (!f32) {
+        void* q = host ? (void*)(fs.result8 + k * fb) : (void*)((unsigned char*)mid + k * fb);
+        if (pix_is_yuv(fs.pix))
+          HIPCHK(h, film_launch_rgb_to_yuv420(joined, q, fs.H, fs.W, fs.pix, s));
+        else
+          HIPCHK(h, film_launch_to_uint8(joined, static_cast<uint8_t*>(q), (int64_t)nv, s));
+        if (host) HIPCHK(h, hipMemcpyAsync((unsigned char*)mid + k * fb, q, fb, hipMemcpyDeviceToHost, s));
+      } else if (host) {
+        HIPCHK(h, hipMemcpyAsync((float*)mid + k * nv, joined, nv * sizeof(float), hipMemcpyDeviceToHost, s));
+      }
+      if (t.feed >= 0) HIPCHK(h, stream_cut(joined, FILM_PIX_F32, tp, Q, t.feed, s));
+      ++made;
     }
   }
   if (host) HIPCHK(h, hipStreamSynchronize(s));
-  *produced = primed ? 1 : 0;
+  *produced = made;
   fs.primed = true; fs.slot = slot; fs.plan_id = P0->id; fs.geo = tp;
   fs.hist_valid = scene_k > 0; fs.cut = cut ? 1 : 0;
   unprime.armed = false;

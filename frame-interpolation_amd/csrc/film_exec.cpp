@@ -177,17 +177,18 @@ int run_plan(film_t* h, Plan* P, hipStream_t s, size_t n_ops) {
       HIPCHK(h, hipEventRecord(P->ev[i + 1], s));
     }
     HIPCHK(h, hipStreamSynchronize(s));
-    struct Acc { int launches = 0; double ms = 0, flops = 0, bytes = 0; };
-    std::map<std::string, Acc> cls;
+    if (!h->profile_append) { h->profile_ops.clear(); h->profile_classes.clear(); }   // (appending: one film_stream_push of several runs)
+    auto& cls = h->profile_classes;
     std::ostringstream ops;
     for (size_t i = 0; i < n; ++i) {
       float ms = 0;
       HIPCHK(h, hipEventElapsedTime(&ms, P->ev[i], P->ev[i + 1]));
-      Acc& a = cls[kKindName[P->ops[i].kind]];
+      film_t::ProfileClass& a = cls[kKindName[P->ops[i].kind]];
       a.launches++; a.ms += ms; a.flops += P->ops[i].flops; a.bytes += P->ops[i].bytes;
-      ops << (i ? "," : "") << "{\"tag\":\"" << P->ops[i].tag << "\",\"kind\":\"" << kKindName[P->ops[i].kind] << "\",\"ms\":" << ms
+      ops << (i || !h->profile_ops.empty() ? "," : "") << "{\"tag\":\"" << P->ops[i].tag << "\",\"kind\":\"" << kKindName[P->ops[i].kind] << "\",\"ms\":" << ms
           << ",\"flops\":" << P->ops[i].flops << ",\"bytes\":" << P->ops[i].bytes << ",\"tile\":" << P->ops[i].tile << "}";
     }
+    h->profile_ops += ops.str();
     std::ostringstream o;
     o << "{\"B\":" << B << ",\"H\":" << H << ",\"W\":" << W << ",\"classes\":{";
     bool first = true;
@@ -196,7 +197,7 @@ int run_plan(film_t* h, Plan* P, hipStream_t s, size_t n_ops) {
         << ",\"flops\":" << kv.second.flops << ",\"bytes\":" << kv.second.bytes << "}";
       first = false;
     }
-    o << "},\"ops\":[" << ops.str() << "]}";
+    o << "},\"ops\":[" << h->profile_ops << "]}";
     h->profile_json = o.str();
   } else if (prefix) {
     for (size_t i = 0; i < n_ops; ++i) HIPCHK(h, launch_op(P->ops[i], P->arena, h->packed_dev, s));

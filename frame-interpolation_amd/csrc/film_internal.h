@@ -130,14 +130,25 @@ struct Plan {
   // 0: a pair plan (img0 = [x0 tiles | x1 tiles], 2B images); > 0: a sequence plan over B / tiles consecutive frame pairs of `tiles`
   // tiles each (img0 = B + tiles images, frame-major: image f * tiles + t; pair-tile p reads images p and p + tiles)
   int tiles = 0;
-  // A stream plan (film_stream_*): the sequence plan of ONE pair of `tiles` tiles (B == tiles, img0 = 2 tiles images) whose two frame
-  // halves take turns.  slot = the half the pushed frame fills - its image pyramid and feature ops, NB = tiles, are ops [0, n_extract) -
-  // the other half holds what the push before left there: the pair's earlier frame.  The cached plan is the slot-0 orientation; `twin`
-  // is the slot-1 one over the SAME buffers and workspace (it owns no arena).  -1: not a stream plan.
+  // A stream plan (film_stream_*): the sequence plan of ONE pair of `tiles` tiles (B == tiles) over `slots` frame slots of `tiles` images
+  // each in the per-image buffers (img*, feat*, extractor scratch): 2 for a plain stream - the two frames of a pair take turns - and T + 1
+  // with option "stream_times" = T: slots 0 and 1 take turns for the input frames, slot 1 + d holds the depth-d mid-frame that is fed back.
+  // An ORIENTATION is (left, right, extract): image 0 of the pair is the frame in slot `left`, image 1 the one in slot `right`, and with
+  // `extract` the image pyramid and feature ops of the right frame, NB = tiles, are ops [0, n_extract) - else the plan has none of them
+  // (n_extract = 0: a plan of its own with its own lane analysis, never the tail of an extracting one).  `slot` = right (-1: not a stream
+  // plan).  The cached plan is orientation (1, 0, extract); `others` holds the rest, keyed by orientation_key, over the SAME buffers and
+  // workspace (they own no arena), built on first use (plan_orientation).
   int slot = -1;
+  int slots = 0, left = -1;
+  bool extract = true;
   size_t n_extract = 0;
-  std::unique_ptr<Plan> twin;
-  Plan* orientation(int s) { return s == slot ? this : twin.get(); }
+  std::map<int, std::unique_ptr<Plan>> others;
+  static int orientation_key(int l, int r, bool e) { return (l * 16 + r) * 2 + (e ? 1 : 0); }
+  Plan* orientation(int s) {   // the extracting orientation of a two-slot push into slot s, if it is built
+    if (s == slot && left == 1 - s && extract) return this;
+    auto it = others.find(orientation_key(1 - s, s, true));
+    return it == others.end() ? nullptr : it->second.get();
+  }
   uint64_t id = 0;           // unique per handle and build: a stream tells a rebuilt plan (its carried features are gone) from the one it filled
   std::vector<Buffer> bufs;
   std::vector<OpDesc> ops;
@@ -176,6 +187,8 @@ struct FilmStream {
   void* keep = nullptr;             // the last pushed frame: [H][W][3] float32 or bytes, or the H * W * 3 / 2 bytes of a 4:2:0 frame
   float* result = nullptr;          // the joined float32 mid-frame of a host or 8-bit push
   unsigned char* result8 = nullptr; // ... quantised (RGB bytes or a 4:2:0 frame, 8-bit or 10-bit), of a host push that is not float32
+  int times = 1;                    // option "stream_times" when the stream was opened: a primed push writes 2^times - 1 frames; `result` (float32
+                                    // streams) and `result8` hold that many frames, so that a host push downloads them behind one wait
   bool primed = false;              // `keep` holds a frame
   int slot = 0;                     // the half of the plan's frame buffers it was extracted into ...
   uint64_t plan_id = 0;             // ... of this plan (Plan::id) ...
@@ -229,6 +242,7 @@ struct film_handle {
   // cross-faded over the shared pixels (tile_geometry in film_engine.cpp; blend_tiles_kernel).  0 (default): the reference's disjoint
   // patches.  -1: as much as the tile's align padding holds (the padded tile, and with it the plan, stays the same).
   int opt_block_overlap_h = 0, opt_block_overlap_w = 0;
+  int opt_stream_times = 1;   // film_stream_open: T = 1 .. 6, a primed push of that stream writes the 2^T - 1 frames of the reference's recursion
   int opt_scene_cut = 0;      // film_stream_push: permille of the histogram distance from which a pair of frames is a scene cut (0: off)
   int opt_host_overlap = 1;   // film_interpolate(FILM_MEM_HOST): 1 = the second frame's upload behind the first frame's first layers, the first half of the
                               // result downloaded behind the second half's last layer (film_engine.cpp, "host pipeline"); 0 = copies, then work, then copy
@@ -257,6 +271,11 @@ struct film_handle {
   int opt_fold4_shape = -1; // tests: >= 0 = every conv_fold4_kernel op that can run this Fold4Tile shape does
   int opt_w43_shape = -1; // tests: >= 0 = every conv_wino43_kernel op that can run this Wino43Tile shape does (instead of the autotuned one)
   std::string profile_json;
+  // option "profile": what run_plan has measured - of the last run, or (profile_append: a film_stream_push of several runs) of every run since the flag was set
+  struct ProfileClass { int launches = 0; double ms = 0, flops = 0, bytes = 0; };
+  bool profile_append = false;
+  std::string profile_ops;
+  std::map<std::string, ProfileClass> profile_classes;
   std::map<std::string, int> tune_cache;  // conv shape signature -> fastest tile
   std::map<std::string, int> tune_import; // choices of an earlier process (film_import_tune): taken, if still a candidate of
                                           // the op's kernel family, instead of timing the candidates again
@@ -325,17 +344,20 @@ int run_plan(film_t* h, Plan* P, hipStream_t s, size_t n_ops = SIZE_MAX);   // n
 
 // ---- film_tune.cpp (the nine *_candidates of kConvFamily: film_kernels.h)
 std::vector<int> conv_candidates(const OpDesc& op);
-int autotune_plan(film_t* h, Plan* P);
+int autotune_plan(film_t* h, Plan* P, bool measure = true);   // !measure: only the choices made already (the workspace is not touched)
 
 // ---- film_plans.cpp
-int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles = 0, bool stream = false);   // stream: B == tiles
+int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles = 0, int slots = 0);   // slots >= 2: the stream plan, B == tiles
+// orientation (left, right, extract) of the stream plan P0 (what get_plan returned), built, tuned and cached with it on first use
+int plan_orientation(film_t* h, Plan* P0, int left, int right, bool extract, Plan** out);
 void drop_plans(film_t* h);   // waits for the device, then frees every cached plan
 int max_units(film_t* h, int H, int W, const char* what, const char* advice, int* units);
 
 // ---- film_planner.cpp
-// fills P->bufs / ops / arena_floats for (B, H, W) (tiles > 0: sequence plan; slot >= 0: that orientation of a stream plan, B == tiles)
-int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles = 0, int slot = -1);
+// fills P->bufs / ops / arena_floats for (B, H, W) (tiles > 0: sequence plan; slots >= 2: orientation (left, right, extract) of the stream plan
+// of that many frame slots, B == tiles)
+int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles = 0, int slots = 0, int left = -1, int right = -1, bool extract = true);
 int64_t limited_buffer_bytes(const Plan* P);                // largest buffer a kernel with whole-buffer 32-bit offsets reads
-std::string plan_json(film_t* h, const Plan& P);
+std::string plan_json(film_t* h, const Plan& P, bool orientation_keys = false);   // (a stream plan: "slot", or "slots", "left", "right")
 
 }  // namespace film_internal

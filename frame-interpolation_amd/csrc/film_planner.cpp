@@ -9,10 +9,11 @@
 // A sequence plan (tiles > 0) runs F - 1 consecutive pairs of F frames: the image pyramids and the extractor run once per
 // frame (B + tiles images), every op that reaches the other image of a pair is emitted per direction with that image one
 // pointer offset of `tiles` images away, and the flow estimator (2B) and the decoder (B) are the pair plan's.
-// A stream plan (slot = 0 / 1) is the sequence plan of ONE pair whose two frame halves take turns between calls: the per-image stages
-// run on the `tiles` images of half `slot` only - the frame just pushed, the pair's later one - and come first in the op list
-// (Plan::n_extract of them); the other half holds what the call before left there, the pair's earlier frame.  Both orientations
-// lay out the same buffers at the same offsets and emit the same ops but for those image offsets.
+// A stream plan is the sequence plan of ONE pair over `slots` frame slots of `tiles` images each (2: the two frames of a pair take turns
+// between calls; T + 1 with option "stream_times" = T: one more slot per depth of mid-frames that are fed back).  An orientation (left,
+// right, extract) reads the pair's earlier frame in slot `left` and its later one in slot `right`; with `extract` the per-image stages run
+// on the `tiles` images of slot `right` only and come first in the op list (Plan::n_extract of them), else the plan has none of them.
+// Every orientation lays out the same buffers at the same offsets and emits the same ops but for those image offsets.
 // Top down: the kernel decisions (plain_conv_family / folded_conv_family / conv_ksplit: pure functions of a convolution's shape, its buffers'
 // layout and the options - never of timing or the batch size), the Planner (a helper per op kind, a member per stage of the graph,
 // Planner::build their sequence), the cross-lane dependencies of the two-stream replay (analyze_lanes), a plan as JSON (film_plan_json).
@@ -618,7 +619,7 @@ struct Planner {
     }
   }
 
-  int build(int B_, int H_, int W_, int T_, int slot) {
+  int build(int B_, int H_, int W_, int T_, int slots, int left, int right, bool extract) {
     const film_config& c = h->cfg;
     B = B_; H0 = H_; W0 = W_; T = T_;
     NL = c.pyramid_levels; FL = c.fusion_pyramid_levels;
@@ -627,17 +628,23 @@ struct Planner {
     NI = seq ? B + T : N2;
     i0 = 0; i1 = seq ? T : B;
     NE = NI; e0 = 0;
-    if (slot >= 0) {   // stream plan: the pushed frame (the pair's image 1) is extracted into half `slot`, image 0 waits in the other half
-      if (slot > 1 || B != T) return fail(h, FILM_ERR_INVALID, "a stream plan has slot 0 or 1 and one pair of its tiles");
-      i0 = (1 - slot) * T; i1 = slot * T;
+    if (slots > 0) {   // stream plan: the right frame (the pair's image 1) is extracted into slot `right`, image 0 waits in slot `left`
+      if (slots < 2 || left < 0 || right < 0 || left >= slots || right >= slots || left == right || B != T)
+        return fail(h, FILM_ERR_INVALID, "a stream plan has two different slots out of its %d and one pair of its tiles", slots);
+      NI = slots * T;
+      i0 = left * T; i1 = right * T;
       NE = T; e0 = i1;
     }
     fc = feature_channels(c);
     ff = fusion_filters(c);
-    P->B = B; P->H = H0; P->W = W0; P->tiles = T; P->slot = slot;
+    P->B = B; P->H = H0; P->W = W0; P->tiles = T;
+    P->slots = slots; P->slot = slots > 0 ? right : -1; P->left = slots > 0 ? left : -1; P->extract = extract;
     add_buffers();
     emit_image_pyramids();
     for (int i = 0; i < NL; ++i) emit_extractor(i);
+    // an orientation that extracts nothing: the extraction is emitted all the same - its split-K regions are part of the workspace
+    // every orientation shares - and dropped again BEFORE the lanes are analysed, so no remaining op waits for one of them
+    if (slots > 0 && !extract) P->ops.clear();
     P->n_extract = P->ops.size();
     for (int l = NL - 1; l >= 0; --l) emit_flow(l);
     // Option "lanes" >= 2 (NOT the default - measured 2 % slower, see opt_lanes), large frames: the COARSE decoder levels (>= 2) join the side stream right behind the
@@ -721,9 +728,9 @@ struct Planner {
 
 }  // namespace
 
-int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles, int slot) {
+int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles, int slots, int left, int right, bool extract) {
   Planner pl{h, P};
-  return pl.build(B, H, W, tiles, slot);
+  return pl.build(B, H, W, tiles, slots, left, right, extract);
 }
 
 // The conv kernels other than conv_wino43_kernel address their inputs with 32-bit byte offsets from the start of the
@@ -789,11 +796,16 @@ void json_op(JsonObject& j, const OpDesc& op, const Plan& P) {
 }
 }  // namespace
 
-std::string plan_json(film_t* h, const Plan& P) {
+std::string plan_json(film_t* h, const Plan& P, bool orientation_keys) {
   std::ostringstream o;
   JsonObject j{o};
   j.num("B", P.B); j.num("H", P.H); j.num("W", P.W);
-  if (P.slot >= 0) { j.str("kind", "stream"); j.num("tiles", P.tiles); j.num("slot", P.slot); j.num("n_extract", P.n_extract); }
+  if (P.slot >= 0) {
+    j.str("kind", "stream"); j.num("tiles", P.tiles);
+    if (orientation_keys) { j.num("slots", P.slots); j.num("left", P.left); j.num("right", P.slot); }
+    else j.num("slot", P.slot);
+    j.num("n_extract", P.n_extract);
+  }
   else if (P.tiles > 0) { j.str("kind", "sequence"); j.num("n_pairs", P.B / P.tiles); j.num("tiles", P.tiles); }
   j.num("arena_floats", P.arena_floats); j.num("offset32_buffer_bytes", limited_buffer_bytes(&P)); j.num("packed_floats", h->packed_floats);
   j.objects("buffers", P.bufs.data(), P.bufs.size(), [](JsonObject& e, const Buffer& b) {

@@ -5,7 +5,7 @@
 namespace film_internal {
 namespace {
 void free_plan(Plan* p) {
-  if (p->twin) { p->twin->arena = nullptr; free_plan(p->twin.get()); }   // (the other orientation of a stream plan works on this plan's arena)
+  for (auto& kv : p->others) { kv.second->arena = nullptr; free_plan(kv.second.get()); }   // (the other orientations of a stream plan work on this plan's arena)
   if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
   if (p->graph) (void)hipGraphDestroy(p->graph);
   for (auto e : p->ev) (void)hipEventDestroy(e);
@@ -15,7 +15,8 @@ void free_plan(Plan* p) {
 
 // Plan `index` leaves the cache with everything it holds on the device.  Work that may still run on it is the caller's to wait for.
 void forget_plan(film_t* h, size_t index) {
-  if (h->last_plan == h->plans[index].get() || (h->last_plan && h->last_plan == h->plans[index]->twin.get())) h->last_plan = nullptr;
+  if (h->last_plan == h->plans[index].get()) h->last_plan = nullptr;
+  for (auto& kv : h->plans[index]->others) if (h->last_plan == kv.second.get()) h->last_plan = nullptr;
   free_plan(h->plans[index].get());
   h->plans.erase(h->plans.begin() + index);
 }
@@ -39,18 +40,64 @@ int64_t arena_budget_bytes(film_t* h) {
   }
   return std::max<int64_t>(cap, 1);
 }
+
+// test knobs: one tile shape for every F(4,3) / nested-Winograd / conv_fold4_kernel op it fits (same bits as any other, by construction)
+void force_shapes(film_t* h, Plan* R) {
+  const std::pair<ConvFamily, int> forced[] = {{FAM_W43, h->opt_w43_shape}, {FAM_W2D, h->opt_w2d_shape}, {FAM_FOLD4, h->opt_fold4_shape}};
+  for (const auto& [fam, shape] : forced) {
+    if (shape < 0) continue;
+    for (OpDesc& op : R->ops) {
+      if (op.kind != OP_CONV || op.family != fam) continue;
+      const std::vector<int> cands = conv_candidates(op);
+      const int want = conv_tile(fam, shape, true);
+      if (std::find(cands.begin(), cands.end(), want) != cands.end()) op.tile = want;
+    }
+  }
+}
+
+// One more orientation of the stream plan P over P's buffers: built and checked against P's layout, not yet tuned
+int add_orientation(film_t* h, Plan* P, int left, int right, bool extract, Plan** out) {
+  std::unique_ptr<Plan> Q(new Plan);
+  int rc = plan_build(h, Q.get(), P->B, P->H, P->W, P->tiles, P->slots, left, right, extract);
+  if (rc) return rc;
+  bool alike = Q->arena_floats == P->arena_floats && Q->bufs.size() == P->bufs.size() && Q->n_extract == (extract ? P->n_extract : 0);
+  for (size_t i = 0; alike && i < Q->bufs.size(); ++i) alike = Q->bufs[i].name == P->bufs[i].name && Q->bufs[i].off == P->bufs[i].off && Q->bufs[i].floats == P->bufs[i].floats;
+  if (!alike) return fail(h, FILM_ERR_INVALID, "planner: the orientations of a stream plan lay out different workspaces");
+  Q->id = P->id;
+  *out = Q.get();
+  P->others[Plan::orientation_key(left, right, extract)] = std::move(Q);
+  return FILM_OK;
+}
 }  // namespace
+
+int plan_orientation(film_t* h, Plan* P0, int left, int right, bool extract, Plan** out) {
+  if (P0->slots < 2) return fail(h, FILM_ERR_INVALID, "planner: not a stream plan");
+  if (P0->left == left && P0->slot == right && P0->extract == extract) { *out = P0; return FILM_OK; }
+  auto it = P0->others.find(Plan::orientation_key(left, right, extract));
+  if (it != P0->others.end()) { *out = it->second.get(); return FILM_OK; }
+  Plan* Q = nullptr;
+  int rc = add_orientation(h, P0, left, right, extract, &Q);
+  if (rc) return rc;
+  Q->arena = P0->arena;
+  // its conv shapes are the first orientation's, measured when the workspace was allocated: the choices are taken, nothing is timed - the
+  // workspace holds the carried frames of a running stream
+  if (Q->arena && h->opt_autotune && h->finalized && (rc = autotune_plan(h, Q, false))) return rc;
+  force_shapes(h, Q);
+  *out = Q;
+  return FILM_OK;
+}
 
 void drop_plans(film_t* h) {
   if (!h->plan_only) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); }   // (forwards may still be running on them)
   while (!h->plans.empty()) forget_plan(h, h->plans.size() - 1);
 }
 
-// Plans are cached per (B, H, W, tiles, stream): tiles = 0 for pair plans, > 0 for sequence plans (Plan::tiles), stream for the
-// stream plan of `tiles` tiles (Plan::slot >= 0: both orientations, one cache entry, one workspace) - the kinds never stand in
-// for each other.  All count toward the three device plans kept alive.
-int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles, bool stream) {
-  const auto same = [&](const Plan& p) { return p.B == B && p.H == H && p.W == W && p.tiles == tiles && (p.slot >= 0) == stream; };
+// Plans are cached per (B, H, W, tiles, slots): tiles = 0 for pair plans, > 0 for sequence plans (Plan::tiles), slots >= 2 for the
+// stream plan of `tiles` tiles over that many frame slots (Plan::slot >= 0: all its orientations, one cache entry, one workspace) -
+// the kinds never stand in for each other.  All count toward the three device plans kept alive.
+int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles, int slots) {
+  const bool stream = slots > 0;
+  const auto same = [&](const Plan& p) { return p.B == B && p.H == H && p.W == W && p.tiles == tiles && p.slots == slots; };
   const int div = 1 << (h->cfg.pyramid_levels - 1);
   if (B < 1 || H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
   if (H % div || W % div)
@@ -61,23 +108,25 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
   if ((H >> wl) < 2 || (W >> wl) < 2)
     return fail(h, FILM_ERR_INVALID, "input %d x %d too small: warped pyramid level %d would be smaller than 2x2", H, W, wl);
   if ((int64_t)2 * B * H * W >= (int64_t)1 << 31) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
+  if ((int64_t)slots * B * H * W >= (int64_t)1 << 31) return fail(h, FILM_ERR_INVALID, "batch too large (slots*B*H*W must fit int32: \"stream_times\")");
   for (auto& p : h->plans)
     if (same(*p) && (!need_device || p->arena)) { *out = p.get(); p->last_use = ++h->tick; return FILM_OK; }
   if (need_device)   // a description-only plan of this shape (film_plan_json, max_units) is superseded, not kept beside the new one
     for (size_t i = 0; i < h->plans.size(); ++i)
       if (same(*h->plans[i])) { forget_plan(h, i); break; }
   std::unique_ptr<Plan> P(new Plan);
-  int rc = plan_build(h, P.get(), B, H, W, tiles, stream ? 0 : -1);
+  int rc = stream ? plan_build(h, P.get(), B, H, W, tiles, slots, 1, 0, true) : plan_build(h, P.get(), B, H, W, tiles);
   if (rc) return rc;
   P->id = ++h->plan_ids;
-  if (stream) {
-    P->twin.reset(new Plan);
-    Plan& Q = *P->twin;
-    if ((rc = plan_build(h, &Q, B, H, W, tiles, 1))) return rc;
-    bool alike = Q.arena_floats == P->arena_floats && Q.bufs.size() == P->bufs.size() && Q.n_extract == P->n_extract;
-    for (size_t i = 0; alike && i < Q.bufs.size(); ++i) alike = Q.bufs[i].name == P->bufs[i].name && Q.bufs[i].off == P->bufs[i].off && Q.bufs[i].floats == P->bufs[i].floats;
-    if (!alike) return fail(h, FILM_ERR_INVALID, "planner: the two orientations of a stream plan lay out different workspaces");
-    Q.id = P->id;
+  Plan* twin = nullptr;   // a stream plan: the orientation of the second push comes with it, the deeper ones on first use (plan_orientation)
+  if (stream && (rc = add_orientation(h, P.get(), 0, 1, true, &twin))) return rc;
+  if (need_device && slots > 2) {
+    // the slots of "stream_times" > 1 grow the per-image buffers beyond what max_units has budgeted for a pair of frames
+    const int64_t lim = limited_buffer_bytes(P.get()), bytes = P->arena_floats * (int64_t)sizeof(float);
+    if (lim > kMaxBufferBytes || bytes > arena_budget_bytes(h))
+      return fail(h, FILM_ERR_NOMEM, "stream_times = %d: the workspace of %d frame slots (%.1f MB, largest 32-bit addressed buffer %.1f MB) does not fit "
+                  "(64 GiB / 60 %% of the free HBM of workspace, 4 GiB per buffer) - use a smaller \"stream_times\" or a finer block_shape",
+                  slots - 1, slots, bytes * 1e-6, lim * 1e-6);
   }
   if (need_device) {
     // keep at most 3 device plans alive (workspaces are GBs at 1080p tiles)
@@ -105,31 +154,22 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
     }
     if (e != hipSuccess) {
       P->arena = nullptr;
+      if (slots > 2)
+        return fail(h, FILM_ERR_NOMEM, "workspace hipMalloc of %.1f MB (stream_times = %d: %d frame slots) failed: %s", P->arena_floats * 4e-6, slots - 1, slots,
+                    hipGetErrorString(e));
       return fail(h, FILM_ERR_NOMEM, "workspace hipMalloc of %.1f MB failed: %s", P->arena_floats * 4e-6, hipGetErrorString(e));
     }
     HIPCHK(h, hipMemsetAsync(P->arena, 0, (size_t)P->arena_floats * sizeof(float), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (P->twin) P->twin->arena = P->arena;
+    if (twin) twin->arena = P->arena;
     if (h->opt_autotune && h->finalized) {
       int trc = autotune_plan(h, P.get());
-      if (trc == FILM_OK && P->twin) trc = autotune_plan(h, P->twin.get());   // (its shapes are the first orientation's: nothing is measured again)
+      if (trc == FILM_OK && twin) trc = autotune_plan(h, twin);   // (its shapes are the first orientation's: nothing is measured again)
       if (trc) { free_plan(P.get()); return trc; }
     }
   }
-  // test knobs: one tile shape for every F(4,3) / nested-Winograd / conv_fold4_kernel op it fits (same bits as any other, by construction)
-  const std::pair<ConvFamily, int> forced[] = {{FAM_W43, h->opt_w43_shape}, {FAM_W2D, h->opt_w2d_shape}, {FAM_FOLD4, h->opt_fold4_shape}};
-  for (const auto& [fam, shape] : forced) {
-    if (shape < 0) continue;
-    for (Plan* R : {P.get(), P->twin.get()}) {
-      if (!R) continue;
-      for (OpDesc& op : R->ops) {
-        if (op.kind != OP_CONV || op.family != fam) continue;
-        const std::vector<int> cands = conv_candidates(op);
-        const int want = conv_tile(fam, shape, true);
-        if (std::find(cands.begin(), cands.end(), want) != cands.end()) op.tile = want;
-      }
-    }
-  }
+  force_shapes(h, P.get());
+  if (twin) force_shapes(h, twin);
   P->last_use = ++h->tick;
   *out = P.get();
   h->plans.push_back(std::move(P));

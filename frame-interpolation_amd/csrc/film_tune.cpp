@@ -101,10 +101,10 @@ std::vector<int> conv_candidates(const OpDesc& op) { return kConvFamily[op.famil
 // Measure, don't guess: every distinct conv shape of a plan is timed once with each tile shape that fits
 // its Cout (random activations, the real weights) and keeps the fastest.  The choice cannot change the
 // results: every output element is the same k-ordered fma chain whatever the tile.
-int autotune_plan(film_t* h, Plan* P) {
+int autotune_plan(film_t* h, Plan* P, bool measure) {
   bool need = false;
   for (const OpDesc& op : P->ops) {
-    if (op.kind != OP_CONV) continue;
+    if (op.kind != OP_CONV || !measure) continue;
     const std::string sig = conv_signature(op);
     if (h->tune_cache.count(sig)) continue;
     auto it = h->tune_import.find(sig);
@@ -185,8 +185,11 @@ int autotune_plan(film_t* h, Plan* P) {
     HIPCHK(h, hipMemsetAsync(P->arena, 0, (size_t)P->arena_floats * sizeof(float), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
-  for (OpDesc& op : P->ops)
-    if (op.kind == OP_CONV) op.tile = h->tune_cache.at(conv_signature(op));
+  for (OpDesc& op : P->ops) {
+    if (op.kind != OP_CONV) continue;
+    const auto it = h->tune_cache.find(conv_signature(op));
+    if (it != h->tune_cache.end()) op.tile = it->second;   // (always there behind a measuring call; else the planner's default tile stays)
+  }
   return FILM_OK;
 }
 

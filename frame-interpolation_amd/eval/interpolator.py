@@ -172,7 +172,8 @@ class Interpolator:
     bs = self._block_shape if self._block_shape is not None and np.prod(self._block_shape) > 1 else None
     return self._engine.interpolate_sequence(frames, align=self._align, block_shape=bs)
 
-  def open_stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False, scene_cut: int = 0):
+  def open_stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False, scene_cut: int = 0,
+                  times: int = 1):
     """(extension) A frame stream of h x w frames (film_hip.engine.FilmStream; film_stream_*): push() one frame at a time and get
     the mid-frame between it and the one pushed before, bit-identical to self(previous, frame, dt) with align, block_shape and
     block_overlap as set, with one feature extraction per frame.  pix 'f32': float32 frames, not clipped; 'u8': uint8 frames in
@@ -180,12 +181,14 @@ class Interpolator:
     `matrix` ('bt709' | 'bt601') and limited or full range; 'i010' / 'p010': the same with 10-bit samples, uint16 [h * 3 // 2, w].  scene_cut (0 .. 1000 permille): non-zero sets the engine option "scene_cut"
     (include/film_hip.h) before the stream opens - a push that the histogram rule calls a scene cut then returns None like a first push,
     FilmStream.cut_info() tells why; an engine option like block_overlap, so it stays set; 0 (default) leaves the engine as it is.
+    times (1 .. 6): a primed push returns the [2^times - 1, ...] frames of the times_to_interpolate recursion between the two frames, each
+    bit-identical to self() on its float32 parents (engine option "stream_times", set for this stream only).
     One stream per Interpolator at a time."""
     if self._align is not None:
       assert self._align > 0, 'align must be a positive number.'
     bs = self._block_shape if self._block_shape is not None and np.prod(self._block_shape) > 1 else None
     return self._engine.open_stream(h, w, align=self._align, block_shape=bs, pix=pix, matrix=matrix, full_range=full_range,
-                                    scene_cut=scene_cut)
+                                    scene_cut=scene_cut, times=times)
 
   def __call__(self, x0: np.ndarray, x1: np.ndarray,
                dt: np.ndarray) -> np.ndarray:

@@ -74,7 +74,8 @@ EXPORTED_SYMBOLS = (
     'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json',
     'film_debug_arena', 'film_debug_run_op', 'film_debug_tile_map',
     'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json',
-    'film_to_yuv420', 'film_debug_yuv_cut', 'film_frame_histogram', 'film_stream_cut_info')
+    'film_to_yuv420', 'film_debug_yuv_cut', 'film_frame_histogram', 'film_stream_cut_info',
+    'film_stream_pair_plan_json', 'film_stream_schedule_json')
 
 _lib = None
 
@@ -151,6 +152,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_stream_close.argtypes = [vp]
     lib.film_stream_plan_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_frame_histogram.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+    lib.film_stream_pair_plan_json.argtypes = [vp] + [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_int64, i64p]
+    lib.film_stream_schedule_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_stream_cut_info.argtypes = [vp, i64p, i64p, ctypes.POINTER(ctypes.c_int)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
@@ -210,12 +213,17 @@ class FilmStream:
     frames ('i010': the code in bits 0-9, = yuv420p10le; 'p010': the code in bits 6-15) as uint16 [H * 3 // 2, W] with the same planes.
     With the engine option "scene_cut" > 0 (FilmEngine.open_stream(scene_cut=...)) a push that the histogram rule calls a scene cut returns
     None / False like a first push, and cut_info() tells the two apart.
+    times = T > 1 (FilmEngine.open_stream(times=...); engine option "stream_times", read when the stream opens): a primed push returns
+    the 2^T - 1 frames of the reference's times_to_interpolate = T recursion between the two frames, [2^T - 1, *shape] in temporal
+    order - every one bit-identical to interpolate_frames on its float32 parents, quantised (if at all) only on the way out.
     One stream per engine at a time; use it as a context manager or close() it."""
 
     def __init__(self, engine: 'FilmEngine', h: int, w: int, align: Optional[int], block_shape, pix: str, matrix: str = 'bt709',
-                 full_range: bool = False):
+                 full_range: bool = False, times: int = 1):
         self._code = pix_code(pix, matrix, full_range)
         self._eng = engine
+        self.times = int(times)                  # what the engine option said when the stream was opened
+        self.per_push = (1 << self.times) - 1    # frames of a primed push
         self.shape = (int(h) * 3 // 2, int(w)) if pix in YUV420 else (int(h), int(w), 3)
         self.pix = pix
         self.dtype = PIX[pix][1]
@@ -226,30 +234,34 @@ class FilmStream:
     def push(self, frame: np.ndarray, out: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
         """frame: host array of the stream's shape and dtype.  None for the first frame after open / reset, else the mid-frame
         (a new array, or `out`: a writable C-contiguous array of the frame's shape and dtype).  None too for a frame that option
-        "scene_cut" found to start a new scene (`out` is then left as it was)."""
+        "scene_cut" found to start a new scene (`out` is then left as it was).  times > 1: the result and `out` are
+        [2^times - 1, *frame shape] - a float32 caller does well to reuse one `out`: at 1080p with times = 2 a push into the fresh
+        75 MB array measured 3 ms per frame slower than into a reused one (profiles/stream_recursion_bench.log)."""
         a = np.asarray(frame)
         if a.dtype != self.dtype or a.shape != self.shape:
             raise ValueError(f'expected a {np.dtype(self.dtype).name} array of shape {self.shape}, got {a.dtype} {a.shape}')
         a = np.ascontiguousarray(a)
+        oshape = self.shape if self.times == 1 else (self.per_push,) + self.shape
         if out is None:
-            out = np.empty(self.shape, self.dtype)
-        elif out.dtype != self.dtype or out.shape != self.shape or not out.flags['C_CONTIGUOUS'] or not out.flags['WRITEABLE']:
-            raise ValueError(f'out must be a writable C-contiguous {np.dtype(self.dtype).name} array of shape {self.shape}')
+            out = np.empty(oshape, self.dtype)
+        elif out.dtype != self.dtype or out.shape != oshape or not out.flags['C_CONTIGUOUS'] or not out.flags['WRITEABLE']:
+            raise ValueError(f'out must be a writable C-contiguous {np.dtype(self.dtype).name} array of shape {oshape}')
         produced = ctypes.c_int(0)
         eng = self._eng
         eng._check(eng._lib.film_stream_push(eng._h, a.ctypes.data, out.ctypes.data, ctypes.byref(produced), FILM_MEM_HOST, None))
         eng.save_tune_cache()
         return out if produced.value else None
 
-    def push_device(self, ptr_in: int, ptr_out: int, stream: Optional[int] = None) -> bool:
-        """Device-resident push: raw device pointers to one frame of the stream's pixel type each, asynchronous on `stream`.
-        Returns whether ptr_out receives a mid-frame (False for the first frame after open / reset; ptr_out may then be 0 - and for a
-        scene cut found by option "scene_cut", which leaves ptr_out untouched)."""
+    def push_device(self, ptr_in: int, ptr_out: int, stream: Optional[int] = None):
+        """Device-resident push: raw device pointers to one frame of the stream's pixel type (ptr_out: to 2^times - 1 of them),
+        asynchronous on `stream`.  times == 1: returns whether ptr_out receives a mid-frame (False for the first frame after open /
+        reset; ptr_out may then be 0 - and for a scene cut found by option "scene_cut", which leaves ptr_out untouched).
+        times > 1: returns the number of frames written, 2^times - 1 or 0."""
         produced = ctypes.c_int(0)
         eng = self._eng
         eng._check(eng._lib.film_stream_push(eng._h, ctypes.c_void_p(ptr_in), ctypes.c_void_p(ptr_out) if ptr_out else None,
                                              ctypes.byref(produced), FILM_MEM_DEVICE, ctypes.c_void_p(stream) if stream else None))
-        return bool(produced.value)
+        return bool(produced.value) if self.times == 1 else produced.value
 
     def reset(self) -> None:
         """Forgets the carried frame (scene cut, seek): the next push produces nothing."""
@@ -506,16 +518,26 @@ class FilmEngine:
                                                         ctypes.c_void_p(stream) if stream else None))
 
     def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32', matrix: str = 'bt709',
-                    full_range: bool = False, scene_cut: int = 0) -> FilmStream:
+                    full_range: bool = False, scene_cut: int = 0, times: int = 1) -> FilmStream:
         """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix 'f32' | 'u8' |
         'i420' | 'nv12' | 'i010' | 'p010', the latter four (8-bit and 10-bit 4:2:0, h and w even) with the colour `matrix` 'bt709' | 'bt601' and
         limited or full range.
         scene_cut: 0 .. 1000 permille; non-zero sets the engine option "scene_cut" (include/film_hip.h) before the stream opens - a handle
         option like block_overlap, so it STAYS set for later streams of this engine until set_option('scene_cut', 0); 0 (default) leaves
-        the engine as it is."""
+        the engine as it is.
+        times: 1 .. 6 = the engine option "stream_times" for THIS stream (set, the stream opened, the option set back to what it was): a
+        primed push returns the 2^times - 1 frames of the times_to_interpolate recursion (FilmStream)."""
         if scene_cut:
             self.set_option('scene_cut', int(scene_cut))
-        return FilmStream(self, h, w, align, block_shape, pix, matrix, full_range)
+        times = int(times)
+        before = getattr(self, '_stream_times', 1)   # (option "stream_times" as last set through set_option)
+        if times == before:
+            return FilmStream(self, h, w, align, block_shape, pix, matrix, full_range, times)
+        self.set_option('stream_times', times)
+        try:
+            return FilmStream(self, h, w, align, block_shape, pix, matrix, full_range, times)
+        finally:
+            self.set_option('stream_times', before)
 
     def frame_histogram_device(self, ptr: int, h: int, w: int, hist_ptr: int, pix: str = 'u8', matrix: str = 'bt709', full_range: bool = False,
                                stream: Optional[int] = None) -> None:
@@ -578,6 +600,8 @@ class FilmEngine:
 
     def set_option(self, key: str, value: int) -> None:
         self._check(self._lib.film_set_option(self._h, key.encode(), int(value)))
+        if key == 'stream_times':
+            self._stream_times = int(value)
         if key in ('block_overlap_h', 'block_overlap_w'):
             self._block_overlap = tuple(int(value) if key == k else o
                                         for k, o in zip(('block_overlap_h', 'block_overlap_w'), self.block_overlap))
@@ -612,6 +636,15 @@ class FilmEngine:
     def stream_plan(self, tiles: int, h: int, w: int, slot: int) -> dict:
         """film_stream_plan_json: the plan a stream of `tiles` h x w tiles runs when the pushed frame fills half `slot` (0 / 1)."""
         return self._json_call(self._lib.film_stream_plan_json, int(tiles), int(h), int(w), int(slot))
+
+    def stream_pair_plan(self, tiles: int, h: int, w: int, times: int, left: int, right: int, extract: bool = True) -> dict:
+        """film_stream_pair_plan_json: the plan of one pair run (frame in slot `left`, frame in slot `right`, with or without the right
+        frame's extraction) of a stream of `tiles` h x w tiles opened with times (times + 1 frame slots)."""
+        return self._json_call(self._lib.film_stream_pair_plan_json, int(tiles), int(h), int(w), int(times), int(left), int(right), int(bool(extract)))
+
+    def stream_schedule(self, times: int, slot: int) -> dict:
+        """film_stream_schedule_json: the pair runs of one primed push whose input lands in slot 0 / 1, in execution order."""
+        return self._json_call(self._lib.film_stream_schedule_json, int(times), int(slot))
 
     def tiling(self, h: int, w: int, align: Optional[int] = None, block_shape=None) -> dict:
         """film_tiling_json: the tile geometry of an h x w frame with the engine's current block_overlap options (resolved overlap,

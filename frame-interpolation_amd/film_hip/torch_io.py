@@ -81,20 +81,22 @@ class DeviceStream:
     """A frame stream on frames that already live in HBM (DeviceInterpolator.stream): push(frame) takes a [H,W,3] CUDA tensor, float32
     or uint8 as opened (a 4:2:0 stream: uint8 [H * 3 // 2, W]; a 10-bit one: int16 or uint16 of that shape), and returns the mid-frame between it and the frame pushed before as a new tensor of the same kind - None for
     the first frame after opening or reset(), and for a frame that the engine option "scene_cut" found to start a new scene.  Asynchronous on the
-    current torch stream (with "scene_cut" > 0 a push waits for the frame's histogram: include/film_hip.h)."""
+    current torch stream (with "scene_cut" > 0 a push waits for the frame's histogram: include/film_hip.h).
+    times > 1: a primed push returns the [2^times - 1, *frame shape] frames of the times_to_interpolate recursion (FilmStream)."""
 
     def __init__(self, engine: FilmEngine, h: int, w: int, align, block_shape, pix: str, matrix: str = 'bt709', full_range: bool = False,
-                 scene_cut: int = 0):
+                 scene_cut: int = 0, times: int = 1):
         self._stream = engine.open_stream(h, w, align=align, block_shape=block_shape, pix=pix, matrix=matrix, full_range=full_range,
-                                          scene_cut=scene_cut)
+                                          scene_cut=scene_cut, times=times)
         self._dtypes = pix_dtypes(pix)
 
     def push(self, frame: torch.Tensor) -> Optional[torch.Tensor]:
         assert frame.is_cuda and frame.dtype in self._dtypes and tuple(frame.shape) == self._stream.shape
         frame = frame.contiguous()
-        out = torch.empty_like(frame)
+        st = self._stream
+        out = torch.empty_like(frame) if st.times == 1 else torch.empty((st.per_push,) + tuple(frame.shape), dtype=frame.dtype, device=frame.device)
         stream = torch.cuda.current_stream(frame.device).cuda_stream
-        return out if self._stream.push_device(frame.data_ptr(), out.data_ptr(), stream) else None
+        return out if st.push_device(frame.data_ptr(), out.data_ptr(), stream) else None
 
     def reset(self) -> None:
         self._stream.reset()
@@ -161,16 +163,18 @@ class DeviceInterpolator:
                                                  block_shape=bs if bs is not None and bs[0] * bs[1] > 1 else None, stream=stream)
         return out
 
-    def stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False, scene_cut: int = 0) -> DeviceStream:
+    def stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False, scene_cut: int = 0,
+               times: int = 1) -> DeviceStream:
         """Extension: a frame stream of h x w frames (film_stream_*), padded / tiled like batch(): push one CUDA tensor at a time, float32
         or ('u8') uint8, and get the mid-frame with the frame before - bit-identical to batch(previous, frame), one extraction per frame.
         'i420' / 'nv12': 8-bit 4:2:0 frames as uint8 [h * 3 // 2, w] tensors, converted inside the cut and the quantisation.
         'i010' / 'p010': 10-bit 4:2:0 frames as 16-bit tensors of that shape - torch.int16 (taken as a bit pattern) or torch.uint16 where
         the installed torch has it; the mid-frame comes back in the dtype that was pushed.
-        scene_cut (0 .. 1000 permille): non-zero sets the ENGINE option "scene_cut" before the stream opens, and it stays set (like block_overlap)."""
+        scene_cut (0 .. 1000 permille): non-zero sets the ENGINE option "scene_cut" before the stream opens, and it stays set (like block_overlap).
+        times (1 .. 6): the stream's "stream_times" - a primed push returns [2^times - 1, ...] frames, the times_to_interpolate recursion."""
         bs = self._block_shape
         return DeviceStream(self._engine, h, w, self._align, bs if bs is not None and bs[0] * bs[1] > 1 else None, pix, matrix, full_range,
-                            scene_cut)
+                            scene_cut, times)
 
     def __call__(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         if self._block_shape is not None and self._block_shape[0] * self._block_shape[1] > 1:

@@ -57,15 +57,23 @@ def _read_line(f: BinaryIO) -> bytes:
     raise Y4MError(f'a line of more than {_MAX_LINE} bytes: not a YUV4MPEG2 stream')
 
 
-def double_rate(tokens: Sequence[str]) -> List[str]:
-    """The header tokens with the numerator of the F token doubled (twice the frames in the same time); everything else as it is."""
+def multiply_rate(tokens: Sequence[str], k: int) -> List[str]:
+    """The header tokens with the numerator of the F token multiplied by the integer k >= 1 (k times the frames in the same time);
+    everything else as it is."""
+    if int(k) != k or k < 1:
+        raise ValueError(f'the frame rate is multiplied by a positive integer, got {k!r}')
     out = []
     for t in tokens:
         if t[:1] == 'F' and ':' in t:
             num, den = t[1:].split(':', 1)
-            t = f'F{int(num) * 2}:{den}'
+            t = f'F{int(num) * int(k)}:{den}'
         out.append(t)
     return out
+
+
+def double_rate(tokens: Sequence[str]) -> List[str]:
+    """The header tokens with the numerator of the F token doubled (twice the frames in the same time); everything else as it is."""
+    return multiply_rate(tokens, 2)
 
 
 def parse_header(line: bytes, depths: Sequence[int] = (8,)) -> Tuple[int, int, List[str]]:

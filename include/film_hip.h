@@ -183,7 +183,35 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                      the pushed frame fills; pushes alternate) as film_plan_json text with "kind":"stream", "tiles", "slot",
  *                      "n_extract": B = tiles, img0 / the feature buffers hold 2 * tiles images, ops [0, n_extract) are the pushed
  *                      frame's image pyramid and extractor (all a first push runs), the rest is the sequence plan of one pair with the
- *                      earlier frame at image (1 - slot) * tiles.  Both orientations list the same buffers.  Works on plan-only handles. */
+ *                      earlier frame at image (1 - slot) * tiles.  Both orientations list the same buffers.  Works on plan-only handles.
+ *                      Always the two-slot plan of "stream_times" = 1, whatever the option says.
+ * Recursive mid-frames (option "stream_times" = T, 1 .. 6, default 1; read by film_stream_open and fixed for that stream's life).  With T > 1
+ * a primed film_stream_push writes the 2^T - 1 frames of the reference's times_to_interpolate = T recursion (eval/util.py,
+ * _recursive_generator) between the previous frame and the pushed one to `mid`: contiguous frames of the stream's pixel type in temporal
+ * order, `mid` holding (2^T - 1) frames, *produced = 2^T - 1.  A first push, a push after film_stream_reset and a scene-cut push write
+ * nothing and set *produced = 0, as with T = 1; a NULL `mid` on a primed push is FILM_ERR_INVALID and unprimes the stream.
+ *   Definition.  With the previous frame at position 0 and the pushed one at 2^T, the frame at position (2 j + 1) 2^(T - d), d = 1 .. T, is
+ *     film_interpolate of the frames at positions (2 j) 2^(T - d) and (2 j + 2) 2^(T - d) - its two depth-(d - 1) neighbours - as FLOAT32
+ *     frames: a mid-frame that is fed back is never quantised on the way.  A FILM_PIX_F32 stream returns these floats, a FILM_PIX_U8 stream
+ *     film_to_uint8 of them, a 4:2:0 stream film_to_yuv420 of them; the inputs are dequantised once, by the cut.  Every output is therefore
+ *     bit-identical to pairwise film_interpolate calls on its float32 parents under the handle's current options.
+ *   Cost.  Per primed push 2^T - 1 pair runs (flow estimator + fusion) and 2^(T - 1) feature extractions: the pushed frame's and one per
+ *     fed-back mid-frame; the deepest mids are never extracted and no frame is extracted twice.  The runs go one after the other, one pair
+ *     each (no breadth-first batching).  The stream plan holds T + 1 frame slots in its per-image buffers; if that workspace does not fit,
+ *     film_stream_open returns FILM_ERR_NOMEM with "stream_times" in the message.  FILM_MEM_HOST: every frame is downloaded as soon as it
+ *     is quantised, the call waits once at the end.
+ *   film_stream_pair_plan_json  the plan of ONE pair run of a "stream_times" = `times` stream plan of `tiles` (padded) H x W tiles: image 0
+ *                      is the frame in slot `left`, image 1 the one in slot `right` (slots 0 .. times: 0 and 1 take turns for the input
+ *                      frames, slot 1 + d holds the depth-d mid-frame), and with extract != 0 the right frame's image pyramid and
+ *                      extractor run first (ops [0, n_extract)), else "n_extract" is 0 and the plan holds no such op.  film_plan_json
+ *                      text with "kind":"stream", "tiles", "slots" (= times + 1), "left", "right", "n_extract"; every orientation lists
+ *                      the same buffers, whose per-image ones hold slots * tiles images.  times = 1, left = 1 - s, right = s, extract = 1
+ *                      has the ops and buffers of film_stream_plan_json(slot = s).  FILM_ERR_INVALID: times outside 1 .. 6, left == right,
+ *                      a slot outside 0 .. times.  Works on plan-only handles.
+ *   film_stream_schedule_json  the pair runs of one primed push whose input frame lands in `slot` (0 / 1), in execution order:
+ *                      {"times", "slot", "slots", "produced", "steps":[{"left", "right", "extract", "index", "depth", "feed"}, ...]} - the
+ *                      step yields frame `index` (1 .. 2^T - 1) of `mid`, a depth-`depth` mid-frame, from the orientation (left, right,
+ *                      extract), and cuts it into slot `feed` for its children (-1: it has none).  Works on plan-only handles. */
 #define FILM_PIX_F32 0   /* frames and results float32 [H,W,3], as everywhere else */
 #define FILM_PIX_U8  1   /* frames and results uint8 [H,W,3]: x = u8 / 255.0f (IEEE, = read_image), result = film_to_uint8's rule */
 /* 8-bit Y'CbCr 4:2:0 frames: the conversion in is fused into the tile cut, the conversion out into the quantisation, so such a frame
@@ -264,6 +292,9 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
 int film_stream_reset(film_t* h);
 int film_stream_close(film_t* h);
 int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* buf, int64_t capacity, int64_t* needed);
+int film_stream_pair_plan_json(film_t* h, int tiles, int H, int W, int times, int left, int right, int extract, char* buf, int64_t capacity,
+                               int64_t* needed);
+int film_stream_schedule_json(film_t* h, int times, int slot, char* buf, int64_t capacity, int64_t* needed);
 
 /* Execution options.  Keys:
  *   "autotune" 0/1 time every distinct conv shape of a new plan with each fitting tile shape and keep
@@ -360,6 +391,10 @@ int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* bu
  *                  normalised in float32, w_i(y) = a_i(y) / sum_i a_i(y).  A pixel = sum over the covering tiles (i, j) in
  *                  row-major order of (wy_i * wx_j) * value, float32, one rounding per operation, no fused multiply-add;
  *                  independent of how the tiles are chunked.  Does not drop the cached plans (their key carries the tile size).
+ *   "stream_times" T  (extension; 1 .. 6, default 1 = today's streams: the same plan, device calls, workspace and bits)  read by
+ *                  film_stream_open and fixed for that stream's life - a later change affects the next open only.  T > 1: a primed
+ *                  film_stream_push writes 2^T - 1 frames ("Recursive mid-frames" above).  Does not drop the cached plans (their key
+ *                  carries the slot count).
  *   "scene_cut" k  (extension; 0 .. 1000 permille, default 0 = off, today's pushes: no launch, copy, allocation or wait is added)  read at
  *                  every film_stream_push, like "block_overlap_*".  k > 0: after the frame has reached the stream's own copy the push
  *                  takes its histogram there (film_frame_histogram's kernel), downloads the 3 KB and WAITS for them - so also a

@@ -20,6 +20,11 @@ copies of one picture: D = 0 for RGB, a fraction of a percent of 2 S for 4:2:0, 
 alternating a frame and its halved codes: extraction only); `*_first` - a first push (reset() + push, scene_cut = 0), what a cut should cost;
 and `hist <layout> <size> <data>` - frame_histogram_kernel alone (film_frame_histogram, hip events around 50 calls, microseconds per call)
 at 1080p and 4K on random bytes and on a constant frame, beside the frame's bytes over the measured HBM copy rate (6.29 TB/s).
+--times T[,T..] is a run of its own about recursive streams (engine option "stream_times"): at 1080p 2x2, for `f32` and `i420`, device-resident
+and host pushes, the milliseconds PER GENERATED FRAME of a steady push of a stream opened with times = T (2^T - 1 frames per push) beside
+this tree's times = 1 push, beside film_hip.recursive.interpolate_pair_recursively on the same pair (float32, device-resident: 2^T - 1 pair
+calls, every fed-back frame extracted twice) and - with --baseline-root - beside the baseline's times = 1 push; the frames of the f32 push are
+compared bit for bit with that recursion in the worker.  It also lists the stream plan's workspace for T = 1, 2, 3 and 6.
 Every measurement: untimed warm-up calls (plan build, autotune, first launches), then --reps timed windows of `n` calls, each
 ended by a device synchronise; the window's ms per call is one sample.  Each tree keeps its autotune choices in a file of its own
 under --scratch, so that the rounds of a tree run the same tiles.  The report gives mean and range over all samples of a
@@ -155,6 +160,79 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
     print('STREAM_BENCH ' + json.dumps(out), flush=True)
 
 
+def times_worker(root, reps, times_list):
+    """--times: the rows of the recursive streams at the first point (see the module text); prints one JSON line."""
+    for p in (root, os.path.join(root, 'frame-interpolation_amd')):
+        sys.path.insert(0, p)
+    import numpy as np
+    import torch
+    from film_hip import weights as W
+    from film_hip import recursive
+    from film_hip.engine import FilmEngine
+    from film_hip.options import PUBLISHED
+    from film_hip.torch_io import DeviceInterpolator
+    eng = FilmEngine(PUBLISHED, device=0)
+    eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
+    name, h, w, align, block, n, _ = POINTS[0]
+    res = {}
+    out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {name: res}}
+
+    def timed(call, calls, per_call, warm=2):
+        for _ in range(warm):
+            call()
+        torch.cuda.synchronize()
+        samples = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                call()
+            torch.cuda.synchronize()
+            samples.append((time.perf_counter() - t0) * 1e3 / (calls * per_call))
+        return [round(s, 4) for s in samples]
+
+    til = eng.tiling(h, w, align=align, block_shape=block)
+    tiles = block[0] * block[1]
+    res['workspace_bytes'] = {str(t): 4 * eng.stream_pair_plan(tiles, til['padded_h'], til['padded_w'], t, 1, 0, True)['arena_floats'] for t in (1, 2, 3, 6)}
+    it = DeviceInterpolator(eng, align=align, block_shape=list(block))
+    fr = _frames(4, h, w)
+    x = [torch.from_numpy(f).cuda() for f in fr]
+    y = [torch.empty((h * 3 // 2, w), dtype=torch.uint8, device='cuda') for _ in x]
+    for src, dst in zip(x, y):
+        eng.to_yuv420_device(src.data_ptr(), dst.data_ptr(), h, w, 'i420')
+    torch.cuda.synchronize()
+    host = {'f32': list(fr), 'i420': [t.cpu().numpy() for t in y]}
+    dev = {'f32': x, 'i420': y}
+    state = {'i': 0}
+
+    def nxt(m):
+        state['i'] = (state['i'] + 1) % m
+        return state['i']
+
+    res['identical'] = True
+    for t in [1] + [v for v in times_list if v != 1]:
+        per = (1 << t) - 1
+        calls = max(3, n // per)
+        for pix in ('f32', 'i420'):
+            with it.stream(h, w, pix, times=t) as st:
+                st.push(dev[pix][0])
+                if pix == 'f32' and t > 1:
+                    got = st.push(x[1])
+                    ref = recursive.interpolate_pair_recursively(x[0], x[1], t, it)[1:-1]
+                    res['identical'] = res['identical'] and bool(torch.equal(got, ref))
+                res[f'push_{pix}_t{t}'] = timed(lambda: st.push(dev[pix][nxt(4)]), calls, per)
+            with eng.open_stream(h, w, align=align, block_shape=block, pix=pix, times=t) as st:
+                st.push(host[pix][0])
+                res[f'host_push_{pix}_t{t}'] = timed(lambda: st.push(host[pix][nxt(4)]), max(3, calls // 3), per)
+        if t > 1:
+            def rec():
+                i = nxt(3)
+                return recursive.interpolate_pair_recursively(x[i], x[i + 1], t, it)
+            res[f'recursive_pair_t{t}'] = timed(rec, calls, per)
+    eng.save_tune_cache()
+    eng.close()
+    print('STREAM_BENCH ' + json.dumps(out), flush=True)
+
+
 def scene_rows(eng, it, timed, nxt, h, w, align, block, n, x8, i420):
     """The --scene_cut rows of one point: see the module text.  x8 / i420: the bench frames as CUDA tensors."""
     res = {}
@@ -237,10 +315,11 @@ def histogram_alone(calls=50, reps=3):
     return out
 
 
-def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False):
+def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False, times=None):
     env = dict(os.environ, FILM_TUNE_CACHE=tune_file)
     cmd = [sys.executable, os.path.abspath(__file__), '--worker', root, '--reps', str(reps)] + (['--quick'] if quick else [])
     cmd += (['--rows', ','.join(rows)] if rows else []) + (['--points', ','.join(points)] if points else []) + (['--scene_cut'] if scene_cut else [])
+    cmd += ['--times', ','.join(str(t) for t in times)] if times else []
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)   # (a hung worker ends the run: nothing is started behind it)
     for line in p.stdout.splitlines():
         if line.startswith('STREAM_BENCH '):
@@ -250,6 +329,48 @@ def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=
 
 def _stat(v):
     return f'{statistics.mean(v):8.3f} [{min(v):8.3f} .. {max(v):8.3f}]'
+
+
+def times_main(args, times):
+    """--times: rounds of (baseline's times = 1 pushes,) this tree's rows; the report in ms per generated frame."""
+    os.makedirs(args.scratch, exist_ok=True)
+    name = POINTS[0][0]
+    t1_rows = ['push_f32', 'push_i420', 'host_push_f32', 'host_push_i420']
+    base, this = [], []
+    for r in range(args.rounds):
+        if args.baseline_root:
+            base.append(_run_worker(os.path.abspath(args.baseline_root), args.reps, False, os.path.join(args.scratch, 'stream_bench_tune_baseline.txt'),
+                                    t1_rows, [name]))
+            print(f'# round {r + 1}/{args.rounds} baseline: done', flush=True)
+        this.append(_run_worker(HERE, args.reps, False, os.path.join(args.scratch, 'stream_bench_tune_this.txt'), times=times))
+        print(f'# round {r + 1}/{args.rounds} this: done', flush=True)
+    pts = [r['points'][name] for r in this]
+    lines = [f'# tools/stream_bench.py --times {",".join(map(str, times))}  this = {this[0]["version"]}' +
+             (f'  baseline = {base[0]["version"]}' if base else '') + f'  {this[0]["device"]}  rounds={args.rounds} reps={args.reps}',
+             '# ms per GENERATED FRAME (a times = T push generates 2^T - 1), device-resident unless "host": mean [min .. max] over rounds x reps windows',
+             f'{name}:']
+    for key in t1_rows:
+        if base:
+            lines.append(f'  {"baseline " + key:<26} {_stat([s for r in base for s in r["points"][name][key]])}')
+    for key in sorted(k for k in pts[0] if k not in ('identical', 'workspace_bytes')):
+        lines.append(f'  {key:<26} {_stat([s for p in pts for s in p[key]])}')
+    for pre in ('push_f32', 'push_i420', 'host_push_f32', 'host_push_i420'):
+        one = [statistics.mean(p[pre + '_t1']) for p in pts]
+        for t in times:
+            if t == 1:
+                continue
+            d = [statistics.mean(p[f'{pre}_t{t}']) - o for p, o in zip(pts, one)]
+            lines.append(f'  {f"{pre}_t{t} - {pre}_t1":<40} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms per frame'
+                         f'   (spread of {pre}_t1 over all windows: {max(s for p in pts for s in p[pre + "_t1"]) - min(s for p in pts for s in p[pre + "_t1"]):.3f} ms)')
+    lines.append(f'  times > 1 push_f32 == interpolate_pair_recursively, bit for bit: {all(p["identical"] for p in pts)}')
+    lines.append('  stream plan workspace, bytes: ' + '  '.join(f'T={t}: {b} ({b / 2**30:.2f} GiB)' for t, b in pts[0]['workspace_bytes'].items()))
+    lines.append('# raw: ' + json.dumps({'baseline': base, 'this': this}))
+    print('\n'.join(lines), flush=True)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    if not all(p['identical'] for p in pts):
+        raise SystemExit('a times > 1 push differs from the pairwise recursion')
 
 
 def main(argv=None):
@@ -263,10 +384,16 @@ def main(argv=None):
     ap.add_argument('--rows', default=None, help='comma-separated measurements to take (default: all), e.g. push_u8,push_i420,host_push_u8')
     ap.add_argument('--points', default=None, help='comma-separated points to run (default: all), e.g. "1080p 2x2"')
     ap.add_argument('--scene_cut', action='store_true', help='add the cost of option "scene_cut" and of its histogram kernel alone (see above)')
+    ap.add_argument('--times', default=None, help='comma-separated "stream_times" values, e.g. 2,3: the recursive-stream report instead (see above)')
     ap.add_argument('--worker', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     rows = args.rows.split(',') if args.rows else None
     points = args.points.split(',') if args.points else None
+    times = [int(t) for t in args.times.split(',')] if args.times else None
+    if times and args.worker:
+        return times_worker(args.worker, args.reps, times)
+    if times:
+        return times_main(args, times)
     if args.worker:
         return worker(args.worker, args.reps, args.quick, rows, points, args.scene_cut)
     os.makedirs(args.scratch, exist_ok=True)
