@@ -1,6 +1,7 @@
 // film_engine.cpp -- C-ABI (include/film_hip.h) of the MI355X FILM inference engine: handle lifetime, the option table, the JSON queries,
-// tiling, staging and chunking of film_forward / film_interpolate / film_interpolate_sequence, the host-buffer pipeline, the frame streams (film_stream_*), film_get_tap and the
-// debug entry points.  The executor lives in film_exec.cpp, the autotuner in film_tune.cpp, the plan cache in film_plans.cpp, the planner in
+// tiling, staging and chunking of film_forward / film_interpolate / film_interpolate_sequence, the host-buffer pipeline, film_get_tap and the
+// debug entry points, and the helpers the entry points of film_stream.cpp (the frame streams, film_stream_*) share with these (tile_geometry,
+// check_pix, need_device, pick_stream).  The executor lives in film_exec.cpp, the autotuner in film_tune.cpp, the plan cache in film_plans.cpp, the planner in
 // film_planner.cpp, the layer table and the weight packer in film_layers.cpp, the shared structures in film_internal.h.
 // There is no CPU execution path here: plan-only handles (device = -1) can pack weights and describe
 // plans, every compute entry point needs a HIP device.
@@ -30,66 +31,7 @@ int copy_out_string(film_t* h, const std::string& s, char* buf, int64_t cap, int
   return FILM_OK;
 }
 
-}  // namespace film_internal
-
-using namespace film_internal;
-
-namespace {
-
-// ---- options: one row per key of film_set_option (what each value means: include/film_hip.h; the measurements behind the defaults: beside the
-// opt_* fields in film_internal.h).  A value is range-checked, refused where it needs a kernel family this library does not hold, normalised and
-// stored; the plans carry the op list, the buffer layout, the lanes and the kernel and tile of every op, so a CHANGED value of an option that
-// decides any of those drops them.
-enum OptNorm { AS_IS, BOOL, NONNEG, LOW5 };   // stored: value | value != 0 | max(value, 0) | value & 31
-// a row reads: key, field, norm, drops_plans [, lo, hi, refusal [, family, need_lo, need_hi, family_refusal]]
-struct OptionRow {
-  const char* key;
-  int film_t::*field;   // nullptr: "pack_groups" stores nothing - it packs the weight layout groups 1..value of a finalized handle now
-  OptNorm norm;
-  bool drops_plans;
-  int64_t lo = 0, hi = 0;
-  const char* refusal = nullptr;          // of a value outside lo..hi (nullptr: every value is accepted)
-  ConvFamily family = FAM_BUF;
-  int need_lo = 0, need_hi = 0;
-  const char* family_refusal = nullptr;   // of a stored value in need_lo..need_hi when `family` is not built (nullptr: no such values; %d = the value)
-};
-constexpr OptionRow kOptions[] = {
-    {"graph", &film_t::opt_graph, AS_IS, false, 0, 2, "graph: 0 (one stream, eager), 1 (hipGraph replay) or 2 (two lanes, eager: the default)"},
-    {"profile", &film_t::opt_profile, BOOL, false},
-    {"autotune", &film_t::opt_autotune, BOOL, false},
-    {"max_batch", &film_t::opt_max_batch, NONNEG, false},
-    {"host_overlap", &film_t::opt_host_overlap, BOOL, false},
-    {"block_overlap_h", &film_t::opt_block_overlap_h, AS_IS, false, -1, 65535, "block_overlap_h: -1 (what the align padding of a tile holds) or 0 .. 65535 rows"},
-    {"block_overlap_w", &film_t::opt_block_overlap_w, AS_IS, false, -1, 65535, "block_overlap_w: -1 (what the align padding of a tile holds) or 0 .. 65535 columns"},
-    {"stream_times", &film_t::opt_stream_times, AS_IS, false, 1, 6, "stream_times: 1 .. 6 (a primed push of a stream opened with T writes 2^T - 1 frames)"},
-    {"scene_cut", &film_t::opt_scene_cut, AS_IS, false, 0, 1000, "scene_cut: 0 (off) or 1 .. 1000 permille of the histogram distance"},
-    {"tune_ms", &film_t::opt_tune_ms, NONNEG, false},
-    {"splitk", &film_t::opt_splitk, BOOL, true},
-    {"pack_groups", nullptr, AS_IS, false, 1, 4, "pack_groups: 1 .. 4"},
-    {"fuse", &film_t::opt_fuse, LOW5, true},
-    {"fold2x2", &film_t::opt_fold2x2, AS_IS, true, 0, 2, "fold2x2: 0, 1 or 2"},
-    {"planar", &film_t::opt_planar, BOOL, true},
-    {"winograd", &film_t::opt_wino, AS_IS, true, 0, 3, "winograd: 0, 1, 2 or 3", FAM_WINO, 2, 2,
-     "winograd = 2 (F(2,3) kernel on every level) needs a library built with FILM_EXTRA_FAMILIES=1"},
-    {"halo_all", &film_t::opt_halo_all, BOOL, true, 0, 0, nullptr, FAM_HALO, 1, 1, "halo_all needs a library built with FILM_EXTRA_FAMILIES=1"},
-    {"lanes", &film_t::opt_lanes, AS_IS, true, 0, 3, "lanes: 0, 1, 2 or 3"},
-    {"wino2d", &film_t::opt_wino2d, AS_IS, true, 0, 2, "wino2d: 0, 1 or 2"},
-    {"w2d_small_px", &film_t::opt_w2d_small_px, AS_IS, true, 0, 1 << 30, "w2d_small_px: pixels per image, 0 = never"},
-    {"w2d_min_px", &film_t::opt_w2d_min_px, AS_IS, true, 1, 1 << 30, "w2d_min_px: pixels per image"},
-    {"w2d_splitk", &film_t::opt_w2d_splitk, AS_IS, true, 0, 16, "w2d_splitk: 0 (off), 1 (default rule) or 2..16 (A/B: the cap on levels of <= 1024 pixels)"},
-    {"w2d_shape", &film_t::opt_w2d_shape, AS_IS, true, -1, W2D_SHAPES - 1, "w2d_shape: -1 (autotuned) or a Wino2dTile shape index"},
-    {"fold4_shape", &film_t::opt_fold4_shape, AS_IS, true, -1, F4_4x32, "fold4_shape: -1 (autotuned) or a Fold4Tile shape index"},
-    {"w43_shape", &film_t::opt_w43_shape, AS_IS, true, -1, 31, "w43_shape: -1 (autotuned) or a Wino43Tile shape index"},
-    {"precision", &film_t::opt_precision, AS_IS, true, 0, 2, "precision: 0 (f32), 1 (bf16x6) or 2 (bf16x3)", FAM_SPLIT6, 1, 2,
-     "precision %d (bf16 split modes) needs a library built with FILM_EXTRA_FAMILIES=1; this build runs fp32 MFMA only"},
-};
-constexpr bool option_rows_complete() {
-  for (const OptionRow& o : kOptions)
-    if ((o.lo < o.hi) != (o.refusal != nullptr) || ((o.family != FAM_BUF) != (o.family_refusal != nullptr))) return false;
-  return true;
-}
-static_assert(option_rows_complete(), "a row with a range (a family) carries its refusal message, a row without leaves lo = hi (family = FAM_BUF)");
-
+// ---- what the entry points here and in film_stream.cpp share
 // Geometry of a frame cut into block_h x block_w patches, each padded to a multiple of `align` (_pad_to_align, eval/interpolator.py:45-52).
 // The two refusals are the reference's asserts (eval/interpolator.py:84-89), same messages.  tp->B, src, dst and the tile range are the caller's.
 // Options "block_overlap_h" / "block_overlap_w" are resolved here, per axis of nb blocks of p pixels: one block has no overlap; -1 is
@@ -134,6 +76,79 @@ int check_pix(film_t* h, int pix, int H, int W) {
 // samples of one H x W frame of pixel type `pix` (S of "Scene cuts", include/film_hip.h), and its bytes
 int64_t frame_samples(int pix, int H, int W) { return pix_is_yuv(pix) ? (int64_t)H * W * 3 / 2 : (int64_t)H * W * 3; }
 size_t frame_bytes(int pix, int H, int W) { return (size_t)frame_samples(pix, H, W) * pix_sample_bytes(pix); }
+// The refusals the compute entry points share (`fn`: the entry point); where they stand among its other checks is the entry point's choice.
+int need_device(film_t* h, const char* fn) {
+  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: %s needs a HIP device (no CPU fallback)", fn);
+  if (!h->finalized) return fail(h, FILM_ERR_STATE, "film_finalize has not been called");
+  return FILM_OK;
+}
+hipStream_t pick_stream(film_t* h, int mem_kind, void* stream) {
+  // stream == NULL: host buffers -> the handle's own (non-blocking) stream, synchronised before returning;
+  // device buffers -> the NULL (legacy default) stream, i.e. ordered with the caller's default-stream work
+  // (torch's default stream IS the NULL stream, and its handle is 0).
+  return stream ? (hipStream_t)stream : (mem_kind == FILM_MEM_DEVICE ? (hipStream_t) nullptr : h->stream);
+}
+
+}  // namespace film_internal
+
+using namespace film_internal;
+
+namespace {
+
+// ---- options: one row per key of film_set_option (what each value means: include/film_hip.h; the measurements behind the defaults: beside the
+// opt_* fields in film_internal.h).  A value is range-checked, refused where it needs a kernel family this library does not hold, normalised and
+// stored; the plans carry the op list, the buffer layout, the lanes and the kernel and tile of every op, so a CHANGED value of an option that
+// decides any of those drops them.
+enum OptNorm { AS_IS, BOOL, NONNEG, LOW5 };   // stored: value | value != 0 | max(value, 0) | value & 31
+// a row reads: key, field, norm, drops_plans [, lo, hi, refusal [, family, need_lo, need_hi, family_refusal]]
+struct OptionRow {
+  const char* key;
+  int film_t::*field;   // nullptr: "pack_groups" stores nothing - it packs the weight layout groups 1..value of a finalized handle now
+  OptNorm norm;
+  bool drops_plans;
+  int64_t lo = 0, hi = 0;
+  const char* refusal = nullptr;          // of a value outside lo..hi (nullptr: every value is accepted)
+  ConvFamily family = FAM_BUF;
+  int need_lo = 0, need_hi = 0;
+  const char* family_refusal = nullptr;   // of a stored value in need_lo..need_hi when `family` is not built (nullptr: no such values; %d = the value)
+};
+constexpr OptionRow kOptions[] = {
+    {"graph", &film_t::opt_graph, AS_IS, false, 0, 2, "graph: 0 (one stream, eager), 1 (hipGraph replay) or 2 (two lanes, eager: the default)"},
+    {"profile", &film_t::opt_profile, BOOL, false},
+    {"autotune", &film_t::opt_autotune, BOOL, false},
+    {"max_batch", &film_t::opt_max_batch, NONNEG, false},
+    {"host_overlap", &film_t::opt_host_overlap, BOOL, false},
+    {"block_overlap_h", &film_t::opt_block_overlap_h, AS_IS, false, -1, 65535, "block_overlap_h: -1 (what the align padding of a tile holds) or 0 .. 65535 rows"},
+    {"block_overlap_w", &film_t::opt_block_overlap_w, AS_IS, false, -1, 65535, "block_overlap_w: -1 (what the align padding of a tile holds) or 0 .. 65535 columns"},
+    {"stream_times", &film_t::opt_stream_times, AS_IS, false, 1, kMaxStreamTimes, "stream_times: 1 .. 6 (a primed push of a stream opened with T writes 2^T - 1 frames)"},
+    {"scene_cut", &film_t::opt_scene_cut, AS_IS, false, 0, 1000, "scene_cut: 0 (off) or 1 .. 1000 permille of the histogram distance"},
+    {"tune_ms", &film_t::opt_tune_ms, NONNEG, false},
+    {"splitk", &film_t::opt_splitk, BOOL, true},
+    {"pack_groups", nullptr, AS_IS, false, 1, 4, "pack_groups: 1 .. 4"},
+    {"fuse", &film_t::opt_fuse, LOW5, true},
+    {"fold2x2", &film_t::opt_fold2x2, AS_IS, true, 0, 2, "fold2x2: 0, 1 or 2"},
+    {"planar", &film_t::opt_planar, BOOL, true},
+    {"winograd", &film_t::opt_wino, AS_IS, true, 0, 3, "winograd: 0, 1, 2 or 3", FAM_WINO, 2, 2,
+     "winograd = 2 (F(2,3) kernel on every level) needs a library built with FILM_EXTRA_FAMILIES=1"},
+    {"halo_all", &film_t::opt_halo_all, BOOL, true, 0, 0, nullptr, FAM_HALO, 1, 1, "halo_all needs a library built with FILM_EXTRA_FAMILIES=1"},
+    {"lanes", &film_t::opt_lanes, AS_IS, true, 0, 3, "lanes: 0, 1, 2 or 3"},
+    {"wino2d", &film_t::opt_wino2d, AS_IS, true, 0, 2, "wino2d: 0, 1 or 2"},
+    {"w2d_small_px", &film_t::opt_w2d_small_px, AS_IS, true, 0, 1 << 30, "w2d_small_px: pixels per image, 0 = never"},
+    {"w2d_min_px", &film_t::opt_w2d_min_px, AS_IS, true, 1, 1 << 30, "w2d_min_px: pixels per image"},
+    {"w2d_splitk", &film_t::opt_w2d_splitk, AS_IS, true, 0, 16, "w2d_splitk: 0 (off), 1 (default rule) or 2..16 (A/B: the cap on levels of <= 1024 pixels)"},
+    {"w2d_shape", &film_t::opt_w2d_shape, AS_IS, true, -1, W2D_SHAPES - 1, "w2d_shape: -1 (autotuned) or a Wino2dTile shape index"},
+    {"fold4_shape", &film_t::opt_fold4_shape, AS_IS, true, -1, F4_4x32, "fold4_shape: -1 (autotuned) or a Fold4Tile shape index"},
+    {"w43_shape", &film_t::opt_w43_shape, AS_IS, true, -1, 31, "w43_shape: -1 (autotuned) or a Wino43Tile shape index"},
+    {"precision", &film_t::opt_precision, AS_IS, true, 0, 2, "precision: 0 (f32), 1 (bf16x6) or 2 (bf16x3)", FAM_SPLIT6, 1, 2,
+     "precision %d (bf16 split modes) needs a library built with FILM_EXTRA_FAMILIES=1; this build runs fp32 MFMA only"},
+};
+constexpr bool option_rows_complete() {
+  for (const OptionRow& o : kOptions)
+    if ((o.lo < o.hi) != (o.refusal != nullptr) || ((o.family != FAM_BUF) != (o.family_refusal != nullptr))) return false;
+  return true;
+}
+static_assert(option_rows_complete(), "a row with a range (a family) carries its refusal message, a row without leaves lo = hi (family = FAM_BUF)");
+
 // The handle's staging buffer in HBM (whole frames of the FILM_MEM_HOST entry points), grown on demand.
 int ensure_stage(film_t* h, size_t bytes, hipStream_t s) {
   if (h->stage_bytes >= bytes) return FILM_OK;
@@ -165,12 +180,6 @@ void sequence_chunk(int n, int T, int cap, int* k, int* nt) {
   }
   *k = balanced_chunk(n, std::max(bk, 1));
   *nt = balanced_chunk(T, bt);
-}
-// The refusals the compute entry points share (`fn`: the entry point); where they stand among its other checks is the entry point's choice.
-int need_device(film_t* h, const char* fn) {
-  if (h->plan_only) return fail(h, FILM_ERR_NO_DEVICE, "plan-only handle: %s needs a HIP device (no CPU fallback)", fn);
-  if (!h->finalized) return fail(h, FILM_ERR_STATE, "film_finalize has not been called");
-  return FILM_OK;
 }
 // The retry rule of the chunk loops: a chunk of more than one unit whose workspace did not fit (FILM_ERR_NOMEM from get_plan: nothing was
 // launched) is halved, and the caller goes again from the same place.
@@ -227,13 +236,6 @@ int run_chunk(film_t* h, Plan* P, TileMapParams tp, const std::vector<Cut>& cuts
     HIPCHK(h, film_launch_join_tiles(tp, s));
   }
   return FILM_OK;
-}
-
-hipStream_t pick_stream(film_t* h, int mem_kind, void* stream) {
-  // stream == NULL: host buffers -> the handle's own (non-blocking) stream, synchronised before returning;
-  // device buffers -> the NULL (legacy default) stream, i.e. ordered with the caller's default-stream work
-  // (torch's default stream IS the NULL stream, and its handle is 0).
-  return stream ? (hipStream_t)stream : (mem_kind == FILM_MEM_DEVICE ? (hipStream_t) nullptr : h->stream);
 }
 
 int forward_chunk(film_t* h, const float* x0, const float* x1, int B, int H, int W, float* out, int mem_kind, void* stream) {
@@ -324,71 +326,6 @@ int interpolate_host_pipeline(film_t* h, Plan* P, TileMapParams tp, const float*
   }
   HIPCHK(h, hipStreamSynchronize(s));
   drain.armed = false;
-  return FILM_OK;
-}
-
-// ---- frame streams (film_stream_*; the contract: include/film_hip.h) ----
-// The stream's device buffers go back and it is closed.  Work that may still use them is the caller's to wait for.
-void stream_free(film_t* h) {
-  FilmStream& fs = h->fs;
-  for (void* p : {fs.keep, (void*)fs.result, (void*)fs.result8, (void*)fs.hist_dev})
-    if (p) (void)hipFree(p);
-  if (fs.hist_pin) (void)hipHostFree(fs.hist_pin);
-  fs = FilmStream{};
-}
-// what of a TileMapParams tile_geometry decides: the same values cut the same tiles
-bool same_geometry(const TileMapParams& a, const TileMapParams& b) {
-  const int va[] = {a.H, a.W, a.bh, a.bw, a.ph, a.pw, a.TH, a.TW, a.oy, a.ox, a.ovy, a.ovx, a.eh, a.ew};
-  const int vb[] = {b.H, b.W, b.bh, b.bw, b.ph, b.pw, b.TH, b.TW, b.oy, b.ox, b.ovy, b.ovx, b.eh, b.ew};
-  return std::equal(std::begin(va), std::end(va), std::begin(vb));
-}
-// A frame of pixel type `pix` -> its tiles in slot `slot` of the plan's img0 (an 8-bit frame is dequantised by the cut itself)
-hipError_t stream_cut(const void* frame, int pix, TileMapParams tp, const Plan* P, int slot, hipStream_t s) {
-  tp.tile0 = 0; tp.ntiles = tp.bh * tp.bw;
-  tp.src = (const float*)frame;
-  tp.dst = P->at("img0") + (int64_t)slot * tp.ntiles * tp.TH * tp.TW * 3;
-  return film_launch_cut_tiles(tp, pix, s);
-}
-
-// The steps of ONE primed push of a "stream_times" = T stream whose input frame lands in slot `slot` (0 / 1; the frame before waits in the
-// other one), in execution order - the reference's recursion (eval/util.py, _recursive_generator) depth first.  A step runs the pair
-// (frame in slot `left`, frame in slot `right`) - with `extract`, behind the extraction of the right frame, which no step has extracted
-// before - and yields the frame at position `index` of the 2^T - 1 between the two inputs (1-based, temporal order), a depth-`depth`
-// mid-frame.  feed >= 0: the result is cut, as float32, into slot `feed` = 1 + depth, where its two children find it: the left child
-// (left, feed) extracts it, the right child (feed, right) reads what the left one extracted.  The deepest mids are fed nowhere.
-struct StreamStep { int left, right, extract, index, depth, feed; };
-void stream_steps(int T, int left, int right, bool extract, int depth, int index, std::vector<StreamStep>* v) {
-  const int feed = depth < T ? 1 + depth : -1;
-  v->push_back({left, right, extract ? 1 : 0, index, depth, feed});
-  if (feed < 0) return;
-  const int half = 1 << (T - depth - 1);
-  stream_steps(T, left, feed, true, depth + 1, index - half, v);
-  stream_steps(T, feed, right, false, depth + 1, index + half, v);
-}
-std::vector<StreamStep> stream_schedule(int T, int slot) {
-  std::vector<StreamStep> v;
-  stream_steps(T, 1 - slot, slot, true, 1, 1 << (T - 1), &v);
-  return v;
-}
-
-// Option "scene_cut" = k > 0: the histogram of the frame in fs.keep, taken on `s`, downloaded and waited for; *cut = the rule's verdict
-// against the carried histogram when the stream is primed and has one.  The new histogram becomes the carried one (valid once the push succeeds).
-int stream_scene_cut(film_t* h, hipStream_t s, int k, bool* cut) {
-  FilmStream& fs = h->fs;
-  constexpr size_t bytes = FILM_HIST_BINS * sizeof(uint32_t);
-  if (!fs.hist_dev) HIPCHK(h, hipMalloc((void**)&fs.hist_dev, bytes));
-  if (!fs.hist_pin) HIPCHK(h, hipHostMalloc((void**)&fs.hist_pin, bytes, hipHostMallocDefault));
-  HIPCHK(h, film_launch_frame_histogram(fs.keep, fs.H, fs.W, fs.pix, fs.hist_dev, s));
-  HIPCHK(h, hipMemcpyAsync(fs.hist_pin, fs.hist_dev, bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  if (fs.primed && fs.hist_valid) {
-    int64_t D = 0;
-    for (int i = 0; i < FILM_HIST_BINS; ++i) D += std::llabs((int64_t)fs.hist_pin[i] - (int64_t)fs.hist_prev[i]);
-    fs.cut_distance = D;
-    *cut = 1000 * D >= (int64_t)k * 2 * frame_samples(fs.pix, fs.H, fs.W);
-  }
-  fs.hist_valid = false;   // (until the push has succeeded)
-  std::copy(fs.hist_pin, fs.hist_pin + FILM_HIST_BINS, fs.hist_prev);
   return FILM_OK;
 }
 
@@ -690,212 +627,6 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
     }
   }
   return st.finish();
-}
-
-int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* buf, int64_t cap, int64_t* needed) {
-  if (!h) return FILM_ERR_INVALID;
-  if (tiles < 1) return fail(h, FILM_ERR_INVALID, "tiles must be positive");
-  if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the half of the frame buffers the pushed frame fills)");
-  if (tiles >= 1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
-  Plan* P = nullptr;
-  int rc = get_plan(h, tiles, H, W, false, &P, tiles, 2);
-  if (rc) return rc;
-  return copy_out_string(h, plan_json(h, *P->orientation(slot)), buf, cap, needed);
-}
-
-int film_stream_pair_plan_json(film_t* h, int tiles, int H, int W, int times, int left, int right, int extract, char* buf, int64_t cap, int64_t* needed) {
-  if (!h) return FILM_ERR_INVALID;
-  if (tiles < 1) return fail(h, FILM_ERR_INVALID, "tiles must be positive");
-  if (times < 1 || times > 6) return fail(h, FILM_ERR_INVALID, "times must be 1 .. 6 (option \"stream_times\")");
-  if (left < 0 || right < 0 || left > times || right > times || left == right)
-    return fail(h, FILM_ERR_INVALID, "left and right must be two different slots of 0 .. %d (times + 1 frame slots)", times);
-  if (tiles >= 1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
-  Plan *P = nullptr, *Q = nullptr;
-  int rc = get_plan(h, tiles, H, W, false, &P, tiles, times + 1);
-  if (rc == FILM_OK) rc = plan_orientation(h, P, left, right, extract != 0, &Q);
-  if (rc) return rc;
-  return copy_out_string(h, plan_json(h, *Q, true), buf, cap, needed);
-}
-
-int film_stream_schedule_json(film_t* h, int times, int slot, char* buf, int64_t cap, int64_t* needed) {
-  if (!h) return FILM_ERR_INVALID;
-  if (times < 1 || times > 6) return fail(h, FILM_ERR_INVALID, "times must be 1 .. 6 (option \"stream_times\")");
-  if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the slot the pushed frame fills)");
-  std::ostringstream o;
-  o << "{\"times\":" << times << ",\"slot\":" << slot << ",\"slots\":" << times + 1 << ",\"produced\":" << (1 << times) - 1 << ",\"steps\":[";
-  const std::vector<StreamStep> steps = stream_schedule(times, slot);
-  for (size_t i = 0; i < steps.size(); ++i) {
-    const StreamStep& t = steps[i];
-    o << (i ? "," : "") << "{\"left\":" << t.left << ",\"right\":" << t.right << ",\"extract\":" << t.extract << ",\"index\":" << t.index
-      << ",\"depth\":" << t.depth << ",\"feed\":" << t.feed << "}";
-  }
-  o << "]}";
-  return copy_out_string(h, o.str(), buf, cap, needed);
-}
-
-int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix) {
-  if (!h) return FILM_ERR_INVALID;
-  if (h->fs.open) return fail(h, FILM_ERR_STATE, "a stream is already open on this handle (one per handle: close it, or create another handle)");
-  int rc = check_pix(h, pix, H, W);
-  if (rc) return rc;
-  if (H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
-  TileMapParams tp{};
-  tp.B = 1;
-  rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
-  if (rc == FILM_OK) rc = need_device(h, "film_stream_open");
-  if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  int tmax = 1;
-  rc = max_units(h, tp.TH, tp.TW, "tile", "use a finer block_shape", &tmax);
-  if (rc) return rc;
-  const int T = tp.bh * tp.bw;
-  // a stream neither chunks a frame nor halves on out-of-memory: the carried features of ALL tiles live in one plan
-  if (T > tmax)
-    return fail(h, FILM_ERR_INVALID, "a stream runs the whole frame in one model invocation: its %d tiles of %d x %d exceed the %d tiles one invocation "
-                "may take (64 GiB / 60 %% of the free HBM of workspace, 4 GiB per 32-bit addressed buffer, \"max_batch\") - use a finer block_shape", T, tp.TH, tp.TW, tmax);
-  const int times = h->opt_stream_times;   // fixed for this stream's life
-  Plan* P = nullptr;
-  rc = get_plan(h, T, tp.TH, tp.TW, true, &P, T, times + 1);   // (built and tuned now; FILM_ERR_NOMEM when the workspace does not fit)
-  if (rc) return rc;
-  FilmStream& fs = h->fs;
-  const size_t nv = (size_t)H * W * 3;
-  const size_t fb = frame_bytes(pix, H, W);
-  // a primed push leaves n frames: a host push downloads each as soon as it is there and waits once, so each has a place of its own -
-  // float32 streams in `result`, the others (whose float32 frame is only joined, quantised and fed back) in `result8`
-  const size_t n = ((size_t)1 << times) - 1;
-  const bool f32 = pix_layout(pix) == FILM_PIX_F32;
-  const size_t rbytes = (f32 ? n : 1) * nv * sizeof(float), qbytes = f32 ? 0 : n * fb;
-  hipError_t e = hipMalloc(&fs.keep, (fb + 3) & ~(size_t)3);   // (whole 32-bit words: the 8-bit cuts read aligned words)
-  if (e == hipSuccess) e = hipMalloc((void**)&fs.result, rbytes);
-  if (e == hipSuccess && !f32) e = hipMalloc((void**)&fs.result8, qbytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    stream_free(h);
-    return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's frame buffers (%.1f MB, stream_times = %d) failed", (fb + rbytes + qbytes) * 1e-6, times);
-  }
-  fs.open = true;
-  fs.times = times;
-  fs.H = H; fs.W = W; fs.align = align; fs.block_h = block_h; fs.block_w = block_w; fs.pix = pix;
-  return FILM_OK;
-}
-
-int film_stream_reset(film_t* h) {
-  if (!h) return FILM_ERR_INVALID;
-  if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
-  h->fs.primed = false;
-  h->fs.hist_valid = false;
-  return FILM_OK;
-}
-
-int film_stream_cut_info(film_t* h, int64_t* distance, int64_t* samples, int* cut) {
-  if (!h) return FILM_ERR_INVALID;
-  const FilmStream& fs = h->fs;
-  if (!fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
-  if (distance) *distance = fs.cut_distance;
-  if (samples) *samples = frame_samples(fs.pix, fs.H, fs.W);
-  if (cut) *cut = fs.cut;
-  return FILM_OK;
-}
-
-int film_stream_close(film_t* h) {
-  if (!h) return FILM_ERR_INVALID;
-  if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
-  (void)hipSetDevice(h->device);
-  (void)hipDeviceSynchronize();   // (device-resident pushes are asynchronous: what they read must outlive them)
-  stream_free(h);
-  return FILM_OK;
-}
-
-int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int mem_kind, void* stream) {
-  if (!h) return FILM_ERR_INVALID;
-  FilmStream& fs = h->fs;
-  if (!fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
-  hipStream_t s = pick_stream(h, mem_kind == FILM_MEM_DEVICE ? FILM_MEM_DEVICE : FILM_MEM_HOST, stream);
-  // Whatever fails from here on: the stream forgets its carried frame (as after film_stream_reset), and both streams are drained before
-  // the error goes back to the caller, who may then free or reuse `frame` / `mid`.
-  struct Unprime {
-    film_t* h; hipStream_t s; bool armed;
-    ~Unprime() {
-      if (!armed) return;
-      h->fs.primed = false;
-      h->fs.hist_valid = false;
-      (void)hipStreamSynchronize(h->stream2);
-      (void)hipStreamSynchronize(s);
-    }
-  } unprime{h, s, true};
-  if (produced) *produced = 0;
-  fs.cut_distance = -1; fs.cut = 0;
-  if (!frame || !produced || (fs.primed && !mid)) return fail(h, FILM_ERR_INVALID, "NULL argument");
-  if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
-  HIPCHK(h, hipSetDevice(h->device));
-  TileMapParams tp{};
-  tp.B = 1;
-  int rc = tile_geometry(h, fs.H, fs.W, fs.block_h, fs.block_w, fs.align, &tp);   // ("block_overlap_*" as they are NOW)
-  if (rc) return rc;
-  const int T = tp.bh * tp.bw;
-  Plan* P0 = nullptr;
-  rc = get_plan(h, T, tp.TH, tp.TW, true, &P0, T, fs.times + 1);
-  if (rc) return rc;
-  const bool host = mem_kind == FILM_MEM_HOST;
-  const size_t nv = (size_t)fs.H * fs.W * 3;
-  if (fs.primed && (fs.plan_id != P0->id || !same_geometry(fs.geo, tp))) {
-    // the plan that held the previous frame's pyramids was evicted or dropped since (or the tiles changed): extract that frame again
-    // from the stream's own copy, where it was - the same ops on the same values, the same bits
-    Plan* R = nullptr;
-    if ((rc = plan_orientation(h, P0, 1 - fs.slot, fs.slot, true, &R))) return rc;
-    HIPCHK(h, stream_cut(fs.keep, fs.pix, tp, R, fs.slot, s));
-    if ((rc = run_plan(h, R, s, R->n_extract))) return rc;
-  }
-  const size_t fb = frame_bytes(fs.pix, fs.H, fs.W);
-  HIPCHK(h, hipMemcpyAsync(fs.keep, frame, fb, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-  // option "scene_cut": a cut is film_stream_reset followed by this push - the frame starts a new scene in slot 0, extraction only
-  const int scene_k = h->opt_scene_cut;
-  bool cut = false;
-  if (scene_k > 0 && (rc = stream_scene_cut(h, s, scene_k, &cut))) return rc;
-  const bool primed = fs.primed && !cut;
-  const int slot = primed ? 1 - fs.slot : 0;
-  Plan* P = nullptr;
-  if ((rc = plan_orientation(h, P0, 1 - slot, slot, true, &P))) return rc;
-  HIPCHK(h, stream_cut(fs.keep, fs.pix, tp, P, slot, s));
-  int made = 0;
-  if (!primed) {
-    if ((rc = run_plan(h, P, s, P->n_extract))) return rc;
-  } else {
-    // One pair run per generated frame, in the order of stream_schedule (times = 1: the one pair of the two inputs).  Each result is
-    // joined in float32 by the kernels of film_interpolate - straight into its place in `mid` for a device float32 stream - then
-    // quantised into its place by film_to_uint8's kernel for an 8-bit RGB stream, by film_to_yuv420's for a 4:2:0 stream (8-bit or
-    // 10-bit); a result that has children is cut from the float32 frame - never from the quantised one - into its slot by the float cut.
-    struct AppendProfile { film_t* h; ~AppendProfile() { h->profile_append = false; } } append{h};
-    const bool f32 = fs.pix == FILM_PIX_F32;
-    for (const StreamStep& t : stream_schedule(fs.times, slot)) {
-      Plan* Q = nullptr;
-      if ((rc = plan_orientation(h, P0, t.left, t.right, t.extract != 0, &Q)) || (rc = run_plan(h, Q, s))) return rc;
-      h->profile_append = true;   // (option "profile": the runs of this push add up)
-      const size_t k = (size_t)t.index - 1;
-      float* joined = !f32 ? fs.result : host ? fs.result + k * nv : (float*)mid + k * nv;
-      TileMapParams j = tp;
-      j.tile0 = 0; j.ntiles = T; j.src = Q->at("out"); j.dst = joined;
-      HIPCHK(h, film_launch_join_tiles(j, s));
-      if (!f32) {
-        void* q = host ? (void*)(fs.result8 + k * fb) : (void*)((unsigned char*)mid + k * fb);
-        if (pix_is_yuv(fs.pix))
-          HIPCHK(h, film_launch_rgb_to_yuv420(joined, q, fs.H, fs.W, fs.pix, s));
-        else
-          HIPCHK(h, film_launch_to_uint8(joined, static_cast<uint8_t*>(q), (int64_t)nv, s));
-        if (host) HIPCHK(h, hipMemcpyAsync((unsigned char*)mid + k * fb, q, fb, hipMemcpyDeviceToHost, s));
-      } else if (host) {
-        HIPCHK(h, hipMemcpyAsync((float*)mid + k * nv, joined, nv * sizeof(float), hipMemcpyDeviceToHost, s));
-      }
-      if (t.feed >= 0) HIPCHK(h, stream_cut(joined, FILM_PIX_F32, tp, Q, t.feed, s));
-      ++made;
-    }
-  }
-  if (host) HIPCHK(h, hipStreamSynchronize(s));
-  *produced = made;
-  fs.primed = true; fs.slot = slot; fs.plan_id = P0->id; fs.geo = tp;
-  fs.hist_valid = scene_k > 0; fs.cut = cut ? 1 : 0;
-  unprime.armed = false;
-  return FILM_OK;
 }
 
 int film_get_tap(film_t* h, const char* name, float* dst, int64_t cap, int64_t dims[4]) {

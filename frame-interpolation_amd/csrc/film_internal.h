@@ -3,6 +3,7 @@
 //
 //   film_engine.cpp   C-ABI entry points: handle lifetime, the option table, the JSON queries, tiling and chunking of film_forward /
 //                     film_interpolate / film_interpolate_sequence, the host-buffer pipeline, taps, the debug entry points
+//   film_stream.cpp   the frame streams (film_stream_*): the schedule of a push, where its frames live, the scene-cut rule, their JSON queries
 //   film_exec.cpp     the executor: launch of one op, the two-lane issue, run_plan (eager, hipGraph capture / replay, profiling)
 //   film_tune.cpp     the tile candidates of each kernel family, the autotuner, the tune cache as text
 //   film_plans.cpp    the plan cache with its workspace arenas and eviction, the units-per-invocation limits
@@ -130,25 +131,27 @@ struct Plan {
   // 0: a pair plan (img0 = [x0 tiles | x1 tiles], 2B images); > 0: a sequence plan over B / tiles consecutive frame pairs of `tiles`
   // tiles each (img0 = B + tiles images, frame-major: image f * tiles + t; pair-tile p reads images p and p + tiles)
   int tiles = 0;
-  // A stream plan (film_stream_*): the sequence plan of ONE pair of `tiles` tiles (B == tiles) over `slots` frame slots of `tiles` images
-  // each in the per-image buffers (img*, feat*, extractor scratch): 2 for a plain stream - the two frames of a pair take turns - and T + 1
-  // with option "stream_times" = T: slots 0 and 1 take turns for the input frames, slot 1 + d holds the depth-d mid-frame that is fed back.
+  // ---- stream plans only (film_stream_*) ----
+  // A stream plan is the sequence plan of ONE pair of `tiles` tiles (B == tiles) over `slots` frame slots of `tiles` images each in the
+  // per-image buffers (img*, feat*, extractor scratch): 2 for a plain stream - the two frames of a pair take turns - and T + 1 with option
+  // "stream_times" = T: slots 0 and 1 take turns for the input frames, slot 1 + d holds the depth-d mid-frame that is fed back.
   // An ORIENTATION is (left, right, extract): image 0 of the pair is the frame in slot `left`, image 1 the one in slot `right`, and with
   // `extract` the image pyramid and feature ops of the right frame, NB = tiles, are ops [0, n_extract) - else the plan has none of them
-  // (n_extract = 0: a plan of its own with its own lane analysis, never the tail of an extracting one).  `slot` = right (-1: not a stream
-  // plan).  The cached plan is orientation (1, 0, extract); `others` holds the rest, keyed by orientation_key, over the SAME buffers and
-  // workspace (they own no arena), built on first use (plan_orientation).
-  int slot = -1;
-  int slots = 0, left = -1;
+  // (n_extract = 0: a plan of its own with its own lane analysis, never the tail of an extracting one).  right = -1: not a stream plan.
+  // Ownership: the CACHE ENTRY (what get_plan returns; itself orientation (1, 0, extract)) owns the buffer layout, the id and the workspace,
+  // and holds every other orientation in `orientations`, keyed by orientation_key.  An orientation owns its ops, events and graph and
+  // borrows the rest (owns_arena = false): same bufs, same id, same arena pointer, gone with its entry.  plan_orientation (film_plans.cpp)
+  // is the one way to an orientation: it finds it or builds it on first use.
+  int slots = 0, left = -1, right = -1;
   bool extract = true;
   size_t n_extract = 0;
-  std::map<int, std::unique_ptr<Plan>> others;
+  bool owns_arena = true;
+  std::map<int, std::unique_ptr<Plan>> orientations;
   static int orientation_key(int l, int r, bool e) { return (l * 16 + r) * 2 + (e ? 1 : 0); }
-  Plan* orientation(int s) {   // the extracting orientation of a two-slot push into slot s, if it is built
-    if (s == slot && left == 1 - s && extract) return this;
-    auto it = others.find(orientation_key(1 - s, s, true));
-    return it == others.end() ? nullptr : it->second.get();
+  bool holds(const Plan* q) const {   // q is this cache entry or one of its orientations
+    return q == this || std::any_of(orientations.begin(), orientations.end(), [q](const auto& kv) { return kv.second.get() == q; });
   }
+  // ----
   uint64_t id = 0;           // unique per handle and build: a stream tells a rebuilt plan (its carried features are gone) from the one it filled
   std::vector<Buffer> bufs;
   std::vector<OpDesc> ops;
@@ -326,6 +329,16 @@ inline FamilyCodes family_codes(ConvFamily f) {
 
 // ---- film_engine.cpp
 int copy_out_string(film_t* h, const std::string& s, char* buf, int64_t cap, int64_t* needed);   // a text result of the C-ABI, or its size
+int tile_geometry(film_t* h, int H, int W, int block_h, int block_w, int align, TileMapParams* tp);   // a frame cut into padded tiles, or a refusal
+int check_pix(film_t* h, int pix, int H, int W);      // FILM_OK, or the refusal of a `pix` argument for H x W frames
+int64_t frame_samples(int pix, int H, int W);         // samples of one H x W frame of pixel type `pix` ...
+size_t frame_bytes(int pix, int H, int W);            // ... and its bytes
+int need_device(film_t* h, const char* fn);           // the refusals the compute entry points share (`fn`: the entry point)
+hipStream_t pick_stream(film_t* h, int mem_kind, void* stream);   // the stream a call with `stream` (NULL: the default of its mem_kind) works on
+constexpr int kMaxStreamTimes = 6;                    // option "stream_times": 1 .. this
+
+// ---- film_stream.cpp
+void stream_free(film_t* h);   // the open stream's device buffers go back and it is closed (film_stream_close, film_destroy)
 
 // ---- film_exec.cpp
 hipError_t launch_op(const OpDesc& op, float* arena, const float* wts, hipStream_t s);
@@ -348,7 +361,8 @@ int autotune_plan(film_t* h, Plan* P, bool measure = true);   // !measure: only 
 
 // ---- film_plans.cpp
 int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles = 0, int slots = 0);   // slots >= 2: the stream plan, B == tiles
-// orientation (left, right, extract) of the stream plan P0 (what get_plan returned), built, tuned and cached with it on first use
+// orientation (left, right, extract) of the stream plan P0 (what get_plan returned): found, or built, tuned and cached with it on first use.
+// (1, 0, extract) is P0 itself and (0, 1, extract) comes with it; nothing else looks for an orientation.
 int plan_orientation(film_t* h, Plan* P0, int left, int right, bool extract, Plan** out);
 void drop_plans(film_t* h);   // waits for the device, then frees every cached plan
 int max_units(film_t* h, int H, int W, const char* what, const char* advice, int* units);

@@ -638,7 +638,7 @@ struct Planner {
     fc = feature_channels(c);
     ff = fusion_filters(c);
     P->B = B; P->H = H0; P->W = W0; P->tiles = T;
-    P->slots = slots; P->slot = slots > 0 ? right : -1; P->left = slots > 0 ? left : -1; P->extract = extract;
+    P->slots = slots; P->right = slots > 0 ? right : -1; P->left = slots > 0 ? left : -1; P->extract = extract;
     add_buffers();
     emit_image_pyramids();
     for (int i = 0; i < NL; ++i) emit_extractor(i);
@@ -800,10 +800,10 @@ std::string plan_json(film_t* h, const Plan& P, bool orientation_keys) {
   std::ostringstream o;
   JsonObject j{o};
   j.num("B", P.B); j.num("H", P.H); j.num("W", P.W);
-  if (P.slot >= 0) {
+  if (P.right >= 0) {
     j.str("kind", "stream"); j.num("tiles", P.tiles);
-    if (orientation_keys) { j.num("slots", P.slots); j.num("left", P.left); j.num("right", P.slot); }
-    else j.num("slot", P.slot);
+    if (orientation_keys) { j.num("slots", P.slots); j.num("left", P.left); j.num("right", P.right); }
+    else j.num("slot", P.right);
     j.num("n_extract", P.n_extract);
   }
   else if (P.tiles > 0) { j.str("kind", "sequence"); j.num("n_pairs", P.B / P.tiles); j.num("tiles", P.tiles); }

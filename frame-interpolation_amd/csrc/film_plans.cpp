@@ -5,18 +5,17 @@
 namespace film_internal {
 namespace {
 void free_plan(Plan* p) {
-  for (auto& kv : p->others) { kv.second->arena = nullptr; free_plan(kv.second.get()); }   // (the other orientations of a stream plan work on this plan's arena)
+  for (auto& kv : p->orientations) free_plan(kv.second.get());
   if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
   if (p->graph) (void)hipGraphDestroy(p->graph);
   for (auto e : p->ev) (void)hipEventDestroy(e);
   for (auto e : p->lane_ev) if (e) (void)hipEventDestroy(e);
-  if (p->arena) (void)hipFree(p->arena);
+  if (p->arena && p->owns_arena) (void)hipFree(p->arena);
 }
 
 // Plan `index` leaves the cache with everything it holds on the device.  Work that may still run on it is the caller's to wait for.
 void forget_plan(film_t* h, size_t index) {
-  if (h->last_plan == h->plans[index].get()) h->last_plan = nullptr;
-  for (auto& kv : h->plans[index]->others) if (h->last_plan == kv.second.get()) h->last_plan = nullptr;
+  if (h->plans[index]->holds(h->last_plan)) h->last_plan = nullptr;
   free_plan(h->plans[index].get());
   h->plans.erase(h->plans.begin() + index);
 }
@@ -55,35 +54,30 @@ void force_shapes(film_t* h, Plan* R) {
   }
 }
 
-// One more orientation of the stream plan P over P's buffers: built and checked against P's layout, not yet tuned
-int add_orientation(film_t* h, Plan* P, int left, int right, bool extract, Plan** out) {
-  std::unique_ptr<Plan> Q(new Plan);
-  int rc = plan_build(h, Q.get(), P->B, P->H, P->W, P->tiles, P->slots, left, right, extract);
-  if (rc) return rc;
-  bool alike = Q->arena_floats == P->arena_floats && Q->bufs.size() == P->bufs.size() && Q->n_extract == (extract ? P->n_extract : 0);
-  for (size_t i = 0; alike && i < Q->bufs.size(); ++i) alike = Q->bufs[i].name == P->bufs[i].name && Q->bufs[i].off == P->bufs[i].off && Q->bufs[i].floats == P->bufs[i].floats;
-  if (!alike) return fail(h, FILM_ERR_INVALID, "planner: the orientations of a stream plan lay out different workspaces");
-  Q->id = P->id;
-  *out = Q.get();
-  P->others[Plan::orientation_key(left, right, extract)] = std::move(Q);
-  return FILM_OK;
-}
 }  // namespace
 
 int plan_orientation(film_t* h, Plan* P0, int left, int right, bool extract, Plan** out) {
   if (P0->slots < 2) return fail(h, FILM_ERR_INVALID, "planner: not a stream plan");
-  if (P0->left == left && P0->slot == right && P0->extract == extract) { *out = P0; return FILM_OK; }
-  auto it = P0->others.find(Plan::orientation_key(left, right, extract));
-  if (it != P0->others.end()) { *out = it->second.get(); return FILM_OK; }
-  Plan* Q = nullptr;
-  int rc = add_orientation(h, P0, left, right, extract, &Q);
+  if (P0->left == left && P0->right == right && P0->extract == extract) { *out = P0; return FILM_OK; }
+  const int key = Plan::orientation_key(left, right, extract);
+  const auto it = P0->orientations.find(key);
+  if (it != P0->orientations.end()) { *out = it->second.get(); return FILM_OK; }
+  // first use: built over P0's buffers and checked against its layout
+  std::unique_ptr<Plan> Q(new Plan);
+  int rc = plan_build(h, Q.get(), P0->B, P0->H, P0->W, P0->tiles, P0->slots, left, right, extract);
   if (rc) return rc;
+  bool alike = Q->arena_floats == P0->arena_floats && Q->bufs.size() == P0->bufs.size() && Q->n_extract == (extract ? P0->n_extract : 0);
+  for (size_t i = 0; alike && i < Q->bufs.size(); ++i) alike = Q->bufs[i].name == P0->bufs[i].name && Q->bufs[i].off == P0->bufs[i].off && Q->bufs[i].floats == P0->bufs[i].floats;
+  if (!alike) return fail(h, FILM_ERR_INVALID, "planner: the orientations of a stream plan lay out different workspaces");
+  Q->id = P0->id;
   Q->arena = P0->arena;
-  // its conv shapes are the first orientation's, measured when the workspace was allocated: the choices are taken, nothing is timed - the
+  Q->owns_arena = false;
+  // its conv shapes are the cache entry's, measured when the workspace was allocated: the choices are taken, nothing is timed - the
   // workspace holds the carried frames of a running stream
-  if (Q->arena && h->opt_autotune && h->finalized && (rc = autotune_plan(h, Q, false))) return rc;
-  force_shapes(h, Q);
-  *out = Q;
+  if (Q->arena && h->opt_autotune && h->finalized && (rc = autotune_plan(h, Q.get(), false))) return rc;
+  force_shapes(h, Q.get());
+  *out = Q.get();
+  P0->orientations[key] = std::move(Q);
   return FILM_OK;
 }
 
@@ -93,7 +87,7 @@ void drop_plans(film_t* h) {
 }
 
 // Plans are cached per (B, H, W, tiles, slots): tiles = 0 for pair plans, > 0 for sequence plans (Plan::tiles), slots >= 2 for the
-// stream plan of `tiles` tiles over that many frame slots (Plan::slot >= 0: all its orientations, one cache entry, one workspace) -
+// stream plan of `tiles` tiles over that many frame slots (Plan::right >= 0: all its orientations, one cache entry, one workspace) -
 // the kinds never stand in for each other.  All count toward the three device plans kept alive.
 int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int tiles, int slots) {
   const bool stream = slots > 0;
@@ -118,8 +112,6 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
   int rc = stream ? plan_build(h, P.get(), B, H, W, tiles, slots, 1, 0, true) : plan_build(h, P.get(), B, H, W, tiles);
   if (rc) return rc;
   P->id = ++h->plan_ids;
-  Plan* twin = nullptr;   // a stream plan: the orientation of the second push comes with it, the deeper ones on first use (plan_orientation)
-  if (stream && (rc = add_orientation(h, P.get(), 0, 1, true, &twin))) return rc;
   if (need_device && slots > 2) {
     // the slots of "stream_times" > 1 grow the per-image buffers beyond what max_units has budgeted for a pair of frames
     const int64_t lim = limited_buffer_bytes(P.get()), bytes = P->arena_floats * (int64_t)sizeof(float);
@@ -161,15 +153,13 @@ int get_plan(film_t* h, int B, int H, int W, bool need_device, Plan** out, int t
     }
     HIPCHK(h, hipMemsetAsync(P->arena, 0, (size_t)P->arena_floats * sizeof(float), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (twin) twin->arena = P->arena;
-    if (h->opt_autotune && h->finalized) {
-      int trc = autotune_plan(h, P.get());
-      if (trc == FILM_OK && twin) trc = autotune_plan(h, twin);   // (its shapes are the first orientation's: nothing is measured again)
-      if (trc) { free_plan(P.get()); return trc; }
-    }
+    if (h->opt_autotune && h->finalized && (rc = autotune_plan(h, P.get()))) { free_plan(P.get()); return rc; }
   }
   force_shapes(h, P.get());
-  if (twin) force_shapes(h, twin);
+  // a stream plan: the orientation of the second push comes with it - no push of a running stream builds a plan, and film_stream_open
+  // reports orientations that disagree about the layout; the deeper ones come on first use
+  Plan* second = nullptr;
+  if (stream && (rc = plan_orientation(h, P.get(), 0, 1, true, &second))) { free_plan(P.get()); return rc; }
   P->last_use = ++h->tick;
   *out = P.get();
   h->plans.push_back(std::move(P));

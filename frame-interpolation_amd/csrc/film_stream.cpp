@@ -1,0 +1,306 @@
+// film_stream.cpp -- the frame streams of the C-ABI (film_stream_*; the contract: include/film_hip.h): the one open stream of a handle
+// (FilmStream, film_internal.h), the schedule of a push, where the frames of a push live, the scene-cut rule, and the JSON queries about
+// the stream plan.  The stream plan and its orientations are the plan cache's (get_plan / plan_orientation, film_plans.cpp); tile geometry,
+// the `pix` check and the stream choice are shared with the other entry points (film_engine.cpp).
+#include "film_internal.h"
+
+using namespace film_internal;
+
+// The stream's device buffers go back and it is closed.  Work that may still use them is the caller's to wait for.
+void film_internal::stream_free(film_t* h) {
+  FilmStream& fs = h->fs;
+  for (void* p : {fs.keep, (void*)fs.result, (void*)fs.result8, (void*)fs.hist_dev})
+    if (p) (void)hipFree(p);
+  if (fs.hist_pin) (void)hipHostFree(fs.hist_pin);
+  fs = FilmStream{};
+}
+
+namespace {
+
+// what of a TileMapParams tile_geometry decides: the same values cut the same tiles
+bool same_geometry(const TileMapParams& a, const TileMapParams& b) {
+  const int va[] = {a.H, a.W, a.bh, a.bw, a.ph, a.pw, a.TH, a.TW, a.oy, a.ox, a.ovy, a.ovx, a.eh, a.ew};
+  const int vb[] = {b.H, b.W, b.bh, b.bw, b.ph, b.pw, b.TH, b.TW, b.oy, b.ox, b.ovy, b.ovx, b.eh, b.ew};
+  return std::equal(std::begin(va), std::end(va), std::begin(vb));
+}
+// A frame of pixel type `pix` -> its tiles in slot `slot` of the plan's img0 (an 8-bit frame is dequantised by the cut itself)
+hipError_t stream_cut(const void* frame, int pix, TileMapParams tp, const Plan* P, int slot, hipStream_t s) {
+  tp.tile0 = 0; tp.ntiles = tp.bh * tp.bw;
+  tp.src = (const float*)frame;
+  tp.dst = P->at("img0") + (int64_t)slot * tp.ntiles * tp.TH * tp.TW * 3;
+  return film_launch_cut_tiles(tp, pix, s);
+}
+
+// The steps of ONE primed push of a "stream_times" = T stream whose input frame lands in slot `slot` (0 / 1; the frame before waits in the
+// other one), in execution order - the reference's recursion (eval/util.py, _recursive_generator) depth first.  A step runs the pair
+// (frame in slot `left`, frame in slot `right`) - with `extract`, behind the extraction of the right frame, which no step has extracted
+// before - and yields the frame at position `index` of the 2^T - 1 between the two inputs (1-based, temporal order), a depth-`depth`
+// mid-frame.  feed >= 0: the result is cut, as float32, into slot `feed` = 1 + depth, where its two children find it: the left child
+// (left, feed) extracts it, the right child (feed, right) reads what the left one extracted.  The deepest mids are fed nowhere.
+struct StreamStep { int left, right, extract, index, depth, feed; };
+void stream_steps(int T, int left, int right, bool extract, int depth, int index, std::vector<StreamStep>* v) {
+  const int feed = depth < T ? 1 + depth : -1;
+  v->push_back({left, right, extract ? 1 : 0, index, depth, feed});
+  if (feed < 0) return;
+  const int half = 1 << (T - depth - 1);
+  stream_steps(T, left, feed, true, depth + 1, index - half, v);
+  stream_steps(T, feed, right, false, depth + 1, index + half, v);
+}
+std::vector<StreamStep> stream_schedule(int T, int slot) {
+  std::vector<StreamStep> v;
+  stream_steps(T, 1 - slot, slot, true, 1, 1 << (T - 1), &v);
+  return v;
+}
+
+// Where the n = 2^times - 1 frames of a primed push live.  A host push downloads each frame as soon as it is there and waits once, so each
+// has a place of its own on the device: a float32 stream's in fs.result; every other stream's - whose float32 frame is only joined,
+// quantised and fed back - in fs.result8, behind ONE float32 frame in fs.result.  A device push writes straight into the caller's `mid`.
+// film_stream_open sizes the two buffers from here, film_stream_push takes the places of frame k from here.
+struct StreamFrames {
+  size_t nv, fb, n;   // values of a float32 frame; bytes of a frame of the stream's pixel type; frames per push
+  bool f32;
+  StreamFrames(int pix, int H, int W, int times)
+      : nv((size_t)H * W * 3), fb(frame_bytes(pix, H, W)), n(((size_t)1 << times) - 1), f32(pix_layout(pix) == FILM_PIX_F32) {}
+  size_t result_bytes() const { return (f32 ? n : 1) * nv * sizeof(float); }   // of fs.result
+  size_t result8_bytes() const { return f32 ? 0 : n * fb; }                    // of fs.result8 (0: the stream has none)
+  // joined: the float32 frame the join writes; quant: the quantised frame (RGB bytes or a 4:2:0 frame), nullptr for a float32 stream;
+  // host: where a host push downloads the frame to, fb bytes from `quant` or else `joined`, nullptr for a device push
+  struct Place { float* joined; void *quant, *host; };
+  Place place(const FilmStream& fs, void* mid, bool host, size_t k) const {   // of frame k (0-based, temporal order) of a push into `mid`
+    void* out = (unsigned char*)mid + k * fb;   // (a float32 frame: fb = nv floats)
+    if (f32) return {host ? fs.result + k * nv : (float*)out, nullptr, host ? out : nullptr};
+    return {fs.result, host ? (void*)(fs.result8 + k * fb) : out, host ? out : nullptr};
+  }
+};
+
+// Whatever fails in a push behind this guard: the stream forgets its carried frame (as after film_stream_reset), and both streams are
+// drained before the error goes back to the caller, who may then free or reuse `frame` / `mid`.
+struct Unprime {
+  film_t* h; hipStream_t s; bool armed;
+  ~Unprime() { if (armed) { h->fs.primed = h->fs.hist_valid = false; (void)hipStreamSynchronize(h->stream2); (void)hipStreamSynchronize(s); } }
+};
+// option "profile": the pair runs of one push add up (the push sets the flag behind its first run), and the next call starts afresh
+struct AppendProfile { film_t* h; ~AppendProfile() { h->profile_append = false; } };
+
+// The plan that held the carried frame's pyramids was evicted or dropped since that frame was pushed (or the tiles changed): the frame is
+// extracted again from the stream's own copy, into the slot where it was - the same ops on the same values, the same bits.
+int stream_reextract(film_t* h, Plan* P0, const TileMapParams& tp, hipStream_t s) {
+  const FilmStream& fs = h->fs;
+  Plan* R = nullptr;
+  int rc = plan_orientation(h, P0, 1 - fs.slot, fs.slot, true, &R);
+  if (rc) return rc;
+  HIPCHK(h, stream_cut(fs.keep, fs.pix, tp, R, fs.slot, s));
+  return run_plan(h, R, s, R->n_extract);
+}
+
+// Option "scene_cut" = k > 0: the histogram of the frame in fs.keep, taken on `s`, downloaded and waited for; *cut = the rule's verdict
+// against the carried histogram when the stream is primed and has one.  The new histogram becomes the carried one (valid once the push succeeds).
+int stream_scene_cut(film_t* h, hipStream_t s, int k, bool* cut) {
+  FilmStream& fs = h->fs;
+  constexpr size_t bytes = FILM_HIST_BINS * sizeof(uint32_t);
+  if (!fs.hist_dev) HIPCHK(h, hipMalloc((void**)&fs.hist_dev, bytes));
+  if (!fs.hist_pin) HIPCHK(h, hipHostMalloc((void**)&fs.hist_pin, bytes, hipHostMallocDefault));
+  HIPCHK(h, film_launch_frame_histogram(fs.keep, fs.H, fs.W, fs.pix, fs.hist_dev, s));
+  HIPCHK(h, hipMemcpyAsync(fs.hist_pin, fs.hist_dev, bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  if (fs.primed && fs.hist_valid) {
+    int64_t D = 0;
+    for (int i = 0; i < FILM_HIST_BINS; ++i) D += std::llabs((int64_t)fs.hist_pin[i] - (int64_t)fs.hist_prev[i]);
+    fs.cut_distance = D;
+    *cut = 1000 * D >= (int64_t)k * 2 * frame_samples(fs.pix, fs.H, fs.W);
+  }
+  fs.hist_valid = false;   // (until the push has succeeded)
+  std::copy(fs.hist_pin, fs.hist_pin + FILM_HIST_BINS, fs.hist_prev);
+  return FILM_OK;
+}
+
+// One result of a push, the "out" tiles of the pair run Q, delivered to `p`: joined in float32 by the kernels of film_interpolate, then
+// quantised by film_to_uint8's kernel for an 8-bit RGB stream, by film_to_yuv420's for a 4:2:0 stream (8-bit or 10-bit), then downloaded
+// (a host push: queued, not waited for); feed >= 0: a result that has children is cut from the float32 frame - never from the quantised
+// one - into slot `feed` by the float cut.
+int stream_deliver(film_t* h, const Plan* Q, const TileMapParams& tp, const StreamFrames& fr, const StreamFrames::Place& p, int feed, hipStream_t s) {
+  const FilmStream& fs = h->fs;
+  TileMapParams j = tp;
+  j.tile0 = 0; j.ntiles = tp.bh * tp.bw; j.src = Q->at("out"); j.dst = p.joined;
+  HIPCHK(h, film_launch_join_tiles(j, s));
+  if (p.quant && pix_is_yuv(fs.pix))
+    HIPCHK(h, film_launch_rgb_to_yuv420(p.joined, p.quant, fs.H, fs.W, fs.pix, s));
+  else if (p.quant)
+    HIPCHK(h, film_launch_to_uint8(p.joined, static_cast<uint8_t*>(p.quant), (int64_t)fr.nv, s));
+  if (p.host) HIPCHK(h, hipMemcpyAsync(p.host, p.quant ? p.quant : (void*)p.joined, fr.fb, hipMemcpyDeviceToHost, s));
+  if (feed >= 0) HIPCHK(h, stream_cut(p.joined, FILM_PIX_F32, tp, Q, feed, s));
+  return FILM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (tiles < 1) return fail(h, FILM_ERR_INVALID, "tiles must be positive");
+  if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the half of the frame buffers the pushed frame fills)");
+  if (tiles >= 1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
+  Plan *P = nullptr, *Q = nullptr;
+  int rc = get_plan(h, tiles, H, W, false, &P, tiles, 2);
+  if (rc == FILM_OK) rc = plan_orientation(h, P, 1 - slot, slot, true, &Q);
+  if (rc) return rc;
+  return copy_out_string(h, plan_json(h, *Q), buf, cap, needed);
+}
+
+int film_stream_pair_plan_json(film_t* h, int tiles, int H, int W, int times, int left, int right, int extract, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (tiles < 1) return fail(h, FILM_ERR_INVALID, "tiles must be positive");
+  if (times < 1 || times > kMaxStreamTimes) return fail(h, FILM_ERR_INVALID, "times must be 1 .. 6 (option \"stream_times\")");
+  if (left < 0 || right < 0 || left > times || right > times || left == right)
+    return fail(h, FILM_ERR_INVALID, "left and right must be two different slots of 0 .. %d (times + 1 frame slots)", times);
+  if (tiles >= 1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
+  Plan *P = nullptr, *Q = nullptr;
+  int rc = get_plan(h, tiles, H, W, false, &P, tiles, times + 1);
+  if (rc == FILM_OK) rc = plan_orientation(h, P, left, right, extract != 0, &Q);
+  if (rc) return rc;
+  return copy_out_string(h, plan_json(h, *Q, true), buf, cap, needed);
+}
+
+int film_stream_schedule_json(film_t* h, int times, int slot, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (times < 1 || times > kMaxStreamTimes) return fail(h, FILM_ERR_INVALID, "times must be 1 .. 6 (option \"stream_times\")");
+  if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the slot the pushed frame fills)");
+  std::ostringstream o;
+  o << "{\"times\":" << times << ",\"slot\":" << slot << ",\"slots\":" << times + 1 << ",\"produced\":" << (1 << times) - 1 << ",\"steps\":[";
+  const std::vector<StreamStep> steps = stream_schedule(times, slot);
+  for (size_t i = 0; i < steps.size(); ++i) {
+    const StreamStep& t = steps[i];
+    o << (i ? "," : "") << "{\"left\":" << t.left << ",\"right\":" << t.right << ",\"extract\":" << t.extract << ",\"index\":" << t.index
+      << ",\"depth\":" << t.depth << ",\"feed\":" << t.feed << "}";
+  }
+  o << "]}";
+  return copy_out_string(h, o.str(), buf, cap, needed);
+}
+
+int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix) {
+  if (!h) return FILM_ERR_INVALID;
+  if (h->fs.open) return fail(h, FILM_ERR_STATE, "a stream is already open on this handle (one per handle: close it, or create another handle)");
+  int rc = check_pix(h, pix, H, W);
+  if (rc) return rc;
+  if (H < 1 || W < 1) return fail(h, FILM_ERR_INVALID, "B, H, W must be positive");
+  TileMapParams tp{};
+  tp.B = 1;
+  rc = tile_geometry(h, H, W, block_h, block_w, align, &tp);
+  if (rc == FILM_OK) rc = need_device(h, "film_stream_open");
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  int tmax = 1;
+  rc = max_units(h, tp.TH, tp.TW, "tile", "use a finer block_shape", &tmax);
+  if (rc) return rc;
+  const int T = tp.bh * tp.bw;
+  // a stream neither chunks a frame nor halves on out-of-memory: the carried features of ALL tiles live in one plan
+  if (T > tmax)
+    return fail(h, FILM_ERR_INVALID, "a stream runs the whole frame in one model invocation: its %d tiles of %d x %d exceed the %d tiles one invocation "
+                "may take (64 GiB / 60 %% of the free HBM of workspace, 4 GiB per 32-bit addressed buffer, \"max_batch\") - use a finer block_shape", T, tp.TH, tp.TW, tmax);
+  const int times = h->opt_stream_times;   // fixed for this stream's life
+  Plan* P = nullptr;
+  rc = get_plan(h, T, tp.TH, tp.TW, true, &P, T, times + 1);   // (built and tuned now; FILM_ERR_NOMEM when the workspace does not fit)
+  if (rc) return rc;
+  FilmStream& fs = h->fs;
+  const StreamFrames fr(pix, H, W, times);
+  hipError_t e = hipMalloc(&fs.keep, (fr.fb + 3) & ~(size_t)3);   // (whole 32-bit words: the 8-bit cuts read aligned words)
+  if (e == hipSuccess) e = hipMalloc((void**)&fs.result, fr.result_bytes());
+  if (e == hipSuccess && fr.result8_bytes()) e = hipMalloc((void**)&fs.result8, fr.result8_bytes());
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    stream_free(h);
+    return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's frame buffers (%.1f MB, stream_times = %d) failed",
+                (fr.fb + fr.result_bytes() + fr.result8_bytes()) * 1e-6, times);
+  }
+  fs.open = true;
+  fs.times = times;
+  fs.H = H; fs.W = W; fs.align = align; fs.block_h = block_h; fs.block_w = block_w; fs.pix = pix;
+  return FILM_OK;
+}
+
+int film_stream_reset(film_t* h) {
+  if (!h) return FILM_ERR_INVALID;
+  if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  h->fs.primed = false;
+  h->fs.hist_valid = false;
+  return FILM_OK;
+}
+
+int film_stream_cut_info(film_t* h, int64_t* distance, int64_t* samples, int* cut) {
+  if (!h) return FILM_ERR_INVALID;
+  const FilmStream& fs = h->fs;
+  if (!fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  if (distance) *distance = fs.cut_distance;
+  if (samples) *samples = frame_samples(fs.pix, fs.H, fs.W);
+  if (cut) *cut = fs.cut;
+  return FILM_OK;
+}
+
+int film_stream_close(film_t* h) {
+  if (!h) return FILM_ERR_INVALID;
+  if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();   // (device-resident pushes are asynchronous: what they read must outlive them)
+  stream_free(h);
+  return FILM_OK;
+}
+
+// The order of the device work of a push - keep-copy; histogram, download, wait (option "scene_cut"); cut; per step of the schedule: run,
+// join, quantise, download, feed-cut; one wait for a host push - is what lets a host push download a frame beside the next pair run, and
+// what makes it hold for pageable memory, whose copies block the calling thread.
+int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int mem_kind, void* stream) {
+  if (!h) return FILM_ERR_INVALID;
+  FilmStream& fs = h->fs;
+  if (!fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  hipStream_t s = pick_stream(h, mem_kind == FILM_MEM_DEVICE ? FILM_MEM_DEVICE : FILM_MEM_HOST, stream);
+  Unprime unprime{h, s, true};   // (whatever fails from here on)
+  if (produced) *produced = 0;
+  fs.cut_distance = -1; fs.cut = 0;
+  if (!frame || !produced || (fs.primed && !mid)) return fail(h, FILM_ERR_INVALID, "NULL argument");
+  if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
+  HIPCHK(h, hipSetDevice(h->device));
+  TileMapParams tp{};
+  tp.B = 1;
+  int rc = tile_geometry(h, fs.H, fs.W, fs.block_h, fs.block_w, fs.align, &tp);   // ("block_overlap_*" as they are NOW)
+  if (rc) return rc;
+  const int T = tp.bh * tp.bw;
+  Plan* P0 = nullptr;
+  rc = get_plan(h, T, tp.TH, tp.TW, true, &P0, T, fs.times + 1);
+  if (rc) return rc;
+  const bool host = mem_kind == FILM_MEM_HOST;
+  if (fs.primed && (fs.plan_id != P0->id || !same_geometry(fs.geo, tp)) && (rc = stream_reextract(h, P0, tp, s))) return rc;
+  HIPCHK(h, hipMemcpyAsync(fs.keep, frame, frame_bytes(fs.pix, fs.H, fs.W), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  // option "scene_cut": a cut is film_stream_reset followed by this push - the frame starts a new scene in slot 0, extraction only
+  const int scene_k = h->opt_scene_cut;
+  bool cut = false;
+  if (scene_k > 0 && (rc = stream_scene_cut(h, s, scene_k, &cut))) return rc;
+  const bool primed = fs.primed && !cut;
+  const int slot = primed ? 1 - fs.slot : 0;
+  Plan* P = nullptr;
+  if ((rc = plan_orientation(h, P0, 1 - slot, slot, true, &P))) return rc;
+  HIPCHK(h, stream_cut(fs.keep, fs.pix, tp, P, slot, s));
+  int made = 0;
+  if (!primed) {
+    if ((rc = run_plan(h, P, s, P->n_extract))) return rc;
+  } else {
+    // one pair run per generated frame, in the order of stream_schedule (times = 1: the one pair of the two inputs)
+    AppendProfile append{h};
+    const StreamFrames fr(fs.pix, fs.H, fs.W, fs.times);
+    for (const StreamStep& t : stream_schedule(fs.times, slot)) {
+      Plan* Q = nullptr;
+      if ((rc = plan_orientation(h, P0, t.left, t.right, t.extract != 0, &Q)) || (rc = run_plan(h, Q, s))) return rc;
+      h->profile_append = true;
+      if ((rc = stream_deliver(h, Q, tp, fr, fr.place(fs, mid, host, (size_t)t.index - 1), t.feed, s))) return rc;
+      ++made;
+    }
+  }
+  if (host) HIPCHK(h, hipStreamSynchronize(s));
+  *produced = made;
+  fs.primed = true; fs.slot = slot; fs.plan_id = P0->id; fs.geo = tp;
+  fs.hist_valid = scene_k > 0; fs.cut = cut ? 1 : 0;
+  unprime.armed = false;
+  return FILM_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // frame_kernels.hip -- frame I/O: the kernels that move pixels between the caller's frames and the tiles a plan works on (gfx950, wave64).
-// None of them is an op of a plan; film_engine.cpp calls the four launchers at the end of this file and film_launch_frame_histogram, which stands beside its kernel.
+// None of them is an op of a plan; film_engine.cpp and film_stream.cpp call the four launchers at the end of this file and film_launch_frame_histogram, which stands beside its kernel.
 //
 //   frame_to_tiles<OVERLAP>             _pad_to_align + image_to_patches, float32 frames    eval/interpolator.py:30-63, :66-104
 //   frame_u8_to_tiles<OVERLAP>          the same on 8-bit RGB frames: float32(byte) / 255   eval/util.py read_image

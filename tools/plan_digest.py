@@ -4,7 +4,9 @@ csrc/film_planner.cpp that must leave every plan as it is.  Plan-only handles (d
 pins nothing - run it on the library before and after the change and `diff` the two outputs.
 
   FILM_HIP_LIB=<libfilm_hip*.so> python tools/plan_digest.py            one line per record: "<config> <options> <call> <sha1>", the sha1
-                                                                          of the JSON text film_plan_json / film_sequence_plan_json returned,
+                                                                          of the JSON text film_plan_json / film_sequence_plan_json /
+                                                                          film_stream_plan_json / film_stream_pair_plan_json /
+                                                                          film_stream_schedule_json returned,
                                                                           or of "error <code>: <message>" for a refused call or option value;
                                                                           then "records <n>" and "digest <sha1 over all lines>"
   FILM_HIP_LIB=... python tools/plan_digest.py --splitk                  instead: the conv ops with ksplit > 1 of the default plans of the
@@ -15,7 +17,9 @@ The library comes from FILM_HIP_LIB like for every other tool (film_hip/engine.p
                                                                           families - most of the family rules only show there)
 Option grid: every film_set_option key that drops the cached plans (kOptions in csrc/film_engine.cpp), one at a time over its whole
 range - for the two pixel thresholds, both sides of every level size the planner can compare them with in these shapes - plus the
-combinations the rules couple.  About 6 000 records, well under a minute on a host-only build."""
+combinations the rules couple.  Per setting also the stream plans (STREAM_SHAPES): both orientations of the two-slot plan, every pair run
+(left, right, extract) the schedules of "stream_times" = 1 .. 3 list, the schedules themselves and one refused argument set.  About
+42 000 records (48 000 with the opt-in families), a few minutes on a host-only build."""
 import ctypes
 import hashlib
 import itertools
@@ -36,6 +40,8 @@ PAIR_SHAPES = {
     'TINY': [(1, 32, 32), (2, 32, 48), (1, 64, 40), (1, 64, 64), (2, 64, 96), (1, 256, 256), (1, 36, 32)],   # (the last: refused)
 }
 SEQUENCE_SHAPES = [(3, 1, 256, 448), (2, 4, 576, 960)]      # (pairs, tiles, H, W)
+STREAM_SHAPES = {'PUBLISHED': [(1, 256, 256), (4, 576, 960)], 'TINY': [(1, 32, 48), (2, 32, 48), (1, 64, 96), (2, 64, 96)]}   # (tiles, H, W)
+STREAM_TIMES = (1, 2, 3)
 
 # pixels per image of the pyramid levels of the shapes above that lie near the defaults (256 / 1536): "px >= option" flips between t and t + 1
 LEVEL_PX = [64, 192, 256, 448, 540, 768, 1024, 1536, 1792, 2160, 4096]
@@ -96,6 +102,27 @@ def engine_with(opt, setting):
     return eng, None
 
 
+def stream_records(eng, head):
+    """The stream plans of one engine: see the module text."""
+    lib = eng._lib
+    runs = {}       # times -> the (left, right, extract) of every pair run its two schedules list, in their order
+    for times in STREAM_TIMES:
+        for slot in (0, 1):
+            text = call_text(eng, lib.film_stream_schedule_json, times, slot)
+            yield f'{head} stream_schedule({times},{slot})', text
+            for step in json.loads(text)['steps']:
+                runs.setdefault(times, {})[(step['left'], step['right'], step['extract'])] = None
+    for t, h, w in STREAM_SHAPES[head.split()[0]]:
+        for slot in (0, 1):
+            yield f'{head} stream_plan({t},{h},{w},{slot})', call_text(eng, lib.film_stream_plan_json, t, h, w, slot)
+        for times in STREAM_TIMES:
+            for left, right, extract in runs[times]:
+                yield (f'{head} stream_pair_plan({t},{h},{w},{times},{left},{right},{extract})',
+                       call_text(eng, lib.film_stream_pair_plan_json, t, h, w, times, left, right, extract))
+    t, h, w = STREAM_SHAPES[head.split()[0]][0]
+    yield f'{head} stream_pair_plan({t},{h},{w},1,1,1,1)', call_text(eng, lib.film_stream_pair_plan_json, t, h, w, 1, 1, 1, 1)   # (refused: left == right)
+
+
 def records():
     from film_hip import options as O
     for cfg in ('PUBLISHED', 'TINY'):
@@ -109,6 +136,7 @@ def records():
                 yield f'{cfg} {name} plan({b},{h},{w})', call_text(eng, eng._lib.film_plan_json, b, h, w)
             for n, t, h, w in SEQUENCE_SHAPES if cfg == 'PUBLISHED' else [(2, 1, 64, 40), (2, 2, 32, 48)]:
                 yield f'{cfg} {name} sequence_plan({n},{t},{h},{w})', call_text(eng, eng._lib.film_sequence_plan_json, n, t, h, w)
+            yield from stream_records(eng, f'{cfg} {name}')
             eng.close()
 
 
