@@ -192,6 +192,8 @@ struct FilmStream {
   unsigned char* result8 = nullptr; // ... quantised (RGB bytes or a 4:2:0 frame, 8-bit or 10-bit), of a host push that is not float32
   int times = 1;                    // option "stream_times" when the stream was opened: a primed push writes 2^times - 1 frames; `result` (float32
                                     // streams) and `result8` hold that many frames, so that a host push downloads them behind one wait
+  uint64_t mask = 1;                // film_stream_select: bit i - 1 = position i of a primed push is wanted; film_stream_open selects all
+                                    // 2^times - 1, and neither film_stream_reset nor a scene cut changes it
   bool primed = false;              // `keep` holds a frame
   int slot = 0;                     // the half of the plan's frame buffers it was extracted into ...
   uint64_t plan_id = 0;             // ... of this plan (Plan::id) ...

@@ -32,25 +32,35 @@ hipError_t stream_cut(const void* frame, int pix, TileMapParams tp, const Plan* 
 }
 
 // The steps of ONE primed push of a "stream_times" = T stream whose input frame lands in slot `slot` (0 / 1; the frame before waits in the
-// other one), in execution order - the reference's recursion (eval/util.py, _recursive_generator) depth first.  A step runs the pair
-// (frame in slot `left`, frame in slot `right`) - with `extract`, behind the extraction of the right frame, which no step has extracted
-// before - and yields the frame at position `index` of the 2^T - 1 between the two inputs (1-based, temporal order), a depth-`depth`
-// mid-frame.  feed >= 0: the result is cut, as float32, into slot `feed` = 1 + depth, where its two children find it: the left child
-// (left, feed) extracts it, the right child (feed, right) reads what the left one extracted.  The deepest mids are fed nowhere.
-struct StreamStep { int left, right, extract, index, depth, feed; };
-void stream_steps(int T, int left, int right, bool extract, int depth, int index, std::vector<StreamStep>* v) {
-  const int feed = depth < T ? 1 + depth : -1;
-  v->push_back({left, right, extract ? 1 : 0, index, depth, feed});
-  if (feed < 0) return;
-  const int half = 1 << (T - depth - 1);
-  stream_steps(T, left, feed, true, depth + 1, index - half, v);
-  stream_steps(T, feed, right, false, depth + 1, index + half, v);
+// other one), in execution order - the reference's recursion (eval/util.py, _recursive_generator) depth first, restricted to C: the
+// positions selected by `mask` (bit i - 1: position i; film_stream_select) and their ancestors.  A pair step runs the pair (frame in slot
+// `left`, frame in slot `right`) - with `extract`, behind the extraction of the right frame, which no step has extracted before - and
+// yields the frame at position `index` of the 2^T - 1 between the two inputs (1-based, temporal order), a depth-`depth` mid-frame; `deliver`:
+// the position is selected, the frame goes to the caller.  feed >= 0: the result has a child in C and is cut, as float32, into slot
+// `feed` = 1 + depth, where its children find it: the left child (left, feed) extracts it, the right child (feed, right) reads what the
+// left one extracted.  When only the right child is in C, nobody has extracted the fed-back frame: a step that is no pair (`pair` = false)
+// stands in front of the right child - the left child's orientation run to n_extract, like a first push; its `index` / `depth` are those
+// of the frame it extracts.  An empty selection leaves one such step, for the pushed frame (position 2^T, depth 0).
+struct StreamStep { int left, right, extract, index, depth, feed; bool deliver, pair; };
+uint64_t full_mask(int T) { return ((uint64_t)1 << ((1 << T) - 1)) - 1; }
+// the positions index - half + 1 .. index + half - 1: the subtree of the mid-frame at `index` whose parents are `half` positions away
+uint64_t subtree_mask(int index, int half) { return (((uint64_t)1 << (2 * half - 1)) - 1) << (index - half); }
+void stream_steps(int T, uint64_t mask, int left, int right, bool extract, int depth, int index, std::vector<StreamStep>* v) {
+  const int half = depth < T ? 1 << (T - depth - 1) : 0;   // of the children (0: the deepest mids have none)
+  const bool l = half && (mask & subtree_mask(index - half, half)), r = half && (mask & subtree_mask(index + half, half));
+  const int feed = l || r ? 1 + depth : -1;
+  v->push_back({left, right, extract ? 1 : 0, index, depth, feed, (mask >> (index - 1) & 1) != 0, true});
+  if (l) stream_steps(T, mask, left, feed, true, depth + 1, index - half, v);
+  else if (r) v->push_back({left, feed, 1, index, depth, -1, false, false});
+  if (r) stream_steps(T, mask, feed, right, false, depth + 1, index + half, v);
 }
-std::vector<StreamStep> stream_schedule(int T, int slot) {
+std::vector<StreamStep> stream_schedule(int T, int slot, uint64_t mask) {
   std::vector<StreamStep> v;
-  stream_steps(T, 1 - slot, slot, true, 1, 1 << (T - 1), &v);
+  if (mask) stream_steps(T, mask, 1 - slot, slot, true, 1, 1 << (T - 1), &v);
+  else v.push_back({1 - slot, slot, 1, 1 << T, 0, -1, false, false});
   return v;
 }
+std::vector<StreamStep> stream_schedule(int T, int slot) { return stream_schedule(T, slot, full_mask(T)); }
 
 // Where the n = 2^times - 1 frames of a primed push live.  A host push downloads each frame as soon as it is there and waits once, so each
 // has a place of its own on the device: a float32 stream's in fs.result; every other stream's - whose float32 frame is only joined,
@@ -71,6 +81,9 @@ struct StreamFrames {
     if (f32) return {host ? fs.result + k * nv : (float*)out, nullptr, host ? out : nullptr};
     return {fs.result, host ? (void*)(fs.result8 + k * fb) : out, host ? out : nullptr};
   }
+  // of a frame that is only fed back (film_stream_select: an ancestor that is not selected): joined in the stream's own fs.result - the
+  // copies and cuts of a push are ordered on one stream - never quantised, downloaded or written to `mid`
+  static Place fed_only(const FilmStream& fs) { return {fs.result, nullptr, nullptr}; }
 };
 
 // Whatever fails in a push behind this guard: the stream forgets its carried frame (as after film_stream_reset), and both streams are
@@ -132,6 +145,36 @@ int stream_deliver(film_t* h, const Plan* Q, const TileMapParams& tp, const Stre
   return FILM_OK;
 }
 
+int check_schedule_query(film_t* h, int times, int slot) {
+  if (times < 1 || times > kMaxStreamTimes) return fail(h, FILM_ERR_INVALID, "times must be 1 .. 6 (option \"stream_times\")");
+  if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the slot the pushed frame fills)");
+  return FILM_OK;
+}
+int check_mask(film_t* h, int times, uint64_t mask) {
+  if (mask & ~full_mask(times))
+    return fail(h, FILM_ERR_INVALID, "mask has a bit at or above %d: a stream_times = %d push has positions 1 .. %d (bit i - 1: position i)",
+                (1 << times) - 1, times, (1 << times) - 1);
+  return FILM_OK;
+}
+// film_stream_schedule_json (mask == nullptr: the full push, the keys it always had) / film_stream_select_schedule_json
+std::string schedule_json(int times, int slot, const uint64_t* mask) {
+  const std::vector<StreamStep> steps = mask ? stream_schedule(times, slot, *mask) : stream_schedule(times, slot);
+  const int produced = mask ? __builtin_popcountll(*mask) : (1 << times) - 1;
+  std::ostringstream o;
+  o << "{\"times\":" << times << ",\"slot\":" << slot << ",\"slots\":" << times + 1 << ",\"produced\":" << produced;
+  if (mask) o << ",\"mask\":" << *mask;
+  o << ",\"steps\":[";
+  for (size_t i = 0; i < steps.size(); ++i) {
+    const StreamStep& t = steps[i];
+    o << (i ? "," : "") << "{\"left\":" << t.left << ",\"right\":" << t.right << ",\"extract\":" << t.extract << ",\"index\":" << t.index
+      << ",\"depth\":" << t.depth << ",\"feed\":" << t.feed;
+    if (mask) o << ",\"deliver\":" << (t.deliver ? 1 : 0) << ",\"run\":\"" << (t.pair ? "pair" : "extract") << "\"";
+    o << "}";
+  }
+  o << "]}";
+  return o.str();
+}
+
 }  // namespace
 
 extern "C" {
@@ -164,18 +207,26 @@ int film_stream_pair_plan_json(film_t* h, int tiles, int H, int W, int times, in
 
 int film_stream_schedule_json(film_t* h, int times, int slot, char* buf, int64_t cap, int64_t* needed) {
   if (!h) return FILM_ERR_INVALID;
-  if (times < 1 || times > kMaxStreamTimes) return fail(h, FILM_ERR_INVALID, "times must be 1 .. 6 (option \"stream_times\")");
-  if (slot != 0 && slot != 1) return fail(h, FILM_ERR_INVALID, "slot must be 0 or 1 (the slot the pushed frame fills)");
-  std::ostringstream o;
-  o << "{\"times\":" << times << ",\"slot\":" << slot << ",\"slots\":" << times + 1 << ",\"produced\":" << (1 << times) - 1 << ",\"steps\":[";
-  const std::vector<StreamStep> steps = stream_schedule(times, slot);
-  for (size_t i = 0; i < steps.size(); ++i) {
-    const StreamStep& t = steps[i];
-    o << (i ? "," : "") << "{\"left\":" << t.left << ",\"right\":" << t.right << ",\"extract\":" << t.extract << ",\"index\":" << t.index
-      << ",\"depth\":" << t.depth << ",\"feed\":" << t.feed << "}";
-  }
-  o << "]}";
-  return copy_out_string(h, o.str(), buf, cap, needed);
+  int rc = check_schedule_query(h, times, slot);
+  if (rc) return rc;
+  return copy_out_string(h, schedule_json(times, slot, nullptr), buf, cap, needed);
+}
+
+int film_stream_select_schedule_json(film_t* h, int times, int slot, uint64_t mask, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  int rc = check_schedule_query(h, times, slot);
+  if (rc == FILM_OK) rc = check_mask(h, times, mask);
+  if (rc) return rc;
+  return copy_out_string(h, schedule_json(times, slot, &mask), buf, cap, needed);
+}
+
+int film_stream_select(film_t* h, uint64_t mask) {
+  if (!h) return FILM_ERR_INVALID;
+  if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  int rc = check_mask(h, h->fs.times, mask);
+  if (rc) return rc;
+  h->fs.mask = mask;
+  return FILM_OK;
 }
 
 int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix) {
@@ -215,6 +266,7 @@ int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_
   }
   fs.open = true;
   fs.times = times;
+  fs.mask = full_mask(times);
   fs.H = H; fs.W = W; fs.align = align; fs.block_h = block_h; fs.block_w = block_w; fs.pix = pix;
   return FILM_OK;
 }
@@ -257,7 +309,7 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
   Unprime unprime{h, s, true};   // (whatever fails from here on)
   if (produced) *produced = 0;
   fs.cut_distance = -1; fs.cut = 0;
-  if (!frame || !produced || (fs.primed && !mid)) return fail(h, FILM_ERR_INVALID, "NULL argument");
+  if (!frame || !produced || (fs.primed && fs.mask && !mid)) return fail(h, FILM_ERR_INVALID, "NULL argument");
   if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
   HIPCHK(h, hipSetDevice(h->device));
   TileMapParams tp{};
@@ -284,15 +336,18 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
   if (!primed) {
     if ((rc = run_plan(h, P, s, P->n_extract))) return rc;
   } else {
-    // one pair run per generated frame, in the order of stream_schedule (times = 1: the one pair of the two inputs)
+    // one pair run per member of the selection and its ancestors, in the order of stream_schedule (times = 1: the one pair of the two
+    // inputs); the selected frames are packed into `mid` in temporal order
     AppendProfile append{h};
     const StreamFrames fr(fs.pix, fs.H, fs.W, fs.times);
-    for (const StreamStep& t : stream_schedule(fs.times, slot)) {
+    for (const StreamStep& t : stream_schedule(fs.times, slot, fs.mask)) {
       Plan* Q = nullptr;
-      if ((rc = plan_orientation(h, P0, t.left, t.right, t.extract != 0, &Q)) || (rc = run_plan(h, Q, s))) return rc;
+      if ((rc = plan_orientation(h, P0, t.left, t.right, t.extract != 0, &Q)) || (rc = run_plan(h, Q, s, t.pair ? SIZE_MAX : Q->n_extract))) return rc;
       h->profile_append = true;
-      if ((rc = stream_deliver(h, Q, tp, fr, fr.place(fs, mid, host, (size_t)t.index - 1), t.feed, s))) return rc;
-      ++made;
+      if (!t.pair) continue;
+      const size_t k = (size_t)__builtin_popcountll(fs.mask & (((uint64_t)1 << (t.index - 1)) - 1));   // selected positions before this one
+      if ((rc = stream_deliver(h, Q, tp, fr, t.deliver ? fr.place(fs, mid, host, k) : StreamFrames::fed_only(fs), t.feed, s))) return rc;
+      made += t.deliver;
     }
   }
   if (host) HIPCHK(h, hipStreamSynchronize(s));

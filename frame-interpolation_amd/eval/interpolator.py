@@ -182,7 +182,9 @@ class Interpolator:
     (include/film_hip.h) before the stream opens - a push that the histogram rule calls a scene cut then returns None like a first push,
     FilmStream.cut_info() tells why; an engine option like block_overlap, so it stays set; 0 (default) leaves the engine as it is.
     times (1 .. 6): a primed push returns the [2^times - 1, ...] frames of the times_to_interpolate recursion between the two frames, each
-    bit-identical to self() on its float32 parents (engine option "stream_times", set for this stream only).
+    bit-identical to self() on its float32 parents (engine option "stream_times", set for this stream only).  The stream's
+    select(positions) narrows a primed push to some of those 2^times - 1 positions - only they and their ancestors are run - which is how
+    eval.video_cli --fps converts to a rate that is no power of two (film_hip/retime.py).
     One stream per Interpolator at a time."""
     if self._align is not None:
       assert self._align > 0, 'align must be a positive number.'

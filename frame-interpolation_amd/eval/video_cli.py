@@ -15,13 +15,19 @@ of consecutive frames' sample histograms, in permille of its maximum): across a 
 cut is written again in their place (a frame hold: once, or 2^T - 1 times), so the output keeps its frame count at a uniform rate.  No value is recommended:
 the detector's hit and miss rates on real footage are unmeasured.
 
+--fps N[:D] converts to any frame rate up to 2^T times the input's (24 -> 60, 25 -> 60, 24000/1001 -> 60000/1001, 24 -> 30, 50 -> 60):
+every output instant is snapped to the grid of 2^-T input intervals (film_hip/retime.py; T = --times_to_interpolate, 3 or 4 for such
+rates), an output that lands on an input frame is that frame, and each push computes only the positions its interval needs and their
+ancestors in the recursion (FilmStream.select) - 24 -> 60 at T = 3 makes four pair runs per input interval where a full push makes seven.
+Input frames no output lands on are not written; the snap errors and the pair runs made are reported on stderr.
+
 The output header keeps the input's tokens with the frame rate (F) doubled (multiplied by 2^T).  What is read: film_hip/y4m.py (8-bit and 10-bit 4:2:0, progressive).
 """
 import argparse
 import sys
 from typing import Optional
 
-from film_hip import y4m
+from film_hip import retime, y4m
 
 from . import interpolator as interpolator_lib
 
@@ -46,7 +52,12 @@ def build_parser() -> argparse.ArgumentParser:
                          'before the cut is held instead of a mid-frame.  0 (default): off.  No value is recommended (unmeasured on footage).')
     ap.add_argument('--times_to_interpolate', type=int, default=1, metavar='T',
                     help='1 .. 6: multiply the frame rate by 2^T - 2^T - 1 frames between every two input frames, the recursion of the '
-                         'reference.  1 (default): double it.')
+                         'reference.  1 (default): double it.  With --fps: the depth of the timing grid, 2^-T of an input interval - 3 or 4 '
+                         'is what a conversion that is no power of two wants (a snap error of at most 1/16 or 1/32 of an input interval).')
+    ap.add_argument('--fps', default=None, metavar='N[:D]',
+                    help='Convert to this frame rate (N, N:D or N/D, e.g. 60 or 60000:1001) instead of multiplying the rate: every output '
+                         'frame is the input frame or mid-frame nearest to its instant on the grid of --times_to_interpolate, and only those '
+                         'mid-frames are computed.  At most 2^T times the input rate; the input header must name its rate (an F token).')
     return ap
 
 
@@ -82,20 +93,100 @@ def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', ful
     return writer.frames_written
 
 
+def convert_frame_rate(it, reader: y4m.Y4MReader, out, rate_out, matrix: str = 'bt709', full_range: Optional[bool] = None,
+                       scene_cut: int = 0, cuts: Optional[list] = None, times: int = 1, stats: Optional[dict] = None) -> int:
+    """--fps: streams reader's frames through a stream of `it` opened as double_frame_rate opens it and writes the video at rate_out =
+    (num, den) to `out`; returns the number of frames written.  film_hip.retime snaps every output instant to the grid of 2^-times input
+    intervals: an output that lands on an input frame is that frame verbatim (an input frame no output lands on is not written), every
+    other one is a position of the push of the next input frame, and each push selects just its positions (FilmStream.select), so only
+    they and their ancestors in the recursion are computed.  A scene cut (scene_cut > 0) holds the previous input frame once per position
+    selected for that interval.  rate_out = the input rate times 2^times writes what double_frame_rate(times=times) writes.
+    stats (a dict) receives 'snap_max' and 'snap_mean' (the snap error of the written frames, in input intervals), 'pair_runs' (made)
+    and 'pair_runs_full' (what full pushes would have made).  ValueError: no F token in the header, or what retime.Retime refuses."""
+    times = int(times)
+    if reader.rate is None:
+        raise ValueError('--fps needs the frame rate of the input: its header has no F token')
+    rt = retime.Retime(reader.rate, rate_out, times)
+    per_push = (1 << times) - 1
+    dyadic = rt.p << times == rt.q         # (the header of --times_to_interpolate, which multiplies the numerator as it stands)
+    full = reader.full_range if full_range is None else bool(full_range)
+    writer = y4m.Y4MWriter(out, y4m.multiply_rate(reader.tokens, 1 << times) if dyadic else y4m.set_rate(reader.tokens, rate_out))
+    err_max = err_sum = runs = pushes = 0
+
+    def snapped(j0: int, count: int):
+        nonlocal err_max, err_sum
+        for j in range(j0, j0 + count):
+            e = abs(rt.error(j)[0])
+            err_max, err_sum = max(err_max, e), err_sum + e
+
+    with it.open_stream(reader.height, reader.width, pix='i010' if getattr(reader, 'depth', 8) == 10 else 'i420', matrix=matrix, full_range=full,
+                        **({'scene_cut': int(scene_cut)} if scene_cut else {}), **({'times': times} if times != 1 else {})) as st:
+        prev = None
+        selected = pending = tuple(range(1, per_push + 1))
+        intervals = rt.intervals()
+        for i, frame in enumerate(reader):
+            if i:
+                if pending != selected:
+                    st.select(pending)
+                    selected = pending
+                mid = st.push(frame)
+                pushes += 1
+                if mid is not None:
+                    for m in (mid,) if times == 1 else mid:
+                        writer.write(m)
+                    runs += retime.push_cost(times, pending)[0]
+                elif scene_cut and (pending or st.cut_info()[2]):
+                    for _ in pending:
+                        writer.write(prev)      # a frame hold across the cut
+                    if cuts is not None:
+                        cuts.append(i)
+                snapped(iv.j + iv.write, len(pending))
+            else:
+                st.push(frame)
+            iv = next(intervals)                # (interval i: is input frame i written, and what the NEXT push selects)
+            if iv.write:
+                writer.write(frame)
+                snapped(iv.j, 1)
+            pending = iv.positions
+            prev = frame if scene_cut else None
+    if stats is not None:
+        den = rt.error(0)[1]
+        n = writer.frames_written
+        stats.update(snap_max=err_max / den, snap_mean=err_sum / den / n if n else 0.0, pair_runs=runs, pair_runs_full=pushes * per_push)
+    return writer.frames_written
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if not 1 <= args.times_to_interpolate <= 6:
         raise SystemExit('--times_to_interpolate must be 1 .. 6')
+    rate_out = None
+    if args.fps is not None:
+        try:
+            rate_out = retime.parse_rate(args.fps)
+        except ValueError as e:
+            raise SystemExit(f'--fps: {e}')
     fin = sys.stdin.buffer if args.input == '-' else open(args.input, 'rb')
     try:
         reader = y4m.Y4MReader(fin, depths=(8, 10))       # (the header's refusals come before the model is loaded)
+        if rate_out is not None:                          # (and those of the conversion)
+            if reader.rate is None:
+                raise SystemExit('--fps needs the frame rate of the input: its header has no F token')
+            try:
+                retime.Retime(reader.rate, rate_out, args.times_to_interpolate)
+            except ValueError as e:
+                raise SystemExit(f'--fps: {e}')
         overlap = (args.block_overlap_height, args.block_overlap_width)
         it = interpolator_lib.Interpolator(args.model_path, args.align, [args.block_height, args.block_width],
                                            **({'block_overlap': overlap} if any(overlap) else {}))
         fout = sys.stdout.buffer if args.output == '-' else open(args.output, 'wb')
         try:
-            cuts = []
-            n = double_frame_rate(it, reader, fout, args.matrix, args.full_range, args.scene_cut, cuts, args.times_to_interpolate)
+            cuts, stats = [], {}
+            if rate_out is None:
+                n = double_frame_rate(it, reader, fout, args.matrix, args.full_range, args.scene_cut, cuts, args.times_to_interpolate)
+            else:
+                n = convert_frame_rate(it, reader, fout, rate_out, args.matrix, args.full_range, args.scene_cut, cuts,
+                                       args.times_to_interpolate, stats)
             fout.flush()
         finally:
             if fout is not sys.stdout.buffer:
@@ -105,6 +196,11 @@ def main(argv=None) -> int:
             fin.close()
     print(f'{args.input}: {reader.frames_read} frames in, {n} frames out' +
           (f', {len(cuts)} scene cuts' + (f' (the first at input frame {cuts[0]})' if cuts else '') if args.scene_cut else ''), file=sys.stderr)
+    if stats:
+        num, den = reader.rate
+        print(f'{num}:{den} -> {rate_out[0]}:{rate_out[1]} frames per second on a grid of 1/{1 << args.times_to_interpolate} input interval: '
+              f'snap error max {stats["snap_max"]:.4f} mean {stats["snap_mean"]:.4f} input intervals; {stats["pair_runs"]} pair runs '
+              f'against {stats["pair_runs_full"]} of full pushes ({(1 << args.times_to_interpolate) - 1} per interval)', file=sys.stderr)
     return n
 
 

@@ -75,7 +75,7 @@ EXPORTED_SYMBOLS = (
     'film_debug_arena', 'film_debug_run_op', 'film_debug_tile_map',
     'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json',
     'film_to_yuv420', 'film_debug_yuv_cut', 'film_frame_histogram', 'film_stream_cut_info',
-    'film_stream_pair_plan_json', 'film_stream_schedule_json')
+    'film_stream_pair_plan_json', 'film_stream_schedule_json', 'film_stream_select', 'film_stream_select_schedule_json')
 
 _lib = None
 
@@ -154,6 +154,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_frame_histogram.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
     lib.film_stream_pair_plan_json.argtypes = [vp] + [ctypes.c_int] * 7 + [ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_stream_schedule_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
+    lib.film_stream_select.argtypes = [vp, ctypes.c_uint64]
+    lib.film_stream_select_schedule_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_stream_cut_info.argtypes = [vp, i64p, i64p, ctypes.POINTER(ctypes.c_int)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
@@ -204,6 +206,19 @@ def frame_histogram_device(ptr: int, h: int, w: int, hist_ptr: int, pix: str = '
         raise FilmError(rc, 'film_frame_histogram failed')
 
 
+def selection_mask(times: int, positions) -> int:
+    """film_stream_select's mask of 1-based positions of a "stream_times" = times push (bit i - 1: position i); None: all 2^times - 1."""
+    n = (1 << int(times)) - 1
+    if positions is None:
+        return (1 << n) - 1
+    mask = 0
+    for i in positions:
+        if int(i) != i or not 1 <= i <= n:
+            raise ValueError(f'a position of a times = {times} push is an integer 1 .. {n}, got {i!r}')
+        mask |= 1 << (int(i) - 1)
+    return mask
+
+
 class FilmStream:
     """One open frame stream of an engine (film_stream_*; FilmEngine.open_stream): push() one frame at a time and get the mid-frame
     between it and the frame pushed before - bit-identical to interpolate_frames(previous, frame) - with one feature extraction per
@@ -216,6 +231,8 @@ class FilmStream:
     times = T > 1 (FilmEngine.open_stream(times=...); engine option "stream_times", read when the stream opens): a primed push returns
     the 2^T - 1 frames of the reference's times_to_interpolate = T recursion between the two frames, [2^T - 1, *shape] in temporal
     order - every one bit-identical to interpolate_frames on its float32 parents, quantised (if at all) only on the way out.
+    select(positions) narrows a primed push to some of those positions (a frame-rate conversion that is no power of two:
+    film_hip/retime.py): only they and their ancestors in the recursion are run, and the push returns [len(selection), *shape].
     One stream per engine at a time; use it as a context manager or close() it."""
 
     def __init__(self, engine: 'FilmEngine', h: int, w: int, align: Optional[int], block_shape, pix: str, matrix: str = 'bt709',
@@ -223,7 +240,8 @@ class FilmStream:
         self._code = pix_code(pix, matrix, full_range)
         self._eng = engine
         self.times = int(times)                  # what the engine option said when the stream was opened
-        self.per_push = (1 << self.times) - 1    # frames of a primed push
+        self.per_push = (1 << self.times) - 1    # frames of a primed push with every position selected
+        self.selection = tuple(range(1, self.per_push + 1))   # select(): the 1-based positions a primed push returns, ascending
         self.shape = (int(h) * 3 // 2, int(w)) if pix in YUV420 else (int(h), int(w), 3)
         self.pix = pix
         self.dtype = PIX[pix][1]
@@ -236,12 +254,13 @@ class FilmStream:
         (a new array, or `out`: a writable C-contiguous array of the frame's shape and dtype).  None too for a frame that option
         "scene_cut" found to start a new scene (`out` is then left as it was).  times > 1: the result and `out` are
         [2^times - 1, *frame shape] - a float32 caller does well to reuse one `out`: at 1080p with times = 2 a push into the fresh
-        75 MB array measured 3 ms per frame slower than into a reused one (profiles/stream_recursion_bench.log)."""
+        75 MB array measured 3 ms per frame slower than into a reused one (profiles/stream_recursion_bench.log).  After select():
+        [len(selection), *frame shape], and None whenever nothing was produced - an empty selection included."""
         a = np.asarray(frame)
         if a.dtype != self.dtype or a.shape != self.shape:
             raise ValueError(f'expected a {np.dtype(self.dtype).name} array of shape {self.shape}, got {a.dtype} {a.shape}')
         a = np.ascontiguousarray(a)
-        oshape = self.shape if self.times == 1 else (self.per_push,) + self.shape
+        oshape = self.shape if self.times == 1 else (len(self.selection),) + self.shape
         if out is None:
             out = np.empty(oshape, self.dtype)
         elif out.dtype != self.dtype or out.shape != oshape or not out.flags['C_CONTIGUOUS'] or not out.flags['WRITEABLE']:
@@ -256,15 +275,24 @@ class FilmStream:
         """Device-resident push: raw device pointers to one frame of the stream's pixel type (ptr_out: to 2^times - 1 of them),
         asynchronous on `stream`.  times == 1: returns whether ptr_out receives a mid-frame (False for the first frame after open /
         reset; ptr_out may then be 0 - and for a scene cut found by option "scene_cut", which leaves ptr_out untouched).
-        times > 1: returns the number of frames written, 2^times - 1 or 0."""
+        times > 1: returns the number of frames written, 2^times - 1 (after select(): len(selection), which ptr_out holds) or 0."""
         produced = ctypes.c_int(0)
         eng = self._eng
         eng._check(eng._lib.film_stream_push(eng._h, ctypes.c_void_p(ptr_in), ctypes.c_void_p(ptr_out) if ptr_out else None,
                                              ctypes.byref(produced), FILM_MEM_DEVICE, ctypes.c_void_p(stream) if stream else None))
         return bool(produced.value) if self.times == 1 else produced.value
 
+    def select(self, positions=None) -> None:
+        """film_stream_select: from the next push on a primed push returns only the frames at `positions` - an iterable of 1-based
+        positions 1 .. 2^times - 1 (duplicates count once), or None for all - in temporal order, each bit-identical to that frame of a
+        full push; only they and their ancestors in the recursion are run (FilmEngine.stream_schedule(times, slot, select=...)).  The
+        selection holds until it is changed; reset() and scene cuts keep it."""
+        mask = selection_mask(self.times, positions)
+        self._eng._check(self._eng._lib.film_stream_select(self._eng._h, mask))
+        self.selection = tuple(i for i in range(1, self.per_push + 1) if mask >> (i - 1) & 1)
+
     def reset(self) -> None:
-        """Forgets the carried frame (scene cut, seek): the next push produces nothing."""
+        """Forgets the carried frame (scene cut, seek): the next push produces nothing.  The selection stays."""
         self._eng._check(self._eng._lib.film_stream_reset(self._eng._h))
 
     def cut_info(self) -> Tuple[int, int, int]:
@@ -642,9 +670,15 @@ class FilmEngine:
         frame's extraction) of a stream of `tiles` h x w tiles opened with times (times + 1 frame slots)."""
         return self._json_call(self._lib.film_stream_pair_plan_json, int(tiles), int(h), int(w), int(times), int(left), int(right), int(bool(extract)))
 
-    def stream_schedule(self, times: int, slot: int) -> dict:
-        """film_stream_schedule_json: the pair runs of one primed push whose input lands in slot 0 / 1, in execution order."""
-        return self._json_call(self._lib.film_stream_schedule_json, int(times), int(slot))
+    def stream_schedule(self, times: int, slot: int, select=None) -> dict:
+        """film_stream_schedule_json: the pair runs of one primed push whose input lands in slot 0 / 1, in execution order.  select (an
+        iterable of 1-based positions, FilmStream.select): film_stream_select_schedule_json - the steps of the push with that selection,
+        each with "deliver" and "run" ('pair' | 'extract')."""
+        if select is None:
+            return self._json_call(self._lib.film_stream_schedule_json, int(times), int(slot))
+        if not 1 <= int(times) <= 6:
+            raise ValueError(f'times must be 1 .. 6, got {times}')
+        return self._json_call(self._lib.film_stream_select_schedule_json, int(times), int(slot), selection_mask(times, select))
 
     def tiling(self, h: int, w: int, align: Optional[int] = None, block_shape=None) -> dict:
         """film_tiling_json: the tile geometry of an h x w frame with the engine's current block_overlap options (resolved overlap,

@@ -1,0 +1,114 @@
+"""Frame-rate conversion by selected mid-frames: which positions of which push make a video of rate c/d out of one of rate a/b.
+
+A "stream_times" = T frame stream can produce, between two consecutive input frames, the frames at the 2^T - 1 instants i / 2^T of the
+interval (FilmStream.select picks some of them).  Output frame j of the converted video lies at u_j = j (a d) / (b c) input intervals
+from the first input frame; it is SNAPPED to the nearest instant of that grid, g_j = round(u_j 2^T), ties to the even grid index (the
+even index is the shallower, cheaper frame of the recursion).  Interval k = g_j >> T and position i = g_j & (2^T - 1): i = 0 is input
+frame k itself, i > 0 is position i of the push of input frame k + 1.  The snap error |g_j / 2^T - u_j| is at most 2^-(T + 1) input
+intervals, and the g_j are strictly increasing as long as the output rate is at most 2^T times the input rate, which is what Retime
+accepts.  Integers only: no rate is ever a float here.
+"""
+from math import gcd
+from typing import Iterable, Iterator, NamedTuple, Tuple
+
+
+def parse_rate(text: str) -> Tuple[int, int]:
+    """'60', '60000:1001' or '60000/1001' -> the reduced fraction (num, den); ValueError for anything else or a rate that is not positive."""
+    s = str(text).strip().replace('/', ':')
+    parts = s.split(':')
+    if not 1 <= len(parts) <= 2 or not all(p.isdigit() for p in parts):
+        raise ValueError(f'a frame rate is N, N:D or N/D with positive integers, got {text!r}')
+    num, den = int(parts[0]), int(parts[1]) if len(parts) == 2 else 1
+    if num < 1 or den < 1:
+        raise ValueError(f'a frame rate is N, N:D or N/D with positive integers, got {text!r}')
+    g = gcd(num, den)
+    return num // g, den // g
+
+
+def closure(times: int, positions: Iterable[int]) -> Tuple[int, ...]:
+    """C: the positions (1 .. 2^times - 1) and all their ancestors in the recursion tree, ascending - the pair runs of a push with that
+    selection.  The mid-frame at position i = (2 j + 1) h, h = 2^(times - depth), is a child of the one of i - h, i + h that is an odd
+    multiple of 2 h."""
+    n = 1 << times
+    c = set()
+    for i in positions:
+        if not 1 <= i < n:
+            raise ValueError(f'a position of a times = {times} push is 1 .. {n - 1}, got {i!r}')
+        while i not in c:
+            c.add(i)
+            h = i & -i
+            if 2 * h == n:
+                break                    # the root: its parents are the two input frames
+            i = i - h if (i - h) // (2 * h) & 1 else i + h
+    return tuple(sorted(c))
+
+
+def push_cost(times: int, positions: Iterable[int]) -> Tuple[int, int]:
+    """(pair runs, feature extractions) of a primed push with that selection: |C|, and 1 (the pushed frame) + the members of C that have
+    a child in C."""
+    c = set(closure(times, positions))
+    fed = sum(1 for i in c if (i & -i) > 1 and (i - (i & -i) // 2 in c or i + (i & -i) // 2 in c))
+    return len(c), 1 + fed
+
+
+class Interval(NamedTuple):
+    k: int                        # the interval between input frames k and k + 1
+    write: bool                   # an output lands on input frame k: it is written verbatim ...
+    positions: Tuple[int, ...]    # ... then these positions (ascending) of the push of input frame k + 1
+    j: int                        # the index of the first output of this interval (the input frame, or else the first position)
+
+
+class Retime:
+    """rate_in = (a, b), rate_out = (c, d), times = T: the timing of the conversion on the grid of 2^-T input intervals."""
+
+    def __init__(self, rate_in: Tuple[int, int], rate_out: Tuple[int, int], times: int):
+        (a, b), (c, d) = ((int(x) for x in r) for r in (rate_in, rate_out))
+        if min(a, b, c, d) < 1:
+            raise ValueError(f'frame rates are fractions of positive integers, got {rate_in!r} -> {rate_out!r}')
+        if not 1 <= int(times) <= 6:
+            raise ValueError(f'times must be 1 .. 6, got {times!r}')
+        self.times = int(times)
+        p, q = a * d, b * c           # u_j = j p / q
+        g = gcd(p, q)
+        self.p, self.q = p // g, q // g
+        if self.q > self.p << self.times:
+            raise ValueError(f'output rate {c}/{d} is more than 2^{self.times} = {1 << self.times} times the input rate {a}/{b}: two '
+                             f'outputs would land on one instant of the timing grid - use a deeper grid (times_to_interpolate)')
+
+    def grid(self, j: int) -> int:
+        """g_j: u_j 2^T rounded to the nearest integer, ties to even."""
+        g, r = divmod(j * self.p << self.times, self.q)
+        return g + (2 * r > self.q or (2 * r == self.q and g & 1))
+
+    def error(self, j: int) -> Tuple[int, int]:
+        """The snap error g_j / 2^T - u_j of output j in input intervals, as (numerator, denominator > 0)."""
+        return self.grid(j) * self.q - (j * self.p << self.times), self.q << self.times
+
+    def intervals(self) -> Iterator[Interval]:
+        """Interval 0, 1, 2, ... without end.  What a converter does with Interval k: write input frame k if `write`; when input frame k + 1
+        arrives, push it with `positions` selected and write what comes back.  The positions of the interval behind the last input frame
+        are dropped: those outputs lie past the end of the video."""
+        j, k, mask = 0, 0, (1 << self.times) - 1
+        while True:
+            j0, write, pos = j, False, []
+            while self.grid(j) >> self.times == k:
+                i = self.grid(j) & mask
+                if i:
+                    pos.append(i)
+                else:
+                    write = True
+                j += 1
+            yield Interval(k, write, tuple(pos), j0)
+            k += 1
+
+    def outputs(self, frames_in: int) -> int:
+        """The frames a video of frames_in input frames converts to: the outputs at or before the last input frame."""
+        if frames_in < 1:
+            return 0
+        last = (frames_in - 1) << self.times
+        j = last * self.q // (self.p << self.times)          # u_j <= frames_in - 1 < u_(j + 1); rounding moves at most one output across
+        while self.grid(j + 1) <= last:
+            j += 1
+        while j >= 0 and self.grid(j) > last:
+            j -= 1
+        return j + 1

@@ -94,9 +94,17 @@ class DeviceStream:
         assert frame.is_cuda and frame.dtype in self._dtypes and tuple(frame.shape) == self._stream.shape
         frame = frame.contiguous()
         st = self._stream
-        out = torch.empty_like(frame) if st.times == 1 else torch.empty((st.per_push,) + tuple(frame.shape), dtype=frame.dtype, device=frame.device)
+        out = torch.empty_like(frame) if st.times == 1 else torch.empty((len(st.selection),) + tuple(frame.shape), dtype=frame.dtype, device=frame.device)
         stream = torch.cuda.current_stream(frame.device).cuda_stream
         return out if st.push_device(frame.data_ptr(), out.data_ptr(), stream) else None
+
+    def select(self, positions=None) -> None:
+        """FilmStream.select: a primed push returns only the frames at these 1-based positions, [len(selection), *frame shape] (None: all)."""
+        self._stream.select(positions)
+
+    @property
+    def selection(self):
+        return self._stream.selection
 
     def reset(self) -> None:
         self._stream.reset()

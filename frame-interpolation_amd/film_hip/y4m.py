@@ -15,6 +15,7 @@ XCOLORRANGE=FULL marks full-range samples.
 """
 from __future__ import annotations
 
+import math
 from typing import BinaryIO, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -74,6 +75,18 @@ def multiply_rate(tokens: Sequence[str], k: int) -> List[str]:
 def double_rate(tokens: Sequence[str]) -> List[str]:
     """The header tokens with the numerator of the F token doubled (twice the frames in the same time); everything else as it is."""
     return multiply_rate(tokens, 2)
+
+
+def set_rate(tokens: Sequence[str], rate: Tuple[int, int]) -> List[str]:
+    """The header tokens with the F token naming the frame rate num / den, as the reduced fraction (appended when there is no F token);
+    everything else as it is."""
+    num, den = int(rate[0]), int(rate[1])
+    if num < 1 or den < 1:
+        raise ValueError(f'a frame rate is a fraction of positive integers, got {rate!r}')
+    g = math.gcd(num, den)
+    f = f'F{num // g}:{den // g}'
+    out = [f if t[:1] == 'F' and ':' in t else t for t in tokens]
+    return out if f in out else out + [f]
 
 
 def parse_header(line: bytes, depths: Sequence[int] = (8,)) -> Tuple[int, int, List[str]]:

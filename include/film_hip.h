@@ -211,7 +211,32 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *   film_stream_schedule_json  the pair runs of one primed push whose input frame lands in `slot` (0 / 1), in execution order:
  *                      {"times", "slot", "slots", "produced", "steps":[{"left", "right", "extract", "index", "depth", "feed"}, ...]} - the
  *                      step yields frame `index` (1 .. 2^T - 1) of `mid`, a depth-`depth` mid-frame, from the orientation (left, right,
- *                      extract), and cuts it into slot `feed` for its children (-1: it has none).  Works on plan-only handles. */
+ *                      extract), and cuts it into slot `feed` for its children (-1: it has none).  Works on plan-only handles.
+ * Selected mid-frames (film_stream_select).  A frame-rate conversion that is no power of two wants a few of the 2^T - 1 positions of each
+ * push, not all of them (film_hip/retime.py turns two rates into those choices).  A selection tells the open stream which ones:
+ *   film_stream_select  bit i - 1 of `mask` stands for position i (1 .. 2^T - 1, temporal order) of the stream's "stream_times" = T.  The
+ *                      selection belongs to the open stream: film_stream_open selects all 2^T - 1 positions, a selection holds for every
+ *                      later push until it is changed, and film_stream_reset and a scene cut leave it as it is.  A primed push then writes
+ *                      popcount(mask) frames to `mid`, packed in temporal order, and reports that count in *produced; every frame is
+ *                      bit-identical to the frame at its position of a full push.  mask = 0 is allowed: such a push only extracts the
+ *                      pushed frame, like a first push, reports *produced = 0 and takes a NULL `mid`.  FILM_ERR_STATE: no open stream.
+ *                      FILM_ERR_INVALID, with "mask" in the message: a bit at or above 2^T - 1.
+ *   What runs.  Let C be the selected positions and all their ancestors in the recursion (the parents a position is interpolated from, and
+ *     theirs).  The push walks the depth-first order of film_stream_schedule_json restricted to C, one pair run per member.  A member with a
+ *     child in C is fed back - cut as float32 into slot 1 + depth - as in a full push; a member that is not selected is joined (into the
+ *     stream's own buffer) and fed back, but neither quantised nor downloaded nor written to `mid`.  In a full push a fed-back frame is
+ *     extracted by its left child's run; when only the right child is in C, an extraction-only run stands in front of that child: the
+ *     left child's orientation (its left slot, the fed-back frame's slot as `right`, extract = 1) run to "n_extract", as a first push runs
+ *     its plan.  Per push: |C| pair runs, and 1 + (members of C with a child in C) extractions.  With every position selected the push
+ *     makes exactly the device calls of a stream that was never given a selection.  The workspace, the T + 1 slots and the stream's
+ *     buffers are those of 2^T - 1 frames whatever is selected.
+ *   film_stream_select_schedule_json  the steps of the primed push of a "stream_times" = `times` stream with selection `mask` whose input
+ *                      lands in `slot`: the keys of film_stream_schedule_json plus "mask"; "produced" = popcount(mask); every step gains
+ *                      "deliver" (1: the frame goes to `mid`, 0: it is only fed back) and "run" ("pair", or "extract" for an
+ *                      extraction-only step, whose "index" and "depth" are those of the frame it extracts, with "feed" -1 and "deliver"
+ *                      0).  mask = 0: the one step is the extraction of the pushed frame ("index" 2^T, "depth" 0).  With the full mask
+ *                      the steps are those of film_stream_schedule_json.  Refuses what that query refuses, and a bad mask as
+ *                      film_stream_select does.  Works on plan-only handles. */
 #define FILM_PIX_F32 0   /* frames and results float32 [H,W,3], as everywhere else */
 #define FILM_PIX_U8  1   /* frames and results uint8 [H,W,3]: x = u8 / 255.0f (IEEE, = read_image), result = film_to_uint8's rule */
 /* 8-bit Y'CbCr 4:2:0 frames: the conversion in is fused into the tile cut, the conversion out into the quantisation, so such a frame
@@ -295,6 +320,8 @@ int film_stream_plan_json(film_t* h, int tiles, int H, int W, int slot, char* bu
 int film_stream_pair_plan_json(film_t* h, int tiles, int H, int W, int times, int left, int right, int extract, char* buf, int64_t capacity,
                                int64_t* needed);
 int film_stream_schedule_json(film_t* h, int times, int slot, char* buf, int64_t capacity, int64_t* needed);
+int film_stream_select(film_t* h, uint64_t mask);
+int film_stream_select_schedule_json(film_t* h, int times, int slot, uint64_t mask, char* buf, int64_t capacity, int64_t* needed);
 
 /* Execution options.  Keys:
  *   "autotune" 0/1 time every distinct conv shape of a new plan with each fitting tile shape and keep

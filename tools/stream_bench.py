@@ -20,6 +20,9 @@ copies of one picture: D = 0 for RGB, a fraction of a percent of 2 S for 4:2:0, 
 alternating a frame and its halved codes: extraction only); `*_first` - a first push (reset() + push, scene_cut = 0), what a cut should cost;
 and `hist <layout> <size> <data>` - frame_histogram_kernel alone (film_frame_histogram, hip events around 50 calls, microseconds per call)
 at 1080p and 4K on random bytes and on a constant frame, beside the frame's bytes over the measured HBM copy rate (6.29 TB/s).
+--times T --select "3,6/2,5" is a run of its own about selected mid-frames (FilmStream.select; a frame-rate conversion such as 24 -> 60
+takes the positions {3, 6} and {2, 5} of a T = 3 push in turn): at 1080p 2x2, the milliseconds PER PUSH of a device-resident `f32` push
+and a host `i420` push that take the selections in turn, beside this tree's full push and - with --baseline-root - the baseline's.
 --times T[,T..] is a run of its own about recursive streams (engine option "stream_times"): at 1080p 2x2, for `f32` and `i420`, device-resident
 and host pushes, the milliseconds PER GENERATED FRAME of a steady push of a stream opened with times = T (2^T - 1 frames per push) beside
 this tree's times = 1 push, beside film_hip.recursive.interpolate_pair_recursively on the same pair (float32, device-resident: 2^T - 1 pair
@@ -233,6 +236,133 @@ def times_worker(root, reps, times_list):
     print('STREAM_BENCH ' + json.dumps(out), flush=True)
 
 
+def select_worker(root, reps, t, selections):
+    """--select: the milliseconds PER PUSH of a times = t stream at the first point, `f32` device-resident and `i420` from host buffers:
+    `full_*` - every position (what any tree with "stream_times" offers) - and, where the tree has FilmStream.select, `select_*` - the
+    selections taken in turn, push after push, one select() per push.  The selected frames of the f32 push are compared bit for bit
+    with those positions of the full push of the same frames.  Prints one JSON line."""
+    for p in (root, os.path.join(root, 'frame-interpolation_amd')):
+        sys.path.insert(0, p)
+    import numpy as np
+    import torch
+    from film_hip import weights as W
+    from film_hip.engine import FilmEngine, FilmStream
+    from film_hip.options import PUBLISHED
+    from film_hip.torch_io import DeviceInterpolator
+    eng = FilmEngine(PUBLISHED, device=0)
+    eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
+    name, h, w, align, block, _, _ = POINTS[0]
+    res = {}
+    out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {name: res}}
+    calls = 2 * len(selections)          # pushes per timed window: every selection as often as every other
+
+    def timed(call, warm=2):
+        for _ in range(warm):
+            call()
+        torch.cuda.synchronize()
+        samples = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                call()
+            torch.cuda.synchronize()
+            samples.append((time.perf_counter() - t0) * 1e3 / calls)
+        return [round(s, 4) for s in samples]
+
+    it = DeviceInterpolator(eng, align=align, block_shape=list(block))
+    fr = _frames(4, h, w)
+    x = [torch.from_numpy(f).cuda() for f in fr]
+    y = [torch.empty((h * 3 // 2, w), dtype=torch.uint8, device='cuda') for _ in x]
+    for src, dst in zip(x, y):
+        eng.to_yuv420_device(src.data_ptr(), dst.data_ptr(), h, w, 'i420')
+    torch.cuda.synchronize()
+    host = [v.cpu().numpy() for v in y]
+    state = {'i': 0, 's': 0}
+
+    def nxt(m):
+        state['i'] = (state['i'] + 1) % m
+        return state['i']
+
+    def turn(st):          # the next selection, in turn
+        state['s'] = (state['s'] + 1) % len(selections)
+        st.select(selections[state['s']])
+        return state['s']
+
+    has_select = hasattr(FilmStream, 'select')
+    with it.stream(h, w, 'f32', times=t) as st:
+        st.push(x[0])
+        res['full_push_f32'] = timed(lambda: st.push(x[nxt(4)]))
+        if has_select:
+            st.reset()
+            st.push(x[0])
+            full = st.push(x[1])
+            res['identical'] = True
+            for sel in selections:
+                st.reset()
+                st.push(x[0])
+                st.select(sel)
+                got = st.push(x[1])
+                res['identical'] = res['identical'] and bool(torch.equal(got, full[[p - 1 for p in sel]]))
+            res['select_push_f32'] = timed(lambda: (turn(st), st.push(x[nxt(4)])))
+    with eng.open_stream(h, w, align=align, block_shape=block, pix='i420', times=t) as st:
+        st.push(host[0])
+        out_full = np.empty(((1 << t) - 1,) + host[0].shape, np.uint8)
+        res['full_host_push_i420'] = timed(lambda: st.push(host[nxt(4)], out=out_full))
+        if has_select:
+            outs = [np.empty((len(sel),) + host[0].shape, np.uint8) for sel in selections]
+            res['select_host_push_i420'] = timed(lambda: st.push(host[nxt(4)], out=outs[turn(st)]))
+    eng.save_tune_cache()
+    eng.close()
+    print('STREAM_BENCH ' + json.dumps(out), flush=True)
+
+
+def select_main(args, t, selections):
+    """--select: rounds of (the baseline's full pushes,) this tree's full and selected pushes; the report in ms per push.  Both trees keep
+    their autotune choices in ONE file (the first worker fills it): the full pushes are compared on equal tile choices."""
+    os.makedirs(args.scratch, exist_ok=True)
+    tune = os.path.join(args.scratch, 'stream_bench_tune_select.txt')
+    name = POINTS[0][0]
+    base, this = [], []
+    for r in range(args.rounds):
+        if args.baseline_root:
+            base.append(_run_worker(os.path.abspath(args.baseline_root), args.reps, False, tune, times=[t], select=args.select))
+            print(f'# round {r + 1}/{args.rounds} baseline: done', flush=True)
+        this.append(_run_worker(HERE, args.reps, False, tune, times=[t], select=args.select))
+        print(f'# round {r + 1}/{args.rounds} this: done', flush=True)
+    pts = [r['points'][name] for r in this]
+    bpts = [r['points'][name] for r in base]
+    lines = [f'# tools/stream_bench.py --times {t} --select "{args.select}"  this = {this[0]["version"]}' +
+             (f'  baseline = {base[0]["version"]}' if base else '') + f'  {this[0]["device"]}  rounds={args.rounds} reps={args.reps}',
+             f'# ms per PUSH of a times = {t} stream (a full push generates {(1 << t) - 1} frames; the selections {args.select} are taken in turn), '
+             'f32 device-resident, i420 from host buffers: mean [min .. max] over rounds x reps windows',
+             f'{name}:']
+    for pix in ('push_f32', 'host_push_i420'):
+        full, sel = 'full_' + pix, 'select_' + pix
+        if bpts:
+            lines.append(f'  {"baseline " + full:<32} {_stat([s for p in bpts for s in p[full]])}')
+        lines.append(f'  {full:<32} {_stat([s for p in pts for s in p[full]])}')
+        lines.append(f'  {sel:<32} {_stat([s for p in pts for s in p[sel]])}')
+        fm, sm = (statistics.mean(s for p in pts for s in p[k]) for k in (full, sel))
+        lines.append(f'  {sel + " / " + full:<48} {sm / fm:.3f}')
+        if bpts:
+            bw = [s for p in bpts for s in p[full]]
+            bm = [statistics.mean(p[full]) for p in bpts]
+            d = [statistics.mean(p[full]) - b for p, b in zip(pts, bm)]
+            lines.append(f'  {full + " - baseline " + full:<48} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms'
+                         f'   (baseline: round means {" ".join(f"{b:.3f}" for b in bm)}, spread of its windows {max(bw) - min(bw):.3f} ms)')
+            d = [statistics.mean(p[sel]) - b for p, b in zip(pts, bm)]
+            lines.append(f'  {sel + " - baseline " + full:<48} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms'
+                         f'   ({sm / statistics.mean(bw):.3f} of the baseline\'s full push)')
+    lines.append(f'  selected frames of push_f32 == those positions of the full push, bit for bit: {all(p["identical"] for p in pts)}')
+    lines.append('# raw: ' + json.dumps({'baseline': base, 'this': this}))
+    print('\n'.join(lines), flush=True)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    if not all(p['identical'] for p in pts):
+        raise SystemExit('a selected frame differs from the full push')
+
+
 def scene_rows(eng, it, timed, nxt, h, w, align, block, n, x8, i420):
     """The --scene_cut rows of one point: see the module text.  x8 / i420: the bench frames as CUDA tensors."""
     res = {}
@@ -315,11 +445,12 @@ def histogram_alone(calls=50, reps=3):
     return out
 
 
-def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False, times=None):
+def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False, times=None, select=None):
     env = dict(os.environ, FILM_TUNE_CACHE=tune_file)
     cmd = [sys.executable, os.path.abspath(__file__), '--worker', root, '--reps', str(reps)] + (['--quick'] if quick else [])
     cmd += (['--rows', ','.join(rows)] if rows else []) + (['--points', ','.join(points)] if points else []) + (['--scene_cut'] if scene_cut else [])
     cmd += ['--times', ','.join(str(t) for t in times)] if times else []
+    cmd += ['--select', select] if select else []
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)   # (a hung worker ends the run: nothing is started behind it)
     for line in p.stdout.splitlines():
         if line.startswith('STREAM_BENCH '):
@@ -385,11 +516,21 @@ def main(argv=None):
     ap.add_argument('--points', default=None, help='comma-separated points to run (default: all), e.g. "1080p 2x2"')
     ap.add_argument('--scene_cut', action='store_true', help='add the cost of option "scene_cut" and of its histogram kernel alone (see above)')
     ap.add_argument('--times', default=None, help='comma-separated "stream_times" values, e.g. 2,3: the recursive-stream report instead (see above)')
+    ap.add_argument('--select', default=None, metavar='"3,6/2,5"',
+                    help='with --times T (one value): the selected-push report instead - the selections (1-based positions, comma-separated; '
+                         '"/" between selections) are taken in turn, push after push (FilmStream.select), beside the full push of this tree and of the baseline')
     ap.add_argument('--worker', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     rows = args.rows.split(',') if args.rows else None
     points = args.points.split(',') if args.points else None
     times = [int(t) for t in args.times.split(',')] if args.times else None
+    if args.select:
+        if not times or len(times) != 1:
+            raise SystemExit('--select needs --times T with one value')
+        selections = [tuple(int(p) for p in part.split(',') if p.strip()) for part in args.select.split('/')]
+        if args.worker:
+            return select_worker(args.worker, args.reps, times[0], selections)
+        return select_main(args, times[0], selections)
     if times and args.worker:
         return times_worker(args.worker, args.reps, times)
     if times:
