@@ -56,25 +56,34 @@ int tile_geometry(film_t* h, int H, int W, int block_h, int block_w, int align, 
   }
   return FILM_OK;
 }
-// The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the 4:2:0 layouts (pix_layout,
-// pix_is_yuv, pix_is_yuv10, pix_sample_bytes: film_kernels.h).
+// The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the Y'CbCr layouts (pix_layout,
+// pix_is_yuv, pix_is_yuv10, pix_sample_bytes, pix_chroma_shift: film_kernels.h).
 // FILM_OK, or the refusal of a pix value for H x W frames (include/film_hip.h, film_stream_open)
 int check_pix(film_t* h, int pix, int H, int W) {
   const int layout = pix_layout(pix), flags = pix & ~0xff;
+  constexpr int known = FILM_YUV_BT601 | FILM_YUV_BT2020 | FILM_YUV_FULL;
   if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !pix_is_yuv(pix))
-    return fail(h, FILM_ERR_INVALID, "bad pix layout %d: FILM_PIX_F32 (0), FILM_PIX_U8 (1), FILM_PIX_I420 (16), FILM_PIX_NV12 (17), FILM_PIX_I010 (32) or FILM_PIX_P010 (33)",
-                layout);
-  if (flags & ~(FILM_YUV_BT601 | FILM_YUV_FULL))
-    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: unknown bits 0x%x set (flags: FILM_YUV_BT601 0x100, FILM_YUV_FULL 0x400)", (unsigned)pix,
-                (unsigned)(flags & ~(FILM_YUV_BT601 | FILM_YUV_FULL)));
+    return fail(h, FILM_ERR_INVALID, "bad pix layout %d: FILM_PIX_F32 (0), FILM_PIX_U8 (1), FILM_PIX_I420 (16), FILM_PIX_NV12 (17), FILM_PIX_I422 (20), FILM_PIX_I444 (24), "
+                "FILM_PIX_I010 (32), FILM_PIX_P010 (33), FILM_PIX_I210 (36) or FILM_PIX_I410 (40)", layout);
+  if (flags & ~known)
+    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: unknown bits 0x%x set (flags: FILM_YUV_BT601 0x100, FILM_YUV_FULL 0x400, FILM_YUV_BT2020 0x2000)", (unsigned)pix,
+                (unsigned)(flags & ~known));
   if (flags && !pix_is_yuv(pix))
-    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: the colour flags belong to the 4:2:0 layouts, not to an RGB layout", (unsigned)pix);
-  if (pix_is_yuv(pix) && H > 0 && W > 0 && ((H | W) & 1))
+    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: the colour flags belong to the Y'CbCr layouts, not to an RGB layout", (unsigned)pix);
+  if ((flags & FILM_YUV_BT601) && (flags & FILM_YUV_BT2020))
+    return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: FILM_YUV_BT601 and FILM_YUV_BT2020 name two matrices", (unsigned)pix);
+  const ChromaShift cs = pix_chroma_shift(pix);
+  if (cs.sy && H > 0 && W > 0 && ((H | W) & 1))
     return fail(h, FILM_ERR_INVALID, "pix: 4:2:0 needs even sizes, got %d x %d", H, W);
+  if (cs.sx && !cs.sy && H > 0 && W > 0 && (W & 1))
+    return fail(h, FILM_ERR_INVALID, "pix: 4:2:2 needs an even width, got %d x %d", H, W);
   return FILM_OK;
 }
 // samples of one H x W frame of pixel type `pix` (S of "Scene cuts", include/film_hip.h), and its bytes
-int64_t frame_samples(int pix, int H, int W) { return pix_is_yuv(pix) ? (int64_t)H * W * 3 / 2 : (int64_t)H * W * 3; }
+int64_t frame_samples(int pix, int H, int W) {
+  const ChromaShift cs = pix_chroma_shift(pix);
+  return pix_is_yuv(pix) ? (int64_t)H * W + 2 * (int64_t)(H >> cs.sy) * (W >> cs.sx) : (int64_t)H * W * 3;
+}
 size_t frame_bytes(int pix, int H, int W) { return (size_t)frame_samples(pix, H, W) * pix_sample_bytes(pix); }
 // The refusals the compute entry points share (`fn`: the entry point); where they stand among its other checks is the entry point's choice.
 int need_device(film_t* h, const char* fn) {
@@ -384,10 +393,15 @@ int film_frame_histogram(const void* frame_dev, int H, int W, int pix, uint32_t*
   return film_launch_frame_histogram(frame_dev, H, W, pix, hist_dev, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
 }
 
-int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream) {
+int film_to_yuv(const float* src, void* dst, int H, int W, int pix, void* stream) {
   if (!src || !dst || H < 1 || W < 1 || !pix_is_yuv(pix) || check_pix(nullptr, pix, H, W) != FILM_OK) return FILM_ERR_INVALID;
   if (pix_is_yuv10(pix) && (reinterpret_cast<uintptr_t>(dst) & 1)) return FILM_ERR_INVALID;   // (16-bit samples)
   return film_launch_rgb_to_yuv420(src, dst, H, W, pix, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
+}
+
+int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream) {
+  if (!pix_chroma_shift(pix).sy) return FILM_ERR_INVALID;   // (the 4:2:0 layouts only, as ever; no Y'CbCr layout at all: film_to_yuv refuses it)
+  return film_to_yuv(src, dst, H, W, pix, stream);
 }
 
 #ifndef FILM_SRC_ID
@@ -718,10 +732,11 @@ int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, i
   if (!h) return FILM_ERR_INVALID;
   if (!frames_dev || !tiles_dev) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: NULL argument");
   if (!pix_is_yuv(pix))
-    return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: bad pix layout %d: FILM_PIX_I420 (16), FILM_PIX_NV12 (17), FILM_PIX_I010 (32) or FILM_PIX_P010 (33)", pix_layout(pix));
+    return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: bad pix layout %d: FILM_PIX_I420 (16), FILM_PIX_NV12 (17), FILM_PIX_I422 (20), FILM_PIX_I444 (24), "
+                "FILM_PIX_I010 (32), FILM_PIX_P010 (33), FILM_PIX_I210 (36) or FILM_PIX_I410 (40)", pix_layout(pix));
   int rc = check_pix(h, pix, H, W);
   if (rc) return rc;
-  if (reinterpret_cast<uintptr_t>(frames_dev) & 3) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: the frames of a 4:2:0 pix must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(frames_dev) & 3) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: the frames of a Y'CbCr pix must be 4-byte aligned");
   return debug_tile_map(h, "film_debug_yuv_cut", 0, pix, frames_dev, tiles_dev, B, H, W, align, block_h, block_w, tile0, ntiles, (hipStream_t)stream);
 }
 

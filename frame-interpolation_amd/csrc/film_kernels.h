@@ -380,25 +380,42 @@ hipError_t film_launch_flow_up(const FlowUpParams& p, hipStream_t s);
 hipError_t film_launch_flow_add(const FlowAddParams& p, hipStream_t s);
 hipError_t film_launch_warp(const WarpParams& p, hipStream_t s);
 hipError_t film_launch_pack_flow(const PackFlowParams& p, hipStream_t s);
-// frame_kernels.hip: frame I/O.  `pix` is the public value (include/film_hip.h): a layout in bits 0-7 plus FILM_YUV_BT601 / FILM_YUV_FULL for the
-// 4:2:0 layouts; the launchers decode it.  Overlapped tiles and their cross-fade when p.ovy | p.ovx.
-// What a pix value says, for the launchers, film_engine.cpp and the host-only build alike: its layout, 4:2:0 or not, 10-bit 4:2:0 or not, and the
-// bytes of one sample (float32 for FILM_PIX_F32 and for what check_pix refuses anyway).
+// frame_kernels.hip: frame I/O.  `pix` is the public value (include/film_hip.h): a layout in bits 0-7 plus FILM_YUV_BT601 / FILM_YUV_BT2020 /
+// FILM_YUV_FULL for the Y'CbCr layouts; the launchers decode it.  Overlapped tiles and their cross-fade when p.ovy | p.ovx.
+// What a pix value says, for the launchers, film_engine.cpp and the host-only build alike: its layout, Y'CbCr or not, 10-bit Y'CbCr or not, the
+// bytes of one sample (float32 for FILM_PIX_F32 and for what check_pix refuses anyway), and the chroma shifts of a Y'CbCr layout.
 inline int pix_layout(int pix) { return pix & 0xff; }
-inline bool pix_is_yuv10(int pix) { return pix_layout(pix) == FILM_PIX_I010 || pix_layout(pix) == FILM_PIX_P010; }   // 16-bit samples
-inline bool pix_is_yuv(int pix) { return pix_layout(pix) == FILM_PIX_I420 || pix_layout(pix) == FILM_PIX_NV12 || pix_is_yuv10(pix); }
+inline bool pix_is_yuv10(int pix) {   // 16-bit samples
+  const int l = pix_layout(pix);
+  return l == FILM_PIX_I010 || l == FILM_PIX_P010 || l == FILM_PIX_I210 || l == FILM_PIX_I410;
+}
+inline bool pix_is_yuv(int pix) {
+  const int l = pix_layout(pix);
+  return l == FILM_PIX_I420 || l == FILM_PIX_NV12 || l == FILM_PIX_I422 || l == FILM_PIX_I444 || pix_is_yuv10(pix);
+}
 inline int pix_sample_bytes(int pix) { return pix_is_yuv10(pix) ? 2 : pix_is_yuv(pix) || pix_layout(pix) == FILM_PIX_U8 ? 1 : (int)sizeof(float); }
+// A chroma plane of an H x W Y'CbCr frame is [H >> sy][W >> sx]: (1, 1) for 4:2:0, (1, 0) for 4:2:2, (0, 0) for 4:4:4 (and for what is no Y'CbCr layout)
+struct ChromaShift { int sx, sy; };
+inline ChromaShift pix_chroma_shift(int pix) {
+  const int l = pix_layout(pix);
+  if (l == FILM_PIX_I444 || l == FILM_PIX_I410 || !pix_is_yuv(pix)) return {0, 0};
+  if (l == FILM_PIX_I422 || l == FILM_PIX_I210) return {1, 0};
+  return {1, 1};
+}
 // pad + image_to_patches of tiles [tile0, tile0 + ntiles): p.src is float32 [B][H][W][3] (FILM_PIX_F32), or bytes that the cut converts - [B][H][W][3]
 // (FILM_PIX_U8: float32(byte) / 255.0f, correctly rounded) or 4:2:0 frames of H * W * 3 / 2 bytes each (FILM_PIX_I420 / NV12; H and W even),
-// or 10-bit 4:2:0 frames of H * W * 3 / 2 little-endian uint16 samples each (FILM_PIX_I010 / P010; H and W even, the pointer 4-byte aligned).
+// or 10-bit 4:2:0 frames of H * W * 3 / 2 little-endian uint16 samples each (FILM_PIX_I010 / P010; H and W even, the pointer 4-byte aligned),
+// or planar 4:2:2 / 4:4:4 frames of 2 H W / 3 H W samples each (FILM_PIX_I422 / I444: bytes; I210 / I410: uint16; 4:2:2: W even; frame b at sample
+// b * S, the batch pointer 4-byte aligned).
 hipError_t film_launch_cut_tiles(const TileMapParams& p, int pix, hipStream_t s);
 // crop + patches_to_image, or crop + cross-fade.  The cross-fade adds to what the tiles below tile0 left in dst, so the launches of one
 // frame go in tile order on one stream.
 hipError_t film_launch_join_tiles(const TileMapParams& p, hipStream_t s);
 // write_image's rounding on the device: dst[i] = uint8(clip(src[i] * 255, 0, 255) + 0.5)  (eval/util.py:51-52)
 hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipStream_t s);
-// float32 [H][W][3] -> one 4:2:0 frame of H * W * 3 / 2 samples (clip, matrix, 2 x 2 box mean of the chroma, quantisation): bytes for
-// FILM_PIX_I420 / NV12, uint16 for FILM_PIX_I010 / P010 (dst then 2-byte aligned, else hipErrorInvalidValue)
+// float32 [H][W][3] -> one Y'CbCr frame (clip, matrix, the chroma mean of the subsampling - 2 x 2, 1 x 2 or none -, quantisation): bytes for
+// the 8-bit layouts, uint16 for the 10-bit ones (dst then 2-byte aligned, else hipErrorInvalidValue).  The name is its first use's: it serves
+// every Y'CbCr layout.
 hipError_t film_launch_rgb_to_yuv420(const float* src, void* dst, int H, int W, int pix, hipStream_t s);
 // The sample histogram of one frame (include/film_hip.h, "Scene cuts"): hist[p * 256 + v] = the samples of plane p with 8-bit code v.  The launcher
 // zeroes the 768 counters first: a call overwrites.  `frame` is 4-byte aligned and its allocation a whole number of 32-bit words (as for the 8-bit

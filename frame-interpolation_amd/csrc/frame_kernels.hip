@@ -3,18 +3,19 @@
 //
 //   frame_to_tiles<OVERLAP>             _pad_to_align + image_to_patches, float32 frames    eval/interpolator.py:30-63, :66-104
 //   frame_u8_to_tiles<OVERLAP>          the same on 8-bit RGB frames: float32(byte) / 255   eval/util.py read_image
-//   frame_yuv_to_tiles<OVERLAP,LAYOUT>  the same on 4:2:0 frames (I420 / NV12 / I010 / P010)  include/film_hip.h, "The 4:2:0 arithmetic", "The 10-bit ..."
+//   frame_yuv_to_tiles<OVERLAP,LAYOUT>  the same on Y'CbCr frames (4:2:0, 4:2:2, 4:4:4; 8 / 10 bit)  include/film_hip.h, "The 4:2:0 arithmetic", "The 10-bit ...", "The 4:2:2 and 4:4:4 ..."
 //   tiles_to_frame                    crop + patches_to_image                             eval/interpolator.py:107-126, :192-206
 //   blend_tiles                         crop + cross-fade of overlapped tiles               include/film_hip.h, "block_overlap_h"
 //   to_uint8                            clip(x * 255, 0, 255) + 0.5, truncated              eval/util.py:51-52 (write_image)
-//   rgb_to_yuv<LAYOUT>                  float32 RGB -> the planes of one 4:2:0 frame        the same two sections
+//   rgb_to_yuv<LAYOUT>                  float32 RGB -> the planes of one Y'CbCr frame       the same three sections
 //   frame_histogram<LAYOUT>            3 x 256 counters of a frame's 8-bit sample codes    include/film_hip.h, "Scene cuts"
 //
 // OVERLAP: the tile's content is the patch grown by the overlap, from film_tile_origin (options "block_overlap_h" / "block_overlap_w").
-// LAYOUT: a FILM_PIX_* value.  The 4:2:0 cut and quantiser are written once over Yuv420<LAYOUT>, which states what a layout decides: the sample
-// type and how many fit a 32-bit word, planar or semi-planar chroma, where the code sits in a sample, the largest code and the chroma midpoint,
-// the constants the kernels take and the aligned multi-sample load.  What only one depth does stands behind `if constexpr`: the 8-bit LDS tables
-// against the 10-bit division, and P010's direct reads of its CbCr pair words.
+// LAYOUT: a FILM_PIX_* value.  The Y'CbCr cut and quantiser are written once over YuvLayout<LAYOUT>, which states what a layout decides: the sample
+// type and how many fit a 32-bit word, the chroma shifts (SX, SY) = (1, 1) for 4:2:0, (1, 0) for 4:2:2, (0, 0) for 4:4:4, planar or semi-planar
+// chroma, where the code sits in a sample, the largest code and the chroma midpoint, the constants the kernels take and the aligned multi-sample
+// load.  What only one depth or one subsampling does stands behind `if constexpr`: the 8-bit LDS tables against the 10-bit division, P010's
+// direct reads of its CbCr pair words, the four chroma samples per group of 4:4:4, the chroma means of the quantiser.
 //
 // This file is compiled with -ffp-contract=off, like misc_kernels.hip: the cross-fade, the colour matrices and the quantisers are specified
 // as separate multiply / add operations (one rounding each), so a*b+c must not become an fma here.
@@ -213,14 +214,21 @@ __device__ __forceinline__ uint64_t load_samples_aligned(const uint16_t* p, int 
   return v;
 }
 
-// What a 4:2:0 layout decides, for the one cut and the one quantiser below.  A frame is H * W * 3 / 2 samples: its Y plane [H][W] first, then
-// Cb [H/2][W/2] and Cr [H/2][W/2] (I420, I010) or CbCr [H/2][W/2][2] (NV12, P010).  A sample is a byte, or a little-endian 16-bit word that
-// keeps its 10-bit code in bits 0-9 (I010: the upper six are ignored) or in bits 6-15 (P010: the lower six are).
-template <int LAYOUT> struct Yuv420 {
-  static_assert(LAYOUT == FILM_PIX_I420 || LAYOUT == FILM_PIX_NV12 || LAYOUT == FILM_PIX_I010 || LAYOUT == FILM_PIX_P010, "a 4:2:0 layout");
+// What a Y'CbCr layout decides, for the one cut and the one quantiser below.  A frame is its Y plane [H][W] first, then Cb [H >> SY][W >> SX]
+// and Cr [H >> SY][W >> SX] (planar) or, 4:2:0 only, CbCr [H/2][W/2][2] (NV12, P010): H * W * 3 / 2 samples (4:2:0; H, W even), 2 H W (4:2:2;
+// W even) or 3 H W (4:4:4; any H, W).  A sample is a byte, or a little-endian 16-bit word that keeps its 10-bit code in bits 0-9 (I010, I210,
+// I410: the upper six are ignored) or in bits 6-15 (P010: the lower six are).
+template <int LAYOUT> struct YuvLayout {
+  static_assert(LAYOUT == FILM_PIX_I420 || LAYOUT == FILM_PIX_NV12 || LAYOUT == FILM_PIX_I010 || LAYOUT == FILM_PIX_P010 || LAYOUT == FILM_PIX_I422 ||
+                LAYOUT == FILM_PIX_I444 || LAYOUT == FILM_PIX_I210 || LAYOUT == FILM_PIX_I410, "a Y'CbCr layout");
   static constexpr int PIX = LAYOUT;
-  static constexpr bool WIDE = LAYOUT == FILM_PIX_I010 || LAYOUT == FILM_PIX_P010;                  // 10-bit codes in 16-bit samples
+  static constexpr bool WIDE = LAYOUT == FILM_PIX_I010 || LAYOUT == FILM_PIX_P010 || LAYOUT == FILM_PIX_I210 || LAYOUT == FILM_PIX_I410;   // 10-bit codes in 16-bit samples
   static constexpr bool SEMI_PLANAR = LAYOUT == FILM_PIX_NV12 || LAYOUT == FILM_PIX_P010;
+  static constexpr int SX = LAYOUT == FILM_PIX_I444 || LAYOUT == FILM_PIX_I410 ? 0 : 1;            // chroma column of frame column x: x >> SX
+  static constexpr int SY = SX == 0 || LAYOUT == FILM_PIX_I422 || LAYOUT == FILM_PIX_I210 ? 0 : 1;   // chroma row of frame row y: y >> SY
+  static constexpr int GROUP_CHROMA = SX ? 3 : 4;   // the most chroma samples per plane under four pixels of a row
+  // samples of one chroma plane of an H x W frame (H * W = plane)
+  static __host__ __device__ __forceinline__ int64_t chroma_plane(int64_t plane) { return SX + SY == 2 ? plane / 4 : SX + SY == 1 ? plane / 2 : plane; }
   using Sample = std::conditional_t<WIDE, uint16_t, uint8_t>;
   using Consts = std::conditional_t<WIDE, Yuv10Consts, YuvTables>;       // the kernels' constants
   static constexpr int BITS = 8 * (int)sizeof(Sample), PER_WORD = 32 / BITS;   // of a stored sample; samples per 32-bit word
@@ -239,15 +247,16 @@ template <int LAYOUT> struct Yuv420 {
   }
 };
 
-// frame_u8_to_tiles_kernel on a 4:2:0 frame batch: p.src points at samples, frame b at sample b * H * W * 3 / 2 (10 bits: 4-byte aligned).
-// thread = four pixels (twelve floats) of one row of the tile buffer.  Pixel (fy, fx) of the FRAME takes the chroma sample (fy >> 1, fx >> 1):
+// frame_u8_to_tiles_kernel on a Y'CbCr frame batch: p.src points at samples (4-byte aligned), frame b at sample b * S, S the samples of a frame
+// (a 4:4:4 frame of odd size: not a word boundary - every read below is of the aligned words that hold a sample).
+// thread = four pixels (twelve floats) of one row of the tile buffer.  Pixel (fy, fx) of the FRAME takes the chroma sample (fy >> SY, fx >> SX):
 // origins and patch sizes may be odd, so the pairing follows the frame coordinate.  A group wholly inside the tile's content reads its four
-// Y samples and its two or three chroma samples per plane as aligned 32-bit words (Yuv420::load), P010 as the two or three aligned words that
-// ARE its CbCr pairs (a pair never straddles a word, W being even); a group that touches the padding or the row's end goes sample by sample.
+// Y samples and its two or three (4:4:4: four) chroma samples per plane as aligned 32-bit words (YuvLayout::load), P010 as the two or three aligned
+// words that ARE its CbCr pairs (a pair never straddles a word, W being even); a group that touches the padding or the row's end goes sample by sample.
 // 8 bits look the luma and chroma values up in the two tables (copied to LDS); 10 bits divide (Yuv10Consts) and declare no LDS.
 template <bool OVERLAP, int LAYOUT>
-__global__ __launch_bounds__(256) void frame_yuv_to_tiles_kernel(TileMapParams p, typename Yuv420<LAYOUT>::Consts k) {
-  using L = Yuv420<LAYOUT>;
+__global__ __launch_bounds__(256) void frame_yuv_to_tiles_kernel(TileMapParams p, typename YuvLayout<LAYOUT>::Consts k) {
+  using L = YuvLayout<LAYOUT>;
   using Sample = typename L::Sample;
   const float *ly = nullptr, *lc = nullptr;
   if constexpr (!L::WIDE) {
@@ -275,18 +284,19 @@ __global__ __launch_bounds__(256) void frame_yuv_to_tiles_kernel(TileMapParams p
     const int fy = C::row0(p, ty) + sy;
     const int fx = C::col0(p, tx) + s0;   // frame column of the group's first pixel
     const int64_t plane = (int64_t)p.H * p.W;
-    const Sample* frame0 = reinterpret_cast<const Sample*>(p.src) + (int64_t)b * (plane + plane / 2);
+    const int64_t cplane = L::chroma_plane(plane);
+    const Sample* frame0 = reinterpret_cast<const Sample*>(p.src) + (int64_t)b * (plane + 2 * cplane);
     const Sample* yrow = frame0 + (int64_t)fy * p.W;
-    const int hw = p.W >> 1;
-    // semi-planar: one row of Cb Cr pairs; planar: a Cb row and, H/2 * W/2 samples further on, the Cr row
-    const Sample* crow = frame0 + plane + (int64_t)(fy >> 1) * (L::SEMI_PLANAR ? p.W : hw);
-    const int64_t cr_off = L::SEMI_PLANAR ? 1 : plane / 4;
+    const int hw = p.W >> L::SX;
+    // semi-planar: one row of Cb Cr pairs; planar: a Cb row and, one chroma plane further on, the Cr row
+    const Sample* crow = frame0 + plane + (int64_t)(fy >> L::SY) * (L::SEMI_PLANAR ? p.W : hw);
+    const int64_t cr_off = L::SEMI_PLANAR ? 1 : cplane;
     uint32_t yb[4], cbb[4], crb[4];
     bool have[4];
     if (s0 >= 0 && s0 + 4 <= cw) {
       const uint64_t yw = L::load(yrow + fx, 4);
-      const int c0 = fx >> 1, nc = ((fx + 3) >> 1) - c0 + 1;      // two chroma samples per plane, three from an odd column
-      uint32_t cbs[3], crs[3];
+      const int c0 = fx >> L::SX, nc = ((fx + 3) >> L::SX) - c0 + 1;      // two chroma samples per plane, three from an odd column; 4:4:4: four
+      uint32_t cbs[L::GROUP_CHROMA], crs[L::GROUP_CHROMA];
       if constexpr (LAYOUT == FILM_PIX_P010) {
         const uint32_t* cwp = reinterpret_cast<const uint32_t*>(crow) + c0;   // (4-byte aligned: the frame is, and H * W and W are even)
         const uint32_t w0 = cwp[0], w1 = cwp[1], w2 = nc > 2 ? cwp[2] : 0u;
@@ -300,14 +310,18 @@ __global__ __launch_bounds__(256) void frame_yuv_to_tiles_kernel(TileMapParams p
       } else {
         const uint64_t wb = L::load(crow + c0, nc), wr = L::load(crow + cr_off + c0, nc);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) { cbs[q] = (uint32_t)(wb >> (L::BITS * q)) & L::MASK; crs[q] = (uint32_t)(wr >> (L::BITS * q)) & L::MASK; }
+        for (int q = 0; q < L::GROUP_CHROMA; ++q) { cbs[q] = (uint32_t)(wb >> (L::BITS * q)) & L::MASK; crs[q] = (uint32_t)(wr >> (L::BITS * q)) & L::MASK; }
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int q = ((fx + j) >> 1) - c0;
         yb[j] = (uint32_t)(yw >> (L::BITS * j)) & L::MASK;
-        cbb[j] = q == 0 ? cbs[0] : q == 1 ? cbs[1] : cbs[2];
-        crb[j] = q == 0 ? crs[0] : q == 1 ? crs[1] : crs[2];
+        if constexpr (L::SX == 0) {
+          cbb[j] = cbs[j]; crb[j] = crs[j];
+        } else {
+          const int q = ((fx + j) >> 1) - c0;
+          cbb[j] = q == 0 ? cbs[0] : q == 1 ? cbs[1] : cbs[2];
+          crb[j] = q == 0 ? crs[0] : q == 1 ? crs[1] : crs[2];
+        }
         have[j] = true;
       }
     } else {
@@ -316,7 +330,7 @@ __global__ __launch_bounds__(256) void frame_yuv_to_tiles_kernel(TileMapParams p
         have[j] = s0 + j >= 0 && s0 + j < cw;
         yb[j] = cbb[j] = crb[j] = 0;
         if (have[j]) {
-          const int c = (fx + j) >> 1;
+          const int c = (fx + j) >> L::SX;
           yb[j] = yrow[fx + j];
           cbb[j] = L::SEMI_PLANAR ? crow[2 * c] : crow[c];
           crb[j] = L::SEMI_PLANAR ? crow[2 * c + 1] : crow[cr_off + c];
@@ -376,24 +390,28 @@ __device__ __forceinline__ void store_sample_words(void* d, const uint32_t (&q)[
   }
 }
 
-// float32 frame [H][W][3] -> the planes of one 4:2:0 frame (film_to_yuv420; the quantisation of a 4:2:0 stream's push): dst points at samples
-// (10 bits: 2-byte aligned).  thread = 2 rows x 8 pixels: sixteen Y samples and four chroma samples per plane, which leave as whole 32-bit words
-// where the block is complete and the address allows, sample by sample otherwise.  A sample is the code << Yuv420::SHIFT: the bits a 10-bit
-// layout ignores are written as zero.  H and W are even.
+// float32 frame [H][W][3] -> the planes of one Y'CbCr frame (film_to_yuv / film_to_yuv420; the quantisation of a Y'CbCr stream's push): dst points
+// at samples (10 bits: 2-byte aligned).  thread = 2 rows x 8 pixels: sixteen Y samples and, per plane, four chroma samples (4:2:0: the 2 x 2 means),
+// two rows of four (4:2:2: the 1 x 2 means) or two rows of eight (4:4:4: no mean), which leave as whole 32-bit words where the block is complete
+// and the address allows, sample by sample otherwise.  A sample is the code << YuvLayout::SHIFT: the bits a 10-bit layout ignores are written as
+// zero.  4:2:0: H and W are even; 4:2:2: W is even, an odd H ends on a block of one row; 4:4:4: the last block of a row may hold an odd count of pixels.
 template <int LAYOUT>
-__global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const float* __restrict__ src, typename Yuv420<LAYOUT>::Sample* __restrict__ dst, int H, int W,
-                                                         typename Yuv420<LAYOUT>::Consts k) {
-  using L = Yuv420<LAYOUT>;
+__global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const float* __restrict__ src, typename YuvLayout<LAYOUT>::Sample* __restrict__ dst, int H, int W,
+                                                         typename YuvLayout<LAYOUT>::Consts k) {
+  using L = YuvLayout<LAYOUT>;
   using Sample = typename L::Sample;
+  constexpr int CR = L::SY ? 1 : 2, CN = L::SX ? 4 : 8;   // chroma rows of a block, chroma samples per row and plane
   const int bpr = (W + 7) / 8;      // blocks per row pair
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (int64_t)(H / 2) * bpr) return;
+  if (i >= (int64_t)((H + 1) / 2) * bpr) return;
   const int x0 = (int)(i % bpr) * 8, y0 = (int)(i / bpr) * 2;
-  const int np = min(8, W - x0);    // pixels of the block per row: even
-  uint32_t yq[2][8], cbq[4], crq[4];
+  const int np = min(8, W - x0);    // pixels of the block per row: even, but for 4:4:4
+  const int rows = L::SY ? 2 : min(2, H - y0);   // rows of the block: one at the end of an odd H (which only SY = 0 has)
+  uint32_t yq[2][8], cbq[CR][CN], crq[CR][CN];
   float cbf[2][8], crf[2][8];
 #pragma unroll
   for (int dy = 0; dy < 2; ++dy) {
+    if (dy >= rows) continue;
     const float* s = src + ((int64_t)(y0 + dy) * W + x0) * 3;
     float px[24];
     if (np == 8 && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
@@ -416,15 +434,29 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const float* __restrict
     }
   }
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float mb = ((cbf[0][2 * q] + cbf[0][2 * q + 1]) + (cbf[1][2 * q] + cbf[1][2 * q + 1])) * 0.25f;
-    const float mr = ((crf[0][2 * q] + crf[0][2 * q + 1]) + (crf[1][2 * q] + crf[1][2 * q + 1])) * 0.25f;
-    cbq[q] = quantise<L::QMAX>(mb * k.m.c_scale + (float)L::MID) << L::SHIFT;
-    crq[q] = quantise<L::QMAX>(mr * k.m.c_scale + (float)L::MID) << L::SHIFT;
+  for (int c = 0; c < CR; ++c) {
+    if (c >= rows) continue;
+#pragma unroll
+    for (int q = 0; q < CN; ++q) {
+      float mb, mr;
+      if constexpr (L::SY) {          // 4:2:0: the 2 x 2 box
+        mb = ((cbf[0][2 * q] + cbf[0][2 * q + 1]) + (cbf[1][2 * q] + cbf[1][2 * q + 1])) * 0.25f;
+        mr = ((crf[0][2 * q] + crf[0][2 * q + 1]) + (crf[1][2 * q] + crf[1][2 * q + 1])) * 0.25f;
+      } else if constexpr (L::SX) {   // 4:2:2: the pair of a row
+        mb = (cbf[c][2 * q] + cbf[c][2 * q + 1]) * 0.5f;
+        mr = (crf[c][2 * q] + crf[c][2 * q + 1]) * 0.5f;
+      } else {                        // 4:4:4: the pixel's own
+        mb = cbf[c][q];
+        mr = crf[c][q];
+      }
+      cbq[c][q] = quantise<L::QMAX>(mb * k.m.c_scale + (float)L::MID) << L::SHIFT;
+      crq[c][q] = quantise<L::QMAX>(mr * k.m.c_scale + (float)L::MID) << L::SHIFT;
+    }
   }
   const int64_t plane = (int64_t)H * W;
 #pragma unroll
   for (int dy = 0; dy < 2; ++dy) {
+    if (dy >= rows) continue;
     Sample* d = dst + (int64_t)(y0 + dy) * W + x0;
     if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
       store_sample_words<L::PER_WORD>(d, yq[dy]);
@@ -437,23 +469,28 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const float* __restrict
   if constexpr (L::SEMI_PLANAR) {
     Sample* d = dst + plane + (int64_t)(y0 >> 1) * W + x0;
     if (np == 8 && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
-      const uint32_t pairs[8] = {cbq[0], crq[0], cbq[1], crq[1], cbq[2], crq[2], cbq[3], crq[3]};
+      const uint32_t pairs[8] = {cbq[0][0], crq[0][0], cbq[0][1], crq[0][1], cbq[0][2], crq[0][2], cbq[0][3], crq[0][3]};
       store_sample_words<L::PER_WORD>(d, pairs);
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        if (2 * q < np) { d[2 * q] = (Sample)cbq[q]; d[2 * q + 1] = (Sample)crq[q]; }
+        if (2 * q < np) { d[2 * q] = (Sample)cbq[0][q]; d[2 * q + 1] = (Sample)crq[0][q]; }
     }
   } else {
-    Sample* db = dst + plane + (int64_t)(y0 >> 1) * (W >> 1) + (x0 >> 1);
-    Sample* dr = db + plane / 4;
-    if (np == 8 && (reinterpret_cast<uintptr_t>(db) & 3) == 0 && (reinterpret_cast<uintptr_t>(dr) & 3) == 0) {
-      store_sample_words<L::PER_WORD>(db, cbq);
-      store_sample_words<L::PER_WORD>(dr, crq);
-    } else {
+    const int64_t cplane = L::chroma_plane(plane);
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (2 * q < np) { db[q] = (Sample)cbq[q]; dr[q] = (Sample)crq[q]; }
+    for (int c = 0; c < CR; ++c) {
+      if (c >= rows) continue;
+      Sample* db = dst + plane + (int64_t)((y0 >> L::SY) + c) * (W >> L::SX) + (x0 >> L::SX);
+      Sample* dr = db + cplane;
+      if (np == 8 && (reinterpret_cast<uintptr_t>(db) & 3) == 0 && (reinterpret_cast<uintptr_t>(dr) & 3) == 0) {
+        store_sample_words<L::PER_WORD>(db, cbq[c]);
+        store_sample_words<L::PER_WORD>(dr, crq[c]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < CN; ++q)
+          if ((q << L::SX) < np) { db[q] = (Sample)cbq[c][q]; dr[q] = (Sample)crq[c][q]; }
+      }
     }
   }
 }
@@ -523,7 +560,9 @@ __global__ __launch_bounds__(256) void blend_tiles_kernel(TileMapParams p, int b
 
 // ---- the per-frame sample histogram (film_frame_histogram; include/film_hip.h, "Scene cuts") ----------------------------------------------
 // hist[p][v] += the samples of plane p with 8-bit code v, over the n elements of one frame: bytes (LAYOUT = FILM_PIX_U8 / I420 / NV12) or
-// floats (FILM_PIX_F32, whose code is film_to_uint8's byte).  `plane` = H * W, the bytes of the Y plane of a 4:2:0 frame.
+// floats (FILM_PIX_F32, whose code is film_to_uint8's byte).  `plane` = H * W, the samples of the Y plane of a Y'CbCr frame, `cplane` those of
+// one of its chroma planes (H * W / 4, H * W / 2 or H * W: the planar instances serve every subsampling; the I422 / I444 frames run the I420
+// instance, I210 / I410 the I010 one).
 //   loads     The frame is walked in the ALIGNED 16-byte vectors that hold it, one vector per lane and step of a grid-stride loop: a
 //             vector that lies wholly inside the frame is one 16-byte load; the first vector of a frame that does not start on a 16-byte
 //             boundary and the last partial one are read as the 32-bit words that hold at least one element of the frame (the pointer is
@@ -531,7 +570,8 @@ __global__ __launch_bounds__(256) void blend_tiles_kernel(TileMapParams p, int b
 //             only the elements of the frame.
 //   planes    interleaved RGB: element index mod 3; I420: three consecutive ranges; NV12: the Y range, then Cb at even and Cr at odd offsets.
 //   10 bits   LAYOUT = FILM_PIX_I010 / P010: the elements are 16-bit samples, eight per vector and two per word (n and `plane` count samples;
-//             the pointer is 4-byte aligned and n is even, so no word is partial); planes as I420 / NV12; a sample counts in bin code >> 2,
+//             the pointer is 4-byte aligned; a 4:4:4 frame of odd size has an odd n: its last word is partial and, like every word of a
+//             vector that is not whole, is counted by element); planes as I420 / NV12; a sample counts in bin code >> 2,
 //             the code being bits 0-9 (I010) or 6-15 (P010) of the word.
 //   counting  LDS integer atomics into HIST_COPIES sub-histograms per workgroup, laid out [bin][copy] with copy = lane & 7: eight
 //             neighbouring lanes never share an address, a flat picture (every lane on one bin) meets 8-way instead of 64-way same-address
@@ -540,7 +580,8 @@ __global__ __launch_bounds__(256) void blend_tiles_kernel(TileMapParams p, int b
 //             the arrival order.  hist is zeroed by the launcher.
 constexpr int HIST_COPIES = 8;
 template <int LAYOUT>
-__global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(const void* __restrict__ frame, int64_t n, int64_t plane, uint32_t* __restrict__ hist) {
+__global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(const void* __restrict__ frame, int64_t n, int64_t plane, int64_t cplane,
+                                                                            uint32_t* __restrict__ hist) {
   constexpr bool F32 = LAYOUT == FILM_PIX_F32;
   constexpr bool U16 = LAYOUT == FILM_PIX_I010 || LAYOUT == FILM_PIX_P010;   // 10-bit samples in 16-bit words: the code counted is v >> 2
   constexpr int EPV = F32 ? 4 : U16 ? 8 : 16;   // elements per 16-byte vector
@@ -570,8 +611,8 @@ __global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(cons
     }
     // what decides the plane of position j, as small integers
     const int c0 = (int)(((uint32_t)v % 3u + (uint32_t)(18 - head)) % 3u);           // RGB: channel of position 0 = (EPV v - head) mod 3, EPV mod 3 = 1 (v < 2^29)
-    const int d1 = (int)min((int64_t)EPV, max((int64_t)0, plane - e0));              // 4:2:0: positions below d1 are Y ...
-    const int d2 = (int)min((int64_t)EPV, max((int64_t)0, plane + plane / 4 - e0));  // ... I420: below d2 Cb, from d2 on Cr
+    const int d1 = (int)min((int64_t)EPV, max((int64_t)0, plane - e0));              // Y'CbCr: positions below d1 are Y ...
+    const int d2 = (int)min((int64_t)EPV, max((int64_t)0, plane + cplane - e0));     // ... planar: below d2 Cb, from d2 on Cr
     const int par = (int)((e0 - plane) & 1);                                         // NV12: parity of position 0 inside the CbCr plane
 #pragma unroll
     for (int j = 0; j < EPV; ++j) {
@@ -606,8 +647,9 @@ hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix,
   const bool yuv = pix_is_yuv(pix);
   if (!frame || !hist || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(frame) & 3)) return hipErrorInvalidValue;
   if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !yuv) return hipErrorInvalidValue;
-  if (yuv && ((H | W) & 1)) return hipErrorInvalidValue;
-  const int64_t plane = (int64_t)H * W, n = yuv ? plane + plane / 2 : plane * 3;
+  const ChromaShift cs = pix_chroma_shift(pix);
+  if (yuv && ((W & cs.sx) | (H & cs.sy))) return hipErrorInvalidValue;
+  const int64_t plane = (int64_t)H * W, cplane = yuv ? (int64_t)(H >> cs.sy) * (W >> cs.sx) : 0, n = yuv ? plane + 2 * cplane : plane * 3;
   int dev = 0, cus = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -617,10 +659,10 @@ hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix,
   const int64_t nvec = (n + epv - 1) / epv + 1;   // (+ 1: a frame that starts inside a vector)
   const int64_t grid = std::min<int64_t>((int64_t)std::max(cus, 1) * FILM_HIST_WG_PER_CU, (nvec + FILM_HIST_THREADS - 1) / FILM_HIST_THREADS);
   auto kernel = layout == FILM_PIX_F32 ? frame_histogram_kernel<FILM_PIX_F32> : layout == FILM_PIX_U8 ? frame_histogram_kernel<FILM_PIX_U8>
-              : layout == FILM_PIX_I420 ? frame_histogram_kernel<FILM_PIX_I420> : layout == FILM_PIX_NV12 ? frame_histogram_kernel<FILM_PIX_NV12>
-              : layout == FILM_PIX_I010 ? frame_histogram_kernel<FILM_PIX_I010> : frame_histogram_kernel<FILM_PIX_P010>;
+              : layout == FILM_PIX_NV12 ? frame_histogram_kernel<FILM_PIX_NV12> : layout == FILM_PIX_P010 ? frame_histogram_kernel<FILM_PIX_P010>
+              : pix_is_yuv10(pix) ? frame_histogram_kernel<FILM_PIX_I010> : frame_histogram_kernel<FILM_PIX_I420>;   // (planar: every subsampling)
   static_assert(FILM_HIST_THREADS == 256, "launch_units starts workgroups of 256");
-  return launch_units(kernel, grid * FILM_HIST_THREADS, s, frame, n, plane, hist);   // `grid` workgroups
+  return launch_units(kernel, grid * FILM_HIST_THREADS, s, frame, n, plane, cplane, hist);   // `grid` workgroups
 }
 
 namespace {
@@ -643,9 +685,10 @@ const U8Table& u8_table() {
 }
 
 // The tables of one colour setting (include/film_hip.h, "The 4:2:0 arithmetic"): built once per setting, on the host.
-YuvTables make_yuv_tables(bool bt601, bool full) {
+// matrix: 0 BT.709, 1 BT.601, 2 BT.2020 non-constant luminance
+YuvTables make_yuv_tables(int matrix, bool full) {
   YuvTables t;
-  const double Kr = bt601 ? 0.299 : 0.2126, Kb = bt601 ? 0.114 : 0.0722, Kg = 1.0 - Kr - Kb;
+  const double Kr = matrix == 1 ? 0.299 : matrix == 2 ? 0.2627 : 0.2126, Kb = matrix == 1 ? 0.114 : matrix == 2 ? 0.0593 : 0.0722, Kg = 1.0 - Kr - Kb;
   for (int i = 0; i < 256; ++i) {
     t.y[i] = full ? (float)i / 255.0f : ((float)i - 16.0f) / 219.0f;
     t.c[i] = ((float)i - 128.0f) / (full ? 255.0f : 224.0f);
@@ -660,8 +703,9 @@ YuvTables make_yuv_tables(bool bt601, bool full) {
 }
 // the tables of a public pix value (its FILM_YUV_* flags)
 const YuvTables& yuv_tables(int pix) {
-  static const YuvTables all[4] = {make_yuv_tables(false, false), make_yuv_tables(false, true), make_yuv_tables(true, false), make_yuv_tables(true, true)};
-  return all[((pix & FILM_YUV_BT601) ? 2 : 0) + ((pix & FILM_YUV_FULL) ? 1 : 0)];
+  static const YuvTables all[6] = {make_yuv_tables(0, false), make_yuv_tables(0, true), make_yuv_tables(1, false),
+                                   make_yuv_tables(1, true),  make_yuv_tables(2, false), make_yuv_tables(2, true)};
+  return all[((pix & FILM_YUV_BT601) ? 2 : (pix & FILM_YUV_BT2020) ? 4 : 0) + ((pix & FILM_YUV_FULL) ? 1 : 0)];
 }
 // The same for a 10-bit layout (include/film_hip.h, "The 10-bit 4:2:0 arithmetic"): the matrix is that of the 8-bit tables, the scales are 10-bit.
 Yuv10Consts yuv10_consts(int pix) {
@@ -673,13 +717,17 @@ Yuv10Consts yuv10_consts(int pix) {
   return k;
 }
 
-// f(Yuv420<LAYOUT>()) for the 4:2:0 layout of a pix value: how both launchers below choose their kernel instance
+// f(YuvLayout<LAYOUT>()) for the Y'CbCr layout of a pix value: how both launchers below choose their kernel instance
 template <class F> hipError_t with_yuv_layout(int pix, F f) {
   switch (pix_layout(pix)) {
-    case FILM_PIX_I420: return f(Yuv420<FILM_PIX_I420>());
-    case FILM_PIX_NV12: return f(Yuv420<FILM_PIX_NV12>());
-    case FILM_PIX_I010: return f(Yuv420<FILM_PIX_I010>());
-    case FILM_PIX_P010: return f(Yuv420<FILM_PIX_P010>());
+    case FILM_PIX_I420: return f(YuvLayout<FILM_PIX_I420>());
+    case FILM_PIX_NV12: return f(YuvLayout<FILM_PIX_NV12>());
+    case FILM_PIX_I010: return f(YuvLayout<FILM_PIX_I010>());
+    case FILM_PIX_P010: return f(YuvLayout<FILM_PIX_P010>());
+    case FILM_PIX_I422: return f(YuvLayout<FILM_PIX_I422>());
+    case FILM_PIX_I444: return f(YuvLayout<FILM_PIX_I444>());
+    case FILM_PIX_I210: return f(YuvLayout<FILM_PIX_I210>());
+    case FILM_PIX_I410: return f(YuvLayout<FILM_PIX_I410>());
     default: return hipErrorInvalidValue;
   }
 }
@@ -694,9 +742,9 @@ hipError_t film_launch_cut_tiles(const TileMapParams& p, int pix, hipStream_t s)
   if (p.ntiles <= 0) return hipSuccess;
   if (!pix_is_yuv(pix))
     return launch_units(ov ? frame_u8_to_tiles_kernel<true> : frame_u8_to_tiles_kernel<false>, (int64_t)p.ntiles * p.TH * ((p.TW * 3 + 11) / 12), s, p, u8_table());
-  if ((p.H | p.W) & 1) return hipErrorInvalidValue;
   return with_yuv_layout(pix, [&](auto l) {
     using L = decltype(l);
+    if ((p.W & L::SX) | (p.H & L::SY)) return hipErrorInvalidValue;   // (a subsampled axis is even)
     return launch_units(ov ? frame_yuv_to_tiles_kernel<true, L::PIX> : frame_yuv_to_tiles_kernel<false, L::PIX>, (int64_t)p.ntiles * p.TH * ((p.TW + 3) / 4), s, p,
                         L::consts(pix));
   });
@@ -722,10 +770,11 @@ hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipSt
 }
 
 hipError_t film_launch_rgb_to_yuv420(const float* src, void* dst, int H, int W, int pix, hipStream_t s) {
-  if (H <= 0 || W <= 0 || ((H | W) & 1)) return hipErrorInvalidValue;
+  if (H <= 0 || W <= 0) return hipErrorInvalidValue;
   if (pix_is_yuv10(pix) && (reinterpret_cast<uintptr_t>(dst) & 1)) return hipErrorInvalidValue;
   return with_yuv_layout(pix, [&](auto l) {
     using L = decltype(l);
-    return launch_units(rgb_to_yuv_kernel<L::PIX>, (int64_t)(H / 2) * ((W + 7) / 8), s, src, static_cast<typename L::Sample*>(dst), H, W, L::consts(pix));
+    if ((W & L::SX) | (H & L::SY)) return hipErrorInvalidValue;   // (a subsampled axis is even)
+    return launch_units(rgb_to_yuv_kernel<L::PIX>, (int64_t)((H + 1) / 2) * ((W + 7) / 8), s, src, static_cast<typename L::Sample*>(dst), H, W, L::consts(pix));
   });
 }

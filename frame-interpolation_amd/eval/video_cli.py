@@ -4,7 +4,9 @@ mid-frame of each consecutive pair between them.  --times_to_interpolate T multi
 that are interpolated further stay float32 on the GPU, only the output is quantised, and every frame is extracted once).  Video in, video out: the frames stay 8-bit Y'CbCr 4:2:0 from the file to the GPU and
 back (a frame stream with pix 'i420': the colour conversion runs inside the engine's tile cut and quantisation, one feature extraction
 per frame), no PNGs, no ffmpeg, a few frames of memory.  A 10-bit stream (C420p10, `ffmpeg -pix_fmt yuv420p10le`) stays 10-bit the same
-way (pix 'i010'): no flag is needed, the header says it.
+way (pix 'i010'): no flag is needed, the header says it.  --chroma any also takes planar 4:2:2 and 4:4:4 video (C422, C444, C422p10,
+C444p10: pix 'i422' / 'i444' / 'i210' / 'i410'), which keeps its chroma resolution all the way; --matrix bt2020nc decodes and encodes with the
+BT.2020 non-constant-luminance matrix.
 
   cd frame-interpolation_amd
   python -m eval.video_cli --model_path <model dir> --input in.y4m --output out.y4m
@@ -21,7 +23,7 @@ rates), an output that lands on an input frame is that frame, and each push comp
 ancestors in the recursion (FilmStream.select) - 24 -> 60 at T = 3 makes four pair runs per input interval where a full push makes seven.
 Input frames no output lands on are not written; the snap errors and the pair runs made are reported on stderr.
 
-The output header keeps the input's tokens with the frame rate (F) doubled (multiplied by 2^T).  What is read: film_hip/y4m.py (8-bit and 10-bit 4:2:0, progressive).
+The output header keeps the input's tokens with the frame rate (F) doubled (multiplied by 2^T).  What is read: film_hip/y4m.py (8-bit and 10-bit 4:2:0, with --chroma any planar 4:2:2 and 4:4:4; progressive).
 """
 import argparse
 import sys
@@ -44,7 +46,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--block_overlap_height', type=int, default=0,
                     help='Rows every patch takes from its neighbours (cross-faded); 0: disjoint patches; -1: what the align padding holds.')
     ap.add_argument('--block_overlap_width', type=int, default=0, help='The same for columns.')
-    ap.add_argument('--matrix', choices=['bt709', 'bt601'], default='bt709', help="The Y'CbCr matrix of the video.")
+    ap.add_argument('--matrix', choices=['bt709', 'bt601', 'bt2020nc'], default='bt709',
+                    help="The Y'CbCr matrix of the video (bt2020nc: BT.2020 non-constant luminance, what 10-bit UHD / HDR video is coded with).")
+    ap.add_argument('--chroma', choices=['420', 'any'], default='420',
+                    help='420 (default): only 4:2:0 video is read, anything else is refused before the model is loaded.  any: planar 4:2:2 and '
+                         '4:4:4 (C422, C444, C422p10, C444p10) too - the frames stay in that subsampling from the file to the GPU and back.')
     ap.add_argument('--full_range', action='store_true', default=None,
                     help='Full-range samples (0..255, 10-bit: 0..1023); default: what the header says (XCOLORRANGE=FULL), else limited range.')
     ap.add_argument('--scene_cut', type=int, default=0, metavar='PERMILLE',
@@ -61,9 +67,14 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def stream_pix(reader) -> str:
+    """The stream layout of a reader's frames: its `.pix` ('i420' ... 'i410'), else I010 for a 10-bit reader and I420 for any other."""
+    return getattr(reader, 'pix', None) or ('i010' if getattr(reader, 'depth', 8) == 10 else 'i420')
+
+
 def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', full_range: Optional[bool] = None, scene_cut: int = 0,
                       cuts: Optional[list] = None, times: int = 1) -> int:
-    """Streams reader's frames through an I420 stream (I010 for a 10-bit reader) of `it` (an eval.interpolator.Interpolator) and writes the doubled video to the
+    """Streams reader's frames through a stream of the reader's layout (stream_pix: I420, I010 for a 10-bit reader, I422 ... I410) of `it` (an eval.interpolator.Interpolator) and writes the doubled video to the
     binary file object `out`.  Returns the number of frames written.  One input frame and one mid-frame are alive at a time (two input
     frames with scene_cut).  scene_cut > 0 (permille, engine option "scene_cut"): a push after the first that returns no mid-frame is
     a scene cut - the previous input frame is written again in the mid-frame's place; `cuts` (a list) receives the index of every input
@@ -75,7 +86,7 @@ def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', ful
         raise ValueError(f'times_to_interpolate must be 1 .. 6, got {times}')
     full = reader.full_range if full_range is None else bool(full_range)
     writer = y4m.Y4MWriter(out, y4m.multiply_rate(reader.tokens, 1 << times))
-    with it.open_stream(reader.height, reader.width, pix='i010' if getattr(reader, 'depth', 8) == 10 else 'i420', matrix=matrix, full_range=full,
+    with it.open_stream(reader.height, reader.width, pix=stream_pix(reader), matrix=matrix, full_range=full,
                         **({'scene_cut': int(scene_cut)} if scene_cut else {}), **({'times': times} if times != 1 else {})) as st:
         prev = None
         for i, frame in enumerate(reader):
@@ -119,7 +130,7 @@ def convert_frame_rate(it, reader: y4m.Y4MReader, out, rate_out, matrix: str = '
             e = abs(rt.error(j)[0])
             err_max, err_sum = max(err_max, e), err_sum + e
 
-    with it.open_stream(reader.height, reader.width, pix='i010' if getattr(reader, 'depth', 8) == 10 else 'i420', matrix=matrix, full_range=full,
+    with it.open_stream(reader.height, reader.width, pix=stream_pix(reader), matrix=matrix, full_range=full,
                         **({'scene_cut': int(scene_cut)} if scene_cut else {}), **({'times': times} if times != 1 else {})) as st:
         prev = None
         selected = pending = tuple(range(1, per_push + 1))
@@ -168,7 +179,7 @@ def main(argv=None) -> int:
             raise SystemExit(f'--fps: {e}')
     fin = sys.stdin.buffer if args.input == '-' else open(args.input, 'rb')
     try:
-        reader = y4m.Y4MReader(fin, depths=(8, 10))       # (the header's refusals come before the model is loaded)
+        reader = y4m.Y4MReader(fin, depths=(8, 10), chroma=y4m.CHROMAS if args.chroma == 'any' else ('420',))       # (the header's refusals come before the model is loaded)
         if rate_out is not None:                          # (and those of the conversion)
             if reader.rate is None:
                 raise SystemExit('--fps needs the frame rate of the input: its header has no F token')

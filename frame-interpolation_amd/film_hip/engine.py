@@ -29,21 +29,33 @@ FILM_ERR_NO_DEVICE = -3
 FILM_ERR_NOMEM = -5
 # pixel types of a frame stream (film_stream_open)
 FILM_PIX_F32, FILM_PIX_U8, FILM_PIX_I420, FILM_PIX_NV12, FILM_PIX_I010, FILM_PIX_P010 = 0, 1, 16, 17, 32, 33
+FILM_PIX_I422, FILM_PIX_I444, FILM_PIX_I210, FILM_PIX_I410 = 20, 24, 36, 40
 PIX = {'f32': (FILM_PIX_F32, np.float32), 'u8': (FILM_PIX_U8, np.uint8), 'i420': (FILM_PIX_I420, np.uint8), 'nv12': (FILM_PIX_NV12, np.uint8),
-       'i010': (FILM_PIX_I010, np.uint16), 'p010': (FILM_PIX_P010, np.uint16)}
+       'i010': (FILM_PIX_I010, np.uint16), 'p010': (FILM_PIX_P010, np.uint16), 'i422': (FILM_PIX_I422, np.uint8), 'i444': (FILM_PIX_I444, np.uint8),
+       'i210': (FILM_PIX_I210, np.uint16), 'i410': (FILM_PIX_I410, np.uint16)}
 YUV420 = ('i420', 'nv12', 'i010', 'p010')      # the 4:2:0 layouts: a frame is an array [H * 3 // 2, W] of samples
-# colour flags of the 4:2:0 pixel types (added to the layout code)
-FILM_YUV_BT601, FILM_YUV_FULL = 0x100, 0x400
-YUV_MATRIX = {'bt709': 0, 'bt601': FILM_YUV_BT601}
+YUV422 = ('i422', 'i210')                      # planar 4:2:2: [2 * H, W] (the Y plane, then Cb [H, W / 2] and Cr [H, W / 2])
+YUV444 = ('i444', 'i410')                      # planar 4:4:4: [3 * H, W]
+YUV = YUV420 + YUV422 + YUV444
+# colour flags of the Y'CbCr pixel types (added to the layout code)
+FILM_YUV_BT601, FILM_YUV_FULL, FILM_YUV_BT2020 = 0x100, 0x400, 0x2000
+YUV_MATRIX = {'bt709': 0, 'bt601': FILM_YUV_BT601, 'bt2020nc': FILM_YUV_BT2020}
 
 
 def pix_code(pix: str, matrix: str = 'bt709', full_range: bool = False) -> int:
-    """The `pix` argument of the C-ABI: the layout code of `pix` plus the colour flags (which only the 4:2:0 layouts accept)."""
+    """The `pix` argument of the C-ABI: the layout code of `pix` plus the colour flags (which only the Y'CbCr layouts accept)."""
     if pix not in PIX:
         raise ValueError(f'pix must be one of {sorted(PIX)}, got {pix!r}')
     if matrix not in YUV_MATRIX:
-        raise ValueError(f"matrix must be 'bt709' or 'bt601', got {matrix!r}")
+        raise ValueError(f"matrix must be 'bt709', 'bt601' or 'bt2020nc', got {matrix!r}")
     return PIX[pix][0] | YUV_MATRIX[matrix] | (FILM_YUV_FULL if full_range else 0)
+
+
+def frame_shape(pix: str, h: int, w: int) -> Tuple[int, ...]:
+    """The array shape of one h x w frame of pixel type `pix`: [H, W, 3] for the RGB types, [H * 3 // 2, W] / [2 * H, W] / [3 * H, W] samples
+    for the 4:2:0 / 4:2:2 / 4:4:4 layouts."""
+    h, w = int(h), int(w)
+    return (h * 3 // 2, w) if pix in YUV420 else (2 * h, w) if pix in YUV422 else (3 * h, w) if pix in YUV444 else (h, w, 3)
 # film_image_metrics flags (include/film_hip.h); METRIC_FLAGS maps the metric names of eval/metrics.py to them
 FILM_METRIC_L1, FILM_METRIC_L2, FILM_METRIC_PSNR, FILM_METRIC_SSIM, FILM_METRIC_CLIP = 1, 2, 4, 8, 16
 METRIC_FLAGS = {'l1': FILM_METRIC_L1, 'l2': FILM_METRIC_L2, 'psnr': FILM_METRIC_PSNR, 'ssim': FILM_METRIC_SSIM}
@@ -74,7 +86,7 @@ EXPORTED_SYMBOLS = (
     'film_interpolate_sequence', 'film_sequence_plan_json', 'film_image_metrics', 'film_tiling_json',
     'film_debug_arena', 'film_debug_run_op', 'film_debug_tile_map',
     'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json',
-    'film_to_yuv420', 'film_debug_yuv_cut', 'film_frame_histogram', 'film_stream_cut_info',
+    'film_to_yuv420', 'film_to_yuv', 'film_debug_yuv_cut', 'film_frame_histogram', 'film_stream_cut_info',
     'film_stream_pair_plan_json', 'film_stream_schedule_json', 'film_stream_select', 'film_stream_select_schedule_json')
 
 _lib = None
@@ -144,6 +156,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_debug_tile_map.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     lib.film_to_yuv420.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
+    lib.film_to_yuv.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     lib.film_debug_yuv_cut.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     lib.film_stream_open.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -199,7 +212,8 @@ def frame_histogram_device(ptr: int, h: int, w: int, hist_ptr: int, pix: str = '
                            stream: Optional[int] = None) -> None:
     """film_frame_histogram: the 3 x 256 sample histogram (include/film_hip.h, "Scene cuts") of ONE h x w device frame of pixel type `pix`
     into 768 device uint32 at hist_ptr (overwritten), asynchronous on `stream` of the current device.  ptr must be 4-byte aligned and an
-    8-bit frame lie in an allocation of whole 32-bit words.  A 10-bit sample ('i010' | 'p010') counts in the bin of its code >> 2.  Needs no engine."""
+    8-bit frame lie in an allocation of whole 32-bit words (so must a 10-bit 4:4:4 frame of odd size).  A 10-bit sample ('i010' | 'p010' | 'i210' |
+    'i410') counts in the bin of its code >> 2.  Needs no engine."""
     rc = load_library().film_frame_histogram(ctypes.c_void_p(ptr), int(h), int(w), pix_code(pix, matrix, full_range), ctypes.c_void_p(hist_ptr),
                                              ctypes.c_void_p(stream) if stream else None)
     if rc != 0:
@@ -225,7 +239,9 @@ class FilmStream:
     frame.  Frames and results are [H,W,3] float32 ('f32') or uint8 ('u8': x = u8 / 255, result = eval.util.to_uint8's bytes), or
     8-bit Y'CbCr 4:2:0 frames ('i420', 'nv12') as uint8 [H * 3 // 2, W]: the Y plane, then the Cb and Cr planes (I420) or the plane of
     CbCr pairs (NV12), with `matrix` 'bt709' | 'bt601' and limited or full range (the arithmetic: include/film_hip.h); or 10-bit 4:2:0
-    frames ('i010': the code in bits 0-9, = yuv420p10le; 'p010': the code in bits 6-15) as uint16 [H * 3 // 2, W] with the same planes.
+    frames ('i010': the code in bits 0-9, = yuv420p10le; 'p010': the code in bits 6-15) as uint16 [H * 3 // 2, W] with the same planes;
+    or planar 4:2:2 ('i422' uint8, 'i210' uint16; W even) as [2 * H, W] and planar 4:4:4 ('i444' uint8, 'i410' uint16; any size) as [3 * H, W].
+    `matrix` may also be 'bt2020nc' (BT.2020 non-constant luminance), with every Y'CbCr layout.
     With the engine option "scene_cut" > 0 (FilmEngine.open_stream(scene_cut=...)) a push that the histogram rule calls a scene cut returns
     None / False like a first push, and cut_info() tells the two apart.
     times = T > 1 (FilmEngine.open_stream(times=...); engine option "stream_times", read when the stream opens): a primed push returns
@@ -242,7 +258,7 @@ class FilmStream:
         self.times = int(times)                  # what the engine option said when the stream was opened
         self.per_push = (1 << self.times) - 1    # frames of a primed push with every position selected
         self.selection = tuple(range(1, self.per_push + 1))   # select(): the 1-based positions a primed push returns, ascending
-        self.shape = (int(h) * 3 // 2, int(w)) if pix in YUV420 else (int(h), int(w), 3)
+        self.shape = frame_shape(pix, h, w)
         self.pix = pix
         self.dtype = PIX[pix][1]
         bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
@@ -548,8 +564,8 @@ class FilmEngine:
     def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32', matrix: str = 'bt709',
                     full_range: bool = False, scene_cut: int = 0, times: int = 1) -> FilmStream:
         """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix 'f32' | 'u8' |
-        'i420' | 'nv12' | 'i010' | 'p010', the latter four (8-bit and 10-bit 4:2:0, h and w even) with the colour `matrix` 'bt709' | 'bt601' and
-        limited or full range.
+        'i420' | 'nv12' | 'i010' | 'p010' (8-bit and 10-bit 4:2:0, h and w even) | 'i422' | 'i210' (4:2:2, w even) | 'i444' | 'i410' (4:4:4), the
+        Y'CbCr ones with the colour `matrix` 'bt709' | 'bt601' | 'bt2020nc' and limited or full range.
         scene_cut: 0 .. 1000 permille; non-zero sets the engine option "scene_cut" (include/film_hip.h) before the stream opens - a handle
         option like block_overlap, so it STAYS set for later streams of this engine until set_option('scene_cut', 0); 0 (default) leaves
         the engine as it is.
@@ -625,6 +641,15 @@ class FilmEngine:
                                       ctypes.c_void_p(stream) if stream else None)
         if rc != 0:
             raise FilmError(rc, 'film_to_yuv420 failed')
+
+    def to_yuv_device(self, src_ptr: int, dst_ptr: int, h: int, w: int, pix: str = 'i444', matrix: str = 'bt709',
+                      full_range: bool = False, stream: Optional[int] = None) -> None:
+        """film_to_yuv: h x w x 3 device floats -> one frame of ANY Y'CbCr layout (4:2:0, 4:2:2, 4:4:4; device bytes, or 16-bit words for the
+        10-bit layouts: dst_ptr 2-byte aligned), asynchronous."""
+        rc = self._lib.film_to_yuv(ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), int(h), int(w), pix_code(pix, matrix, full_range),
+                                   ctypes.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise FilmError(rc, 'film_to_yuv failed')
 
     def set_option(self, key: str, value: int) -> None:
         self._check(self._lib.film_set_option(self._h, key.encode(), int(value)))

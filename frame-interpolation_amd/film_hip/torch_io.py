@@ -11,7 +11,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .engine import PIX, YUV420, FilmEngine, frame_histogram_device
+from .engine import PIX, YUV, YUV420, YUV422, FilmEngine, frame_histogram_device
 
 
 def pinned_frame(shape) -> 'np.ndarray':
@@ -60,14 +60,16 @@ def pix_dtypes(pix: str):
 
 def frame_histogram(frame: torch.Tensor, pix: str = 'u8') -> torch.Tensor:
     """film_frame_histogram of one CUDA frame: [H,W,3] uint8 ('u8') or float32 ('f32'), or an 8-bit 4:2:0 frame as uint8 [H * 3 // 2, W]
-    ('i420' | 'nv12'), or a 10-bit one as int16 / uint16 [H * 3 // 2, W] ('i010' | 'p010': bin = code >> 2) -> int64 [3, 256] on the frame's
+    ('i420' | 'nv12'), or a 10-bit one as int16 / uint16 [H * 3 // 2, W] ('i010' | 'p010': bin = code >> 2), or a planar 4:2:2 / 4:4:4 frame
+    [2 * H, W] ('i422' | 'i210') / [3 * H, W] ('i444' | 'i410'), uint8 or 16-bit -> int64 [3, 256] on the frame's
     device: the number of samples of every plane with every 8-bit code (include/film_hip.h, "Scene cuts").  Asynchronous on the current
     torch stream."""
     assert frame.is_cuda and frame.dtype in pix_dtypes(pix)
     frame = frame.contiguous()
-    if pix in YUV420:
-        assert frame.dim() == 2 and frame.shape[0] % 3 == 0
-        h, w = frame.shape[0] * 2 // 3, frame.shape[1]
+    if pix in YUV:
+        num, den = (3, 2) if pix in YUV420 else (2, 1) if pix in YUV422 else (3, 1)      # rows of the frame per row of the picture
+        assert frame.dim() == 2 and frame.shape[0] % num == 0
+        h, w = frame.shape[0] * den // num, frame.shape[1]
     else:
         assert frame.dim() == 3 and frame.shape[-1] == 3
         h, w = frame.shape[0], frame.shape[1]
@@ -178,6 +180,8 @@ class DeviceInterpolator:
         'i420' / 'nv12': 8-bit 4:2:0 frames as uint8 [h * 3 // 2, w] tensors, converted inside the cut and the quantisation.
         'i010' / 'p010': 10-bit 4:2:0 frames as 16-bit tensors of that shape - torch.int16 (taken as a bit pattern) or torch.uint16 where
         the installed torch has it; the mid-frame comes back in the dtype that was pushed.
+        'i422' / 'i210' and 'i444' / 'i410': planar 4:2:2 / 4:4:4 frames as [2 * h, w] / [3 * h, w] tensors, uint8 or 16-bit as above.
+        matrix: 'bt709' | 'bt601' | 'bt2020nc', for every Y'CbCr layout.
         scene_cut (0 .. 1000 permille): non-zero sets the ENGINE option "scene_cut" before the stream opens, and it stays set (like block_overlap).
         times (1 .. 6): the stream's "stream_times" - a primed push returns [2^times - 1, ...] frames, the times_to_interpolate recursion."""
         bs = self._block_shape

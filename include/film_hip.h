@@ -253,10 +253,23 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  * function (PQ, HLG, gamma) is not the engine's business: the network sees the non-linear samples it was given. */
 #define FILM_PIX_I010   32      /* Y[H][W], Cb[H/2][W/2], Cr[H/2][W/2], little-endian uint16, code in bits 0-9 (= yuv420p10le, Y4M C420p10): H*W*3 bytes */
 #define FILM_PIX_P010   33      /* Y[H][W], CbCr[H/2][W/2][2], little-endian uint16, code in bits 6-15 (what VCN / VA-API / D3D decoders emit): H*W*3 bytes */
+/* Planar Y'CbCr 4:2:2 and 4:4:4 frames, 8-bit and 10-bit: mezzanine / broadcast video (4:2:2, mostly 10-bit), screen captures, animation masters and
+ * graphics (4:4:4).  Same flags, same fusion into the cut and the quantisation ("The 4:2:2 and 4:4:4 arithmetic" below).  S = the samples of a frame:
+ * 2 H W (4:2:2) or 3 H W (4:4:4).  4:2:2 needs an even W (an odd H is fine; the message contains "4:2:2 needs an even width"); 4:4:4 takes any
+ * H, W >= 1, like the RGB layouts.  Device pointers stay 4-byte aligned (2-byte for a 10-bit dst of the quantiser), inside an allocation of whole
+ * 32-bit words; in a batch (film_debug_yuv_cut, B > 1) frame b starts at sample b * S, which for an odd-sized 4:4:4 frame is no word boundary: the
+ * kernels read the aligned words that hold a sample. */
+#define FILM_PIX_I422   20      /* Y[H][W], Cb[H][W/2], Cr[H][W/2], bytes (= yuv422p, Y4M C422): 2*H*W bytes */
+#define FILM_PIX_I444   24      /* Y[H][W], Cb[H][W], Cr[H][W], bytes (= yuv444p, Y4M C444): 3*H*W bytes */
+#define FILM_PIX_I210   36      /* as I422, little-endian uint16, code in bits 0-9 (= yuv422p10le, Y4M C422p10): 4*H*W bytes */
+#define FILM_PIX_I410   40      /* as I444, little-endian uint16, code in bits 0-9 (= yuv444p10le, Y4M C444p10): 6*H*W bytes */
 #define FILM_YUV_BT601  0x100   /* matrix: absent = BT.709 */
 #define FILM_YUV_FULL   0x400   /* range: absent = limited (8-bit 16..235 / 16..240, 10-bit 64..940 / 64..960) */
+#define FILM_YUV_BT2020 0x2000  /* matrix: BT.2020 non-constant luminance, (Kr, Kb) = (0.2627, 0.0593) - what nearly all 10-bit UHD / HDR content is coded with.
+                                 * Valid with every Y'CbCr layout and with FILM_YUV_FULL; together with FILM_YUV_BT601: FILM_ERR_INVALID ("pix" in the
+                                 * message).  Constant-luminance BT.2020 and the transfer function (PQ, HLG) stay the caller's business. */
 /* The 4:2:0 arithmetic.  Every operation is float32 with one rounding, no fused multiply-add.  (Kr, Kb) = (0.2126, 0.0722) for BT.709,
- * (0.299, 0.114) for BT.601, Kg = 1 - Kr - Kb; every constant below is computed from them in double and rounded to float32 once.
+ * (0.299, 0.114) for BT.601, (0.2627, 0.0593) for BT.2020 (FILM_YUV_BT2020), Kg = 1 - Kr - Kb; every constant below is computed from them in double and rounded to float32 once.
  *   In (bytes -> RGB).  Per-byte tables, IEEE division on the host: limited range y[v] = (float(v) - 16) / 219, c[v] = (float(v) - 128) / 224;
  *     full range y[v] = float(v) / 255, c[v] = (float(v) - 128) / 255.  Pixel (y, x) takes the chroma sample (y >> 1, x >> 1): chroma is
  *     treated as centre-sited and replicated.  With y = y[Y], cb = c[Cb], cr = c[Cr]:
@@ -282,9 +295,16 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *     C = q10(m * 896 + 512);  full: Y = q10(Yf * 1023), C = q10(m * 1023 + 512).  I010 stores the code, P010 stores code << 6: the ignored bits
  *     are written as zero.
  *   A frame whose decoded RGB stays inside the gamut returns code for code (tests/test_yuv10_cpu.py checks it for all four colour settings).
- *   Not provided (at either depth): 12-bit and deeper samples; 4:2:2 / 4:4:4 layouts; a BT.2020 matrix (no flag bit selects one: 0x200 / 0x800 and every other bit stay
- *   refused); sited bilinear chroma (MPEG-2 left siting - the box treatment is consistent in and out); 4:2:0 frames on film_interpolate /
- *   film_interpolate_sequence themselves (film_to_yuv420 converts their results).
+ * The 4:2:2 and 4:4:4 arithmetic (FILM_PIX_I422 / I444: the 8-bit arithmetic; FILM_PIX_I210 / I410: the 10-bit one, code v = w & 1023).  Constants,
+ * operation order, clips, code rules, ranges and quantisers are those of the two sections above.  Only the chroma pairing and the mean change.
+ *   In.   4:2:2: pixel (y, x) takes the chroma sample (y, x >> 1).  4:4:4: pixel (y, x) takes the chroma sample (y, x).  As in 4:2:0 the pairing
+ *     follows the frame coordinate, not the tile's.
+ *   Out.  4:2:2: m = (c[y][2k] + c[y][2k+1]) * 0.5f.  4:4:4: m = c[y][x], no mean.
+ *   A frame whose decoded RGB stays inside the gamut returns code for code (tests/test_yuv_chroma_cpu.py checks it for both depths, the three
+ *   subsamplings and all six colour settings).
+ *   Not provided (at any depth): 12-bit and deeper samples; semi-planar or packed 4:2:2 / 4:4:4 (NV16, P210, NV24, v210, Y410); constant-luminance
+ *   BT.2020 (flag bits 0x200 / 0x800 / 0x1000 and every other bit stay refused); sited bilinear chroma (MPEG-2 left siting - the box treatment is
+ *   consistent in and out); Y'CbCr frames on film_interpolate / film_interpolate_sequence themselves (film_to_yuv converts their results).
  * Scene cuts.  Across a cut a stream would interpolate between two unrelated pictures.  The engine offers an exact per-frame statistic
  * computed where the frame already lies, an integer decision rule, and a stream that resets itself (option "scene_cut").  Integers only.
  *   Histogram of a frame: uint32_t hist[3][256], hist[p][v] = the number of samples of plane p with 8-bit code v.
@@ -295,7 +315,9 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                     The colour flags are validated as everywhere else and otherwise ignored: the statistic is about the stored codes.
  *     FILM_PIX_I010 / FILM_PIX_P010   the same planes and sample counts; a sample with 10-bit code v counts in bin v >> 2, so the [3][256]
  *                     layout, S and the rule below do not change.
- *     Every plane sums to its sample count.  S = the samples of one frame: 3 H W for RGB, 3 H W / 2 for 4:2:0.
+ *     FILM_PIX_I422 / I444 / I210 / I410   plane 0 = the H * W Y samples, planes 1 and 2 = the Cb and Cr samples: H * W / 2 each (4:2:2) or H * W each
+ *                     (4:4:4); a 10-bit sample counts in bin code >> 2.
+ *     Every plane sums to its sample count.  S = the samples of one frame: 3 H W for RGB and 4:4:4, 3 H W / 2 for 4:2:0, 2 H W for 4:2:2.
  *   Distance: D = sum over p, v of |h1[p][v] - h0[p][v]|, an int64 with 0 <= D <= 2 S; the score is D / (2 S).  Moving content leaves it
  *     at 0 (a permutation of the samples has the same histogram); two frames with no code in common give 1.
  *   Rule: with "scene_cut" = k, 1 <= k <= 1000 (permille), a pair of frames is a cut iff 1000 D >= k * 2 S, compared in 64-bit integers.
@@ -503,9 +525,9 @@ int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int 
  * [0, B * block_h * block_w).  Then FILM_ERR_NO_DEVICE on a plan-only handle.  Not on any forward path. */
 int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h,
                         int block_w, int tile0, int ntiles, void* stream);
-/* film_debug_yuv_cut: ONE cut of a batch of B 4:2:0 frames (frame b at byte b * H * W * 3 / 2 of frames_dev - b * H * W * 3 for a 10-bit layout -,
+/* film_debug_yuv_cut: ONE cut of a batch of B Y'CbCr frames (frame b at sample b * S of frames_dev, S = 3 H W / 2, 2 H W or 3 H W samples of one or two bytes,
  * a 4-byte aligned DEVICE pointer into an allocation of whole 32-bit words) into float32 RGB tiles: film_debug_tile_map mode 0 with pix =
- * FILM_PIX_I420 / FILM_PIX_NV12 / FILM_PIX_I010 / FILM_PIX_P010 plus colour flags - same geometry, same tile buffer, same refusals (and those of `pix` above), reached through the
+ * a Y'CbCr layout (FILM_PIX_I420 / NV12 / I422 / I444 / I010 / P010 / I210 / I410) plus colour flags - same geometry, same tile buffer, same refusals (and those of `pix` above), reached through the
  * dispatch a 4:2:0 stream's push cuts with (tests/test_yuv_gpu.py).  Not on any forward path. */
 int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h, int block_w,
                        int tile0, int ntiles, void* stream);
@@ -539,8 +561,12 @@ int film_to_uint8(const float* src, unsigned char* dst, int64_t n, void* stream)
  * alignment of dst for the 8-bit layouts, 2-byte alignment for the 10-bit ones (else FILM_ERR_INVALID; whole 32-bit words are
  * stored where it allows); asynchronous on `stream` (NULL: the default stream) of the current device, like film_to_uint8.  What a 4:2:0
  * stream's push quantises its result with; results of film_interpolate / film_interpolate_sequence leave as 4:2:0 through it too.
- * FILM_ERR_INVALID: a NULL pointer, H or W < 1 or odd, pix no 4:2:0 pixel type. */
+ * FILM_ERR_INVALID: a NULL pointer, H or W < 1 or odd, pix no 4:2:0 pixel type (FILM_YUV_BT2020 is accepted; the 4:2:2 / 4:4:4 layouts are film_to_yuv's). */
 int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream);
+/* film_to_yuv420's contract for EVERY Y'CbCr layout: "Out" of the layout's arithmetic, one frame of S samples (4:2:0: 3 H W / 2, H and W even; 4:2:2:
+ * 2 H W, W even; 4:4:4: 3 H W, any size), bytes or 16-bit words (dst then 2-byte aligned).  What a Y'CbCr stream's push quantises its result with.
+ * FILM_ERR_INVALID: a NULL pointer, H or W < 1, a size the layout refuses, an odd 10-bit dst, pix no Y'CbCr pixel type. */
+int film_to_yuv(const float* src, void* dst, int H, int W, int pix, void* stream);
 
 /* The variable-restore half of `tf.compat.v2.saved_model.load(model_path)` (reference eval/interpolator.py:148): reads the
  * checkpoint of a Keras SavedModel - `<path>/variables/variables.index` + `.data-0000N-of-0000M`, written by model.save()

@@ -10,7 +10,8 @@ device-resident), `push_i420` / `push_nv12` (the same on 8-bit 4:2:0 frames, whe
 4:2:0 frames, where the tree has them), `sequence`
 (film_interpolate_sequence over a long sequence, per generated frame) and, at the first point, the host-buffer calls `host_pair`
 (film_interpolate on numpy arrays, as bench.py's host_buffers), `host_push_f32`, `host_push_u8`, `host_push_i420`, `host_push_nv12`,
-`host_push_i010`, `host_push_p010`.
+`host_push_i010`, `host_push_p010`; and, for trees that have the planar 4:2:2 / 4:4:4 layouts, `push_i422`, `push_i444`, `push_i210`, `push_i410` and
+their `host_` forms.
 The 8-bit 4:2:0 rows are compared with the BASELINE's `push_u8` / `host_push_u8` (what such a caller had before: RGB bytes), the 10-bit rows
 with the BASELINE's `push_i420` / `host_push_i420` (what such a caller had before: the frames truncated to 8 bits), whose spread over the
 rounds is reported next to them.  --rows / --points restrict a run to some measurements.
@@ -74,6 +75,7 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
     has_stream = hasattr(eng, 'open_stream')
     has_yuv = 'i420' in getattr(engine_mod, 'PIX', {})
     has_yuv10 = 'i010' in getattr(engine_mod, 'PIX', {})
+    has_chroma = 'i444' in getattr(engine_mod, 'PIX', {})      # planar 4:2:2 / 4:4:4, 8- and 10-bit
     has_scene = scene_cut and hasattr(engine_mod, 'frame_histogram_device')
     want = lambda key: rows is None or key in rows      # noqa: E731
     out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {}}
@@ -124,12 +126,13 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
                     res['push_u8'] = timed(lambda: st.push(x8[nxt(4)]), n)
             yuv = {}
             if has_yuv and h % 2 == 0 and w % 2 == 0:      # the frames as 4:2:0, converted by the engine itself
-                for pix in ('i420', 'nv12') + (('i010', 'p010') if has_yuv10 else ()):
+                for pix in ('i420', 'nv12') + (('i010', 'p010') if has_yuv10 else ()) + (('i422', 'i444', 'i210', 'i410') if has_chroma else ()):
                     if not (want('push_' + pix) or want('host_push_' + pix) or (pix == 'i420' and has_scene and pi == 0)):
                         continue
-                    yuv[pix] = [torch.empty((h * 3 // 2, w), dtype=torch.int16 if pix in ('i010', 'p010') else torch.uint8, device='cuda') for _ in x]
+                    rows_of = {'i422': 2 * h, 'i210': 2 * h, 'i444': 3 * h, 'i410': 3 * h}.get(pix, h * 3 // 2)
+                    yuv[pix] = [torch.empty((rows_of, w), dtype=torch.int16 if pix in ('i010', 'p010', 'i210', 'i410') else torch.uint8, device='cuda') for _ in x]
                     for src, dst in zip(x, yuv[pix]):
-                        eng.to_yuv420_device(src.data_ptr(), dst.data_ptr(), h, w, pix)
+                        (eng.to_yuv_device if has_chroma else eng.to_yuv420_device)(src.data_ptr(), dst.data_ptr(), h, w, pix)
                     torch.cuda.synchronize()
                     if want('push_' + pix):
                         with it.stream(h, w, pix) as st:
@@ -420,12 +423,12 @@ def histogram_alone(calls=50, reps=3):
     out = {}
     hist = torch.empty(768, dtype=torch.int32, device='cuda')
     for size, (h, w) in (('1080p', (1080, 1920)), ('4K', (2160, 3840))):
-        for pix in ('u8', 'i420', 'nv12', 'f32') + (('i010', 'p010') if 'i010' in PIX else ()):
-            shape = (h * 3 // 2, w) if pix in ('i420', 'nv12', 'i010', 'p010') else (h, w, 3)
+        for pix in ('u8', 'i420', 'nv12', 'f32') + (('i010', 'p010') if 'i010' in PIX else ()) + (('i422', 'i444', 'i210', 'i410') if 'i444' in PIX else ()):
+            shape = (h * 3 // 2, w) if pix in ('i420', 'nv12', 'i010', 'p010') else (2 * h, w) if pix in ('i422', 'i210') else (3 * h, w) if pix in ('i444', 'i410') else (h, w, 3)
             for data in ('random', 'constant'):
                 if pix == 'f32':
                     fr = torch.rand(shape, device='cuda') if data == 'random' else torch.full(shape, 0.5, device='cuda')
-                elif pix in ('i010', 'p010'):      # 10-bit codes in 16-bit words (int16 as a bit pattern), P010's in bits 6-15
+                elif pix in ('i010', 'p010', 'i210', 'i410'):      # 10-bit codes in 16-bit words (int16 as a bit pattern), P010's in bits 6-15
                     fr = torch.randint(0, 1024, shape, dtype=torch.int32, device='cuda') if data == 'random' else torch.full(shape, 64, dtype=torch.int32, device='cuda')
                     fr = (((fr << 6) + 32768) % 65536 - 32768 if pix == 'p010' else fr).to(torch.int16)
                 else:
@@ -554,11 +557,12 @@ def main(argv=None):
         lines.append(f'{name}:')
         pts = [r['points'][name] for r in this]
         base = [r['points'][name] for r in runs.get('baseline', [])]
-        for key in ('pair', 'push_u8', 'push_i420', 'host_push_u8', 'host_push_i420'):
+        for key in ('pair', 'push_u8', 'push_i420', 'push_i010', 'host_push_u8', 'host_push_i420', 'host_push_i010'):
             if base and key in base[0]:
                 lines.append(f'  {"baseline " + key:<22} {_stat([s for p in base for s in p[key]])}')
-        for key in ('pair', 'push_f32', 'push_u8', 'push_i420', 'push_nv12', 'push_i010', 'push_p010', 'sequence', 'host_pair', 'host_push_f32',
-                    'host_push_u8', 'host_push_i420', 'host_push_nv12', 'host_push_i010', 'host_push_p010'):
+        for key in ('pair', 'push_f32', 'push_u8', 'push_i420', 'push_nv12', 'push_i010', 'push_p010', 'push_i422', 'push_i444', 'push_i210', 'push_i410',
+                    'sequence', 'host_pair', 'host_push_f32', 'host_push_u8', 'host_push_i420', 'host_push_nv12', 'host_push_i010', 'host_push_p010',
+                    'host_push_i422', 'host_push_i444', 'host_push_i210', 'host_push_i410'):
             if key in pts[0]:
                 lines.append(f'  {key:<22} {_stat([s for p in pts for s in p[key]])}' + ('   (per generated frame)' if key == 'sequence' else ''))
         lines.append(f'  push_f32 == pair, bit for bit: {all(p.get("identical", True) for p in pts)}')
@@ -575,7 +579,10 @@ def main(argv=None):
         # against the baseline's show that the 8-bit paths are unchanged
         for mine, theirs in [(f'{pre}push_{pix}', f'{pre}push_u8') for pre in ('', 'host_') for pix in ('i420', 'nv12')] + \
                             [(f'{pre}push_{pix}', f'{pre}push_i420') for pre in ('', 'host_') for pix in ('i010', 'p010')] + \
-                            ([(f'{pre}push_{pix}', f'{pre}push_{pix}') for pre in ('', 'host_') for pix in ('u8', 'i420')] if 'push_i010' in pts[0] or 'host_push_i010' in pts[0] else []):
+                            ([(f'{pre}push_{pix}', f'{pre}push_{pix}') for pre in ('', 'host_') for pix in ('u8', 'i420')] if 'push_i010' in pts[0] or 'host_push_i010' in pts[0] else []) + \
+                            ([(f'{pre}push_{pix}', f'{pre}push_{pix}') for pre in ('', 'host_') for pix in ('i010', 'p010')] +      # the planar 4:2:2 / 4:4:4 pushes against the
+                             [(f'{pre}push_{pix}', f'{pre}push_u8') for pre in ('', 'host_') for pix in ('i422', 'i444', 'i210', 'i410')]      # baseline's 8-bit RGB push
+                             if any(k in pts[0] for k in ('push_i444', 'host_push_i444', 'push_i410', 'host_push_i410')) else []):
             if base and theirs in base[0] and mine in pts[0]:
                 bm = [statistics.mean(p[theirs]) for p in base]
                 d = [statistics.mean(p[mine]) - b for p, b in zip(pts, bm)]
