@@ -56,15 +56,14 @@ int tile_geometry(film_t* h, int H, int W, int block_h, int block_w, int align, 
   }
   return FILM_OK;
 }
-// The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the Y'CbCr layouts (pix_layout,
-// pix_is_yuv, pix_is_yuv10, pix_sample_bytes, pix_chroma_shift: film_kernels.h).
+// The `pix` argument of the stream and debug entry points: a layout in bits 0-7 plus the colour flags of the Y'CbCr layouts (kPixLayouts and its
+// look-ups: film_kernels.h).
 // FILM_OK, or the refusal of a pix value for H x W frames (include/film_hip.h, film_stream_open)
 int check_pix(film_t* h, int pix, int H, int W) {
   const int layout = pix_layout(pix), flags = pix & ~0xff;
   constexpr int known = FILM_YUV_BT601 | FILM_YUV_BT2020 | FILM_YUV_FULL;
   if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !pix_is_yuv(pix))
-    return fail(h, FILM_ERR_INVALID, "bad pix layout %d: FILM_PIX_F32 (0), FILM_PIX_U8 (1), FILM_PIX_I420 (16), FILM_PIX_NV12 (17), FILM_PIX_I422 (20), FILM_PIX_I444 (24), "
-                "FILM_PIX_I010 (32), FILM_PIX_P010 (33), FILM_PIX_I210 (36) or FILM_PIX_I410 (40)", layout);
+    return fail(h, FILM_ERR_INVALID, "bad pix layout %d: %s", layout, pix_layout_list(false).c_str());
   if (flags & ~known)
     return fail(h, FILM_ERR_INVALID, "bad pix 0x%x: unknown bits 0x%x set (flags: FILM_YUV_BT601 0x100, FILM_YUV_FULL 0x400, FILM_YUV_BT2020 0x2000)", (unsigned)pix,
                 (unsigned)(flags & ~known));
@@ -396,7 +395,7 @@ int film_frame_histogram(const void* frame_dev, int H, int W, int pix, uint32_t*
 int film_to_yuv(const float* src, void* dst, int H, int W, int pix, void* stream) {
   if (!src || !dst || H < 1 || W < 1 || !pix_is_yuv(pix) || check_pix(nullptr, pix, H, W) != FILM_OK) return FILM_ERR_INVALID;
   if (pix_is_yuv10(pix) && (reinterpret_cast<uintptr_t>(dst) & 1)) return FILM_ERR_INVALID;   // (16-bit samples)
-  return film_launch_rgb_to_yuv420(src, dst, H, W, pix, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
+  return film_launch_rgb_to_yuv(src, dst, H, W, pix, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
 }
 
 int film_to_yuv420(const float* src, void* dst, int H, int W, int pix, void* stream) {
@@ -732,8 +731,7 @@ int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, i
   if (!h) return FILM_ERR_INVALID;
   if (!frames_dev || !tiles_dev) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: NULL argument");
   if (!pix_is_yuv(pix))
-    return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: bad pix layout %d: FILM_PIX_I420 (16), FILM_PIX_NV12 (17), FILM_PIX_I422 (20), FILM_PIX_I444 (24), "
-                "FILM_PIX_I010 (32), FILM_PIX_P010 (33), FILM_PIX_I210 (36) or FILM_PIX_I410 (40)", pix_layout(pix));
+    return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: bad pix layout %d: %s", pix_layout(pix), pix_layout_list(true).c_str());
   int rc = check_pix(h, pix, H, W);
   if (rc) return rc;
   if (reinterpret_cast<uintptr_t>(frames_dev) & 3) return fail(h, FILM_ERR_INVALID, "film_debug_yuv_cut: the frames of a Y'CbCr pix must be 4-byte aligned");

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/film_hip.h"   // FILM_PIX_*, FILM_YUV_*: the `pix` of the frame I/O launchers
@@ -382,25 +383,35 @@ hipError_t film_launch_warp(const WarpParams& p, hipStream_t s);
 hipError_t film_launch_pack_flow(const PackFlowParams& p, hipStream_t s);
 // frame_kernels.hip: frame I/O.  `pix` is the public value (include/film_hip.h): a layout in bits 0-7 plus FILM_YUV_BT601 / FILM_YUV_BT2020 /
 // FILM_YUV_FULL for the Y'CbCr layouts; the launchers decode it.  Overlapped tiles and their cross-fade when p.ovy | p.ovx.
-// What a pix value says, for the launchers, film_engine.cpp and the host-only build alike: its layout, Y'CbCr or not, 10-bit Y'CbCr or not, the
-// bytes of one sample (float32 for FILM_PIX_F32 and for what check_pix refuses anyway), and the chroma shifts of a Y'CbCr layout.
-inline int pix_layout(int pix) { return pix & 0xff; }
-inline bool pix_is_yuv10(int pix) {   // 16-bit samples
-  const int l = pix_layout(pix);
-  return l == FILM_PIX_I010 || l == FILM_PIX_P010 || l == FILM_PIX_I210 || l == FILM_PIX_I410;
+// What a pix value says, for the launchers, film_engine.cpp and the host-only build alike, is one row of kPixLayouts, in the order of the codes (the
+// order a refusal lists them in): depth 0 for the two RGB layouts, else the bits of a Y'CbCr code (10-bit codes lie in 16-bit samples); a chroma plane
+// of an H x W frame is [H >> sy][W >> sx] - 4:2:0 (1, 1), 4:2:2 (1, 0), 4:4:4 (0, 0) -, or the two are one plane of CbCr pairs (semi_planar).
+struct PixLayout { int code; const char* name; int depth, sample_bytes, sx, sy; bool semi_planar; };
+#define FILM_PIX_ROW(NAME, ...) {FILM_PIX_##NAME, "FILM_PIX_" #NAME, __VA_ARGS__}
+constexpr PixLayout kPixLayouts[] = {
+  FILM_PIX_ROW(F32, 0, (int)sizeof(float), 0, 0, false), FILM_PIX_ROW(U8, 0, 1, 0, 0, false),
+  FILM_PIX_ROW(I420, 8, 1, 1, 1, false),  FILM_PIX_ROW(NV12, 8, 1, 1, 1, true),   FILM_PIX_ROW(I422, 8, 1, 1, 0, false),  FILM_PIX_ROW(I444, 8, 1, 0, 0, false),
+  FILM_PIX_ROW(I010, 10, 2, 1, 1, false), FILM_PIX_ROW(P010, 10, 2, 1, 1, true),  FILM_PIX_ROW(I210, 10, 2, 1, 0, false), FILM_PIX_ROW(I410, 10, 2, 0, 0, false),
+};
+#undef FILM_PIX_ROW
+constexpr int pix_layout(int pix) { return pix & 0xff; }
+constexpr PixLayout pix_row(int pix) {
+  for (const PixLayout& r : kPixLayouts)
+    if (r.code == pix_layout(pix)) return r;
+  return {-1, "", 0, (int)sizeof(float), 0, 0, false};   // what check_pix refuses: no Y'CbCr layout, float32 samples, no chroma shifts
 }
-inline bool pix_is_yuv(int pix) {
-  const int l = pix_layout(pix);
-  return l == FILM_PIX_I420 || l == FILM_PIX_NV12 || l == FILM_PIX_I422 || l == FILM_PIX_I444 || pix_is_yuv10(pix);
-}
-inline int pix_sample_bytes(int pix) { return pix_is_yuv10(pix) ? 2 : pix_is_yuv(pix) || pix_layout(pix) == FILM_PIX_U8 ? 1 : (int)sizeof(float); }
-// A chroma plane of an H x W Y'CbCr frame is [H >> sy][W >> sx]: (1, 1) for 4:2:0, (1, 0) for 4:2:2, (0, 0) for 4:4:4 (and for what is no Y'CbCr layout)
+constexpr bool pix_is_yuv(int pix) { return pix_row(pix).depth != 0; }
+constexpr bool pix_is_yuv10(int pix) { return pix_row(pix).depth == 10; }   // 16-bit samples
+constexpr int pix_sample_bytes(int pix) { return pix_row(pix).sample_bytes; }
 struct ChromaShift { int sx, sy; };
-inline ChromaShift pix_chroma_shift(int pix) {
-  const int l = pix_layout(pix);
-  if (l == FILM_PIX_I444 || l == FILM_PIX_I410 || !pix_is_yuv(pix)) return {0, 0};
-  if (l == FILM_PIX_I422 || l == FILM_PIX_I210) return {1, 0};
-  return {1, 1};
+constexpr ChromaShift pix_chroma_shift(int pix) { return {pix_row(pix).sx, pix_row(pix).sy}; }
+// "FILM_PIX_I420 (16), FILM_PIX_NV12 (17), ... or FILM_PIX_I410 (40)": the layouts as a refusal names them, all ten or the Y'CbCr ones
+inline std::string pix_layout_list(bool yuv_only) {
+  std::string s;
+  for (const PixLayout& r : kPixLayouts)
+    if (r.depth || !yuv_only)
+      s += (s.empty() ? "" : &r == std::end(kPixLayouts) - 1 ? " or " : ", ") + std::string(r.name) + " (" + std::to_string(r.code) + ")";
+  return s;
 }
 // pad + image_to_patches of tiles [tile0, tile0 + ntiles): p.src is float32 [B][H][W][3] (FILM_PIX_F32), or bytes that the cut converts - [B][H][W][3]
 // (FILM_PIX_U8: float32(byte) / 255.0f, correctly rounded) or 4:2:0 frames of H * W * 3 / 2 bytes each (FILM_PIX_I420 / NV12; H and W even),
@@ -414,9 +425,8 @@ hipError_t film_launch_join_tiles(const TileMapParams& p, hipStream_t s);
 // write_image's rounding on the device: dst[i] = uint8(clip(src[i] * 255, 0, 255) + 0.5)  (eval/util.py:51-52)
 hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipStream_t s);
 // float32 [H][W][3] -> one Y'CbCr frame (clip, matrix, the chroma mean of the subsampling - 2 x 2, 1 x 2 or none -, quantisation): bytes for
-// the 8-bit layouts, uint16 for the 10-bit ones (dst then 2-byte aligned, else hipErrorInvalidValue).  The name is its first use's: it serves
-// every Y'CbCr layout.
-hipError_t film_launch_rgb_to_yuv420(const float* src, void* dst, int H, int W, int pix, hipStream_t s);
+// the 8-bit layouts, uint16 for the 10-bit ones (dst then 2-byte aligned, else hipErrorInvalidValue).
+hipError_t film_launch_rgb_to_yuv(const float* src, void* dst, int H, int W, int pix, hipStream_t s);
 // The sample histogram of one frame (include/film_hip.h, "Scene cuts"): hist[p * 256 + v] = the samples of plane p with 8-bit code v.  The launcher
 // zeroes the 768 counters first: a call overwrites.  `frame` is 4-byte aligned and its allocation a whole number of 32-bit words (as for the 8-bit
 // cuts).  A lane reads FILM_HIST_VEC_BYTES per step; the grid is min(what the frame needs, FILM_HIST_WG_PER_CU workgroups per compute unit) of

@@ -137,7 +137,7 @@ int stream_deliver(film_t* h, const Plan* Q, const TileMapParams& tp, const Stre
   j.tile0 = 0; j.ntiles = tp.bh * tp.bw; j.src = Q->at("out"); j.dst = p.joined;
   HIPCHK(h, film_launch_join_tiles(j, s));
   if (p.quant && pix_is_yuv(fs.pix))
-    HIPCHK(h, film_launch_rgb_to_yuv420(p.joined, p.quant, fs.H, fs.W, fs.pix, s));
+    HIPCHK(h, film_launch_rgb_to_yuv(p.joined, p.quant, fs.H, fs.W, fs.pix, s));
   else if (p.quant)
     HIPCHK(h, film_launch_to_uint8(p.joined, static_cast<uint8_t*>(p.quant), (int64_t)fr.nv, s));
   if (p.host) HIPCHK(h, hipMemcpyAsync(p.host, p.quant ? p.quant : (void*)p.joined, fr.fb, hipMemcpyDeviceToHost, s));

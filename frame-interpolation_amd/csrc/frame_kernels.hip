@@ -717,8 +717,9 @@ Yuv10Consts yuv10_consts(int pix) {
   return k;
 }
 
-// f(YuvLayout<LAYOUT>()) for the Y'CbCr layout of a pix value: how both launchers below choose their kernel instance
-template <class F> hipError_t with_yuv_layout(int pix, F f) {
+// f(YuvLayout<LAYOUT>()) for the Y'CbCr layout of a pix value: how both launchers below choose their kernel instance (constexpr for the
+// static_asserts behind it, which walk its cases at compile time)
+template <class F> constexpr hipError_t with_yuv_layout(int pix, F f) {
   switch (pix_layout(pix)) {
     case FILM_PIX_I420: return f(YuvLayout<FILM_PIX_I420>());
     case FILM_PIX_NV12: return f(YuvLayout<FILM_PIX_NV12>());
@@ -731,6 +732,21 @@ template <class F> hipError_t with_yuv_layout(int pix, F f) {
     default: return hipErrorInvalidValue;
   }
 }
+// kPixLayouts (film_kernels.h) says what the cases above and the YuvLayout of each say: checked here, over all 256 layout codes
+template <class F> constexpr bool every_layout_code(F ok) {
+  for (int code = 0; code < 256; code++)
+    if (!ok(code, pix_row(code))) return false;
+  return true;
+}
+static_assert(every_layout_code([](int code, PixLayout r) { return (with_yuv_layout(code, [](auto) { return hipSuccess; }) == hipSuccess) == (r.depth != 0); }),
+              "with_yuv_layout's cases are the Y'CbCr rows of kPixLayouts");
+static_assert(every_layout_code([](int code, PixLayout r) {
+                return with_yuv_layout(code, [r](auto l) {
+                  using L = decltype(l);
+                  return L::PIX == r.code && L::WIDE == (r.depth == 10) && L::SEMI_PLANAR == r.semi_planar && L::SX == r.sx && L::SY == r.sy &&
+                         (int)sizeof(typename L::Sample) == r.sample_bytes ? hipSuccess : hipErrorUnknown;
+                }) != hipErrorUnknown; }),
+              "every YuvLayout's WIDE, SEMI_PLANAR, SX, SY and Sample are its row of kPixLayouts");
 
 }  // namespace
 
@@ -769,7 +785,7 @@ hipError_t film_launch_to_uint8(const float* src, uint8_t* dst, int64_t n, hipSt
   return launch_units(to_uint8_kernel, (n + 3) / 4, s, src, dst, n);
 }
 
-hipError_t film_launch_rgb_to_yuv420(const float* src, void* dst, int H, int W, int pix, hipStream_t s) {
+hipError_t film_launch_rgb_to_yuv(const float* src, void* dst, int H, int W, int pix, hipStream_t s) {
   if (H <= 0 || W <= 0) return hipErrorInvalidValue;
   if (pix_is_yuv10(pix) && (reinterpret_cast<uintptr_t>(dst) & 1)) return hipErrorInvalidValue;
   return with_yuv_layout(pix, [&](auto l) {

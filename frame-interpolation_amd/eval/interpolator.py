@@ -177,9 +177,8 @@ class Interpolator:
     """(extension) A frame stream of h x w frames (film_hip.engine.FilmStream; film_stream_*): push() one frame at a time and get
     the mid-frame between it and the one pushed before, bit-identical to self(previous, frame, dt) with align, block_shape and
     block_overlap as set, with one feature extraction per frame.  pix 'f32': float32 frames, not clipped; 'u8': uint8 frames in
-    and util.to_uint8's bytes out; 'i420' / 'nv12': 8-bit Y'CbCr 4:2:0 frames as uint8 [h * 3 // 2, w] in and out, with the colour
-    `matrix` ('bt709' | 'bt601' | 'bt2020nc') and limited or full range; 'i010' / 'p010': the same with 10-bit samples, uint16 [h * 3 // 2, w];
-    'i422' / 'i210': planar 4:2:2 (w even) as uint8 / uint16 [2 * h, w]; 'i444' / 'i410': planar 4:4:4 as uint8 / uint16 [3 * h, w].  scene_cut (0 .. 1000 permille): non-zero sets the engine option "scene_cut"
+    and util.to_uint8's bytes out; a Y'CbCr layout of film_hip/pixfmt.py's table: frames as FilmStream describes them in and out, with the
+    colour `matrix` ('bt709' | 'bt601' | 'bt2020nc') and limited or full range.  scene_cut (0 .. 1000 permille): non-zero sets the engine option "scene_cut"
     (include/film_hip.h) before the stream opens - a push that the histogram rule calls a scene cut then returns None like a first push,
     FilmStream.cut_info() tells why; an engine option like block_overlap, so it stays set; 0 (default) leaves the engine as it is.
     times (1 .. 6): a primed push returns the [2^times - 1, ...] frames of the times_to_interpolate recursion between the two frames, each

@@ -69,7 +69,7 @@ def build_parser() -> argparse.ArgumentParser:
 
 def stream_pix(reader) -> str:
     """The stream layout of a reader's frames: its `.pix` ('i420' ... 'i410'), else I010 for a 10-bit reader and I420 for any other."""
-    return getattr(reader, 'pix', None) or ('i010' if getattr(reader, 'depth', 8) == 10 else 'i420')
+    return getattr(reader, 'pix', None) or y4m.PIX_NAME.get(('420', getattr(reader, 'depth', 8)), 'i420')
 
 
 def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', full_range: Optional[bool] = None, scene_cut: int = 0,

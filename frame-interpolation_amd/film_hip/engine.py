@@ -13,6 +13,7 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
+from . import pixfmt
 from .options import Options, PUBLISHED
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -27,15 +28,10 @@ FILM_ERR_INVALID = -1
 FILM_ERR_STATE = -2
 FILM_ERR_NO_DEVICE = -3
 FILM_ERR_NOMEM = -5
-# pixel types of a frame stream (film_stream_open)
-FILM_PIX_F32, FILM_PIX_U8, FILM_PIX_I420, FILM_PIX_NV12, FILM_PIX_I010, FILM_PIX_P010 = 0, 1, 16, 17, 32, 33
-FILM_PIX_I422, FILM_PIX_I444, FILM_PIX_I210, FILM_PIX_I410 = 20, 24, 36, 40
-PIX = {'f32': (FILM_PIX_F32, np.float32), 'u8': (FILM_PIX_U8, np.uint8), 'i420': (FILM_PIX_I420, np.uint8), 'nv12': (FILM_PIX_NV12, np.uint8),
-       'i010': (FILM_PIX_I010, np.uint16), 'p010': (FILM_PIX_P010, np.uint16), 'i422': (FILM_PIX_I422, np.uint8), 'i444': (FILM_PIX_I444, np.uint8),
-       'i210': (FILM_PIX_I210, np.uint16), 'i410': (FILM_PIX_I410, np.uint16)}
-YUV420 = ('i420', 'nv12', 'i010', 'p010')      # the 4:2:0 layouts: a frame is an array [H * 3 // 2, W] of samples
-YUV422 = ('i422', 'i210')                      # planar 4:2:2: [2 * H, W] (the Y plane, then Cb [H, W / 2] and Cr [H, W / 2])
-YUV444 = ('i444', 'i410')                      # planar 4:4:4: [3 * H, W]
+# pixel types of a frame stream (film_stream_open): film_hip/pixfmt.py's table under the names of include/film_hip.h, FILM_PIX_F32 ... FILM_PIX_I410
+globals().update({'FILM_PIX_' + lay.name.upper(): lay.code for lay in pixfmt.LAYOUTS})
+PIX = {lay.name: (lay.code, lay.dtype) for lay in pixfmt.LAYOUTS}
+YUV420, YUV422, YUV444 = pixfmt.names('420'), pixfmt.names('422'), pixfmt.names('444')      # frames [H * 3 // 2, W], [2 * H, W], [3 * H, W]
 YUV = YUV420 + YUV422 + YUV444
 # colour flags of the Y'CbCr pixel types (added to the layout code)
 FILM_YUV_BT601, FILM_YUV_FULL, FILM_YUV_BT2020 = 0x100, 0x400, 0x2000
@@ -51,11 +47,7 @@ def pix_code(pix: str, matrix: str = 'bt709', full_range: bool = False) -> int:
     return PIX[pix][0] | YUV_MATRIX[matrix] | (FILM_YUV_FULL if full_range else 0)
 
 
-def frame_shape(pix: str, h: int, w: int) -> Tuple[int, ...]:
-    """The array shape of one h x w frame of pixel type `pix`: [H, W, 3] for the RGB types, [H * 3 // 2, W] / [2 * H, W] / [3 * H, W] samples
-    for the 4:2:0 / 4:2:2 / 4:4:4 layouts."""
-    h, w = int(h), int(w)
-    return (h * 3 // 2, w) if pix in YUV420 else (2 * h, w) if pix in YUV422 else (3 * h, w) if pix in YUV444 else (h, w, 3)
+frame_shape = pixfmt.frame_shape
 # film_image_metrics flags (include/film_hip.h); METRIC_FLAGS maps the metric names of eval/metrics.py to them
 FILM_METRIC_L1, FILM_METRIC_L2, FILM_METRIC_PSNR, FILM_METRIC_SSIM, FILM_METRIC_CLIP = 1, 2, 4, 8, 16
 METRIC_FLAGS = {'l1': FILM_METRIC_L1, 'l2': FILM_METRIC_L2, 'psnr': FILM_METRIC_PSNR, 'ssim': FILM_METRIC_SSIM}
@@ -212,8 +204,8 @@ def frame_histogram_device(ptr: int, h: int, w: int, hist_ptr: int, pix: str = '
                            stream: Optional[int] = None) -> None:
     """film_frame_histogram: the 3 x 256 sample histogram (include/film_hip.h, "Scene cuts") of ONE h x w device frame of pixel type `pix`
     into 768 device uint32 at hist_ptr (overwritten), asynchronous on `stream` of the current device.  ptr must be 4-byte aligned and an
-    8-bit frame lie in an allocation of whole 32-bit words (so must a 10-bit 4:4:4 frame of odd size).  A 10-bit sample ('i010' | 'p010' | 'i210' |
-    'i410') counts in the bin of its code >> 2.  Needs no engine."""
+    8-bit frame lie in an allocation of whole 32-bit words (so must a 10-bit 4:4:4 frame of odd size).  A 10-bit sample counts in the bin of its code >> 2.
+    Needs no engine."""
     rc = load_library().film_frame_histogram(ctypes.c_void_p(ptr), int(h), int(w), pix_code(pix, matrix, full_range), ctypes.c_void_p(hist_ptr),
                                              ctypes.c_void_p(stream) if stream else None)
     if rc != 0:
@@ -563,9 +555,9 @@ class FilmEngine:
 
     def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32', matrix: str = 'bt709',
                     full_range: bool = False, scene_cut: int = 0, times: int = 1) -> FilmStream:
-        """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix 'f32' | 'u8' |
-        'i420' | 'nv12' | 'i010' | 'p010' (8-bit and 10-bit 4:2:0, h and w even) | 'i422' | 'i210' (4:2:2, w even) | 'i444' | 'i410' (4:4:4), the
-        Y'CbCr ones with the colour `matrix` 'bt709' | 'bt601' | 'bt2020nc' and limited or full range.
+        """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix is a name of
+        film_hip/pixfmt.py's table (FilmStream describes the frames; 4:2:0 needs h and w even, 4:2:2 w even), the Y'CbCr ones with the colour
+        `matrix` 'bt709' | 'bt601' | 'bt2020nc' and limited or full range.
         scene_cut: 0 .. 1000 permille; non-zero sets the engine option "scene_cut" (include/film_hip.h) before the stream opens - a handle
         option like block_overlap, so it STAYS set for later streams of this engine until set_option('scene_cut', 0); 0 (default) leaves
         the engine as it is.
@@ -633,23 +625,23 @@ class FilmEngine:
         if rc != 0:
             raise FilmError(rc, 'film_to_uint8 failed')
 
+    def _to_yuv(self, symbol: str, src_ptr, dst_ptr, h, w, pix, matrix, full_range, stream) -> None:
+        rc = getattr(self._lib, symbol)(ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), int(h), int(w), pix_code(pix, matrix, full_range),
+                                        ctypes.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise FilmError(rc, f'{symbol} failed')
+
     def to_yuv420_device(self, src_ptr: int, dst_ptr: int, h: int, w: int, pix: str = 'i420', matrix: str = 'bt709',
                          full_range: bool = False, stream: Optional[int] = None) -> None:
-        """film_to_yuv420: h x w x 3 device floats -> one 4:2:0 frame of h * w * 3 // 2 device bytes ('i420' | 'nv12') or 16-bit words ('i010' |
-        'p010': dst_ptr 2-byte aligned), asynchronous."""
-        rc = self._lib.film_to_yuv420(ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), int(h), int(w), pix_code(pix, matrix, full_range),
-                                      ctypes.c_void_p(stream) if stream else None)
-        if rc != 0:
-            raise FilmError(rc, 'film_to_yuv420 failed')
+        """film_to_yuv420: h x w x 3 device floats -> one 4:2:0 frame of h * w * 3 // 2 device bytes, or 16-bit words for the 10-bit layouts
+        (dst_ptr 2-byte aligned), asynchronous."""
+        self._to_yuv('film_to_yuv420', src_ptr, dst_ptr, h, w, pix, matrix, full_range, stream)
 
     def to_yuv_device(self, src_ptr: int, dst_ptr: int, h: int, w: int, pix: str = 'i444', matrix: str = 'bt709',
                       full_range: bool = False, stream: Optional[int] = None) -> None:
         """film_to_yuv: h x w x 3 device floats -> one frame of ANY Y'CbCr layout (4:2:0, 4:2:2, 4:4:4; device bytes, or 16-bit words for the
         10-bit layouts: dst_ptr 2-byte aligned), asynchronous."""
-        rc = self._lib.film_to_yuv(ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), int(h), int(w), pix_code(pix, matrix, full_range),
-                                   ctypes.c_void_p(stream) if stream else None)
-        if rc != 0:
-            raise FilmError(rc, 'film_to_yuv failed')
+        self._to_yuv('film_to_yuv', src_ptr, dst_ptr, h, w, pix, matrix, full_range, stream)
 
     def set_option(self, key: str, value: int) -> None:
         self._check(self._lib.film_set_option(self._h, key.encode(), int(value)))
@@ -751,7 +743,7 @@ class FilmEngine:
         index n - tile0 of the tile buffer.  u8 (cut only): the frames are bytes in a 4-byte aligned allocation of whole 32-bit words.
         Asynchronous on `stream` (default stream when None)."""
         bh, bw = (int(block_shape[0]), int(block_shape[1])) if block_shape else (1, 1)
-        self._check(self._lib.film_debug_tile_map(self._h, {'cut': 0, 'join': 1}[mode], FILM_PIX_U8 if u8 else FILM_PIX_F32,
+        self._check(self._lib.film_debug_tile_map(self._h, {'cut': 0, 'join': 1}[mode], pix_code('u8' if u8 else 'f32'),
                                                   ctypes.c_void_p(frames_ptr), ctypes.c_void_p(tiles_ptr), int(b), int(h), int(w),
                                                   int(align or 0), bh, bw, int(tile0), int(ntiles),
                                                   ctypes.c_void_p(stream) if stream else None))

@@ -11,7 +11,8 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .engine import PIX, YUV, YUV420, YUV422, FilmEngine, frame_histogram_device
+from . import pixfmt
+from .engine import FilmEngine, frame_histogram_device
 
 
 def pinned_frame(shape) -> 'np.ndarray':
@@ -53,26 +54,19 @@ def patches_to_image(patches: torch.Tensor, block_shape: List[int]) -> torch.Ten
 def pix_dtypes(pix: str):
     """The torch dtypes a frame of pixel type `pix` may have.  A 10-bit frame is 16-bit words: torch.int16 is taken as a bit pattern, and
     torch.uint16 where the installed torch has it."""
-    if PIX[pix][1].__name__ == 'uint16':
+    if pixfmt.BY_NAME[pix].dtype.__name__ == 'uint16':
         return (torch.int16,) + ((torch.uint16,) if hasattr(torch, 'uint16') else ())
     return (torch.float32,) if pix == 'f32' else (torch.uint8,)
 
 
 def frame_histogram(frame: torch.Tensor, pix: str = 'u8') -> torch.Tensor:
-    """film_frame_histogram of one CUDA frame: [H,W,3] uint8 ('u8') or float32 ('f32'), or an 8-bit 4:2:0 frame as uint8 [H * 3 // 2, W]
-    ('i420' | 'nv12'), or a 10-bit one as int16 / uint16 [H * 3 // 2, W] ('i010' | 'p010': bin = code >> 2), or a planar 4:2:2 / 4:4:4 frame
-    [2 * H, W] ('i422' | 'i210') / [3 * H, W] ('i444' | 'i410'), uint8 or 16-bit -> int64 [3, 256] on the frame's
-    device: the number of samples of every plane with every 8-bit code (include/film_hip.h, "Scene cuts").  Asynchronous on the current
-    torch stream."""
+    """film_frame_histogram of one CUDA frame of pixel type `pix` (film_hip/pixfmt.py; shape and dtype as FilmStream describes them: [H,W,3]
+    uint8 or float32, or a Y'CbCr frame [H * 3 // 2, W] / [2 * H, W] / [3 * H, W], uint8 or - 10-bit, bin = code >> 2 - int16 / uint16)
+    -> int64 [3, 256] on the frame's device: the number of samples of every plane with every 8-bit code (include/film_hip.h, "Scene
+    cuts").  Asynchronous on the current torch stream."""
     assert frame.is_cuda and frame.dtype in pix_dtypes(pix)
     frame = frame.contiguous()
-    if pix in YUV:
-        num, den = (3, 2) if pix in YUV420 else (2, 1) if pix in YUV422 else (3, 1)      # rows of the frame per row of the picture
-        assert frame.dim() == 2 and frame.shape[0] % num == 0
-        h, w = frame.shape[0] * den // num, frame.shape[1]
-    else:
-        assert frame.dim() == 3 and frame.shape[-1] == 3
-        h, w = frame.shape[0], frame.shape[1]
+    h, w = pixfmt.frame_size(pix, tuple(frame.shape))
     hist = torch.empty((3, 256), dtype=torch.int32, device=frame.device)
     with torch.cuda.device(frame.device):
         frame_histogram_device(frame.data_ptr(), h, w, hist.data_ptr(), pix, stream=torch.cuda.current_stream(frame.device).cuda_stream)
@@ -177,10 +171,9 @@ class DeviceInterpolator:
                times: int = 1) -> DeviceStream:
         """Extension: a frame stream of h x w frames (film_stream_*), padded / tiled like batch(): push one CUDA tensor at a time, float32
         or ('u8') uint8, and get the mid-frame with the frame before - bit-identical to batch(previous, frame), one extraction per frame.
-        'i420' / 'nv12': 8-bit 4:2:0 frames as uint8 [h * 3 // 2, w] tensors, converted inside the cut and the quantisation.
-        'i010' / 'p010': 10-bit 4:2:0 frames as 16-bit tensors of that shape - torch.int16 (taken as a bit pattern) or torch.uint16 where
-        the installed torch has it; the mid-frame comes back in the dtype that was pushed.
-        'i422' / 'i210' and 'i444' / 'i410': planar 4:2:2 / 4:4:4 frames as [2 * h, w] / [3 * h, w] tensors, uint8 or 16-bit as above.
+        A Y'CbCr pix (film_hip/pixfmt.py; FilmStream describes the frames): tensors of the frame's shape, converted inside the cut and the
+        quantisation; uint8, or for the 10-bit layouts 16-bit - torch.int16 (taken as a bit pattern) or torch.uint16 where the installed
+        torch has it; the mid-frame comes back in the dtype that was pushed.
         matrix: 'bt709' | 'bt601' | 'bt2020nc', for every Y'CbCr layout.
         scene_cut (0 .. 1000 permille): non-zero sets the ENGINE option "scene_cut" before the stream opens, and it stays set (like block_overlap).
         times (1 .. 6): the stream's "stream_times" - a primed push returns [2^times - 1, ...] frames, the times_to_interpolate recursion."""

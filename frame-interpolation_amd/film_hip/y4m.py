@@ -26,13 +26,15 @@ from typing import BinaryIO, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import pixfmt
+
 MAGIC = b'YUV4MPEG2'
 FRAME = b'FRAME'
 C420 = ('420', '420jpeg', '420mpeg2', '420paldv')
 C420_10 = ('420p10',)      # 10-bit 4:2:0, little-endian 16-bit words
 # the planar 4:2:2 / 4:4:4 tokens: token -> (chroma, depth); and the stream layout (FilmEngine.open_stream's pix) of every (chroma, depth)
-C_OTHER = {'422': ('422', 8), '444': ('444', 8), '422p10': ('422', 10), '444p10': ('444', 10)}
-PIX_NAME = {('420', 8): 'i420', ('420', 10): 'i010', ('422', 8): 'i422', ('422', 10): 'i210', ('444', 8): 'i444', ('444', 10): 'i410'}
+PIX_NAME = pixfmt.Y4M_PIX
+C_OTHER = {c + ('p10' if d == 10 else ''): (c, d) for c, d in PIX_NAME if c != '420'}
 CHROMAS = ('420', '422', '444')
 _MAX_LINE = 4096
 
@@ -168,7 +170,7 @@ class Y4MReader:
     """Iterates over the frames of a YUV4MPEG2 stream (a binary file object) as uint8 arrays [H * 3 // 2, W].  depths=(8, 10) also takes
     C420p10 streams, whose frames are uint16 arrays of that shape (decoded from little-endian bytes); `depth` says which it is.
     chroma=('420', '422', '444') also takes C422 / C444 (and, with depths=(8, 10), C422p10 / C444p10) streams, whose frames are [2 * H, W] /
-    [3 * H, W]; `chroma` says which it is and `pix` names the stream layout ('i420', 'i010', 'i422', 'i210', 'i444', 'i410')."""
+    [3 * H, W]; `chroma` says which it is and `pix` names the stream layout (PIX_NAME)."""
 
     def __init__(self, f: BinaryIO, depths: Sequence[int] = (8,), chroma: Sequence[str] = ('420',)):
         self._f = f

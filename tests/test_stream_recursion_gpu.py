@@ -157,8 +157,10 @@ def test_u8_recursive_stream(published, mem):
     assert not np.array_equal(util.to_uint8(other), got[1][0])
 
 
-def _yuv_scene(R, layout, f, h, w, seed):
+def _yuv_scene(layout, f, h, w, seed):
     """f 4:2:0 frames (clean samples) of a scene that moves by (2, -2) px per frame."""
+    import yuv_ref
+    R = yuv_ref.FORMATS[layout]
     base = R.designed_frames(1, h, w, seed)[0]
     Y, Cb, Cr = R.unpack(base, layout)
     if layout == 'i010':      # (the designed 10-bit words carry junk in the ignored bits: keep the codes)
@@ -169,16 +171,14 @@ def _yuv_scene(R, layout, f, h, w, seed):
 @pytest.mark.parametrize('mem', ['host', 'device'])
 @pytest.mark.parametrize('layout,matrix,full', [('i420', 'bt709', False), ('i010', 'bt601', True)])
 def test_yuv_recursive_stream(published, layout, matrix, full, mem):
-    """'i420' / 'i010', T = 2: the samples are film_to_yuv420 of the float32 T = 2 stream on the frames dequantised by tests/yuv_ref.py /
-    tests/yuv10_ref.py (whose agreement with the device cut tests/test_yuv_gpu.py and tests/test_yuv10_gpu.py establish)."""
+    """'i420' / 'i010', T = 2: the samples are film_to_yuv420 of the float32 T = 2 stream on the frames dequantised by tests/yuv_ref.py
+    (whose agreement with the device cut tests/test_yuv_gpu.py and tests/test_yuv10_gpu.py establish)."""
     import torch
-    if layout == 'i420':
-        import yuv_ref as R
-    else:
-        import yuv10_ref as R
+    import yuv_ref
+    R = yuv_ref.FORMATS[layout]
     opt, weights, eng = published
     h, w = 128, 192
-    frames = _yuv_scene(R, layout, 3, h, w, seed=h + w)
+    frames = _yuv_scene(layout, 3, h, w, seed=h + w)
     key = ('yuv', layout)
     if key not in _WANT:
         x = np.stack([R.yuv_in(fr, layout, matrix, full) for fr in frames])
@@ -336,14 +336,9 @@ def test_video_cli_times_to_interpolate(published, tmp_path, monkeypatch, colour
         it._align, it._block_shape = align or None, block_shape or None
         return it
 
-    if colour == '420jpeg':
-        import yuv_ref as R
-        layout, kw = 'i420', {}
-    else:
-        import yuv10_ref as R
-        layout, kw = 'i010', {'colour': '420p10'}
+    layout, kw = ('i420', {}) if colour == '420jpeg' else ('i010', {'colour': '420p10'})
     n = 4
-    frames = _yuv_scene(R, layout, n, 64, 64, seed=5)
+    frames = _yuv_scene(layout, n, 64, 64, seed=5)
     src, dst = tmp_path / 'in.y4m', tmp_path / 'out.y4m'
     tokens = y4m.header_tokens(64, 64, (24, 1), **kw)
     with open(src, 'wb') as f:

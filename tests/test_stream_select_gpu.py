@@ -133,14 +133,9 @@ def test_selected_pushes_of_quantised_streams(published, pix, mem):
         h, w, kw = 256, 256, {}
         frames = _frames_u8(N, h, w, seed=31)
     else:
-        if pix == 'i420':
-            import yuv_ref as R
-            kw = dict(matrix='bt709', full_range=False)
-        else:
-            import yuv10_ref as R
-            kw = dict(matrix='bt601', full_range=True)
+        kw = dict(matrix='bt709', full_range=False) if pix == 'i420' else dict(matrix='bt601', full_range=True)
         h, w = 128, 192
-        frames = _yuv_scene(R, pix, N, h, w, seed=h + w)
+        frames = _yuv_scene(pix, N, h, w, seed=h + w)
     want = _full(eng, (pix,), frames, 3, 64, None, pix, **kw)
     got = _push_selected(eng, frames, [(3, 6), (2, 5), (3, 6), (2, 5), None], 3, 64, None, mem, pix, **kw)
     _assert_selected(got, want)
@@ -297,14 +292,9 @@ def test_video_cli_fps(published, tmp_path, monkeypatch, capsys, colour):
         it._align, it._block_shape = align or None, block_shape or None
         return it
 
-    if colour == '420jpeg':
-        import yuv_ref as R
-        layout, kw = 'i420', {}
-    else:
-        import yuv10_ref as R
-        layout, kw = 'i010', {'colour': '420p10'}
+    layout, kw = ('i420', {}) if colour == '420jpeg' else ('i010', {'colour': '420p10'})
     n = 4
-    frames = _yuv_scene(R, layout, n, 64, 64, seed=5)
+    frames = _yuv_scene(layout, n, 64, 64, seed=5)
     src, dst, ref = tmp_path / 'in.y4m', tmp_path / 'out.y4m', tmp_path / 'ref.y4m'
     tokens = y4m.header_tokens(64, 64, (24, 1), **kw)
     with open(src, 'wb') as f:

@@ -208,7 +208,7 @@ def test_tile_map_entry_point_is_declared_exported_and_refuses():
     host = re.split(r'^(?=hipError_t film_launch_\w+\()', src[src.index('hipLaunchKernelGGL('):], flags=re.M)
     named = {re.match(r'hipError_t (\w+)\(', f).group(1): len(re.findall(cut_kernel, f)) for f in host[1:]}
     # float32, u8 and 4:2:0 (every layout through one helper): each named with and without overlap
-    assert named == {'film_launch_cut_tiles': 2 + 2 + 2, 'film_launch_join_tiles': 0, 'film_launch_to_uint8': 0, 'film_launch_rgb_to_yuv420': 0}
+    assert named == {'film_launch_cut_tiles': 2 + 2 + 2, 'film_launch_join_tiles': 0, 'film_launch_to_uint8': 0, 'film_launch_rgb_to_yuv': 0}
     assert not re.search(cut_kernel, host[0])
 
     eng = FilmEngine(TINY, device=-1)

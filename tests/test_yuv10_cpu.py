@@ -1,4 +1,4 @@
-"""CPU tests of the 10-bit Y'CbCr 4:2:0 path (FILM_PIX_I010 / FILM_PIX_P010): tests/yuv10_ref.py - the numpy restatement of "The 10-bit
+"""CPU tests of the 10-bit Y'CbCr 4:2:0 path (FILM_PIX_I010 / FILM_PIX_P010): tests/yuv_ref.py - the numpy restatement of "The 10-bit
 4:2:0 arithmetic" in include/film_hip.h that tests/test_yuv10_gpu.py compares the kernels with, bit for bit - against an independent float64
 evaluation, known answers and its own round trip; I010 <-> P010; which kernel instance and branch every GPU case reaches and that the
 comparison on the designed data finds each planted fault; the refusals of the new pixel codes on a plan-only handle; the Y4M reader /
@@ -11,9 +11,13 @@ import re
 import numpy as np
 import pytest
 
-import yuv10_ref as R
-import yuv_ref as R8
+import yuv_ref as R
 from conftest import ROOT
+
+FMT = R.FORMATS['i010']
+LAYOUTS = FMT.layouts
+COLOURS = [(m, f) for m in ('bt709', 'bt601') for f in (False, True)]      # the four colour settings of the 4:2:0 tests
+FAULTS = ('p010_as_i010', 'i010_as_p010', 'ignored_bits_not_masked', 'eight_bit_scale_shifted', 'cb_cr_swapped', 'chroma_from_tile_coordinate')
 
 
 @pytest.fixture(scope='module')
@@ -33,7 +37,7 @@ def geos():
 def _in_f64(Y, Cb, Cr, matrix, full):
     """From the definition Y' = Kr R + Kg G + Kb B, Cb = (B - Y') / (2 (1 - Kb)), Cr = (R - Y') / (2 (1 - Kr)) in float64, with the 10-bit
     code ranges of Rec. ITU-R BT.709 / BT.2100 (64 .. 940, 64 .. 960, centre 512); G is solved from the luma equation."""
-    Kr, Kb = R8.KR_KB[matrix]
+    Kr, Kb = R.KR_KB[matrix]
     Kg = 1 - Kr - Kb
     Y, Cb, Cr = (a.astype(np.float64) for a in (Y, Cb, Cr))
     y, cb, cr = (Y / 1023, (Cb - 512) / 1023, (Cr - 512) / 1023) if full else ((Y - 64) / 876, (Cb - 512) / 896, (Cr - 512) / 896)
@@ -43,19 +47,19 @@ def _in_f64(Y, Cb, Cr, matrix, full):
     return np.clip(np.stack([r, g, b], -1), 0, 1)
 
 
-@pytest.mark.parametrize('matrix,full', R.COLOURS)
+@pytest.mark.parametrize('matrix,full', COLOURS)
 def test_in_against_float64(matrix, full):
     """Every (Y, Cb, Cr) triple of a 64-step grid plus the extremes: at most 1e-6 apart - five float32 roundings on magnitudes up to 2."""
     v = np.unique(np.concatenate([np.arange(0, 1024, 16), R.EXTREMES]))
     Y, Cb, Cr = np.meshgrid(v, v, v, indexing='ij')
-    got = R.samples_to_rgb(Y, Cb, Cr, matrix, full)
+    got = FMT.samples_to_rgb(Y, Cb, Cr, matrix, full)
     err = np.abs(got.astype(np.float64) - _in_f64(Y, Cb, Cr, matrix, full)).max()
     print(f'{matrix} full={full}: in, max |float32 - float64| = {err:.3g}')
     assert err <= 1e-6
 
 
 def _solid(y, cb, cr, layout='i010'):
-    return R.pack(R.store(np.full((2, 2), y), layout), R.store(np.full((1, 1), cb), layout), R.store(np.full((1, 1), cr), layout), layout)
+    return FMT.pack(FMT.store(np.full((2, 2), y), layout), FMT.store(np.full((1, 1), cb), layout), FMT.store(np.full((1, 1), cr), layout), layout)
 
 
 @pytest.mark.parametrize('matrix', ['bt709', 'bt601'])
@@ -64,55 +68,55 @@ def test_known_answers(matrix):
     table's codes times four (the 10-bit ranges are the 8-bit ranges shifted by two bits, so a colour whose 8-bit value before rounding is
     within 1/8 of its code lands on four times that code) - within one code - and come back within 0.0025 (half a code of Y, 0.5 / 876,
     plus half a code of chroma times the largest coefficient, 1.86 * 0.5 / 896, is 0.0016)."""
-    for layout in R.LAYOUTS:
-        assert not R.yuv_in(_solid(64, 512, 512, layout), layout, matrix, False).any()
-        assert (R.yuv_in(_solid(940, 512, 512, layout), layout, matrix, False) == 1).all()
-        assert not R.yuv_in(_solid(0, 512, 512, layout), layout, matrix, True).any() and (R.yuv_in(_solid(1023, 512, 512, layout), layout, matrix, True) == 1).all()
+    for layout in LAYOUTS:
+        assert not FMT.yuv_in(_solid(64, 512, 512, layout), layout, matrix, False).any()
+        assert (FMT.yuv_in(_solid(940, 512, 512, layout), layout, matrix, False) == 1).all()
+        assert not FMT.yuv_in(_solid(0, 512, 512, layout), layout, matrix, True).any() and (FMT.yuv_in(_solid(1023, 512, 512, layout), layout, matrix, True) == 1).all()
     table = {'bt709': {(1, 0, 0): (63, 102, 240), (0, 1, 0): (173, 42, 26), (0, 0, 1): (32, 240, 118), (1, 1, 1): (235, 128, 128), (0, 0, 0): (16, 128, 128)},
              'bt601': {(1, 0, 0): (81, 90, 240), (0, 1, 0): (145, 54, 34), (0, 0, 1): (41, 240, 110), (1, 1, 1): (235, 128, 128), (0, 0, 0): (16, 128, 128)}}[matrix]
     for rgb, codes8 in table.items():
         x = np.broadcast_to(np.array(rgb, np.float32), (2, 2, 3))
-        for layout in R.LAYOUTS:
-            fr = R.yuv_out(x, layout, matrix, False)
-            got = [int(R.code(p, layout).ravel()[0]) for p in R.unpack(fr, layout)]
+        for layout in LAYOUTS:
+            fr = FMT.yuv_out(x, layout, matrix, False)
+            got = [int(FMT.code(p, layout).ravel()[0]) for p in FMT.unpack(fr, layout)]
             assert all(abs(g - 4 * c) <= 2 for g, c in zip(got, codes8)), (rgb, layout, got)
             if sum(rgb) in (0, 3):
                 assert got == [4 * c for c in codes8]
-            assert np.abs(R.yuv_in(fr, layout, matrix, False) - x).max() <= 0.0025, rgb
+            assert np.abs(FMT.yuv_in(fr, layout, matrix, False) - x).max() <= 0.0025, rgb
 
 
 # ---- round trip, layouts ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('layout', R.LAYOUTS)
-@pytest.mark.parametrize('matrix,full', R.COLOURS)
+@pytest.mark.parametrize('layout', LAYOUTS)
+@pytest.mark.parametrize('matrix,full', COLOURS)
 def test_in_gamut_round_trip_is_the_identity(matrix, full, layout):
     """Replicate in and box mean out are inverse: every 2 x 2 block of a random frame whose four decoded pixels stay strictly inside the
     gamut returns code for code - Y and chroma -, junk in the ignored bits or not.  The blocks inside the gamut are asserted to be a
     non-trivial share: more than a quarter of the frame and more than 200 000 samples."""
     rng = np.random.default_rng(3)
     h, w = 480, 960
-    fr = R.pack(R.store(rng.integers(200, 824, (h, w)), layout), R.store(rng.integers(400, 625, (h // 2, w // 2)), layout),
-                R.store(rng.integers(400, 625, (h // 2, w // 2)), layout), layout)
-    fr = R.with_junk(fr, layout, 4)
-    rgb = R.yuv_in(fr, layout, matrix, full)
+    fr = FMT.pack(FMT.store(rng.integers(200, 824, (h, w)), layout), FMT.store(rng.integers(400, 625, (h // 2, w // 2)), layout),
+                FMT.store(rng.integers(400, 625, (h // 2, w // 2)), layout), layout)
+    fr = FMT.with_junk(fr, layout, 4)
+    rgb = FMT.yuv_in(fr, layout, matrix, full)
     inside = ((rgb > 0) & (rgb < 1)).all(-1)
     block = inside[0::2, 0::2] & inside[0::2, 1::2] & inside[1::2, 0::2] & inside[1::2, 1::2]
     samples = 6 * int(block.sum())
     print(f'{layout} {matrix} full={full}: {block.mean():.3f} of the blocks inside the gamut, {samples} samples')
     assert block.mean() > 0.25 and samples > 200000
-    back = R.yuv_out(rgb, layout, matrix, full)
-    Y0, Cb0, Cr0 = (R.code(p, layout) for p in R.unpack(fr, layout))
-    Y1, Cb1, Cr1 = R.unpack(back, layout)
+    back = FMT.yuv_out(rgb, layout, matrix, full)
+    Y0, Cb0, Cr0 = (FMT.code(p, layout) for p in FMT.unpack(fr, layout))
+    Y1, Cb1, Cr1 = FMT.unpack(back, layout)
     assert not ((Y1 if layout == 'i010' else Y1 & 63) >> (10 if layout == 'i010' else 0)).any()      # the ignored bits come back as zero
-    Y1, Cb1, Cr1 = (R.code(p, layout) for p in (Y1, Cb1, Cr1))
+    Y1, Cb1, Cr1 = (FMT.code(p, layout) for p in (Y1, Cb1, Cr1))
     pix = block.repeat(2, 0).repeat(2, 1)
     assert np.array_equal(Y1[pix], Y0[pix]) and np.array_equal(Cb1[block], Cb0[block]) and np.array_equal(Cr1[block], Cr0[block])
 
 
 def test_layouts_and_codes():
     w = np.array([0, 1, 63, 64, 1023, 1024, 0xffc0, 0xffff, 0x8001], np.uint16)
-    assert R.code(w, 'i010').tolist() == [0, 1, 63, 64, 1023, 0, 960, 1023, 1] and R.code(w, 'p010').tolist() == [0, 0, 0, 1, 15, 16, 1023, 1023, 512]
-    assert R.store([0, 1, 1023], 'p010').tolist() == [0, 64, 0xffc0] and R.store([0, 1, 1023], 'i010').tolist() == [0, 1, 1023]
-    fr = R.designed_frames(2, 30, 50, 9)
+    assert FMT.code(w, 'i010').tolist() == [0, 1, 63, 64, 1023, 0, 960, 1023, 1] and FMT.code(w, 'p010').tolist() == [0, 0, 0, 1, 15, 16, 1023, 1023, 512]
+    assert FMT.store([0, 1, 1023], 'p010').tolist() == [0, 64, 0xffc0] and FMT.store([0, 1, 1023], 'i010').tolist() == [0, 1, 1023]
+    fr = FMT.designed_frames(2, 30, 50, 9)
     for f in fr:
         clean = R.convert_layout(f, 'i010', 'i010')
         assert not np.array_equal(clean, f) and clean.max() <= 1023                      # (the designed frames carry junk)
@@ -121,14 +125,14 @@ def test_layouts_and_codes():
         assert np.array_equal(p[:30] >> 6, f[:30] & 1023)
         assert np.array_equal(p.ravel()[1500::2] >> 6, f.ravel()[1500:1875] & 1023) and np.array_equal(p.ravel()[1501::2] >> 6, f.ravel()[1875:] & 1023)
         assert np.array_equal(R.convert_layout(p, 'p010', 'i010'), clean)
-        for matrix, full in R.COLOURS:
-            assert np.array_equal(R.yuv_in(R.with_junk(p, 'p010', 1), 'p010', matrix, full), R.yuv_in(f, 'i010', matrix, full))
-        assert np.array_equal(R.histogram(p, 'p010'), R.histogram(f, 'i010')) and R.histogram(f, 'i010').sum(1).tolist() == [1500, 375, 375]
+        for matrix, full in COLOURS:
+            assert np.array_equal(FMT.yuv_in(FMT.with_junk(p, 'p010', 1), 'p010', matrix, full), FMT.yuv_in(f, 'i010', matrix, full))
+        assert np.array_equal(FMT.histogram(p, 'p010'), FMT.histogram(f, 'i010')) and FMT.histogram(f, 'i010').sum(1).tolist() == [1500, 375, 375]
     rgb = np.random.default_rng(1).uniform(-0.1, 1.1, (16, 18, 3)).astype(np.float32)
-    for matrix, full in R.COLOURS:
-        assert np.array_equal(R.yuv_out(rgb, 'p010', matrix, full), R.convert_layout(R.yuv_out(rgb, 'i010', matrix, full), 'i010', 'p010'))
+    for matrix, full in COLOURS:
+        assert np.array_equal(FMT.yuv_out(rgb, 'p010', matrix, full), R.convert_layout(FMT.yuv_out(rgb, 'i010', matrix, full), 'i010', 'p010'))
     # the 10-bit out is the 8-bit out at four times the resolution: the codes agree after >> 2 up to the rounding of the two quantisers
-    a, b = R.code(R.yuv_out(rgb, 'i010'), 'i010').astype(np.int64), R8.yuv_out(rgb, 'i420').astype(np.int64)
+    a, b = FMT.code(FMT.yuv_out(rgb, 'i010'), 'i010').astype(np.int64), R.FORMATS['i420'].yuv_out(rgb, 'i420').astype(np.int64)
     assert np.abs(a - 4 * b).max() <= 3
 
 
@@ -136,11 +140,11 @@ def test_designed_data():
     """Every code 0 .. 1023 in every Y plane of 1024 samples or more; the extreme codes in every plane that has room; random junk in the
     ignored bits of both layouts; the P010 frames hold the codes of the I010 frames."""
     for c in R.CASES:
-        fr = R.designed_frames(c.B, c.H, c.W, 5)
-        pf = R.designed_frames(c.B, c.H, c.W, 5, 'p010')
+        fr = FMT.designed_frames(c.B, c.H, c.W, 5)
+        pf = FMT.designed_frames(c.B, c.H, c.W, 5, 'p010')
         assert fr.dtype == np.uint16 and fr.shape == (c.B, c.H * 3 // 2, c.W)
         for f, p in zip(fr, pf):
-            Y = R.code(R.unpack(f, 'i010')[0], 'i010')
+            Y = FMT.code(FMT.unpack(f, 'i010')[0], 'i010')
             if Y.size >= 1024:
                 assert len(np.unique(Y)) == 1024, c.name
             if Y.size >= 40:
@@ -148,7 +152,7 @@ def test_designed_data():
             assert np.array_equal(R.convert_layout(p, 'p010', 'i010'), R.convert_layout(f, 'i010', 'i010'))
             if f.size >= 24:
                 assert (f >> 10).any() and (p & 63).any(), c.name
-        allY = np.concatenate([R.code(R.unpack(f, 'i010')[0], 'i010').ravel() for f in fr])
+        allY = np.concatenate([FMT.code(FMT.unpack(f, 'i010')[0], 'i010').ravel() for f in fr])
         assert {0, 1023} <= set(allY.tolist()) or c.H * c.W < 8, c.name
 
 
@@ -158,11 +162,11 @@ def test_cut_equals_frame_conversion_then_float_cut(case, geos):
     """The cut (the formulas on the gathered words) == table look-ups on the whole frame, then tile_map_ref's float cut."""
     geo = geos[case.name]
     total = case.B * len(geo['origins_y']) * len(geo['origins_x'])
-    for layout in R.LAYOUTS:
-        fr = R.designed_frames(case.B, case.H, case.W, 4, layout)
-        for matrix, full in R.COLOURS:
-            a = R.cut(fr, geo, 0, total, layout, matrix, full)
-            b = R.cut_via_frames(fr, geo, 0, total, layout, matrix, full)
+    for layout in LAYOUTS:
+        fr = FMT.designed_frames(case.B, case.H, case.W, 4, layout)
+        for matrix, full in COLOURS:
+            a = FMT.cut(fr, geo, 0, total, layout, matrix, full)
+            b = FMT.cut_via_frames(fr, geo, 0, total, layout, matrix, full)
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (layout, matrix, full)
 
 
@@ -180,14 +184,14 @@ OUT_OFFSETS = (0, 2)                           # ... with dst 4-byte aligned and
 
 def test_the_cases_reach_every_instance_and_branch(geos):
     """Which instance of the 10-bit cut kernel and which of its branches the calls of tests/test_yuv10_gpu.py take, from the kernel's own
-    conditions restated in yuv10_ref.branches; the same for rgb_to_yuv10_kernel on that test's sizes.  The table goes to the log."""
+    conditions restated in yuv_ref.Format.branches; the same for rgb_to_yuv10_kernel on that test's sizes.  The table goes to the log."""
     seen = {}
     for c in R.CASES:
         s = seen[c.name] = set()
-        for layout in R.LAYOUTS:
+        for layout in LAYOUTS:
             for ranges in R.ranges_of(c, geos[c.name]).values():
                 for tile0, nt in ranges:
-                    s |= R.branches(c, geos[c.name], layout, tile0, nt)
+                    s |= FMT.branches(c, geos[c.name], layout, tile0, nt)
         print(c.name, '|', ', '.join(sorted(s)))
     union = set().union(*seen.values())
     assert union == ALL_BRANCHES, (sorted(ALL_BRANCHES - union), sorted(union - ALL_BRANCHES))
@@ -198,23 +202,23 @@ def test_the_cases_reach_every_instance_and_branch(geos):
     assert 'scalar stores' in seen['y6-12x22-b1x2-noalign']
     out = {}
     for h, w in OUT_SIZES:
-        for layout in R.LAYOUTS:
-            out[h, w, layout] = set().union(*[R.out_branches(h, w, layout, o) for o in OUT_OFFSETS])
+        for layout in LAYOUTS:
+            out[h, w, layout] = set().union(*[FMT.out_branches(h, w, layout, o) for o in OUT_OFFSETS])
             print(f'{h}x{w} {layout} |', ', '.join(sorted(out[h, w, layout])))
     assert set().union(*out.values()) == ALL_OUT_BRANCHES
 
 
 def test_the_restatement_passes_its_own_comparison(geos):
     """On every case, both layouts, every partition (the colour settings take turns over the cases)."""
-    backend = R.NumpyBackend(lambda c: geos[c.name])
+    backend = FMT.NumpyBackend(lambda c: geos[c.name])
     for i, c in enumerate(R.CASES):
-        matrix, full = R.COLOURS[i % 4]
-        for layout in R.LAYOUTS:
+        matrix, full = COLOURS[i % 4]
+        for layout in LAYOUTS:
             for ranges in R.ranges_of(c, geos[c.name]).values():
-                assert not list(R.check_cut(backend, c, geos[c.name], layout, matrix, full, ranges, twice=False)), c.name
+                assert not list(FMT.check_cut(backend, c, geos[c.name], layout, matrix, full, ranges, twice=False)), c.name
 
 
-@pytest.mark.parametrize('fault', R.FAULTS)
+@pytest.mark.parametrize('fault', FAULTS)
 def test_every_planted_fault_fails_the_comparison(fault, geos):
     """The restatement with one fault planted as the backend of the comparison the GPU test runs, on the same designed data: found in
     every case in which the fault changes what the backend does (a code rule only with the layout it belongs to; the shifted 8-bit scale
@@ -222,19 +226,19 @@ def test_every_planted_fault_fails_the_comparison(fault, geos):
     every = [c.name for c in R.CASES]
     must = {'p010_as_i010': every, 'i010_as_p010': every, 'ignored_bits_not_masked': every, 'eight_bit_scale_shifted': every, 'cb_cr_swapped': every,
             'chroma_from_tile_coordinate': ['y1-30x50-b3x2', 'y2-30x50-b3x2-ov3x5', 'y6-12x22-b1x2-noalign']}[fault]
-    layouts = {'p010_as_i010': ['p010'], 'i010_as_p010': ['i010']}.get(fault, R.LAYOUTS)
+    layouts = {'p010_as_i010': ['p010'], 'i010_as_p010': ['i010']}.get(fault, LAYOUTS)
     full = fault == 'eight_bit_scale_shifted'
-    backend = R.NumpyBackend(lambda c: geos[c.name], fault)
+    backend = FMT.NumpyBackend(lambda c: geos[c.name], fault)
     for c in R.CASES:
         if c.name in must:
             for layout in layouts:
                 ranges = R.ranges_of(c, geos[c.name])['one']
-                first = next(R.check_cut(backend, c, geos[c.name], layout, 'bt709', full, ranges, seed=17, twice=False), None)
+                first = next(FMT.check_cut(backend, c, geos[c.name], layout, 'bt709', full, ranges, seed=17, twice=False), None)
                 print(fault, layout, '->', first)
                 assert first is not None, (fault, c.name, layout)
     if fault == 'eight_bit_scale_shifted':      # limited range: 219 << 2, 224 << 2 ARE the 10-bit divisors
         c = R.CASES[0]
-        assert not list(R.check_cut(backend, c, geos[c.name], 'i010', 'bt709', False, R.ranges_of(c, geos[c.name])['one'], twice=False))
+        assert not list(FMT.check_cut(backend, c, geos[c.name], 'i010', 'bt709', False, R.ranges_of(c, geos[c.name])['one'], twice=False))
 
 
 # ---- the entry points -------------------------------------------------------------------------------------------------------------------------
@@ -329,7 +333,7 @@ def _y4m_bytes(tokens, frames):
 
 def test_y4m_10bit_round_trip_and_byte_order():
     from film_hip import y4m
-    frames = R.designed_frames(3, 30, 50, 2) & 1023
+    frames = FMT.designed_frames(3, 30, 50, 2) & 1023
     tokens = y4m.header_tokens(50, 30, (30000, 1001), True, colour='420p10')
     assert tokens == ['W50', 'H30', 'F30000:1001', 'Ip', 'A1:1', 'C420p10', 'XCOLORRANGE=FULL']
     assert y4m.header_tokens(50, 30, (24, 1), True) == ['W50', 'H30', 'F24:1', 'Ip', 'A1:1', 'C420jpeg', 'XCOLORRANGE=FULL']       # (as before)
@@ -421,7 +425,7 @@ def test_video_cli_frame_order_and_header_on_a_10bit_stream(tmp_path, monkeypatc
             self.log.append((h, w, pix, matrix, full_range))
             return Stream(self.log)
 
-    frames = R.designed_frames(5, 4, 6, 1)
+    frames = FMT.designed_frames(5, 4, 6, 1)
     tokens = ['W6', 'H4', 'F25:1', 'Ip', 'A1:1', 'C420p10', 'XCOLORRANGE=FULL', 'XYSCSS=420P10']
     data = _y4m_bytes(tokens, frames)
 
@@ -439,7 +443,7 @@ def test_video_cli_frame_order_and_header_on_a_10bit_stream(tmp_path, monkeypatc
         assert n == 9 and it.log == [(4, 6, 'i010', 'bt601', want_full), 'closed']
         check(out.getvalue())
     it, out = It(), io.BytesIO()      # an 8-bit stream goes on as before
-    f8 = R8.designed_frames(2, 4, 6, 1)
+    f8 = R.FORMATS['i420'].designed_frames(2, 4, 6, 1)
     assert cli.double_frame_rate(it, y4m.Y4MReader(io.BytesIO(_y4m_bytes(tokens[:5], f8)), depths=(8, 10)), out) == 3
     assert it.log == [(4, 6, 'i420', 'bt709', False), 'closed']
     # main() opens its reader for both depths and needs no flag

@@ -1,4 +1,4 @@
-"""GPU tests of the 10-bit Y'CbCr 4:2:0 path (FILM_PIX_I010 / FILM_PIX_P010), bit for bit against the numpy restatement tests/yuv10_ref.py
+"""GPU tests of the 10-bit Y'CbCr 4:2:0 path (FILM_PIX_I010 / FILM_PIX_P010), bit for bit against the numpy restatement tests/yuv_ref.py
 (include/film_hip.h, "The 10-bit 4:2:0 arithmetic"): frame_yuv10_to_tiles_kernel alone through film_debug_yuv_cut on designed data with guard
 bands (tests/test_yuv10_cpu.py shows which instance and branch every case reaches and that the comparison finds each planted fault);
 rgb_to_yuv10_kernel alone through film_to_yuv420; the two 10-bit instances of frame_histogram_kernel through film_frame_histogram and
@@ -8,7 +8,11 @@ import numpy as np
 import pytest
 
 import tile_map_ref as T
-import yuv10_ref as R
+import yuv_ref as R
+
+FMT = R.FORMATS['i010']
+LAYOUTS = FMT.layouts
+COLOURS = [(m, f) for m in ('bt709', 'bt601') for f in (False, True)]      # the four colour settings of the 4:2:0 tests
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +50,7 @@ def _down(t):
 
 # ---- the cut alone ------------------------------------------------------------------------------------------------------------------------
 class GpuBackend:
-    """film_debug_yuv_cut as a backend of yuv10_ref.check_cut: both allocations go up as torch tensors (guard | payload | guard in ONE
+    """film_debug_yuv_cut as a backend of yuv_ref.Format.check_cut: both allocations go up as torch tensors (guard | payload | guard in ONE
     allocation each), the entry point gets the payloads' addresses, both come back."""
 
     def __init__(self, eng):
@@ -55,14 +59,14 @@ class GpuBackend:
     def __call__(self, frames_alloc, tiles_alloc, case, tile0, ntiles, layout, matrix, full):
         import torch
         ft, tt = _up(frames_alloc), torch.from_numpy(np.array(tiles_alloc)).cuda()
-        fp, tp = ft.data_ptr() + 2 * R.GUARD_U16, tt.data_ptr() + 4 * T.GUARD
+        fp, tp = ft.data_ptr() + 2 * FMT.guard, tt.data_ptr() + 4 * T.GUARD
         assert fp % 4 == 0 and tp % 16 == 0 and ft.numel() % 2 == 0
         self.eng.debug_yuv_cut(fp, tp, case.B, case.H, case.W, case.align, case.block, tile0, ntiles, pix=layout, matrix=matrix, full_range=full)
         torch.cuda.synchronize()
         return _down(ft), tt.cpu().numpy()
 
 
-@pytest.mark.parametrize('layout', R.LAYOUTS)
+@pytest.mark.parametrize('layout', LAYOUTS)
 @pytest.mark.parametrize('case', R.CASES, ids=lambda c: c.name)
 def test_cut(eng, case, layout):
     """All four colour settings, every range of every partition: tiles_dev[0 : ntiles] == the restatement on the bits, the padding +0.0,
@@ -71,8 +75,8 @@ def test_cut(eng, case, layout):
     try:
         geo = eng.tiling(case.H, case.W, case.align, case.block)
         backend = GpuBackend(eng)
-        findings = [f'[{name}] {m}' for matrix, full in R.COLOURS for name, ranges in R.ranges_of(case, geo).items()
-                    for m in R.check_cut(backend, case, geo, layout, matrix, full, ranges, seed=17)]
+        findings = [f'[{name}] {m}' for matrix, full in COLOURS for name, ranges in R.ranges_of(case, geo).items()
+                    for m in FMT.check_cut(backend, case, geo, layout, matrix, full, ranges, seed=17)]
     finally:
         eng.set_block_overlap(0)
     assert not findings, f'{len(findings)} findings:\n' + '\n'.join(findings[:12])
@@ -91,7 +95,7 @@ def _rgb(h, w, seed):
 
 
 @pytest.mark.parametrize('offset', [0, 1], ids=lambda o: f'dst+{2 * o}')
-@pytest.mark.parametrize('layout', R.LAYOUTS)
+@pytest.mark.parametrize('layout', LAYOUTS)
 @pytest.mark.parametrize('h,w', [(2, 2), (16, 18), (30, 50)])
 def test_to_yuv420(eng, h, w, layout, offset):
     """dst 4-byte aligned (whole words where the rows allow) and 2 bytes behind that (samples): the frame == the restatement, the guard
@@ -100,17 +104,17 @@ def test_to_yuv420(eng, h, w, layout, offset):
     n = h * w * 3 // 2
     src = _rgb(h, w, seed=h + w)
     st = torch.from_numpy(src).cuda()
-    for ci, (matrix, full) in enumerate(R.COLOURS):
-        alloc = np.random.default_rng(ci).integers(0, 65536, R.GUARD_U16 + offset + n + R.GUARD_U16).astype(np.uint16)
+    for ci, (matrix, full) in enumerate(COLOURS):
+        alloc = np.random.default_rng(ci).integers(0, 65536, FMT.guard + offset + n + FMT.guard).astype(np.uint16)
         dt = _up(alloc)
         assert dt.data_ptr() % 4 == 0 and st.data_ptr() % 16 == 0
-        eng.to_yuv420_device(st.data_ptr(), dt.data_ptr() + 2 * (R.GUARD_U16 + offset), h, w, layout, matrix, full)
+        eng.to_yuv420_device(st.data_ptr(), dt.data_ptr() + 2 * (FMT.guard + offset), h, w, layout, matrix, full)
         torch.cuda.synchronize()
         got = _down(dt)
         want = np.array(alloc)
-        want[R.GUARD_U16 + offset:R.GUARD_U16 + offset + n] = R.yuv_out(src, layout, matrix, full).ravel()
+        want[FMT.guard + offset:FMT.guard + offset + n] = FMT.yuv_out(src, layout, matrix, full).ravel()
         bad = np.flatnonzero(got != want)
-        assert bad.size == 0, (matrix, full, bad.size, bad[:8] - R.GUARD_U16 - offset, got[bad[:8]], want[bad[:8]])
+        assert bad.size == 0, (matrix, full, bad.size, bad[:8] - FMT.guard - offset, got[bad[:8]], want[bad[:8]])
     assert np.array_equal(st.cpu().numpy().view(np.uint32), src.view(np.uint32))
 
 
@@ -118,7 +122,7 @@ def test_to_yuv420(eng, h, w, layout, offset):
 HIST_GUARD = 16     # guard words around the 768 counters
 
 
-@pytest.mark.parametrize('layout', R.LAYOUTS)
+@pytest.mark.parametrize('layout', LAYOUTS)
 @pytest.mark.parametrize('h,w', [(30, 50), (2, 2)])
 def test_histogram(h, w, layout):
     """film_frame_histogram == numpy bincount of code >> 2 per plane, on designed frames (random junk in the ignored bits) inside guard
@@ -127,11 +131,11 @@ def test_histogram(h, w, layout):
     import torch
     from film_hip.engine import frame_histogram_device
     from film_hip.torch_io import frame_histogram
-    frame = np.array(R.designed_frames(1, h, w, seed=h + w, layout=layout)[0])
-    codes = R.code(frame, layout)
-    frame[(codes >> 2) == 77] = R.store(320, layout)          # bin 77 is the guard's: codes 308 .. 311
-    guard_word = int(R.store(309, layout)) | (0x0400 if layout == 'i010' else 0x0020)
-    want = R.histogram(frame, layout)
+    frame = np.array(FMT.designed_frames(1, h, w, seed=h + w, layout=layout)[0])
+    codes = FMT.code(frame, layout)
+    frame[(codes >> 2) == 77] = FMT.store(320, layout)          # bin 77 is the guard's: codes 308 .. 311
+    guard_word = int(FMT.store(309, layout)) | (0x0400 if layout == 'i010' else 0x0020)
+    want = FMT.histogram(frame, layout)
     assert want[:, 77].sum() == 0 and want.sum(1).tolist() == [h * w, h * w // 4, h * w // 4]
     for offset_words in (0, 1, 2, 3):
         front, back = 32 + 2 * offset_words, 32
@@ -165,9 +169,9 @@ _WANT = {}
 
 def _scene(f, h, w, seed):
     """f I010 frames (clean words) of a scene that moves by (2, -2) px per frame, with every code in the Y plane."""
-    base = R.designed_frames(1, h, w, seed)[0]
-    Y, Cb, Cr = (R.code(p, 'i010').astype(np.uint16) for p in R.unpack(base, 'i010'))
-    return np.stack([R.pack(np.roll(Y, (2 * i, -2 * i), (0, 1)), np.roll(Cb, (i, -i), (0, 1)), np.roll(Cr, (i, -i), (0, 1)), 'i010') for i in range(f)])
+    base = FMT.designed_frames(1, h, w, seed)[0]
+    Y, Cb, Cr = (FMT.code(p, 'i010').astype(np.uint16) for p in FMT.unpack(base, 'i010'))
+    return np.stack([FMT.pack(np.roll(Y, (2 * i, -2 * i), (0, 1)), np.roll(Cb, (i, -i), (0, 1)), np.roll(Cr, (i, -i), (0, 1)), 'i010') for i in range(f)])
 
 
 def _want(tiny, name):
@@ -175,17 +179,17 @@ def _want(tiny, name):
     if name not in _WANT:
         f, h, w, align, block, (matrix, full) = STREAMS[name]
         frames = _scene(f, h, w, seed=h + w)
-        x = np.stack([R.yuv_in(fr, 'i010', matrix, full) for fr in frames])
+        x = np.stack([FMT.yuv_in(fr, 'i010', matrix, full) for fr in frames])
         mids = tiny.interpolate_frames(x[:-1], x[1:], align=align, block_shape=block)
         assert np.isfinite(mids).all()
-        want = np.stack([R.yuv_out(m, 'i010', matrix, full) for m in mids])
+        want = np.stack([FMT.yuv_out(m, 'i010', matrix, full) for m in mids])
         frames.setflags(write=False); want.setflags(write=False)
         _WANT[name] = frames, want
     return _WANT[name]
 
 
 @pytest.mark.parametrize('mem', ['host', 'device'])
-@pytest.mark.parametrize('layout', R.LAYOUTS)
+@pytest.mark.parametrize('layout', LAYOUTS)
 @pytest.mark.parametrize('name', list(STREAMS))
 def test_stream(tiny, name, layout, mem):
     """Every push's mid == yuv_out(interpolate_frames(yuv_in(previous), yuv_in(frame))), code for code - also the push after "fuse" 31 -> 0
@@ -196,8 +200,8 @@ def test_stream(tiny, name, layout, mem):
     if layout == 'p010':
         frames = np.stack([R.convert_layout(fr, 'i010', 'p010') for fr in frames])
         want = np.stack([R.convert_layout(m, 'i010', 'p010') for m in want])
-        assert np.array_equal(R.unpack(want[0], 'p010')[0], R.unpack(_want(tiny, name)[1][0], 'i010')[0] << 6)
-    frames = np.stack([R.with_junk(fr, layout, 7 + i) for i, fr in enumerate(frames)])
+        assert np.array_equal(FMT.unpack(want[0], 'p010')[0], FMT.unpack(_want(tiny, name)[1][0], 'i010')[0] << 6)
+    frames = np.stack([FMT.with_junk(fr, layout, 7 + i) for i, fr in enumerate(frames)])
     assert (frames != np.stack([R.convert_layout(fr, layout, layout) for fr in frames])).any()
 
     def drop_plans():
@@ -237,18 +241,18 @@ def test_stream(tiny, name, layout, mem):
     assert len({m.tobytes() for m in want}) == f - 1       # (the mids differ from each other: a stale result would show)
 
 
-@pytest.mark.parametrize('layout', R.LAYOUTS)
+@pytest.mark.parametrize('layout', LAYOUTS)
 def test_stream_scene_cut_reports_the_restatements_distance(tiny, layout):
     """A 10-bit stream with "scene_cut" set: D and S of cut_info are those of the restatement's histograms (bin = code >> 2), the rule
     1000 D >= k * 2 S decides, and a cut push produces nothing."""
     h, w = 64, 64
     frames = _scene(3, h, w, seed=9)
-    other = R.pack(*[(R.code(p, 'i010') // 2).astype(np.uint16) for p in R.unpack(frames[0], 'i010')], 'i010')      # halved codes: a different histogram
+    other = FMT.pack(*[(FMT.code(p, 'i010') // 2).astype(np.uint16) for p in FMT.unpack(frames[0], 'i010')], 'i010')      # halved codes: a different histogram
     seq = [frames[0], frames[1], other, frames[2]]
     if layout == 'p010':
         seq = [R.convert_layout(fr, 'i010', 'p010') for fr in seq]
-    seq = [R.with_junk(fr, layout, i) for i, fr in enumerate(seq)]
-    hists = [R.histogram(fr, layout) for fr in seq]
+    seq = [FMT.with_junk(fr, layout, i) for i, fr in enumerate(seq)]
+    hists = [FMT.histogram(fr, layout) for fr in seq]
     D = [int(np.abs(hists[i] - hists[i - 1]).sum()) for i in range(1, 4)]
     S = h * w * 3 // 2
     k = 300
@@ -298,5 +302,5 @@ def test_video_cli(tiny, tmp_path, monkeypatch):
     for i in range(4):
         assert np.array_equal(got[2 * i + 1], mids[i]), i
     assert not np.array_equal(mids[0], mids[1])
-    want = R.yuv_out(tiny.interpolate_frames(R.yuv_in(frames[0], 'i010', 'bt601')[None], R.yuv_in(frames[1], 'i010', 'bt601')[None], align=64)[0], 'i010', 'bt601')
+    want = FMT.yuv_out(tiny.interpolate_frames(FMT.yuv_in(frames[0], 'i010', 'bt601')[None], FMT.yuv_in(frames[1], 'i010', 'bt601')[None], align=64)[0], 'i010', 'bt601')
     assert np.array_equal(mids[0], want)

@@ -1,6 +1,6 @@
 """CPU tests of the planar 4:2:2 / 4:4:4 layouts (FILM_PIX_I422 / I444 / I210 / I410) and of the BT.2020 matrix flag (FILM_YUV_BT2020,
-'bt2020nc'): tests/yuv_sub_ref.py - the numpy restatement tests/test_yuv_chroma_gpu.py compares the kernels with, bit for bit - against an
-independent float64 evaluation, known answers and its own round trip; against yuv_ref / yuv10_ref where those state the same thing; which
+'bt2020nc'): tests/yuv_ref.py - the numpy restatement tests/test_yuv_chroma_gpu.py compares the kernels with, bit for bit - against an
+independent float64 evaluation, known answers and its own round trip; against the digests recorded from the modules it replaced; which
 kernel instance and branch every GPU case reaches and that the comparisons on the designed data find each planted fault; the codes and
 refusals on a plan-only handle; film_to_yuv; the Y4M reader / writer on the four new tokens; eval/video_cli.py with a stand-in interpolator.
 No GPU."""
@@ -12,12 +12,12 @@ import re
 import numpy as np
 import pytest
 
-import yuv10_ref as R10
-import yuv_ref as R8
-import yuv_sub_ref as R
+import yuv_ref as R
 from conftest import ROOT
 
 NEW, OLD = R.NEW_LAYOUTS, R.OLD_LAYOUTS
+COLOURS = [(m, f) for m in R.MATRICES for f in (False, True)]      # the six colour settings
+FAULTS = ('chroma_row_halved', 'chroma_col_halved', 'chroma_from_tile_coordinate', 'cb_cr_swapped', 'bt709_under_bt2020', 'box_2x2_mean')
 
 
 @pytest.fixture(scope='module')
@@ -26,7 +26,7 @@ def geos():
     from film_hip.options import TINY
     eng = FilmEngine(TINY, device=-1)
     out = {}
-    for c in list(R8.CASES) + R.CASES_422 + R.CASES_444:
+    for c in list(R.CASES) + R.CASES_422 + R.CASES_444:
         eng.set_block_overlap(c.overlap)
         out[c.name] = eng.tiling(c.H, c.W, c.align, c.block)
     eng.close()
@@ -62,7 +62,7 @@ def _out_f64(rgb, depth, sx, sy, matrix, full):
 
 
 @pytest.mark.parametrize('depth', [8, 10])
-@pytest.mark.parametrize('matrix,full', R.COLOURS)
+@pytest.mark.parametrize('matrix,full', COLOURS)
 def test_in_against_float64(matrix, full, depth):
     """Every (Y, Cb, Cr) triple of a 64-step grid plus the extremes: at most 1e-6 apart - five float32 roundings on magnitudes below 2
     (BT.2020's largest coefficient is 1.8814)."""
@@ -78,7 +78,7 @@ def test_in_against_float64(matrix, full, depth):
 
 
 @pytest.mark.parametrize('layout', NEW)
-@pytest.mark.parametrize('matrix,full', R.COLOURS)
+@pytest.mark.parametrize('matrix,full', COLOURS)
 def test_out_against_float64(matrix, full, layout):
     """The bound of tests/test_yuv_cpu.py's test_out_against_float64: equal codes wherever the float64 value is farther than 1e-4 of an 8-bit
     code from a rounding tie, at most one code apart elsewhere, at most 1 % of the values so excused.  A 10-bit code is a quarter of an 8-bit
@@ -101,19 +101,18 @@ def test_out_against_float64(matrix, full, layout):
     assert near_all <= 0.01 * n_all
 
 
-def test_the_420_instances_restate_yuv_ref_and_yuv10_ref():
-    """SubFormat at (SX, SY) = (1, 1) with the two older matrices gives the bits of tests/yuv_ref.py / tests/yuv10_ref.py: in, out, histogram."""
-    rgb = R.designed_rgb(16, 18, 3)
-    for layout in OLD:
-        f, old = R.FORMATS[layout], (R8 if layout in R8.LAYOUTS else R10)
-        fr = old.designed_frames(1, 16, 18, 5, layout)[0]
-        for matrix, full in R8.COLOURS:
-            assert np.array_equal(f.yuv_in(fr, layout, matrix, full).view(np.uint32), old.yuv_in(fr, layout, matrix, full).view(np.uint32))
-            assert np.array_equal(f.yuv_out(rgb, layout, matrix, full), old.yuv_out(rgb, layout, matrix, full))
-        if layout in R10.LAYOUTS:
-            assert np.array_equal(f.histogram(fr, layout), R10.histogram(fr, layout))
-    for m in ('bt709', 'bt601'):
-        assert R.constants(m) == R8.constants(m)
+def test_the_restatement_computes_what_the_recorded_digests_say():
+    """tests/golden/yuv_ref_digests.json was written from the three reference modules that tests/yuv_ref.py replaced: the designed frames, in,
+    out, histogram, the cut with and without every planted fault and the branch names of all ten layouts - the 4:2:0 ones both with their own
+    designed frames and colour settings and as the (SX, SY) = (1, 1) instance of the general statement - are still those, digest for digest."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location('make_yuv_ref_golden', os.path.join(ROOT, 'tools', 'make_yuv_ref_golden.py'))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    want, got = json.load(open(tool.PATH)), tool.digests()
+    assert len(want) > 600 and sorted(got) == sorted(want)
+    assert got == want, sorted(k for k in want if got[k] != want[k])[:12]
 
 
 # ---- known answers ----------------------------------------------------------------------------------------------------------------------------
@@ -162,7 +161,7 @@ def test_in_gamut_round_trip_is_the_identity(layout):
     fr = f.pack(f.store(rng.integers(50 * s, 206 * s, (h, w)), layout), f.store(rng.integers(100 * s, 157 * s, (ch, cw)), layout),
                 f.store(rng.integers(100 * s, 157 * s, (ch, cw)), layout), layout)
     fr = f.with_junk(fr, layout, 4)
-    for matrix, full in (R.COLOURS if layout in NEW else [('bt2020nc', False), ('bt2020nc', True)]):
+    for matrix, full in (COLOURS if layout in NEW else [('bt2020nc', False), ('bt2020nc', True)]):
         rgb = f.yuv_in(fr, layout, matrix, full)
         inside = ((rgb > 0) & (rgb < 1)).all(-1)
         block = inside.reshape(ch, 1 << f.sy, cw, 1 << f.sx).all((1, 3))
@@ -178,7 +177,7 @@ def test_in_gamut_round_trip_is_the_identity(layout):
 
 # ---- which kernel instances and branches the GPU cases reach -----------------------------------------------------------------------------------
 def test_the_cases_reach_every_instance_and_branch(geos):
-    """From the kernels' own conditions restated in SubFormat.branches / out_branches: the calls of tests/test_yuv_chroma_gpu.py reach both
+    """From the kernels' own conditions restated in yuv_ref.Format.branches / out_branches: the calls of tests/test_yuv_chroma_gpu.py reach both
     cut instances and the quantiser instance of every new layout and every branch of theirs - chroma from row fy, four chroma samples per
     group, an odd block row, an odd pixel count per row, a frame of a batch that starts off a word boundary among them.  The table goes to the log."""
     for layout in NEW:
@@ -223,7 +222,7 @@ def test_the_restatement_passes_its_own_comparison(geos):
     for layout in NEW:
         f = R.FORMATS[layout]
         for i, c in enumerate(R.cases_of(layout)):
-            matrix, full = R.COLOURS[i % 6]
+            matrix, full = COLOURS[i % 6]
             for ranges in R.ranges_of(c, geos[c.name]).values():
                 assert not list(f.check_cut(backend[layout], c, geos[c.name], layout, matrix, full, ranges, twice=False)), (layout, c.name)
                 fr = f.frames_view(f.new_frames_alloc(c, layout, 1), c)
@@ -232,7 +231,7 @@ def test_the_restatement_passes_its_own_comparison(geos):
                                       f.cut_via_frames(fr, geos[c.name], r0[0], r0[1], layout, matrix, full).view(np.uint32))
 
 
-@pytest.mark.parametrize('fault', R.FAULTS)
+@pytest.mark.parametrize('fault', FAULTS)
 def test_every_planted_fault_fails_the_comparison(fault, geos):
     """The restatement with one fault planted, in the comparison the GPU test runs on the same designed data: found in every case in which
     the fault changes what is computed (a wrong chroma row needs more than one row; the pairing cannot go wrong from an even origin - and
@@ -242,7 +241,7 @@ def test_every_planted_fault_fails_the_comparison(fault, geos):
             f = R.FORMATS[layout]
             for h, w in [(2, 2), (16, 18), (30, 50)]:
                 src = R.designed_rgb(h, w, seed=h + w)
-                for matrix, full in R.COLOURS:
+                for matrix, full in COLOURS:
                     assert not np.array_equal(f.yuv_out(src, layout, matrix, full, fault), f.yuv_out(src, layout, matrix, full)), (layout, h, w)
         return
     layouts = {'chroma_row_halved': ('i422', 'i210'), 'chroma_col_halved': ('i444', 'i410')}.get(fault, NEW)
@@ -261,7 +260,7 @@ def test_every_planted_fault_fails_the_comparison(fault, geos):
                 print(fault, layout, c.name, '->', first)
                 assert first is not None, (fault, c.name, layout)
     if fault == 'bt709_under_bt2020':      # ... and under the other flags nothing changes
-        f, c = R.FORMATS['i444'], R8.CASES[0]
+        f, c = R.FORMATS['i444'], R.CASES[0]
         backend = f.NumpyBackend(lambda c: geos[c.name], fault)
         assert not list(f.check_cut(backend, c, geos[c.name], 'i444', 'bt601', False, R.ranges_of(c, geos[c.name])['one'], twice=False))
 
@@ -491,6 +490,6 @@ def test_video_cli_frame_order_and_header_on_a_422p10_stream(tmp_path, monkeypat
     assert all(np.array_equal(got[2 * i], frames[i]) for i in range(5))
     assert all(np.array_equal(got[2 * i + 1], ((frames[i].astype(np.int64) + frames[i + 1]) // 2).astype(np.uint16)) for i in range(4))
     # a 4:2:0 file goes on as before, --chroma any or not
-    f8 = R8.designed_frames(2, 4, 6, 1)
+    f8 = R.FORMATS['i420'].designed_frames(2, 4, 6, 1)
     src.write_bytes(_y4m_bytes(['W6', 'H4', 'F25:1', 'Ip', 'A1:1'], f8))
     assert cli.main(['--input', str(src), '--output', str(dst), '--chroma', 'any']) == 3 and made[1].log == [(4, 6, 'i420', 'bt709', False), 'closed']

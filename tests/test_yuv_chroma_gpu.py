@@ -1,5 +1,5 @@
 """GPU tests of the planar 4:2:2 / 4:4:4 layouts (FILM_PIX_I422 / I444 / I210 / I410) and of the BT.2020 matrix flag, bit for bit against the
-numpy restatement tests/yuv_sub_ref.py (include/film_hip.h, "The 4:2:2 and 4:4:4 arithmetic"): the cut alone through film_debug_yuv_cut on
+numpy restatement tests/yuv_ref.py (include/film_hip.h, "The 4:2:2 and 4:4:4 arithmetic"): the cut alone through film_debug_yuv_cut on
 designed data with guard bands (tests/test_yuv_chroma_cpu.py shows which instance and branch every case reaches and that the comparison
 finds each planted fault); the quantiser alone through film_to_yuv; the histogram through film_frame_histogram; frame streams on the TINY
 net from host and device memory, with a selection and with "scene_cut"; eval/video_cli.py on a small C444p10 file.  No tolerance anywhere."""
@@ -7,10 +7,11 @@ import numpy as np
 import pytest
 
 import tile_map_ref as T
-import yuv_sub_ref as R
+import yuv_ref as R
 
 pytestmark = pytest.mark.gpu
 NEW = R.NEW_LAYOUTS
+COLOURS = [(m, f) for m in R.MATRICES for f in (False, True)]      # the six colour settings
 
 
 @pytest.fixture(scope='module')
@@ -47,7 +48,7 @@ def _down(t, dtype):
 
 # ---- the cut alone ------------------------------------------------------------------------------------------------------------------------
 class GpuBackend:
-    """film_debug_yuv_cut as a backend of SubFormat.check_cut: both allocations go up as torch tensors (guard | payload | guard in ONE
+    """film_debug_yuv_cut as a backend of yuv_ref.Format.check_cut: both allocations go up as torch tensors (guard | payload | guard in ONE
     allocation each, the frames' a whole number of 32-bit words), the entry point gets the payloads' addresses, both come back."""
 
     def __init__(self, eng, fmt):
@@ -73,7 +74,7 @@ def test_cut(eng, layout, case):
     try:
         geo = eng.tiling(case.H, case.W, case.align, case.block)
         backend = GpuBackend(eng, f)
-        findings = [f'[{name}] {m}' for matrix, full in R.COLOURS for name, ranges in R.ranges_of(case, geo).items()
+        findings = [f'[{name}] {m}' for matrix, full in COLOURS for name, ranges in R.ranges_of(case, geo).items()
                     for m in f.check_cut(backend, case, geo, layout, matrix, full, ranges, seed=17)]
     finally:
         eng.set_block_overlap(0)
@@ -94,7 +95,7 @@ def test_to_yuv(eng, layout, hw, offset):
     src = R.designed_rgb(h, w, seed=h + w)
     assert (src < 0).any() and (src > 1).any()
     st = torch.from_numpy(src).cuda()
-    colours = R.COLOURS if layout in NEW else [('bt2020nc', False), ('bt2020nc', True)]
+    colours = COLOURS if layout in NEW else [('bt2020nc', False), ('bt2020nc', True)]
     for ci, (matrix, full) in enumerate(colours):
         size = -(-(2 * f.guard + offset + n) // f.per_word) * f.per_word
         alloc = np.random.default_rng(ci).integers(0, 1 << 8 * f.dtype.itemsize, size).astype(f.dtype)

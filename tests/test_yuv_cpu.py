@@ -14,6 +14,11 @@ import pytest
 import yuv_ref as R
 from conftest import ROOT
 
+FMT = R.FORMATS['i420']
+LAYOUTS = FMT.layouts      # ('i420', 'nv12')
+COLOURS = [(m, f) for m in ('bt709', 'bt601') for f in (False, True)]      # the four colour settings of the 4:2:0 tests
+FAULTS = ('chroma_from_tile_coordinate', 'cb_cr_swapped', 'nv12_as_i420')      # what the cut of an 8-bit 4:2:0 frame can get wrong
+
 
 @pytest.fixture(scope='module')
 def geos():
@@ -53,24 +58,24 @@ def _out_f64(rgb, matrix, full):
     return (y * 255, cb * 255 + 128, cr * 255 + 128) if full else (y * 219 + 16, cb * 224 + 128, cr * 224 + 128)
 
 
-@pytest.mark.parametrize('matrix,full', R.COLOURS)
+@pytest.mark.parametrize('matrix,full', COLOURS)
 def test_in_against_float64(matrix, full):
     """Every (Y, Cb, Cr) triple of a 64-step grid plus the extremes: at most 1e-6 apart - five float32 roundings on magnitudes up to 2."""
     v = np.unique(np.concatenate([np.arange(0, 256, 4), [1, 15, 16, 17, 127, 128, 129, 234, 235, 236, 239, 240, 241, 254, 255]]))
     Y, Cb, Cr = np.meshgrid(v, v, v, indexing='ij')
-    got = R.samples_to_rgb(Y, Cb, Cr, matrix, full)
+    got = FMT.samples_to_rgb(Y, Cb, Cr, matrix, full)
     err = np.abs(got.astype(np.float64) - _in_f64(Y, Cb, Cr, matrix, full)).max()
     print(f'{matrix} full={full}: in, max |float32 - float64| = {err:.3g}')
     assert err <= 1e-6
 
 
-@pytest.mark.parametrize('matrix,full', R.COLOURS)
+@pytest.mark.parametrize('matrix,full', COLOURS)
 def test_out_against_float64(matrix, full):
     """Uniform random RGB in [-0.1, 1.1]: equal bytes wherever the float64 value is farther than 1e-4 from a rounding tie, at most one
     code apart elsewhere, and at most 1 % of the values so excused."""
     rgb = np.random.default_rng(7).uniform(-0.1, 1.1, (120, 160, 3)).astype(np.float32)
-    got = R.unpack(R.yuv_out(rgb, 'i420', matrix, full), 'i420')
-    f32 = R.out_unquantised(rgb, matrix, full)
+    got = FMT.unpack(FMT.yuv_out(rgb, 'i420', matrix, full), 'i420')
+    f32 = FMT.out_unquantised(rgb, matrix, full)
     near_all, n_all = 0, 0
     for name, g, v32, v64 in zip('Y Cb Cr'.split(), got, f32, _out_f64(rgb, matrix, full)):
         v64 = np.clip(v64, 0, 255)
@@ -86,7 +91,7 @@ def test_out_against_float64(matrix, full):
 
 # ---- known answers ------------------------------------------------------------------------------------------------------------------------
 def _solid(y, cb, cr, layout='i420'):
-    return R.pack(np.full((2, 2), y), np.full((1, 1), cb), np.full((1, 1), cr), layout)
+    return FMT.pack(np.full((2, 2), y), np.full((1, 1), cb), np.full((1, 1), cr), layout)
 
 
 @pytest.mark.parametrize('matrix', ['bt709', 'bt601'])
@@ -94,56 +99,56 @@ def test_known_answers(matrix):
     """Limited-range black and white exactly; the 100 % primaries against the standards' 8-bit tables (Rec. ITU-R BT.709 / BT.601 colour
     bars): out gives the table's codes, in gives the primary back within 0.01 - half a code of Y (0.5 / 219) plus half a code of chroma
     times the largest coefficient (1.86 * 0.5 / 224) is 0.0064."""
-    assert not R.yuv_in(_solid(16, 128, 128), 'i420', matrix, False).any()
-    assert (R.yuv_in(_solid(235, 128, 128), 'i420', matrix, False) == 1).all()
-    assert not R.yuv_in(_solid(0, 128, 128), 'i420', matrix, True).any() and (R.yuv_in(_solid(255, 128, 128), 'i420', matrix, True) == 1).all()
+    assert not FMT.yuv_in(_solid(16, 128, 128), 'i420', matrix, False).any()
+    assert (FMT.yuv_in(_solid(235, 128, 128), 'i420', matrix, False) == 1).all()
+    assert not FMT.yuv_in(_solid(0, 128, 128), 'i420', matrix, True).any() and (FMT.yuv_in(_solid(255, 128, 128), 'i420', matrix, True) == 1).all()
     table = {'bt709': {(1, 0, 0): (63, 102, 240), (0, 1, 0): (173, 42, 26), (0, 0, 1): (32, 240, 118), (1, 1, 0): (219, 16, 138),
                        (0, 1, 1): (188, 154, 16), (1, 0, 1): (78, 214, 230), (1, 1, 1): (235, 128, 128), (0, 0, 0): (16, 128, 128)},
              'bt601': {(1, 0, 0): (81, 90, 240), (0, 1, 0): (145, 54, 34), (0, 0, 1): (41, 240, 110), (1, 1, 0): (210, 16, 146),
                        (0, 1, 1): (170, 166, 16), (1, 0, 1): (106, 202, 222), (1, 1, 1): (235, 128, 128), (0, 0, 0): (16, 128, 128)}}[matrix]
     for rgb, codes in table.items():
         x = np.broadcast_to(np.array(rgb, np.float32), (2, 2, 3))
-        for layout in R.LAYOUTS:
-            fr = R.yuv_out(x, layout, matrix, False)
+        for layout in LAYOUTS:
+            fr = FMT.yuv_out(x, layout, matrix, False)
             assert np.array_equal(fr, _solid(*codes, layout)), (rgb, layout, fr.ravel())
-            assert np.abs(R.yuv_in(fr, layout, matrix, False) - x).max() <= 0.01, rgb
+            assert np.abs(FMT.yuv_in(fr, layout, matrix, False) - x).max() <= 0.01, rgb
 
 
 # ---- round trip, layouts ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('layout', R.LAYOUTS)
-@pytest.mark.parametrize('matrix,full', R.COLOURS)
+@pytest.mark.parametrize('layout', LAYOUTS)
+@pytest.mark.parametrize('matrix,full', COLOURS)
 def test_in_gamut_round_trip_is_the_identity(matrix, full, layout):
     """Replicate in and box mean out are inverse: a frame whose RGB stays inside the gamut returns byte for byte."""
     rng = np.random.default_rng(3)
-    fr = R.pack(rng.integers(90, 166, (30, 50)), rng.integers(108, 149, (15, 25)), rng.integers(108, 149, (15, 25)), layout)
-    rgb = R.yuv_in(fr, layout, matrix, full)
+    fr = FMT.pack(rng.integers(90, 166, (30, 50)), rng.integers(108, 149, (15, 25)), rng.integers(108, 149, (15, 25)), layout)
+    rgb = FMT.yuv_in(fr, layout, matrix, full)
     assert rgb.min() > 0 and rgb.max() < 1
-    assert np.array_equal(R.yuv_out(rgb, layout, matrix, full), fr)
+    assert np.array_equal(FMT.yuv_out(rgb, layout, matrix, full), fr)
 
 
 def test_layouts():
-    fr = R.designed_frames(2, 30, 50, 9)
+    fr = FMT.designed_frames(2, 30, 50, 9)
     for f in fr:
         nv = R.convert_layout(f, 'i420', 'nv12')
         assert nv.shape == f.shape and np.array_equal(nv[:30], f[:30]) and not np.array_equal(nv, f)
         assert np.array_equal(nv.ravel()[1500::2], f.ravel()[1500:1875]) and np.array_equal(nv.ravel()[1501::2], f.ravel()[1875:])
         assert np.array_equal(R.convert_layout(nv, 'nv12', 'i420'), f)
-        assert np.array_equal(R.yuv_in(nv, 'nv12'), R.yuv_in(f, 'i420'))
+        assert np.array_equal(FMT.yuv_in(nv, 'nv12'), FMT.yuv_in(f, 'i420'))
     rgb = np.random.default_rng(1).uniform(-0.1, 1.1, (16, 18, 3)).astype(np.float32)
-    assert np.array_equal(R.yuv_out(rgb, 'nv12'), R.convert_layout(R.yuv_out(rgb, 'i420'), 'i420', 'nv12'))
+    assert np.array_equal(FMT.yuv_out(rgb, 'nv12'), R.convert_layout(FMT.yuv_out(rgb, 'i420'), 'i420', 'nv12'))
 
 
 def test_designed_data():
     """Every byte value in every plane that has 256 samples; in the smaller chroma planes of y5 over the frames of the batch."""
     for c in R.CASES:
-        fr = R.designed_frames(c.B, c.H, c.W, 5)
-        planes = [R.unpack(f, 'i420') for f in fr]
+        fr = FMT.designed_frames(c.B, c.H, c.W, 5)
+        planes = [FMT.unpack(f, 'i420') for f in fr]
         for pi in range(3):
             if planes[0][pi].size >= 256:
                 assert all(len(np.unique(p[pi])) == 256 for p in planes), (c.name, pi)
             elif c.B * planes[0][pi].size >= 400:
                 assert len(np.unique(np.concatenate([p[pi].ravel() for p in planes]))) == 256, (c.name, pi)
-        nv = R.designed_frames(c.B, c.H, c.W, 5, 'nv12')
+        nv = FMT.designed_frames(c.B, c.H, c.W, 5, 'nv12')
         assert all(np.array_equal(R.convert_layout(a, 'i420', 'nv12'), b) for a, b in zip(fr, nv))
 
 
@@ -152,11 +157,11 @@ def test_designed_data():
 def test_cut_equals_frame_conversion_then_float_cut(case, geos):
     geo = geos[case.name]
     total = case.B * len(geo['origins_y']) * len(geo['origins_x'])
-    for layout in R.LAYOUTS:
-        fr = R.designed_frames(case.B, case.H, case.W, 4, layout)
-        for matrix, full in R.COLOURS:
-            a = R.cut(fr, geo, 0, total, layout, matrix, full)
-            b = R.cut_via_frames(fr, geo, 0, total, layout, matrix, full)
+    for layout in LAYOUTS:
+        fr = FMT.designed_frames(case.B, case.H, case.W, 4, layout)
+        for matrix, full in COLOURS:
+            a = FMT.cut(fr, geo, 0, total, layout, matrix, full)
+            b = FMT.cut_via_frames(fr, geo, 0, total, layout, matrix, full)
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (layout, matrix, full)
 
 
@@ -172,14 +177,14 @@ OUT_SIZES = [(2, 2), (16, 18), (30, 50)]       # what tests/test_yuv_gpu.py runs
 
 def test_the_cases_reach_every_instance_and_branch(geos):
     """Which instance of the cut kernel and which of its branches the calls of tests/test_yuv_gpu.py take, from the kernel's own
-    conditions restated in yuv_ref.branches; the same for rgb_to_yuv420_kernel on that test's sizes.  The table goes to the log."""
+    conditions restated in yuv_ref.Format.branches; the same for rgb_to_yuv420_kernel on that test's sizes.  The table goes to the log."""
     seen = {}
     for c in R.CASES:
         s = seen[c.name] = set()
-        for layout in R.LAYOUTS:
+        for layout in LAYOUTS:
             for ranges in R.ranges_of(c, geos[c.name]).values():
                 for tile0, nt in ranges:
-                    s |= R.branches(c, geos[c.name], layout, tile0, nt)
+                    s |= FMT.branches(c, geos[c.name], layout, tile0, nt)
         print(c.name, '|', ', '.join(sorted(s)))
     union = set().union(*seen.values())
     assert union == ALL_BRANCHES, (sorted(ALL_BRANCHES - union), sorted(union - ALL_BRANCHES))
@@ -192,21 +197,21 @@ def test_the_cases_reach_every_instance_and_branch(geos):
     assert {(1500 + j * 25) % 4 for j in range(15)} == {0, 1, 2, 3}
     out = {}
     for h, w in OUT_SIZES:
-        for layout in R.LAYOUTS:
-            out[h, w, layout] = R.out_branches(h, w, layout, 0) | R.out_branches(h, w, layout, R.T.GUARD_U8)
+        for layout in LAYOUTS:
+            out[h, w, layout] = FMT.out_branches(h, w, layout, 0) | FMT.out_branches(h, w, layout, R.T.GUARD_U8)
             print(f'{h}x{w} {layout} |', ', '.join(sorted(out[h, w, layout])))
     assert set().union(*out.values()) == ALL_OUT_BRANCHES
 
 
 def test_the_restatement_passes_its_own_comparison(geos):
-    backend = R.NumpyBackend(lambda c: geos[c.name])
+    backend = FMT.NumpyBackend(lambda c: geos[c.name])
     for c in (R.CASES[1], R.CASES[3]):
-        for layout in R.LAYOUTS:
+        for layout in LAYOUTS:
             for ranges in R.ranges_of(c, geos[c.name]).values():
-                assert not list(R.check_cut(backend, c, geos[c.name], layout, 'bt601', True, ranges, twice=False)), c.name
+                assert not list(FMT.check_cut(backend, c, geos[c.name], layout, 'bt601', True, ranges, twice=False)), c.name
 
 
-@pytest.mark.parametrize('fault', R.FAULTS)
+@pytest.mark.parametrize('fault', FAULTS)
 def test_every_planted_fault_fails_the_comparison(fault, geos):
     """The restatement with one fault planted as the backend of the comparison the GPU test runs, on the same designed data: found in
     every case in which the fault changes what the backend does (the chroma pairing cannot go wrong from an even origin; a frame with
@@ -214,12 +219,12 @@ def test_every_planted_fault_fails_the_comparison(fault, geos):
     must = {'chroma_from_tile_coordinate': ['y1-30x50-b3x2', 'y2-30x50-b3x2-ov3x5', 'y6-12x22-b1x2-noalign'],
             'cb_cr_swapped': ['y1-30x50-b3x2', 'y2-30x50-b3x2-ov3x5', 'y3-16x16', 'y5-18x44-b1x2', 'y6-12x22-b1x2-noalign'],
             'nv12_as_i420': ['y1-30x50-b3x2', 'y2-30x50-b3x2-ov3x5', 'y3-16x16', 'y5-18x44-b1x2', 'y6-12x22-b1x2-noalign']}[fault]
-    backend = R.NumpyBackend(lambda c: geos[c.name], fault)
+    backend = FMT.NumpyBackend(lambda c: geos[c.name], fault)
     for c in R.CASES:
         if c.name in must:
-            for layout in (['nv12'] if fault == 'nv12_as_i420' else R.LAYOUTS):
+            for layout in (['nv12'] if fault == 'nv12_as_i420' else LAYOUTS):
                 ranges = R.ranges_of(c, geos[c.name])['one']
-                first = next(R.check_cut(backend, c, geos[c.name], layout, 'bt709', False, ranges, seed=17, twice=False), None)
+                first = next(FMT.check_cut(backend, c, geos[c.name], layout, 'bt709', False, ranges, seed=17, twice=False), None)
                 print(fault, layout, '->', first)
                 assert first is not None, (fault, c.name, layout)
 
@@ -320,7 +325,7 @@ def _y4m_bytes(tokens, frames):
 
 def test_y4m_round_trip_and_header():
     from film_hip import y4m
-    frames = R.designed_frames(3, 30, 50, 2)
+    frames = FMT.designed_frames(3, 30, 50, 2)
     tokens = ['W50', 'H30', 'F30000:1001', 'Ip', 'A1:1', 'C420mpeg2', 'XYSCSS=420MPEG2', 'XCOLORRANGE=FULL']
     data = _y4m_bytes(tokens, frames)
     assert data.startswith(b'YUV4MPEG2 W50 H30 F30000:1001 Ip A1:1 C420mpeg2 XYSCSS=420MPEG2 XCOLORRANGE=FULL\nFRAME\n')
@@ -410,7 +415,7 @@ def test_video_cli_parser_and_frame_order():
             self.log.append((h, w, pix, matrix, full_range))
             return Stream(self.log)
 
-    frames = R.designed_frames(5, 4, 6, 1)
+    frames = FMT.designed_frames(5, 4, 6, 1)
     tokens = ['W6', 'H4', 'F25:1', 'Ip', 'A1:1', 'C420jpeg', 'XCOLORRANGE=FULL']
     for override, want_full in ((None, True), (False, False)):
         it, out = It(), io.BytesIO()

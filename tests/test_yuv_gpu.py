@@ -8,6 +8,10 @@ import pytest
 import tile_map_ref as T
 import yuv_ref as R
 
+FMT = R.FORMATS['i420']
+LAYOUTS = FMT.layouts      # ('i420', 'nv12')
+COLOURS = [(m, f) for m in ('bt709', 'bt601') for f in (False, True)]      # the four colour settings of the 4:2:0 tests
+
 pytestmark = pytest.mark.gpu
 
 
@@ -34,7 +38,7 @@ def tiny():
 
 # ---- the cut alone ------------------------------------------------------------------------------------------------------------------------
 class GpuBackend:
-    """film_debug_yuv_cut as a backend of yuv_ref.check_cut: both allocations go up as torch tensors (guard | payload | guard in ONE
+    """film_debug_yuv_cut as a backend of yuv_ref.Format.check_cut: both allocations go up as torch tensors (guard | payload | guard in ONE
     allocation each), the entry point gets the payloads' addresses, both come back."""
 
     def __init__(self, eng):
@@ -50,7 +54,7 @@ class GpuBackend:
         return ft.cpu().numpy(), tt.cpu().numpy()
 
 
-@pytest.mark.parametrize('layout', R.LAYOUTS)
+@pytest.mark.parametrize('layout', LAYOUTS)
 @pytest.mark.parametrize('case', R.CASES, ids=lambda c: c.name)
 def test_cut(eng, case, layout):
     """All four colour settings, every range of every partition: tiles_dev[0 : ntiles] == the restatement on the bits, the padding +0.0,
@@ -59,8 +63,8 @@ def test_cut(eng, case, layout):
     try:
         geo = eng.tiling(case.H, case.W, case.align, case.block)
         backend = GpuBackend(eng)
-        findings = [f'[{name}] {m}' for matrix, full in R.COLOURS for name, ranges in R.ranges_of(case, geo).items()
-                    for m in R.check_cut(backend, case, geo, layout, matrix, full, ranges, seed=17)]
+        findings = [f'[{name}] {m}' for matrix, full in COLOURS for name, ranges in R.ranges_of(case, geo).items()
+                    for m in FMT.check_cut(backend, case, geo, layout, matrix, full, ranges, seed=17)]
     finally:
         eng.set_block_overlap(0)
     assert not findings, f'{len(findings)} findings:\n' + '\n'.join(findings[:12])
@@ -79,7 +83,7 @@ def _rgb(h, w, seed):
 
 
 @pytest.mark.parametrize('offset', [0, 1, 2], ids=lambda o: f'dst+{o}')
-@pytest.mark.parametrize('layout', R.LAYOUTS)
+@pytest.mark.parametrize('layout', LAYOUTS)
 @pytest.mark.parametrize('h,w', [(2, 2), (16, 18), (30, 50)])
 def test_to_yuv420(eng, h, w, layout, offset):
     """dst 4-byte aligned (whole words where the rows allow) and 1 / 2 bytes behind that (bytes): the frame == the restatement, the guard
@@ -88,7 +92,7 @@ def test_to_yuv420(eng, h, w, layout, offset):
     n = h * w * 3 // 2
     src = _rgb(h, w, seed=h + w)
     st = torch.from_numpy(src).cuda()
-    for ci, (matrix, full) in enumerate(R.COLOURS):
+    for ci, (matrix, full) in enumerate(COLOURS):
         alloc = np.random.default_rng(ci).integers(0, 256, T.GUARD_U8 + offset + n + T.GUARD_U8, dtype=np.uint8)
         dt = torch.from_numpy(alloc).cuda()
         assert dt.data_ptr() % 4 == 0 and st.data_ptr() % 16 == 0
@@ -96,7 +100,7 @@ def test_to_yuv420(eng, h, w, layout, offset):
         torch.cuda.synchronize()
         got = dt.cpu().numpy()
         want = np.array(alloc)
-        want[T.GUARD_U8 + offset:T.GUARD_U8 + offset + n] = R.yuv_out(src, layout, matrix, full).ravel()
+        want[T.GUARD_U8 + offset:T.GUARD_U8 + offset + n] = FMT.yuv_out(src, layout, matrix, full).ravel()
         bad = np.flatnonzero(got != want)
         assert bad.size == 0, (matrix, full, bad.size, bad[:8] - T.GUARD_U8 - offset, got[bad[:8]], want[bad[:8]])
     assert np.array_equal(st.cpu().numpy().view(np.uint32), src.view(np.uint32))
@@ -113,9 +117,9 @@ _WANT = {}
 
 def _scene(f, h, w, seed):
     """f I420 frames of a scene that moves by (2, -2) px per frame, with every byte value in the Y plane."""
-    base = R.designed_frames(1, h, w, seed)[0]
-    Y, Cb, Cr = R.unpack(base, 'i420')
-    return np.stack([R.pack(np.roll(Y, (2 * i, -2 * i), (0, 1)), np.roll(Cb, (i, -i), (0, 1)), np.roll(Cr, (i, -i), (0, 1)), 'i420') for i in range(f)])
+    base = FMT.designed_frames(1, h, w, seed)[0]
+    Y, Cb, Cr = FMT.unpack(base, 'i420')
+    return np.stack([FMT.pack(np.roll(Y, (2 * i, -2 * i), (0, 1)), np.roll(Cb, (i, -i), (0, 1)), np.roll(Cr, (i, -i), (0, 1)), 'i420') for i in range(f)])
 
 
 def _want(tiny, name):
@@ -123,21 +127,21 @@ def _want(tiny, name):
     if name not in _WANT:
         f, h, w, align, block, overlap, (matrix, full) = STREAMS[name]
         frames = _scene(f, h, w, seed=h + w)
-        x = np.stack([R.yuv_in(fr, 'i420', matrix, full) for fr in frames])
+        x = np.stack([FMT.yuv_in(fr, 'i420', matrix, full) for fr in frames])
         tiny.set_block_overlap(overlap)
         try:
             mids = tiny.interpolate_frames(x[:-1], x[1:], align=align, block_shape=block)
         finally:
             tiny.set_block_overlap(0)
         assert np.isfinite(mids).all()
-        want = np.stack([R.yuv_out(m, 'i420', matrix, full) for m in mids])
+        want = np.stack([FMT.yuv_out(m, 'i420', matrix, full) for m in mids])
         frames.setflags(write=False); want.setflags(write=False)
         _WANT[name] = frames, want
     return _WANT[name]
 
 
 @pytest.mark.parametrize('mem', ['host', 'device'])
-@pytest.mark.parametrize('layout', R.LAYOUTS)
+@pytest.mark.parametrize('layout', LAYOUTS)
 @pytest.mark.parametrize('name', list(STREAMS))
 def test_stream(tiny, name, layout, mem):
     """Every push's mid == yuv_out(interpolate_frames(yuv_in(previous), yuv_in(frame))), byte for byte - also the push after "fuse" 31 -> 0

@@ -73,9 +73,10 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
     eng = FilmEngine(PUBLISHED, device=0)
     eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
     has_stream = hasattr(eng, 'open_stream')
-    has_yuv = 'i420' in getattr(engine_mod, 'PIX', {})
-    has_yuv10 = 'i010' in getattr(engine_mod, 'PIX', {})
-    has_chroma = 'i444' in getattr(engine_mod, 'PIX', {})      # planar 4:2:2 / 4:4:4, 8- and 10-bit
+    PIX = getattr(engine_mod, 'PIX', {})                       # this worker also runs in older trees (--baseline-root): what the tree has, it uses
+    has_yuv, has_yuv10 = 'i420' in PIX, 'i010' in PIX
+    has_chroma = 'i444' in PIX                                 # planar 4:2:2 / 4:4:4, 8- and 10-bit
+    shape_of = getattr(engine_mod, 'frame_shape', lambda pix, h, w: (h * 3 // 2, w))      # (a tree without it has the 4:2:0 layouts alone)
     has_scene = scene_cut and hasattr(engine_mod, 'frame_histogram_device')
     want = lambda key: rows is None or key in rows      # noqa: E731
     out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {}}
@@ -129,8 +130,7 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
                 for pix in ('i420', 'nv12') + (('i010', 'p010') if has_yuv10 else ()) + (('i422', 'i444', 'i210', 'i410') if has_chroma else ()):
                     if not (want('push_' + pix) or want('host_push_' + pix) or (pix == 'i420' and has_scene and pi == 0)):
                         continue
-                    rows_of = {'i422': 2 * h, 'i210': 2 * h, 'i444': 3 * h, 'i410': 3 * h}.get(pix, h * 3 // 2)
-                    yuv[pix] = [torch.empty((rows_of, w), dtype=torch.int16 if pix in ('i010', 'p010', 'i210', 'i410') else torch.uint8, device='cuda') for _ in x]
+                    yuv[pix] = [torch.empty(shape_of(pix, h, w), dtype=torch.int16 if PIX[pix][1] is np.uint16 else torch.uint8, device='cuda') for _ in x]
                     for src, dst in zip(x, yuv[pix]):
                         (eng.to_yuv_device if has_chroma else eng.to_yuv420_device)(src.data_ptr(), dst.data_ptr(), h, w, pix)
                     torch.cuda.synchronize()
@@ -419,16 +419,19 @@ def histogram_alone(calls=50, reps=3):
     """frame_histogram_kernel alone: {"<layout> <size> <data>": [microseconds per call, ...]} from hip events around `calls` calls."""
     import torch
     from film_hip.torch_io import frame_histogram
+    import numpy as np
+    from film_hip import engine as engine_mod
     from film_hip.engine import PIX, frame_histogram_device
+    shape_of = getattr(engine_mod, 'frame_shape', lambda pix, h, w: (h * 3 // 2, w) if pix in ('i420', 'nv12', 'i010', 'p010') else (h, w, 3))
     out = {}
     hist = torch.empty(768, dtype=torch.int32, device='cuda')
     for size, (h, w) in (('1080p', (1080, 1920)), ('4K', (2160, 3840))):
-        for pix in ('u8', 'i420', 'nv12', 'f32') + (('i010', 'p010') if 'i010' in PIX else ()) + (('i422', 'i444', 'i210', 'i410') if 'i444' in PIX else ()):
-            shape = (h * 3 // 2, w) if pix in ('i420', 'nv12', 'i010', 'p010') else (2 * h, w) if pix in ('i422', 'i210') else (3 * h, w) if pix in ('i444', 'i410') else (h, w, 3)
+        for pix in ('u8', 'i420', 'nv12', 'f32') + tuple(p for p in ('i010', 'p010', 'i422', 'i444', 'i210', 'i410') if p in PIX):
+            shape = shape_of(pix, h, w)
             for data in ('random', 'constant'):
                 if pix == 'f32':
                     fr = torch.rand(shape, device='cuda') if data == 'random' else torch.full(shape, 0.5, device='cuda')
-                elif pix in ('i010', 'p010', 'i210', 'i410'):      # 10-bit codes in 16-bit words (int16 as a bit pattern), P010's in bits 6-15
+                elif PIX[pix][1] is np.uint16:      # 10-bit codes in 16-bit words (int16 as a bit pattern), P010's in bits 6-15
                     fr = torch.randint(0, 1024, shape, dtype=torch.int32, device='cuda') if data == 'random' else torch.full(shape, 64, dtype=torch.int32, device='cuda')
                     fr = (((fr << 6) + 32768) % 65536 - 32768 if pix == 'p010' else fr).to(torch.int16)
                 else:
