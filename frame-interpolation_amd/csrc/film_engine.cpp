@@ -130,6 +130,9 @@ constexpr OptionRow kOptions[] = {
     {"block_overlap_w", &film_t::opt_block_overlap_w, AS_IS, false, -1, 65535, "block_overlap_w: -1 (what the align padding of a tile holds) or 0 .. 65535 columns"},
     {"stream_times", &film_t::opt_stream_times, AS_IS, false, 1, kMaxStreamTimes, "stream_times: 1 .. 6 (a primed push of a stream opened with T writes 2^T - 1 frames)"},
     {"scene_cut", &film_t::opt_scene_cut, AS_IS, false, 0, 1000, "scene_cut: 0 (off) or 1 .. 1000 permille of the histogram distance"},
+    {"dup_hi", &film_t::opt_dup_hi, AS_IS, false, -1, 16320, "dup_hi: -1 (off) or 0 .. 16320, the largest 8 x 8 block SAD of a duplicate frame in 8-bit code units"},
+    {"dup_lo", &film_t::opt_dup_lo, AS_IS, false, 0, 16320, "dup_lo: 0 .. 16320, the block SAD in 8-bit code units above which a block counts as changed"},
+    {"dup_frac", &film_t::opt_dup_frac, AS_IS, false, 0, 1000, "dup_frac: 0 .. 1000 permille of a plane's blocks that may count as changed in a duplicate frame"},
     {"tune_ms", &film_t::opt_tune_ms, NONNEG, false},
     {"splitk", &film_t::opt_splitk, BOOL, true},
     {"pack_groups", nullptr, AS_IS, false, 1, 4, "pack_groups: 1 .. 4"},
@@ -390,6 +393,13 @@ int film_frame_histogram(const void* frame_dev, int H, int W, int pix, uint32_t*
       (reinterpret_cast<uintptr_t>(frame_dev) & 3))
     return FILM_ERR_INVALID;
   return film_launch_frame_histogram(frame_dev, H, W, pix, hist_dev, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
+}
+
+int film_frame_diff(const void* a_dev, const void* b_dev, int H, int W, int pix, int lo, uint64_t* out_dev, void* stream) {
+  if (!a_dev || !b_dev || !out_dev || H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31) || check_pix(nullptr, pix, H, W) != FILM_OK ||
+      ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(b_dev)) & 3) || lo < 0 || lo > 65535 || (reinterpret_cast<uintptr_t>(out_dev) & 7))
+    return FILM_ERR_INVALID;
+  return film_launch_frame_diff(a_dev, b_dev, H, W, pix, lo, out_dev, (hipStream_t)stream) == hipSuccess ? FILM_OK : FILM_ERR_HIP;
 }
 
 int film_to_yuv(const float* src, void* dst, int H, int W, int pix, void* stream) {

@@ -205,6 +205,12 @@ struct FilmStream {
   bool hist_valid = false;          // hist_prev is the histogram of the frame in `keep`
   int64_t cut_distance = -1;        // film_stream_cut_info: D of the last push (-1: no comparison made) ...
   int cut = 0;                      // ... and whether it was treated as a cut
+  // option "dup_hi" (include/film_hip.h, "Duplicate frames"); the three buffers are allocated by the first push that needs them
+  void* keep2 = nullptr;            // where such a push lands: compared with `keep`, then dropped or swapped with it
+  uint64_t* diff_dev = nullptr;     // out[3][4] of the comparison ...
+  uint64_t* diff_pin = nullptr;     // ... downloaded here (pinned host memory)
+  int64_t dup_stats[12] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // film_stream_dup_info: out[3][4] of the last push (-1: no comparison made) ...
+  int dup = 0;                      // ... and whether it was dropped as a duplicate
 };
 
 struct film_handle {
@@ -249,6 +255,9 @@ struct film_handle {
   int opt_block_overlap_h = 0, opt_block_overlap_w = 0;
   int opt_stream_times = 1;   // film_stream_open: T = 1 .. 6, a primed push of that stream writes the 2^T - 1 frames of the reference's recursion
   int opt_scene_cut = 0;      // film_stream_push: permille of the histogram distance from which a pair of frames is a scene cut (0: off)
+  // film_stream_push: a pushed frame is a duplicate of the carried one iff, per plane, no 8 x 8 block SAD exceeds dup_hi and at most dup_frac
+  // permille of the blocks exceed dup_lo (8-bit code units; x 4 on 10-bit layouts); dup_hi = -1: off, today's pushes
+  int opt_dup_hi = -1, opt_dup_lo = 0, opt_dup_frac = 1000;
   int opt_host_overlap = 1;   // film_interpolate(FILM_MEM_HOST): 1 = the second frame's upload behind the first frame's first layers, the first half of the
                               // result downloaded behind the second half's last layer (film_engine.cpp, "host pipeline"); 0 = copies, then work, then copy
   hipEvent_t pipe_ev[2] = {nullptr, nullptr};   // its two events (second frame in place / first half stitched), lazily created

@@ -436,6 +436,17 @@ hipError_t film_launch_rgb_to_yuv(const float* src, void* dst, int H, int W, int
 #define FILM_HIST_WG_PER_CU 2
 #define FILM_HIST_VEC_BYTES 16
 hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix, uint32_t* hist, hipStream_t s);
+// The 8 x 8 block SADs of two frames of one pixel type (include/film_hip.h, "Duplicate frames"): out[p] = {total, max, over, blocks} of plane p,
+// `over` counting the blocks whose SAD is > lo (0 .. 65535, stored-code units).  The launcher zeroes the 96 bytes first: a call overwrites.  `a`
+// and `b` are 4-byte aligned, `out` 8-byte aligned; refusals as film_launch_frame_histogram.  A lane takes one block position (the blocks of
+// the planes that interleave there) per step; the grid is min(what the frame needs, FILM_DIFF_WG_PER_CU workgroups per compute unit) of
+// FILM_DIFF_THREADS lanes with grid-stride loops, so one pass of the full grid covers CUs * WG_PER_CU * THREADS block positions per plane group.
+// (One workgroup per compute unit: every workgroup ends in up to twelve atomics on one 96-byte line, and at 4K - 507 to 761 workgroups when uncapped -
+// two random frames measured 31 - 35 us with a cap of 4 or 2 and 20 - 24 us with 1; 1080p needs fewer than 256 workgroups and does not change.
+// profiles/dedup_bench.log, last block.)
+#define FILM_DIFF_THREADS 256
+#define FILM_DIFF_WG_PER_CU 1
+hipError_t film_launch_frame_diff(const void* a, const void* b, int H, int W, int pix, int lo, uint64_t* out, hipStream_t s);
 // fills n floats with a deterministic pseudo-random pattern in [-1, 1) (autotune inputs only)
 hipError_t film_launch_fill_random(float* dst, int64_t n, uint32_t seed, hipStream_t s);
 

@@ -1,5 +1,5 @@
 // film_stream.cpp -- the frame streams of the C-ABI (film_stream_*; the contract: include/film_hip.h): the one open stream of a handle
-// (FilmStream, film_internal.h), the schedule of a push, where the frames of a push live, the scene-cut rule, and the JSON queries about
+// (FilmStream, film_internal.h), the schedule of a push, where the frames of a push live, the scene-cut and duplicate rules, and the JSON queries about
 // the stream plan.  The stream plan and its orientations are the plan cache's (get_plan / plan_orientation, film_plans.cpp); tile geometry,
 // the `pix` check and the stream choice are shared with the other entry points (film_engine.cpp).
 #include "film_internal.h"
@@ -9,9 +9,10 @@ using namespace film_internal;
 // The stream's device buffers go back and it is closed.  Work that may still use them is the caller's to wait for.
 void film_internal::stream_free(film_t* h) {
   FilmStream& fs = h->fs;
-  for (void* p : {fs.keep, (void*)fs.result, (void*)fs.result8, (void*)fs.hist_dev})
+  for (void* p : {fs.keep, fs.keep2, (void*)fs.result, (void*)fs.result8, (void*)fs.hist_dev, (void*)fs.diff_dev})
     if (p) (void)hipFree(p);
   if (fs.hist_pin) (void)hipHostFree(fs.hist_pin);
+  if (fs.diff_pin) (void)hipHostFree(fs.diff_pin);
   fs = FilmStream{};
 }
 
@@ -124,6 +125,32 @@ int stream_scene_cut(film_t* h, hipStream_t s, int k, bool* cut) {
   }
   fs.hist_valid = false;   // (until the push has succeeded)
   std::copy(fs.hist_pin, fs.hist_pin + FILM_HIST_BINS, fs.hist_prev);
+  return FILM_OK;
+}
+
+// Option "dup_hi" = hi >= 0: `frame` goes to fs.keep2 on `s`; on a primed stream it is compared there with the carried frame in fs.keep
+// (film_frame_diff's kernel), the 96 bytes are downloaded and waited for, and *dup = the rule's verdict (include/film_hip.h, "Duplicate
+// frames").  The caller drops the push or swaps the two buffers.
+int stream_duplicate(film_t* h, const void* frame, bool host, hipStream_t s, int hi, bool* dup) {
+  FilmStream& fs = h->fs;
+  const size_t fb = frame_bytes(fs.pix, fs.H, fs.W);
+  constexpr size_t bytes = 12 * sizeof(uint64_t);
+  if (!fs.keep2) HIPCHK(h, hipMalloc(&fs.keep2, (fb + 3) & ~(size_t)3));   // (whole 32-bit words, as fs.keep)
+  if (!fs.diff_dev) HIPCHK(h, hipMalloc((void**)&fs.diff_dev, bytes));
+  if (!fs.diff_pin) HIPCHK(h, hipHostMalloc((void**)&fs.diff_pin, bytes, hipHostMallocDefault));
+  HIPCHK(h, hipMemcpyAsync(fs.keep2, frame, fb, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  if (!fs.primed) return FILM_OK;
+  const int64_t m = pix_is_yuv10(fs.pix) ? 4 : 1;   // a value means the same on the 8- and 10-bit versions of one video
+  HIPCHK(h, film_launch_frame_diff(fs.keep, fs.keep2, fs.H, fs.W, fs.pix, (int)(h->opt_dup_lo * m), fs.diff_dev, s));
+  HIPCHK(h, hipMemcpyAsync(fs.diff_pin, fs.diff_dev, bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  bool same = true;
+  for (int p = 0; p < 3; ++p) {
+    const uint64_t* o = fs.diff_pin + 4 * p;   // {total, max, over, blocks}
+    for (int k = 0; k < 4; ++k) fs.dup_stats[4 * p + k] = (int64_t)o[k];
+    same = same && (int64_t)o[1] <= hi * m && 1000 * (int64_t)o[2] <= (int64_t)h->opt_dup_frac * (int64_t)o[3];
+  }
+  *dup = same;
   return FILM_OK;
 }
 
@@ -289,6 +316,15 @@ int film_stream_cut_info(film_t* h, int64_t* distance, int64_t* samples, int* cu
   return FILM_OK;
 }
 
+int film_stream_dup_info(film_t* h, int64_t* stats, int* dup) {
+  if (!h) return FILM_ERR_INVALID;
+  const FilmStream& fs = h->fs;
+  if (!fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  if (stats) std::copy(fs.dup_stats, fs.dup_stats + 12, stats);
+  if (dup) *dup = fs.dup;
+  return FILM_OK;
+}
+
 int film_stream_close(film_t* h) {
   if (!h) return FILM_ERR_INVALID;
   if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
@@ -298,7 +334,7 @@ int film_stream_close(film_t* h) {
   return FILM_OK;
 }
 
-// The order of the device work of a push - keep-copy; histogram, download, wait (option "scene_cut"); cut; per step of the schedule: run,
+// The order of the device work of a push - (option "dup_hi": copy beside the carried frame, compare, download, wait; a duplicate ends here) keep-copy; histogram, download, wait (option "scene_cut"); cut; per step of the schedule: run,
 // join, quantise, download, feed-cut; one wait for a host push - is what lets a host push download a frame beside the next pair run, and
 // what makes it hold for pageable memory, whose copies block the calling thread.
 int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int mem_kind, void* stream) {
@@ -312,17 +348,31 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
   if (!frame || !produced || (fs.primed && fs.mask && !mid)) return fail(h, FILM_ERR_INVALID, "NULL argument");
   if (mem_kind != FILM_MEM_HOST && mem_kind != FILM_MEM_DEVICE) return fail(h, FILM_ERR_INVALID, "bad mem_kind");
   HIPCHK(h, hipSetDevice(h->device));
+  const bool host = mem_kind == FILM_MEM_HOST;
+  // option "dup_hi": duplicates are decided first - a dropped push leaves the stream as it was (the plan and the carried histogram included)
+  const int dup_hi = h->opt_dup_hi;
+  std::fill(fs.dup_stats, fs.dup_stats + 12, (int64_t)-1); fs.dup = 0;
+  int rc = FILM_OK;
+  if (dup_hi >= 0) {
+    bool dup = false;
+    if ((rc = stream_duplicate(h, frame, host, s, dup_hi, &dup))) return rc;
+    if (dup) {
+      fs.dup = 1;
+      unprime.armed = false;
+      return FILM_OK;
+    }
+  }
   TileMapParams tp{};
   tp.B = 1;
-  int rc = tile_geometry(h, fs.H, fs.W, fs.block_h, fs.block_w, fs.align, &tp);   // ("block_overlap_*" as they are NOW)
+  rc = tile_geometry(h, fs.H, fs.W, fs.block_h, fs.block_w, fs.align, &tp);   // ("block_overlap_*" as they are NOW)
   if (rc) return rc;
   const int T = tp.bh * tp.bw;
   Plan* P0 = nullptr;
   rc = get_plan(h, T, tp.TH, tp.TW, true, &P0, T, fs.times + 1);
   if (rc) return rc;
-  const bool host = mem_kind == FILM_MEM_HOST;
   if (fs.primed && (fs.plan_id != P0->id || !same_geometry(fs.geo, tp)) && (rc = stream_reextract(h, P0, tp, s))) return rc;
-  HIPCHK(h, hipMemcpyAsync(fs.keep, frame, frame_bytes(fs.pix, fs.H, fs.W), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  if (dup_hi >= 0) std::swap(fs.keep, fs.keep2);   // (behind the re-extraction, which reads the carried frame's copy)
+  else HIPCHK(h, hipMemcpyAsync(fs.keep, frame, frame_bytes(fs.pix, fs.H, fs.W), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
   // option "scene_cut": a cut is film_stream_reset followed by this push - the frame starts a new scene in slot 0, extraction only
   const int scene_k = h->opt_scene_cut;
   bool cut = false;

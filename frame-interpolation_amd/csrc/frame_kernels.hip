@@ -1,5 +1,5 @@
 // frame_kernels.hip -- frame I/O: the kernels that move pixels between the caller's frames and the tiles a plan works on (gfx950, wave64).
-// None of them is an op of a plan; film_engine.cpp and film_stream.cpp call the four launchers at the end of this file and film_launch_frame_histogram, which stands beside its kernel.
+// None of them is an op of a plan; film_engine.cpp and film_stream.cpp call the four launchers at the end of this file and film_launch_frame_histogram / film_launch_frame_diff, which stand beside their kernels.
 //
 //   frame_to_tiles<OVERLAP>             _pad_to_align + image_to_patches, float32 frames    eval/interpolator.py:30-63, :66-104
 //   frame_u8_to_tiles<OVERLAP>          the same on 8-bit RGB frames: float32(byte) / 255   eval/util.py read_image
@@ -9,6 +9,7 @@
 //   to_uint8                            clip(x * 255, 0, 255) + 0.5, truncated              eval/util.py:51-52 (write_image)
 //   rgb_to_yuv<LAYOUT>                  float32 RGB -> the planes of one Y'CbCr frame       the same three sections
 //   frame_histogram<LAYOUT>            3 x 256 counters of a frame's 8-bit sample codes    include/film_hip.h, "Scene cuts"
+//   frame_diff<LAYOUT>                 the 8 x 8 block SADs of two frames, per plane       include/film_hip.h, "Duplicate frames"
 //
 // OVERLAP: the tile's content is the patch grown by the overlap, from film_tile_origin (options "block_overlap_h" / "block_overlap_w").
 // LAYOUT: a FILM_PIX_* value.  The Y'CbCr cut and quantiser are written once over YuvLayout<LAYOUT>, which states what a layout decides: the sample
@@ -638,6 +639,176 @@ __global__ __launch_bounds__(FILM_HIST_THREADS) void frame_histogram_kernel(cons
   }
 }
 
+// ---- the block SADs of two frames (film_frame_diff; include/film_hip.h, "Duplicate frames") ------------------------------------------------
+// out[p] = {total, max, over, blocks} of the 8 x 8 block SADs of plane p between frames a and b, on full-depth codes.  Integers only (the F32
+// quantisation aside), so the result does not depend on the grid or the arrival order.
+//   groups    A frame is one to three GROUPS of planes whose samples interleave: a planar Y'CbCr frame is three groups of one plane, a
+//             semi-planar one is Y and the CbCr pairs (two planes), an RGB frame is one group of three.  A group of NP planes of hp x wp
+//             samples is hp rows of wp * NP elements; its blocks are those of its planes, anchored on the plane.
+//   lanes     one lane per block position of a group - NP blocks -, adjacent lanes on adjacent blocks of a block row, in a grid-stride loop
+//             per group (the group is a compile-time value inside the loop, so the NP block SADs stay in registers and no accumulator is
+//             indexed by a runtime plane).  A whole row segment - eight samples per plane - whose address is 4-byte aligned is read as the
+//             2 NP (8-bit) or 4 NP (16-bit) 32-bit words that ARE it: wave-wide that is one coalesced run of 8 or 16 bytes per lane, and
+//             v_sad_u8 / v_sad_u16 take the words as they are (interleaved planes: masked per plane first - a masked-out byte adds 0).  A
+//             partial block or an unaligned row goes sample by sample.  No load reaches outside the frame.
+//   codes     8 bits: the byte; 10 bits: (w >> SHIFT) & 1023, on both halves of a word at once; F32: film_to_uint8's byte, as the histogram.
+//   reduce    per lane 3 x {total (64-bit), max, over, blocks}; wave shuffles, LDS across the four waves, then one lane per plane flushes
+//             with integer atomics (64-bit add, unsigned max, add, add).  `blocks` counts the blocks the lanes VISITED.  out is zeroed by the launcher.
+struct DiffGroup { int64_t off; int hp, wp, bw; int64_t units; };   // first element, plane size in samples, blocks per block row, block positions
+struct DiffParams {
+  const void *a, *b;
+  DiffGroup g[3];
+  uint32_t lo;
+  unsigned long long* out;
+};
+// what the comparison asks of a layout: the two RGB types, else what YuvLayout<LAYOUT> says (sample width, semi-planar chroma, where the code sits)
+struct RgbDiffTraits { static constexpr bool WIDE = false, SEMI_PLANAR = false; static constexpr int SHIFT = 0; };
+template <int LAYOUT> struct DiffLayout {
+  static constexpr bool F32 = LAYOUT == FILM_PIX_F32, RGB = F32 || LAYOUT == FILM_PIX_U8;
+  using L = std::conditional_t<RGB, RgbDiffTraits, YuvLayout<RGB ? FILM_PIX_I420 : LAYOUT>>;
+  static constexpr bool WIDE = L::WIDE, SEMI = L::SEMI_PLANAR;
+  static constexpr int SHIFT = L::SHIFT;
+  static constexpr int GROUPS = RGB ? 1 : SEMI ? 2 : 3;
+  static constexpr int planes(int g) { return RGB ? 3 : SEMI && g == 1 ? 2 : 1; }          // NP of group g
+  static constexpr int plane(int g, int c) { return RGB ? c : SEMI ? (g ? 1 + c : 0) : g; }   // the plane of its component c
+  using Elem = std::conditional_t<F32, float, std::conditional_t<WIDE, uint16_t, uint8_t>>;
+};
+// byte t of word k of a row segment of three interleaved 8-bit planes belongs to plane (4 k + t) % 3
+constexpr uint32_t rgb_word_mask(int k, int c) {
+  uint32_t m = 0;
+  for (int t = 0; t < 4; ++t)
+    if ((4 * k + t) % 3 == c) m |= 0xffu << (8 * t);
+  return m;
+}
+// s[c] += the absolute differences of component c over `cols` samples per plane of one row of a block
+template <int LAYOUT, int NP>
+__device__ __forceinline__ void diff_row(const typename DiffLayout<LAYOUT>::Elem* pa, const typename DiffLayout<LAYOUT>::Elem* pb, int cols, uint32_t (&s)[NP]) {
+  using D = DiffLayout<LAYOUT>;
+  if constexpr (D::F32) {
+    auto q = [](float x) { return (int)(quantise<255>(x * 255.f) & 255u); };   // film_to_uint8's operations, as frame_histogram_kernel's
+    if (cols == 8) {
+#pragma unroll
+      for (int e = 0; e < 8 * NP; ++e) s[e % NP] += (uint32_t)abs(q(pa[e]) - q(pb[e]));
+    } else {
+      for (int x = 0; x < cols; ++x)
+#pragma unroll
+        for (int c = 0; c < NP; ++c) s[c] += (uint32_t)abs(q(pa[x * NP + c]) - q(pb[x * NP + c]));
+    }
+  } else {
+    const bool words = cols == 8 && ((reinterpret_cast<uintptr_t>(pa) | reinterpret_cast<uintptr_t>(pb)) & 3) == 0;
+    if (words) {
+      const uint32_t* wa = reinterpret_cast<const uint32_t*>(pa);
+      const uint32_t* wb = reinterpret_cast<const uint32_t*>(pb);
+      constexpr int NW = 8 * NP * (int)sizeof(typename D::Elem) / 4;
+#pragma unroll
+      for (int k = 0; k < NW; ++k) {
+        uint32_t x = wa[k], y = wb[k];
+        if constexpr (D::WIDE) {
+          x = (x >> D::SHIFT) & 0x03ff03ffu; y = (y >> D::SHIFT) & 0x03ff03ffu;   // both codes of the word
+          if constexpr (NP == 1) s[0] = __builtin_amdgcn_sad_u16(x, y, s[0]);
+          else {   // a CbCr pair
+            s[0] = __builtin_amdgcn_sad_u16(x & 0xffffu, y & 0xffffu, s[0]);
+            s[1] = __builtin_amdgcn_sad_u16(x >> 16, y >> 16, s[1]);
+          }
+        } else if constexpr (NP == 1) s[0] = __builtin_amdgcn_sad_u8(x, y, s[0]);
+        else if constexpr (NP == 2) {
+          s[0] = __builtin_amdgcn_sad_u8(x & 0x00ff00ffu, y & 0x00ff00ffu, s[0]);
+          s[1] = __builtin_amdgcn_sad_u8(x & 0xff00ff00u, y & 0xff00ff00u, s[1]);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) s[c] = __builtin_amdgcn_sad_u8(x & rgb_word_mask(k % 3, c), y & rgb_word_mask(k % 3, c), s[c]);
+        }
+      }
+    } else {
+      for (int x = 0; x < cols; ++x)
+#pragma unroll
+        for (int c = 0; c < NP; ++c) {
+          int u = pa[x * NP + c], v = pb[x * NP + c];
+          if constexpr (D::WIDE) { u = (u >> D::SHIFT) & 1023; v = (v >> D::SHIFT) & 1023; }
+          s[c] += (uint32_t)abs(u - v);
+        }
+    }
+  }
+}
+struct DiffAcc { unsigned long long total[3]; uint32_t max[3], over[3], blocks[3]; };
+template <int LAYOUT, int G>
+__device__ __forceinline__ void diff_group(const DiffParams& p, DiffAcc& acc) {
+  using D = DiffLayout<LAYOUT>;
+  using Elem = typename D::Elem;
+  constexpr int NP = D::planes(G);
+  const DiffGroup g = p.g[G];
+  const int64_t pitch = (int64_t)g.wp * NP;
+  for (int64_t u = (int64_t)blockIdx.x * FILM_DIFF_THREADS + threadIdx.x; u < g.units; u += (int64_t)gridDim.x * FILM_DIFF_THREADS) {
+    const int i = (int)(u / g.bw), j = (int)(u % g.bw);
+    const int rows = min(8, g.hp - 8 * i), cols = min(8, g.wp - 8 * j);
+    const int64_t e0 = g.off + (int64_t)(8 * i) * pitch + (int64_t)(8 * j) * NP;
+    const Elem* pa = static_cast<const Elem*>(p.a) + e0;
+    const Elem* pb = static_cast<const Elem*>(p.b) + e0;
+    uint32_t s[NP];
+#pragma unroll
+    for (int c = 0; c < NP; ++c) s[c] = 0;
+    if (rows == 8) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) diff_row<LAYOUT, NP>(pa + r * pitch, pb + r * pitch, cols, s);
+    } else {
+      for (int r = 0; r < rows; ++r) diff_row<LAYOUT, NP>(pa + r * pitch, pb + r * pitch, cols, s);
+    }
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+      const int pl = D::plane(G, c);
+      acc.total[pl] += s[c];
+      acc.max[pl] = max(acc.max[pl], s[c]);
+      acc.over[pl] += s[c] > p.lo ? 1u : 0u;
+      acc.blocks[pl] += 1u;
+    }
+  }
+}
+template <int LAYOUT>
+__global__ __launch_bounds__(FILM_DIFF_THREADS) void frame_diff_kernel(DiffParams p) {
+  using D = DiffLayout<LAYOUT>;
+  DiffAcc acc{};
+  diff_group<LAYOUT, 0>(p, acc);
+  if constexpr (D::GROUPS > 1) diff_group<LAYOUT, 1>(p, acc);
+  if constexpr (D::GROUPS > 2) diff_group<LAYOUT, 2>(p, acc);
+  // wave: shuffles; workgroup: LDS; device: one lane per plane
+  constexpr int WAVES = FILM_DIFF_THREADS / 64;
+  __shared__ unsigned long long sh_total[WAVES][3];
+  __shared__ uint32_t sh_rest[WAVES][3][3];
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      acc.total[pl] += __shfl_down(acc.total[pl], d, 64);
+      acc.max[pl] = max(acc.max[pl], (uint32_t)__shfl_down(acc.max[pl], d, 64));
+      acc.over[pl] += __shfl_down(acc.over[pl], d, 64);
+      acc.blocks[pl] += __shfl_down(acc.blocks[pl], d, 64);
+    }
+  }
+  const int wave = threadIdx.x / 64;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+      sh_total[wave][pl] = acc.total[pl];
+      sh_rest[wave][pl][0] = acc.max[pl]; sh_rest[wave][pl][1] = acc.over[pl]; sh_rest[wave][pl][2] = acc.blocks[pl];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int pl = threadIdx.x;
+    unsigned long long total = 0, mx = 0, over = 0, blocks = 0;
+    for (int w = 0; w < WAVES; ++w) {
+      total += sh_total[w][pl];
+      mx = max(mx, (unsigned long long)sh_rest[w][pl][0]);
+      over += sh_rest[w][pl][1]; blocks += sh_rest[w][pl][2];
+    }
+    unsigned long long* o = p.out + 4 * pl;
+    if (total) atomicAdd(o, total);
+    if (mx) atomicMax(o + 1, mx);
+    if (over) atomicAdd(o + 2, over);
+    if (blocks) atomicAdd(o + 3, blocks);
+  }
+}
+
 }  // namespace
 
 // One frame's histogram: zeroes the 768 counters, then counts.  At most FILM_HIST_WG_PER_CU workgroups per compute unit, fewer for a frame
@@ -663,6 +834,43 @@ hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix,
               : pix_is_yuv10(pix) ? frame_histogram_kernel<FILM_PIX_I010> : frame_histogram_kernel<FILM_PIX_I420>;   // (planar: every subsampling)
   static_assert(FILM_HIST_THREADS == 256, "launch_units starts workgroups of 256");
   return launch_units(kernel, grid * FILM_HIST_THREADS, s, frame, n, plane, cplane, hist);   // `grid` workgroups
+}
+
+// The block SADs of two frames: zeroes the twelve counters, then compares.  At most FILM_DIFF_WG_PER_CU workgroups per compute unit, fewer
+// for a frame that has fewer block positions; the grid-stride loops take the rest.  The instances are the histogram's.
+hipError_t film_launch_frame_diff(const void* a, const void* b, int H, int W, int pix, int lo, uint64_t* out, hipStream_t s) {
+  const int layout = pix_layout(pix);   // (the colour flags do not enter)
+  const bool yuv = pix_is_yuv(pix);
+  if (!a || !b || !out || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3))
+    return hipErrorInvalidValue;
+  if (lo < 0 || lo > 65535 || (reinterpret_cast<uintptr_t>(out) & 7)) return hipErrorInvalidValue;
+  if (layout != FILM_PIX_F32 && layout != FILM_PIX_U8 && !yuv) return hipErrorInvalidValue;
+  const PixLayout row = pix_row(pix);
+  if (yuv && ((W & row.sx) | (H & row.sy))) return hipErrorInvalidValue;
+  DiffParams p{};
+  p.a = a; p.b = b; p.lo = (uint32_t)lo; p.out = reinterpret_cast<unsigned long long*>(out);
+  auto group = [](int64_t off, int hp, int wp) {
+    const int bw = (wp + 7) / 8;
+    return DiffGroup{off, hp, wp, bw, (int64_t)((hp + 7) / 8) * bw};
+  };
+  p.g[0] = group(0, H, W);
+  if (yuv) {
+    const int hc = H >> row.sy, wc = W >> row.sx;
+    p.g[1] = group((int64_t)H * W, hc, wc);                                           // Cb, or the CbCr pairs
+    if (!row.semi_planar) p.g[2] = group((int64_t)H * W + (int64_t)hc * wc, hc, wc);   // Cr
+  }
+  int dev = 0, cus = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e == hipSuccess) e = hipMemsetAsync(out, 0, 12 * sizeof(uint64_t), s);
+  if (e != hipSuccess) return e;
+  const int64_t units = std::max(p.g[0].units, std::max(p.g[1].units, p.g[2].units));   // (every group's loop starts at lane 0)
+  const int64_t grid = std::min<int64_t>((int64_t)std::max(cus, 1) * FILM_DIFF_WG_PER_CU, (units + FILM_DIFF_THREADS - 1) / FILM_DIFF_THREADS);
+  auto kernel = layout == FILM_PIX_F32 ? frame_diff_kernel<FILM_PIX_F32> : layout == FILM_PIX_U8 ? frame_diff_kernel<FILM_PIX_U8>
+              : layout == FILM_PIX_NV12 ? frame_diff_kernel<FILM_PIX_NV12> : layout == FILM_PIX_P010 ? frame_diff_kernel<FILM_PIX_P010>
+              : pix_is_yuv10(pix) ? frame_diff_kernel<FILM_PIX_I010> : frame_diff_kernel<FILM_PIX_I420>;   // (planar: every subsampling)
+  static_assert(FILM_DIFF_THREADS == 256, "launch_units starts workgroups of 256");
+  return launch_units(kernel, grid * FILM_DIFF_THREADS, s, p);   // `grid` workgroups
 }
 
 namespace {

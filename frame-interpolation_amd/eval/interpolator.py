@@ -173,7 +173,7 @@ class Interpolator:
     return self._engine.interpolate_sequence(frames, align=self._align, block_shape=bs)
 
   def open_stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False, scene_cut: int = 0,
-                  times: int = 1):
+                  times: int = 1, dedup=None):
     """(extension) A frame stream of h x w frames (film_hip.engine.FilmStream; film_stream_*): push() one frame at a time and get
     the mid-frame between it and the one pushed before, bit-identical to self(previous, frame, dt) with align, block_shape and
     block_overlap as set, with one feature extraction per frame.  pix 'f32': float32 frames, not clipped; 'u8': uint8 frames in
@@ -185,12 +185,15 @@ class Interpolator:
     bit-identical to self() on its float32 parents (engine option "stream_times", set for this stream only).  The stream's
     select(positions) narrows a primed push to some of those 2^times - 1 positions - only they and their ancestors are run - which is how
     eval.video_cli --fps converts to a rate that is no power of two (film_hip/retime.py).
+    dedup (None | hi | (hi, lo, frac)): not None sets the engine options "dup_hi", "dup_lo" and "dup_frac" (include/film_hip.h, "Duplicate
+    frames") before the stream opens - a push judged a duplicate of the carried frame then returns None and changes nothing,
+    FilmStream.dup_info() tells why; engine options like scene_cut, so they stay set; None (default) leaves the engine as it is.
     One stream per Interpolator at a time."""
     if self._align is not None:
       assert self._align > 0, 'align must be a positive number.'
     bs = self._block_shape if self._block_shape is not None and np.prod(self._block_shape) > 1 else None
     return self._engine.open_stream(h, w, align=self._align, block_shape=bs, pix=pix, matrix=matrix, full_range=full_range,
-                                    scene_cut=scene_cut, times=times)
+                                    scene_cut=scene_cut, times=times, dedup=dedup)
 
   def __call__(self, x0: np.ndarray, x1: np.ndarray,
                dt: np.ndarray) -> np.ndarray:

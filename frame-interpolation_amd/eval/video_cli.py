@@ -23,6 +23,11 @@ rates), an output that lands on an input frame is that frame, and each push comp
 ancestors in the recursion (FilmStream.select) - 24 -> 60 at T = 3 makes four pair runs per input interval where a full push makes seven.
 Input frames no output lands on are not written; the snap errors and the pair runs made are reported on stderr.
 
+--dedup HI[:LO[:FRAC]] (with --fps) drops input frames that repeat the last kept frame (engine options "dup_hi" / "dup_lo" / "dup_frac",
+include/film_hip.h, "Duplicate frames": 8 x 8 block sums of absolute differences per plane) and spreads the outputs of the stretched
+interval over the one push that closes it: 24p film in a 60p container comes out as even motion, not as the source's stutter at a
+higher rate.  The frame count and the header are those of the same command without the flag.  No values are recommended.
+
 The output header keeps the input's tokens with the frame rate (F) doubled (multiplied by 2^T).  What is read: film_hip/y4m.py (8-bit and 10-bit 4:2:0, with --chroma any planar 4:2:2 and 4:4:4; progressive).
 """
 import argparse
@@ -64,6 +69,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help='Convert to this frame rate (N, N:D or N/D, e.g. 60 or 60000:1001) instead of multiplying the rate: every output '
                          'frame is the input frame or mid-frame nearest to its instant on the grid of --times_to_interpolate, and only those '
                          'mid-frames are computed.  At most 2^T times the input rate; the input header must name its rate (an F token).')
+    ap.add_argument('--dedup', default=None, metavar='HI[:LO[:FRAC]]',
+                    help='With --fps: drop input frames that repeat the last kept one and spread the outputs over the longer interval, so '
+                         'repeated frames (film in a 30p / 60p container, animation on twos and threes, screen captures) stop stuttering.  A '
+                         'frame is a duplicate when, in every plane, no 8 x 8 block differs by more than HI (sum of absolute differences in '
+                         '8-bit code units, 0 .. 16320) and at most FRAC permille (default 1000) of the blocks differ by more than LO (default '
+                         '0).  0 drops exact repeats only.  No values are recommended (unmeasured on footage).')
     return ap
 
 
@@ -167,10 +178,96 @@ def convert_frame_rate(it, reader: y4m.Y4MReader, out, rate_out, matrix: str = '
     return writer.frames_written
 
 
+def parse_dedup(text: str):
+    """'HI', 'HI:LO' or 'HI:LO:FRAC' -> (hi, lo, frac) for open_stream(dedup=...); lo defaults to 0, frac to 1000.  ValueError otherwise."""
+    parts = str(text).strip().split(':')
+    if not 1 <= len(parts) <= 3 or not all(p.isdigit() for p in parts):
+        raise ValueError(f'HI, HI:LO or HI:LO:FRAC with non-negative integers, got {text!r}')
+    hi, lo, frac = ([int(p) for p in parts] + [0, 1000][len(parts) - 1:])[:3]
+    if hi > 16320 or lo > 16320 or frac > 1000:
+        raise ValueError(f'HI and LO are 0 .. 16320 and FRAC is 0 .. 1000 permille, got {text!r}')
+    return hi, lo, frac
+
+
+def convert_frame_rate_dedup(it, reader: y4m.Y4MReader, out, rate_out, dedup, matrix: str = 'bt709', full_range: Optional[bool] = None,
+                             scene_cut: int = 0, cuts: Optional[list] = None, times: int = 1, stats: Optional[dict] = None) -> int:
+    """--fps with --dedup: convert_frame_rate on a stream opened with dedup = (hi, lo, frac) (engine options "dup_hi" / "dup_lo" / "dup_frac":
+    a pushed frame judged a duplicate of the last KEPT frame is dropped by the stream).  The kept frames k_0 = 0 < k_1 < ... cut the video into
+    spans; retime.Retime.span spreads the outputs of a span over the grid of the ONE push that closes it, so a repeated frame no longer
+    stutters: A A A B at three outputs per input becomes A, 1/9, 2/9 ... of the way to B instead of A A' A'' B.  Before input frame i is
+    pushed, with k the last kept frame, the positions of span(k, i - k) are selected - what the push needs if it closes the span; a
+    duplicate runs nothing and the next frame tries again with a longer span.  A closed span is written in order: g = 0 the held frame k,
+    0 < g < 2^T the push's results, g = 2^T the pushed frame; a scene cut on the closing frame holds frame k in place of the results.  A run
+    of duplicates the video ends in is written as the last kept frame.  The frame count and the header are convert_frame_rate's, and a video
+    without duplicates is written byte for byte as by it.  One kept frame is held until its span closes.
+    stats gains 'duplicates' (pushes dropped) and 'repeats' (outputs that shared a grid index with the one before)."""
+    times = int(times)
+    if reader.rate is None:
+        raise ValueError('--fps needs the frame rate of the input: its header has no F token')
+    rt = retime.Retime(reader.rate, rate_out, times)
+    per_push, top = (1 << times) - 1, 1 << times
+    dyadic = rt.p << times == rt.q
+    full = reader.full_range if full_range is None else bool(full_range)
+    writer = y4m.Y4MWriter(out, y4m.multiply_rate(reader.tokens, 1 << times) if dyadic else y4m.set_rate(reader.tokens, rate_out))
+    err_max = err_sum = runs = pushes = duplicates = repeats = 0
+    with it.open_stream(reader.height, reader.width, pix=stream_pix(reader), matrix=matrix, full_range=full, dedup=tuple(dedup),
+                        **({'scene_cut': int(scene_cut)} if scene_cut else {}), **({'times': times} if times != 1 else {})) as st:
+        selected = tuple(range(1, per_push + 1))
+        k, held, seen = 0, None, 0
+        for i, frame in enumerate(reader):
+            seen = i + 1
+            if not i:
+                st.push(frame)
+                held = frame
+                continue
+            sp = rt.span(k, i - k)
+            pos = tuple(sorted({g for g in sp.grid if 0 < g < top}))
+            if pos != selected:
+                st.select(pos)
+                selected = pos
+            mid = st.push(frame)
+            pushes += 1
+            if st.dup_info()[1]:
+                duplicates += 1
+                continue
+            at = {}
+            if mid is not None:
+                at = dict(zip(pos, (mid,) if times == 1 else mid))
+                runs += retime.push_cost(times, pos)[0]
+            elif scene_cut and (pos or st.cut_info()[2]):
+                at = None                       # a frame hold across the cut
+                if cuts is not None:
+                    cuts.append(i)
+            for n, g in enumerate(sp.grid):
+                writer.write(held if g == 0 or (g < top and at is None) else frame if g == top else at[g])
+                e = abs(rt.span_error(k, i - k, sp.j + n)[0])
+                err_max, err_sum = max(err_max, e), err_sum + e
+            repeats += len(sp.grid) - len(set(sp.grid))
+            k, held = i, frame
+        # the outputs at or behind the last kept frame: the frame itself when it is the last input, else the run of duplicates the video ends in
+        while writer.frames_written < rt.outputs(seen):
+            writer.write(held)
+    if stats is not None:
+        den = rt.error(0)[1]
+        n = writer.frames_written
+        stats.update(snap_max=err_max / den, snap_mean=err_sum / den / n if n else 0.0, pair_runs=runs, pair_runs_full=pushes * per_push,
+                     duplicates=duplicates, repeats=repeats)
+    return writer.frames_written
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     if not 1 <= args.times_to_interpolate <= 6:
         raise SystemExit('--times_to_interpolate must be 1 .. 6')
+    dedup = None
+    if args.dedup is not None:
+        if args.fps is None:
+            raise SystemExit('--dedup needs --fps: only the frame-rate conversion selects the positions of a push (the input rate times two '
+                             'with --times_to_interpolate 3 is a conversion too)')
+        try:
+            dedup = parse_dedup(args.dedup)
+        except ValueError as e:
+            raise SystemExit(f'--dedup: {e}')
     rate_out = None
     if args.fps is not None:
         try:
@@ -195,9 +292,12 @@ def main(argv=None) -> int:
             cuts, stats = [], {}
             if rate_out is None:
                 n = double_frame_rate(it, reader, fout, args.matrix, args.full_range, args.scene_cut, cuts, args.times_to_interpolate)
-            else:
+            elif dedup is None:
                 n = convert_frame_rate(it, reader, fout, rate_out, args.matrix, args.full_range, args.scene_cut, cuts,
                                        args.times_to_interpolate, stats)
+            else:
+                n = convert_frame_rate_dedup(it, reader, fout, rate_out, dedup, args.matrix, args.full_range, args.scene_cut, cuts,
+                                             args.times_to_interpolate, stats)
             fout.flush()
         finally:
             if fout is not sys.stdout.buffer:
@@ -212,6 +312,9 @@ def main(argv=None) -> int:
         print(f'{num}:{den} -> {rate_out[0]}:{rate_out[1]} frames per second on a grid of 1/{1 << args.times_to_interpolate} input interval: '
               f'snap error max {stats["snap_max"]:.4f} mean {stats["snap_mean"]:.4f} input intervals; {stats["pair_runs"]} pair runs '
               f'against {stats["pair_runs_full"]} of full pushes ({(1 << args.times_to_interpolate) - 1} per interval)', file=sys.stderr)
+    if dedup is not None:
+        print(f'--dedup {dedup[0]}:{dedup[1]}:{dedup[2]}: {stats["duplicates"]} duplicate input frames dropped, {stats["repeats"]} output frames '
+              'repeat the grid position of the one before', file=sys.stderr)
     return n
 
 

@@ -79,7 +79,8 @@ EXPORTED_SYMBOLS = (
     'film_debug_arena', 'film_debug_run_op', 'film_debug_tile_map',
     'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json',
     'film_to_yuv420', 'film_to_yuv', 'film_debug_yuv_cut', 'film_frame_histogram', 'film_stream_cut_info',
-    'film_stream_pair_plan_json', 'film_stream_schedule_json', 'film_stream_select', 'film_stream_select_schedule_json')
+    'film_stream_pair_plan_json', 'film_stream_schedule_json', 'film_stream_select', 'film_stream_select_schedule_json',
+    'film_frame_diff', 'film_stream_dup_info')
 
 _lib = None
 
@@ -162,6 +163,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_stream_select.argtypes = [vp, ctypes.c_uint64]
     lib.film_stream_select_schedule_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_stream_cut_info.argtypes = [vp, i64p, i64p, ctypes.POINTER(ctypes.c_int)]
+    lib.film_frame_diff.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+    lib.film_stream_dup_info.argtypes = [vp, i64p, ctypes.POINTER(ctypes.c_int)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ('film_destroy',):
@@ -210,6 +213,27 @@ def frame_histogram_device(ptr: int, h: int, w: int, hist_ptr: int, pix: str = '
                                              ctypes.c_void_p(stream) if stream else None)
     if rc != 0:
         raise FilmError(rc, 'film_frame_histogram failed')
+
+
+def frame_diff_device(ptr_a: int, ptr_b: int, h: int, w: int, out_ptr: int, pix: str = 'u8', matrix: str = 'bt709', full_range: bool = False,
+                      lo: int = 0, stream: Optional[int] = None) -> None:
+    """film_frame_diff: the 8 x 8 block SAD statistics (include/film_hip.h, "Duplicate frames") of TWO h x w device frames of pixel type `pix`
+    into 12 device uint64 at out_ptr ([3][4]: total, max, over, blocks per plane; overwritten), asynchronous on `stream` of the current device.
+    `over` counts the blocks whose SAD is > lo (0 .. 65535, stored-code units).  The frame pointers follow frame_histogram_device's contract,
+    out_ptr is 8-byte aligned.  Needs no engine."""
+    rc = load_library().film_frame_diff(ctypes.c_void_p(ptr_a), ctypes.c_void_p(ptr_b), int(h), int(w), pix_code(pix, matrix, full_range), int(lo),
+                                        ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None)
+    if rc != 0:
+        raise FilmError(rc, 'film_frame_diff failed')
+
+
+def dedup_options(dedup) -> Tuple[int, int, int]:
+    """open_stream(dedup=...) as the options ("dup_hi", "dup_lo", "dup_frac"): hi, or (hi, lo, frac)."""
+    given = tuple(dedup) if isinstance(dedup, (tuple, list)) else (dedup,)
+    if not 1 <= len(given) <= 3:
+        raise ValueError(f'dedup is hi or (hi, lo, frac), got {dedup!r}')
+    hi, lo, frac = given + (0, 1000)[len(given) - 1:]
+    return int(hi), int(lo), int(frac)
 
 
 def selection_mask(times: int, positions) -> int:
@@ -309,6 +333,15 @@ class FilmStream:
         d, n, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
         self._eng._check(self._eng._lib.film_stream_cut_info(self._eng._h, ctypes.byref(d), ctypes.byref(n), ctypes.byref(c)))
         return d.value, n.value, c.value
+
+    def dup_info(self):
+        """film_stream_dup_info: (stats, dup) of the last push - stats the int64 [3, 4] block statistics (total, max, over, blocks per plane)
+        of the pushed frame against the carried one, or None when no comparison was made; dup 1 if the push was dropped as a duplicate
+        (it returned None / False like a first push and changed nothing)."""
+        stats, c = (ctypes.c_int64 * 12)(), ctypes.c_int(0)
+        self._eng._check(self._eng._lib.film_stream_dup_info(self._eng._h, stats, ctypes.byref(c)))
+        a = np.array(stats[:], np.int64).reshape(3, 4)
+        return (None if (a < 0).all() else a), c.value
 
     def close(self) -> None:
         if self._open and getattr(self._eng, '_h', None) is not None and self._eng._h.value:
@@ -554,7 +587,7 @@ class FilmEngine:
                                                         ctypes.c_void_p(stream) if stream else None))
 
     def open_stream(self, h: int, w: int, align: Optional[int] = None, block_shape=None, pix: str = 'f32', matrix: str = 'bt709',
-                    full_range: bool = False, scene_cut: int = 0, times: int = 1) -> FilmStream:
+                    full_range: bool = False, scene_cut: int = 0, times: int = 1, dedup=None) -> FilmStream:
         """film_stream_open: a frame stream of h x w frames, padded / tiled like interpolate_frames(align, block_shape); pix is a name of
         film_hip/pixfmt.py's table (FilmStream describes the frames; 4:2:0 needs h and w even, 4:2:2 w even), the Y'CbCr ones with the colour
         `matrix` 'bt709' | 'bt601' | 'bt2020nc' and limited or full range.
@@ -562,9 +595,16 @@ class FilmEngine:
         option like block_overlap, so it STAYS set for later streams of this engine until set_option('scene_cut', 0); 0 (default) leaves
         the engine as it is.
         times: 1 .. 6 = the engine option "stream_times" for THIS stream (set, the stream opened, the option set back to what it was): a
-        primed push returns the 2^times - 1 frames of the times_to_interpolate recursion (FilmStream)."""
+        primed push returns the 2^times - 1 frames of the times_to_interpolate recursion (FilmStream).
+        dedup: None (default) leaves the engine as it is; hi, or (hi, lo, frac), sets the engine options "dup_hi", "dup_lo" and "dup_frac"
+        (include/film_hip.h, "Duplicate frames"; hi alone: lo = 0, frac = 1000) before the stream opens - handle options like scene_cut, so
+        they STAY set for later streams of this engine until set_option('dup_hi', -1).  A push judged a duplicate of the carried frame then
+        returns None / False and changes nothing; FilmStream.dup_info() tells it from a first push or a cut."""
         if scene_cut:
             self.set_option('scene_cut', int(scene_cut))
+        if dedup is not None:
+            for key, v in zip(('dup_hi', 'dup_lo', 'dup_frac'), dedup_options(dedup)):
+                self.set_option(key, v)
         times = int(times)
         before = getattr(self, '_stream_times', 1)   # (option "stream_times" as last set through set_option)
         if times == before:

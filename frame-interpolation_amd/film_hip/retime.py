@@ -7,6 +7,11 @@ even index is the shallower, cheaper frame of the recursion).  Interval k = g_j 
 frame k itself, i > 0 is position i of the push of input frame k + 1.  The snap error |g_j / 2^T - u_j| is at most 2^-(T + 1) input
 intervals, and the g_j are strictly increasing as long as the output rate is at most 2^T times the input rate, which is what Retime
 accepts.  Integers only: no rate is ever a float here.
+
+Stretched intervals (Retime.span).  A stream that drops duplicate frames (engine option "dup_hi") keeps the input frames k_0 = 0 < k_1 < ...;
+span m = [k_m, k_(m+1)) is n_m input intervals long and is closed by ONE push, whose 2^T grid is spread over all of it: output j belongs to the
+span iff k_m <= u_j < k_(m+1), and its grid index is g = round((u_j - k_m) 2^T / n_m), ties to even - 0 and 2^T are the two kept frames.  With
+n_m = 1 throughout this writes the frames described above.
 """
 from math import gcd
 from typing import Iterable, Iterator, NamedTuple, Tuple
@@ -58,6 +63,11 @@ class Interval(NamedTuple):
     j: int                        # the index of the first output of this interval (the input frame, or else the first position)
 
 
+class Span(NamedTuple):
+    j: int                        # the index of the first output inside the span (the next span's when `grid` is empty)
+    grid: Tuple[int, ...]         # per output, in order: 0 = the kept frame that opens the span, 2^T = the one that closes it, else a position
+
+
 class Retime:
     """rate_in = (a, b), rate_out = (c, d), times = T: the timing of the conversion on the grid of 2^-T input intervals."""
 
@@ -100,6 +110,31 @@ class Retime:
                 j += 1
             yield Interval(k, write, tuple(pos), j0)
             k += 1
+
+    def span(self, k: int, n: int) -> 'Span':
+        """The outputs of a STRETCHED interval: input frames k and k + n (n >= 1) are kept and the n - 1 between them were dropped as duplicates
+        of frame k.  Output j belongs to the span iff k <= u_j < k + n (compared exactly, as fractions); its grid index spreads the span over
+        the 2^T grid, g = round((u_j - k) 2^T / n), ties to the even index, 0 <= g <= 2^T: g = 0 is frame k verbatim, g = 2^T is frame k + n
+        verbatim, anything else is position g of the push of frame k + n, which closes the span.  A long span may give several outputs one g:
+        the position is selected once and written once per such output.  Returns Span(j, grid): the index of the span's first output and the
+        grid indices of its outputs in order.  n = 1 walks the frames intervals() walks (there an output that rounds UP to an input frame opens
+        the next interval, here it closes its own span with g = 2^T: the same frame; the shift by k 2^T is even, so the ties fall alike)."""
+        if k < 0 or n < 1:
+            raise ValueError(f'a span starts at an input frame k >= 0 and is n >= 1 intervals long, got k = {k!r}, n = {n!r}')
+        j0 = -(-k * self.q // self.p)                     # the first j with j p / q >= k
+        den, grid, j = self.q * n, [], j0
+        while j * self.p < (k + n) * self.q:
+            g, r = divmod((j * self.p - k * self.q) << self.times, den)
+            grid.append(g + (2 * r > den or (2 * r == den and g & 1)))
+            j += 1
+        return Span(j0, tuple(grid))
+
+    def span_error(self, k: int, n: int, j: int) -> Tuple[int, int]:
+        """The snap error k + g n / 2^T - u_j of output j of span(k, n) in INPUT intervals, as (numerator, denominator > 0) with error()'s
+        denominator: the instant the written frame stands for against the instant the output is shown at."""
+        sp = self.span(k, n)
+        g = sp.grid[j - sp.j]
+        return (g * n + (k << self.times)) * self.q - (j * self.p << self.times), self.q << self.times
 
     def outputs(self, frames_in: int) -> int:
         """The frames a video of frames_in input frames converts to: the outputs at or before the last input frame."""

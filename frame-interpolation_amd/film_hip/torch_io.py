@@ -12,7 +12,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import pixfmt
-from .engine import FilmEngine, frame_histogram_device
+from .engine import FilmEngine, frame_diff_device, frame_histogram_device
 
 
 def pinned_frame(shape) -> 'np.ndarray':
@@ -73,6 +73,20 @@ def frame_histogram(frame: torch.Tensor, pix: str = 'u8') -> torch.Tensor:
     return hist.to(torch.int64)      # (counts stay below 2^31: H * W < 2^31)
 
 
+def frame_diff(a: torch.Tensor, b: torch.Tensor, pix: str = 'u8', lo: int = 0) -> torch.Tensor:
+    """film_frame_diff of two CUDA frames of pixel type `pix` (shapes and dtypes as frame_histogram takes them, both alike and on one device)
+    -> int64 [3, 4] on the frames' device: per plane the total, the maximum, the number above `lo` (strictly; 0 .. 65535, stored-code units)
+    and the number of the 8 x 8 block SADs between the two frames, on full-depth codes (include/film_hip.h, "Duplicate frames").
+    Asynchronous on the current torch stream."""
+    assert a.is_cuda and a.dtype in pix_dtypes(pix) and b.device == a.device and b.dtype == a.dtype and b.shape == a.shape
+    a, b = a.contiguous(), b.contiguous()
+    h, w = pixfmt.frame_size(pix, tuple(a.shape))
+    out = torch.empty((3, 4), dtype=torch.int64, device=a.device)   # (the twelve uint64 stay far below 2^63)
+    with torch.cuda.device(a.device):
+        frame_diff_device(a.data_ptr(), b.data_ptr(), h, w, out.data_ptr(), pix, lo=lo, stream=torch.cuda.current_stream(a.device).cuda_stream)
+    return out
+
+
 class DeviceStream:
     """A frame stream on frames that already live in HBM (DeviceInterpolator.stream): push(frame) takes a [H,W,3] CUDA tensor, float32
     or uint8 as opened (a 4:2:0 stream: uint8 [H * 3 // 2, W]; a 10-bit one: int16 or uint16 of that shape), and returns the mid-frame between it and the frame pushed before as a new tensor of the same kind - None for
@@ -81,9 +95,9 @@ class DeviceStream:
     times > 1: a primed push returns the [2^times - 1, *frame shape] frames of the times_to_interpolate recursion (FilmStream)."""
 
     def __init__(self, engine: FilmEngine, h: int, w: int, align, block_shape, pix: str, matrix: str = 'bt709', full_range: bool = False,
-                 scene_cut: int = 0, times: int = 1):
+                 scene_cut: int = 0, times: int = 1, dedup=None):
         self._stream = engine.open_stream(h, w, align=align, block_shape=block_shape, pix=pix, matrix=matrix, full_range=full_range,
-                                          scene_cut=scene_cut, times=times)
+                                          scene_cut=scene_cut, times=times, dedup=dedup)
         self._dtypes = pix_dtypes(pix)
 
     def push(self, frame: torch.Tensor) -> Optional[torch.Tensor]:
@@ -108,6 +122,11 @@ class DeviceStream:
     def cut_info(self):
         """FilmStream.cut_info: (distance, samples, cut) of the last push (engine option "scene_cut")."""
         return self._stream.cut_info()
+
+    def dup_info(self):
+        """FilmStream.dup_info: (stats [3, 4] or None, dup) of the last push (engine option "dup_hi"): a push dropped as a duplicate of the
+        carried frame returned None and changed nothing."""
+        return self._stream.dup_info()
 
     def close(self) -> None:
         self._stream.close()
@@ -168,7 +187,7 @@ class DeviceInterpolator:
         return out
 
     def stream(self, h: int, w: int, pix: str = 'f32', matrix: str = 'bt709', full_range: bool = False, scene_cut: int = 0,
-               times: int = 1) -> DeviceStream:
+               times: int = 1, dedup=None) -> DeviceStream:
         """Extension: a frame stream of h x w frames (film_stream_*), padded / tiled like batch(): push one CUDA tensor at a time, float32
         or ('u8') uint8, and get the mid-frame with the frame before - bit-identical to batch(previous, frame), one extraction per frame.
         A Y'CbCr pix (film_hip/pixfmt.py; FilmStream describes the frames): tensors of the frame's shape, converted inside the cut and the
@@ -176,10 +195,12 @@ class DeviceInterpolator:
         torch has it; the mid-frame comes back in the dtype that was pushed.
         matrix: 'bt709' | 'bt601' | 'bt2020nc', for every Y'CbCr layout.
         scene_cut (0 .. 1000 permille): non-zero sets the ENGINE option "scene_cut" before the stream opens, and it stays set (like block_overlap).
-        times (1 .. 6): the stream's "stream_times" - a primed push returns [2^times - 1, ...] frames, the times_to_interpolate recursion."""
+        times (1 .. 6): the stream's "stream_times" - a primed push returns [2^times - 1, ...] frames, the times_to_interpolate recursion.
+        dedup (None | hi | (hi, lo, frac)): not None sets the ENGINE options "dup_hi" / "dup_lo" / "dup_frac" before the stream opens, and they stay
+        set (like scene_cut): a push judged a duplicate of the carried frame returns None and changes nothing (DeviceStream.dup_info)."""
         bs = self._block_shape
         return DeviceStream(self._engine, h, w, self._align, bs if bs is not None and bs[0] * bs[1] > 1 else None, pix, matrix, full_range,
-                            scene_cut, times)
+                            scene_cut, times, dedup)
 
     def __call__(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         if self._block_shape is not None and self._block_shape[0] * self._block_shape[1] > 1:

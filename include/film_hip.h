@@ -177,6 +177,8 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                      the one before, or -1 when no comparison was made (the option is 0, the first frame, the push after a reset or after a
  *                      failed push, the first push after the option was turned on); *samples = S of one frame; *cut = 1 when the push
  *                      was treated as a scene cut, else 0.  NULL outputs are skipped.
+ *   film_stream_dup_info  what the last push found with option "dup_hi" (below, "Duplicate frames"): the block statistics of the pushed frame
+ *                      against the carried one, and whether the push was dropped as a duplicate (it then set *produced = 0 and changed nothing).
  *   film_stream_close  frees the stream's buffers (film_destroy closes an open stream too).
  * push / reset / close without an open stream: FILM_ERR_STATE.
  *   film_stream_plan_json  the stream plan of `tiles` (padded) H x W tiles in orientation `slot` (0 / 1: the half of the frame buffers
@@ -331,9 +333,41 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *     allocation of whole 32-bit words (as for the 8-bit cuts: the last partial word is read, only the frame's bytes are counted; a 10-bit frame is
  *     whole words).
  *     FILM_ERR_INVALID: a NULL pointer, H or W < 1, H * W >= 2^31, a pix the stream entry points refuse (odd sizes with 4:2:0 included),
- *     a frame_dev that is not 4-byte aligned. */
+ *     a frame_dev that is not 4-byte aligned.
+ * Duplicate frames.  Film in a 30p or 60p container, animation drawn on twos and threes, screen captures and anything converted from a variable
+ * to a constant frame rate repeat frames; interpolating between two copies of one picture costs a full push and keeps the stutter.  The histogram
+ * above cannot see a repeat (its distance is 0 for pure motion too).  The engine offers an exact, spatially aware statistic of two frames, an
+ * integer decision rule, and a stream that ignores a push judged a duplicate (options "dup_hi", "dup_lo", "dup_frac").  Integers only.
+ *   Planes and codes.  Two frames a, b of one `pix`, H and W.  The planes and their sizes are those of the histogram: plane 0 is H x W, planes 1
+ *     and 2 are (H >> sy) x (W >> sx) for Y'CbCr - (sx, sy) = (1, 1) for 4:2:0, (1, 0) for 4:2:2, (0, 0) for 4:4:4 - and H x W for the RGB types; the
+ *     Cb and Cr planes of FILM_PIX_NV12 / P010 are the de-interleaved samples.  The code of a sample is taken at FULL depth: the stored byte (8-bit
+ *     layouts); w & 1023 (FILM_PIX_I010 / I210 / I410); w >> 6 (FILM_PIX_P010); the byte frame[y][x][c] (FILM_PIX_U8); the byte film_to_uint8
+ *     stores for frame[y][x][c], by the float32 operations of the FILM_PIX_F32 histogram (FILM_PIX_F32).
+ *   Blocks.  Block (i, j) of a plane of Hp x Wp samples holds rows 8 i .. min(8 i + 8, Hp) - 1 and columns 8 j .. min(8 j + 8, Wp) - 1: the grid is
+ *     anchored on the plane, partial blocks at the right and bottom edge count as they are, blocks_p = ceil(Hp / 8) * ceil(Wp / 8).  The SAD of a
+ *     block is s = sum |a - b| over its samples, at most 64 * 1023 = 65472.
+ *   Result: uint64_t out[3][4], out[p] = {total, max, over, blocks} of plane p: total = the sum of s over its blocks (past 2^32 at 4K, hence 64
+ *     bits), max = the largest s, over = the number of blocks with s > lo (strictly; `lo` is a call argument in stored-code units), blocks = blocks_p.
+ *   Rule: with "dup_hi" = h >= 0, "dup_lo" = l and "dup_frac" = f, and m = 1 for the 8-bit, U8 and F32 types and m = 4 for the 10-bit layouts (a
+ *     value then means the same on the 8- and 10-bit versions of one video, as code >> 2 does for the histogram), frame b is a duplicate of
+ *     frame a iff for EVERY plane p: max_p <= h * m and 1000 * over_p <= f * blocks_p, with over counted at lo = l * m; all in 64-bit integers.
+ *     h = 0 with the other defaults (l = 0, f = 1000) means exact duplicates only.
+ *   NO values are recommended: hit and miss rates on real footage are UNMEASURED, as for "scene_cut" - choose them on your own material.  (The
+ *   defaults of ffmpeg's mpdecimate filter, hi = 768, lo = 320, frac = 0.33, are that filter's own, for a different block definition; they are
+ *   named here for orientation and not endorsed.)
+ *   film_frame_diff: the statistic of TWO H x W frames of pixel type `pix` on DEVICE pointers, without a handle, asynchronous on `stream`
+ *     (NULL: the default stream) of the current device, like film_frame_histogram.  out_dev receives the 12 uint64_t; the call overwrites them -
+ *     it never accumulates.  Alignment and allocation contract of a_dev and b_dev: film_frame_histogram's.  The colour flags are validated and
+ *     otherwise ignored: the statistic is about the stored codes.
+ *     FILM_ERR_INVALID: what film_frame_histogram refuses (a NULL pointer, H or W < 1, H * W >= 2^31, a pix the stream entry points refuse, a frame
+ *     pointer that is not 4-byte aligned), lo outside 0 .. 65535, an out_dev that is not 8-byte aligned.
+ *   film_stream_dup_info: what the last push found with option "dup_hi" >= 0: stats[12] = the out[3][4] of its comparison, or twelve -1 when
+ *     none was made (the option is -1, the first frame, the push after a reset or a failed push); *dup = 1 when the push was dropped as a
+ *     duplicate, else 0.  NULL outputs are skipped.  FILM_ERR_STATE: no open stream. */
 int film_frame_histogram(const void* frame_dev, int H, int W, int pix, uint32_t* hist_dev, void* stream);
 int film_stream_cut_info(film_t* h, int64_t* distance, int64_t* samples, int* cut);
+int film_frame_diff(const void* a_dev, const void* b_dev, int H, int W, int pix, int lo, uint64_t* out_dev, void* stream);
+int film_stream_dup_info(film_t* h, int64_t stats[12], int* dup);
 int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_w, int pix);
 int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int mem_kind, void* stream);
 int film_stream_reset(film_t* h);
@@ -453,7 +487,22 @@ int film_stream_select_schedule_json(film_t* h, int times, int slot, uint64_t ma
  *                  (no flow estimator, no fusion) - and the next push interpolates inside the new scene.  No comparison is made on the
  *                  first frame, after film_stream_reset, after a failed push, and on the first push after the option was turned on.
  *                  film_stream_cut_info reports what the last push found.  No threshold is recommended: see "Scene cuts".  Does not
- *                  drop the cached plans. */
+ *                  drop the cached plans.
+ *   "dup_hi" h / "dup_lo" l / "dup_frac" f  (extension; h: -1 .. 16320, default -1 = off, today's pushes: the frame is copied straight into the
+ *                  stream's copy and no launch, copy, allocation or wait is added; l: 0 .. 16320, default 0; f: 0 .. 1000 permille, default
+ *                  1000)  read at every film_stream_push.  h >= 0: the pushed frame is uploaded or copied into a SECOND keep buffer of the
+ *                  stream (allocated by the first such push).  On a primed stream film_frame_diff's kernel compares it there with the carried
+ *                  frame's copy, the 96 bytes are downloaded and WAITED for - so also a device-resident push blocks the calling thread - and
+ *                  the rule of "Duplicate frames" above decides.  Duplicate: the push ends there with *produced = 0; `mid` is untouched and
+ *                  the stream is exactly as before the call - primed state, slot, carried frame and its copy, carried histogram, selection and
+ *                  plan; no cut, extraction or pair run is queued, no histogram is taken, and film_stream_cut_info reports that no comparison
+ *                  was made (-1, cut 0).  Not a duplicate: the two keep buffers swap roles and the push goes on as always, the "scene_cut"
+ *                  histogram of the new frame included: duplicates are decided first and never count as cuts.  The carried frame of a run
+ *                  of near-duplicates is the FIRST of the run and every later frame is compared with it, the last kept one, so slow drift
+ *                  is eventually seen.  No comparison is made on an unprimed push (the first, after film_stream_reset, after a failed push).
+ *                  The argument checks of a push come first, a NULL `mid` on a primed push included; a failure behind them unprimes the
+ *                  stream as always.  film_stream_dup_info reports what the last push found.  No values are recommended: see "Duplicate
+ *                  frames".  None of the three drops the cached plans. */
 int film_set_option(film_t* h, const char* key, int64_t value);
 
 /* The tile geometry film_interpolate / film_interpolate_sequence use for H x W frames with these arguments and the handle's current

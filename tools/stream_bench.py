@@ -29,6 +29,12 @@ and host pushes, the milliseconds PER GENERATED FRAME of a steady push of a stre
 this tree's times = 1 push, beside film_hip.recursive.interpolate_pair_recursively on the same pair (float32, device-resident: 2^T - 1 pair
 calls, every fed-back frame extracted twice) and - with --baseline-root - beside the baseline's times = 1 push; the frames of the f32 push are
 compared bit for bit with that recursion in the worker.  It also lists the stream plan's workspace for T = 1, 2, 3 and 6.
+--dedup is a run of its own about duplicate frames (engine options "dup_hi" / "dup_lo" / "dup_frac"): at 1080p 2x2, for `u8`, `i420` and `i010`,
+device-resident and host pushes, (a) this tree's push with dup_hi = -1 beside - with --baseline-root - the baseline's push, whose code path it is;
+(b) `*_dd0` - the steady push with dup_hi = 0 on the bench frames, which are never duplicates (rolled copies of one picture), against -1 in the
+same process: the price of the copy, the kernel, the 96-byte download and the wait; (c) `*_dup` - a push that IS a duplicate (the carried frame
+again); (d) `<layout> <size> <data>` - frame_diff_kernel alone (film_frame_diff, hip events around 50 calls, microseconds per call) at 1080p and
+4K on two random frames and on a frame against itself, beside the bytes of both frames over the measured HBM copy rate (6.29 TB/s).
 Every measurement: untimed warm-up calls (plan build, autotune, first launches), then --reps timed windows of `n` calls, each
 ended by a device synchronise; the window's ms per call is one sample.  Each tree keeps its autotune choices in a file of its own
 under --scratch, so that the rounds of a tree run the same tiles.  The report gives mean and range over all samples of a
@@ -451,10 +457,180 @@ def histogram_alone(calls=50, reps=3):
     return out
 
 
-def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False, times=None, select=None):
+DEDUP_PIX = ('u8', 'i420', 'i010')
+
+
+def dedup_worker(root, reps):
+    """--dedup: the rows about option "dup_hi" at the first point (see the module text); prints one JSON line."""
+    for p in (root, os.path.join(root, 'frame-interpolation_amd')):
+        sys.path.insert(0, p)
+    import numpy as np
+    import torch
+    from film_hip import weights as W
+    from film_hip.engine import FilmEngine, PIX, frame_shape
+    from film_hip.options import PUBLISHED
+    from film_hip.torch_io import DeviceInterpolator
+    eng = FilmEngine(PUBLISHED, device=0)
+    eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
+    name, h, w, align, block, n, _ = POINTS[0]
+    res = {}
+    out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0), 'points': {name: res}}
+
+    def timed(call, n, warm=3):
+        for _ in range(warm):
+            call()
+        torch.cuda.synchronize()
+        samples = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                call()
+            torch.cuda.synchronize()
+            samples.append((time.perf_counter() - t0) * 1e3 / n)
+        return [round(s, 4) for s in samples]
+
+    it = DeviceInterpolator(eng, align=align, block_shape=list(block))
+    fr = _frames(4, h, w)
+    x = [torch.from_numpy(f).cuda() for f in fr]
+    dev = {'u8': [torch.from_numpy((f * 255 + 0.5).astype(np.uint8)).cuda() for f in fr]}
+    for pix in ('i420', 'i010'):
+        dev[pix] = [torch.empty(frame_shape(pix, h, w), dtype=torch.int16 if PIX[pix][1] is np.uint16 else torch.uint8, device='cuda') for _ in x]
+        for src, dst in zip(x, dev[pix]):
+            eng.to_yuv_device(src.data_ptr(), dst.data_ptr(), h, w, pix)
+    torch.cuda.synchronize()
+    del x
+    state = {'i': 0}
+
+    def nxt(m):
+        state['i'] = (state['i'] + 1) % m
+        return state['i']
+
+    hn = max(5, n // 3)
+    try:
+        for pix in DEDUP_PIX:
+            d = dev[pix]
+            host = [t.cpu().numpy().view(np.uint16 if t.dtype == torch.int16 else np.uint8) for t in d]
+            for dedup, suf in ((None, ''), (0, '_dd0')):      # "dup_hi" = -1, then 0 on frames that are never duplicates (rolled copies)
+                eng.set_option('dup_hi', -1)
+                with it.stream(h, w, pix, dedup=dedup) as st:
+                    st.push(d[0])
+                    res[f'push_{pix}{suf}'] = timed(lambda: st.push(d[nxt(4)]), n)
+                    assert st.dup_info() == (None, 0) if dedup is None else (st.dup_info()[0] is not None and st.dup_info()[1] == 0), (pix, st.dup_info())
+                with eng.open_stream(h, w, align=align, block_shape=block, pix=pix) as st:      # (the option stays set)
+                    st.push(host[0])
+                    res[f'host_push_{pix}{suf}'] = timed(lambda: st.push(host[nxt(4)]), hn, warm=2)
+            with it.stream(h, w, pix, dedup=0) as st:          # a push that IS a duplicate: the carried frame again
+                st.push(d[0])
+                res[f'push_{pix}_dup'] = timed(lambda: st.push(d[0]), n)
+                assert st.dup_info()[1] == 1, (pix, st.dup_info())
+            with eng.open_stream(h, w, align=align, block_shape=block, pix=pix) as st:
+                st.push(host[0])
+                res[f'host_push_{pix}_dup'] = timed(lambda: st.push(host[0]), hn, warm=2)
+                assert st.dup_info()[1] == 1, (pix, st.dup_info())
+    finally:
+        eng.set_option('dup_hi', -1)
+    del dev
+    torch.cuda.empty_cache()
+    out['diff_us'] = diff_alone()
+    eng.save_tune_cache()
+    eng.close()
+    print('STREAM_BENCH ' + json.dumps(out), flush=True)
+
+
+def diff_alone(calls=50, reps=3):
+    """frame_diff_kernel alone: {"<layout> <size> <data>": [microseconds per call, ..., bytes of both frames]} from hip events around `calls` calls
+    of film_frame_diff (memset + kernel), on two random frames and on a frame against itself."""
+    import numpy as np
+    import torch
+    from film_hip.engine import PIX, frame_diff_device, frame_shape
+    from film_hip.torch_io import frame_diff
+    out = {}
+    stats = torch.empty(12, dtype=torch.int64, device='cuda')
+    for size, (h, w) in (('1080p', (1080, 1920)), ('4K', (2160, 3840))):
+        for pix in ('u8', 'i420', 'nv12', 'i010', 'p010', 'f32'):
+            shape = frame_shape(pix, h, w)
+
+            def rand():
+                if pix == 'f32':
+                    return torch.rand(shape, device='cuda')
+                if PIX[pix][1] is np.uint16:
+                    return torch.randint(-32768, 32768, shape, dtype=torch.int32, device='cuda').to(torch.int16)      # (every bit of the word)
+                return torch.randint(0, 256, shape, dtype=torch.uint8, device='cuda')
+            a = rand()
+            for data, b in (('random', rand()), ('identical', a.clone())):
+                blocks = frame_diff(a, b, pix)[:, 3]
+                assert (frame_diff(a, b, pix)[:, 0] == 0).all() == (data == 'identical') and int(blocks[0]) == -(-h // 8) * -(-w // 8)
+                s = torch.cuda.current_stream().cuda_stream
+                samples = []
+                for _ in range(reps + 1):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(calls):
+                        frame_diff_device(a.data_ptr(), b.data_ptr(), h, w, stats.data_ptr(), pix, stream=s)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    samples.append(round(e0.elapsed_time(e1) * 1e3 / calls, 2))
+                out[f'{pix} {size} {data}'] = samples[1:] + [2 * a.numel() * a.element_size()]      # (the first window warms up; last entry: the bytes of both frames)
+    return out
+
+
+def dedup_main(args):
+    """--dedup: rounds of (the baseline's plain pushes,) this tree's rows; (a) - (d) of the module text."""
+    os.makedirs(args.scratch, exist_ok=True)
+    name = POINTS[0][0]
+    plain_rows = [f'{pre}push_{pix}' for pre in ('', 'host_') for pix in DEDUP_PIX]
+    base, this = [], []
+    for r in range(args.rounds):
+        if args.baseline_root:
+            base.append(_run_worker(os.path.abspath(args.baseline_root), args.reps, False, os.path.join(args.scratch, 'stream_bench_tune_baseline.txt'),
+                                    plain_rows, [name]))
+            print(f'# round {r + 1}/{args.rounds} baseline: done', flush=True)
+        this.append(_run_worker(HERE, args.reps, False, os.path.join(args.scratch, 'stream_bench_tune_this.txt'), dedup=True))
+        print(f'# round {r + 1}/{args.rounds} this: done', flush=True)
+    pts = [r['points'][name] for r in this]
+    bpts = [r['points'][name] for r in base]
+    lines = [f'# tools/stream_bench.py --dedup  this = {this[0]["version"]}' + (f'  baseline = {base[0]["version"]}' if base else '') +
+             f'  {this[0]["device"]}  rounds={args.rounds} reps={args.reps}',
+             '# ms per push, device-resident unless "host": mean [min .. max] over rounds x reps windows.  "" = dup_hi -1, _dd0 = dup_hi 0 on frames that are',
+             '# never duplicates, _dup = a push that is a duplicate',
+             f'{name}:']
+    for key in plain_rows:
+        if bpts:
+            lines.append(f'  {"baseline " + key:<26} {_stat([s for p in bpts for s in p[key]])}')
+    for key in plain_rows:
+        for suf in ('', '_dd0', '_dup'):
+            lines.append(f'  {key + suf:<26} {_stat([s for p in pts for s in p[key + suf]])}')
+    for key in plain_rows:
+        if bpts:      # (a)
+            bm = [statistics.mean(p[key]) for p in bpts]
+            d = [statistics.mean(p[key]) - b for p, b in zip(pts, bm)]
+            lines.append(f'  (a) {key + " - baseline " + key:<40} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms'
+                         f'   (baseline round means {" ".join(f"{b:.3f}" for b in bm)}, spread {max(bm) - min(bm):.3f} ms; '
+                         f'all windows {max(s for p in bpts for s in p[key]) - min(s for p in bpts for s in p[key]):.3f} ms)')
+    for key in plain_rows:      # (b)
+        d = [statistics.mean(p[key + '_dd0']) - statistics.mean(p[key]) for p in pts]
+        allw = [s for p in pts for s in p[key]]
+        lines.append(f'  (b) {key + "_dd0 - " + key:<40} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms'
+                     f'   (spread of {key} over all windows of this tree: {max(allw) - min(allw):.3f} ms)')
+    for key in plain_rows:      # (c)
+        lines.append(f'  (c) {key + "_dup":<40} {_stat([s for p in pts for s in p[key + "_dup"]])} ms')
+    lines.append('(d) frame_diff_kernel alone (memset + kernel per call), microseconds per call: mean [min .. max]; the bytes of both frames / 6.29 TB/s beside it')
+    for key in this[0]['diff_us']:
+        v = [s for r in this for s in r['diff_us'][key][:-1]]
+        nbytes = this[0]['diff_us'][key][-1]
+        lines.append(f'  {key:<24} {_stat(v)} us   {nbytes / 1e6:7.2f} MB   {nbytes / 6.29e12 * 1e6:6.2f} us at the HBM rate')
+    lines.append('# raw: ' + json.dumps({'baseline': base, 'this': this}))
+    print('\n'.join(lines), flush=True)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False, times=None, select=None, dedup=False):
     env = dict(os.environ, FILM_TUNE_CACHE=tune_file)
     cmd = [sys.executable, os.path.abspath(__file__), '--worker', root, '--reps', str(reps)] + (['--quick'] if quick else [])
     cmd += (['--rows', ','.join(rows)] if rows else []) + (['--points', ','.join(points)] if points else []) + (['--scene_cut'] if scene_cut else [])
+    cmd += ['--dedup'] if dedup else []
     cmd += ['--times', ','.join(str(t) for t in times)] if times else []
     cmd += ['--select', select] if select else []
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)   # (a hung worker ends the run: nothing is started behind it)
@@ -525,6 +701,7 @@ def main(argv=None):
     ap.add_argument('--select', default=None, metavar='"3,6/2,5"',
                     help='with --times T (one value): the selected-push report instead - the selections (1-based positions, comma-separated; '
                          '"/" between selections) are taken in turn, push after push (FilmStream.select), beside the full push of this tree and of the baseline')
+    ap.add_argument('--dedup', action='store_true', help='the report about option "dup_hi" and its block-SAD kernel alone instead (see above)')
     ap.add_argument('--worker', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     rows = args.rows.split(',') if args.rows else None
@@ -537,6 +714,8 @@ def main(argv=None):
         if args.worker:
             return select_worker(args.worker, args.reps, times[0], selections)
         return select_main(args, times[0], selections)
+    if args.dedup:
+        return dedup_worker(args.worker, args.reps) if args.worker else dedup_main(args)
     if times and args.worker:
         return times_worker(args.worker, args.reps, times)
     if times:
