@@ -83,101 +83,6 @@ def stream_pix(reader) -> str:
     return getattr(reader, 'pix', None) or y4m.PIX_NAME.get(('420', getattr(reader, 'depth', 8)), 'i420')
 
 
-def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', full_range: Optional[bool] = None, scene_cut: int = 0,
-                      cuts: Optional[list] = None, times: int = 1) -> int:
-    """Streams reader's frames through a stream of the reader's layout (stream_pix: I420, I010 for a 10-bit reader, I422 ... I410) of `it` (an eval.interpolator.Interpolator) and writes the doubled video to the
-    binary file object `out`.  Returns the number of frames written.  One input frame and one mid-frame are alive at a time (two input
-    frames with scene_cut).  scene_cut > 0 (permille, engine option "scene_cut"): a push after the first that returns no mid-frame is
-    a scene cut - the previous input frame is written again in the mid-frame's place; `cuts` (a list) receives the index of every input
-    frame that starts a new scene.
-    times = T > 1: the frame rate times 2^T - a push returns the 2^T - 1 frames between two input frames (a stream opened with times=T),
-    and the hold across a cut writes the previous frame that many times."""
-    times = int(times)
-    if not 1 <= times <= 6:
-        raise ValueError(f'times_to_interpolate must be 1 .. 6, got {times}')
-    full = reader.full_range if full_range is None else bool(full_range)
-    writer = y4m.Y4MWriter(out, y4m.multiply_rate(reader.tokens, 1 << times))
-    with it.open_stream(reader.height, reader.width, pix=stream_pix(reader), matrix=matrix, full_range=full,
-                        **({'scene_cut': int(scene_cut)} if scene_cut else {}), **({'times': times} if times != 1 else {})) as st:
-        prev = None
-        for i, frame in enumerate(reader):
-            mid = st.push(frame)
-            if mid is not None:
-                for m in (mid,) if times == 1 else mid:
-                    writer.write(m)
-            elif scene_cut and prev is not None:
-                for _ in range((1 << times) - 1):
-                    writer.write(prev)      # a frame hold across the cut
-                if cuts is not None:
-                    cuts.append(i)
-            writer.write(frame)
-            prev = frame if scene_cut else None
-    return writer.frames_written
-
-
-def convert_frame_rate(it, reader: y4m.Y4MReader, out, rate_out, matrix: str = 'bt709', full_range: Optional[bool] = None,
-                       scene_cut: int = 0, cuts: Optional[list] = None, times: int = 1, stats: Optional[dict] = None) -> int:
-    """--fps: streams reader's frames through a stream of `it` opened as double_frame_rate opens it and writes the video at rate_out =
-    (num, den) to `out`; returns the number of frames written.  film_hip.retime snaps every output instant to the grid of 2^-times input
-    intervals: an output that lands on an input frame is that frame verbatim (an input frame no output lands on is not written), every
-    other one is a position of the push of the next input frame, and each push selects just its positions (FilmStream.select), so only
-    they and their ancestors in the recursion are computed.  A scene cut (scene_cut > 0) holds the previous input frame once per position
-    selected for that interval.  rate_out = the input rate times 2^times writes what double_frame_rate(times=times) writes.
-    stats (a dict) receives 'snap_max' and 'snap_mean' (the snap error of the written frames, in input intervals), 'pair_runs' (made)
-    and 'pair_runs_full' (what full pushes would have made).  ValueError: no F token in the header, or what retime.Retime refuses."""
-    times = int(times)
-    if reader.rate is None:
-        raise ValueError('--fps needs the frame rate of the input: its header has no F token')
-    rt = retime.Retime(reader.rate, rate_out, times)
-    per_push = (1 << times) - 1
-    dyadic = rt.p << times == rt.q         # (the header of --times_to_interpolate, which multiplies the numerator as it stands)
-    full = reader.full_range if full_range is None else bool(full_range)
-    writer = y4m.Y4MWriter(out, y4m.multiply_rate(reader.tokens, 1 << times) if dyadic else y4m.set_rate(reader.tokens, rate_out))
-    err_max = err_sum = runs = pushes = 0
-
-    def snapped(j0: int, count: int):
-        nonlocal err_max, err_sum
-        for j in range(j0, j0 + count):
-            e = abs(rt.error(j)[0])
-            err_max, err_sum = max(err_max, e), err_sum + e
-
-    with it.open_stream(reader.height, reader.width, pix=stream_pix(reader), matrix=matrix, full_range=full,
-                        **({'scene_cut': int(scene_cut)} if scene_cut else {}), **({'times': times} if times != 1 else {})) as st:
-        prev = None
-        selected = pending = tuple(range(1, per_push + 1))
-        intervals = rt.intervals()
-        for i, frame in enumerate(reader):
-            if i:
-                if pending != selected:
-                    st.select(pending)
-                    selected = pending
-                mid = st.push(frame)
-                pushes += 1
-                if mid is not None:
-                    for m in (mid,) if times == 1 else mid:
-                        writer.write(m)
-                    runs += retime.push_cost(times, pending)[0]
-                elif scene_cut and (pending or st.cut_info()[2]):
-                    for _ in pending:
-                        writer.write(prev)      # a frame hold across the cut
-                    if cuts is not None:
-                        cuts.append(i)
-                snapped(iv.j + iv.write, len(pending))
-            else:
-                st.push(frame)
-            iv = next(intervals)                # (interval i: is input frame i written, and what the NEXT push selects)
-            if iv.write:
-                writer.write(frame)
-                snapped(iv.j, 1)
-            pending = iv.positions
-            prev = frame if scene_cut else None
-    if stats is not None:
-        den = rt.error(0)[1]
-        n = writer.frames_written
-        stats.update(snap_max=err_max / den, snap_mean=err_sum / den / n if n else 0.0, pair_runs=runs, pair_runs_full=pushes * per_push)
-    return writer.frames_written
-
-
 def parse_dedup(text: str):
     """'HI', 'HI:LO' or 'HI:LO:FRAC' -> (hi, lo, frac) for open_stream(dedup=...); lo defaults to 0, frac to 1000.  ValueError otherwise."""
     parts = str(text).strip().split(':')
@@ -189,30 +94,47 @@ def parse_dedup(text: str):
     return hi, lo, frac
 
 
-def convert_frame_rate_dedup(it, reader: y4m.Y4MReader, out, rate_out, dedup, matrix: str = 'bt709', full_range: Optional[bool] = None,
-                             scene_cut: int = 0, cuts: Optional[list] = None, times: int = 1, stats: Optional[dict] = None) -> int:
-    """--fps with --dedup: convert_frame_rate on a stream opened with dedup = (hi, lo, frac) (engine options "dup_hi" / "dup_lo" / "dup_frac":
-    a pushed frame judged a duplicate of the last KEPT frame is dropped by the stream).  The kept frames k_0 = 0 < k_1 < ... cut the video into
-    spans; retime.Retime.span spreads the outputs of a span over the grid of the ONE push that closes it, so a repeated frame no longer
-    stutters: A A A B at three outputs per input becomes A, 1/9, 2/9 ... of the way to B instead of A A' A'' B.  Before input frame i is
-    pushed, with k the last kept frame, the positions of span(k, i - k) are selected - what the push needs if it closes the span; a
-    duplicate runs nothing and the next frame tries again with a longer span.  A closed span is written in order: g = 0 the held frame k,
-    0 < g < 2^T the push's results, g = 2^T the pushed frame; a scene cut on the closing frame holds frame k in place of the results.  A run
-    of duplicates the video ends in is written as the last kept frame.  The frame count and the header are convert_frame_rate's, and a video
-    without duplicates is written byte for byte as by it.  One kept frame is held until its span closes.
-    stats gains 'duplicates' (pushes dropped) and 'repeats' (outputs that shared a grid index with the one before)."""
+def retime_video(it, reader: y4m.Y4MReader, out, rate_out=None, dedup=None, matrix: str = 'bt709', full_range: Optional[bool] = None,
+                 scene_cut: int = 0, cuts: Optional[list] = None, times: int = 1, stats: Optional[dict] = None) -> int:
+    """The one frame loop of the command.  Streams reader's frames through a stream of the reader's layout (stream_pix: I420, I010 for a
+    10-bit reader, I422 ... I410) of `it` (an eval.interpolator.Interpolator), opened with times = T, and writes the video at rate_out =
+    (num, den) to the binary file object `out`; returns the number of frames written.  rate_out None: 2^T times the input rate, whatever
+    that is (--times_to_interpolate alone: the header needs no F token).  film_hip.retime snaps every output instant to the grid of 2^-T
+    input intervals.  The KEPT input frames k_0 = 0 < k_1 < ... (all of them, unless the stream drops duplicates) cut the video into spans,
+    and retime.Retime.span spreads the outputs of a span over the grid of the ONE push that closes it.  Before input frame i is pushed, with
+    k the last kept frame, the positions of span(k, i - k) are selected (FilmStream.select, only where they differ from the selection in
+    force: a rate of 2^T times the input's never selects) - what the push needs if it closes the span, so only they and their ancestors in
+    the recursion are computed.  A closed span is written in order: g = 0 the held frame k, 0 < g < 2^T the push's results, g = 2^T the
+    pushed frame; an input frame no output lands on is not written.  What lies at or behind the last kept frame is written as that frame.
+    One kept frame is held until its span closes, so input frame k is written when the push of the next kept frame has returned.
+    scene_cut > 0 (permille, engine option "scene_cut"): a push after the first that returns no frames is a scene cut - frame k is written
+    again in place of every result (a frame hold); `cuts` (a list) receives the index of every input frame that starts a new scene.
+    dedup = (hi, lo, frac) (engine options "dup_hi" / "dup_lo" / "dup_frac"): a pushed frame the stream judges a duplicate of the last kept
+    frame is dropped - it runs nothing, and the next frame tries again with a longer span, so a repeated frame no longer stutters: A A A B
+    at three outputs per input becomes A, 1/9, 2/9 ... of the way to B instead of A A' A'' B.  The frame count and the header are those
+    without dedup, and a video without duplicates is written byte for byte as without it.
+    stats (a dict) receives 'snap_max' and 'snap_mean' (the snap error of the written frames, in input intervals), 'pair_runs' (made) and
+    'pair_runs_full' (what full pushes would have made); with dedup also 'duplicates' (pushes dropped) and 'repeats' (outputs that shared
+    a grid index with the one before).  ValueError: times outside 1 .. 6; with rate_out, no F token in the header or what retime.Retime
+    refuses."""
     times = int(times)
-    if reader.rate is None:
+    if rate_out is None:
+        if not 1 <= times <= 6:
+            raise ValueError(f'times_to_interpolate must be 1 .. 6, got {times}')
+        rt = retime.Retime((1, 1), (1 << times, 1), times)
+    elif reader.rate is None:
         raise ValueError('--fps needs the frame rate of the input: its header has no F token')
-    rt = retime.Retime(reader.rate, rate_out, times)
+    else:
+        rt = retime.Retime(reader.rate, rate_out, times)
     per_push, top = (1 << times) - 1, 1 << times
-    dyadic = rt.p << times == rt.q
+    dyadic = rt.p << times == rt.q         # (the header of --times_to_interpolate, which multiplies the numerator as it stands)
     full = reader.full_range if full_range is None else bool(full_range)
-    writer = y4m.Y4MWriter(out, y4m.multiply_rate(reader.tokens, 1 << times) if dyadic else y4m.set_rate(reader.tokens, rate_out))
+    writer = y4m.Y4MWriter(out, y4m.multiply_rate(reader.tokens, top) if dyadic else y4m.set_rate(reader.tokens, rate_out))
     err_max = err_sum = runs = pushes = duplicates = repeats = 0
-    with it.open_stream(reader.height, reader.width, pix=stream_pix(reader), matrix=matrix, full_range=full, dedup=tuple(dedup),
-                        **({'scene_cut': int(scene_cut)} if scene_cut else {}), **({'times': times} if times != 1 else {})) as st:
-        selected = tuple(range(1, per_push + 1))
+    with it.open_stream(reader.height, reader.width, pix=stream_pix(reader), matrix=matrix, full_range=full,
+                        **({'dedup': tuple(dedup)} if dedup is not None else {}), **({'scene_cut': int(scene_cut)} if scene_cut else {}),
+                        **({'times': times} if times != 1 else {})) as st:
+        selected = tuple(range(1, top))
         k, held, seen = 0, None, 0
         for i, frame in enumerate(reader):
             seen = i + 1
@@ -227,7 +149,7 @@ def convert_frame_rate_dedup(it, reader: y4m.Y4MReader, out, rate_out, dedup, ma
                 selected = pos
             mid = st.push(frame)
             pushes += 1
-            if st.dup_info()[1]:
+            if dedup is not None and st.dup_info()[1]:
                 duplicates += 1
                 continue
             at = {}
@@ -244,15 +166,38 @@ def convert_frame_rate_dedup(it, reader: y4m.Y4MReader, out, rate_out, dedup, ma
                 err_max, err_sum = max(err_max, e), err_sum + e
             repeats += len(sp.grid) - len(set(sp.grid))
             k, held = i, frame
-        # the outputs at or behind the last kept frame: the frame itself when it is the last input, else the run of duplicates the video ends in
-        while writer.frames_written < rt.outputs(seen):
+        # the outputs at or behind the last kept frame: the frame itself when it is the last input, else the run of duplicates the video ends
+        # in.  (An output just behind the last input frame was rounded down to it: without dedup that snap error is counted, with dedup the
+        # tail counts none - what the two modes have always reported.)
+        for j in range(writer.frames_written, rt.outputs(seen)):
             writer.write(held)
+            e = abs(rt.error(j)[0]) if dedup is None else 0
+            err_max, err_sum = max(err_max, e), err_sum + e
     if stats is not None:
         den = rt.error(0)[1]
         n = writer.frames_written
         stats.update(snap_max=err_max / den, snap_mean=err_sum / den / n if n else 0.0, pair_runs=runs, pair_runs_full=pushes * per_push,
-                     duplicates=duplicates, repeats=repeats)
+                     **({'duplicates': duplicates, 'repeats': repeats} if dedup is not None else {}))
     return writer.frames_written
+
+
+def double_frame_rate(it, reader: y4m.Y4MReader, out, matrix: str = 'bt709', full_range: Optional[bool] = None, scene_cut: int = 0,
+                      cuts: Optional[list] = None, times: int = 1) -> int:
+    """--times_to_interpolate alone: retime_video at 2^times times the input rate."""
+    return retime_video(it, reader, out, None, None, matrix, full_range, scene_cut, cuts, times)
+
+
+def convert_frame_rate(it, reader: y4m.Y4MReader, out, rate_out, matrix: str = 'bt709', full_range: Optional[bool] = None,
+                       scene_cut: int = 0, cuts: Optional[list] = None, times: int = 1, stats: Optional[dict] = None, dedup=None) -> int:
+    """--fps, with or without --dedup: retime_video at rate_out = (num, den)."""
+    return retime_video(it, reader, out, rate_out, dedup, matrix, full_range, scene_cut, cuts, times, stats)
+
+
+def convert_frame_rate_dedup(it, reader: y4m.Y4MReader, out, rate_out, dedup, matrix: str = 'bt709', full_range: Optional[bool] = None,
+                             scene_cut: int = 0, cuts: Optional[list] = None, times: int = 1, stats: Optional[dict] = None) -> int:
+    """convert_frame_rate(..., dedup=dedup) under its earlier name and argument order: code written against the interface before the one
+    driver, the tests of that commit among them, runs unchanged."""
+    return retime_video(it, reader, out, rate_out, dedup, matrix, full_range, scene_cut, cuts, times, stats)
 
 
 def main(argv=None) -> int:
@@ -290,14 +235,8 @@ def main(argv=None) -> int:
         fout = sys.stdout.buffer if args.output == '-' else open(args.output, 'wb')
         try:
             cuts, stats = [], {}
-            if rate_out is None:
-                n = double_frame_rate(it, reader, fout, args.matrix, args.full_range, args.scene_cut, cuts, args.times_to_interpolate)
-            elif dedup is None:
-                n = convert_frame_rate(it, reader, fout, rate_out, args.matrix, args.full_range, args.scene_cut, cuts,
-                                       args.times_to_interpolate, stats)
-            else:
-                n = convert_frame_rate_dedup(it, reader, fout, rate_out, dedup, args.matrix, args.full_range, args.scene_cut, cuts,
-                                             args.times_to_interpolate, stats)
+            n = retime_video(it, reader, fout, rate_out, dedup, args.matrix, args.full_range, args.scene_cut, cuts, args.times_to_interpolate,
+                             stats if rate_out is not None else None)
             fout.flush()
         finally:
             if fout is not sys.stdout.buffer:

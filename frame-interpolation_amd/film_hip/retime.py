@@ -3,18 +3,17 @@
 A "stream_times" = T frame stream can produce, between two consecutive input frames, the frames at the 2^T - 1 instants i / 2^T of the
 interval (FilmStream.select picks some of them).  Output frame j of the converted video lies at u_j = j (a d) / (b c) input intervals
 from the first input frame; it is SNAPPED to the nearest instant of that grid, g_j = round(u_j 2^T), ties to the even grid index (the
-even index is the shallower, cheaper frame of the recursion).  Interval k = g_j >> T and position i = g_j & (2^T - 1): i = 0 is input
-frame k itself, i > 0 is position i of the push of input frame k + 1.  The snap error |g_j / 2^T - u_j| is at most 2^-(T + 1) input
-intervals, and the g_j are strictly increasing as long as the output rate is at most 2^T times the input rate, which is what Retime
-accepts.  Integers only: no rate is ever a float here.
+even index is the shallower, cheaper frame of the recursion): g_j >> T is an input frame and g_j & (2^T - 1) the position behind it, 0
+the frame itself.  The snap error |g_j / 2^T - u_j| is at most 2^-(T + 1) input intervals, and the g_j are strictly increasing as long as
+the output rate is at most 2^T times the input rate, which is what Retime accepts.  Integers only: no rate is ever a float here.
 
-Stretched intervals (Retime.span).  A stream that drops duplicate frames (engine option "dup_hi") keeps the input frames k_0 = 0 < k_1 < ...;
-span m = [k_m, k_(m+1)) is n_m input intervals long and is closed by ONE push, whose 2^T grid is spread over all of it: output j belongs to the
-span iff k_m <= u_j < k_(m+1), and its grid index is g = round((u_j - k_m) 2^T / n_m), ties to even - 0 and 2^T are the two kept frames.  With
-n_m = 1 throughout this writes the frames described above.
+Spans (Retime.span), the one walk over the outputs.  The input frames a stream keeps are k_0 = 0 < k_1 < ... - all of them, k_m = m, unless it
+drops duplicate frames (engine option "dup_hi").  Span m = [k_m, k_(m+1)) is n_m input intervals long and is closed by ONE push, whose 2^T grid
+is spread over all of it: output j belongs to the span iff k_m <= u_j < k_(m+1), and its grid index is g = round((u_j - k_m) 2^T / n_m), ties to
+even - 0 and 2^T are the two kept frames.  A span of one interval writes the frames of the g_j above: g = g_j - k_m 2^T.
 """
 from math import gcd
-from typing import Iterable, Iterator, NamedTuple, Tuple
+from typing import Iterable, NamedTuple, Tuple
 
 
 def parse_rate(text: str) -> Tuple[int, int]:
@@ -56,13 +55,6 @@ def push_cost(times: int, positions: Iterable[int]) -> Tuple[int, int]:
     return len(c), 1 + fed
 
 
-class Interval(NamedTuple):
-    k: int                        # the interval between input frames k and k + 1
-    write: bool                   # an output lands on input frame k: it is written verbatim ...
-    positions: Tuple[int, ...]    # ... then these positions (ascending) of the push of input frame k + 1
-    j: int                        # the index of the first output of this interval (the input frame, or else the first position)
-
-
 class Span(NamedTuple):
     j: int                        # the index of the first output inside the span (the next span's when `grid` is empty)
     grid: Tuple[int, ...]         # per output, in order: 0 = the kept frame that opens the span, 2^T = the one that closes it, else a position
@@ -94,31 +86,14 @@ class Retime:
         """The snap error g_j / 2^T - u_j of output j in input intervals, as (numerator, denominator > 0)."""
         return self.grid(j) * self.q - (j * self.p << self.times), self.q << self.times
 
-    def intervals(self) -> Iterator[Interval]:
-        """Interval 0, 1, 2, ... without end.  What a converter does with Interval k: write input frame k if `write`; when input frame k + 1
-        arrives, push it with `positions` selected and write what comes back.  The positions of the interval behind the last input frame
-        are dropped: those outputs lie past the end of the video."""
-        j, k, mask = 0, 0, (1 << self.times) - 1
-        while True:
-            j0, write, pos = j, False, []
-            while self.grid(j) >> self.times == k:
-                i = self.grid(j) & mask
-                if i:
-                    pos.append(i)
-                else:
-                    write = True
-                j += 1
-            yield Interval(k, write, tuple(pos), j0)
-            k += 1
-
     def span(self, k: int, n: int) -> 'Span':
         """The outputs of a STRETCHED interval: input frames k and k + n (n >= 1) are kept and the n - 1 between them were dropped as duplicates
         of frame k.  Output j belongs to the span iff k <= u_j < k + n (compared exactly, as fractions); its grid index spreads the span over
         the 2^T grid, g = round((u_j - k) 2^T / n), ties to the even index, 0 <= g <= 2^T: g = 0 is frame k verbatim, g = 2^T is frame k + n
         verbatim, anything else is position g of the push of frame k + n, which closes the span.  A long span may give several outputs one g:
         the position is selected once and written once per such output.  Returns Span(j, grid): the index of the span's first output and the
-        grid indices of its outputs in order.  n = 1 walks the frames intervals() walks (there an output that rounds UP to an input frame opens
-        the next interval, here it closes its own span with g = 2^T: the same frame; the shift by k 2^T is even, so the ties fall alike)."""
+        grid indices of its outputs in order.  n = 1: g = grid(j) - k 2^T (an output that rounds UP to input frame k + 1 closes its span with
+        g = 2^T; the shift by k 2^T is even, so the ties fall alike)."""
         if k < 0 or n < 1:
             raise ValueError(f'a span starts at an input frame k >= 0 and is n >= 1 intervals long, got k = {k!r}, n = {n!r}')
         j0 = -(-k * self.q // self.p)                     # the first j with j p / q >= k

@@ -1,5 +1,5 @@
 """CPU tests of retiming over stretched intervals (film_hip/retime.py, Retime.span) and of eval/video_cli.py --dedup: span() against a brute
-force in fractions.Fraction, n = 1 against intervals(), and the command on scripted duplicate patterns through a stand-in stream that records
+force in fractions.Fraction, n = 1 against grid(), and the command on scripted duplicate patterns through a stand-in stream that records
 what was selected for every push - frame count, header, which frames are verbatim, the hold on a cut, the trailing run, and the bytes of a
 video without duplicates with and without the flag.  No GPU."""
 import io
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from film_hip import retime
+from standin_stream import It as _It, between as _between
 
 RATES = [((24, 1), (60, 1)), ((25, 1), (60, 1)), ((24000, 1001), (60000, 1001)), ((24, 1), (48, 1))]
 
@@ -65,15 +66,15 @@ def test_span_against_the_definition(rate_in, rate_out):
 
 
 @pytest.mark.parametrize('rate_in, rate_out', RATES)
-def test_spans_of_one_interval_walk_the_frames_of_intervals(rate_in, rate_out):
-    """n = 1: the same sequence of frames, frame for frame - (input index, position) per output, position 0 being the input frame itself."""
+def test_spans_of_one_interval_walk_the_frames_of_the_grid(rate_in, rate_out):
+    """n = 1: the sequence of frames of g_j, frame for frame - (input index, position) per output, position 0 being the input frame itself."""
     for times in (2, 3, 4) if rate_out != (48, 1) else (1, 2, 3, 4):
         rt = retime.Retime(rate_in, rate_out, times)
         top = 1 << times
-        old, ivs = [], rt.intervals()
-        for _ in range(40):
-            iv = next(ivs)
-            old += ([(iv.k, 0)] if iv.write else []) + [(iv.k, p) for p in iv.positions]
+        old, j = [], 0
+        while rt.grid(j) >> times < 40:
+            old.append((rt.grid(j) >> times, rt.grid(j) & (top - 1)))
+            j += 1
         new = []
         for k in range(40):
             sp = rt.span(k, 1)
@@ -85,70 +86,6 @@ def test_spans_of_one_interval_walk_the_frames_of_intervals(rate_in, rate_out):
 
 
 # ---- eval/video_cli.py --dedup on a stand-in stream --------------------------------------------------------------------------------------------
-def _avg(a, b):
-    return ((a.astype(np.int32) + b) // 2).astype(np.uint8)
-
-
-def _between(a, b, times):
-    """{position: frame} of the stand-in's recursion between a and b: a frame is the average of its two parents."""
-    at = {0: a, 1 << times: b}
-    step = 1 << times
-    while step > 1:
-        for lo in range(0, 1 << times, step):
-            at[lo + step // 2] = _avg(at[lo], at[lo + step])
-        step //= 2
-    return at
-
-
-class _Stream:
-    """A recording stream: with dedup in the open arguments a pushed frame equal to the carried one is dropped (nothing runs, nothing changes);
-    records the selection in force at every push that was not dropped."""
-
-    def __init__(self, times, cut_at, dedup):
-        self.prev, self.i, self.times, self.cut_at, self.dedup = None, -1, times, cut_at, dedup
-        self.was_cut = self.was_dup = 0
-        self.selection = tuple(range(1, 1 << times))
-        self.selects, self.pushes = [], []
-
-    def __enter__(self): return self
-    def __exit__(self, *exc): pass
-
-    def select(self, positions=None):
-        self.selection = tuple(range(1, 1 << self.times)) if positions is None else tuple(sorted(set(positions)))
-        self.selects.append(self.selection)
-
-    def cut_info(self):
-        return -1, 1, self.was_cut
-
-    def dup_info(self):
-        return None, self.was_dup
-
-    def push(self, frame):
-        self.i += 1
-        self.was_cut = 0
-        self.was_dup = int(self.dedup is not None and self.prev is not None and np.array_equal(frame, self.prev))
-        if self.was_dup:
-            return None
-        mid = None
-        self.was_cut = int(self.prev is not None and self.i == self.cut_at)
-        if self.prev is not None:
-            self.pushes.append((self.i, self.selection))
-        if self.prev is not None and not self.was_cut and self.selection:
-            at = _between(self.prev, frame, self.times)
-            mid = at[1] if self.times == 1 else np.stack([at[p] for p in self.selection])
-        self.prev = frame
-        return mid
-
-
-class _It:
-    def __init__(self, cut_at=None): self.cut_at, self.kw, self.stream = cut_at, None, None
-
-    def open_stream(self, h, w, pix, matrix, full_range, **kw):
-        self.kw = kw
-        self.stream = _Stream(kw.get('times', 1), self.cut_at if kw.get('scene_cut') else None, kw.get('dedup'))
-        return self.stream
-
-
 def _video(pattern, rate=(24, 1)):
     """A 4 x 6 I420 video whose frame i is picture pattern[i]: equal letters are equal frames."""
     from film_hip import y4m
@@ -167,10 +104,7 @@ def _convert(data, rate_out, times, dedup, scene_cut=0, cut_at=None):
     from film_hip import y4m
     it, out, cuts, stats = _It(cut_at), io.BytesIO(), [], {}
     rd = y4m.Y4MReader(io.BytesIO(data))
-    if dedup is None:
-        n = cli.convert_frame_rate(it, rd, out, rate_out, 'bt709', None, scene_cut, cuts, times, stats)
-    else:
-        n = cli.convert_frame_rate_dedup(it, rd, out, rate_out, dedup, 'bt709', None, scene_cut, cuts, times, stats)
+    n = cli.convert_frame_rate(it, rd, out, rate_out, 'bt709', None, scene_cut, cuts, times, stats, dedup=dedup)
     back = y4m.Y4MReader(io.BytesIO(out.getvalue()))
     got = list(back)
     assert n == len(got)
@@ -265,6 +199,17 @@ def test_video_without_duplicates_is_written_byte_for_byte(rate_in, rate_out, ti
         assert with_flag[4]['snap_max'] == pytest.approx(without[4]['snap_max'])
 
 
+def test_the_earlier_name_of_the_dedup_conversion_is_kept():
+    """convert_frame_rate_dedup(it, reader, out, rate_out, dedup, ...), the interface before the one driver: the same bytes, cuts and statistics."""
+    from eval import video_cli as cli
+    from film_hip import y4m
+    _, data = _video('AABBBCDD')
+    it, out, cuts, stats = _It(5), io.BytesIO(), [], {}
+    n = cli.convert_frame_rate_dedup(it, y4m.Y4MReader(io.BytesIO(data)), out, (48, 1), (0, 0, 1000), 'bt709', None, 250, cuts, 3, stats)
+    want = _convert(data, (48, 1), 3, (0, 0, 1000), scene_cut=250, cut_at=5)
+    assert n == 15 and (out.getvalue(), cuts, stats, it.kw, it.stream.pushes) == (want[5], want[3], want[4], want[0].kw, want[0].stream.pushes)
+
+
 def test_dedup_flag_needs_fps_and_parses(tmp_path, monkeypatch):
     from eval import interpolator as interpolator_lib
     from eval import video_cli as cli
@@ -308,3 +253,22 @@ def test_video_cli_main_with_dedup(tmp_path, monkeypatch, capsys):
     want = _expected(frames, [0, 2, 5, 6], (24, 1), (48, 1), 3)
     assert len(got) == 15 and all(np.array_equal(g, w) for g, w in zip(got, want))
     assert its[0].kw == {'times': 3, 'dedup': (0, 0, 1000)}
+
+
+def test_the_one_loop_writes_what_the_three_loops_wrote():
+    """tests/golden/video_cli_digests.json was written by tools/make_video_cli_golden.py from the commit that had one frame loop per mode
+    (--times_to_interpolate, --fps, --fps --dedup): per case the bytes written, the return value, the cuts, what open_stream got, every
+    select() and every push that ran, and the statistics to the last bit are still those."""
+    import importlib.util
+    import json
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('make_video_cli_golden', os.path.join(root, 'tools', 'make_video_cli_golden.py'))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    want, got = json.load(open(tool.PATH)), json.loads(json.dumps(tool.records()))
+    assert len(want) >= 100 and sorted(got) == sorted(want)
+    for name in sorted(want):
+        assert sorted(got[name]) == sorted(want[name]), name
+        for key in want[name]:
+            assert got[name][key] == want[name][key], (name, key)

@@ -1,7 +1,10 @@
 """GPU tests of frame streams that drop duplicate frames (options "dup_hi" / "dup_lo" / "dup_frac"; include/film_hip.h, "Duplicate frames"),
 on the TINY net: a push judged a duplicate reports dup = 1 and the restatement's statistics (tests/frame_diff_ref.py), produces nothing,
 leaves `out` and the stream untouched, and the next real push returns the bits of a plain stream that never saw the dropped frames - from
-host and device memory, for an RGB, an 8-bit and a 10-bit Y'CbCr layout, with recursion and a selection, and beside option "scene_cut"."""
+host and device memory, for an RGB, an 8-bit and a 10-bit Y'CbCr layout, with recursion and a selection, and beside option "scene_cut"; and
+the eval.video_cli --dedup command end to end."""
+import io
+
 import numpy as np
 import pytest
 
@@ -190,3 +193,50 @@ def test_without_the_option_nothing_is_compared_or_dropped(tiny):
     dedup, _, _, _ = _run(tiny, 'u8', 'host', [f['A'], f['A'], f['B']], dedup=0)
     assert dedup[1] is None and _same(dedup[2], _plain(tiny, 'u8')['A_B'])
     assert _same(got[2], dedup[2])           # (A, A, B plain: the carried frame of the last push is A either way)
+
+
+def test_video_cli_dedup(tiny, tmp_path, monkeypatch, capsys):
+    """eval.video_cli --fps 48 --times_to_interpolate 2 --dedup 0 on a 64 x 64 24 fps .y4m A A B C: the span of two intervals is spread over
+    the full push of B, then B, position 2 of the push of C, and C - seven frames, each the bytes of a frame of --times_to_interpolate 2 on
+    A B C; and on A B C the flag changes no byte."""
+    from eval import interpolator as interpolator_lib
+    from eval import video_cli as cli
+    from film_hip import y4m
+    real = interpolator_lib.Interpolator
+
+    def interp(model_path, align, block_shape, **kw):
+        it = real.__new__(real)
+        it._options, it._engine = tiny.options, tiny
+        it._align, it._block_shape = align or None, block_shape or None
+        return it
+
+    a, b, c = np.random.default_rng(23).integers(0, 256, (3, 96, 64), dtype=np.uint8)        # 64 x 64 I420 frames of random codes
+
+    def video(name, frames):
+        with open(tmp_path / name, 'wb') as f:
+            wr = y4m.Y4MWriter(f, y4m.header_tokens(64, 64, (24, 1)))
+            for fr in frames:
+                wr.write(fr)
+        return str(tmp_path / name)
+
+    def run(src, name, *flags):
+        n = cli.main(['--input', src, '--output', str(tmp_path / name), '--times_to_interpolate', '2', *flags])
+        return n, (tmp_path / name).read_bytes(), capsys.readouterr().err
+
+    monkeypatch.setattr(interpolator_lib, 'Interpolator', interp)
+    aabc, abc = video('aabc.y4m', [a, a, b, c]), video('abc.y4m', [a, b, c])
+    _options_off(tiny)
+    try:
+        n_ref, ref, _ = run(abc, 'ref.y4m')
+        n, got, err = run(aabc, 'out.y4m', '--fps', '48', '--dedup', '0')
+        _options_off(tiny)                       # (handle options: the next command runs without them)
+        plain = run(abc, 'plain.y4m', '--fps', '48')
+        same = run(abc, 'same.y4m', '--fps', '48', '--dedup', '0')
+    finally:
+        _options_off(tiny)
+    every, frames = list(y4m.Y4MReader(io.BytesIO(ref))), list(y4m.Y4MReader(io.BytesIO(got)))
+    assert n_ref == len(every) == 9 and len({e.tobytes() for e in every}) == 9
+    assert n == len(frames) == 7 and '1 duplicate input frames dropped' in err
+    for j, g in enumerate((0, 1, 2, 3, 4, 6, 8)):
+        assert frames[j].tobytes() == every[g].tobytes(), (j, g)
+    assert plain[0] == same[0] == 5 and same[1] == plain[1] and '0 duplicate input frames dropped' in same[2]

@@ -15,6 +15,7 @@ import re
 import numpy as np
 import pytest
 
+from standin_stream import It as _It, between as _between
 from test_sequence_cpu import _tiny_engine
 
 H, W = 32, 48
@@ -284,14 +285,15 @@ def test_retime_properties():
 
 
 def _table(rate_in, rate_out, times, n):
+    """From the definition: output j is position g_j & (2^T - 1) behind input frame g_j >> T, position 0 being the frame itself."""
     from film_hip import retime
     rt = retime.Retime(rate_in, rate_out, times)
-    rows = []
-    for iv in rt.intervals():
-        if iv.k == n:
-            return rows, rt
-        assert iv.k == len(rows) and iv.j == sum(w + len(p) for w, p in rows)
-        rows.append((iv.write, iv.positions))
+    rows, j = [(False, ())] * n, 0
+    while rt.grid(j) >> times < n:
+        k, i = rt.grid(j) >> times, rt.grid(j) & ((1 << times) - 1)
+        rows[k] = (rows[k][0], rows[k][1] + (i,)) if i else (True, rows[k][1])
+        j += 1
+    return rows, rt
 
 
 def test_retime_tables():
@@ -331,59 +333,6 @@ def test_set_rate():
 
 
 # ---- the CLI ----------------------------------------------------------------------------------------------------------------------------
-def _avg(a, b):
-    return ((a.astype(np.int32) + b) // 2).astype(np.uint8)
-
-
-def _between(a, b, times):
-    """{position: frame} of the stand-in's recursion between a and b: a frame is the average of its two parents."""
-    at = {0: a, 1 << times: b}
-    step = 1 << times
-    while step > 1:
-        for lo in range(0, 1 << times, step):
-            at[lo + step // 2] = _avg(at[lo], at[lo + step])
-        step //= 2
-    return at
-
-
-class _Stream:
-    """The stand-in stream of test_video_cli_times_to_interpolate, with a selection."""
-
-    def __init__(self, times, cut_at):
-        self.prev, self.i, self.times, self.cut_at, self.was_cut = None, -1, times, cut_at, 0
-        self.selection = tuple(range(1, 1 << times))
-        self.selects = []
-
-    def __enter__(self): return self
-    def __exit__(self, *exc): pass
-
-    def select(self, positions=None):
-        self.selection = tuple(range(1, 1 << self.times)) if positions is None else tuple(sorted(set(positions)))
-        self.selects.append(self.selection)
-
-    def cut_info(self):
-        return -1, 1, self.was_cut
-
-    def push(self, frame):
-        self.i += 1
-        mid = None
-        self.was_cut = int(self.prev is not None and self.i == self.cut_at)
-        if self.prev is not None and not self.was_cut and self.selection:
-            at = _between(self.prev, frame, self.times)
-            mid = at[1] if self.times == 1 else np.stack([at[p] for p in self.selection])
-        self.prev = frame
-        return mid
-
-
-class _It:
-    def __init__(self, cut_at=None): self.cut_at, self.kw, self.stream = cut_at, None, None
-
-    def open_stream(self, h, w, pix, matrix, full_range, **kw):
-        self.kw = kw
-        self.stream = _Stream(kw.get('times', 1), self.cut_at if kw.get('scene_cut') else None)
-        return self.stream
-
-
 def _video(n, rate, tokens=None):
     from film_hip import y4m
     frames = np.random.default_rng(5).integers(0, 256, (n, 6, 6), dtype=np.uint8)        # 4 x 6 I420 frames
