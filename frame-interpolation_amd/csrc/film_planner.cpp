@@ -793,6 +793,9 @@ void json_op(JsonObject& j, const OpDesc& op, const Plan& P) {
   j.objects("segs", op.seg, op.nseg, [&](JsonObject& s, const SegDesc& g) {
     s.view("v", g.v, P); s.num("boff", g.boff); s.num("bmod", g.bmod); s.num("up", g.up);
   });
+  // the tile codes the autotuner and film_debug_run_op would try for the op (a plan-only handle can say them: they depend on the descriptor alone)
+  const std::vector<int> cands = op.kind == OP_CONV ? conv_candidates(op) : std::vector<int>();
+  j.ints("cands", cands.data(), cands.size());
 }
 }  // namespace
 

@@ -6,7 +6,11 @@ for the exact families, within 2 x the float32 restatement's own error on the po
 Two engines per plan: one with integer weights (op_harness.make_integer_weights: the exact regime and the designed impulse sets), one
 with the seeded synthetic weights (the rounding regime on random normal activations at three dynamic ranges).  Autotune is off: the
 test runs every candidate of every conv op itself.  FILM_OP_ERRORS=<file> makes the run write its error table there (the source of
-profiles/op_isolation_errors.md)."""
+profiles/op_isolation_errors.md).
+
+The case lists and the definition of "covered" live in tests/op_cases.py: the kernel variants the plans of the real workloads hold and
+the small plans above do not (unsplit deep conv_wino2d layers, the 9 x 15 level's split, the per-direction warps) run through NEW_CASES,
+only the ops no earlier case covers (test_workload_variants_in_isolation), with the same checks."""
 import os
 import time
 
@@ -15,46 +19,22 @@ import pytest
 
 from conftest import has_extra_families, needs_extra_families
 
+import op_cases as OC
 import op_harness as OH
+from op_cases import CASES, EXTRA_CASES, NEW_CASES, _case_id, _config
 
 pytestmark = pytest.mark.gpu
 _T0 = time.time()
 
 _KINDS, _FAMILIES, _CASES_RUN, _TABLE, _COUNTS = set(), set(), set(), [], []
+_RAN = OC.Covered()  # signature (op_cases.signature) and candidate codes of every op that ran
 _PLANNED = set()    # every conv family any op of any plan of this run uses (from the plan JSON: what the bound libraries hold and select)
 DEFAULT_FAMILIES = {'BUF', 'C3', 'W2D', 'W43', 'FOLD4', 'FOLD2'}
 EXTRA_FAMILIES = {'HALO', 'SPLIT6', 'SPLIT3', 'WINO', 'WINOX3', 'FOLDX3'}
 ALL_KINDS = {'conv_mfma', 'conv_pw', 'flow_head', 'pool', 'warp', 'flow_up', 'flow_add', 'pack_flow'}
 
 
-def _config(name):
-    from film_hip.options import Options, PUBLISHED, TINY
-    # the fine levels of a 1080p tile at 64 .. 256 channels, on frames of any multiple of 4
-    wide = Options(pyramid_levels=3, fusion_pyramid_levels=3, specialized_levels=2, sub_levels=3, flow_convs=(3, 3, 3),
-                   flow_filters=(64, 128, 128), filters=64)
-    return {'published': PUBLISHED, 'tiny': TINY, 'wide': wide}[name]
-
-
-_DEFAULT_PLANS = [('published', (1, 64, 64)), ('published', (2, 128, 64)), ('published', (1, 128, 320)),
-                  ('wide', (1, 36, 60)), ('wide', (1, 20, 44)), ('wide', (2, 68, 100)), ('wide', (1, 12, 132)),
-                  ('tiny', (3, 64, 24)), ('tiny', (2, 64, 32, 1))]       # (the last: a sequence plan of two pairs of one tile)
-_OPTION_SETS = [{'wino2d': 2}, {'winograd': 3}, {'winograd': 0, 'wino2d': 0}, {'winograd': 3, 'wino2d': 0}, {'fold2x2': 0}, {'fold2x2': 2},
-                {'planar': 0}, {'fuse': 0}, {'splitk': 0}, {'w2d_splitk': 0}, {'w2d_splitk': 16}]
-_EXTRA_OPTION_SETS = [{'precision': 1}, {'precision': 2}, {'halo_all': 1}, {'winograd': 2}, {'winograd': 2, 'wino2d': 0},
-                      {'halo_all': 1, 'winograd': 0, 'wino2d': 0}, {'precision': 1, 'halo_all': 1}, {'precision': 2, 'halo_all': 1},
-                      {'precision': 2, 'winograd': 2}]
-_OPTION_PLANS = [('published', (1, 64, 64)), ('wide', (1, 36, 60))]
-
-
-def _case_id(cfg, key, options):
-    return f'{cfg}-{"x".join(map(str, key))}' + ''.join(f'-{k}{v}' for k, v in options.items())
-
-
-CASES = [(cfg, key, {}) for cfg, key in _DEFAULT_PLANS] + [(cfg, key, o) for o in _OPTION_SETS for cfg, key in _OPTION_PLANS]
-EXTRA_CASES = [(cfg, key, o) for o in _EXTRA_OPTION_SETS for cfg, key in _OPTION_PLANS]
-
-
-def _run_case(cfg, key, options):
+def _run_case(cfg, key, options, only=None):
     from film_hip import weights as W
     from film_hip.engine import FilmEngine
     opt = _config(cfg)
@@ -75,6 +55,11 @@ def _run_case(cfg, key, options):
             h = OH.Harness(OH.GpuBackend(eng, key), plan, packed, integer)
             # ops of ONE plan that share their descriptor (op_harness.dedup_key) run once; nothing else is skipped
             ops = distinct = h.distinct_ops()
+            if only is not None:    # (test_workload_variants_in_isolation: indices into the plan as a plan-only handle states it - the same plan)
+                want = [(OC.signature(op), op['cands']) for op in OC.case_plan(cfg, key, options)['ops']]
+                assert [(OC.signature(op), op['cands']) for op in plan['ops']] == want, 'the device plan differs from the plan-only one'
+                seen = {OH.dedup_key(plan['ops'][i]) for i in only}
+                ops = [i for i in distinct if OH.dedup_key(plan['ops'][i]) in seen]
             _PLANNED.update(OH.family(op) for op in plan['ops'] if op['kind'] == 'conv_mfma')
             for i in ops:
                 op = plan['ops'][i]
@@ -84,12 +69,15 @@ def _run_case(cfg, key, options):
                     _FAMILIES.add(OH.family(op))
                     n = h.n_candidates[i]       # (what film_debug_run_op reported for the op)
                     assert h.ran_candidates[i] == n >= 1, f'{op["tag"]}: {h.ran_candidates[i]} of {n} candidates ran'
+                    assert n == len(op['cands']), f'{op["tag"]}: the plan lists {op["cands"]}, film_debug_run_op has {n} candidates'
+                if integer or op['kind'] in ('conv_mfma', 'conv_pw', 'flow_head'):     # (check_op has nothing to run otherwise)
+                    _RAN.add(OC.signature(op), OC.candidates(op))
             total = len(plan['ops'])
             for r in h.records:
                 _TABLE.append((_case_id(cfg, key, options), r))
             if integer:
                 _COUNTS.append((_case_id(cfg, key, options), total, len(distinct), len(ops), eng.version()))
-                print(f'{_case_id(cfg, key, options)}: {total} ops in the plan, {len(distinct)} distinct ones run')
+                print(f'{_case_id(cfg, key, options)}: {total} ops in the plan, {len(ops)} of {len(distinct)} distinct ones run')
         finally:
             eng.close()
     print(f'{_case_id(cfg, key, options)}: {time.time() - t0:.1f} s')
@@ -106,6 +94,16 @@ def test_every_op_in_isolation(cfg, key, options):
 @pytest.mark.parametrize('cfg,key,options', EXTRA_CASES, ids=[_case_id(*c) for c in EXTRA_CASES])
 def test_every_op_in_isolation_extra_families(cfg, key, options):
     _run_case(cfg, key, options)
+
+
+@pytest.mark.parametrize('cfg,key,options', NEW_CASES, ids=[_case_id(*c) for c in NEW_CASES])
+def test_workload_variants_in_isolation(cfg, key, options):
+    """The kernel variants only the plans of real workloads hold (op_cases.workload_plans), on the small plans of NEW_CASES that plan them
+    too: the ops of the case whose signature and candidate list no earlier case of CASES + NEW_CASES covers, checked like every other op."""
+    cases = CASES + NEW_CASES
+    only = OC.ops_no_earlier_case_covers(cases, cases.index((cfg, key, options)))
+    assert only, 'every op of the case is covered by an earlier one: the case adds nothing'
+    _run_case(cfg, key, options, only=only)
 
 
 def test_debug_entry_points_refuse_what_the_header_says(tiny_weights):
@@ -139,8 +137,10 @@ def test_debug_entry_points_refuse_what_the_header_says(tiny_weights):
 
 def test_coverage_of_the_isolation_run():
     """Every op kind, every conv family of the bound library (and of the extra-families library when it has been built) and every
-    candidate (asserted per op above) has run.  Needs the whole file to have run in this session."""
-    want = {_case_id(*c) for c in CASES}
+    candidate (asserted per op above) has run - and every kernel variant (op_cases.signature, with a superset of its tile candidates) of
+    every op the plans of the real workloads hold (op_cases.workload_plans, on a plan-only handle).  Needs the whole file to have run in
+    this session."""
+    want = {_case_id(*c) for c in CASES + NEW_CASES}
     extra_built = has_extra_families() or os.path.isfile(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                                     'frame-interpolation_amd', 'film_hip', 'libfilm_hip_extra.so'))
     if extra_built:
@@ -152,6 +152,11 @@ def test_coverage_of_the_isolation_run():
     assert _PLANNED <= _FAMILIES, _PLANNED - _FAMILIES
     fams = DEFAULT_FAMILIES | (EXTRA_FAMILIES if extra_built else set())
     assert fams <= _PLANNED, fams - _PLANNED
+    missing = {}
+    for label, op in OC.workload_ops():
+        if not _RAN.covers(op):
+            missing.setdefault(OC.signature(op), (label, op['tag'], f'{op["H"]}x{op["W"]}'))
+    assert not missing, f'{len(missing)} kernel variants of the workload plans did not run in isolation:\n' + OC.format_uncovered(missing)
     path = os.environ.get('FILM_OP_ERRORS')
     if path:
         _write_table(path)
@@ -180,5 +185,5 @@ def _write_table(path):
             f.write(f'| {fam} | {K} | {s} | {n} | {er:.2f} | {eg:.2f} | {shown} | {ef:.2f} | {tag} |\n')
         f.write('\n## Ops per plan\n\n| plan | ops | distinct ops run | library |\n|---|---|---|---|\n')
         for case, total, distinct, run, ver in _COUNTS:
-            f.write(f'| {case} | {total} | {distinct} | {ver} |\n')
+            f.write(f'| {case} | {total} | {run if run == distinct else f"{run} of {distinct}"} | {ver} |\n')
         f.write(f'\nWall time of the file: {time.time() - _T0:.0f} s.\n')
