@@ -163,6 +163,15 @@ def resize_nearest(x: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
     return x[:, ys][:, :, xs]
 
 
+def warp_query(flow_yx_neg: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The query points (qy, qx) of dense_image_warp: grid - flow, in the flow's dtype ([N, H, W] each)."""
+    h, w = flow_yx_neg.shape[1:3]
+    gy, gx = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
+    qy = gy.astype(flow_yx_neg.dtype)[None] - flow_yx_neg[..., 0]
+    qx = gx.astype(flow_yx_neg.dtype)[None] - flow_yx_neg[..., 1]
+    return qy, qx
+
+
 def dense_image_warp(image: np.ndarray, flow_yx_neg: np.ndarray) -> np.ndarray:
     """tfa.image.dense_image_warp(image, flow) (TFA 0.15.0): query = grid - flow with
     flow in (dy, dx) order, then interpolate_bilinear(indexing='ij'):
@@ -171,9 +180,7 @@ def dense_image_warp(image: np.ndarray, flow_yx_neg: np.ndarray) -> np.ndarray:
     n, h, w, c = image.shape
     assert h >= 2 and w >= 2, 'dense_image_warp needs a grid of at least 2x2'
     dt = image.dtype
-    gy, gx = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
-    qy = gy.astype(flow_yx_neg.dtype)[None] - flow_yx_neg[..., 0]
-    qx = gx.astype(flow_yx_neg.dtype)[None] - flow_yx_neg[..., 1]
+    qy, qx = warp_query(flow_yx_neg)
 
     def axis(q, size):
         fl = np.minimum(np.maximum(np.floor(q), 0), size - 2)

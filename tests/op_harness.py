@@ -24,7 +24,18 @@ For one op, Harness.check_op
      the restatement - the same op, the same inputs, the same outputs.  (A maximum over the whole output against a maximum over a
      sample does not compare like with like: e has a long tail, and every kernel family, torch's own CPU convolution included,
      exceeded 2 x by 10-60 % that way.)  Where the restatement is affordable over the whole output (FULL_COST) it covers it; beyond,
-     the whole output is held to WHOLE_FACTOR = 4 x the restatement's maximum on the sample.
+     the whole output is held to WHOLE_FACTOR = 4 x the restatement's maximum on the sample;
+     real-valued regime of the resampling kinds (REAL_KINDS: pool, flow_up, flow_add, pack_flow, warp - in the pass that is not integer;
+     the weights do not matter to them): every output view equals, value for value, plan_interp.run_op on a FLOAT32 arena - the
+     oracle states these ops one numpy operation at a time in the array's dtype, so that is the kernels' documented arithmetic with
+     one rounding per operation: the summation order of the pools, no fma in the lerps, the clamp in float before the conversion.
+     Input sets (input_sets): `normal*s` (random sources, flows of a few pixels that are not dyadic, one in eight up to two frame
+     sizes away), and for a warp `edges` (flows solved so that q lands on and next to every clamp: Q_CLASSES, _edge_flows) and `huge`
+     (flows of 1e6 .. 3e38 and +-inf).  On the sets with finite flows the output and the float32 oracle are also both held to an
+     a-priori bound against float64 (f64_bounds), and a difference in bits is reported with both errors: "rounded differently" against
+     "wrong" at a glance,
+  8. fused epilogues (the pass that is not integer): a conv op's fused pool is avg_pool2x2 of the `out` the same launch stored, a flow
+     head's fused sum is `out` + in2, both in float32, bit for bit.
 
 It does not poison the background with NaN, and the F(4,3)-based kernels (conv_wino43_kernel, conv_wino2d_kernel: their 1/6, 1/12,
 1/24 weight transforms are rounded) and the bf16 split modes (restated with the split conv_split_impl.h defines) are held to
@@ -44,6 +55,7 @@ WHOLE_ARENA_BYTES = 64 << 20
 BAND_FLOATS = (1 << 20) // 4
 EXACT_KINDS = ('conv_pw', 'flow_head', 'pool', 'flow_up', 'flow_add', 'pack_flow', 'warp')
 EXACT_FAMILIES = ('BUF', 'C3', 'HALO', 'WINO', 'FOLD4', 'FOLD2')      # conv families held to bit-exactness on integer operands
+REAL_KINDS = ('pool', 'flow_up', 'flow_add', 'pack_flow', 'warp')     # the resampling kinds: held to the float32 oracle's bits on real data
 # The restatement costs a float64 multiply-add per product on the CPU: it covers the whole output of an op up to FULL_COST
 # multiply-adds (most ops of the small plans), a sample of SAMPLE_COST beyond.
 FULL_COST = 3e8
@@ -231,6 +243,206 @@ class InputSet:
     exact: bool                       # small integers: every partial sum is a float32 number
     values: Dict[str, np.ndarray]     # input view name -> [nb, h, w, C] float32
     poi: List[Tuple[int, int, int]]   # (n, y, x) the set was designed around
+    finite: bool = True               # no infinite flow: the float64 bound of the resampling kinds applies
+
+
+# ----------------------------------------------------------------------------------------------
+# the resampling kinds on real data: designed flows, and the a-priori bound against float64
+# ----------------------------------------------------------------------------------------------
+FLOW_VIEWS = ('in2', 'pack_b', 'pack_f')     # the flows a warp reads directly (in3 is the coarse flow behind the fused x2 resize)
+HUGE_FLOWS = (1e6, 2.0 ** 31, 1e30, 3e38)
+# q classes of one axis of a warp (warp_classes); `edges` puts at least one pixel into each, for every directly read flow
+Q_CLASSES = ('floor(q) < 0', 'q an integer inside the frame', 'size-2 < q < size-1', 'q = size-1', 'q > size-1', 'alpha clamped to 0',
+             'alpha clamped to 1', 'float32 q and exact q floor differently')
+# ... and what the random flows of `normal*s` reach behind the fused resize, where the flow is derived and cannot be solved for: every
+# class that is an interval of q.  An integer q, and a q within half an ulp below one, are points: a derived flow does not hit them.
+Q_CLASSES_OF_A_DERIVED_FLOW = (0, 2, 4, 5, 6)
+
+
+def _flow_scale(op: dict, name: str) -> float:
+    return op['fscale'] if name in ('in2', 'in3') else 0.5
+
+
+def _edge_variants(size: int, coord: np.ndarray, fscale: float) -> np.ndarray:
+    """[variant, pixel] float32 flows of one axis: q = coord + fscale * flow aimed at every target (-1, 0, 0.5, 1, size - 2, size - 1, size, 2 size) and at its neighbours one
+    and two ulps to either side, for both meanings of "one ulp": the float32 neighbours t of the target, flow = (t - coord) / fscale
+    rounded once (they are the q next to the target that float32 can hold), and the float32 neighbours of the flow solved for the
+    target itself (their exact q lies between two float32 numbers: float32 q is rounded back onto one of them, which is how it comes
+    to floor differently from the exact q).  A neighbour of zero would be a denormal: those variants keep the flow of the target."""
+    c = coord.astype(np.float64)
+    out = []
+    for base in (-1.0, 0.0, 0.5, 1.0, size - 2.0, size - 1.0, float(size), 2.0 * size):
+        f0 = ((base - c) / fscale).astype(np.float32)
+        out.append(f0)
+        for k in (-2, -1, 1, 2):
+            t = np.float32(base)
+            for _ in range(abs(k)):
+                t = np.nextafter(t, np.float32(np.inf if k > 0 else -np.inf))
+            out.append(((np.float64(t) - c) / fscale).astype(np.float32) if base != 0 else f0)
+            f = f0.copy()
+            for _ in range(abs(k)):
+                f = np.nextafter(f, np.float32(np.inf if k > 0 else -np.inf))
+            out.append(np.where(f0 != 0, f, f0))
+    return np.stack(out)
+
+
+def _axis_classes(q32: np.ndarray, q64: np.ndarray, size: int) -> np.ndarray:
+    """[..., len(Q_CLASSES)] bool: the classes of Q_CLASSES that float32 q (and, for the last, the exact q next to it) falls into."""
+    fl = np.floor(q32)
+    a = q32 - np.minimum(np.maximum(fl, 0), size - 2)       # alpha before its clamp
+    return np.stack([fl < 0, (q32 == fl) & (q32 >= 0) & (q32 <= size - 1), (q32 > size - 2) & (q32 < size - 1), q32 == size - 1, q32 > size - 1,
+                     a < 0, a > 1, fl != np.floor(q64)], axis=-1)
+
+
+def _edge_flows(rng, nb: int, h: int, w: int, fscale: float) -> np.ndarray:
+    """[nb, h, w, 2] float32 flow (x, y) whose q covers every class of Q_CLASSES on both axes (a level has at least 2 x 2 pixels and a
+    launch at least one image), the variants of _edge_variants spread over rows, columns and images.  A few pixels are given
+    the variant that puts a class on record that no pixel holds yet; every other pixel walks through the variant list."""
+    n = nb * h * w
+    ys, xs = np.divmod(np.arange(n) % (h * w), w)
+    flow = np.zeros((n, 2), np.float32)
+    for comp, (size, coord) in enumerate(((w, xs), (h, ys))):
+        var = _edge_variants(size, coord, fscale)                   # [V, n]
+        c = coord.astype(np.float32)
+        with np.errstate(all='ignore'):
+            q32 = c + np.float32(fscale) * var
+            q64 = c.astype(np.float64) + np.float64(fscale) * var.astype(np.float64)
+        cls = _axis_classes(q32, q64, size)                        # [V, n, classes]
+        step = int(rng.integers(1, len(var)))
+        pick = (np.arange(n) * 5 + step) % len(var)                 # (5 and the 72 variants are coprime)
+        order = rng.permutation(n)
+        held = np.zeros(len(Q_CLASSES), bool)
+        fixed = 0
+        while not held.all():
+            assert fixed < n, 'more classes than pixels'
+            i = order[fixed]
+            gain = (cls[:, i] & ~held).sum(axis=1)
+            if gain.any():
+                pick[i] = int(np.argmax(gain))
+            held |= cls[pick[i], i]
+            fixed += 1
+        # (the pixels behind `fixed` keep their walk: they can only add to what is held)
+        flow[:, comp] = var[pick, np.arange(n)]
+    return flow.reshape(nb, h, w, 2)
+
+
+def warp_queries(op: dict, values: Dict[str, np.ndarray], dtype) -> List[Tuple[str, np.ndarray, np.ndarray]]:
+    """(flow view, qy, qx) of every flow a warp op samples with, per flow pixel: the oracle's own query points (fo.warp_query of the
+    oracle's own flow statements, plan_interp.run_op) in `dtype`."""
+    fo = PI.fo
+    nb, h, w = op['NB'], op['H'], op['W']
+    out = []
+    for name, v, nbv, hv, wv in in_views(op):
+        if name == 'in3':
+            flow = fo.resize_bilinear(np.float32(2) * values[name].astype(dtype), (h, w))
+        elif name in FLOW_VIEWS:
+            flow = values[name].astype(dtype)
+        else:
+            continue
+        with np.errstate(all='ignore'):
+            qy, qx = fo.warp_query(-(np.float32(_flow_scale(op, name)) * flow)[..., ::-1])
+        out.append((name, qy, qx))
+    return out
+
+
+def warp_classes(op: dict, values: Dict[str, np.ndarray]) -> Dict[Tuple[str, str], np.ndarray]:
+    """{(flow view, axis): number of pixels in each class of Q_CLASSES}, from the oracle's q in float32 and in float64."""
+    out = {}
+    for (name, qy, qx), (_, ry, rx) in zip(warp_queries(op, values, np.float32), warp_queries(op, values, np.float64)):
+        out[(name, 'y')] = _axis_classes(qy, ry, op['H']).reshape(-1, len(Q_CLASSES)).sum(axis=0)
+        out[(name, 'x')] = _axis_classes(qx, rx, op['W']).reshape(-1, len(Q_CLASSES)).sum(axis=0)
+    return out
+
+
+# One float32 operation rounds by at most U = 2^-24 of its result.  A lerp as the oracle states it - three operations, d = b - a,
+# p = d t, r = a + p (or p + a), 0 <= t <= 1 exact - on operands of magnitude <= M that carry an error <= e: the exact lerp of the
+# operands carries <= e (a convex combination); |d| <= 2 M' (M' = M + e) rounds by <= 2 U M'; |p| <= 2 M' (1 + U) by <= 2 U M' (1 + U);
+# |a + p| <= M' (1 + 4 U + 2 U^2) by U times that: e' <= e + LERP U M', LERP = 5 + 6 U + 2 U^2.
+LERP = 5 + 6 * ULP + 2 * ULP ** 2
+
+
+def _lerp_bound(M, e=0.0):
+    return e + LERP * ULP * (M + e)
+
+
+def _flow_up_bound(x64: np.ndarray, size) -> np.ndarray:
+    """flow_up / the fused resize: 2 x is exact and the lerp weights are the same float32 numbers in either precision, so the error is
+    the roundings of the three lerps (top and bottom along x, then along y) on M = the largest magnitude of the four corners."""
+    fo = PI.fo
+    h, w = x64.shape[1:3]
+    ylo, yhi, _ = fo._resize_axis_weights(h, size[0], np.float64)
+    xlo, xhi, _ = fo._resize_axis_weights(w, size[1], np.float64)
+    a = np.abs(2.0 * x64)
+    M = np.maximum(np.maximum(a[:, ylo][:, :, xlo], a[:, ylo][:, :, xhi]), np.maximum(a[:, yhi][:, :, xlo], a[:, yhi][:, :, xhi]))
+    return _lerp_bound(M, _lerp_bound(M))
+
+
+def _warp_bound(src64: np.ndarray, qy: np.ndarray, qx: np.ndarray, dy, dx) -> np.ndarray:
+    """A warp of src64 [nb, h, w, C] at the exact query points (qy, qx) [nb, h, w] that float32 knows to within (dy, dx): bilinear
+    interpolation with clamped indices and weights is a continuous function of q, linear inside a cell with the corner differences
+    as slopes, across cell borders and across both clamps - so float32 q moves the exact result by at most dx Dx + dy Dy, D = the
+    largest difference of neighbouring corners over the cells q +- d touches (two per axis when q lies within d of a border: a
+    different floor on the two sides is covered, not excluded).  Its weights are then exact functions of float32 q (q - floor(q) is
+    exact, the clamps round monotonically), and the three lerps round as in _lerp_bound on M = the largest corner magnitude of those
+    cells (a corner outside them has the weight 0: the lerp returns the other corner bit for bit)."""
+    nb, h, w, _ = src64.shape
+    b = np.arange(nb)[:, None, None]
+
+    def cells(q, d, size):
+        lo = np.clip(np.floor(q - d), 0, size - 2).astype(np.int64)
+        hi = np.clip(np.floor(q + d), 0, size - 2).astype(np.int64)
+        return lo, lo + 1, hi + 1
+    rows, cols = cells(qy, dy, h), cells(qx, dx, w)
+    v = [[src64[b, r, c] for c in cols] for r in rows]
+    M = np.max([np.abs(v[i][j]) for i in range(3) for j in range(3)], axis=0)
+    Dx = np.max([np.abs(v[i][j + 1] - v[i][j]) for i in range(3) for j in range(2)], axis=0)
+    Dy = np.max([np.abs(v[i + 1][j] - v[i][j]) for i in range(2) for j in range(3)], axis=0)
+    return dx[..., None] * Dx + dy[..., None] * Dy + _lerp_bound(M, _lerp_bound(M))
+
+
+def f64_bounds(op: dict, values: Dict[str, np.ndarray], ref64: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """{output view: a-priori bound on |float32 result - float64 result|} of an op of the resampling kinds, elementwise, from one
+    rounding of at most U = 2^-24 (relative) per float32 operation of the oracle's statements:
+      flow_add    one addition: U |result|
+      pack_flow   one multiplication (by 0.5: exact): U |result|; the zero channels: 0
+      pool        three additions, each partial sum at most S = |a| + |b| + |c| + |d| (times (1 + U) per earlier rounding), then
+                  the exact x 0.25: 0.25 S ((1 + U)^3 - 1)
+      flow_up     _flow_up_bound
+      warp        _warp_bound with d = U |q| (q = coord + fscale flow is one rounded addition: fscale is 1 or 0.5); behind the
+                  fused resize the flow itself carries e = _flow_up_bound: d = fscale e (1 + U) + U |q|, and out2 is held to e"""
+    k, nb, h, w = op['kind'], op['NB'], op['H'], op['W']
+    v64 = {name: a.astype(np.float64) for name, a in values.items()}
+    if k in ('flow_add', 'pack_flow'):
+        return {'out': ULP * np.abs(ref64['out'])}
+    if k == 'pool':
+        a = np.abs(v64['in'][:, :h // 2 * 2, :w // 2 * 2])
+        S = a[:, 0::2, 0::2] + a[:, 0::2, 1::2] + a[:, 1::2, 0::2] + a[:, 1::2, 1::2]
+        return {'out': 0.25 * S * ((1 + ULP) ** 3 - 1)}
+    if k == 'flow_up':
+        return {'out': _flow_up_bound(v64['in'], (2 * h, 2 * w))}
+    assert k == 'warp', k
+    assert op['fscale'] in (1.0, 0.5), 'fscale flow is taken to be exact'
+    out = {}
+    q = {name: (qy, qx) for name, qy, qx in warp_queries(op, values, np.float64)}
+    if 'in3' in q:
+        e = _flow_up_bound(v64['in3'], (h, w))
+        out['out2'] = e
+        qy, qx = q['in3']
+        s = op['fscale'] * (1 + ULP)
+        dy, dx = s * e[..., 1] + ULP * np.abs(qy), s * e[..., 0] + ULP * np.abs(qx)
+    else:
+        qy, qx = (np.roll(a, -op.get('flow_brot', 0), axis=0) for a in q['in2'])
+        dy, dx = ULP * np.abs(qy), ULP * np.abs(qx)
+    out['out'] = _warp_bound(np.roll(v64['in'], -op.get('src_brot', 0), axis=0), qy, qx, dy, dx)
+    if 'pack_b' in q:
+        mb = values['pack_b'].shape[0]
+        bound = np.zeros(ref64['img_out'].shape)
+        for c0, name, ims in ((0, 'pack_b', v64['img_in'][:mb]), (3, 'pack_f', v64['img_in'][mb:])):
+            qy, qx = q[name]
+            bound[..., c0:c0 + 3] = _warp_bound(ims, qy, qx, ULP * np.abs(qy), ULP * np.abs(qx))
+        bound[..., 6:10] = ULP * np.abs(ref64['img_out'][..., 6:10])
+        out['img_out'] = bound
+    return out
 
 
 def _conv_concat_to_views(op: dict, x: np.ndarray) -> Dict[str, np.ndarray]:
@@ -261,7 +473,42 @@ def input_sets(op: dict, seed: int, integer_weights: bool) -> List[InputSet]:
         # rounding regime: random normal activations at the dynamic ranges of a trained net (1, 1e2, 1e3: tests/test_gpu_r3.py)
         scale = (1.0, 100.0, 1000.0)[seed % 3]
         vals = {name: (rng.standard_normal((nbv, hv, wv, v['C']), dtype=np.float32) * np.float32(scale)) for name, v, nbv, hv, wv in ivs}
-        return [InputSet(f'normal*{scale:g}', False, vals, [])]
+        if k != 'warp':
+            return [InputSet(f'normal*{scale:g}', False, vals, [])]
+        # a warp's flows: a few pixels, not dyadic; about one pixel in eight up to two frame sizes away
+        flows = [(name, nbv, hv, wv) for name, v, nbv, hv, wv in ivs if name in FLOW_VIEWS + ('in3',)]
+        for name, nbv, hv, wv in flows:
+            f = rng.standard_normal((nbv, hv, wv, 2), dtype=np.float32) * np.float32(3.0)
+            far = rng.random((nbv, hv, wv)) < 0.125
+            f[far] = (rng.uniform(-2, 2, (int(far.sum()), 2)) * (w, h)).astype(np.float32)
+            vals[name] = f / np.float32(_flow_scale(op, name) * (2 if name == 'in3' else 1))
+        sets.append(InputSet(f'normal*{scale:g}', False, dict(vals), []))
+        if any(name in FLOW_VIEWS for name, *_ in flows):
+            ev = dict(vals)
+            for name, nbv, hv, wv in flows:
+                if name in FLOW_VIEWS:
+                    ev[name] = _edge_flows(rng, nbv, hv, wv, _flow_scale(op, name))
+            sets.append(InputSet('edges', False, ev, []))
+        # huge: +-1e6, 2^31, 1e30, 3e38 and, on the flows read directly, +-inf on every fifth flow component; the coarse flow of
+        # the fused resize stops at 8e37 (flow_up_at doubles it and subtracts two such values: 3.2e38 is still finite)
+        hv_ = dict(vals)
+        for name, nbv, hv, wv in flows:
+            mags = HUGE_FLOWS + (np.inf,) if name in FLOW_VIEWS else HUGE_FLOWS[:3] + (8e37,)
+            lattice = np.array([s * m for m in mags for s in (1, -1)], np.float32)
+            f = vals[name].copy().reshape(-1)
+            j = np.arange(0, f.size, 5)
+            f[j] = lattice[(j // 5) % len(lattice)]
+            hv_[name] = f.reshape(vals[name].shape)
+        sets.append(InputSet('huge', False, hv_, [], finite=False))
+        # the flow a fused warp samples the features with IS one of the flows it packs (in2 and pack_b / pack_f share their buffer):
+        # the values of a set are what the views hold once all of them are written, in the order check_op writes them
+        lo, hi = min(extent(v, *s)[0] for _, v, *s in ivs), max(extent(v, *s)[1] for _, v, *s in ivs)
+        tmp = np.zeros(hi - lo, np.float32)
+        for iset in sets:
+            for name, v, *s in ivs:
+                PI._view(tmp, dict(v, off=v['off'] - lo), *s)[...] = iset.values[name]
+            iset.values = {name: PI._view(tmp, dict(v, off=v['off'] - lo), *s).copy() for name, v, *s in ivs}
+        return sets
     if k == 'conv_mfma':
         ct = op['Ctot']
         sets.append(InputSet('dense-int', True, _conv_concat_to_views(op, rng.integers(-3, 4, (nb, h, w, ct)).astype(np.float32)), []))
@@ -364,6 +611,21 @@ class Record:           # one line of the error table
     e_full: float = 0.0     # the backend, on the whole output
 
 
+@dataclasses.dataclass
+class RealRecord:       # one op of the resampling kinds on one real-valued input set
+    op: int
+    tag: str
+    kind: str
+    input_set: str
+    differ: int         # output values that are not the float32 oracle's
+    size: int           # ... of so many
+    has_f64: bool       # the set has finite flows: the float64 bound applies
+    ratio: float = 0.0      # the backend: largest |got - float64| / bound ...
+    e: float = 0.0          # ... |got - float64| there ...
+    bound: float = 0.0      # ... and the bound there
+    ratio_oracle: float = 0.0   # the float32 oracle: largest |oracle - float64| / bound
+
+
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
@@ -405,6 +667,8 @@ class Harness:
         for b in self.bg:
             b[b == 0] = np.float32(1e3)
         self.arena64 = np.zeros(self.n, np.float64)
+        self.arena32 = np.zeros(self.n, np.float32)     # the float32 oracle of the resampling kinds runs here
+        self.real_records: List[RealRecord] = []
         self.cur = None                 # which background the backend holds
         self.records: List[Record] = []
         self.ran_candidates = {}        # op index -> number of candidates run
@@ -438,11 +702,13 @@ class Harness:
         b = next((b for b in self.plan['buffers'] if b['off'] <= off < b['off'] + b['floats']), None)
         return f'arena[{off}]' + (f' = buffer {b["name"]} + {off - b["off"]}' if b else ' (alignment gap)')
 
-    def _reference(self, op, iset: InputSet, ivs, ovs, mag: bool, tap_max: bool = False):
-        """run_op in float64 on the designed inputs -> {output view name: array}.  mag: the magnitude companion.  tap_max (3x3 conv):
-        ... with every tap's weight replaced by the largest magnitude among the nine taps of its (input, output) channel pair."""
+    def _reference(self, op, iset: InputSet, ivs, ovs, mag: bool, tap_max: bool = False, arena=None):
+        """run_op in float64 (arena: in that arena's precision) on the designed inputs -> {output view name: array}.  mag: the magnitude
+        companion.  tap_max (3x3 conv): ... with every tap's weight replaced by the largest magnitude among the nine taps of its
+        (input, output) channel pair."""
+        arena = self.arena64 if arena is None else arena
         for name, v, nb, h, w in ivs:
-            PI._view(self.arena64, v, nb, h, w)[...] = iset.values[name]
+            PI._view(arena, v, nb, h, w)[...] = iset.values[name]
         if tap_max:
             ct, co = op['Ctot'], op['Cout']
             region = self.packed[op['w_off']:op['w_off'] + 9 * ct * co]
@@ -450,11 +716,12 @@ class Harness:
             wv = region.reshape(co, 9, ct)
             wv[...] = np.abs(wv).max(axis=1, keepdims=True)
         try:
-            PI.run_op(op, self.arena64, self.packed, mag=mag)
+            with np.errstate(all='ignore'):     # (the `huge` flows overflow on purpose)
+                PI.run_op(op, arena, self.packed, mag=mag)
         finally:
             if tap_max:
                 region[...] = saved
-        return {name: PI._view(self.arena64, v, nb, h, w).copy() for name, v, nb, h, w in ovs}
+        return {name: PI._view(arena, v, nb, h, w).copy() for name, v, nb, h, w in ovs}
 
     def _sample(self, op, iset: InputSet, rng):
         """(blocks, channels) the restatement is evaluated at: the WHOLE output where that costs at most FULL_COST multiply-adds,
@@ -481,6 +748,44 @@ class Harness:
     # -- one op
     def _first_bad(self, bad):
         return tuple(int(t[0]) for t in np.nonzero(bad))
+
+    def _check_real(self, index, op, iset, cand, got, ref32, ref64, bounds, fails) -> None:
+        """The resampling kinds on real data.  Bits: every output view equals the float32 oracle (run_op on a float32 arena: the
+        kernels' documented arithmetic, one rounding per operation), compared by value (+0 == -0; a NaN differs).  Float64 (input
+        sets with finite flows): |got - ref64| and |oracle - ref64| both within f64_bounds."""
+        differ = size = 0
+        worst = (0.0, 0.0, 0.0, 0.0)      # (e / bound, e, bound) of the backend where that ratio is largest, and the oracle's ratio
+        for name, g in got.items():
+            r32, r64 = ref32[name], ref64[name]
+            bad = ~(g == r32)
+            differ, size = differ + int(bad.sum()), size + bad.size
+            where = lambda i: f'{name}[n {i[0]}, y {i[1]}, x {i[2]}, c {i[3]}]'      # noqa: E731
+            e_got = e_orc = None
+            if bounds is not None:
+                b = bounds[name]
+                e_got, e_orc = np.abs(g.astype(np.float64) - r64), np.abs(r32.astype(np.float64) - r64)
+                e_got[np.isnan(e_got)] = np.inf
+                for who, e in (('got', e_got), ('the float32 oracle', e_orc)):
+                    over = ~(e <= b)
+                    if over.any():
+                        i = self._first_bad(over)
+                        fails.append(Failure('value', index, op['tag'], iset.name, cand, where(i), view=name, coord=i, detail=
+                                             f'{who}: |{(g if who == "got" else r32)[i]!r} - float64 {r64[i]!r}| = {e[i]:.4g} > the a-priori bound {b[i]:.4g} '
+                                             f'({int(over.sum())} of {over.size} exceed it)'))
+                ratio = np.where(b > 0, e_got / np.where(b > 0, b, 1), np.where(e_got > 0, np.inf, 0))
+                j = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+                orc = float(np.where(b > 0, e_orc / np.where(b > 0, b, 1), np.where(e_orc > 0, np.inf, 0)).max())
+                if ratio[j] >= worst[0]:
+                    worst = (float(ratio[j]), float(e_got[j]), float(b[j]), max(worst[3], orc))
+                else:
+                    worst = worst[:3] + (max(worst[3], orc),)
+            if bad.any():
+                i = self._first_bad(bad)
+                against = (f'; against float64 {r64[i]!r}: e(got) = {e_got[i]:.4g}, e(oracle) = {e_orc[i]:.4g}, bound {bounds[name][i]:.4g}'
+                           if bounds is not None else '')
+                fails.append(Failure('value', index, op['tag'], iset.name, cand, where(i), view=name, coord=i, detail=
+                                     f'got {g[i]!r}, the float32 oracle {r32[i]!r} ({int(bad.sum())} of {bad.size} differ){against}'))
+        self.real_records.append(RealRecord(index, op['tag'], op['kind'], iset.name, differ, size, bounds is not None, *worst))
 
     def _run_and_read(self, index, cand, up, touched, ranges, owned, ivs, ovs, iset, fails, check_ownership):
         op = self.plan['ops'][index]
@@ -514,8 +819,6 @@ class Harness:
         conv_like = op['kind'] in ('conv_mfma', 'conv_pw', 'flow_head')
         exact_op = op['kind'] in EXACT_KINDS or fam in EXACT_FAMILIES
         fails: List[Failure] = []
-        if not self.int_w and not conv_like:
-            return fails                # (the rounding regime is for the conv-like ops; the others are exact on integers)
         rng = np.random.default_rng(self.seed * 7919 + index)
         primary = self.cur or 0
         owned = np.zeros(self.n, bool)
@@ -534,8 +837,12 @@ class Harness:
                 PI._view(up, v, nb, h, w)[...] = iset.values[name]
             ref = self._reference(op, iset, ivs, ovs, mag=False)
             exact = iset.exact and exact_op
-            limit = S = rs = None
-            if not exact:
+            real = not iset.exact and op['kind'] in REAL_KINDS
+            limit = S = rs = ref32 = bounds = None
+            if real:
+                ref32 = self._reference(op, iset, ivs, ovs, mag=False, arena=self.arena32)
+                bounds = f64_bounds(op, iset.values, ref) if iset.finite else None
+            elif not exact:
                 sparse = iset.exact and fam in TRANSFORM_TILE
                 S = self._reference(op, iset, ivs, ovs, mag=True, tap_max=sparse)
                 if sparse:
@@ -558,10 +865,22 @@ class Harness:
                 cand = (candidates[k] if candidates is not None else k) if is_conv else -1
                 ncand, got = self._run_and_read(index, cand, up, touched, ranges, owned, ivs, ovs, iset, fails, True)
                 per_cand.append(got)
+                if not self.int_w and conv_like and 'out2' in got:
+                    # the fused epilogue against its unfused op, on what THIS launch wrote: ConvParams::pool_out's stated order
+                    # (pool_vec_kernel's), and the flow head's v = residual + upsampled flow - one float32 operation per statement
+                    want = PI.fo.avg_pool2x2(got['out']) if is_conv else got['out'] + iset.values['in2']
+                    bad = ~(got['out2'] == want)
+                    if bad.any():
+                        i = self._first_bad(bad)
+                        what = 'avg_pool2x2(out)' if is_conv else 'out + in2'
+                        fails.append(Failure('value', index, op['tag'], iset.name, cand, f'out2[n {i[0]}, y {i[1]}, x {i[2]}, c {i[3]}]', view='out2', coord=i, detail=
+                                             f'fused epilogue: got {got["out2"][i]!r}, {what} of the same launch in float32 {want[i]!r} ({int(bad.sum())} of {bad.size} differ)'))
                 if first is None:
                     first = got
                     e_got = e_full = 0.0
-                    for name, g in got.items():
+                    if real:
+                        self._check_real(index, op, iset, cand, got, ref32, ref, bounds, fails)
+                    for name, g in ([] if real else got.items()):
                         r = ref[name]
                         if exact:
                             bad = g.astype(np.float64) != r             # (+0 == -0; a NaN differs)
@@ -594,7 +913,7 @@ class Harness:
                                 i = (int(idx[0][j[0]]), int(idx[1][j[0]]), int(idx[2][j[0]]), int(cs[j[1]]))
                                 fails.append(Failure('value', index, op['tag'], iset.name, cand, f'{name}[n {i[0]}, y {i[1]}, x {i[2]}, c {i[3]}]', view=name, coord=i, detail=
                                                      f'e = {ratio:.2f} > {FACTOR:g} x e_ref {limit:.2f}: got {g[i]!r}, float64 {r[i]!r}, S {s[i]:.4g}'))
-                    if not exact:
+                    if not exact and not real:
                         self.records.append(Record(index, op['tag'], fam, op['ksize'] ** 2 * op['Ctot'], iset.name,
                                                    float('nan') if limit is None else limit, e_got, e_full))
                 else:               # candidates: the bits of the first one

@@ -1,6 +1,7 @@
 """The per-op isolation harness (tests/op_harness.py) without a GPU: over the numpy backend (plan_interp.run_op on a float32 arena)
 every op of a plan passes in the exact regime, and every planted fault is reported by the check that is there for it, at the op and
-the place it was planted.  Also: the two debug entry points are declared and exported, the float64 run_op chain reproduces run_plan,
+the place it was planted - the faults of the resampling kinds (a reordered pool sum, lerps contracted to an fma, a conversion before the
+clamp ...) by the real-valued regime, with on record which of them the small-integer set cannot see.  Also: the two debug entry points are declared and exported, the float64 run_op chain reproduces run_plan,
 and the float32 restatements stay below the a-priori bound of a chunked sum."""
 import os
 import re
@@ -116,6 +117,11 @@ class Faulty(OH.NumpyBackend):
             return super().run(index, candidate)
         op, a, f = self.plan['ops'][index], self.arena, self.fault
         nb, h, w = op['NB'], op['H'], op['W']
+        if f in REAL_FAULTS:
+            n = super().run(index, candidate)
+            with np.errstate(all='ignore'):
+                self._real_fault(op, f)
+            return n
         out = PI._view(a, op['out'], nb, h, w)
         lo, hi = OH.extent(op['out'], nb, h, w)
         if f == 'drop_last_k_chunk':                # the last 8 channels of the first segment never reach the sum
@@ -162,6 +168,82 @@ class Faulty(OH.NumpyBackend):
             y = acc + self.packed[op['b_off']:op['b_off'] + co]
             out[...] = PI.fo.leaky_relu(y) if op['leaky'] else y
         return n
+
+    def _real_fault(self, op, f):
+        """The faults of the resampling kinds (and of a fused pool): the op has run; its `out` (the fused pool: `out2`) is overwritten
+        with what the faulty kernel would have stored."""
+        a, fo = self.arena, PI.fo
+        nb, h, w = op['NB'], op['H'], op['W']
+        if f == 'pool_tree':                        # (a + b) + (c + d) instead of ((a + b) + c) + d
+            x = np.ascontiguousarray(PI._view(a, op['in'], nb, h, w))
+            s = (x[:, 0::2, 0::2] + x[:, 0::2, 1::2]) + (x[:, 1::2, 0::2] + x[:, 1::2, 1::2])
+            PI._view(a, op['out'], nb, h // 2, w // 2)[...] = s * np.float32(0.25)
+        elif f == 'flow_up_fma':                    # a + (b - a) t with the product and the sum rounded once
+            x = np.float32(2) * np.ascontiguousarray(PI._view(a, op['in'], nb, h, w))
+            ylo, yhi, yl = fo._resize_axis_weights(h, 2 * h, np.float32)
+            xlo, xhi, xl = fo._resize_axis_weights(w, 2 * w, np.float32)
+            xl, yl = xl[None, None, :, None], yl[None, :, None, None]
+            top = _fma(x[:, ylo][:, :, xhi] - x[:, ylo][:, :, xlo], xl, x[:, ylo][:, :, xlo])
+            bot = _fma(x[:, yhi][:, :, xhi] - x[:, yhi][:, :, xlo], xl, x[:, yhi][:, :, xlo])
+            PI._view(a, op['out'], nb, 2 * h, 2 * w)[...] = _fma(bot - top, yl, top)
+        elif f == 'pool_before_activation':         # the fused pool of a conv op taken from the values in front of the leaky relu
+            x = PI.conv_input(op, a)
+            ct, co = op['Ctot'], op['Cout']
+            wt = np.ascontiguousarray(self.packed[op['w_off']:op['w_off'] + 9 * ct * co].reshape(co, 3, 3, ct).transpose(1, 2, 3, 0))
+            pre = fo.conv2d_same(x, wt, self.packed[op['b_off']:op['b_off'] + co], None)
+            PI._view(a, op['out2'], nb, h // 2, w // 2)[...] = fo.avg_pool2x2(pre)
+        elif f == 'one_ulp_real':
+            out = PI._view(a, op['out'], nb, h, w)
+            out[0, 1, 1, 0] = np.nextafter(out[0, 1, 1, 0], np.float32(np.inf))
+        else:                                       # a warp: `out` again, from the flow the op used
+            src = np.roll(np.ascontiguousarray(PI._view(a, op['in'], nb, h, w)), -op.get('src_brot', 0), axis=0)
+            if OH._has(op, 'in3'):
+                flow = np.ascontiguousarray(PI._view(a, op['out2'], nb, h, w))
+            else:
+                flow = np.roll(np.ascontiguousarray(PI._view(a, op['in2'], nb, h, w)), -op.get('flow_brot', 0), axis=0)
+            PI._view(a, op['out'], nb, h, w)[...] = _warp_variant(src, np.float32(op['fscale']) * flow, f)
+
+
+def _fma(a, b, c):
+    """float32 a * b + c with the product and the sum in float64, rounded once."""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+REAL_FAULTS = ('pool_tree', 'flow_up_fma', 'pool_before_activation', 'one_ulp_real', 'warp_fma', 'floor_int32', 'clamp_last',
+               'alpha_unclamped', 'swap_flow')
+
+
+def _warp_variant(src, flow, fault):
+    """fo.warp(src, flow) in float32 (flow = (x, y), already scaled) with one fault:
+    warp_fma         every lerp t * (b - a) + a as one fma
+    floor_int32      floor(q) converted to int32 first (out of range: INT32_MIN, what the conversion instruction gives), then clamped
+    clamp_last       the lower index clamped to size - 1 instead of size - 2, the upper corner clamped to size - 1
+    alpha_unclamped  alpha = q - floor, not clipped to [0, 1]
+    swap_flow        the x component of the flow moves y and the other way round"""
+    n, h, w, _ = src.shape
+    if fault == 'swap_flow':
+        flow = flow[..., ::-1]
+    gy, gx = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing='ij')
+    qy, qx = gy[None] + flow[..., 1], gx[None] + flow[..., 0]
+
+    def axis(q, size):
+        fl = np.floor(q)
+        if fault == 'floor_int32':
+            i = np.where(np.isfinite(fl) & (np.abs(fl) < 2.0 ** 31), fl, -2.0 ** 31).astype(np.int64)
+            fl = np.clip(i, 0, size - 2).astype(np.float32)
+        else:
+            fl = np.minimum(np.maximum(fl, 0), size - (1 if fault == 'clamp_last' else 2))
+        al = q - fl
+        if fault != 'alpha_unclamped':
+            al = np.clip(al, 0, 1)
+        lo = fl.astype(np.int64)
+        return lo, np.minimum(lo + 1, size - 1), al[..., None].astype(np.float32)
+    (y0, y1, ay), (x0, x1, ax) = axis(qy, h), axis(qx, w)
+    b = np.arange(n)[:, None, None]
+    lerp = (lambda t, p, q: _fma(t, q - p, p)) if fault == 'warp_fma' else (lambda t, p, q: t * (q - p) + p)
+    top = lerp(ax, src[b, y0, x0], src[b, y0, x1])
+    bot = lerp(ax, src[b, y1, x0], src[b, y1, x1])
+    return lerp(ay, top, bot)
 
 
 def _target(plan, **want):
@@ -256,6 +338,108 @@ def test_one_ulp_in_one_output_is_found(tiny_int):
     fails, op = _planted(plan, packed, 'one_ulp', _target(plan))
     assert {f.check for f in fails} == {'value'}
     assert all(f.coord == (1, 2, 3, 4) and f.view == 'out' for f in fails)
+
+
+# ---- the resampling kinds on real data ----------------------------------------------------------------------------------------------
+UNFUSED = ((2, 32, 48), (('fuse', 0),))      # flow_up, flow_add, pack_flow and the plain warps as ops of their own
+
+
+@pytest.fixture(scope='module')
+def unfused_int():
+    from film_hip.options import TINY
+    return _plan(TINY, UNFUSED[0], True, UNFUSED[1])
+
+
+@pytest.fixture(scope='module')
+def unfused_float():
+    from film_hip.options import TINY
+    return _plan(TINY, UNFUSED[0], False, UNFUSED[1])
+
+
+def _real_ops(plan):
+    return [i for i, op in enumerate(plan['ops']) if op['kind'] in OH.REAL_KINDS]
+
+
+@pytest.mark.parametrize('which', ['tiny', 'unfused'])
+def test_every_resampling_op_passes_on_real_data(which, tiny_float, unfused_float):
+    """plan_interp.run_op in float32 IS the oracle the bits are held to: what this run shows is that the float32 oracle stays within
+    the a-priori float64 bounds on every input set with finite flows, that every set runs, and that the `huge` flows give no NaN."""
+    plan, packed = tiny_float if which == 'tiny' else unfused_float
+    h = OH.Harness(OH.NumpyBackend(plan, packed), plan, packed, False)
+    ops = [i for i in h.distinct_ops() if i in set(_real_ops(plan))]
+    fails = [f for i in ops for f in h.check_op(i)]
+    assert not fails, '\n'.join(map(str, fails[:20]))
+    kinds = {r.kind for r in h.real_records}
+    assert kinds == ({'pool', 'warp'} if which == 'tiny' else set(OH.REAL_KINDS))
+    for r in h.real_records:
+        assert r.differ == 0 and r.size > 0
+        assert r.has_f64 == (r.input_set != 'huge') and (not r.has_f64 or r.ratio == r.ratio_oracle <= 1.0), r
+    sets = lambda tag: {r.input_set.split('*')[0] for r in h.real_records if r.tag == tag}      # noqa: E731
+    for i in ops:
+        op = plan['ops'][i]
+        want = {'normal'} if op['kind'] != 'warp' else {'normal', 'huge'} | (set() if OH._has(op, 'in3') else {'edges'})
+        assert sets(op['tag']) == want, op['tag']
+    # the bounds bind: the oracle uses a good part of them (they are sums of worst cases: a third to nine tenths is what a maximum
+    # over some 1e4 outputs reaches), so that an error of a few ulps would exceed them
+    assert max(r.ratio for r in h.real_records if r.kind == 'warp') > 0.3 and max(r.ratio for r in h.real_records if r.kind == 'pool') > 0.3
+
+
+def test_the_unfaulted_warp_variant_is_the_oracle():
+    rng = np.random.default_rng(3)
+    src = rng.standard_normal((2, 7, 9, 5), dtype=np.float32)
+    flow = rng.standard_normal((2, 7, 9, 2), dtype=np.float32) * np.float32(4)
+    assert np.array_equal(_warp_variant(src, flow, None), PI.fo.warp(src, flow))
+
+
+def _first(plan, kind, **want):
+    return next(i for i, op in enumerate(plan['ops']) if op['kind'] == kind and all(OH._has(op, k) == v for k, v in want.items()))
+
+
+# fault -> (plan, op, the real-valued sets that must report it, whether dense-int reports it)
+REAL_PLANTED = {
+    'pool_tree': ('tiny', lambda p: max(i for i, op in enumerate(p['ops']) if op['kind'] == 'pool'), {'normal'}, False),
+    'pool_tree/c3': ('tiny', lambda p: _first(p, 'pool') + 1, {'normal'}, False),
+    'warp_fma': ('tiny', lambda p: _first(p, 'warp', in3=False, img_out=False), {'normal', 'edges', 'huge'}, False),
+    'warp_fma/fused': ('tiny', lambda p: _first(p, 'warp', in3=True), {'normal', 'huge'}, False),
+    'flow_up_fma': ('unfused', lambda p: _first(p, 'flow_up'), {'normal'}, False),
+    'floor_int32': ('tiny', lambda p: _first(p, 'warp', in3=False, img_out=False), {'huge'}, False),
+    'clamp_last': ('tiny', lambda p: _first(p, 'warp', in3=False, img_out=False), {'normal', 'edges', 'huge'}, False),
+    'alpha_unclamped': ('tiny', lambda p: _first(p, 'warp', in3=False, img_out=True), {'normal', 'edges', 'huge'}, True),
+    'swap_flow': ('unfused', lambda p: _first(p, 'warp', in3=False), {'normal', 'edges', 'huge'}, True),
+    'pool_before_activation': ('tiny', lambda p: next(i for i, op in enumerate(p['ops']) if op['kind'] == 'conv_mfma' and OH._has(op, 'out2')),
+                               {'normal'}, True),
+    'one_ulp_real': ('unfused', lambda p: _first(p, 'warp', in3=False), {'normal', 'edges', 'huge'}, True),
+}
+
+
+@pytest.mark.parametrize('name', list(REAL_PLANTED))
+def test_a_fault_in_a_resampling_kernel_is_found_on_real_data(name, tiny_int, tiny_float, unfused_int, unfused_float):
+    """Each fault is reported by the value check of the real-valued regime, at the op it is planted in and only there, by the input sets
+    listed - and whether the small-integer set of the exact regime sees it is on record: a reordered pool sum and a lerp contracted to
+    an fma have the same bits on dyadic data (the gap the real-valued regime closes), and so has a conversion before the clamp (no
+    integer flow reaches 2^31) and a lower index on the last row (src[size - 1] against 1 * (b - a) + a: equal when that is exact)."""
+    which, pick, want_sets, want_dense = REAL_PLANTED[name]
+    fault = name.split('/')[0]
+    (plan_i, packed_i), (plan_f, packed_f) = (tiny_int, tiny_float) if which == 'tiny' else (unfused_int, unfused_float)
+    t = pick(plan_f)
+    op = plan_f['ops'][t]
+    assert OH.dedup_key(plan_i['ops'][t]) == OH.dedup_key(op)
+    h = OH.Harness(Faulty(plan_f, packed_f, fault, t), plan_f, packed_f, False)
+    fails = h.check_op(t)
+    assert fails and all(f.check == 'value' and f.op == t and f.tag == op['tag'] for f in fails), '\n'.join(map(str, fails[:10]))
+    assert {f.input_set.split('*')[0] for f in fails} == want_sets
+    assert {f.view for f in fails} == ({'out2'} if fault == 'pool_before_activation' else {'out'})
+    if fault == 'pool_before_activation':
+        assert any('fused epilogue' in f.detail for f in fails)
+    elif fault == 'one_ulp_real':
+        assert all(f.coord == (0, 1, 1, 0) for f in fails)
+    elif fault != 'floor_int32':      # a difference in bits names both errors against float64 (the `huge` set has no float64 side)
+        assert any('e(got)' in f.detail and 'e(oracle)' in f.detail for f in fails)
+    for other in (t - 1, t + 1):
+        assert not h.check_op(other), other
+    dense = OH.Harness(Faulty(plan_i, packed_i, fault, t), plan_i, packed_i, True).check_op(t)
+    assert all(f.check == 'value' and f.op == t for f in dense)
+    assert bool(dense) == want_dense, '\n'.join(map(str, dense[:10]))
 
 
 # ---- the references ------------------------------------------------------------------------------------------------------------------

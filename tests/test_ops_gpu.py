@@ -2,9 +2,14 @@
 film_debug_arena / film_debug_run_op - ownership of every float it did not have to write, independence of the background, equal bits
 from every tile candidate, and the value against the float64 reference of the op on the same inputs (bit for bit on small integers
 for the exact families, within 2 x the float32 restatement's own error on the points the restatement is evaluated at otherwise).
+The resampling kinds (pool, flow_up, flow_add, pack_flow, warp) are exact on the small integers too, and on real-valued inputs - random
+fields, flows solved onto every clamp of the warp, flows up to +-inf - every value they store must be the float32 oracle's
+(plan_interp.run_op on a float32 arena), with an a-priori bound against float64 beside it; a fused pool or sum of a conv-like op must
+be its unfused op of what the same launch stored.
 
 Two engines per plan: one with integer weights (op_harness.make_integer_weights: the exact regime and the designed impulse sets), one
-with the seeded synthetic weights (the rounding regime on random normal activations at three dynamic ranges).  Autotune is off: the
+with the seeded synthetic weights (the rounding regime on random normal activations at three dynamic ranges, and the real-valued
+regime of the resampling kinds).  Autotune is off: the
 test runs every candidate of every conv op itself.  FILM_OP_ERRORS=<file> makes the run write its error table there (the source of
 profiles/op_isolation_errors.md).
 
@@ -28,6 +33,8 @@ _T0 = time.time()
 
 _KINDS, _FAMILIES, _CASES_RUN, _TABLE, _COUNTS = set(), set(), set(), [], []
 _RAN = OC.Covered()  # signature (op_cases.signature) and candidate codes of every op that ran
+_RAN_REAL = OC.Covered()    # ... of every op of the resampling kinds that ran on the real-valued input sets
+_REAL_TABLE = []
 _PLANNED = set()    # every conv family any op of any plan of this run uses (from the plan JSON: what the bound libraries hold and select)
 DEFAULT_FAMILIES = {'BUF', 'C3', 'W2D', 'W43', 'FOLD4', 'FOLD2'}
 EXTRA_FAMILIES = {'HALO', 'SPLIT6', 'SPLIT3', 'WINO', 'WINOX3', 'FOLDX3'}
@@ -70,11 +77,14 @@ def _run_case(cfg, key, options, only=None):
                     n = h.n_candidates[i]       # (what film_debug_run_op reported for the op)
                     assert h.ran_candidates[i] == n >= 1, f'{op["tag"]}: {h.ran_candidates[i]} of {n} candidates ran'
                     assert n == len(op['cands']), f'{op["tag"]}: the plan lists {op["cands"]}, film_debug_run_op has {n} candidates'
-                if integer or op['kind'] in ('conv_mfma', 'conv_pw', 'flow_head'):     # (check_op has nothing to run otherwise)
-                    _RAN.add(OC.signature(op), OC.candidates(op))
+                _RAN.add(OC.signature(op), OC.candidates(op))
+                if not integer and op['kind'] in OH.REAL_KINDS:
+                    _RAN_REAL.add(OC.signature(op), OC.candidates(op))
             total = len(plan['ops'])
             for r in h.records:
                 _TABLE.append((_case_id(cfg, key, options), r))
+            for r in h.real_records:
+                _REAL_TABLE.append((_case_id(cfg, key, options), r))
             if integer:
                 _COUNTS.append((_case_id(cfg, key, options), total, len(distinct), len(ops), eng.version()))
                 print(f'{_case_id(cfg, key, options)}: {total} ops in the plan, {len(ops)} of {len(distinct)} distinct ones run')
@@ -152,11 +162,18 @@ def test_coverage_of_the_isolation_run():
     assert _PLANNED <= _FAMILIES, _PLANNED - _FAMILIES
     fams = DEFAULT_FAMILIES | (EXTRA_FAMILIES if extra_built else set())
     assert fams <= _PLANNED, fams - _PLANNED
-    missing = {}
+    missing, missing_real = {}, {}
     for label, op in OC.workload_ops():
         if not _RAN.covers(op):
             missing.setdefault(OC.signature(op), (label, op['tag'], f'{op["H"]}x{op["W"]}'))
+        if op['kind'] in OH.REAL_KINDS and not _RAN_REAL.covers(op):
+            missing_real.setdefault(OC.signature(op), (label, op['tag'], f'{op["H"]}x{op["W"]}'))
     assert not missing, f'{len(missing)} kernel variants of the workload plans did not run in isolation:\n' + OC.format_uncovered(missing)
+    assert not missing_real, (f'{len(missing_real)} variants of the resampling kinds in the workload plans did not run on real-valued inputs:\n' +
+                              OC.format_uncovered(missing_real))
+    # every op of those kinds ran every input set made for it, and no output value differed from the float32 oracle
+    assert _REAL_TABLE and {r.kind for _, r in _REAL_TABLE} == set(OH.REAL_KINDS)
+    assert {r.input_set.split('*')[0] for _, r in _REAL_TABLE if r.kind == 'warp'} == {'normal', 'edges', 'huge'}
     path = os.environ.get('FILM_OP_ERRORS')
     if path:
         _write_table(path)
@@ -183,6 +200,23 @@ def _write_table(path):
         for (fam, K, s), (n, er, eg, ratio, tag, ef) in sorted(rows.items()):
             shown = f'{ratio:.2f}' if er > 0 else '-'
             f.write(f'| {fam} | {K} | {s} | {n} | {er:.2f} | {eg:.2f} | {shown} | {ef:.2f} | {tag} |\n')
+        f.write('\n## The resampling kinds on real-valued inputs\n\n'
+                'pool, flow_up, flow_add, pack_flow and warp against the float32 oracle (plan_interp.run_op on a float32 arena), value for value:\n'
+                '`differ` must be 0.  e = |got - float64| where e / bound is largest, bound = the a-priori bound there (op_harness.f64_bounds: one\n'
+                'rounding per operation of the oracle; required: e <= bound, for the kernel and for the float32 oracle); the `huge` flows include\n'
+                '+-inf and have no float64 column.\n\n'
+                '| kind | input set | ops | values | differ | largest e / bound | e | bound | float32 oracle: largest e / bound |\n|---|---|---|---|---|---|---|---|---|\n')
+        real = {}
+        for case, r in _REAL_TABLE:
+            cur = real.setdefault((r.kind, r.input_set.split('*')[0]), [0, 0, 0, -1.0, 0.0, 0.0, 0.0, r.has_f64])
+            cur[0] += 1
+            cur[1] += r.size
+            cur[2] += r.differ
+            cur[6] = max(cur[6], r.ratio_oracle)
+            if r.ratio > cur[3]:
+                cur[3], cur[4], cur[5] = r.ratio, r.e, r.bound
+        for (kind, s), (n, size, differ, ratio, e, bound, orc, has) in sorted(real.items()):
+            f.write(f'| {kind} | {s} | {n} | {size} | {differ} | ' + (f'{ratio:.3f} | {e:.3g} | {bound:.3g} | {orc:.3f} |\n' if has else '- | - | - | - |\n'))
         f.write('\n## Ops per plan\n\n| plan | ops | distinct ops run | library |\n|---|---|---|---|\n')
         for case, total, distinct, run, ver in _COUNTS:
             f.write(f'| {case} | {total} | {run if run == distinct else f"{run} of {distinct}"} | {ver} |\n')
