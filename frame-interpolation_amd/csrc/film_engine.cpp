@@ -97,6 +97,23 @@ hipStream_t pick_stream(film_t* h, int mem_kind, void* stream) {
   return stream ? (hipStream_t)stream : (mem_kind == FILM_MEM_DEVICE ? (hipStream_t) nullptr : h->stream);
 }
 
+// Chunk size for n independent units with at most maxc per invocation: the largest divisor of n in (maxc / 2, maxc] if
+// there is one, so that every invocation runs the SAME cached plan (16 * 2^k tiles of a 4K recursion with maxc = 15 ->
+// chunks of 8, never a 15 + 1 split that would build, tune and capture a second plan for the remainder); else maxc.
+int balanced_chunk(int n, int maxc) {
+  if (n <= maxc) return n;
+  for (int c = maxc; 2 * c > maxc; --c)
+    if (n % c == 0) return c;
+  return maxc;
+}
+// The retry rule of the chunk loops: a chunk of more than one unit whose workspace did not fit (FILM_ERR_NOMEM from get_plan: nothing was
+// launched) is halved, and the caller goes again from the same place.
+bool halve_on_nomem(int rc, int* chunk) {
+  if (rc != FILM_ERR_NOMEM || *chunk <= 1) return false;
+  *chunk = (*chunk + 1) / 2;
+  return true;
+}
+
 }  // namespace film_internal
 
 using namespace film_internal;
@@ -169,15 +186,6 @@ int ensure_stage(film_t* h, size_t bytes, hipStream_t s) {
   h->stage_bytes = bytes;
   return FILM_OK;
 }
-// Chunk size for n independent units with at most maxc per invocation: the largest divisor of n in (maxc / 2, maxc] if
-// there is one, so that every invocation runs the SAME cached plan (16 * 2^k tiles of a 4K recursion with maxc = 15 ->
-// chunks of 8, never a 15 + 1 split that would build, tune and capture a second plan for the remainder); else maxc.
-int balanced_chunk(int n, int maxc) {
-  if (n <= maxc) return n;
-  for (int c = maxc; 2 * c > maxc; --c)
-    if (n % c == 0) return c;
-  return maxc;
-}
 // Chunk of a sequence of n frame pairs of T tiles each, at most cap pair-tiles per plan: k consecutive pairs x nt tiles, i.e. (k + 1) * nt
 // extracted image-tiles for k * nt pair-tiles.  Most pairs per extracted image = the largest k; ties go to the larger tile range (whole
 // frames first).  Then balanced like balanced_chunk, so that the chunks of a sequence share one cached plan where they can.
@@ -191,13 +199,6 @@ void sequence_chunk(int n, int T, int cap, int* k, int* nt) {
   }
   *k = balanced_chunk(n, std::max(bk, 1));
   *nt = balanced_chunk(T, bt);
-}
-// The retry rule of the chunk loops: a chunk of more than one unit whose workspace did not fit (FILM_ERR_NOMEM from get_plan: nothing was
-// launched) is halved, and the caller goes again from the same place.
-bool halve_on_nomem(int rc, int* chunk) {
-  if (rc != FILM_ERR_NOMEM || *chunk <= 1) return false;
-  *chunk = (*chunk + 1) / 2;
-  return true;
 }
 // Whole frames in HBM for a FILM_MEM_HOST call: the handle's staging buffer as [in_floats of inputs | the result].  open() grows it, upload()
 // copies one input behind those before it and says where the work reads it, `out` is where the work leaves the result, finish() downloads it
@@ -734,6 +735,12 @@ int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* t
   if (pix != FILM_PIX_F32 && pix != FILM_PIX_U8) return fail(h, FILM_ERR_INVALID, "bad pix: FILM_PIX_F32 (0) or FILM_PIX_U8 (1)");
   if (mode == 1 && pix == FILM_PIX_U8) return fail(h, FILM_ERR_INVALID, "film_debug_tile_map: a join writes float32 frames (FILM_PIX_U8 is for the cut only)");
   return debug_tile_map(h, "film_debug_tile_map", mode, pix, frames_dev, tiles_dev, B, H, W, align, block_h, block_w, tile0, ntiles, (hipStream_t)stream);
+}
+
+int film_debug_segment_copy(const int64_t* segs, int n, const float* src_dev, float* dst_dev, void* stream) {
+  static_assert(sizeof(SegmentCopy) == 3 * sizeof(int64_t), "a row of `segs` is a SegmentCopy");
+  const hipError_t e = film_launch_segment_copy(reinterpret_cast<const SegmentCopy*>(segs), n, src_dev, dst_dev, (hipStream_t)stream);   // (the refusals are the launcher's)
+  return e == hipSuccess ? FILM_OK : e == hipErrorInvalidValue ? FILM_ERR_INVALID : FILM_ERR_HIP;
 }
 
 int film_debug_yuv_cut(film_t* h, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h, int block_w,

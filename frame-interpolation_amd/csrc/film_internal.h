@@ -211,6 +211,12 @@ struct FilmStream {
   uint64_t* diff_pin = nullptr;     // ... downloaded here (pinned host memory)
   int64_t dup_stats[12] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // film_stream_dup_info: out[3][4] of the last push (-1: no comparison made) ...
   int dup = 0;                      // ... and whether it was dropped as a duplicate
+  // Tile groups (film_stream.cpp, "tile groups"): a frame whose tiles do not fit one invocation runs as `groups` runs of ONE stream plan of
+  // group_tiles tiles, the last group with the tiles that are left.  Both are decided by film_stream_open and fixed for the stream's life.
+  // groups == 1: the whole frame in one invocation, nothing below is used.
+  int group_tiles = 0, groups = 1;
+  float* carry = nullptr;           // groups > 1: per (group, frame slot) what a pair run reads of an extracted frame - the truth about the carried frame
+  int64_t carry_floats = 0;         // ... its size (allocated again when "block_overlap_*" grows the padded tile)
 };
 
 struct film_handle {
@@ -347,6 +353,8 @@ size_t frame_bytes(int pix, int H, int W);            // ... and its bytes
 int need_device(film_t* h, const char* fn);           // the refusals the compute entry points share (`fn`: the entry point)
 hipStream_t pick_stream(film_t* h, int mem_kind, void* stream);   // the stream a call with `stream` (NULL: the default of its mem_kind) works on
 constexpr int kMaxStreamTimes = 6;                    // option "stream_times": 1 .. this
+int balanced_chunk(int n, int maxc);                  // chunk size for n independent units, at most maxc per invocation
+bool halve_on_nomem(int rc, int* chunk);              // the retry rule of the chunk loops
 
 // ---- film_stream.cpp
 void stream_free(film_t* h);   // the open stream's device buffers go back and it is closed (film_stream_close, film_destroy)
@@ -383,6 +391,7 @@ int max_units(film_t* h, int H, int W, const char* what, const char* advice, int
 // of that many frame slots, B == tiles)
 int plan_build(film_t* h, Plan* P, int B, int H, int W, int tiles = 0, int slots = 0, int left = -1, int right = -1, bool extract = true);
 int64_t limited_buffer_bytes(const Plan* P);                // largest buffer a kernel with whole-buffer 32-bit offsets reads
+void op_views(const OpDesc& op, std::vector<const View*>& rd, std::vector<const View*>& wr);   // the views an op reads / writes
 std::string plan_json(film_t* h, const Plan& P, bool orientation_keys = false);   // (a stream plan: "slot", or "slots", "left", "right")
 
 }  // namespace film_internal

@@ -447,6 +447,24 @@ hipError_t film_launch_frame_histogram(const void* frame, int H, int W, int pix,
 #define FILM_DIFF_THREADS 256
 #define FILM_DIFF_WG_PER_CU 1
 hipError_t film_launch_frame_diff(const void* a, const void* b, int H, int W, int pix, int lo, uint64_t* out, hipStream_t s);
+// One launch copies up to FILM_SEG_MAX segments of floats, segment k: dst[seg[k].dst .. + count) = src[seg[k].src .. + count), bit for bit (a
+// grouped stream's restores and saves: film_stream.cpp).  The table travels in the kernel arguments.  Units are the ALIGNED 16-byte vectors of
+// the destination that hold at least one float of a segment, numbered through all segments (unit0: the prefix sums) and walked by one
+// grid-stride loop with 64-bit indices: a vector wholly inside its segment is one 16-byte store - fed by one 16-byte load where the source
+// is aligned with it, else by four scalar loads -, the first and the last vector of a segment that starts or ends inside one are copied
+// float by float.  Segments may start at any float offset and have any length (0: nothing is copied); they must not overlap each other.
+// The grid is min(what the table needs, FILM_SEG_WG_PER_CU workgroups per compute unit) of FILM_SEG_THREADS lanes.
+#define FILM_SEG_MAX 32
+#define FILM_SEG_THREADS 256
+#define FILM_SEG_WG_PER_CU 8
+struct SegmentCopy { int64_t src, dst, count; };   // float offsets from the two base pointers, floats
+struct SegmentTable {
+  SegmentCopy seg[FILM_SEG_MAX];
+  int64_t unit0[FILM_SEG_MAX + 1];   // unit0[k] .. unit0[k + 1]: the units of segment k (filled by the launcher)
+  int n;
+};
+// n segments (0 .. FILM_SEG_MAX; more: hipErrorInvalidValue, as are a negative offset or count and a pointer that is not 4-byte aligned)
+hipError_t film_launch_segment_copy(const SegmentCopy* segs, int n, const float* src, float* dst, hipStream_t s);
 // fills n floats with a deterministic pseudo-random pattern in [-1, 1) (autotune inputs only)
 hipError_t film_launch_fill_random(float* dst, int64_t n, uint32_t seed, hipStream_t s);
 

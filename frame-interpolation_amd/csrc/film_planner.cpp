@@ -23,6 +23,20 @@ namespace film_internal {
 
 const char* const kKindName[OP_KINDS] = {"conv_mfma", "flow_head", "conv_pw", "pool", "flow_up", "flow_add", "warp", "pack_flow"};
 
+// The views an op reads and the views it writes: what the lane analysis orders, and what tells a grouped stream which buffers a pair run only reads
+void op_views(const OpDesc& op, std::vector<const View*>& rd, std::vector<const View*>& wr) {
+  rd.clear(); wr.clear();
+  if (op.kind == OP_CONV) { for (int i = 0; i < op.nseg; ++i) rd.push_back(&op.seg[i].v); }
+  else { if (op.in.buf >= 0) rd.push_back(&op.in); if (op.in2.buf >= 0) rd.push_back(&op.in2); }
+  if (op.in3.buf >= 0) rd.push_back(&op.in3);
+  if (op.img_in.buf >= 0) rd.push_back(&op.img_in);
+  if (op.pack_b.buf >= 0) { rd.push_back(&op.pack_b); rd.push_back(&op.pack_f); }
+  if (op.out.buf >= 0 && op.pw_out.buf < 0) wr.push_back(&op.out);
+  if (op.pw_out.buf >= 0) wr.push_back(&op.pw_out);
+  if (op.out2.buf >= 0) wr.push_back(&op.out2);
+  if (op.img_out.buf >= 0) wr.push_back(&op.img_out);
+}
+
 namespace {
 // ---- kernel decisions ----------------------------------------------------------------------------------------------------------
 // What the rules below decide from: the layer, the level and the layout of the buffers the convolution reads and writes (a property
@@ -683,16 +697,11 @@ struct Planner {
   }
   static bool overlap(const Access& a, const Access& b) { return a.buf == b.buf && a.c0 < b.c1 && b.c0 < a.c1; }
   void accesses(const OpDesc& op, std::vector<Access>& rd, std::vector<Access>& wr) const {
+    std::vector<const View*> r, w;
+    op_views(op, r, w);
     rd.clear(); wr.clear();
-    if (op.kind == OP_CONV) { for (int i = 0; i < op.nseg; ++i) rd.push_back(access(op.seg[i].v)); }
-    else { if (op.in.buf >= 0) rd.push_back(access(op.in)); if (op.in2.buf >= 0) rd.push_back(access(op.in2)); }
-    if (op.in3.buf >= 0) rd.push_back(access(op.in3));
-    if (op.img_in.buf >= 0) rd.push_back(access(op.img_in));
-    if (op.pack_b.buf >= 0) { rd.push_back(access(op.pack_b)); rd.push_back(access(op.pack_f)); }
-    if (op.out.buf >= 0 && op.pw_out.buf < 0) wr.push_back(access(op.out));
-    if (op.pw_out.buf >= 0) wr.push_back(access(op.pw_out));
-    if (op.out2.buf >= 0) wr.push_back(access(op.out2));
-    if (op.img_out.buf >= 0) wr.push_back(access(op.img_out));
+    for (const View* v : r) rd.push_back(access(*v));
+    for (const View* v : w) wr.push_back(access(*v));
   }
   // For every op: the LAST op of the other lane it conflicts with (RAW, WAR or WAW on overlapping channels of a
   // buffer).  Waiting for the last one is enough: a lane executes in program order.  For the same reason a wait is

@@ -9,7 +9,7 @@ using namespace film_internal;
 // The stream's device buffers go back and it is closed.  Work that may still use them is the caller's to wait for.
 void film_internal::stream_free(film_t* h) {
   FilmStream& fs = h->fs;
-  for (void* p : {fs.keep, fs.keep2, (void*)fs.result, (void*)fs.result8, (void*)fs.hist_dev, (void*)fs.diff_dev})
+  for (void* p : {fs.keep, fs.keep2, (void*)fs.result, (void*)fs.result8, (void*)fs.hist_dev, (void*)fs.diff_dev, (void*)fs.carry})
     if (p) (void)hipFree(p);
   if (fs.hist_pin) (void)hipHostFree(fs.hist_pin);
   if (fs.diff_pin) (void)hipHostFree(fs.diff_pin);
@@ -29,6 +29,13 @@ hipError_t stream_cut(const void* frame, int pix, TileMapParams tp, const Plan* 
   tp.tile0 = 0; tp.ntiles = tp.bh * tp.bw;
   tp.src = (const float*)frame;
   tp.dst = P->at("img0") + (int64_t)slot * tp.ntiles * tp.TH * tp.TW * 3;
+  return film_launch_cut_tiles(tp, pix, s);
+}
+// ... its tiles [tile0, tile0 + ntiles) to `dst` (a tile group: into the group plan's slot, or into the carry)
+hipError_t stream_cut_range(const void* frame, int pix, TileMapParams tp, int tile0, int ntiles, float* dst, hipStream_t s) {
+  tp.tile0 = tile0; tp.ntiles = ntiles;
+  tp.src = (const float*)frame;
+  tp.dst = dst;
   return film_launch_cut_tiles(tp, pix, s);
 }
 
@@ -154,6 +161,17 @@ int stream_duplicate(film_t* h, const void* frame, bool host, hipStream_t s, int
   return FILM_OK;
 }
 
+// The joined float32 frame of a result at p.joined -> its quantised frame (none for a float32 stream) -> the host (a host push: queued, not waited for)
+int stream_quantise(film_t* h, const StreamFrames& fr, const StreamFrames::Place& p, hipStream_t s) {
+  const FilmStream& fs = h->fs;
+  if (p.quant && pix_is_yuv(fs.pix))
+    HIPCHK(h, film_launch_rgb_to_yuv(p.joined, p.quant, fs.H, fs.W, fs.pix, s));
+  else if (p.quant)
+    HIPCHK(h, film_launch_to_uint8(p.joined, static_cast<uint8_t*>(p.quant), (int64_t)fr.nv, s));
+  if (p.host) HIPCHK(h, hipMemcpyAsync(p.host, p.quant ? p.quant : (void*)p.joined, fr.fb, hipMemcpyDeviceToHost, s));
+  return FILM_OK;
+}
+
 // One result of a push, the "out" tiles of the pair run Q, delivered to `p`: joined in float32 by the kernels of film_interpolate, then
 // quantised by film_to_uint8's kernel for an 8-bit RGB stream, by film_to_yuv420's for a 4:2:0 stream (8-bit or 10-bit), then downloaded
 // (a host push: queued, not waited for); feed >= 0: a result that has children is cut from the float32 frame - never from the quantised
@@ -163,13 +181,236 @@ int stream_deliver(film_t* h, const Plan* Q, const TileMapParams& tp, const Stre
   TileMapParams j = tp;
   j.tile0 = 0; j.ntiles = tp.bh * tp.bw; j.src = Q->at("out"); j.dst = p.joined;
   HIPCHK(h, film_launch_join_tiles(j, s));
-  if (p.quant && pix_is_yuv(fs.pix))
-    HIPCHK(h, film_launch_rgb_to_yuv(p.joined, p.quant, fs.H, fs.W, fs.pix, s));
-  else if (p.quant)
-    HIPCHK(h, film_launch_to_uint8(p.joined, static_cast<uint8_t*>(p.quant), (int64_t)fr.nv, s));
-  if (p.host) HIPCHK(h, hipMemcpyAsync(p.host, p.quant ? p.quant : (void*)p.joined, fr.fb, hipMemcpyDeviceToHost, s));
+  int rc = stream_quantise(h, fr, p, s);
+  if (rc) return rc;
   if (feed >= 0) HIPCHK(h, stream_cut(p.joined, FILM_PIX_F32, tp, Q, feed, s));
   return FILM_OK;
+}
+
+// ---- tile groups: a frame of more tiles than one invocation takes --------------------------------------------------------------------
+// Such a stream runs its frame as G groups of n tiles through ONE stream plan of n tiles, group after group (the last group: the r <= n
+// tiles that are left, on the same plan - its surplus images compute on what the group before left there, nobody reads them).  The carry,
+// a device buffer of the stream's own, holds for every (group, frame slot) what a pair run reads of an extracted frame: before a group's
+// run the slots it reads are copied from the carry into the plan, behind a run that extracted a frame that slot is copied out.  Every
+// run is an ordinary run of an ordinary orientation, so the bits are those of the one-group stream.
+//
+// The carry buffers are the per-image buffers (slots * n images) that the ops of a pair run read and none of them writes - the image and
+// feature pyramids.  Images are the outer dimension, so the images of one slot are one contiguous piece of each buffer, and the state of a
+// (group, slot) is one segment per buffer.  The carry lays the segments out [group][slot][buffer], r * per_image floats each.
+struct CarryLayout {
+  std::vector<int> bufs;            // the carry buffers (indices into Plan::bufs), in plan order
+  std::vector<int64_t> per_image;   // floats of one image of each ...
+  int64_t image_floats = 0;         // ... and of all of them
+  int img0 = -1;                    // where the cut's target, "img0", is among them
+  int tiles = 0, n = 0, slots = 0;  // tiles of the frame, of a group (= of the plan), frame slots
+  int groups() const { return (tiles + n - 1) / n; }
+  int ntiles(int g) const { return std::min(n, tiles - g * n); }
+  int64_t floats() const { return (int64_t)slots * tiles * image_floats; }
+  int64_t carry_off(int g, int slot, size_t i) const {   // of buffer i of (group g, slot)
+    int64_t o = ((int64_t)g * n * slots + (int64_t)slot * ntiles(g)) * image_floats;
+    for (size_t k = 0; k < i; ++k) o += ntiles(g) * per_image[k];
+    return o;
+  }
+  int64_t plan_off(const Plan* P, int slot, size_t i) const { return P->bufs[(size_t)bufs[i]].off + (int64_t)slot * n * per_image[i]; }
+  // the segments of (group g, slot) - all of them, or only the img0 tiles a feed-cut left - appended to `out`: carry -> plan, or plan -> carry
+  void segments(const Plan* P, int g, int slot, bool img0_only, bool restore, std::vector<SegmentCopy>* out) const {
+    for (size_t i = 0; i < bufs.size(); ++i) {
+      if (img0_only && (int)i != img0) continue;
+      const int64_t c = carry_off(g, slot, i), p = plan_off(P, slot, i);
+      out->push_back(restore ? SegmentCopy{c, p, ntiles(g) * per_image[i]} : SegmentCopy{p, c, ntiles(g) * per_image[i]});
+    }
+  }
+};
+int carry_layout(film_t* h, Plan* P0, int tiles, CarryLayout* L) {
+  Plan* Q = nullptr;
+  int rc = plan_orientation(h, P0, 1, 0, false, &Q);   // a pair run and nothing else
+  if (rc) return rc;
+  std::vector<char> rd(Q->bufs.size(), 0), wr(Q->bufs.size(), 0);
+  std::vector<const View*> r, w;
+  for (const OpDesc& op : Q->ops) {
+    op_views(op, r, w);
+    for (const View* v : r) rd[(size_t)v->buf] = 1;
+    for (const View* v : w) wr[(size_t)v->buf] = 1;
+  }
+  *L = CarryLayout{};
+  L->tiles = tiles; L->n = P0->tiles; L->slots = P0->slots;
+  for (size_t b = 0; b < Q->bufs.size(); ++b) {
+    const Buffer& B = Q->bufs[b];
+    if (B.N != P0->slots * P0->tiles || !rd[b] || wr[b]) continue;
+    if (B.planar) return fail(h, FILM_ERR_INVALID, "tile groups: the images of a slot of '%s' are no contiguous piece of it", B.name.c_str());
+    if (B.name == "img0") L->img0 = (int)L->bufs.size();
+    L->bufs.push_back((int)b);
+    L->per_image.push_back((int64_t)B.H * B.W * B.C);
+    L->image_floats += L->per_image.back();
+  }
+  if (L->img0 < 0) return fail(h, FILM_ERR_INVALID, "tile groups: a pair run does not read 'img0'");
+  return FILM_OK;
+}
+
+// stream_schedule's steps, each expanded into the runs of its groups: outer = the steps, inner = the groups - a fed-back frame is the JOINED
+// frame (cross-faded when "block_overlap_*" is set), which exists only when all groups of its step have run.  Per run:
+//   restore  the slots copied whole from the carry into the plan in front of it: `left` of a pair run, and `right` when the run does not extract it
+//   cut      where the frame it extracts comes from: CUT_KEEP - the pushed frame (slots 0 / 1), its tiles are cut from the stream's copy into the
+//            plan; CUT_CARRY - a fed-back frame (slot 1 + depth), whose img0 tiles its parent's feed-cut left in the carry: they are restored;
+//            one group (n >= tiles): CUT_PLAN - they are in the plan already
+//   save     the slot copied whole from the plan into the carry behind it: `right` of a run that extracted it (-1: none)
+//   join     a pair run's tiles go into the step's float32 frame; behind the `last` group's the frame is quantised and delivered, and one that
+//            has children is cut, group by group, into the img0 segments of slot `feed` of the carry
+// One group: the steps as they are, no restore, no save (what the one-group push does).
+enum { CUT_NONE = 0, CUT_KEEP, CUT_CARRY, CUT_PLAN };
+struct GroupStep {
+  StreamStep t;
+  int step, group, tile0, ntiles;
+  int restore[2], nrestore;
+  int cut, save;
+  bool last;
+};
+std::vector<GroupStep> group_schedule(const std::vector<StreamStep>& steps, int tiles, int n) {
+  const int G = (tiles + n - 1) / n;
+  std::vector<GroupStep> v;
+  for (size_t i = 0; i < steps.size(); ++i) {
+    const StreamStep& t = steps[i];
+    for (int g = 0; g < G; ++g) {
+      GroupStep q{t, (int)i, g, g * n, std::min(n, tiles - g * n), {-1, -1}, 0, CUT_NONE, -1, g == G - 1};
+      if (t.extract) q.cut = t.right < 2 ? CUT_KEEP : G > 1 ? CUT_CARRY : CUT_PLAN;
+      if (G > 1) {
+        if (t.pair) q.restore[q.nrestore++] = t.left;
+        if (t.pair && !t.extract) q.restore[q.nrestore++] = t.right;
+        if (t.extract) q.save = t.right;
+      }
+      v.push_back(q);
+    }
+  }
+  return v;
+}
+
+// One launch per FILM_SEG_MAX segments (a restore of two slots of the published model: 28)
+int copy_segments(film_t* h, const std::vector<SegmentCopy>& segs, const float* src, float* dst, hipStream_t s) {
+  for (size_t i = 0; i < segs.size(); i += FILM_SEG_MAX)
+    HIPCHK(h, film_launch_segment_copy(segs.data() + i, (int)std::min<size_t>(FILM_SEG_MAX, segs.size() - i), src, dst, s));
+  return FILM_OK;
+}
+
+// The steps of a grouped push, run: `steps` is stream_schedule's list - of a primed push, or the one extraction-only step of a first push
+// and of a re-extraction.  The runs of one call add up in the profile, as the pair runs of a one-group push do.
+int run_group_steps(film_t* h, Plan* P0, const CarryLayout& L, const TileMapParams& tp, const std::vector<StreamStep>& steps, void* mid, bool host,
+                    hipStream_t s, int* made) {
+  FilmStream& fs = h->fs;
+  AppendProfile append{h};
+  const StreamFrames fr(fs.pix, fs.H, fs.W, fs.times);
+  const int64_t tile_floats = (int64_t)tp.TH * tp.TW * 3;
+  std::vector<SegmentCopy> segs;
+  for (const GroupStep& g : group_schedule(steps, L.tiles, L.n)) {
+    const StreamStep& t = g.t;
+    Plan* Q = nullptr;
+    int rc = plan_orientation(h, P0, t.left, t.right, t.extract != 0, &Q);
+    if (rc) return rc;
+    segs.clear();
+    for (int i = 0; i < g.nrestore; ++i) L.segments(Q, g.group, g.restore[i], false, true, &segs);
+    if (g.cut == CUT_CARRY) L.segments(Q, g.group, t.right, true, true, &segs);
+    if ((rc = copy_segments(h, segs, fs.carry, Q->arena, s))) return rc;
+    if (g.cut == CUT_KEEP)
+      HIPCHK(h, stream_cut_range(fs.keep, fs.pix, tp, g.tile0, g.ntiles, Q->at("img0") + (int64_t)t.right * L.n * tile_floats, s));
+    if ((rc = run_plan(h, Q, s, t.pair ? SIZE_MAX : Q->n_extract))) return rc;
+    h->profile_append = true;
+    if (g.save >= 0) {
+      segs.clear();
+      L.segments(Q, g.group, g.save, false, false, &segs);
+      if ((rc = copy_segments(h, segs, Q->arena, fs.carry, s))) return rc;
+    }
+    if (!t.pair) continue;
+    const size_t k = (size_t)__builtin_popcountll(fs.mask & (((uint64_t)1 << (t.index - 1)) - 1));   // selected positions before this one
+    const StreamFrames::Place p = t.deliver ? fr.place(fs, mid, host, k) : StreamFrames::fed_only(fs);
+    TileMapParams j = tp;   // (overlapped tiles: the joins of a frame add up in tile order on this one stream, group after group)
+    j.tile0 = g.tile0; j.ntiles = g.ntiles; j.src = Q->at("out"); j.dst = p.joined;
+    HIPCHK(h, film_launch_join_tiles(j, s));
+    if (!g.last) continue;
+    if ((rc = stream_quantise(h, fr, p, s))) return rc;
+    // the step's frame is ONE buffer that the next step's joins reuse: a frame with children goes to the carry now, never from the quantised one
+    for (int c = 0; t.feed >= 0 && c < L.groups(); ++c)
+      HIPCHK(h, stream_cut_range(p.joined, FILM_PIX_F32, tp, c * L.n, L.ntiles(c), fs.carry + L.carry_off(c, t.feed, (size_t)L.img0), s));
+    *made += t.deliver;
+  }
+  return FILM_OK;
+}
+
+// The carry of the frame geometry `tp`, allocated - or allocated again, when "block_overlap_*" grew the padded tile: such a change re-extracts
+// every group anyway
+int ensure_carry(film_t* h, const CarryLayout& L, const Plan* P0) {
+  FilmStream& fs = h->fs;
+  if (fs.carry && fs.carry_floats >= L.floats()) return FILM_OK;
+  if (fs.carry) {
+    HIPCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipFree(fs.carry));
+    fs.carry = nullptr; fs.carry_floats = 0;
+  }
+  const size_t bytes = (size_t)L.floats() * sizeof(float);   // (64-bit: 10 GB for a 4K frame's two slots)
+  if (hipMalloc((void**)&fs.carry, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    fs.carry = nullptr;
+    return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's carry failed: workspace %lld bytes, carry %lld bytes (%d frame slots of %d tiles), %d tiles per group, %d groups",
+                (long long)(P0->arena_floats * (int64_t)sizeof(float)), (long long)bytes, L.slots, L.tiles, L.n, L.groups());
+  }
+  fs.carry_floats = L.floats();
+  return FILM_OK;
+}
+
+// film_stream_push of a stream of more than one group, behind the duplicate rule: the one-group push, step for step, over the carry.  The
+// carry is the truth about the carried frame: a plan that was evicted and rebuilt needs no re-extraction; a changed tile geometry
+// re-extracts every group from the stream's copy into the carry.
+int push_groups(film_t* h, const void* frame, void* mid, int* produced, bool host, hipStream_t s, int dup_hi, Unprime* unprime) {
+  FilmStream& fs = h->fs;
+  TileMapParams tp{};
+  tp.B = 1;
+  int rc = tile_geometry(h, fs.H, fs.W, fs.block_h, fs.block_w, fs.align, &tp);   // ("block_overlap_*" as they are NOW)
+  if (rc) return rc;
+  Plan* P0 = nullptr;
+  rc = get_plan(h, fs.group_tiles, tp.TH, tp.TW, true, &P0, fs.group_tiles, fs.times + 1);   // (n is the stream's: "max_batch" as it is now does not enter)
+  if (rc) return rc;
+  CarryLayout L;
+  if ((rc = carry_layout(h, P0, tp.bh * tp.bw, &L)) || (rc = ensure_carry(h, L, P0))) return rc;
+  int made = 0;
+  if (fs.primed && !same_geometry(fs.geo, tp) && (rc = run_group_steps(h, P0, L, tp, stream_schedule(fs.times, fs.slot, 0), nullptr, host, s, &made))) return rc;
+  if (dup_hi >= 0) std::swap(fs.keep, fs.keep2);   // (behind the re-extraction, which reads the carried frame's copy)
+  else HIPCHK(h, hipMemcpyAsync(fs.keep, frame, frame_bytes(fs.pix, fs.H, fs.W), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  const int scene_k = h->opt_scene_cut;
+  bool cut = false;
+  if (scene_k > 0 && (rc = stream_scene_cut(h, s, scene_k, &cut))) return rc;
+  const bool primed = fs.primed && !cut;
+  const int slot = primed ? 1 - fs.slot : 0;
+  // a first push is the push of an empty selection: the extraction of the pushed frame, group by group, into the carry
+  if ((rc = run_group_steps(h, P0, L, tp, stream_schedule(fs.times, slot, primed ? fs.mask : 0), mid, host, s, &made))) return rc;
+  if (host) HIPCHK(h, hipStreamSynchronize(s));
+  *produced = made;
+  fs.primed = true; fs.slot = slot; fs.plan_id = P0->id; fs.geo = tp;
+  fs.hist_valid = scene_k > 0; fs.cut = cut ? 1 : 0;
+  unprime->armed = false;
+  return FILM_OK;
+}
+
+// film_stream_group_schedule_json: group_schedule's list, and in front of it the carry buffers of the plan the groups run on
+std::string group_schedule_json(const Plan* P, const CarryLayout& L, int times, int slot, uint64_t mask) {
+  static const char* const kCut[] = {"none", "keep", "carry", "plan"};
+  const int G = L.groups();
+  std::ostringstream o;
+  o << "{\"times\":" << times << ",\"slot\":" << slot << ",\"slots\":" << times + 1 << ",\"mask\":" << mask << ",\"produced\":" << __builtin_popcountll(mask)
+    << ",\"tiles\":" << L.tiles << ",\"group_tiles\":" << L.n << ",\"groups\":" << G << ",\"carry\":[";
+  for (size_t i = 0; i < L.bufs.size(); ++i) o << (i ? "," : "") << "\"" << P->bufs[(size_t)L.bufs[i]].name << "\"";
+  o << "],\"steps\":[";
+  const std::vector<GroupStep> steps = group_schedule(stream_schedule(times, slot, mask), L.tiles, L.n);
+  for (size_t i = 0; i < steps.size(); ++i) {
+    const GroupStep& g = steps[i];
+    const StreamStep& t = g.t;
+    o << (i ? "," : "") << "{\"step\":" << g.step << ",\"group\":" << g.group << ",\"tile0\":" << g.tile0 << ",\"ntiles\":" << g.ntiles << ",\"left\":" << t.left
+      << ",\"right\":" << t.right << ",\"extract\":" << t.extract << ",\"index\":" << t.index << ",\"depth\":" << t.depth << ",\"feed\":" << t.feed
+      << ",\"deliver\":" << (t.deliver ? 1 : 0) << ",\"run\":\"" << (t.pair ? "pair" : "extract") << "\",\"restore\":[";
+    for (int k = 0; k < g.nrestore; ++k) o << (k ? "," : "") << g.restore[k];
+    o << "],\"cut\":\"" << kCut[g.cut] << "\",\"save\":" << g.save << ",\"join\":[";
+    if (t.pair) o << g.tile0 << "," << g.ntiles;
+    o << "],\"last\":" << (g.last ? 1 : 0) << ",\"feed_to\":\"" << (t.feed < 0 || !g.last ? "none" : G > 1 ? "carry" : "plan") << "\"}";
+  }
+  o << "]}";
+  return o.str();
 }
 
 int check_schedule_query(film_t* h, int times, int slot) {
@@ -247,6 +488,51 @@ int film_stream_select_schedule_json(film_t* h, int times, int slot, uint64_t ma
   return copy_out_string(h, schedule_json(times, slot, &mask), buf, cap, needed);
 }
 
+int film_stream_group_schedule_json(film_t* h, int tiles, int H, int W, int times, int slot, uint64_t mask, int group_tiles, char* buf, int64_t cap,
+                                    int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  if (tiles < 1 || group_tiles < 1) return fail(h, FILM_ERR_INVALID, "tiles and group_tiles must be positive");
+  int rc = check_schedule_query(h, times, slot);
+  if (rc == FILM_OK) rc = check_mask(h, times, mask);
+  if (rc) return rc;
+  const int n = std::min(tiles, group_tiles);
+  if (n >= 1 << 30) return fail(h, FILM_ERR_INVALID, "batch too large (2*B*H*W must fit int32)");
+  Plan* P = nullptr;
+  CarryLayout L;
+  if ((rc = get_plan(h, n, H, W, false, &P, n, times + 1)) || (rc = carry_layout(h, P, tiles, &L))) return rc;
+  return copy_out_string(h, group_schedule_json(P, L, times, slot, mask), buf, cap, needed);
+}
+
+int film_stream_layout_json(film_t* h, char* buf, int64_t cap, int64_t* needed) {
+  if (!h) return FILM_ERR_INVALID;
+  const FilmStream& fs = h->fs;
+  if (!fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
+  TileMapParams tp{};
+  tp.B = 1;
+  int rc = tile_geometry(h, fs.H, fs.W, fs.block_h, fs.block_w, fs.align, &tp);   // ("block_overlap_*" as they are NOW)
+  if (rc) return rc;
+  Plan* P = nullptr;
+  CarryLayout L;
+  const bool grouped = fs.groups > 1;   // (one group: no carry, nothing to derive)
+  if ((rc = get_plan(h, fs.group_tiles, tp.TH, tp.TW, false, &P, fs.group_tiles, fs.times + 1)) || (grouped && (rc = carry_layout(h, P, tp.bh * tp.bw, &L)))) return rc;
+  std::ostringstream o;
+  o << "{\"tiles\":" << tp.bh * tp.bw << ",\"groups\":" << fs.groups << ",\"group_tiles\":" << fs.group_tiles << ",\"slots\":" << fs.times + 1
+    << ",\"tile_h\":" << tp.TH << ",\"tile_w\":" << tp.TW << ",\"workspace_bytes\":" << P->arena_floats * (int64_t)sizeof(float) << ",\"workspace_resident\":" << (P->arena ? 1 : 0)
+    << ",\"carry_bytes\":" << (grouped ? L.floats() * (int64_t)sizeof(float) : 0) << ",\"carry\":[";
+  for (size_t i = 0; grouped && i < L.bufs.size(); ++i) o << (i ? "," : "") << "\"" << P->bufs[(size_t)L.bufs[i]].name << "\"";
+  o << "],\"states\":[";
+  for (int g = 0; grouped && g < fs.groups; ++g)
+    for (int sl = 0; sl <= fs.times; ++sl) {
+      o << (g || sl ? "," : "") << "{\"group\":" << g << ",\"slot\":" << sl << ",\"tile0\":" << g * L.n << ",\"ntiles\":" << L.ntiles(g) << ",\"segments\":[";
+      for (size_t i = 0; i < L.bufs.size(); ++i)
+        o << (i ? "," : "") << "{\"buf\":\"" << P->bufs[(size_t)L.bufs[i]].name << "\",\"plan_off\":" << L.plan_off(P, sl, i) << ",\"carry_off\":" << L.carry_off(g, sl, i)
+          << ",\"floats\":" << L.ntiles(g) * L.per_image[i] << "}";
+      o << "]}";
+    }
+  o << "]}";
+  return copy_out_string(h, o.str(), buf, cap, needed);
+}
+
 int film_stream_select(film_t* h, uint64_t mask) {
   if (!h) return FILM_ERR_INVALID;
   if (!h->fs.open) return fail(h, FILM_ERR_STATE, "no open stream (film_stream_open)");
@@ -272,13 +558,13 @@ int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_
   rc = max_units(h, tp.TH, tp.TW, "tile", "use a finer block_shape", &tmax);
   if (rc) return rc;
   const int T = tp.bh * tp.bw;
-  // a stream neither chunks a frame nor halves on out-of-memory: the carried features of ALL tiles live in one plan
-  if (T > tmax)
-    return fail(h, FILM_ERR_INVALID, "a stream runs the whole frame in one model invocation: its %d tiles of %d x %d exceed the %d tiles one invocation "
-                "may take (64 GiB / 60 %% of the free HBM of workspace, 4 GiB per 32-bit addressed buffer, \"max_batch\") - use a finer block_shape", T, tp.TH, tp.TW, tmax);
   const int times = h->opt_stream_times;   // fixed for this stream's life
+  // The whole frame in one invocation where that fits (one group: the stream it always was); else tile groups of n tiles through the plan
+  // of n tiles, n halved while its workspace does not fit.  Only a single tile that is too large is refused.
+  int n = balanced_chunk(T, tmax);
   Plan* P = nullptr;
-  rc = get_plan(h, T, tp.TH, tp.TW, true, &P, T, times + 1);   // (built and tuned now; FILM_ERR_NOMEM when the workspace does not fit)
+  do rc = get_plan(h, n, tp.TH, tp.TW, true, &P, n, times + 1);   // (built and tuned now; FILM_ERR_NOMEM when the workspace does not fit)
+  while (halve_on_nomem(rc, &n));
   if (rc) return rc;
   FilmStream& fs = h->fs;
   const StreamFrames fr(pix, H, W, times);
@@ -291,8 +577,13 @@ int film_stream_open(film_t* h, int H, int W, int align, int block_h, int block_
     return fail(h, FILM_ERR_NOMEM, "hipMalloc of the stream's frame buffers (%.1f MB, stream_times = %d) failed",
                 (fr.fb + fr.result_bytes() + fr.result8_bytes()) * 1e-6, times);
   }
-  fs.open = true;
   fs.times = times;
+  fs.group_tiles = n; fs.groups = (T + n - 1) / n;   // fixed for this stream's life, whatever "max_batch" says later
+  if (fs.groups > 1) {
+    CarryLayout L;
+    if ((rc = carry_layout(h, P, T, &L)) || (rc = ensure_carry(h, L, P))) { stream_free(h); return rc; }
+  }
+  fs.open = true;
   fs.mask = full_mask(times);
   fs.H = H; fs.W = W; fs.align = align; fs.block_h = block_h; fs.block_w = block_w; fs.pix = pix;
   return FILM_OK;
@@ -362,6 +653,7 @@ int film_stream_push(film_t* h, const void* frame, void* mid, int* produced, int
       return FILM_OK;
     }
   }
+  if (fs.groups > 1) return push_groups(h, frame, mid, produced, host, s, dup_hi, &unprime);
   TileMapParams tp{};
   tp.B = 1;
   rc = tile_geometry(h, fs.H, fs.W, fs.block_h, fs.block_w, fs.align, &tp);   // ("block_overlap_*" as they are NOW)

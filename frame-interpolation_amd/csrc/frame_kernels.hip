@@ -1,5 +1,5 @@
 // frame_kernels.hip -- frame I/O: the kernels that move pixels between the caller's frames and the tiles a plan works on (gfx950, wave64).
-// None of them is an op of a plan; film_engine.cpp and film_stream.cpp call the four launchers at the end of this file and film_launch_frame_histogram / film_launch_frame_diff, which stand beside their kernels.
+// None of them is an op of a plan; film_engine.cpp and film_stream.cpp call the four launchers at the end of this file and film_launch_frame_histogram / film_launch_frame_diff / film_launch_segment_copy, which stand beside their kernels.
 //
 //   frame_to_tiles<OVERLAP>             _pad_to_align + image_to_patches, float32 frames    eval/interpolator.py:30-63, :66-104
 //   frame_u8_to_tiles<OVERLAP>          the same on 8-bit RGB frames: float32(byte) / 255   eval/util.py read_image
@@ -10,6 +10,7 @@
 //   rgb_to_yuv<LAYOUT>                  float32 RGB -> the planes of one Y'CbCr frame       the same three sections
 //   frame_histogram<LAYOUT>            3 x 256 counters of a frame's 8-bit sample codes    include/film_hip.h, "Scene cuts"
 //   frame_diff<LAYOUT>                 the 8 x 8 block SADs of two frames, per plane       include/film_hip.h, "Duplicate frames"
+//   segment_copy                       a table of float segments, device to device         film_kernels.h, SegmentTable
 //
 // OVERLAP: the tile's content is the patch grown by the overlap, from film_tile_origin (options "block_overlap_h" / "block_overlap_w").
 // LAYOUT: a FILM_PIX_* value.  The Y'CbCr cut and quantiser are written once over YuvLayout<LAYOUT>, which states what a layout decides: the sample
@@ -871,6 +872,60 @@ hipError_t film_launch_frame_diff(const void* a, const void* b, int H, int W, in
               : pix_is_yuv10(pix) ? frame_diff_kernel<FILM_PIX_I010> : frame_diff_kernel<FILM_PIX_I420>;   // (planar: every subsampling)
   static_assert(FILM_DIFF_THREADS == 256, "launch_units starts workgroups of 256");
   return launch_units(kernel, grid * FILM_DIFF_THREADS, s, p);   // `grid` workgroups
+}
+
+// ---- the segment copy (a grouped stream's restores and saves; film_kernels.h, SegmentTable) ---------------------------------------------
+// (Like the two launchers above, this one stands beside its kernel; launch_units: "host" below.)
+namespace {
+// lane = one aligned 16-byte vector of the destination per step.  The segment of unit u is the one with unit0[k] <= u < unit0[k + 1]; a
+// lane's units grow from step to step, so it walks k forwards from where it stood (empty segments, which own no unit, are passed on the
+// way).  The words are moved as uint32: no float is ever interpreted.
+__global__ __launch_bounds__(FILM_SEG_THREADS) void segment_copy_kernel(SegmentTable t, const uint32_t* src, uint32_t* dst) {
+  const int64_t total = t.unit0[t.n];
+  const int64_t step = (int64_t)gridDim.x * FILM_SEG_THREADS;
+  int k = 0;
+  for (int64_t u = (int64_t)blockIdx.x * FILM_SEG_THREADS + threadIdx.x; u < total; u += step) {
+    while (u >= t.unit0[k + 1]) ++k;   // (u < total = unit0[n]: k stays below n)
+    const SegmentCopy g = t.seg[k];
+    const uint32_t* sp = src + g.src;
+    uint32_t* dp = dst + g.dst;
+    const int lead = (int)((reinterpret_cast<uintptr_t>(dp) >> 2) & 3);   // floats of the segment's first vector in front of it
+    const int64_t j = (u - t.unit0[k]) * 4 - lead;                         // the vector's first float, relative to the segment
+    if (j >= 0 && j + 4 <= g.count) {
+      uint4 v;
+      if ((reinterpret_cast<uintptr_t>(sp + j) & 15) == 0) v = *reinterpret_cast<const uint4*>(sp + j);
+      else v = make_uint4(sp[j], sp[j + 1], sp[j + 2], sp[j + 3]);
+      *reinterpret_cast<uint4*>(dp + j) = v;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (j + e >= 0 && j + e < g.count) dp[j + e] = sp[j + e];
+    }
+  }
+}
+}  // namespace
+
+hipError_t film_launch_segment_copy(const SegmentCopy* segs, int n, const float* src, float* dst, hipStream_t s) {
+  if (n < 0 || n > FILM_SEG_MAX || (n > 0 && (!segs || !src || !dst))) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3) return hipErrorInvalidValue;
+  SegmentTable t{};
+  t.n = n;
+  for (int k = 0; k < n; ++k) {
+    const SegmentCopy& g = segs[k];
+    if (g.src < 0 || g.dst < 0 || g.count < 0) return hipErrorInvalidValue;
+    t.seg[k] = g;
+    const int64_t lead = (int64_t)((reinterpret_cast<uintptr_t>(dst + g.dst) >> 2) & 3);
+    t.unit0[k + 1] = t.unit0[k] + (g.count ? (lead + g.count + 3) / 4 : 0);
+  }
+  const int64_t total = t.unit0[n];
+  if (total == 0) return hipSuccess;
+  int dev = 0, cus = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e != hipSuccess) return e;
+  const int64_t grid = std::min<int64_t>((int64_t)std::max(cus, 1) * FILM_SEG_WG_PER_CU, (total + FILM_SEG_THREADS - 1) / FILM_SEG_THREADS);
+  static_assert(FILM_SEG_THREADS == 256, "launch_units starts workgroups of 256");
+  return launch_units(segment_copy_kernel, grid * FILM_SEG_THREADS, s, t, reinterpret_cast<const uint32_t*>(src), reinterpret_cast<uint32_t*>(dst));   // `grid` workgroups
 }
 
 namespace {

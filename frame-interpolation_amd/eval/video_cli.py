@@ -134,6 +134,10 @@ def retime_video(it, reader: y4m.Y4MReader, out, rate_out=None, dedup=None, matr
     with it.open_stream(reader.height, reader.width, pix=stream_pix(reader), matrix=matrix, full_range=full,
                         **({'dedup': tuple(dedup)} if dedup is not None else {}), **({'scene_cut': int(scene_cut)} if scene_cut else {}),
                         **({'times': times} if times != 1 else {})) as st:
+        lay = st.layout() if hasattr(st, 'layout') else {'groups': 1}   # (a caller's own stream object - the stand-in of the CPU tests - may have none)
+        if lay['groups'] > 1:   # a frame of more tiles than one invocation takes (include/film_hip.h, "Tile groups")
+            print(f'{lay["tiles"]} tiles in {lay["groups"]} groups of {lay["group_tiles"]}: workspace {lay["workspace_bytes"] / 2 ** 30:.2f} GiB + '
+                  f'carry {lay["carry_bytes"] / 2 ** 30:.2f} GiB', file=sys.stderr)
         selected = tuple(range(1, top))
         k, held, seen = 0, None, 0
         for i, frame in enumerate(reader):

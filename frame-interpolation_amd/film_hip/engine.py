@@ -80,7 +80,7 @@ EXPORTED_SYMBOLS = (
     'film_stream_open', 'film_stream_push', 'film_stream_reset', 'film_stream_close', 'film_stream_plan_json',
     'film_to_yuv420', 'film_to_yuv', 'film_debug_yuv_cut', 'film_frame_histogram', 'film_stream_cut_info',
     'film_stream_pair_plan_json', 'film_stream_schedule_json', 'film_stream_select', 'film_stream_select_schedule_json',
-    'film_frame_diff', 'film_stream_dup_info')
+    'film_frame_diff', 'film_stream_dup_info', 'film_stream_layout_json', 'film_stream_group_schedule_json', 'film_debug_segment_copy')
 
 _lib = None
 
@@ -162,6 +162,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.film_stream_schedule_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
     lib.film_stream_select.argtypes = [vp, ctypes.c_uint64]
     lib.film_stream_select_schedule_json.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_int64, i64p]
+    lib.film_stream_layout_json.argtypes = [vp, ctypes.c_char_p, ctypes.c_int64, i64p]
+    lib.film_stream_group_schedule_json.argtypes = [vp] + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, i64p]
+    lib.film_debug_segment_copy.argtypes = [i64p, ctypes.c_int, vp, vp, vp]
     lib.film_stream_cut_info.argtypes = [vp, i64p, i64p, ctypes.POINTER(ctypes.c_int)]
     lib.film_frame_diff.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
     lib.film_stream_dup_info.argtypes = [vp, i64p, ctypes.POINTER(ctypes.c_int)]
@@ -225,6 +228,17 @@ def frame_diff_device(ptr_a: int, ptr_b: int, h: int, w: int, out_ptr: int, pix:
                                         ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None)
     if rc != 0:
         raise FilmError(rc, 'film_frame_diff failed')
+
+
+def segment_copy_device(segs, src_ptr: int, dst_ptr: int, stream: Optional[int] = None) -> None:
+    """film_debug_segment_copy: ONE launch of the kernel a grouped stream moves its carry with - segs, up to 32 rows of (source float offset,
+    destination float offset, count): dst[d : d + count] = src[s : s + count] on two float32 device buffers, bit for bit, asynchronous on
+    `stream` of the current device.  Needs no engine."""
+    table = np.ascontiguousarray(np.asarray(segs, np.int64).reshape(-1, 3))
+    rc = load_library().film_debug_segment_copy(table.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), int(table.shape[0]), ctypes.c_void_p(src_ptr),
+                                                ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream) if stream else None)
+    if rc != 0:
+        raise FilmError(rc, 'film_debug_segment_copy failed')
 
 
 def dedup_options(dedup) -> Tuple[int, int, int]:
@@ -326,6 +340,12 @@ class FilmStream:
     def reset(self) -> None:
         """Forgets the carried frame (scene cut, seek): the next push produces nothing.  The selection stays."""
         self._eng._check(self._eng._lib.film_stream_reset(self._eng._h))
+
+    def layout(self) -> dict:
+        """film_stream_layout_json: how the open stream runs its frame - 'tiles', 'groups' (1: the whole frame in one invocation), 'group_tiles',
+        'slots', 'workspace_bytes', 'carry_bytes' and, for a stream of several tile groups, the carry buffers and the segments of every
+        (group, slot) state (include/film_hip.h, "Tile groups")."""
+        return self._eng._json_call(self._eng._lib.film_stream_layout_json)
 
     def cut_info(self) -> Tuple[int, int, int]:
         """film_stream_cut_info: (distance, samples, cut) of the last push - the histogram distance D to the frame before (-1: no
@@ -726,6 +746,13 @@ class FilmEngine:
         """film_stream_pair_plan_json: the plan of one pair run (frame in slot `left`, frame in slot `right`, with or without the right
         frame's extraction) of a stream of `tiles` h x w tiles opened with times (times + 1 frame slots)."""
         return self._json_call(self._lib.film_stream_pair_plan_json, int(tiles), int(h), int(w), int(times), int(left), int(right), int(bool(extract)))
+
+    def stream_group_schedule(self, tiles: int, h: int, w: int, times: int, slot: int, group_tiles: int, select=None) -> dict:
+        """film_stream_group_schedule_json: the runs of one primed push (select as for stream_schedule; an empty selection: a first push) of
+        a stream whose frame of `tiles` h x w tiles runs in groups of group_tiles - per step and group the restores from the carry, where the
+        extracted frame comes from, the run, the save and the joined tile range (include/film_hip.h, "Tile groups")."""
+        return self._json_call(self._lib.film_stream_group_schedule_json, int(tiles), int(h), int(w), int(times), int(slot),
+                               selection_mask(times, select), int(group_tiles))
 
     def stream_schedule(self, times: int, slot: int, select=None) -> dict:
         """film_stream_schedule_json: the pair runs of one primed push whose input lands in slot 0 / 1, in execution order.  select (an

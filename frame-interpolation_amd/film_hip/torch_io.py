@@ -128,6 +128,10 @@ class DeviceStream:
         carried frame returned None and changed nothing."""
         return self._stream.dup_info()
 
+    def layout(self) -> dict:
+        """FilmStream.layout: tiles, tile groups, tiles per group, workspace and carry bytes of the open stream."""
+        return self._stream.layout()
+
     def close(self) -> None:
         self._stream.close()
 

@@ -157,10 +157,15 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *   film_stream_open   H x W frames, align / block_h / block_w as for film_interpolate (same padding, tiling, "block_overlap_*",
  *                      refusals).  pix: a pixel type below (a layout, for the 4:2:0 layouts plus colour flags).  ONE open stream per handle (a second open: FILM_ERR_STATE);
  *                      several streams = several handles, as for threads.  Builds (and autotunes) the plan, so the pushes are steady.
- *                      The whole frame must fit ONE model invocation: more tiles than the limits of film_interpolate allow (today a
- *                      4K frame cut 4 x 4 would run as two chunks of 8) is FILM_ERR_INVALID with the limit in the message - use a finer
- *                      block shape - and a workspace that cannot be allocated is FILM_ERR_NOMEM: a stream neither chunks a frame
- *                      nor halves on out-of-memory.  Plan-only handle: FILM_ERR_NO_DEVICE; before film_finalize: FILM_ERR_STATE.
+ *                      A frame whose tiles fit ONE model invocation under the limits of film_interpolate runs in one ("one group": nothing
+ *                      below applies, and a push makes the device calls it always made).  A frame of more tiles than an invocation takes
+ *                      ("max_batch", the 4 GiB-per-buffer rule) or one whose workspace of "stream_times" + 1 slots does not fit - a 4K frame
+ *                      cut 4 x 4 with "stream_times" >= 2 on a 288 GB device - runs in TILE GROUPS ("Tile groups"
+ *                      below): n = the chunk film_interpolate would choose, halved while the workspace of n tiles does not fit; n and the
+ *                      number of groups are fixed for the stream's life (a later "max_batch" does not touch an open stream).  FILM_ERR_NOMEM:
+ *                      a single tile's workspace does not fit, or the groups' carry buffer cannot be allocated (the message names the
+ *                      workspace bytes, the carry bytes, n and the groups); FILM_ERR_INVALID: a single tile too large for a 32-bit
+ *                      addressed buffer.  Plan-only handle: FILM_ERR_NO_DEVICE; before film_finalize: FILM_ERR_STATE.
  *   film_stream_push   frame [H,W,3] in, mid [H,W,3] out, both of the stream's pixel type (a 4:2:0 stream: H * W * 3 / 2 samples each - bytes, or 16-bit words for the 10-bit layouts).  The first push after open / reset sets
  *                      *produced = 0 and only cuts the frame into its tiles and runs the image pyramid and the feature extractor
  *                      (`mid` is not touched and may be NULL); every later push sets *produced = 1 and writes `mid`, bit-identical
@@ -238,7 +243,35 @@ int film_interpolate_sequence(film_t* h, const float* frames, int F, int H, int 
  *                      extraction-only step, whose "index" and "depth" are those of the frame it extracts, with "feed" -1 and "deliver"
  *                      0).  mask = 0: the one step is the extraction of the pushed frame ("index" 2^T, "depth" 0).  With the full mask
  *                      the steps are those of film_stream_schedule_json.  Refuses what that query refuses, and a bad mask as
- *                      film_stream_select does.  Works on plan-only handles. */
+ *                      film_stream_select does.  Works on plan-only handles.
+ * Tile groups.  A stream whose T tiles do not fit one invocation runs every step of a push as G = ceil(T / n) runs of ONE stream plan of n
+ * tiles, group after group; the last group holds the r <= n tiles that are left and runs the same plan (its surplus images compute on what
+ * the group before left there; nobody reads them).  A device buffer of the stream's own, the CARRY, holds for every (group, frame slot) what a
+ * pair run reads of an extracted frame: the per-image buffers of the plan that the ops of a pair run read and none of them writes (the
+ * image and feature pyramids), one contiguous segment per buffer.  In front of a group's run the slots it reads are copied from the carry
+ * into the plan, behind a run that extracted a frame that slot is copied out - one kernel launch each way (film_debug_segment_copy's).  Every
+ * run is an ordinary run of an ordinary orientation, so every frame has the bits of the one-group stream and of film_interpolate.  The
+ * order is outer = the steps of film_stream_select_schedule_json, inner = the groups: a frame that is fed back is the JOINED frame (cross-
+ * faded with "block_overlap_*"), which exists when all groups of its step have run; it is then cut, group by group, into the carry.  The
+ * carry is the truth about the carried frame: an evicted and rebuilt plan costs no re-extraction; a changed tile geometry re-extracts
+ * every group from the stream's copy of the frame.  Options, selection, reset, scene cuts and duplicates mean what they mean for one group.
+ * Memory: the workspace of n tiles plus (T + 1 slots) x (the pyramids of all tiles) of carry.
+ *   film_stream_layout_json  the open stream: {"tiles", "groups", "group_tiles", "slots", "tile_h", "tile_w", "workspace_bytes",
+ *                      "workspace_resident" (1: the plan of the groups holds its workspace on the device now, 0: it was evicted or dropped and the next
+ *                      push allocates it again), "carry_bytes", "carry":[buffer names], "states":[{"group", "slot", "tile0", "ntiles", "segments":[{"buf", "plan_off",
+ *                      "carry_off", "floats"}, ...]}, ...]} - offsets in floats into the plan's workspace and into the carry.  One group:
+ *                      "groups" 1, "carry_bytes" 0, no carry buffers and no states.  FILM_ERR_STATE: no open stream.
+ *   film_stream_group_schedule_json  the runs of the primed push of film_stream_select_schedule_json(times, slot, mask) for a frame of `tiles`
+ *                      (padded) H x W tiles in groups of `group_tiles`: {"times", "slot", "slots", "mask", "produced", "tiles",
+ *                      "group_tiles" (at most `tiles`), "groups", "carry":[buffer names], "steps":[...]}, one entry per step and group, in
+ *                      execution order: the step's keys plus "step", "group", "tile0", "ntiles", "restore" (the slots copied whole from the
+ *                      carry in front of the run), "cut" (where the extracted frame comes from: "keep" - cut from the stream's copy of the
+ *                      pushed frame; "carry" - the img0 tiles its parent's feed-cut left in the carry are restored; "plan" - one group: they
+ *                      are in the plan; "none": nothing is extracted), "save" (the slot copied whole into the carry behind the run, -1:
+ *                      none), "join" ([tile0, ntiles] of a pair run, else []), "last" (1: the step's last group - its frame is delivered)
+ *                      and "feed_to" ("carry" / "plan": behind the last group the frame is cut into slot "feed" there; "none").  One group:
+ *                      the steps of film_stream_select_schedule_json with no restore and no save.  A first push is mask = 0.  Refuses what
+ *                      that query refuses and tiles or group_tiles < 1.  Works on plan-only handles. */
 #define FILM_PIX_F32 0   /* frames and results float32 [H,W,3], as everywhere else */
 #define FILM_PIX_U8  1   /* frames and results uint8 [H,W,3]: x = u8 / 255.0f (IEEE, = read_image), result = film_to_uint8's rule */
 /* 8-bit Y'CbCr 4:2:0 frames: the conversion in is fused into the tile cut, the conversion out into the quantisation, so such a frame
@@ -378,6 +411,9 @@ int film_stream_pair_plan_json(film_t* h, int tiles, int H, int W, int times, in
 int film_stream_schedule_json(film_t* h, int times, int slot, char* buf, int64_t capacity, int64_t* needed);
 int film_stream_select(film_t* h, uint64_t mask);
 int film_stream_select_schedule_json(film_t* h, int times, int slot, uint64_t mask, char* buf, int64_t capacity, int64_t* needed);
+int film_stream_layout_json(film_t* h, char* buf, int64_t capacity, int64_t* needed);
+int film_stream_group_schedule_json(film_t* h, int tiles, int H, int W, int times, int slot, uint64_t mask, int group_tiles, char* buf,
+                                    int64_t capacity, int64_t* needed);
 
 /* Execution options.  Keys:
  *   "autotune" 0/1 time every distinct conv shape of a new plan with each fitting tile shape and keep
@@ -574,6 +610,14 @@ int film_debug_run_op(film_t* h, int B, int H, int W, int tiles, int index, int 
  * [0, B * block_h * block_w).  Then FILM_ERR_NO_DEVICE on a plan-only handle.  Not on any forward path. */
 int film_debug_tile_map(film_t* h, int mode, int pix, void* frames_dev, float* tiles_dev, int B, int H, int W, int align, int block_h,
                         int block_w, int tile0, int ntiles, void* stream);
+/* film_debug_segment_copy: ONE launch of the kernel a grouped stream restores and saves its carry with ("Tile groups"), on buffers the caller
+ * owns (tests/test_segment_copy_gpu.py): segs = n x {source float offset, destination float offset, count} (int64, HOST array), n = 0 .. 32;
+ * dst_dev[d .. d + count) = src_dev[s .. s + count) for each, bit for bit, and nothing else is written.  Offsets and counts are arbitrary (a
+ * segment may start at any float and have any length, 0 included); the segments must not overlap each other and lie inside the caller's
+ * allocations.  Asynchronous on `stream` (NULL: the default stream).  Takes no handle and needs no weights.  FILM_ERR_INVALID: n outside
+ * 0 .. 32, a NULL pointer with n > 0, a negative offset or count, a pointer that is not 4-byte aligned.  Not on any forward path of a
+ * one-group stream. */
+int film_debug_segment_copy(const int64_t* segs, int n, const float* src_dev, float* dst_dev, void* stream);
 /* film_debug_yuv_cut: ONE cut of a batch of B Y'CbCr frames (frame b at sample b * S of frames_dev, S = 3 H W / 2, 2 H W or 3 H W samples of one or two bytes,
  * a 4-byte aligned DEVICE pointer into an allocation of whole 32-bit words) into float32 RGB tiles: film_debug_tile_map mode 0 with pix =
  * a Y'CbCr layout (FILM_PIX_I420 / NV12 / I422 / I444 / I010 / P010 / I210 / I410) plus colour flags - same geometry, same tile buffer, same refusals (and those of `pix` above), reached through the

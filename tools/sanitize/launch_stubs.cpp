@@ -20,6 +20,7 @@ STUB(hipError_t film_launch_to_uint8(const float*, uint8_t*, int64_t, hipStream_
 STUB(hipError_t film_launch_rgb_to_yuv(const float*, void*, int, int, int, hipStream_t))
 STUB(hipError_t film_launch_frame_histogram(const void*, int, int, int, uint32_t*, hipStream_t))
 STUB(hipError_t film_launch_frame_diff(const void*, const void*, int, int, int, int, uint64_t*, hipStream_t))
+STUB(hipError_t film_launch_segment_copy(const SegmentCopy*, int, const float*, float*, hipStream_t))
 STUB(hipError_t film_launch_fill_random(float*, int64_t, uint32_t, hipStream_t))
 // metrics_kernels.hip (film_image_metrics refuses a plan-only handle before it reaches either)
 STUB(void film_metrics_layout(MetricsParams&))

@@ -35,6 +35,14 @@ device-resident and host pushes, (a) this tree's push with dup_hi = -1 beside - 
 same process: the price of the copy, the kernel, the 96-byte download and the wait; (c) `*_dup` - a push that IS a duplicate (the carried frame
 again); (d) `<layout> <size> <data>` - frame_diff_kernel alone (film_frame_diff, hip events around 50 calls, microseconds per call) at 1080p and
 4K on two random frames and on a frame against itself, beside the bytes of both frames over the measured HBM copy rate (6.29 TB/s).
+--groups is a run of its own about tile groups (include/film_hip.h, "Tile groups": a frame of more tiles than one invocation takes), this tree
+alone, one process: (b) at 1080p 2x2, the device-resident `f32` push of a stream opened with max_batch = 2 (two groups of two tiles) against
+max_batch = 0 (one group), T = 1 and T = 3 - what the carry costs per pair run; (c) at the point `4K 4x4` (16 tiles of 576 x 960, two groups
+of 8), for `i010` and `f32`, device-resident and host pushes, the ms per push of T = 1 and of T = 3 taking the selections {3, 6} and {2, 5} in
+turn (24 -> 60), beside per-pair film_interpolate on the same frames, with the layout's workspace and carry bytes; the first mid-frame of
+every stream is compared bit for bit with that call; (d) the segment-copy kernel alone over the restore table of one 4K group (two slots),
+hip events around 50 calls, beside hipMemcpyAsync device-to-device over the same segments, and both beside the measured HBM copy rate (6.29 TB/s).
+--groups-parts b,c,d restricts the run.
 Every measurement: untimed warm-up calls (plan build, autotune, first launches), then --reps timed windows of `n` calls, each
 ended by a device synchronise; the window's ms per call is one sample.  Each tree keeps its autotune choices in a file of its own
 under --scratch, so that the rounds of a tree run the same tiles.  The report gives mean and range over all samples of a
@@ -56,6 +64,9 @@ POINTS = [
     ('448x256', 256, 448, 64, None, 200, 32),
     ('256x256', 256, 256, 64, None, 200, 32),
 ]
+# the point of --groups: more tiles than one invocation takes with "stream_times" >= 2 (the default runs take it only when --points names it)
+GROUPS_POINT = ('4K 4x4', 2160, 3840, 64, (4, 4), 4, 4)
+POINTS.append(GROUPS_POINT)
 
 
 def _frames(f, h, w, seed=0):
@@ -101,7 +112,7 @@ def worker(root, reps, quick, rows=None, points=None, scene_cut=False):
         return [round(s, 4) for s in samples]
 
     for pi, (name, h, w, align, block, n, fseq) in enumerate(POINTS):
-        if (quick and pi == 0) or (points is not None and name not in points):
+        if (quick and pi == 0) or (points is not None and name not in points) or (points is None and name == GROUPS_POINT[0]):
             continue
         res = {}
         it = DeviceInterpolator(eng, align=align, block_shape=list(block) if block else None)
@@ -626,14 +637,254 @@ def dedup_main(args):
             f.write('\n'.join(lines) + '\n')
 
 
-def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False, times=None, select=None, dedup=False):
+def groups_worker(root, reps, parts):
+    """--groups: see the module text; prints one JSON line."""
+    for p in (root, os.path.join(root, 'frame-interpolation_amd')):
+        sys.path.insert(0, p)
+    import ctypes
+    import numpy as np
+    import torch
+    from film_hip import weights as W
+    from film_hip import engine as engine_mod
+    from film_hip.engine import FilmEngine
+    from film_hip.options import PUBLISHED
+    from film_hip.torch_io import DeviceInterpolator
+    eng = FilmEngine(PUBLISHED, device=0)
+    eng.set_weights(W.make_synthetic_weights(PUBLISHED, seed=0))
+    out = {'version': FilmEngine.version(), 'device': torch.cuda.get_device_name(0)}
+    state = {'i': 0}
+
+    def nxt(m):
+        state['i'] = (state['i'] + 1) % m
+        return state['i']
+
+    def timed(call, n, warm=2):
+        for _ in range(warm):
+            call()
+        torch.cuda.synchronize()
+        samples = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                call()
+            torch.cuda.synchronize()
+            samples.append(round((time.perf_counter() - t0) * 1e3 / n, 4))
+        return samples
+
+    if 'b' in parts:     # the carry's cost alone: two groups against one, one process
+        name, h, w, align, block, n, _ = POINTS[0]
+        it = DeviceInterpolator(eng, align=align, block_shape=list(block))
+        x = [torch.from_numpy(f).cuda() for f in _frames(4, h, w)]
+        res = {}
+        for t in (1, 3):
+            first = {}
+            for mb in (0, 2):
+                eng.set_option('max_batch', mb)
+                try:
+                    with it.stream(h, w, 'f32', times=t) as st:
+                        eng.set_option('max_batch', 0)
+                        lay = st.layout()
+                        st.push(x[0])
+                        first[mb] = st.push(x[1]).clone()
+                        res[f'push_f32_t{t}_mb{mb}'] = timed(lambda: st.push(x[nxt(4)]), max(4, n // ((1 << t) - 1) // 2))
+                        res[f'layout_t{t}_mb{mb}'] = {k: lay[k] for k in ('tiles', 'groups', 'group_tiles', 'workspace_bytes', 'carry_bytes')}
+                finally:
+                    eng.set_option('max_batch', 0)
+            res[f'identical_t{t}'] = bool(torch.equal(first[0], first[2]))
+        out['b'] = res
+        del x, it, first
+        torch.cuda.empty_cache()
+
+    lay4k = None
+    if 'c' in parts or 'd' in parts:
+        name, h, w, align, block, n, _ = GROUPS_POINT
+        it = DeviceInterpolator(eng, align=align, block_shape=list(block))
+        fr = _frames(4, h, w)
+        x = [torch.from_numpy(f).cuda() for f in fr]
+        res = {}
+        if 'c' in parts:
+            res['pair'] = timed(lambda: it.batch(x[nxt(3)][None], x[state['i'] + 1][None]), n, warm=1)
+            res['host_pair'] = timed(lambda: eng.interpolate_frames(fr[:1], fr[1:2], align=align, block_shape=block), n, warm=1)
+            ref = it.batch(x[0][None], x[1][None])[0]
+            y10 = [torch.empty(engine_mod.frame_shape('i010', h, w), dtype=torch.int16, device='cuda') for _ in x]
+            for src, dst in zip(x, y10):
+                eng.to_yuv_device(src.data_ptr(), dst.data_ptr(), h, w, 'i010')
+            torch.cuda.synchronize()
+            h10 = [t.cpu().numpy().view(np.uint16) for t in y10]
+            # what an i010 stream computes for frames 0 and 1: film_to_yuv of film_interpolate on the frames the cut dequantises
+            deq = [torch.empty_like(x[0]) for _ in range(2)]
+            for src, dst in zip(y10, deq):
+                eng.debug_yuv_cut(src.data_ptr(), dst.data_ptr(), 1, h, w, None, None, 0, 1, pix='i010')
+            ref10 = torch.empty_like(y10[0])
+            eng.to_yuv_device(it.batch(deq[0][None], deq[1][None])[0].data_ptr(), ref10.data_ptr(), h, w, 'i010')
+            torch.cuda.synchronize()
+            del deq
+            same = {}
+            eng.set_option('max_batch', 8)       # T = 1 in two groups of 8, where the whole frame would fit one invocation
+            try:
+                with it.stream(h, w, 'f32') as st:
+                    eng.set_option('max_batch', 0)
+                    lay = st.layout()
+                    res['layout_t1_mb8'] = {k: lay[k] for k in ('tiles', 'groups', 'group_tiles', 'workspace_bytes', 'carry_bytes')}
+                    st.push(x[0])
+                    same['f32_t1_mb8'] = bool(torch.equal(st.push(x[1]), ref))
+                    res['push_f32_t1_mb8'] = timed(lambda: st.push(x[nxt(4)]), n, warm=2)
+            finally:
+                eng.set_option('max_batch', 0)
+            for pix, dev, host in (('f32', x, fr), ('i010', y10, h10)):
+                for t, sels in ((1, [None]), (3, [(3, 6), (2, 5)])):
+                    turn = {'k': 0}
+
+                    def select(st):
+                        if t > 1:
+                            st.select(sels[turn['k'] % len(sels)])
+                            turn['k'] += 1
+
+                    def dev_push(st):
+                        select(st)
+                        return st.push(dev[nxt(4)])
+
+                    def host_push(st):
+                        select(st)
+                        return st.push(host[nxt(4)])
+
+                    with it.stream(h, w, pix, times=t) as st:
+                        lay4k = st.layout()
+                        res[f'layout_t{t}'] = {k: lay4k[k] for k in ('tiles', 'groups', 'group_tiles', 'workspace_bytes', 'carry_bytes')}
+                        st.push(dev[0])
+                        if t > 1:
+                            st.select([4])                      # position 4 of 7 is the mid-frame of the pair
+                        mid = st.push(dev[1])
+                        want = ref if pix == 'f32' else ref10
+                        same[f'{pix}_t{t}'] = bool(torch.equal(mid.reshape(want.shape), want))
+                        res[f'push_{pix}_t{t}'] = timed(lambda: dev_push(st), n, warm=2)
+                    with eng.open_stream(h, w, align=align, block_shape=block, pix=pix, times=t) as st:
+                        st.push(host[0])
+                        res[f'host_push_{pix}_t{t}'] = timed(lambda: host_push(st), n, warm=2)
+            res['identical'] = all(same.values())
+            res['identical_each'] = same
+            del y10, h10
+        if lay4k is None:
+            with it.stream(h, w, 'f32') as st:
+                lay4k = st.layout()
+        out['c'] = res
+        del x, it
+        torch.cuda.empty_cache()
+
+    if 'd' in parts and lay4k and lay4k['groups'] > 1:
+        # the restore table of group 0: both slots, carry -> plan, at the offsets' own alignments, in buffers of their own
+        segs, s_end, d_end = [], 0, 0
+        for stt in lay4k['states']:
+            if stt['group'] != 0 or stt['slot'] > 1:
+                continue
+            for g in stt['segments']:
+                s_off = (s_end + 63) // 64 * 64 + g['carry_off'] % 64
+                d_off = (d_end + 63) // 64 * 64 + g['plan_off'] % 64
+                segs.append((s_off, d_off, g['floats']))
+                s_end, d_end = s_off + g['floats'], d_off + g['floats']
+        src = torch.rand(s_end + 64, device='cuda')
+        dst = torch.zeros(d_end + 64, device='cuda')
+        stream = torch.cuda.current_stream().cuda_stream
+        hip = ctypes.CDLL(engine_mod.hip_runtime_info()[0])
+        hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+
+        def kernel():
+            engine_mod.segment_copy_device(segs, src.data_ptr(), dst.data_ptr(), stream)
+
+        def memcpy():
+            for so, do, c in segs:
+                assert hip.hipMemcpyAsync(dst.data_ptr() + 4 * do, src.data_ptr() + 4 * so, 4 * c, 3, stream) == 0
+
+        def events(call, calls=50):
+            call()
+            torch.cuda.synchronize()
+            samples = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    call()
+                e1.record()
+                torch.cuda.synchronize()
+                samples.append(round(e0.elapsed_time(e1) * 1e3 / calls, 2))
+            return samples
+
+        kernel()
+        torch.cuda.synchronize()
+        ok = all(bool(torch.equal(dst[do:do + c], src[so:so + c])) for so, do, c in segs)
+        out['d'] = {'segments': len(segs), 'bytes': 4 * sum(c for _, _, c in segs), 'copied': ok, 'kernel_us': events(kernel), 'memcpy_us': events(memcpy)}
+    eng.save_tune_cache()
+    eng.close()
+    print('STREAM_BENCH ' + json.dumps(out), flush=True)
+
+
+def groups_main(args):
+    os.makedirs(args.scratch, exist_ok=True)
+    runs = [_run_worker(HERE, args.reps, False, os.path.join(args.scratch, 'stream_bench_tune_this.txt'), groups=args.groups_parts) for _ in range(args.rounds)]
+    r0 = runs[0]
+    lines = [f'# tools/stream_bench.py --groups  this = {r0["version"]}  {r0["device"]}  rounds={args.rounds} reps={args.reps}',
+             '# ms per PUSH, device-resident unless "host": mean [min .. max] over rounds x reps windows']
+    gib = lambda b: f'{b / 2 ** 30:.2f} GiB'      # noqa: E731
+    if 'b' in r0:
+        lines.append(f'{POINTS[0][0]}: the carry alone - max_batch 2 (two groups of two tiles) against max_batch 0 (one group), one process')
+        for t in (1, 3):
+            for mb in (0, 2):
+                lay = r0['b'][f'layout_t{t}_mb{mb}']
+                lines.append(f'  {f"push_f32_t{t}_mb{mb}":<22} {_stat([s for r in runs for s in r["b"][f"push_f32_t{t}_mb{mb}"]])}   {lay["groups"]} x {lay["group_tiles"]} tiles, '
+                             f'workspace {gib(lay["workspace_bytes"])}, carry {gib(lay["carry_bytes"])}')
+            d = [statistics.mean(r['b'][f'push_f32_t{t}_mb2']) - statistics.mean(r['b'][f'push_f32_t{t}_mb0']) for r in runs]
+            lines.append(f'  {f"t{t}: mb2 - mb0":<22} per round: {" ".join(f"{v:+.3f}" for v in d)}   mean {statistics.mean(d):+.3f} ms per push, '
+                         f'{statistics.mean(d) / ((1 << t) - 1):+.3f} ms per pair run ({(1 << t) - 1} per push)')
+            lines.append(f'  t{t}: the grouped push == the one-group push, bit for bit: {all(r["b"][f"identical_t{t}"] for r in runs)}')
+    if 'c' in r0 and 'pair' in r0['c']:
+        c0 = r0['c']
+        lines.append(f'{GROUPS_POINT[0]}: T = 1 full pushes; T = 3 pushes taking the selections (3, 6) and (2, 5) in turn (24 -> 60: 2.5 frames per input interval)')
+        for t in (1, 3):
+            lay = c0[f'layout_t{t}']
+            lines.append(f'  layout T = {t}: {lay["tiles"]} tiles in {lay["groups"]} groups of {lay["group_tiles"]}, workspace {lay["workspace_bytes"]} bytes '
+                         f'({gib(lay["workspace_bytes"])}), carry {lay["carry_bytes"]} bytes ({gib(lay["carry_bytes"])})')
+        lay = c0['layout_t1_mb8']
+        lines.append(f'  layout T = 1, max_batch 8: {lay["tiles"]} tiles in {lay["groups"]} groups of {lay["group_tiles"]}, workspace {lay["workspace_bytes"]} bytes '
+                     f'({gib(lay["workspace_bytes"])}), carry {lay["carry_bytes"]} bytes ({gib(lay["carry_bytes"])})')
+        for key in ('pair', 'host_pair', 'push_f32_t1_mb8') + tuple(f'{pre}push_{pix}_t{t}' for t in (1, 3) for pix in ('f32', 'i010') for pre in ('', 'host_')):
+            lines.append(f'  {key:<22} {_stat([s for r in runs for s in r["c"][key]])}' +
+                         ('   (per-pair film_interpolate, one frame per call)' if key.endswith('pair') else ''))
+        for pre, pair in (('', 'pair'), ('host_', 'host_pair')):
+            pm = statistics.mean(s for r in runs for s in r['c'][pair])
+            for pix in ('f32', 'i010'):
+                p1 = statistics.mean(s for r in runs for s in r['c'][f'{pre}push_{pix}_t1'])
+                p3 = statistics.mean(s for r in runs for s in r['c'][f'{pre}push_{pix}_t3'])
+                lines.append(f'  {pre}push_{pix}: T = 1 {p1:.1f} ms per frame = {1e3 / p1:.2f} frames/s against {pm:.1f} ms = {1e3 / pm:.2f} frames/s of the pair call; '
+                             f'T = 3 selected {p3 / 2:.1f} ms per frame (2 per push) against {pm * 4 / 2:.1f} ms of 4 pair calls per 2 frames')
+        lines.append(f'  the first mid-frame of every stream == film_interpolate (i010: film_to_yuv of it on the dequantised frames), bit for bit: '
+                     f'{all(r["c"]["identical"] for r in runs)}  {json.dumps(c0["identical_each"])}')
+    if 'd' in r0:
+        d0 = r0['d']
+        lines.append(f'segment copy alone: the restore table of one {GROUPS_POINT[0]} group, {d0["segments"]} segments, {d0["bytes"]} bytes ({d0["bytes"] / 1e9:.2f} GB read and as much written); '
+                     f'{2 * d0["bytes"] / 6.29e12 * 1e6:.0f} us at the 6.29 TB/s copy rate (bytes read + bytes written); copied bit for bit: {all(r["d"]["copied"] for r in runs)}')
+        for key in ('kernel_us', 'memcpy_us'):
+            v = [s for r in runs for s in r['d'][key]]
+            lines.append(f'  {key:<22} {_stat(v)} us per call   {2 * d0["bytes"] / statistics.mean(v) / 1e6:.2f} TB/s read + written')
+    lines.append('# raw: ' + json.dumps(runs))
+    print('\n'.join(lines), flush=True)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    ok = all(r.get('b', {}).get(f'identical_t{t}', True) for r in runs for t in (1, 3)) and all(r.get('c', {}).get('identical', True) for r in runs) and \
+        all(r.get('d', {}).get('copied', True) for r in runs)
+    if not ok:
+        raise SystemExit('a grouped push differs from its reference')
+
+
+def _run_worker(root, reps, quick, tune_file, rows=None, points=None, scene_cut=False, times=None, select=None, dedup=False, groups=None):
     env = dict(os.environ, FILM_TUNE_CACHE=tune_file)
     cmd = [sys.executable, os.path.abspath(__file__), '--worker', root, '--reps', str(reps)] + (['--quick'] if quick else [])
     cmd += (['--rows', ','.join(rows)] if rows else []) + (['--points', ','.join(points)] if points else []) + (['--scene_cut'] if scene_cut else [])
     cmd += ['--dedup'] if dedup else []
+    cmd += ['--groups', '--groups-parts', groups] if groups else []
     cmd += ['--times', ','.join(str(t) for t in times)] if times else []
     cmd += ['--select', select] if select else []
-    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)   # (a hung worker ends the run: nothing is started behind it)
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1100 if groups else 900)   # (a hung worker ends the run: nothing is started behind it)
     for line in p.stdout.splitlines():
         if line.startswith('STREAM_BENCH '):
             return json.loads(line[len('STREAM_BENCH '):])
@@ -702,6 +953,8 @@ def main(argv=None):
                     help='with --times T (one value): the selected-push report instead - the selections (1-based positions, comma-separated; '
                          '"/" between selections) are taken in turn, push after push (FilmStream.select), beside the full push of this tree and of the baseline')
     ap.add_argument('--dedup', action='store_true', help='the report about option "dup_hi" and its block-SAD kernel alone instead (see above)')
+    ap.add_argument('--groups', action='store_true', help='the report about tile groups instead (see above): the carry alone, 4K 4x4 pushes, the copy kernel alone')
+    ap.add_argument('--groups-parts', default='b,c,d', help='with --groups: the parts to run, of b (1080p carry cost), c (4K pushes), d (copy kernel alone)')
     ap.add_argument('--worker', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     rows = args.rows.split(',') if args.rows else None
@@ -714,6 +967,8 @@ def main(argv=None):
         if args.worker:
             return select_worker(args.worker, args.reps, times[0], selections)
         return select_main(args, times[0], selections)
+    if args.groups:
+        return groups_worker(args.worker, args.reps, args.groups_parts.split(',')) if args.worker else groups_main(args)
     if args.dedup:
         return dedup_worker(args.worker, args.reps) if args.worker else dedup_main(args)
     if times and args.worker:
